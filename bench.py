@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py — YOLACT-550 frames/s on N MI355X (one process per GPU), plus the roofline of the
+"""bench.py — YOLACT-550 frames/s on N MI355X (one process per GPU); with --full, also the roofline of the
 dominant kernel and the CPU oracle timed on the host cores.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
@@ -11,6 +11,14 @@ yh_set_input_u8_device (device->device) + yh_evaluate (preprocess, 86 convs, FPN
 softmax/top-k/Fast-NMS/mask assembly), hipGraph-replayed. Frames shard across ranks (weak scaling,
 --batch frames per GPU per step); the only collective is the one-time RCCL broadcast of the weight
 blob from rank 0. PyTorch is plumbing here (device buffers, torch.distributed), not the product.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (frames/s, ms_per_step). Everything
+else - the per-launch profile and rooflines, latency and host-fed rates, the batch-1, configs[4] and tflite
+sub-records, the CPU baseline and the engine-vs-oracle figures - runs only with --full (the --no-* switches apply there).
+--dump-outputs DIR writes what the last timed step computed (rank 0's engine) as DIR/<name>.npy:
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/
 """
 import argparse
 import threading
@@ -621,6 +629,47 @@ def tflite_record(ya, invokes=120):
     return rec
 
 
+DUMP_SAMPLE = 1 << 21          # values kept of one large output: a seeded sample beyond that (the dump stays near 50 MB)
+DUMP_SEED = 0x44554D50
+
+
+def dump_sample(a, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """`a` whole if it holds at most k values, else the values at seeded flat positions: the same positions for the same
+    shape in every run, so that two builds' dumps compare element for element."""
+    import numpy as np
+    if a.size <= k:
+        return a
+    idx = np.unique(np.random.default_rng(seed).integers(0, a.size, k))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(eng, out_dir):
+    """What a caller of the timed path receives after its last step, as out_dir/<name>.npy (float32 / float64): the five
+    head outputs of yh_output_read_f32 (loc, conf, mask, proto, cells; sampled by dump_sample where large) and every
+    frame's detections of yh_read_detections, padded to max_dets (class and prior -1, score and box 0 past det_count).
+    The masks are kept whole as per-detection pixel counts and as a sample of the padded [frame][det][h][w] array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    eng.sync()
+    for i in range(eng.output_count()):
+        np.save(os.path.join(out_dir, eng.output_info(i)["name"] + ".npy"), dump_sample(eng.output(i)))
+    n, D = eng.n, eng.cfg.max_dets
+    count = np.zeros(n, np.float64)
+    cls, prior = np.full((n, D), -1.0), np.full((n, D), -1.0)
+    score, box, area = np.zeros((n, D), np.float32), np.zeros((n, D, 4), np.float32), np.zeros((n, D), np.float64)
+    masks = np.zeros((n, D, eng.hp, eng.wp), np.uint8)
+    for f in range(n):
+        dets, m = eng.detections(f, want_masks=True)
+        count[f] = len(dets)
+        for j, d in enumerate(dets):
+            cls[f, j], prior[f, j], score[f, j], box[f, j] = d["class_id"], d["prior"], d["score"], d["box"]
+        masks[f, :len(dets)] = m
+        area[f, :len(dets)] = m.sum(axis=(1, 2))
+    for name, a in (("det_count", count), ("det_class", cls), ("det_prior", prior), ("det_score", score), ("det_box", box),
+                    ("det_mask_area", area), ("det_masks", dump_sample(masks).astype(np.float32))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 VERBOSE = False
 
 
@@ -631,7 +680,9 @@ def progress(msg):
 
 
 def run_config(ya, torch, dist, rank, world, local_rank, batch, steps, warmup, seed, size, blob_dev_ptr, blob_nbytes, ring=4, backbone=50,
-               precision="f16", tune=None, fp8_per_tensor=False):
+               precision="f16", tune=None, fp8_per_tensor=False, full=True, dump_dir=None):
+    """Times `steps` steps after `warmup`; dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs).
+    full=False stops there - no per-launch profile, detections or aux records (prof and ndet come back None)."""
     eng = ya.Engine(input_size=size, backbone=backbone, max_batch=batch, use_graph=True, device=local_rank,
                     precision=ya.PRECISION_FP8 if precision == "fp8" else ya.PRECISION_F16, tune=tune, fp8_per_tensor=fp8_per_tensor)
     eng.load_weights_device(blob_dev_ptr, blob_nbytes)
@@ -663,13 +714,19 @@ def run_config(ya, torch, dist, rank, world, local_rank, batch, steps, warmup, s
     eng.sync(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dt = max_over_ranks(dist, dt, f"cuda:{local_rank}")
+    if dump_dir and rank == 0:
+        progress(f"batch {batch}: dump outputs")
+        dump_outputs(eng, dump_dir)
+    flops = eng.flops_per_frame()
     if dist is not None:
         dist.barrier()
+    if not full:
+        eng.close()
+        return dt, None, flops, None, {}
     progress(f"batch {batch}: timed steps done, per-launch profile")
     prof = eng.profile(with_tail=True, reps=3) if rank == 0 else None
     progress(f"batch {batch}: detections")
     ndet = sum(len(eng.detections(f, want_masks=False)[0]) for f in range(min(batch, 4))) if rank == 0 else 0
-    flops = eng.flops_per_frame()
     aux = {}
     if rank == 0:
         host = bufs[0].cpu().numpy()
@@ -738,10 +795,10 @@ def single_process_main(a, ya, torch, tune):
         step(k)
     g.sync()
     dt = time.perf_counter() - t0
-    ndet = sum(len(g.detections(f, want_masks=False)[0]) for f in range(min(4, a.gpus * a.batch)))
     e0 = g.members[0]
     e0.n = a.batch
-    prof = e0.profile(with_tail=True, reps=3)
+    if a.dump_outputs:   # member 0's share: the first batch frames of the group
+        dump_outputs(e0, a.dump_outputs)
     flops = e0.flops_per_frame()
     fps = a.gpus * a.batch * a.steps / dt
     line = {
@@ -753,10 +810,12 @@ def single_process_main(a, ya, torch, tune):
                                f"ONE process: yh_group over devices {devices}" + (" (members share device 0: a rehearsal, not a measurement)" if ndev < a.gpus else ""),
                    "batch_per_gpu": a.batch, "global_batch": a.batch * a.gpus, "input": [a.size, a.size, 3],
                    "weights": f"seeded synthetic (seed {a.seed}), BN folded", "weights_replication": g.weights_replication(),
-                   "detections_first_frames": ndet, "host": "single process, one worker thread per device (yh_group_evaluate_device)"},
+                   "host": "single process, one worker thread per device (yh_group_evaluate_device)"},
         "net_tflops": round(fps * flops / 1e12, 2), "gflop_per_frame": round(flops / 1e9, 2),
-        "roofline": roofline_of(prof, a.batch),
     }
+    if a.full:
+        line["config"]["detections_first_frames"] = sum(len(g.detections(f, want_masks=False)[0]) for f in range(min(4, a.gpus * a.batch)))
+        line["roofline"] = roofline_of(e0.profile(with_tail=True, reps=3), a.batch)
     g.close()
     print(json.dumps(line), flush=True)
 
@@ -772,6 +831,11 @@ def main():
     ap.add_argument("--precision", default="f16", choices=("f16", "fp8"),
                     help="fp8: E4M3 operands on the block-scaled fp8 MFMA for the K-heavy 3x3 layers (configs[4]: --backbone 101 --size 700 --precision fp8)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-launch profile and rooflines, latency, host-fed rates, the batch1 / configs4 / tflite "
+                         "sub-records and the CPU baseline (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs (rank 0: head outputs, detections) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for the cpu_baseline sample")
     ap.add_argument("--no-batch1", action="store_true")
@@ -794,6 +858,8 @@ def main():
                          "librccl file - the stand-in of tests/rccl_standin/, which lets two ranks share a device (real RCCL refuses that); "
                          "torch.distributed stays on gloo. Not a measurement")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global VERBOSE
     VERBOSE = a.verbose
 
@@ -838,9 +904,10 @@ def main():
     blob_ptr = src.weights_device_ptr()
 
     dt, prof, flops, ndet, aux = run_config(ya, torch, dist, rank, world, local_rank, a.batch, a.steps, a.warmup,
-                                              a.seed, a.size, blob_ptr, nbytes, backbone=a.backbone, precision=a.precision, tune=tune, fp8_per_tensor=a.fp8_per_tensor)
+                                              a.seed, a.size, blob_ptr, nbytes, backbone=a.backbone, precision=a.precision, tune=tune, fp8_per_tensor=a.fp8_per_tensor,
+                                              full=a.full, dump_dir=a.dump_outputs or None)
     extra = {}
-    if a.batch != 1 and not a.no_batch1:   # configs[1]: batch=1 latency case, same run
+    if a.full and a.batch != 1 and not a.no_batch1:   # configs[1]: batch=1 latency case, same run
         s1 = max(a.steps * 4, 40)
         dt1, prof1, _, _, aux1 = run_config(ya, torch, dist, rank, world, local_rank, 1, s1, max(a.warmup, 5), a.seed, a.size,
                                          blob_ptr, nbytes, backbone=a.backbone, precision=a.precision, tune=tune, fp8_per_tensor=a.fp8_per_tensor)
@@ -852,7 +919,7 @@ def main():
                                    latency=aux1["latency"], pcie_inclusive_fps=aux1["pcie_inclusive_fps"], pcie_inclusive_fps_pageable=aux1["pcie_inclusive_fps_pageable"],
                                    host_to_detections_latency=aux1.get("host_to_detections_latency"),
                                    weights_replication=how + " (the headline record's blob: the batch-1 engine loads it device to device)")
-    if a.batch != 1 and not a.no_configs4 and not (a.backbone == 101 and a.precision == "fp8"):
+    if a.full and a.batch != 1 and not a.no_configs4 and not (a.backbone == 101 and a.precision == "fp8"):
         # BASELINE.json configs[4]: YOLACT-700 ResNet-101, fp8 operands on the fp8 MFMA, batch 64 across 8 GPUs = 8 frames per
         # GPU - this rank's share, timed in the same run (same contract: resident frames, graph replay, max over ranks)
         make_src4 = lambda: ya.Engine(input_size=700, backbone=101, max_batch=1, use_graph=False, device=local_rank)   # noqa: E731
@@ -888,7 +955,7 @@ def main():
                     rec["accuracy_frc_balls"] = fp8_vs_oracles(a.seed, img, [dets], aux4["fp8_layers"], 101, usable_cores())
                     rec["accuracy_frc_balls"]["frame"] = "tests/golden/frc_balls.png resized to 700x700 (bilinear)"
             extra["configs4"] = rec
-    if world == 1 and rank == 0 and not a.no_tflite:
+    if a.full and world == 1 and rank == 0 and not a.no_tflite:
         extra["tflite"] = tflite_record(ya)
     if not _LIBRARY_CALL_STUCK:
         src.close()
@@ -906,23 +973,26 @@ def main():
         "config": {"workload": f"YOLACT-{a.size} R{a.backbone}-FPN batch={a.batch} per GPU, {a.size}x{a.size}x3 uint8 frames resident in HBM, "
                                f"hipGraph steady state, frames sharded over {world} GPU(s), " + ("one GPU: no collective" if world == 1 else f"weights replicated once: {how}"),
                    "batch_per_gpu": a.batch, "global_batch": a.batch * world, "input": [a.size, a.size, 3],
-                   "weights": f"seeded synthetic (seed {a.seed}), BN folded", "weights_replication": how,
-                   "detections_first_frames": ndet},
+                   "weights": f"seeded synthetic (seed {a.seed}), BN folded", "weights_replication": how},
         "net_tflops": round(fps * flops / 1e12, 2), "gflop_per_frame": round(flops / 1e9, 2),
         "net_frac_of_mfma_peak": round(fps * flops / 1e12 / (MFMA_F16_DENSE_PEAK_TFLOPS * world), 4),   # against the f16 peak in either precision (mixed-precision step)
-        "roofline": roofline_of(prof, a.batch),
-        "roofline_second": roofline_of(prof, a.batch, rank=1),
-        "kernel_families": family_rooflines(prof),
-        "launches_per_step": len(prof),
-        "latency": aux["latency"],
-        "pcie_inclusive_fps": aux["pcie_inclusive_fps"],
-        "pcie_inclusive_fps_pageable": aux["pcie_inclusive_fps_pageable"],
-        "pcie_inclusive_note": "host frames in pinned / pageable memory through yh_set_input_u8, copy of batch k+1 under step k (two input buffers + copy stream)",
     }
-    line.update(extra)
-    if world == 1 and not a.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(a.seed, aux["host_frame"], budget_s=a.cpu_budget, eng_out=aux["dets_frame0"], backbone=a.backbone,
-                                            fp8_layers=aux.get("fp8_layers"), accept=aux.get("accept"))
+    if a.full:
+        line["config"]["detections_first_frames"] = ndet
+        line.update({
+            "roofline": roofline_of(prof, a.batch),
+            "roofline_second": roofline_of(prof, a.batch, rank=1),
+            "kernel_families": family_rooflines(prof),
+            "launches_per_step": len(prof),
+            "latency": aux["latency"],
+            "pcie_inclusive_fps": aux["pcie_inclusive_fps"],
+            "pcie_inclusive_fps_pageable": aux["pcie_inclusive_fps_pageable"],
+            "pcie_inclusive_note": "host frames in pinned / pageable memory through yh_set_input_u8, copy of batch k+1 under step k (two input buffers + copy stream)",
+        })
+        line.update(extra)
+        if world == 1 and not a.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(a.seed, aux["host_frame"], budget_s=a.cpu_budget, eng_out=aux["dets_frame0"], backbone=a.backbone,
+                                                fp8_layers=aux.get("fp8_layers"), accept=aux.get("accept"))
     print(json.dumps(line), flush=True)
     leave_if_stuck()             # a helper thread is still inside the library's RCCL call: no teardown that could wait for it
     if dist is not None:

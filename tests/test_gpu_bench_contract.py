@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--batch", "8", "--cpu-budget", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--batch", "8", "--cpu-budget", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -47,6 +47,35 @@ def test_bench_prints_one_json_line_with_the_contract_keys(built):
         assert c4["accuracy"][k]["engine_dets"] > 0 and "matched_class_and_prior" in c4["accuracy"][k], k
 
 
+def test_plain_bench_times_the_headline_only_and_dumps_its_last_step(built, tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes the last timed step's outputs (float32 / float64,
+    at most 64 MB at the default batch of 64), the same in two runs of the same command."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        b = json.loads(lines[0])
+        assert b["unit"] == "frames/s" and b["higher_is_better"] is True and b["dtype"] == "f16" and b["steps"] == 2 and b["warmup"] == 1
+        assert b["value"] > 0 and abs(b["value"] - 64 * 2 / (b["ms_per_step"] * 2e-3)) < 0.01 * b["value"]
+        for k in ("roofline", "kernel_families", "latency", "batch1", "configs4", "tflite", "cpu_baseline"):
+            assert k not in b, k
+        files = sorted(p.name for p in d.iterdir())
+        assert files == sorted(f"{n}.npy" for n in ("loc", "conf", "mask", "proto", "cells", "det_count", "det_class", "det_prior",
+                                                    "det_score", "det_box", "det_mask_area", "det_masks")), files
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        out = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+        assert out["loc"].size > 0 and out["det_count"].shape == (64,) and out["det_count"].sum() > 0
+        dumps.append(out)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_graft_entry_smoke_runs(built):
     """__graft_entry__.smoke() is what the driver runs on the GPU box before the bench."""
     sys.path.insert(0, ROOT)
@@ -55,8 +84,9 @@ def test_graft_entry_smoke_runs(built):
 
 
 def test_two_rank_control_flow_on_one_gpu(built):
-    """The N > 1 path of bench.py (barriers, MAX over ranks, rank-0-only extras, weight broadcast) with two
+    """The N > 1 path of a plain bench.py run (barriers, MAX over ranks, weight broadcast) with two
     ranks sharing cuda:0 over gloo (--rehearse-on-one-gpu): a control-flow rehearsal, not a measurement.
+    The same path with --full (rank-0-only extras) runs in test_gpu_rccl_standin.py.
     The real N = 2/4/8 runs use RCCL with one rank per GPU and are the driver's."""
     import socket
     with socket.socket() as s:

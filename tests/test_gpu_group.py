@@ -243,7 +243,7 @@ def test_bench_single_process_mode_prints_the_contract_line(built):
     """bench.py --single-process: the N-GPU path driven by ONE process through yh_group_* (two members sharing device 0 here)."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--steps", "3", "--warmup", "2", "--batch", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--steps", "3", "--warmup", "2", "--batch", "4", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -155,7 +155,7 @@ def test_bench_two_ranks_take_the_library_rccl_path(standin, tmp_path):
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--configs4-batch", "1", "--no-tflite", "--rehearse-on-one-gpu", "--rccl-library", so],
+                        "--configs4-batch", "1", "--no-tflite", "--full", "--rehearse-on-one-gpu", "--rccl-library", so],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
