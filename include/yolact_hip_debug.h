@@ -17,31 +17,15 @@ extern "C" {
 
 #define YH_TUNING_DEFINED
 /* Measurement and test knobs of ONE handle. Every field: -1 = the library's default.
- * None of them changes results beyond the stated f16 tolerance (most are bit-equivalent); they exist so that
- * every launch-plan decision can be re-measured A/B and so that tests can reach every plan with small tensors.
+ * None of them changes results beyond the stated f16 tolerance (most are bit-equivalent); they exist so that tests
+ * can reach every plan with small tensors and check one form against another. A field no test sets does not exist
+ * (tests/test_abi.py guards it): the launch planner's own thresholds are constants beside it (csrc/engine.hip).
  * There are no process-global switches: the library reads no environment variable. */
 typedef struct yh_tuning {
     int32_t plan_cus;        /* CU count the launch plans assume (default: the device's multiProcessorCount) */
-    int32_t mfma16;          /* 256x256 tile on v_mfma_f32_16x16x32_f16 (1, default) or 32x32x16 (0) */
-    int32_t t128x256_m16;    /* 128x256 tile: 2-stage 16x16x32 form on stride-1 layers (1) or the 3-stage ring (0) */
-    int32_t small16;         /* 128x128 tiles on 16x16x32 everywhere (0) */
-    int32_t bigk;            /* K from which Cout >= 128 layers use the 8-wave tiles (256); creation time only */
-    int32_t tailsplit;       /* two-phase launches against wave quantisation (1) */
     int32_t chsplit;         /* 256 + 128 channel split of the 384-channel head (1) */
-    int32_t k1tile;          /* single-stage streaming tiles (four workgroups per CU): 0 off, 1 1x1 layers on the 128x128 form,
-                              * 2 + 64-channel 1x1, 3 + 64-channel 3x3, 4 + 128-channel 3x3, 5 / 6 + 3x3 layers with few big tiles and
-                              * the head's 128-channel remainder (6) */
-    int32_t k1_maxk;         /* ... for 1x1 layers with K <= this (1024) */
-    int32_t splitk_minsteps; /* K-steps from which few-tile launches split K (12) */
-    int32_t t64;             /* 64x64 tiles for latency-bound launches: 0 off, 1 never split K, 2 split K (2) */
-    int32_t t64_maxb;        /* ... when at most this many 128x128 tiles (256) */
-    int32_t t64_minsteps;    /* ... split K from this many K-steps (24) */
-    int32_t stemfuse;        /* fused stem + max pool (1); creation time only */
-    int32_t prefuse;         /* preprocessing inside the stem's patch loader (1); creation time only */
-    int32_t headmerge;       /* the shared head as one multi-level launch per conv (1); creation time only */
     int32_t upfuse;          /* FPN top-down upsamples evaluated in the lateral conv's epilogue instead of a kernel and a
                               * tensor of their own (1); creation time only */
-    int32_t k1_generic;      /* the generic softmax/candidate kernel also for 81 classes (0) */
     int32_t ablate;          /* timing only (results are garbage): bit 0 / bit 1 drop the activation / weight stream (zero-record
                               * descriptors: the loads issue, nothing moves), bit 2 issues no loader instruction at all */
     int32_t op_tile;         /* single-op entry points: force this ConvTile id (-1: the engine's choice) */
@@ -60,9 +44,6 @@ typedef struct yh_tuning {
                               * beside the protonet (default: every batch size); 0: never (the tail's K1-K3 alone fork) */
     int32_t protofuse;       /* the 1x1 conv that makes the 32 prototypes evaluated in the epilogue of the 3x3 conv in front of it
                               * wherever that one runs as single 256 x 256-tile launches (1); creation time only */
-    int32_t k1_min1;         /* streaming tiles: launches of at least this many tiles per CU, in QUARTERS (8 = 2 per CU), for the 1x1
-                              * layers and the 64- / 128-channel 3x3 layers */
-    int32_t k1_min3;         /* ... and (10 = 2.5 per CU) for the 3x3 layers with few big tiles and the head's remainder */
     int32_t chain;           /* identity bottleneck blocks of layers 1-2 as ONE launch each: 3x3 conv + 1x1 expand conv with the residual
                               * add + the next block's 1x1 reduce conv (csrc/bneck.hip; bit-identical to the separate launches). Bit 0
                               * on; bit 4 also fuse launches that only fill 64-pixel tiles (small batches: 3 % faster at batch 1-8).
@@ -77,6 +58,7 @@ typedef struct yh_tuning {
     int32_t tfl_group;       /* TFLite path: 1 (default) independent register-fed convolutions of one kernel form at one depth of the plan's
                               * graph as ONE launch (the prediction head's convolutions over the pyramid levels: 23 launches become 3), the
                               * plan in depth order; 0: one launch per convolution in file order. Same bytes */
+    int32_t reserved[17];    /* ignored by the library (the slots of retired fields: DESIGN.md §9) */
 } yh_tuning;
 
 #ifdef __cplusplus
@@ -92,8 +74,7 @@ extern "C" {
 #endif
 
 /* Replaces the run-time tuning fields of a live handle (captured graphs are dropped and re-captured on the next
- * call); YH_ESTATE if a creation-time field (bigk, stemfuse, prefuse, headmerge, upfuse, dsfuse, protofuse) differs from
- * the handle's. */
+ * call); YH_ESTATE if a creation-time field (upfuse, dsfuse, protofuse) differs from the handle's. */
 int yh_set_tuning(yh_engine* h, const yh_tuning* tune);
 /* The handle's tuning with every default resolved (plan_cus = the CU count the plans really use, ...). The tfl_* fields belong to
  * yh_tfl handles (yh_tfl_create_tuned) and stay -1: an engine handle does not carry them. */

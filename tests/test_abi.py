@@ -60,6 +60,32 @@ def test_struct_layouts_match_the_header(built, tmp_path):
     assert got == want
 
 
+def _tuning_fields():
+    """The field names of yh_tuning, in order, from include/yolact_hip_debug.h."""
+    src = open(os.path.join(ROOT, "include", "yolact_hip_debug.h")).read()
+    body = re.search(r"typedef struct yh_tuning \{(.*?)\} yh_tuning;", src, flags=re.S).group(1)
+    return re.findall(r"int32_t\s+(\w+)\s*(?:\[\d+\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+
+
+def test_every_tuning_field_is_a_test_switch():
+    """A tuning field is a test switch, or it does not exist: every named field of yh_tuning is set by some other test, as a
+    reference arm or to reach a plan with small tensors. The exception is ablate, the one switch that reaches into kernel code
+    (ConvParams::skip_dma, read by the conv loader): it is timing-only (results are garbage), so no test can check its output,
+    and removing it would change every conv kernel's compiled form. The ctypes mirror names the same fields in the same order."""
+    from yolact_amd import capi
+    fields = _tuning_fields()
+    assert len(fields) == len(capi.TUNING_FIELDS) + 1 and fields[-1] == "reserved"
+    assert fields[:-1] == list(capi.TUNING_FIELDS)
+    tests = os.path.dirname(os.path.abspath(__file__))
+    others = [open(os.path.join(tests, f)).read() for f in sorted(os.listdir(tests))
+              if f.startswith("test_") and f.endswith(".py") and f != os.path.basename(__file__)]
+    for name in fields:
+        if name in ("reserved", "ablate"):
+            continue
+        pat = re.compile(r"\b%s\s*=[^=]|[\"']%s[\"']\s*:" % (name, name))
+        assert any(pat.search(t) for t in others), f"yh_tuning.{name} is set by no test: retire it (DESIGN.md section 9)"
+
+
 def test_library_reads_no_environment_variable(built):
     """'No global state' (include/yolact_hip.h): every measurement switch is a field of yh_tuning on the handle; the
     product sources never call getenv and the built library does not even import it."""

@@ -943,7 +943,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_f16(const ConvParams p) {
 
 int conv_tile_ch(ConvTile t) {
     switch (t) { case TILE_128x128: case TILE_128x128_S3: case TILE_128x128_M16: case TILE_128x128_S3_M16: case TILE_128x128_K1: case TILE_128x128_FP8: case TILE_128x256: case TILE_128x256_M16: return 128; case TILE_64x256: case TILE_64x256_SMALLC: case TILE_64x256_K1: case TILE_64x64_S3: case TILE_64x64_FP8: return 64;
-                 case TILE_32x256: return 32; case TILE_96x128_K1: return 96; case TILE_256x256: case TILE_256x256_M16: case TILE_256x256_FP8: return 256; }
+                 case TILE_32x256: return 32; case TILE_96x128_K1: return 96; case TILE_256x256_M16: case TILE_256x256_FP8: return 256; }
     return 0;
 }
 int conv_tile_m(ConvTile t) {
@@ -956,7 +956,6 @@ const char* conv_tile_symbol(ConvTile t) {
         case TILE_32x256: return "conv_igemm_f16<32,256,1,4,0,2>";
         case TILE_64x256_SMALLC: return "conv_igemm_f16<64,256,1,4,1,2>";
         case TILE_128x256: return "conv_igemm_f16<128,256,2,4,0,3>";
-        case TILE_256x256: return "conv_igemm_f16<256,256,2,4,0,2>";
         case TILE_256x256_M16: return "conv_igemm_f16<256,256,2,4,0,2,mfma16>";
         case TILE_128x128_M16: return "conv_igemm_f16<128,128,2,2,0,2,mfma16>";
         case TILE_128x128_S3_M16: return "conv_igemm_f16<128,128,2,2,0,3,mfma16>";
@@ -1064,7 +1063,6 @@ hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream) {
             case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, false, false, true>), grid, dim3(256), 0, stream, p); break;
             case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16, false, false, true>), grid, dim3(256), 0, stream, p); break;
             case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, false, true>), grid, dim3(512), 0, stream, p); break;
-            case TILE_256x256: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 32, false, false, true>), grid, dim3(512), 0, stream, p); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -1086,7 +1084,6 @@ hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream) {
         case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16>), grid, dim3(256), 0, stream, p); break;
         case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16>), grid, dim3(256), 0, stream, p); break;
         case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16>), grid, dim3(512), 0, stream, p); break;
-        case TILE_256x256: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2>), grid, dim3(512), 0, stream, p); break;
         case TILE_256x256_FP8:
             if (!p.scale) return hipErrorInvalidValue;
             hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, true>), grid, dim3(512), 0, stream, p);

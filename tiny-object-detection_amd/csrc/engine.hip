@@ -132,19 +132,14 @@ uint16_t f32_to_f16_bits(float f) {  // round to nearest even, IEEE binary16
 
 // The handle's tuning with every default resolved (include/yolact_hip_debug.h: yh_tuning; -1 = default there).
 struct Tune {
-    int plan_cus, mfma16, t128x256_m16, small16, bigk, tailsplit, chsplit, k1tile, k1_maxk, splitk_minsteps, t64, t64_maxb,
-        t64_minsteps, stemfuse, prefuse, headmerge, upfuse, k1_generic, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, k1_min1, k1_min3, chain;
+    int plan_cus, chsplit, upfuse, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, chain;
 };
 static Tune resolve_tuning(const yh_tuning& t, int device_cus) {
     auto d = [](int v, int def) { return v < 0 ? def : v; };
     Tune r;
     r.plan_cus = t.plan_cus > 0 ? t.plan_cus : device_cus;
-    r.mfma16 = d(t.mfma16, 1); r.t128x256_m16 = d(t.t128x256_m16, 1); r.small16 = d(t.small16, 0); r.bigk = d(t.bigk, 256);
-    r.tailsplit = d(t.tailsplit, 1); r.chsplit = d(t.chsplit, 1); r.k1tile = d(t.k1tile, 6); r.k1_maxk = d(t.k1_maxk, 1024);
-    r.splitk_minsteps = d(t.splitk_minsteps, 12); r.t64 = d(t.t64, 2); r.t64_maxb = d(t.t64_maxb, 256); r.t64_minsteps = d(t.t64_minsteps, 24);
-    r.stemfuse = d(t.stemfuse, 1); r.prefuse = d(t.prefuse, 1); r.headmerge = d(t.headmerge, 1);
-    r.upfuse = d(t.upfuse, 1); r.k1_generic = d(t.k1_generic, 0); r.ablate = d(t.ablate, 0); r.op_tile = t.op_tile; r.op_kslices = d(t.op_kslices, 0);
-    r.tailfork = d(t.tailfork, 1); r.dsfuse = d(t.dsfuse, 1); r.headfork_maxb = d(t.headfork_maxb, 1 << 20); r.protofuse = d(t.protofuse, 1); r.k1_min1 = d(t.k1_min1, 8); r.k1_min3 = d(t.k1_min3, 10);
+    r.chsplit = d(t.chsplit, 1); r.upfuse = d(t.upfuse, 1); r.ablate = d(t.ablate, 0); r.op_tile = t.op_tile; r.op_kslices = d(t.op_kslices, 0);
+    r.tailfork = d(t.tailfork, 1); r.dsfuse = d(t.dsfuse, 1); r.headfork_maxb = d(t.headfork_maxb, 1 << 20); r.protofuse = d(t.protofuse, 1);
     r.chain = d(t.chain, 17);
     return r;
 }
@@ -232,7 +227,7 @@ struct yh_engine {
     hipEvent_t stage_ev[2] = { nullptr, nullptr };
     int stage_idx = 0;
     int last_conv_launches = 0;   // yh_debug_last_conv_launches
-    bool stem_fused = false, pre_fused = false;
+    bool stem_fused = false;
     int tail_fork_op = 0;   // ops[tail_fork_op..] (the protonet) do not feed the tail's K1-K3
     int head_fork_op = 0;   // ops[head_fork_op .. tail_fork_op) are the shared prediction head; the protonet does not read them
     float* splitk_ws_side = nullptr;   // split-K workspace of convolutions launched on the side stream
@@ -351,6 +346,9 @@ void build_conv_table(yh_engine* h) {
     h->blob_bytes = off;
 }
 
+// K from which layers with at least 128 output channels get the 8-wave tiles
+constexpr int kBigK = 256;
+
 int add_panel(yh_engine* h, std::vector<int> src) {
     Panel p;
     p.src = src;
@@ -366,7 +364,7 @@ int add_panel(yh_engine* h, std::vector<int> src) {
     else p.tile = TILE_128x128;
     p.Kpad = d0.cin == 3 ? round_up(d0.k * ((d0.k + 1) / 2), 8) * 8 : d0.k * d0.k * d0.cin;  // stem: k rows x ceil(k/2) chunks
     // K-heavy layers (>= 8 steps of 64): 8-wave tiles on the 3-stage LDS-DMA ring
-    if (p.tile == TILE_128x128 && p.Kpad >= h->tune.bigk) p.tile = (cout % 256 == 0) ? TILE_256x256 : TILE_128x256;
+    if (p.tile == TILE_128x128 && p.Kpad >= kBigK) p.tile = (cout % 256 == 0) ? TILE_256x256_M16 : TILE_128x256;
     p.coutPad = round_up(cout, conv_tile_ch(p.tile));
     h->panels.push_back(p);
     return (int)h->panels.size() - 1;
@@ -378,7 +376,7 @@ int add_panel_kcat(yh_engine* h, int conv_a, int conv_b) {
     Panel& p = h->panels[id];
     p.kcat = conv_b;
     p.Kpad += h->convs[conv_b].cin;
-    if (p.tile == TILE_128x128 && p.Kpad >= h->tune.bigk) p.tile = (p.cout % 256 == 0) ? TILE_256x256 : TILE_128x256;
+    if (p.tile == TILE_128x128 && p.Kpad >= kBigK) p.tile = (p.cout % 256 == 0) ? TILE_256x256_M16 : TILE_128x256;
     p.coutPad = round_up(p.cout, conv_tile_ch(p.tile));
     return id;
 }
@@ -418,11 +416,10 @@ int build_graph_spec(yh_engine* h) {
     if ((rc = new_buf(h, "input", h->in_hp, h->in_hp, 4, &h->in_f16))) return rc;
 
     int ci = 0;  // canonical conv cursor
-    // Fused stem + pool (conv_igemm.hip: stem_pool_f16) unless the size is odd or tune.stemfuse = 0; its patch
-    // loader then also does the preprocessing (raw RGB -> normalised f16) unless tune.prefuse = 0.
-    h->stem_fused = h->tune.stemfuse && (S % 2 == 0);
-    h->pre_fused = h->stem_fused && h->tune.prefuse;
-    if (!h->pre_fused) {
+    // Fused stem + pool (conv_igemm.hip: stem_pool_f16) unless the size is odd; its patch loader then also does
+    // the preprocessing (raw RGB -> normalised f16).
+    h->stem_fused = S % 2 == 0;
+    if (!h->stem_fused) {
         Op o; o.kind = OP_PRE; o.name = "input"; o.label = "preprocess_rgb8_f16:input";
         o.bytes_per_img = (double)S * S * (3 + 8);
         h->ops.push_back(o);
@@ -440,7 +437,7 @@ int build_graph_spec(yh_engine* h) {
         o.in = h->in_f16; o.out = pool; o.res = stem;   // res = optional stem output
         o.P = H2; o.Q = H2;
         o.flops_per_img = 2.0 * H1 * H1 * 64 * 147.0;
-        o.bytes_per_img = (h->pre_fused ? 3.0 * S * S : 8.0 * h->in_hp * h->in_hp) + 2.0 * 64 * H2 * H2;
+        o.bytes_per_img = 3.0 * S * S + 2.0 * 64 * H2 * H2;
         h->ops.push_back(o);
     } else {
     {
@@ -616,9 +613,7 @@ int build_graph_spec(yh_engine* h) {
     const int ci_end = ci;
     // The head's weights are shared by the five levels, whose cells lie end to end in the pyramid
     // buffers: ONE launch per head conv covers all of them (multi-level input: every tap stays inside its
-    // row's own level), instead of five launches of which three have a handful of tiles. tune.headmerge = 0
-    // restores one launch per level.
-    const int headmerge = h->tune.headmerge;
+    // row's own level), instead of five launches of which three have a handful of tiles.
     auto merged = [&](const char* name, int panel, const Buf& in, const Buf& out, int act) {
         Buf bi = in, bo = out;
         bi.h = bo.h = h->cells; bi.w = bo.w = 1;
@@ -634,20 +629,10 @@ int build_graph_spec(yh_engine* h) {
     };
     for (int l = 0; l < 5; ++l) { snprintf(nm, sizeof nm, "head_t%d", l); h->named[nm] = level(h->pyr_t, l); }
     h->head_fork_op = (int)h->ops.size();
-    if (headmerge) {
-        h->ops.push_back(merged("head_t", trunk_panel, h->pyr, h->pyr_t, 1));
-        Op o = merged("head_out", out_panel, h->pyr_t, h->heads, 0);
-        o.tanh_from = 12 + 3 * h->C;
-        h->ops.push_back(o);
-    } else
-    for (int l = 0; l < 5; ++l) {
-        snprintf(nm, sizeof nm, "head_t%d", l);
-        h->ops.push_back(conv_op(h, nm, trunk_panel, level(h->pyr, l), level(h->pyr_t, l), 1, 1, 1, nullptr));
-        snprintf(nm, sizeof nm, "head_out%d", l);
-        Op o = conv_op(h, nm, out_panel, level(h->pyr_t, l), level(h->heads, l), 1, 1, 0, nullptr);
-        o.tanh_from = 12 + 3 * h->C;
-        h->ops.push_back(o);
-    }
+    h->ops.push_back(merged("head_t", trunk_panel, h->pyr, h->pyr_t, 1));
+    Op head_out = merged("head_out", out_panel, h->pyr_t, h->heads, 0);
+    head_out.tanh_from = 12 + 3 * h->C;
+    h->ops.push_back(head_out);
     // ---- protonet (listed after the heads so the detection tail's K1-K3, which need only the head
     // rows, can run on a side stream underneath it; canonical conv indices are unchanged)
     h->tail_fork_op = (int)h->ops.size();
@@ -788,7 +773,6 @@ int alloc_tail(yh_engine* h) {
     d.P = h->P; d.cells = h->cells; d.ldh = h->ldh; d.C = h->C; d.hp = h->hp; d.wp = h->wp;
     d.top_k = h->cfg.top_k; d.max_dets = h->cfg.max_dets;
     d.conf_thresh = h->cfg.conf_thresh; d.nms_thresh = h->cfg.nms_thresh;
-    d.k1_generic = h->tune.k1_generic;
     // the candidate counters start at zero and every consumer (det_class_nms) leaves its own at zero again
     if (hipMemset(d.cls_count, 0, sizeof(int) * (size_t)N * Cf) != hipSuccess) return h->fail(YH_EHIP, "hipMemset tail counters");
     return YH_OK;
@@ -797,65 +781,65 @@ int alloc_tail(yh_engine* h) {
 // ------------------------------------------------------------------------------------------------
 // launching
 // ------------------------------------------------------------------------------------------------
-// The panel fixes the widest channel tile (coutPad); per launch, fall back to the 4-wave
-// 128 x 128 tile (2 workgroups per CU) when the big tile would leave most of the 256 CUs idle.
-ConvTile pick_tile_base(const Tune& tu, const Panel& pn, int M, int stride, int pad, bool ml);
-// ml: the op has a multi-level input (only the tiles launch_conv instantiates for it may be chosen)
-ConvTile pick_tile(const Tune& tu, const Panel& pn, int M, int stride = 0, int pad = 0, bool ml = false) {
-    const ConvTile t = pick_tile_base(tu, pn, M, stride, pad, ml);
-    // Latency-bound launches with few 128 x 128 tiles: 64 x 64 tiles put four times as many workgroups on
-    // the idle CUs and a K step costs a wave 4 MFMAs instead of 16 (tune.t64; 0 = off)
-    if (tu.t64 && t == TILE_128x128_S3 && (long long)((M + 127) / 128) * (pn.coutPad / 128) <= tu.t64_maxb) return TILE_64x64_S3;
-    // 128 x 256: the 2-stage 16x16x32 form measures ~5 % faster than the 3-stage 32x32x16 ring on stride-1
-    // layers (0.112 vs 0.118 ms on the 69 x 69 3x3 convs at batch 64) and slower on the stride-2 one
-    if (tu.t128x256_m16 && t == TILE_128x256 && stride == 1) return TILE_128x256_M16;
-    if (tu.small16 && t == TILE_128x128) return TILE_128x128_M16;
-    if (tu.small16 >= 2 && t == TILE_128x128_S3 && pn.Kpad / 64 < 8) return TILE_128x128_S3_M16;   // (split-K keeps the 32x32x16 form)
-    return t;
-}
-ConvTile pick_tile_base(const Tune& tu, const Panel& pn, int M, int stride, int pad, bool ml) {
-    if (pn.tile == TILE_256x256 || pn.tile == TILE_128x256) {
+// Thresholds of the launch planner, in the units noted (tile counts scale with tu.plan_cus where noted).
+// Streaming tiles for 1x1 layers with K up to this
+constexpr int kK1MaxK = 1024;
+// Streaming tiles from this many tiles per CU, in QUARTERS: 8 = two per CU for the 1x1 layers and the 64- / 128-channel 3x3
+// layers (four measured the same at batch 64 and 4 % slower at batch 16) ...
+constexpr int kK1Min1 = 8;
+// ... and 10 = 2.5 per CU for the 3x3 layers with few big tiles and the head's 128-channel remainder
+constexpr int kK1Min3 = 10;
+// 64 x 64 tiles for latency-bound launches of at most this many 128 x 128 tiles (not scaled)
+constexpr int kT64MaxB = 256;
+// Few-tile launches split K from this many K-steps: the 3-stage 128 x 128 ring ...
+constexpr int kSplitKMinSteps = 12;
+// ... and the 64 x 64 tiles
+constexpr int kT64MinSteps = 24;
+
+// The panel fixes the widest channel tile (coutPad); per launch, the decisions below apply in order.
+// ml: the op has a multi-level input (only the tiles launch_conv instantiates for it may be chosen).
+ConvTile pick_tile(const Tune& tu, const Panel& pn, int M, int stride, bool ml) {
+    const int cus = tu.plan_cus;
+    const long long b128 = (long long)((M + 127) / 128) * (pn.coutPad / 128), m256 = (M + 255) / 256;
+    const long long stream_min1 = (long long)kK1Min1 * cus / 4, stream_min3 = (long long)kK1Min3 * cus / 4;
+    // Latency-bound launches with few 128 x 128 tiles go on the 3-stage ring, which hides the L2 round trip of every
+    // 64-deep K step; with fewer still, on 64 x 64 tiles: four times as many workgroups on the idle CUs, and a K step
+    // costs a wave 4 MFMAs instead of 16
+    const ConvTile ring = b128 <= kT64MaxB ? TILE_64x64_S3 : TILE_128x128_S3;
+    // 1. The 8-wave tiles (one workgroup per CU) where they would leave most CUs idle: the 4-wave 128 x 128 tile
+    // (2 workgroups per CU) - or, for 3x3 layers with >= 2.5 small tiles per CU (layer 4 at batch 64, 648 tiles), its
+    // streaming form, four workgroups per CU: 950 TFLOP/s where the double-buffered 128 x 128 tile gave 730
+    if (pn.tile == TILE_256x256_M16 || pn.tile == TILE_128x256) {
         const int tm = conv_tile_m(pn.tile), tch = conv_tile_ch(pn.tile);
         const long long blocks = (long long)((M + tm - 1) / tm) * (pn.coutPad / tch);
-        if (blocks < tu.plan_cus * 3 / 4) {
-            // latency-bound launches (at most one workgroup per CU): the 3-stage ring hides the
-            // L2 round trip of every 64-deep K step
-            const long long b128 = (long long)((M + 127) / 128) * (pn.coutPad / 128);
-            // (3x3 layers with too few big tiles but >= 2.5 small ones per CU - layer 4 at batch 64, 648 tiles: the streaming
-            // form, four workgroups per CU, runs them at 950 TFLOP/s where the double-buffered 128 x 128 tile gave 730)
-            if (tu.k1tile >= 6 && !ml && pn.k == 3 && b128 >= (long long)tu.k1_min3 * tu.plan_cus / 4) return TILE_128x128_K1;
-            return b128 <= tu.plan_cus ? TILE_128x128_S3 : TILE_128x128;
+        if (blocks < cus * 3 / 4) {
+            if (!ml && pn.k == 3 && b128 >= stream_min3) return TILE_128x128_K1;
+            return b128 <= cus ? ring : TILE_128x128;
         }
     }
-    // HBM-bound 1x1 layers (K <= 512): the single-stage "streaming" forms keep 34-40 KB of LDS per workgroup,
-    // so four workgroups share a CU instead of two and their load and store phases overlap each other
-    // (4.0 -> 5.2 TB/s on the 69 x 69 expand convs at batch 64). tune.k1tile: 0 off, 1: 128x128 form only,
-    // 2: also the 64-channel 1x1 form, 3: also 64-channel 3x3, 4: also 128-channel 3x3, 5: also 256-channel 3x3 layers with
-    // fewer than two rounds of big tiles, 6: also 3x3 layers with less than a round of big tiles (layer 4) and the head's
-    // 128-channel remainder (plan_conv).
-    const int k1 = tu.k1tile;
-    const long long k1_min = (long long)tu.k1_min1 * tu.plan_cus / 4;   // (tune.k1_min1 = 8 quarter-CUs: two tiles per CU. Four measured the same at batch 64 and 4 % slower at batch 16)
-    if (k1 && !ml && pn.k == 1 && pn.Kpad <= tu.k1_maxk) {
-        if (pn.coutPad % 128 == 0 && pn.cout > 64 && (long long)((M + 127) / 128) * (pn.coutPad / 128) >= k1_min) return TILE_128x128_K1;
-        if (k1 >= 2 && pn.tile == TILE_64x256 && (M + 255) / 256 >= k1_min) return TILE_64x256_K1;
+    // 2. HBM-bound 1x1 layers: the single-stage "streaming" forms keep 34-40 KB of LDS per workgroup, so four workgroups
+    // share a CU instead of two and their load and store phases overlap each other (4.0 -> 5.2 TB/s on the 69 x 69 expand
+    // convs at batch 64)
+    if (!ml && pn.k == 1 && pn.Kpad <= kK1MaxK) {
+        if (pn.coutPad % 128 == 0 && pn.cout > 64 && b128 >= stream_min1) return TILE_128x128_K1;
+        if (pn.tile == TILE_64x256 && m256 >= stream_min1) return TILE_64x256_K1;
     }
-    // (the 64-channel 3x3 convs of layer 1 too: 590 -> 715 TFLOP/s - their LDS fill per MFMA is what binds them, and
-    // four co-resident workgroups overlap it better than a double buffer inside two)
-    if (k1 >= 3 && !ml && pn.k == 3 && pn.tile == TILE_64x256 && (M + 255) / 256 >= k1_min) return TILE_64x256_K1;
-    // ... and the 128-channel 3x3 convs of layer 2 (k1 >= 4: 0.118 -> 0.098 ms, 918 TFLOP/s where the 8-wave 128 x 256 forms
-    // gave 740-775), and 256-channel 3x3 layers whose big tiles are fewer than two rounds (k1 >= 5; the 35 x 35 layers at
-    // batch 64: 307 tiles of 256 x 256 = a /rounds + /tail pair, 0.107 ms -> one launch of 1226 small tiles, 0.104 ms)
-    if (k1 >= 4 && !ml && pn.k == 3 && pn.tile == TILE_128x256 && pn.coutPad == 128 && (long long)((M + 127) / 128) >= k1_min) return TILE_128x128_K1;
-    if (k1 >= 5 && !ml && pn.k == 3 && pn.tile == TILE_256x256 && (long long)((M + 255) / 256) * (pn.coutPad / 256) < 2ll * tu.plan_cus &&
-        (long long)((M + 127) / 128) * (pn.coutPad / 128) >= (long long)tu.k1_min3 * tu.plan_cus / 4) return TILE_128x128_K1;
-    // 64-channel layers at small batch (layer 1 at batch 1: 75 tiles of 64 x 256 on 256 CUs): 64 x 64 tiles make four
+    // 3. ... the 64-channel 3x3 convs of layer 1 too: 590 -> 715 TFLOP/s - their LDS fill per MFMA is what binds them, and
+    // four co-resident workgroups overlap it better than a double buffer inside two
+    if (!ml && pn.k == 3 && pn.tile == TILE_64x256 && m256 >= stream_min1) return TILE_64x256_K1;
+    // 4. ... the 128-channel 3x3 convs of layer 2 (0.118 -> 0.098 ms, 918 TFLOP/s where the 8-wave 128 x 256 forms gave
+    // 740-775), and 256-channel 3x3 layers whose big tiles are fewer than two rounds (the 35 x 35 layers at batch 64: 307
+    // tiles of 256 x 256 = a /rounds + /tail pair, 0.107 ms -> one launch of 1226 small tiles, 0.104 ms)
+    if (!ml && pn.k == 3 && pn.tile == TILE_128x256 && pn.coutPad == 128 && b128 >= stream_min1) return TILE_128x128_K1;
+    if (!ml && pn.k == 3 && pn.tile == TILE_256x256_M16 && m256 * (pn.coutPad / 256) < 2ll * cus && b128 >= stream_min3) return TILE_128x128_K1;
+    // 5. 64-channel layers at small batch (layer 1 at batch 1: 75 tiles of 64 x 256 on 256 CUs): 64 x 64 tiles make four
     // times the workgroups
-    if (tu.t64 && !ml && pn.tile == TILE_64x256 && (M + 255) / 256 < tu.plan_cus) return TILE_64x64_S3;
-    if (pn.tile == TILE_128x128 && pn.Kpad >= 256) {
-        const long long b128 = (long long)((M + 127) / 128) * (pn.coutPad / 128);
-        if (b128 <= tu.plan_cus) return TILE_128x128_S3;
-    }
-    if (pn.tile == TILE_256x256 && (tu.mfma16 || ml)) return TILE_256x256_M16;
+    if (!ml && pn.tile == TILE_64x256 && m256 < cus) return TILE_64x64_S3;
+    // 6. K-heavy 128 x 128 launches of at most one round: the ring (above)
+    if (pn.tile == TILE_128x128 && pn.Kpad >= 256 && b128 <= cus) return ring;
+    // 7. 128 x 256: the 2-stage 16x16x32 form measures ~5 % faster than the 3-stage 32x32x16 ring on stride-1 layers
+    // (0.112 vs 0.118 ms on the 69 x 69 3x3 convs at batch 64) and slower on the stride-2 one
+    if (pn.tile == TILE_128x256 && stride == 1) return TILE_128x256_M16;
     return pn.tile;
 }
 
@@ -868,9 +852,9 @@ ConvTile pick_tile_base(const Tune& tu, const Panel& pn, int M, int stride, int 
 // 1.2 rounds of work). When the last round would be less than half full, the launch is split:
 // the first r * 256 workgroups' rows on the big tile, the remaining rows on 128 x 128 tiles (two
 // workgroups per CU, a quarter of the work each), which fill the chip again. Returns the number of
-// big row tiles in phase one, 0 = single launch. tune.tailsplit = 0 turns it off.
+// big row tiles in phase one, 0 = single launch.
 int tail_split_tiles(const Tune& tu, int coutPad, const ConvParams& p, ConvTile tile) {
-    if (!tu.tailsplit || p.k_slices > 1 || coutPad % 128 != 0 || p.m_tile0 || p.ch_tile0) return 0;
+    if (p.k_slices > 1 || coutPad % 128 != 0 || p.m_tile0 || p.ch_tile0) return 0;
     if (tile != TILE_256x256_M16) return 0;   // the only big tile whose bits the small 16x16x32 tiles reproduce
     const int cus = tu.plan_cus;
     const int tm = conv_tile_m(tile), nch = coutPad / conv_tile_ch(tile);
@@ -904,7 +888,7 @@ int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, K
         b.n_ch_tiles = 1; b.ch_tile0 = 2;
         // the 128-channel remainder on the 4-wave 128 x 128 tile (two workgroups per CU: 0.34 -> 0.30 ms at batch 64), in its
         // streaming form where the launch is large (four per CU: 0.31 -> 0.26 ms)
-        const bool streaming = tu.k1tile >= 6 && (long long)((p.M + 127) / 128) >= (long long)tu.k1_min3 * tu.plan_cus / 4;
+        const bool streaming = (long long)((p.M + 127) / 128) >= (long long)kK1Min3 * tu.plan_cus / 4;
         // (round 5, measured and not kept: splitting the 256-wide launch's own last round off - head_out at batch 64 is 1 604 tiles =
         // 6.27 rounds - onto the bit-compatible 128 x 128 tiles: 0.4415 + 0.0480 ms against 0.4912 for the single launch; and a last
         // round up to three quarters full split off for p3 / proto0-2 (4.65 rounds): 0.276 + 0.075 against 0.341 ms, step 9.72 vs 9.67)
@@ -954,7 +938,6 @@ hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile til
 ConvTile dual_conv_tile(ConvTile t) {
     switch (t) {
         case TILE_128x128: case TILE_128x128_K1: case TILE_128x128_S3: case TILE_64x64_S3: case TILE_128x128_M16: case TILE_128x128_S3_M16: case TILE_256x256_M16: return t;
-        case TILE_256x256: return TILE_256x256_M16;
         default: return TILE_128x128;
     }
 }
@@ -995,7 +978,7 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     if (h->tune.ablate & 1) { p.x_bytes = 0; }
     if (h->tune.ablate & 2) { p.w_bytes = 0; }
     if (h->tune.ablate & 4) { p.skip_dma = 1; }
-    ConvTile tile = pick_tile(h->tune, pn, p.M, o.stride, o.pad, o.nlev > 0);
+    ConvTile tile = pick_tile(h->tune, pn, p.M, o.stride, o.nlev > 0);
     if (o.dual) tile = dual_conv_tile(tile);
     if (h->fp8_active) {
         // fp8 precision, calibrated: what this op's output is written as, and (for the K-heavy 3x3 layers) E4M3 operands
@@ -1016,7 +999,7 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
             // (latency-bound launches - at most two 128 x 128 tiles per CU, e.g. R101-700 at batch 8 - on 64 x 64 tiles:
             // a K step of 128 costs a wave 4 MFMAs instead of 16 and four times as many workgroups share the CUs)
             const long long b128 = (long long)((p.M + 127) / 128) * (pn.coutPad / 128);
-            if (tile == TILE_128x128_FP8 && o.nlev == 0 && h->tune.t64 && b128 <= 2ll * h->tune.plan_cus) tile = TILE_64x64_FP8;
+            if (tile == TILE_128x128_FP8 && o.nlev == 0 && b128 <= 2ll * h->tune.plan_cus) tile = TILE_64x64_FP8;
         }
     }
     if (tile_out) *tile_out = tile;
@@ -1030,12 +1013,10 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
         p.w2 = p2.w; p.bias2 = p2.bias; p.y2 = t.out.d;
         p.y = nullptr; p.y8 = nullptr;
     }
-    const int splitk_min = h->tune.splitk_minsteps, t64_mode = h->tune.t64, t64_min = h->tune.t64_minsteps;
-    const bool ring128 = tile == TILE_128x128_S3;
-    const bool ring64 = tile == TILE_64x64_S3 && t64_mode >= 2;
+    const bool ring128 = tile == TILE_128x128_S3, ring64 = tile == TILE_64x64_S3;
     // (launches of at most 32 output pixels - P6 / P7 at batch 1: 25 and 9 - do not split: four workgroups walking 36 k-steps take
     // as long as their slices plus the reduce launch, and the step has two launches fewer)
-    if (p.M > 32 && ((ring128 && p.ksteps >= splitk_min) || (ring64 && p.ksteps >= t64_min))) {
+    if (p.M > 32 && ((ring128 && p.ksteps >= kSplitKMinSteps) || (ring64 && p.ksteps >= kT64MinSteps))) {
         // few tiles, long K: split K so that about one workgroup per CU streams the weights
         const int tm = conv_tile_m(tile);
         const long long tiles = (long long)((p.M + tm - 1) / tm) * p.n_ch_tiles;
@@ -1224,7 +1205,7 @@ int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
             const Panel& pn = h->panels[o.panel];
             StemPoolParams sp;
             sp.x = o.in.d; sp.w = pn.w; sp.bias = pn.bias; sp.pool = o.out.d;
-            sp.rgb = h->pre_fused ? h->in_u8() : nullptr; sp.S = h->S;
+            sp.rgb = h->in_u8(); sp.S = h->S;
             sp.stem = h->cfg.debug_tensors ? o.res.d : nullptr;
             sp.n = n; sp.Hp = o.in.h; sp.Wp = o.in.w; sp.SO = o.res.h; sp.PO = o.out.h;
             sp.tiles_y = (o.out.h + 7) / 8; sp.tiles_x = (o.out.w + 7) / 8;
@@ -1693,16 +1674,14 @@ void yh_destroy(yh_engine* h) {
 int yh_set_tuning(yh_engine* h, const yh_tuning* tune) {
     if (!h || !tune) return YH_EINVAL;
     const Tune t = resolve_tuning(*tune, h->device_cus);
-    if (t.bigk != h->tune.bigk || t.stemfuse != h->tune.stemfuse || t.prefuse != h->tune.prefuse || t.headmerge != h->tune.headmerge ||
-        t.upfuse != h->tune.upfuse || t.dsfuse != h->tune.dsfuse || t.protofuse != h->tune.protofuse)
-        return h->fail(YH_ESTATE, "bigk, stemfuse, prefuse, headmerge, upfuse, dsfuse and protofuse are fixed when the handle is created");
+    if (t.upfuse != h->tune.upfuse || t.dsfuse != h->tune.dsfuse || t.protofuse != h->tune.protofuse)
+        return h->fail(YH_ESTATE, "upfuse, dsfuse and protofuse are fixed when the handle is created");
     HIPCHK(h, hipSetDevice(h->dev));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured plans were made under the old tuning
     h->graphs.clear();
     h->tune = t;
     h->cfg.tune = *tune;
-    h->det.k1_generic = t.k1_generic;
     return YH_OK;
 }
 
@@ -1710,11 +1689,8 @@ int yh_get_tuning(const yh_engine* h, yh_tuning* out) {
     if (!h || !out) return YH_EINVAL;
     memset(out, 0xFF, sizeof *out);
     const Tune& t = h->tune;
-    out->plan_cus = t.plan_cus; out->mfma16 = t.mfma16; out->t128x256_m16 = t.t128x256_m16; out->small16 = t.small16; out->bigk = t.bigk;
-    out->tailsplit = t.tailsplit; out->chsplit = t.chsplit; out->k1tile = t.k1tile; out->k1_maxk = t.k1_maxk; out->splitk_minsteps = t.splitk_minsteps;
-    out->t64 = t.t64; out->t64_maxb = t.t64_maxb; out->t64_minsteps = t.t64_minsteps;
-    out->stemfuse = t.stemfuse; out->prefuse = t.prefuse; out->headmerge = t.headmerge; out->upfuse = t.upfuse; out->k1_generic = t.k1_generic;
-    out->ablate = t.ablate; out->op_tile = t.op_tile; out->op_kslices = t.op_kslices; out->tailfork = t.tailfork; out->dsfuse = t.dsfuse; out->headfork_maxb = t.headfork_maxb; out->protofuse = t.protofuse; out->k1_min1 = t.k1_min1; out->k1_min3 = t.k1_min3; out->chain = t.chain;
+    out->plan_cus = t.plan_cus; out->chsplit = t.chsplit; out->upfuse = t.upfuse; out->ablate = t.ablate; out->op_tile = t.op_tile; out->op_kslices = t.op_kslices;
+    out->tailfork = t.tailfork; out->dsfuse = t.dsfuse; out->headfork_maxb = t.headfork_maxb; out->protofuse = t.protofuse; out->chain = t.chain;
     // (tfl_dot, tfl_graph, tfl_fuse, tfl_group belong to yh_tfl handles - yh_tfl_create_tuned - and stay -1 here: an engine handle does not carry them)
     return YH_OK;
 }
@@ -2727,9 +2703,8 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "conv op: empty output");
     ConvTile tile = cin == 3 ? TILE_64x256_SMALLC : (cout <= 32 ? TILE_32x256 : (cout <= 64 ? TILE_64x256 : TILE_128x128));
     const int Kpad = cin == 3 ? round_up(k * k, 8) * 8 : k * k * cin;
-    if (tile == TILE_128x128 && Kpad >= 512) tile = (cout % 256 == 0) ? TILE_256x256 : TILE_128x256;
-    if (tile == TILE_256x256 && h->tune.mfma16) tile = TILE_256x256_M16;
-    if (tile == TILE_128x256 && stride == 1 && h->tune.t128x256_m16) tile = TILE_128x256_M16;
+    if (tile == TILE_128x128 && Kpad >= 512) tile = (cout % 256 == 0) ? TILE_256x256_M16 : TILE_128x256;
+    if (tile == TILE_128x256 && stride == 1) tile = TILE_128x256_M16;
     if (h->tune.op_tile >= 0 && cin != 3) tile = (ConvTile)h->tune.op_tile;   // test hook: force a tile variant
     if (conv_tile_ch(tile) == 0) return h->fail(YH_EINVAL, "conv op: tune.op_tile is not a tile id");
     const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);

@@ -123,9 +123,10 @@ struct ConvParams {
     float* partial;       // [k_slices][M][partial_ld] f32 workspace
 };
 
-// (ids 4, 9-11, 14, 17, 25, 26 belonged to retired experiments: a 256x128 ring tile, the X3W2 ring, the shared-patch 3x3 kernel, rings of
-// four, the fp8 ring of three, register-fed 32 x 32 tiles - DESIGN.md §4, §12; tools/study/retired_r05_forms.patch)
-enum ConvTile { TILE_128x128 = 0, TILE_64x256 = 1, TILE_32x256 = 2, TILE_64x256_SMALLC = 3, TILE_128x256 = 5, TILE_256x256 = 6, TILE_128x128_S3 = 7, TILE_256x256_M16 = 8,
+// (ids 4, 6, 9-11, 14, 17, 25, 26 belonged to retired experiments: a 256x128 ring tile, the 256 x 256 tile on 32x32x16 MFMAs, the X3W2
+// ring, the shared-patch 3x3 kernel, rings of four, the fp8 ring of three, register-fed 32 x 32 tiles - DESIGN.md §4, §9, §12;
+// tools/study/retired_r05_forms.patch)
+enum ConvTile { TILE_128x128 = 0, TILE_64x256 = 1, TILE_32x256 = 2, TILE_64x256_SMALLC = 3, TILE_128x256 = 5, TILE_128x128_S3 = 7, TILE_256x256_M16 = 8,
                 TILE_128x128_M16 = 12, TILE_128x128_S3_M16 = 13, TILE_128x256_M16 = 15, TILE_64x64_S3 = 16, TILE_256x256_FP8 = 20, TILE_128x128_K1 = 21, TILE_64x256_K1 = 22, TILE_128x128_FP8 = 23, TILE_64x64_FP8 = 24,
                 TILE_96x128_K1 = 27 /* the streaming tile for a 96-channel remainder (the shared head's channels 256 .. 351): multi-level form only */ };
 int conv_tile_ch(ConvTile t);
@@ -236,7 +237,6 @@ struct DetectParams {
     const float* priors;  // [P][4]
     int n, P, cells, ldh, C, hp, wp, top_k, max_dets;
     float conf_thresh, nms_thresh;
-    int k1_generic;       // 1: the generic softmax/candidate kernel also for 81 classes (yh_tuning.k1_generic)
     // workspaces
     int* cls_count;       // [n][C-1]
     uint2* cand;          // [n][C-1][P]  {score bits, prior}

@@ -19,14 +19,14 @@ class YhError(RuntimeError):
 
 PRECISION_F16, PRECISION_FP8 = 0, 1
 
-# yh_tuning (include/yolact_hip.h): per-handle measurement / test knobs, -1 = the library's default
-TUNING_FIELDS = ("plan_cus", "mfma16", "t128x256_m16", "small16", "bigk", "tailsplit", "chsplit", "k1tile", "k1_maxk",
-                 "splitk_minsteps", "t64", "t64_maxb", "t64_minsteps", "stemfuse", "prefuse", "headmerge",
-                 "upfuse", "k1_generic", "ablate", "op_tile", "op_kslices", "tfl_dot", "tfl_graph", "tailfork", "dsfuse", "headfork_maxb", "protofuse", "k1_min1", "k1_min3", "chain", "tfl_fuse", "tfl_group")
+# yh_tuning (include/yolact_hip_debug.h): per-handle measurement / test knobs, -1 = the library's default; the reserved
+# slots that follow them are not named here, so tune= cannot set them
+TUNING_FIELDS = ("plan_cus", "chsplit", "upfuse", "ablate", "op_tile", "op_kslices", "tfl_dot", "tfl_graph", "tailfork", "dsfuse",
+                 "headfork_maxb", "protofuse", "chain", "tfl_fuse", "tfl_group")
 
 
 class Tuning(C.Structure):
-    _fields_ = [(f, C.c_int32) for f in TUNING_FIELDS]
+    _fields_ = [(f, C.c_int32) for f in TUNING_FIELDS] + [("reserved", C.c_int32 * 17)]
 
     @classmethod
     def of(cls, **kw):

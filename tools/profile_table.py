@@ -12,7 +12,7 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--top", type=int, default=200)
 ap.add_argument("--backbone", type=int, default=50)
 ap.add_argument("--precision", default="f16", choices=("f16", "fp8"))
-ap.add_argument("--tune", default="", help="comma-separated yh_tuning fields, e.g. tailfork=0,k1tile=0")
+ap.add_argument("--tune", default="", help="comma-separated yh_tuning fields, e.g. tailfork=0,chain=0")
 a = ap.parse_args()
 tune = {k: int(v) for k, v in (kv.split("=") for kv in a.tune.split(",") if kv)}
 eng = ya.Engine(input_size=a.size, backbone=a.backbone, max_batch=a.batch, use_graph=False, tune=tune,
