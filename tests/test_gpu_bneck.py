@@ -119,3 +119,32 @@ def test_layer3_launch_in_fp8_precision_equals_separate_launches(built):
         (da, ma), (db, mb) = f.detections(fr), u.detections(fr)
         assert da == db and np.array_equal(ma, mb), fr
     f.close(); u.close()
+
+
+@pytest.mark.parametrize("n,s,cfg", [
+    (1, S, {}),                                                   # the default plan at batch 1: the small chain tiles
+    (8, S, {}),                                                   # ... at batch 8: layer 3's expand + next-reduce launches too
+    (2, S, {"tune": {"chain": 17 + 2}}),                          # the expand + next-reduce form forced (bit 1)
+    (2, S, {"tune": {"chain": 0}}),                               # every conv a launch (or two) of its own
+    (2, S, {"tune": {"headfork_maxb": 0}}),                       # the head on the main stream: only the tail forks
+    (2, S, {"debug_tensors": True}),                              # every intermediate materialised: no chains, the stem written
+    (2, S, {"precision": 1}),                                     # fp8 precision (ya.PRECISION_FP8)
+    (8, 700, {"precision": 1, "backbone": 101}),                  # ... configs[4]'s share: the expand + next-reduce launch writes E4M3
+])
+def test_profile_entries_are_the_captured_launches(built, n, s, cfg):
+    """yh_profile_run plans each op with plan_op, as the step does: one profile entry per kernel node of the captured step (the
+    side_touch node is the capture's dummy second branch, not work of the step), with and without the detection tail."""
+    import yolact_amd as ya
+    eng = ya.Engine(input_size=s, max_batch=n, use_graph=True, **cfg)
+    eng.load_weights(eng.generate_weights(seed=1))
+    eng.set_input(np.random.default_rng(n).integers(0, 256, (n, s, s, 3), dtype=np.uint8))
+    if cfg.get("precision") == ya.PRECISION_FP8:
+        eng.fp8_calibrate()
+    eng.evaluate()
+    for with_tail in (True, False):
+        names = [p["name"] for p in eng.profile(with_tail=with_tail, reps=1)]
+        kernels = [ln for ln in eng.graph_nodes(with_tail=with_tail).splitlines() if ln.startswith("kernel ") and "side_touch" not in ln]
+        assert len(names) == len(kernels), (with_tail, len(names), len(kernels))
+        for fam in ("bneck_chain_f16", "bneck_xn_f16", "splitk_reduce_f16"):
+            assert sum(nm.startswith(fam) for nm in names) == sum(fam in ln for ln in kernels), (with_tail, fam)
+    eng.close()

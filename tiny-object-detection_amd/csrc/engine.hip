@@ -532,7 +532,7 @@ int build_graph_spec(yh_engine* h) {
             h->ops[blocks[i + 1].a].in_chain = bo.b;
         }
     }
-    // 256-plane identity blocks (layer 3): expand conv + residual + the next block's reduce conv as one launch (xn_active)
+    // 256-plane identity blocks (layer 3): expand conv + residual + the next block's reduce conv as one launch (xn_tile)
     for (size_t i = 0; i + 1 < blocks.size(); ++i) {
         const BlockOps& bo = blocks[i];
         if (!bo.identity || bo.planes != 256 || blocks[i + 1].stage != bo.stage) continue;
@@ -1134,7 +1134,6 @@ int xn_tile(const yh_engine* h, const Op& oc, int n) {
     // launches at batch 64 - is retired: tools/study/retired_r05_forms.patch)
     return 0;
 }
-bool xn_active(const yh_engine* h, const Op& oc, int n) { return xn_tile(h, oc, n) != 0; }
 int fill_xn_params(yh_engine* h, const Op& oc, int n, BneckParams* out) {
     const Op& oa = h->ops[oc.xn_a];
     const Panel &pc = h->panels[oc.panel], &pa = h->panels[oa.panel];
@@ -1157,25 +1156,38 @@ int fill_xn_params(yh_engine* h, const Op& oc, int n, BneckParams* out) {
     return YH_OK;
 }
 
-int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
-    hipError_t e = hipSuccess;
-    if (o.kind == OP_CONV && conv_absorbed(h, o, n)) return YH_OK;
-    if (o.kind == OP_CONV && o.in_chain >= 0 && chain_active(h, h->ops[o.in_chain], n)) return YH_OK;   // runs inside the chain's launch
-    if (o.kind == OP_CONV && o.in_xn >= 0 && xn_active(h, h->ops[o.in_xn], n)) return YH_OK;           // ... inside the previous block's last launch
-    if (o.kind == OP_CONV && xn_active(h, o, n)) {
-        BneckParams bp;
-        const int rc = fill_xn_params(h, o, n, &bp);
-        if (rc) return rc;
-        e = launch_bneck(bp, 256, xn_tile(h, o, n), side ? h->side : h->stream);
-        if (e != hipSuccess) return h->fail(YH_EHIP, "bneck_chain_f16 (no 3x3):" + o.name + ": " + hipGetErrorString(e));
-        return YH_OK;
+// What op `o` becomes at batch n. Decided here only: launch_op issues the plan, the profiler lists and labels the same plan.
+struct OpLaunch {
+    enum Form { SKIP, XN, CHAIN, CONV, OTHER } form;   // SKIP: computed inside another op's launch; OTHER: not a convolution
+    int planes, tile_m;                                // XN, CHAIN: launch_bneck's arguments besides bp
+    BneckParams bp;
+    ConvParams p;                                      // CONV: plan_conv's arguments besides the panel's coutPad
+    ConvTile tile;
+};
+
+int plan_op(yh_engine* h, const Op& o, int n, OpLaunch* out) {
+    out->form = o.kind == OP_CONV ? OpLaunch::SKIP : OpLaunch::OTHER;
+    out->planes = out->tile_m = 0;
+    if (o.kind != OP_CONV || conv_absorbed(h, o, n)) return YH_OK;
+    if (o.in_chain >= 0 && chain_active(h, h->ops[o.in_chain], n)) return YH_OK;   // runs inside the chain's launch
+    if (o.in_xn >= 0 && xn_tile(h, h->ops[o.in_xn], n)) return YH_OK;              // ... inside the previous block's last launch
+    if ((out->tile_m = xn_tile(h, o, n)) != 0) { out->form = OpLaunch::XN; out->planes = 256; return fill_xn_params(h, o, n, &out->bp); }
+    if (chain_active(h, o, n)) {
+        out->form = OpLaunch::CHAIN; out->planes = h->panels[o.panel].cout; out->tile_m = chain_tile_m(h, o, n);
+        return fill_bneck_params(h, o, n, &out->bp);
     }
-    if (o.kind == OP_CONV && chain_active(h, o, n)) {
-        BneckParams bp;
-        const int rc = fill_bneck_params(h, o, n, &bp);
-        if (rc) return rc;
-        e = launch_bneck(bp, h->panels[o.panel].cout, chain_tile_m(h, o, n), side ? h->side : h->stream);
-        if (e != hipSuccess) return h->fail(YH_EHIP, "bneck_chain_f16:" + o.name + ": " + hipGetErrorString(e));
+    out->form = OpLaunch::CONV;
+    return fill_conv_params(h, o, n, &out->p, &out->tile);
+}
+
+int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
+    OpLaunch pl;
+    const int rc = plan_op(h, o, n, &pl);
+    if (rc || pl.form == OpLaunch::SKIP) return rc;
+    hipError_t e = hipSuccess;
+    if (pl.form == OpLaunch::XN || pl.form == OpLaunch::CHAIN) {
+        e = launch_bneck(pl.bp, pl.planes, pl.tile_m, side ? h->side : h->stream);
+        if (e != hipSuccess) return h->fail(YH_EHIP, (pl.form == OpLaunch::XN ? "bneck_chain_f16 (no 3x3):" : "bneck_chain_f16:") + o.name + ": " + hipGetErrorString(e));
         return YH_OK;
     }
     if (side && o.kind != OP_CONV) return h->fail(YH_EINVAL, "only convolutions fork onto the side stream");
@@ -1183,15 +1195,10 @@ int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
         case OP_PRE:
             e = launch_preprocess(h->in_u8(), h->in_f16.d, n, h->S, h->in_hp, h->in_hp, h->stream);
             break;
-        case OP_CONV: {
-            ConvParams p;
-            ConvTile tile;
-            int rc = fill_conv_params(h, o, n, &p, &tile);
-            if (rc) return rc;
-            if (side && p.partial) p.partial = h->splitk_ws_side;
-            e = launch_conv_planned(h->tune, p, tile, h->panels[o.panel].coutPad, side ? h->side : h->stream);
+        case OP_CONV:
+            if (side && pl.p.partial) pl.p.partial = h->splitk_ws_side;
+            e = launch_conv_planned(h->tune, pl.p, pl.tile, h->panels[o.panel].coutPad, side ? h->side : h->stream);
             break;
-        }
         case OP_POOL:
             e = launch_maxpool3x3s2(o.in.d, o.out.d, n, o.in.h, o.in.w, o.in.c, o.P, o.Q, h->stream);
             break;
@@ -2282,6 +2289,56 @@ int ensure_compat(yh_engine* h, int n_tiles) {
     return YH_OK;
 }
 
+// The device buffers of one single-op call: allocated (and filled - 0 behind a zero-padded input, 0xFF, the NaN pattern an
+// unwritten element shows, in an output) and uploaded in the order the call asks for them, freed when the call returns.
+// The first HIP error is kept and every step after it is skipped.
+struct OpStaging {
+    hipError_t e = hipSuccess;
+    std::vector<void*> bufs;
+    OpStaging() = default;
+    OpStaging(const OpStaging&) = delete;
+    ~OpStaging() { for (void* d : bufs) hipFree(d); }
+    bool ok() const { return e == hipSuccess; }
+    template <class T> T* alloc(size_t bytes, int fill = -1) {
+        void* d = nullptr;
+        if (ok() && (e = hipMalloc(&d, bytes)) == hipSuccess) bufs.push_back(d);
+        if (ok() && fill >= 0) e = hipMemset(d, fill, bytes);
+        return ok() ? (T*)d : nullptr;
+    }
+    void put(const void* d, const void* src, size_t bytes) { if (ok()) e = hipMemcpy((void*)d, src, bytes, hipMemcpyHostToDevice); }
+    template <class T> T* upload(const void* src, size_t bytes) { T* d = alloc<T>(bytes); put(d, src, bytes); return d; }
+    // a conv input with its zero pixel behind the data: `cap` zeroed bytes, the data first; *zero_off = where the zeros start
+    template <class T> T* upload_padded(const void* src, size_t bytes, size_t cap, unsigned* zero_off) {
+        *zero_off = (unsigned)pad16(bytes);
+        T* d = alloc<T>(cap, 0);
+        put(d, src, bytes);
+        return d;
+    }
+    void sync(hipStream_t s) { if (ok()) e = hipStreamSynchronize(s); }
+    void get(void* dst, const void* d, size_t bytes) { if (ok()) e = hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost); }
+    int status(yh_engine* h, const char* what) const { return ok() ? YH_OK : h->fail(YH_EHIP, std::string(what) + hipGetErrorString(e)); }
+};
+
+// rows of c values, zero-padded to rows of ld (input channels to the stored count, output channels to cout8) - and back
+template <class T> std::vector<T> pad_rows(const T* src, size_t rows, size_t c, size_t ld) {
+    std::vector<T> v(rows * ld, T(0));
+    for (size_t m = 0; m < rows; ++m) memcpy(&v[m * ld], &src[m * c], c * sizeof(T));
+    return v;
+}
+void unpad_rows(uint16_t* dst, const std::vector<uint16_t>& src, size_t rows, size_t c, size_t ld) {
+    for (size_t m = 0; m < rows; ++m) memcpy(&dst[m * c], &src[m * ld], c * 2);
+}
+
+// test hook (tune.op_kslices): a forced split-K of a single-op launch (the engine decides it in fill_conv_params)
+void force_split_k(yh_engine* h, ConvParams& p, size_t M, int coutPad) {
+    const int ksl = h->tune.op_kslices;
+    if (ksl < 2 || ksl > p.ksteps || (size_t)ksl * M * coutPad * 4 > yh_engine::kSplitKBytes) return;
+    p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
+    p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
+    p.partial_ld = coutPad;
+    p.partial = h->splitk_ws;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2557,29 +2614,23 @@ int yh_debug_graph_nodes(yh_engine* h, int32_t with_tail, char* out, size_t cap)
 // One profile entry per KERNEL launch (so that the averages agree with rocprofv3's per-kernel stats):
 // a conv op planned as two launches (wave-quantisation tail, channel split, split-K + reduce) gives
 // two entries, its algorithmic FLOPs and bytes shared out by the rows / channels each launch covers.
-struct ProfEntry { int op; int stage; KLaunch k; bool is_conv; };
+// The entries follow plan_op: a SKIP op has none (it is accounted with the launch that computes it), a CONV op one per
+// plan_conv launch, every other op one (launched through launch_op).
+struct ProfEntry { int op; int stage; OpLaunch::Form form; int tile_m; KLaunch k; };
 
 static int build_profile_entries(yh_engine* h, int n, int with_tail, std::vector<ProfEntry>* out) {
     out->clear();
     for (int i = 0; i < (int)h->ops.size(); ++i) {
-        const Op& o = h->ops[i];
-        if (o.kind != OP_CONV) { ProfEntry e{}; e.op = i; e.stage = -1; e.is_conv = false; out->push_back(e); continue; }
-        if (conv_absorbed(h, o, n)) continue;   // (accounted with the launch that computes it)
-        if (o.in_chain >= 0 && chain_active(h, h->ops[o.in_chain], n)) continue;
-        if (chain_active(h, o, n)) { ProfEntry e{}; e.op = i; e.stage = -1; e.is_conv = false; out->push_back(e); continue; }   // one launch: launch_op
-        if (o.in_xn >= 0 && xn_active(h, h->ops[o.in_xn], n)) continue;
-        if (xn_active(h, o, n)) { ProfEntry e{}; e.op = i; e.stage = -1; e.is_conv = false; out->push_back(e); continue; }
-        ConvParams p;
-        ConvTile tile;
-        const int rc = fill_conv_params(h, o, n, &p, &tile);
+        OpLaunch pl;
+        const int rc = plan_op(h, h->ops[i], n, &pl);
         if (rc) return rc;
-        const Panel& pn = h->panels[o.panel];
-        KLaunch k[3];
-        const int nk = plan_conv(h->tune, p, tile, pn.coutPad, k);
-        for (int j = 0; j < nk; ++j) { ProfEntry e{}; e.op = i; e.stage = -1; e.k = k[j]; e.is_conv = true; out->push_back(e); }
+        KLaunch k[3] = {};
+        const int nk = pl.form == OpLaunch::CONV ? plan_conv(h->tune, pl.p, pl.tile, h->panels[h->ops[i].panel].coutPad, k)
+                                                  : (pl.form == OpLaunch::SKIP ? 0 : 1);
+        for (int j = 0; j < nk; ++j) out->push_back(ProfEntry{ i, -1, pl.form, pl.tile_m, k[j] });
     }
     if (with_tail)
-        for (int st = 0; st < detect_launch_count(); ++st) { ProfEntry e{}; e.op = -1; e.stage = st; e.is_conv = false; out->push_back(e); }
+        for (int st = 0; st < detect_launch_count(); ++st) out->push_back(ProfEntry{ -1, st, OpLaunch::OTHER, 0, KLaunch{} });
     return YH_OK;
 }
 
@@ -2610,7 +2661,7 @@ int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, dou
         for (int i = 0; i < nl && rc == YH_OK; ++i) {
             const ProfEntry& pe = ent[i];
             hipEventRecord(ev[2 * i], h->stream);
-            if (pe.is_conv) { if (launch_k(pe.k, h->stream) != hipSuccess) rc = h->fail(YH_EHIP, "conv launch failed in profile run"); }
+            if (pe.form == OpLaunch::CONV) { if (launch_k(pe.k, h->stream) != hipSuccess) rc = h->fail(YH_EHIP, "conv launch failed in profile run"); }
             else if (pe.op >= 0) rc = launch_op(h, h->ops[pe.op], n);
             else if (launch_detect_stage(h->det, pe.stage, h->stream) != hipSuccess) rc = h->fail(YH_EHIP, "detect stage launch failed");
             hipEventRecord(ev[2 * i + 1], h->stream);
@@ -2632,13 +2683,13 @@ int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, dou
         double fl = 0.0, by = 0.0;
         if (pe.op >= 0) {
             const Op& o = h->ops[pe.op];
-            const double frac = pe.is_conv ? pe.k.frac : 1.0;
+            const double frac = pe.form == OpLaunch::CONV ? pe.k.frac : 1.0;
             fl = o.flops_per_img * n * frac;
             by = (o.bytes_per_img * n + o.bytes_fixed) * frac;
-            if (pe.is_conv && pe.k.reduce) {
+            if (pe.form == OpLaunch::CONV && pe.k.reduce) {
                 h->prof_labels[i] = "splitk_reduce_f16:" + o.name;
                 by = (double)pe.k.p.M * pe.k.p.partial_ld * 4.0 * pe.k.p.k_slices + (double)pe.k.p.M * pe.k.p.cout8 * 2.0;
-            } else if (pe.is_conv) {
+            } else if (pe.form == OpLaunch::CONV) {
                 // (kernel symbols of their own in rocprofv3's stats: multi-level, fused 1x1 tail, the streaming tile's 3x3 form)
                 const bool k3 = pe.k.tile == TILE_128x128_K1 && pe.k.p.R == 3 && pe.k.p.S == 3 && pe.k.p.nlev == 0 && !pe.k.p.res_up && !pe.k.p.x2;
                 h->prof_labels[i] = std::string(conv_tile_symbol(pe.k.tile)) + (pe.k.p.nlev > 0 ? "[ml]" : "") + (pe.k.p.w2 ? "[+1x1]" : "") + (k3 ? "[3x3]" : "") + ":" + o.name + pe.k.what;
@@ -2648,19 +2699,19 @@ int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, dou
                     fl += t.flops_per_img * n;
                     by += t.bytes_fixed + 2.0 * n * ((double)t.P * t.Q * h->panels[t.panel].cout - (double)o.P * o.Q * h->panels[o.panel].cout * (h->fp8_active && !o.write_f16 ? 0.0 : 1.0));
                 }
-            } else if (o.kind == OP_CONV && xn_active(h, o, n)) {
+            } else if (pe.form == OpLaunch::XN) {
                 // expand conv + next reduce conv: both convolutions' FLOPs; HBM bytes = b + residual in, y + a' out, the weights
                 const Op& oa = h->ops[o.xn_a];
                 const double px = (double)n * o.P * o.Q;
-                h->prof_labels[i] = std::string(bneck_symbol(256, xn_tile(h, o, n), true, false)) + ":" + o.name + "+" + oa.name;
+                h->prof_labels[i] = std::string(bneck_symbol(256, pe.tile_m, true, false)) + ":" + o.name + "+" + oa.name;
                 fl += oa.flops_per_img * n;
                 by = 2.0 * px * (256.0 + 1024.0 + 1024.0) + px * 256.0 * ((oa.write_f16 || !h->fp8_active ? 2.0 : 0.0) + (h->fp8_active && oa.write_q ? 1.0 : 0.0)) + o.bytes_fixed + oa.bytes_fixed;
-            } else if (o.kind == OP_CONV && chain_active(h, o, n)) {
+            } else if (pe.form == OpLaunch::CHAIN) {
                 // a bottleneck chain: the FLOPs of its two or three convolutions; HBM bytes = a + residual in, y (+ a') out, the weights
                 const Op& oc = h->ops[o.chain_c];
                 const int planes = h->panels[o.panel].cout;
                 const double px = (double)n * o.P * o.Q;
-                h->prof_labels[i] = std::string(bneck_symbol(planes, chain_tile_m(h, o, n), o.chain_a >= 0, oc.dual)) + ":" + o.name + "+" + oc.name;
+                h->prof_labels[i] = std::string(bneck_symbol(planes, pe.tile_m, o.chain_a >= 0, oc.dual)) + ":" + o.name + "+" + oc.name;
                 fl += oc.flops_per_img * n;
                 by = 2.0 * ((double)n * o.in.h * o.in.w * planes + px * 4.0 * planes * (oc.dual ? 1.0 : 2.0) + (oc.dual ? px * oc.in2.c : 0.0)) + o.bytes_fixed + oc.bytes_fixed;
                 if (o.chain_a >= 0) {
@@ -2690,6 +2741,7 @@ int yh_time_steps(yh_engine* h, int32_t with_tail, int32_t steps, float* ms_tota
 }
 
 // ---- single-op entry points (tests) ------------------------------------------------------------
+// Each one reads: validate, stage (host-side repacking, then the device buffers), fill the kernel's parameters, launch, read back.
 static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
                           const float* bias, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
                           const uint16_t* residual, int32_t act, uint16_t* y, const int32_t* level_sizes, int32_t nlev) {
@@ -2708,63 +2760,45 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     if (h->tune.op_tile >= 0 && cin != 3) tile = (ConvTile)h->tune.op_tile;   // test hook: force a tile variant
     if (conv_tile_ch(tile) == 0) return h->fail(YH_EINVAL, "conv op: tune.op_tile is not a tile id");
     const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);
+    const size_t M = (size_t)n * P * Q;
     // host-side staging: pad input channels, repack weights, pad output rows to cout8
-    std::vector<uint16_t> xs((size_t)n * hh * ww * cs, 0), wp((size_t)coutPad * Kpad, 0);
-    for (size_t i = 0; i < (size_t)n * hh * ww; ++i) memcpy(&xs[i * cs], &x[i * cin], (size_t)cin * 2);
+    const std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
+    std::vector<uint16_t> wp((size_t)coutPad * Kpad, 0), rs, ys(M * cout8);
     for (int o = 0; o < cout; ++o)
         for (int t = 0; t < k * k; ++t) memcpy(&wp[(size_t)o * Kpad + (size_t)t * cs], &w[((size_t)o * k * k + t) * cin], (size_t)cin * 2);
-    std::vector<float> bp(coutPad, 0.0f);
-    memcpy(bp.data(), bias, (size_t)cout * 4);
-    const size_t M = (size_t)n * P * Q;
-    std::vector<uint16_t> rs, ys(M * cout8);
-    if (residual) { rs.assign(M * cout8, 0); for (size_t m = 0; m < M; ++m) memcpy(&rs[m * cout8], &residual[m * cout], (size_t)cout * 2); }
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    if (residual) rs = pad_rows(residual, M, cout, cout8);
     std::vector<int2> tab;
     if (cin == 3) { tab.resize(Kpad / 8); for (int i = 0; i < Kpad / 8; ++i) tab[i] = i < k * k ? make_int2(i / k, i % k) : make_int2(1 << 20, 0); }
-    void *dx = nullptr, *dw = nullptr, *db = nullptr, *dy = nullptr, *dr = nullptr, *dt = nullptr;
-    hipError_t e = hipMalloc(&dx, xs.size() * 2 + 64);
-    if (e == hipSuccess) e = hipMemset(dx, 0, xs.size() * 2 + 64);
-    if (e == hipSuccess) e = hipMalloc(&dw, wp.size() * 2);
-    if (e == hipSuccess) e = hipMalloc(&db, bp.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&dy, ys.size() * 2);
-    if (e == hipSuccess && residual) e = hipMalloc(&dr, rs.size() * 2);
-    if (e == hipSuccess && cin == 3) e = hipMalloc(&dt, tab.size() * sizeof(int2));
-    if (e == hipSuccess) e = hipMemcpy(dx, xs.data(), xs.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && residual) e = hipMemcpy(dr, rs.data(), rs.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess && cin == 3) e = hipMemcpy(dt, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dy, 0xFF, ys.size() * 2);
-    if (e == hipSuccess) {
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(xs.data(), xs.size() * 2, xs.size() * 2 + 64, &zo);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
+    const int2* dt = cin == 3 ? st.upload<int2>(tab.data(), tab.size() * sizeof(int2)) : nullptr;
+    if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
-        p.x = (const half_t*)dx; p.w = (const half_t*)dw; p.bias = (const float*)db; p.res = (const half_t*)dr; p.y = (half_t*)dy;
-        p.rs_table = (const int2*)dt;
+        p.x = dx; p.w = dw; p.bias = db; p.res = dr; p.y = dy; p.rs_table = dt;
         p.x_img_stride = (long long)hh * ww * cs; p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
-        p.x_zero_off = (unsigned)((xs.size() * 2 + 15) & ~(size_t)15);
-        p.x_bytes = p.x_zero_off + 16u;
+        p.x_zero_off = zo; p.x_bytes = zo + 16u;
         p.w_bytes = (unsigned)(wp.size() * 2);
         p.N = n; p.H = hh; p.W = ww; p.C = cs; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
         p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad; p.ksteps = Kpad / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
         p.act = act == 1 ? 1 : 0; p.tanh_from = act == 2 ? 0 : INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile);
         if (nlev > 0) {
             p.nlev = nlev;
-            for (int l = 0, st = 0; l < nlev; ++l) { p.lev_start[l] = st; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; st += level_sizes[l] * level_sizes[l]; }
+            for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
         }
-        // test hook: a forced split-K (the engine decides it in fill_conv_params)
-        const int ksl = h->tune.op_kslices;
-        if (ksl > 1 && ksl <= p.ksteps && (size_t)ksl * M * coutPad * 4 <= yh_engine::kSplitKBytes) {
-            p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
-            p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
-            p.partial_ld = coutPad;
-            p.partial = h->splitk_ws;
-        }
-        e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        force_split_k(h, p, M, coutPad);
+        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
     }
-    if (e == hipSuccess) e = hipMemcpy(ys.data(), dy, ys.size() * 2, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dw); hipFree(db); hipFree(dy); if (dr) hipFree(dr); if (dt) hipFree(dt);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("conv op: ") + hipGetErrorString(e));
-    for (size_t m = 0; m < M; ++m) memcpy(&y[m * cout], &ys[m * cout8], (size_t)cout * 2);
+    st.sync(h->stream);
+    st.get(ys.data(), dy, ys.size() * 2);
+    if (const int rc = st.status(h, "conv op: ")) return rc;
+    unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
 }
 
@@ -2787,50 +2821,34 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
     if (conv_tile_ch(tile) == 0 || dual_conv_tile(tile) != tile) return h->fail(YH_EINVAL, "dual conv op: tune.op_tile is not a tile of the two-source form");
     const int K = c1 + c2, coutPad = round_up(cout, conv_tile_ch(tile));
     const size_t M = (size_t)n * ho * wo, n1 = M * c1, n2 = (size_t)n * h2 * w2 * c2;
-    std::vector<uint16_t> wp((size_t)coutPad * K, 0);
-    memcpy(wp.data(), w, (size_t)cout * K * 2);
-    std::vector<float> bp(coutPad, 0.0f);
-    memcpy(bp.data(), bias, (size_t)cout * 4);
-    void *d1 = nullptr, *d2 = nullptr, *dw = nullptr, *db = nullptr, *dy = nullptr;
-    hipError_t e = hipMalloc(&d1, n1 * 2 + 64);
-    if (e == hipSuccess) e = hipMemset(d1, 0, n1 * 2 + 64);
-    if (e == hipSuccess) e = hipMalloc(&d2, n2 * 2 + 64);
-    if (e == hipSuccess) e = hipMemset(d2, 0, n2 * 2 + 64);
-    if (e == hipSuccess) e = hipMalloc(&dw, wp.size() * 2);
-    if (e == hipSuccess) e = hipMalloc(&db, bp.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&dy, M * cout * 2);
-    if (e == hipSuccess) e = hipMemcpy(d1, x1, n1 * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d2, x2, n2 * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dy, 0xFF, M * cout * 2);
-    if (e == hipSuccess) {
+    const std::vector<uint16_t> wp = pad_rows(w, 1, (size_t)cout * K, (size_t)coutPad * K);
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    OpStaging st;
+    unsigned z1 = 0, z2 = 0;
+    const half_t* d1 = st.upload_padded<half_t>(x1, n1 * 2, n1 * 2 + 64, &z1);
+    const half_t* d2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    half_t* dy = st.alloc<half_t>(M * cout * 2, 0xFF);
+    if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
-        p.x = (const half_t*)d1; p.w = (const half_t*)dw; p.bias = (const float*)db; p.y = (half_t*)dy;
+        p.x = d1; p.w = dw; p.bias = db; p.y = dy;
         p.x_img_stride = (long long)ho * wo * c1; p.y_img_stride = (long long)ho * wo * cout;
-        p.x_zero_off = (unsigned)((n1 * 2 + 15) & ~(size_t)15); p.x_bytes = p.x_zero_off + 16u;
-        p.x2 = (const half_t*)d2; p.x2_img_stride = (long long)h2 * w2 * c2;
-        p.x2_zero_off = (unsigned)((n2 * 2 + 15) & ~(size_t)15); p.x2_bytes = p.x2_zero_off + 16u;
+        p.x_zero_off = z1; p.x_bytes = z1 + 16u;
+        p.x2 = d2; p.x2_img_stride = (long long)h2 * w2 * c2;
+        p.x2_zero_off = z2; p.x2_bytes = z2 + 16u;
         p.W2 = w2; p.C2 = c2; p.stride2 = stride2; p.k1steps = c1 / 64;
         p.w_bytes = (unsigned)(wp.size() * 2);
         p.N = n; p.H = ho; p.W = wo; p.C = c1; p.P = ho; p.Q = wo; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
         p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
-        const int ksl = h->tune.op_kslices;   // test hook: a forced split-K
-        if (ksl > 1 && ksl <= p.ksteps && (size_t)ksl * M * coutPad * 4 <= yh_engine::kSplitKBytes && (tile == TILE_128x128_S3 || tile == TILE_64x64_S3)) {
-            p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
-            p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
-            p.partial_ld = coutPad;
-            p.partial = h->splitk_ws;
-        }
-        e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (tile == TILE_128x128_S3 || tile == TILE_64x64_S3) force_split_k(h, p, M, coutPad);   // (the two-source tiles that split K)
+        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
     }
-    if (e == hipSuccess) e = hipMemcpy(y, dy, M * cout * 2, hipMemcpyDeviceToHost);
-    hipFree(d1); hipFree(d2); hipFree(dw); hipFree(db); hipFree(dy);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("dual conv op: ") + hipGetErrorString(e));
-    return YH_OK;
+    st.sync(h->stream);
+    st.get(y, dy, M * cout * 2);
+    return st.status(h, "dual conv op: ");
 }
 
 int yh_op_conv2d_levels_f16(yh_engine* h, const uint16_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
@@ -2845,16 +2863,13 @@ int yh_op_bilinear_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, i
     if (!h || !x || !y || c % 8 != 0 || n < 1) return YH_EINVAL;
     HIPCHK(h, hipSetDevice(h->dev));
     const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
-    void *dx = nullptr, *dy = nullptr;
-    hipError_t e = hipMalloc(&dx, ni * 2);
-    if (e == hipSuccess) e = hipMalloc(&dy, no * 2);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, ni * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_bilinear((const half_t*)dx, (half_t*)dy, n, hh, ww, c, ho, wo, (long long)hh * ww * c, (long long)ho * wo * c, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, no * 2, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dy);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("bilinear op: ") + hipGetErrorString(e));
-    return YH_OK;
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, ni * 2);
+    half_t* dy = st.alloc<half_t>(no * 2);
+    if (st.ok()) st.e = launch_bilinear(dx, dy, n, hh, ww, c, ho, wo, (long long)hh * ww * c, (long long)ho * wo * c, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, no * 2);
+    return st.status(h, "bilinear op: ");
 }
 
 int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, uint16_t* y) {
@@ -2862,16 +2877,13 @@ int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t h
     HIPCHK(h, hipSetDevice(h->dev));
     const int ho = out_dim(hh, 3, 2, 1), wo = out_dim(ww, 3, 2, 1);
     const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
-    void *dx = nullptr, *dy = nullptr;
-    hipError_t e = hipMalloc(&dx, ni * 2);
-    if (e == hipSuccess) e = hipMalloc(&dy, no * 2);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, ni * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_maxpool3x3s2((const half_t*)dx, (half_t*)dy, n, hh, ww, c, ho, wo, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, no * 2, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dy);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("maxpool op: ") + hipGetErrorString(e));
-    return YH_OK;
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, ni * 2);
+    half_t* dy = st.alloc<half_t>(no * 2);
+    if (st.ok()) st.e = launch_maxpool3x3s2(dx, dy, n, hh, ww, c, ho, wo, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, no * 2);
+    return st.status(h, "maxpool op: ");
 }
 
 static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
@@ -2891,34 +2903,27 @@ static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb
             for (int sx = 0; sx < 7; ++sx)
                 for (int c = 0; c < 3; ++c) wp[(size_t)o * 256 + r * 32 + sx * 4 + c] = w[(((size_t)o * 7 + r) * 7 + sx) * 3 + c];
     const size_t ns = (size_t)n * SO * SO * 64, np = (size_t)n * PO * PO * 64;
-    void *dx = nullptr, *dw = nullptr, *db = nullptr, *ds = nullptr, *dp = nullptr, *drgb = nullptr;
-    hipError_t e = hipMalloc(&dx, xs.size() * 2);
-    if (e == hipSuccess && rgb) e = hipMalloc(&drgb, (size_t)n * S * S * 3);
-    if (e == hipSuccess && rgb) e = hipMemcpy(drgb, rgb, (size_t)n * S * S * 3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&dw, wp.size() * 2);
-    if (e == hipSuccess) e = hipMalloc(&db, 64 * 4);
-    if (e == hipSuccess) e = hipMalloc(&ds, ns * 2);
-    if (e == hipSuccess) e = hipMalloc(&dp, np * 2);
-    if (e == hipSuccess) e = hipMemcpy(dx, xs.data(), xs.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, bias, 64 * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(ds, 0xFF, ns * 2);   // NaN pattern: an unwritten stem pixel shows
-    if (e == hipSuccess) e = hipMemset(dp, 0xFF, np * 2);
-    if (e == hipSuccess) {
+    OpStaging st;
+    const half_t* dx = st.alloc<half_t>(xs.size() * 2);
+    const uint8_t* drgb = rgb ? st.upload<uint8_t>(rgb, (size_t)n * S * S * 3) : nullptr;
+    st.put(dx, xs.data(), xs.size() * 2);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bias, 64 * 4);
+    half_t* ds = st.alloc<half_t>(ns * 2, 0xFF);
+    half_t* dp = st.alloc<half_t>(np * 2, 0xFF);
+    if (st.ok()) {
         StemPoolParams sp;
-        sp.x = (const half_t*)dx; sp.w = (const half_t*)dw; sp.bias = (const float*)db; sp.pool = (half_t*)dp;
-        sp.rgb = (const uint8_t*)drgb; sp.S = S;
-        sp.stem = stem_out ? (half_t*)ds : nullptr;
+        sp.x = dx; sp.w = dw; sp.bias = db; sp.pool = dp;
+        sp.rgb = drgb; sp.S = S;
+        sp.stem = stem_out ? ds : nullptr;
         sp.n = n; sp.Hp = Hp; sp.Wp = Hp; sp.SO = SO; sp.PO = PO; sp.tiles_y = (PO + 7) / 8; sp.tiles_x = (PO + 7) / 8;
         sp.x_img_stride = (long long)Hp * Hp * 4; sp.pool_img_stride = (long long)PO * PO * 64; sp.stem_img_stride = (long long)SO * SO * 64;
-        e = launch_stem_pool(sp, h->stream);
+        st.e = launch_stem_pool(sp, h->stream);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess && stem_out) e = hipMemcpy(stem_out, ds, ns * 2, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(pool_out, dp, np * 2, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dw); hipFree(db); hipFree(ds); hipFree(dp); if (drgb) hipFree(drgb);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("stem+pool op: ") + hipGetErrorString(e));
-    return YH_OK;
+    st.sync(h->stream);
+    if (stem_out) st.get(stem_out, ds, ns * 2);
+    st.get(pool_out, dp, np * 2);
+    return st.status(h, "stem+pool op: ");
 }
 
 int yh_op_stem_pool_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t S, const uint16_t* w, const float* bias,
@@ -2942,69 +2947,55 @@ int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int3
     if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "fp8 conv op: empty output");
     const int Kpad = k * k * cin, coutPad = round_up(cout, 256), cout8 = round_up(cout, 8);
     const size_t M = (size_t)n * P * Q, xbytes = (size_t)n * hh * ww * cin;
-    std::vector<uint8_t> wp((size_t)coutPad * Kpad, 0);
-    memcpy(wp.data(), w, (size_t)cout * Kpad);                       // [cout][k][k][cin] is already the panel's K order
-    std::vector<float> bp(coutPad, 0.0f), sp(coutPad, 0.0f);
-    memcpy(bp.data(), bias, (size_t)cout * 4); memcpy(sp.data(), scale, (size_t)cout * 4);
+    const std::vector<uint8_t> wp = pad_rows(w, 1, (size_t)cout * Kpad, (size_t)coutPad * Kpad);   // [cout][k][k][cin] is already the panel's K order
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad), sp = pad_rows(scale, 1, cout, coutPad);
     std::vector<uint16_t> rs, ys(M * cout8);
-    if (residual) { rs.assign(M * cout8, 0); for (size_t m = 0; m < M; ++m) memcpy(&rs[m * cout8], &residual[m * cout], (size_t)cout * 2); }
-    void *dx = nullptr, *dw = nullptr, *db = nullptr, *dsc = nullptr, *dy = nullptr, *dr = nullptr;
-    const size_t zero_off = (xbytes + 15) & ~(size_t)15;
-    hipError_t e = hipMalloc(&dx, zero_off + 64);
-    if (e == hipSuccess) e = hipMemset(dx, 0, zero_off + 64);
-    if (e == hipSuccess) e = hipMalloc(&dw, wp.size());
-    if (e == hipSuccess) e = hipMalloc(&db, bp.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&dsc, sp.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&dy, ys.size() * 2);
-    if (e == hipSuccess && residual) e = hipMalloc(&dr, rs.size() * 2);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, xbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dw, wp.data(), wp.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dsc, sp.data(), sp.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && residual) e = hipMemcpy(dr, rs.data(), rs.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dy, 0xFF, ys.size() * 2);
-    if (e == hipSuccess) {
+    if (residual) rs = pad_rows(residual, M, cout, cout8);
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size());
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    const float* dsc = st.upload<float>(sp.data(), sp.size() * 4);
+    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
+    if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
-        p.x = (const half_t*)dx; p.w = (const half_t*)dw; p.bias = (const float*)db; p.scale = (const float*)dsc;
-        p.res = (const half_t*)dr; p.y = (half_t*)dy;
+        p.x = dx; p.w = dw; p.bias = db; p.scale = dsc; p.res = dr; p.y = dy;
         // the loader's units are 2 bytes: two fp8 values
         p.x_img_stride = (long long)hh * ww * (cin / 2); p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
-        p.x_zero_off = (unsigned)zero_off; p.x_bytes = p.x_zero_off + 16u; p.w_bytes = (unsigned)wp.size();
+        p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)wp.size();
         p.N = n; p.H = hh; p.W = ww; p.C = cin / 2; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
         p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad / 2; p.ksteps = Kpad / 128; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / 256; p.k_slices = 1;
-        e = launch_conv(p, TILE_256x256_FP8, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
+        st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+        st.sync(h->stream);
+        if (st.ok() && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
             hipEventRecord(h->ev0, h->stream);
-            for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_conv(p, TILE_256x256_FP8, h->stream);
+            for (int r = 0; r < reps && st.ok(); ++r) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
             hipEventRecord(h->ev1, h->stream);
-            if (e == hipSuccess) e = hipEventSynchronize(h->ev1);
+            if (st.ok()) st.e = hipEventSynchronize(h->ev1);
             float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
             *ms_per_launch = ms / reps;
         }
     }
-    if (e == hipSuccess) e = hipMemcpy(ys.data(), dy, ys.size() * 2, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dw); hipFree(db); hipFree(dsc); hipFree(dy); if (dr) hipFree(dr);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("fp8 conv op: ") + hipGetErrorString(e));
-    for (size_t m = 0; m < M; ++m) memcpy(&y[m * cout], &ys[m * cout8], (size_t)cout * 2);
+    st.get(ys.data(), dy, ys.size() * 2);
+    if (const int rc = st.status(h, "fp8 conv op: ")) return rc;
+    unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
 }
 
 int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_scale, uint8_t* y) {
     if (!h || !x || !y || n < 1) return YH_EINVAL;
     HIPCHK(h, hipSetDevice(h->dev));
-    void *dx = nullptr, *dy = nullptr;
-    hipError_t e = hipMalloc(&dx, n * 2);
-    if (e == hipSuccess) e = hipMalloc(&dy, n);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, n * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_quantize_e4m3((const half_t*)dx, (uint8_t*)dy, (long long)n, inv_scale, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(y, dy, n, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dy);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("quantize op: ") + hipGetErrorString(e));
-    return YH_OK;
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, n * 2);
+    uint8_t* dy = st.alloc<uint8_t>(n);
+    if (st.ok()) st.e = launch_quantize_e4m3(dx, dy, (long long)n, inv_scale, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, n);
+    return st.status(h, "quantize op: ");
 }
 
 int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask, const uint16_t* proto, int32_t n) {
