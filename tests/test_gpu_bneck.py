@@ -5,6 +5,9 @@ are CONV_2D, CONV_2D + ADD, CONV_2D of the op histogram (data/FRC_model_edgetpu.
 The fused launch is bit-transparent by construction (same MFMA products in the same order, same f32 epilogue operations,
 intermediates rounded where the separate launches store them), so the bar is exact equality with the unfused engine
 (chain = 0) on every tensor both write, on the heads and on the detections - for every tile variant."""
+import re
+from collections import Counter
+
 import numpy as np
 import pytest
 
@@ -121,6 +124,25 @@ def test_layer3_launch_in_fp8_precision_equals_separate_launches(built):
     f.close(); u.close()
 
 
+# A conv launch as (TCH, TM, WCH, WM, SMALLC, STAGES, MT, FP8, ML, TAIL, K3, SPLITK), read from its profile label ...
+def _conv_of_label(name):
+    sym, op = name.split(":", 1)
+    kind, args = sym.split("[")[0].rstrip(">").split("<")
+    a = args.split(",")
+    if kind == "conv_igemm_fp8":   # <TCH,TM,WCH,WM>: the fp8 tiles are 2-stage, 16x16x32
+        base = [int(v) for v in a] + [0, 2, 16, 1]
+    else:                          # <TCH,TM,WCH,WM,SMALLC,STAGES[,mfma16]>
+        base = [int(v) for v in a[:6]] + [16 if "mfma16" in a[6:] else 32, 0]
+    return tuple(base) + (int("[ml]" in sym), int("[+1x1]" in sym), int("[3x3]" in sym), int(op.endswith("/splitk")))
+
+
+# ... and from the mangled kernel symbol of its graph node: the 15 template arguments of conv_igemm_f16, in order
+def _conv_of_node(line):
+    tch, tm, wch, wm, smallc, stages, epi, splitk, mt, ml, fp8, resup, dual, tail, k3 = (
+        int(v) for v in re.findall(r"L[ib](\d+)E", re.search(r"_ZN2yh14conv_igemm_f16I\S*", line).group(0)))
+    return (tch, tm, wch, wm, smallc, stages, mt, fp8, ml, tail, k3, splitk)
+
+
 @pytest.mark.parametrize("n,s,cfg", [
     (1, S, {}),                                                   # the default plan at batch 1: the small chain tiles
     (8, S, {}),                                                   # ... at batch 8: layer 3's expand + next-reduce launches too
@@ -133,7 +155,8 @@ def test_layer3_launch_in_fp8_precision_equals_separate_launches(built):
 ])
 def test_profile_entries_are_the_captured_launches(built, n, s, cfg):
     """yh_profile_run plans each op with plan_op, as the step does: one profile entry per kernel node of the captured step (the
-    side_touch node is the capture's dummy second branch, not work of the step), with and without the detection tail."""
+    side_touch node is the capture's dummy second branch, not work of the step), with and without the detection tail. Each conv
+    entry's label names the kernel launch_conv picked for it: its tile, form ([ml], [+1x1], [3x3], /splitk) and template flags."""
     import yolact_amd as ya
     eng = ya.Engine(input_size=s, max_batch=n, use_graph=True, **cfg)
     eng.load_weights(eng.generate_weights(seed=1))
@@ -147,4 +170,7 @@ def test_profile_entries_are_the_captured_launches(built, n, s, cfg):
         assert len(names) == len(kernels), (with_tail, len(names), len(kernels))
         for fam in ("bneck_chain_f16", "bneck_xn_f16", "splitk_reduce_f16"):
             assert sum(nm.startswith(fam) for nm in names) == sum(fam in ln for ln in kernels), (with_tail, fam)
+        labels = Counter(_conv_of_label(nm) for nm in names if nm.startswith("conv_igemm_"))
+        nodes = Counter(_conv_of_node(ln) for ln in kernels if "conv_igemm_f16" in ln)
+        assert labels == nodes, (with_tail, labels - nodes, nodes - labels)
     eng.close()

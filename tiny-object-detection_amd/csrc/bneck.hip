@@ -590,46 +590,50 @@ __global__ __launch_bounds__(512, 1) void bneck_xn_f16(const BneckParams p) {
     }
 }
 
-const char* bneck_symbol(int planes, int tm, bool next, bool dual) {
-    if (planes == 256) return "bneck_xn_f16";
-    if (dual) return "bneck_chain_f16<64,128,next,dual>";
-    if (planes == 64 && tm == 128) return next ? "bneck_chain_f16<64,128,next>" : "bneck_chain_f16<64,128>";
-    if (planes == 64) return tm == 256 ? (next ? "bneck_chain_f16<64,256,next>" : "bneck_chain_f16<64,256>") : (next ? "bneck_chain_f16<64,64,next>" : "bneck_chain_f16<64,64>");
-    return tm == 128 ? (next ? "bneck_chain_f16<128,128,next>" : "bneck_chain_f16<128,128>") : (next ? "bneck_chain_f16<128,64,next>" : "bneck_chain_f16<128,64>");
+// The chain kernels, keyed by (planes, pixel tile, next block's reduce conv, two-source first block): 64 planes on 256-, 128- and
+// 64-pixel tiles, 128 planes on 128 and 64 (the small tiles for launches that would leave CUs idle). Four waves each. The rows'
+// order is the kernels' order in the code object.
+typedef void (*BneckKernel)(BneckParams);
+struct BneckChain { int planes, tm; bool next, dual; BneckKernel kernel; const char* symbol; };
+constexpr BneckChain kBneckChains[] = {
+    { 64, 128, true, true, bneck_chain_f16<64, 128, 1, 4, 1, 4, true, 1>, "bneck_chain_f16<64,128,next,dual>" },
+    { 64, 256, true, false, bneck_chain_f16<64, 256, 1, 4, 1, 4, true>, "bneck_chain_f16<64,256,next>" },
+    { 64, 256, false, false, bneck_chain_f16<64, 256, 1, 4, 1, 4, false>, "bneck_chain_f16<64,256>" },
+    { 64, 128, true, false, bneck_chain_f16<64, 128, 1, 4, 1, 4, true>, "bneck_chain_f16<64,128,next>" },
+    { 64, 128, false, false, bneck_chain_f16<64, 128, 1, 4, 1, 4, false>, "bneck_chain_f16<64,128>" },
+    { 64, 64, true, false, bneck_chain_f16<64, 64, 2, 2, 2, 2, true>, "bneck_chain_f16<64,64,next>" },
+    { 64, 64, false, false, bneck_chain_f16<64, 64, 2, 2, 2, 2, false>, "bneck_chain_f16<64,64>" },
+    { 128, 128, true, false, bneck_chain_f16<128, 128, 2, 2, 1, 4, true>, "bneck_chain_f16<128,128,next>" },
+    { 128, 128, false, false, bneck_chain_f16<128, 128, 2, 2, 1, 4, false>, "bneck_chain_f16<128,128>" },
+    { 128, 64, true, false, bneck_chain_f16<128, 64, 2, 2, 2, 2, true>, "bneck_chain_f16<128,64,next>" },
+    { 128, 64, false, false, bneck_chain_f16<128, 64, 2, 2, 2, 2, false>, "bneck_chain_f16<128,64>" },
+};
+
+static const BneckChain* bneck_chain(int planes, int tm, bool next, bool dual) {
+    for (const BneckChain& c : kBneckChains)
+        if (c.planes == planes && c.tm == tm && c.next == next && c.dual == dual) return &c;
+    return nullptr;
 }
 
-// planes in {64, 128}; tm: 256 / 64 for 64 planes, 128 / 64 for 128 planes (the small tiles for launches that would leave CUs idle)
+const char* bneck_symbol(int planes, int tm, bool next, bool dual) {
+    if (planes == 256) return "bneck_xn_f16";
+    const BneckChain* c = bneck_chain(planes, tm, next, dual);
+    return c ? c->symbol : "?";
+}
+
 hipError_t launch_bneck(const BneckParams& p, int planes, int tm, hipStream_t stream) {
     if (p.M < 1 || (p.stride != 1 && p.stride != 2)) return hipErrorInvalidValue;
     const int ntiles = (p.M + tm - 1) / tm;
     const dim3 grid((unsigned)ntiles);
-    const bool next = p.a_next != nullptr;
     if (p.no_b) {   // expand conv + residual + next reduce conv of a 256-plane block; b is a tensor (p.a)
         if (planes != 256 || tm != 64 || p.x2 || !p.res || !p.w1n || (!p.a_next && !p.a_next8)) return hipErrorInvalidValue;
         hipLaunchKernelGGL(bneck_xn_f16, grid, dim3(512), 0, stream, p);
         return hipGetLastError();
     }
-    if (p.x2) {   // the stage's first block (two-source expand conv): 64 planes, 64-channel second source, 128-pixel tiles
-        if (planes != 64 || tm != 128 || p.C2 != 64 || !next || p.res) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((bneck_chain_f16<64, 128, 1, 4, 1, 4, true, 1>), grid, dim3(256), 0, stream, p);
-        return hipGetLastError();
-    }
-    if (planes == 64 && tm == 256) {
-        if (next) hipLaunchKernelGGL((bneck_chain_f16<64, 256, 1, 4, 1, 4, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((bneck_chain_f16<64, 256, 1, 4, 1, 4, false>), grid, dim3(256), 0, stream, p);
-    } else if (planes == 64 && tm == 128) {
-        if (next) hipLaunchKernelGGL((bneck_chain_f16<64, 128, 1, 4, 1, 4, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((bneck_chain_f16<64, 128, 1, 4, 1, 4, false>), grid, dim3(256), 0, stream, p);
-    } else if (planes == 64 && tm == 64) {
-        if (next) hipLaunchKernelGGL((bneck_chain_f16<64, 64, 2, 2, 2, 2, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((bneck_chain_f16<64, 64, 2, 2, 2, 2, false>), grid, dim3(256), 0, stream, p);
-    } else if (planes == 128 && tm == 128) {
-        if (next) hipLaunchKernelGGL((bneck_chain_f16<128, 128, 2, 2, 1, 4, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((bneck_chain_f16<128, 128, 2, 2, 1, 4, false>), grid, dim3(256), 0, stream, p);
-    } else if (planes == 128 && tm == 64) {
-        if (next) hipLaunchKernelGGL((bneck_chain_f16<128, 64, 2, 2, 2, 2, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((bneck_chain_f16<128, 64, 2, 2, 2, 2, false>), grid, dim3(256), 0, stream, p);
-    } else return hipErrorInvalidValue;
+    // (the stage's first block, x2: the two-source expand conv takes a 64-channel second source and has no identity shortcut)
+    const BneckChain* c = bneck_chain(planes, tm, p.a_next != nullptr, p.x2 != nullptr);
+    if (!c || (p.x2 && (p.C2 != 64 || p.res))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(c->kernel, grid, dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

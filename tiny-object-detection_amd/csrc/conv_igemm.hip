@@ -19,6 +19,8 @@
 // block kept at the end of every activation allocation (inside the descriptor's range).
 // Epilogue: accumulators -> LDS as f32 [m][ch] (lane holds 4 consecutive channels per register
 // quad), then whole 16-byte f16 channel groups are written with coalesced row stores.
+#include <utility>
+
 #include "yh_internal.h"
 
 namespace yh {
@@ -941,35 +943,97 @@ __global__ __launch_bounds__(256) void splitk_reduce_f16(const ConvParams p) {
     }
 }
 
-int conv_tile_ch(ConvTile t) {
-    switch (t) { case TILE_128x128: case TILE_128x128_S3: case TILE_128x128_M16: case TILE_128x128_S3_M16: case TILE_128x128_K1: case TILE_128x128_FP8: case TILE_128x256: case TILE_128x256_M16: return 128; case TILE_64x256: case TILE_64x256_SMALLC: case TILE_64x256_K1: case TILE_64x64_S3: case TILE_64x64_FP8: return 64;
-                 case TILE_32x256: return 32; case TILE_96x128_K1: return 96; case TILE_256x256_M16: case TILE_256x256_FP8: return 256; }
-    return 0;
-}
-int conv_tile_m(ConvTile t) {
-    switch (t) { case TILE_128x128: case TILE_128x128_S3: case TILE_128x128_M16: case TILE_128x128_S3_M16: case TILE_128x128_K1: case TILE_128x128_FP8: case TILE_96x128_K1: return 128; case TILE_64x64_S3: case TILE_64x64_FP8: return 64; default: return 256; }
-}
-const char* conv_tile_symbol(ConvTile t) {
-    switch (t) {
-        case TILE_128x128: return "conv_igemm_f16<128,128,2,2,0,2>";
-        case TILE_64x256: return "conv_igemm_f16<64,256,1,4,0,2>";
-        case TILE_32x256: return "conv_igemm_f16<32,256,1,4,0,2>";
-        case TILE_64x256_SMALLC: return "conv_igemm_f16<64,256,1,4,1,2>";
-        case TILE_128x256: return "conv_igemm_f16<128,256,2,4,0,3>";
-        case TILE_256x256_M16: return "conv_igemm_f16<256,256,2,4,0,2,mfma16>";
-        case TILE_128x128_M16: return "conv_igemm_f16<128,128,2,2,0,2,mfma16>";
-        case TILE_128x128_S3_M16: return "conv_igemm_f16<128,128,2,2,0,3,mfma16>";
-        case TILE_128x128_S3: return "conv_igemm_f16<128,128,2,2,0,3>";
-        case TILE_128x256_M16: return "conv_igemm_f16<128,256,2,4,0,2,mfma16>";
-        case TILE_64x64_S3: return "conv_igemm_f16<64,64,2,2,0,3>";
-        case TILE_128x128_K1: return "conv_igemm_f16<128,128,2,2,0,1>";
-        case TILE_96x128_K1: return "conv_igemm_f16<96,128,2,2,0,1,mfma16>";
-        case TILE_64x256_K1: return "conv_igemm_f16<64,256,1,4,0,1>";
-        case TILE_256x256_FP8: return "conv_igemm_fp8<256,256,2,4>";
-        case TILE_128x128_FP8: return "conv_igemm_fp8<128,128,2,2>";
-        case TILE_64x64_FP8: return "conv_igemm_fp8<64,64,2,2>";
+// The one list of conv_igemm_f16's instances: a row per tile holds its base configuration, its profile symbol and the forms it is
+// instantiated in. Taking a kernel's address instantiates it, so each row instantiates its tile in the forms it lists and no
+// others (every form of every tile would double the kernels and the build time).
+typedef void (*ConvKernel)(ConvParams);
+struct ConvTileRow { int id, tch, tm, threads; bool fp8; const char* symbol; ConvKernel kernel[CONV_FORMS]; };
+
+template <int TCH, int TM, int WCH, int WM, bool SMALLC, int STAGES, int EPI, int MT, bool FP8, unsigned FORMS>
+struct Tile {
+    template <int F>
+    static constexpr ConvKernel kernel() {
+        if constexpr (!(FORMS >> F & 1)) return nullptr;
+        else return conv_igemm_f16<TCH, TM, WCH, WM, SMALLC, STAGES, EPI, F == FORM_SPLITK || F == FORM_ML_SPLITK || F == FORM_DUAL_SPLITK, MT,
+                                   F == FORM_ML || F == FORM_ML_SPLITK, FP8, F == FORM_RESUP, F == FORM_DUAL || F == FORM_DUAL_SPLITK, F == FORM_TAIL, F == FORM_K3>;
     }
-    return "?";
+    template <int... F>
+    static constexpr ConvTileRow row(ConvTile id, const char* symbol, std::integer_sequence<int, F...>) { return { id, TCH, TM, 64 * WCH * WM, FP8, symbol, { kernel<F>()... } }; }
+    static constexpr ConvTileRow row(ConvTile id, const char* symbol) { return row(id, symbol, std::make_integer_sequence<int, CONV_FORMS>()); }
+};
+
+constexpr unsigned PLAIN = 1u << FORM_PLAIN, K3 = 1u << FORM_K3, SPLITK = 1u << FORM_SPLITK, ML = 1u << FORM_ML, ML_SPLITK = 1u << FORM_ML_SPLITK,
+                   DUAL = 1u << FORM_DUAL, DUAL_SPLITK = 1u << FORM_DUAL_SPLITK, RESUP = 1u << FORM_RESUP, TAIL = 1u << FORM_TAIL;
+constexpr unsigned RING_FORMS = PLAIN | SPLITK | ML | ML_SPLITK | DUAL | DUAL_SPLITK | RESUP;   // the latency-bound 3-stage tiles
+// Tile<TCH, TM, WCH, WM, SMALLC, STAGES, EPI, MT, FP8, forms>::row(id, symbol); a launch runs 64 * WCH * WM threads. The rows' order
+// is the kernels' order in the code object, which can move step time by a few tenths of a percent.
+constexpr ConvTileRow kConvTiles[] = {
+    Tile<128, 128, 2, 2, false, 2, 1, 32, false, PLAIN | ML | DUAL | RESUP>::row(TILE_128x128, "conv_igemm_f16<128,128,2,2,0,2>"),
+    Tile<64,  256, 1, 4, false, 2, 1, 32, false, PLAIN>::row(TILE_64x256, "conv_igemm_f16<64,256,1,4,0,2>"),
+    Tile<32,  256, 1, 4, false, 2, 1, 32, false, PLAIN>::row(TILE_32x256, "conv_igemm_f16<32,256,1,4,0,2>"),
+    Tile<64,  256, 1, 4, true,  2, 1, 32, false, PLAIN>::row(TILE_64x256_SMALLC, "conv_igemm_f16<64,256,1,4,1,2>"),
+    Tile<128, 256, 2, 4, false, 3, 1, 32, false, PLAIN | ML>::row(TILE_128x256, "conv_igemm_f16<128,256,2,4,0,3>"),
+    Tile<128, 128, 2, 2, false, 3, 1, 32, false, RING_FORMS>::row(TILE_128x128_S3, "conv_igemm_f16<128,128,2,2,0,3>"),
+    Tile<256, 256, 2, 4, false, 2, 2, 16, false, PLAIN | ML | DUAL | RESUP | TAIL>::row(TILE_256x256_M16, "conv_igemm_f16<256,256,2,4,0,2,mfma16>"),
+    Tile<128, 128, 2, 2, false, 2, 1, 16, false, PLAIN | ML | DUAL | RESUP>::row(TILE_128x128_M16, "conv_igemm_f16<128,128,2,2,0,2,mfma16>"),
+    Tile<128, 128, 2, 2, false, 3, 1, 16, false, PLAIN | ML | DUAL | RESUP>::row(TILE_128x128_S3_M16, "conv_igemm_f16<128,128,2,2,0,3,mfma16>"),
+    Tile<128, 256, 2, 4, false, 2, 2, 16, false, PLAIN | ML>::row(TILE_128x256_M16, "conv_igemm_f16<128,256,2,4,0,2,mfma16>"),
+    Tile<64,  64,  2, 2, false, 3, 1, 32, false, RING_FORMS>::row(TILE_64x64_S3, "conv_igemm_f16<64,64,2,2,0,3>"),
+    Tile<256, 256, 2, 4, false, 2, 2, 16, true,  PLAIN | ML | TAIL>::row(TILE_256x256_FP8, "conv_igemm_fp8<256,256,2,4>"),
+    Tile<128, 128, 2, 2, false, 1, 2, 32, false, PLAIN | K3 | ML | DUAL | RESUP>::row(TILE_128x128_K1, "conv_igemm_f16<128,128,2,2,0,1>"),
+    Tile<64,  256, 1, 4, false, 1, 2, 32, false, PLAIN>::row(TILE_64x256_K1, "conv_igemm_f16<64,256,1,4,0,1>"),
+    // launches with few 256 x 256 tiles (small batches): four times the workgroups, two per CU
+    Tile<128, 128, 2, 2, false, 2, 1, 16, true,  PLAIN | ML>::row(TILE_128x128_FP8, "conv_igemm_fp8<128,128,2,2>"),
+    // ... and with at most two 128 x 128 tiles per CU: sixteen times the workgroups
+    Tile<64,  64,  2, 2, false, 2, 1, 16, true,  PLAIN>::row(TILE_64x64_FP8, "conv_igemm_fp8<64,64,2,2>"),
+    Tile<96,  128, 2, 2, false, 1, 2, 16, false, ML>::row(TILE_96x128_K1, "conv_igemm_f16<96,128,2,2,0,1,mfma16>"),
+};
+
+static const ConvTileRow& conv_row(ConvTile t) {
+    static constexpr ConvTileRow none = { -1, 0, 0, 0, false, "?", {} };   // not a tile id: no channels, no rows, no forms
+    for (const ConvTileRow& r : kConvTiles)
+        if (r.id == t) return r;
+    return none;
+}
+int conv_tile_ch(ConvTile t) { return conv_row(t).tch; }
+int conv_tile_m(ConvTile t) { return conv_row(t).tm; }
+const char* conv_tile_symbol(ConvTile t) { return conv_row(t).symbol; }
+bool conv_tile_has(ConvTile t, ConvForm f) { return conv_row(t).kernel[f] != nullptr; }
+
+// The form a launch with these parameters takes, whether or not the tile has it.
+static ConvForm conv_form(const ConvParams& p, ConvTile tile) {
+    const bool split = p.k_slices > 1;
+    if (p.nlev > 0) return split ? FORM_ML_SPLITK : FORM_ML;
+    if (p.w2) return FORM_TAIL;
+    if (p.x2) return split ? FORM_DUAL_SPLITK : FORM_DUAL;
+    if (split) return FORM_SPLITK;
+    if (p.res_up) return FORM_RESUP;
+    return p.R == 3 && p.S == 3 && conv_tile_has(tile, FORM_K3) ? FORM_K3 : FORM_PLAIN;
+}
+
+// Parameters a form cannot take.
+static bool conv_form_rejects(const ConvParams& p, ConvForm f) {
+    switch (f) {
+        // multi-level input: the shared prediction head over the whole pyramid
+        case FORM_ML: case FORM_ML_SPLITK: return p.stride != 1 || p.nlev > 5;
+        // fused 1x1 tail: single launches of the 256 x 256 tile whose one channel tile is the whole conv
+        case FORM_TAIL: return p.k_slices > 1 || p.n_ch_tiles != 1 || p.ch_tile0 || p.cout8 != 256 || p.res || p.x2 || p.nlev || !p.bias2 || !p.y2 || p.y || p.y8 || p.tanh_from < 256;
+        // two-source 1x1 form: a bottleneck block's last conv + its projection
+        case FORM_DUAL: case FORM_DUAL_SPLITK: return p.R != 1 || p.S != 1 || p.pad != 0 || p.stride != 1 || p.res_up || p.k1steps < 1 || p.k1steps >= p.ksteps || p.C2 % 64 != 0;
+        default: return false;
+    }
+}
+
+// The kernel symbol a launch is profiled under: the tile's, and a suffix for the forms rocprofv3 lists as symbols of their own
+// (multi-level, fused 1x1 tail, the streaming tile's 3x3 form).
+std::string conv_label(const ConvParams& p, ConvTile tile) {
+    const std::string s = conv_tile_symbol(tile);
+    switch (conv_form(p, tile)) {
+        case FORM_ML: case FORM_ML_SPLITK: return s + "[ml]";
+        case FORM_TAIL: return s + "[+1x1]";
+        case FORM_K3: return s + "[3x3]";
+        default: return s;
+    }
 }
 
 hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream) {
@@ -978,126 +1042,15 @@ hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// One kernel launch (for split-K: the main kernel only).
+// One kernel launch (for split-K: the main kernel only; launch_splitk_reduce finishes it).
 hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream) {
-    const int tm = conv_tile_m(tile);
-    const int n_m_tiles = (p.M + tm - 1) / tm - p.m_tile0;
+    const ConvTileRow& r = conv_row(tile);
+    const ConvForm f = conv_form(p, tile);
+    if (!r.kernel[f] || conv_form_rejects(p, f) || (r.fp8 && !p.scale)) return hipErrorInvalidValue;
+    const int n_m_tiles = (p.M + r.tm - 1) / r.tm - p.m_tile0;
     if (n_m_tiles < 1) return hipErrorInvalidValue;
-    if (p.nlev > 0) {   // multi-level input (the shared prediction head over the whole pyramid): the tiles a head conv can get
-        if (p.stride != 1 || p.nlev > 5) return hipErrorInvalidValue;
-        if (p.k_slices > 1) {
-            const dim3 gk((unsigned)(n_m_tiles * p.n_ch_tiles * p.k_slices));
-            if (tile == TILE_128x128_S3) hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, true, 32, true>), gk, dim3(256), 0, stream, p);
-            else if (tile == TILE_64x64_S3) hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, true, 32, true>), gk, dim3(256), 0, stream, p);
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-        const dim3 grid((unsigned)(n_m_tiles * p.n_ch_tiles));
-        switch (tile) {
-            case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, true>), grid, dim3(512), 0, stream, p); break;
-            case TILE_256x256_FP8:
-                if (!p.scale) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, true, true>), grid, dim3(512), 0, stream, p);
-                break;
-            case TILE_128x128_FP8:
-                if (!p.scale) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, true, true>), grid, dim3(256), 0, stream, p);
-                break;
-            case TILE_128x256_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 256, 2, 4, false, 2, 2, false, 16, true>), grid, dim3(512), 0, stream, p); break;
-            case TILE_128x256: hipLaunchKernelGGL((conv_igemm_f16<128, 256, 2, 4, false, 3, 1, false, 32, true>), grid, dim3(512), 0, stream, p); break;
-            case TILE_128x128: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 32, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_K1: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 1, 2, false, 32, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_96x128_K1: hipLaunchKernelGGL((conv_igemm_f16<96, 128, 2, 2, false, 1, 2, false, 16, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 32, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_64x64_S3: hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, false, 32, true>), grid, dim3(256), 0, stream, p); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.w2) {   // fused 1x1 tail: single launches of the 256 x 256 tile whose one channel tile is the whole conv
-        if (p.k_slices > 1 || p.n_ch_tiles != 1 || p.ch_tile0 || p.cout8 != 256 || p.res || p.x2 || p.nlev || !p.bias2 || !p.y2 || p.y || p.y8 || p.tanh_from < 256) return hipErrorInvalidValue;
-        const dim3 grid((unsigned)(n_m_tiles * p.n_ch_tiles));
-        if (tile == TILE_256x256_M16) hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, false, false, false, true>), grid, dim3(512), 0, stream, p);
-        else if (tile == TILE_256x256_FP8 && p.scale) hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, true, false, false, true>), grid, dim3(512), 0, stream, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (p.x2) {   // two-source 1x1 form (a bottleneck block's last conv + its projection): the tiles dual_conv_tile() maps to
-        if (p.R != 1 || p.S != 1 || p.pad != 0 || p.stride != 1 || p.res_up || p.k1steps < 1 || p.k1steps >= p.ksteps || p.C2 % 64 != 0) return hipErrorInvalidValue;
-        if (p.k_slices > 1) {
-            const dim3 gk((unsigned)(n_m_tiles * p.n_ch_tiles * p.k_slices));
-            if (tile == TILE_128x128_S3) hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, true, 32, false, false, false, true>), gk, dim3(256), 0, stream, p);
-            else if (tile == TILE_64x64_S3) hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, true, 32, false, false, false, true>), gk, dim3(256), 0, stream, p);
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-        const dim3 grid((unsigned)(n_m_tiles * p.n_ch_tiles));
-        switch (tile) {
-            case TILE_128x128: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 32, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_K1: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 1, 2, false, 32, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 32, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_64x64_S3: hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, false, 32, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16, false, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, false, false, true>), grid, dim3(512), 0, stream, p); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.k_slices > 1) {   // split-K main kernel; launch_splitk_reduce finishes it
-        const dim3 gk((unsigned)(n_m_tiles * p.n_ch_tiles * p.k_slices));
-        if (tile == TILE_128x128_S3) hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, true>), gk, dim3(256), 0, stream, p);
-        else if (tile == TILE_64x64_S3) hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, true>), gk, dim3(256), 0, stream, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    const dim3 grid((unsigned)(n_m_tiles * p.n_ch_tiles));
-    if (p.res_up) {   // the FPN lateral convs (1x1, 256 output channels): the tiles pick_tile / plan_conv can give them
-        switch (tile) {
-            case TILE_128x128: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 32, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_K1: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 1, 2, false, 32, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 32, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_64x64_S3: hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1, false, 32, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16, false, false, true>), grid, dim3(256), 0, stream, p); break;
-            case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, false, true>), grid, dim3(512), 0, stream, p); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (tile) {
-        case TILE_128x128: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_128x128_K1:
-            if (p.R == 3 && p.S == 3) hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 1, 2, false, 32, false, false, false, false, false, true>), grid, dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 1, 2>), grid, dim3(256), 0, stream, p);
-            break;
-        case TILE_64x256_K1: hipLaunchKernelGGL((conv_igemm_f16<64, 256, 1, 4, false, 1, 2>), grid, dim3(256), 0, stream, p); break;
-        case TILE_64x256: hipLaunchKernelGGL((conv_igemm_f16<64, 256, 1, 4, false, 2, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_32x256: hipLaunchKernelGGL((conv_igemm_f16<32, 256, 1, 4, false, 2, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_64x256_SMALLC: hipLaunchKernelGGL((conv_igemm_f16<64, 256, 1, 4, true, 2, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_128x256: hipLaunchKernelGGL((conv_igemm_f16<128, 256, 2, 4, false, 3, 1>), grid, dim3(512), 0, stream, p); break;
-        case TILE_128x128_S3: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_64x64_S3: hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 3, 1>), grid, dim3(256), 0, stream, p); break;
-        case TILE_128x256_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 256, 2, 4, false, 2, 2, false, 16>), grid, dim3(512), 0, stream, p); break;
-        case TILE_128x128_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16>), grid, dim3(256), 0, stream, p); break;
-        case TILE_128x128_S3_M16: hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 3, 1, false, 16>), grid, dim3(256), 0, stream, p); break;
-        case TILE_256x256_M16: hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16>), grid, dim3(512), 0, stream, p); break;
-        case TILE_256x256_FP8:
-            if (!p.scale) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((conv_igemm_f16<256, 256, 2, 4, false, 2, 2, false, 16, false, true>), grid, dim3(512), 0, stream, p);
-            break;
-        case TILE_128x128_FP8:   // launches with few 256 x 256 tiles (small batches): four times the workgroups, two per CU
-            if (!p.scale) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((conv_igemm_f16<128, 128, 2, 2, false, 2, 1, false, 16, false, true>), grid, dim3(256), 0, stream, p);
-            break;
-        case TILE_64x64_FP8:     // ... and with at most two 128 x 128 tiles per CU: sixteen times the workgroups
-            if (!p.scale) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((conv_igemm_f16<64, 64, 2, 2, false, 2, 1, false, 16, false, true>), grid, dim3(256), 0, stream, p);
-            break;
-        default: return hipErrorInvalidValue;
-    }
+    const int slices = p.k_slices > 1 ? p.k_slices : 1;   // (the split-K forms' grid also splits K)
+    hipLaunchKernelGGL(r.kernel[f], dim3((unsigned)(n_m_tiles * p.n_ch_tiles * slices)), dim3(r.threads), 0, stream, p);
     return hipGetLastError();
 }
 

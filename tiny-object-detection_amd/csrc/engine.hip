@@ -797,7 +797,7 @@ constexpr int kSplitKMinSteps = 12;
 constexpr int kT64MinSteps = 24;
 
 // The panel fixes the widest channel tile (coutPad); per launch, the decisions below apply in order.
-// ml: the op has a multi-level input (only the tiles launch_conv instantiates for it may be chosen).
+// ml: the op has a multi-level input (only tiles with that form may be chosen: kConvTiles, conv_igemm.hip).
 ConvTile pick_tile(const Tune& tu, const Panel& pn, int M, int stride, bool ml) {
     const int cus = tu.plan_cus;
     const long long b128 = (long long)((M + 127) / 128) * (pn.coutPad / 128), m256 = (M + 255) / 256;
@@ -934,14 +934,6 @@ hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile til
     return hipSuccess;
 }
 
-// The tiles launch_conv instantiates for the two-source form; the others map to their nearest relative.
-ConvTile dual_conv_tile(ConvTile t) {
-    switch (t) {
-        case TILE_128x128: case TILE_128x128_K1: case TILE_128x128_S3: case TILE_64x64_S3: case TILE_128x128_M16: case TILE_128x128_S3_M16: case TILE_256x256_M16: return t;
-        default: return TILE_128x128;
-    }
-}
-
 int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile* tile_out = nullptr) {
     const Panel& pn = h->panels[o.panel];
     ConvParams p;
@@ -979,7 +971,7 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     if (h->tune.ablate & 2) { p.w_bytes = 0; }
     if (h->tune.ablate & 4) { p.skip_dma = 1; }
     ConvTile tile = pick_tile(h->tune, pn, p.M, o.stride, o.nlev > 0);
-    if (o.dual) tile = dual_conv_tile(tile);
+    if (o.dual && !conv_tile_has(tile, FORM_DUAL)) tile = TILE_128x128;
     if (h->fp8_active) {
         // fp8 precision, calibrated: what this op's output is written as, and (for the K-heavy 3x3 layers) E4M3 operands
         p.y = o.write_f16 ? o.out.d : nullptr;
@@ -1005,7 +997,7 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     if (tile_out) *tile_out = tile;
     p.n_ch_tiles = pn.coutPad / conv_tile_ch(tile);
     p.k_slices = 1;
-    if (o.tail_op >= 0 && (tile == TILE_256x256_M16 || tile == TILE_256x256_FP8) && pn.coutPad == 256 && pn.cout == 256 && !o.has_res &&
+    if (o.tail_op >= 0 && conv_tile_has(tile, FORM_TAIL) && pn.coutPad == 256 && pn.cout == 256 && !o.has_res &&
         tail_split_tiles(h->tune, pn.coutPad, p, tile) == 0) {
         // fused 1x1 tail: this launch also computes ops[tail_op] from its tile (launch_op skips that op: conv_absorbed)
         const Op& t = h->ops[o.tail_op];
@@ -2690,9 +2682,7 @@ int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, dou
                 h->prof_labels[i] = "splitk_reduce_f16:" + o.name;
                 by = (double)pe.k.p.M * pe.k.p.partial_ld * 4.0 * pe.k.p.k_slices + (double)pe.k.p.M * pe.k.p.cout8 * 2.0;
             } else if (pe.form == OpLaunch::CONV) {
-                // (kernel symbols of their own in rocprofv3's stats: multi-level, fused 1x1 tail, the streaming tile's 3x3 form)
-                const bool k3 = pe.k.tile == TILE_128x128_K1 && pe.k.p.R == 3 && pe.k.p.S == 3 && pe.k.p.nlev == 0 && !pe.k.p.res_up && !pe.k.p.x2;
-                h->prof_labels[i] = std::string(conv_tile_symbol(pe.k.tile)) + (pe.k.p.nlev > 0 ? "[ml]" : "") + (pe.k.p.w2 ? "[+1x1]" : "") + (k3 ? "[3x3]" : "") + ":" + o.name + pe.k.what;
+                h->prof_labels[i] = conv_label(pe.k.p, pe.k.tile) + ":" + o.name + pe.k.what;
                 if (pe.k.p.w2) {   // fused 1x1 tail: both convolutions' FLOPs; this conv's input and the tail's output
                     const Op& t = h->ops[o.tail_op];
                     h->prof_labels[i] += "+" + t.name;
@@ -2818,7 +2808,7 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
     HIPCHK(h, hipSetDevice(h->dev));
     ConvTile tile = TILE_128x128;
     if (h->tune.op_tile >= 0) tile = (ConvTile)h->tune.op_tile;
-    if (conv_tile_ch(tile) == 0 || dual_conv_tile(tile) != tile) return h->fail(YH_EINVAL, "dual conv op: tune.op_tile is not a tile of the two-source form");
+    if (!conv_tile_has(tile, FORM_DUAL)) return h->fail(YH_EINVAL, "dual conv op: tune.op_tile is not a tile of the two-source form");
     const int K = c1 + c2, coutPad = round_up(cout, conv_tile_ch(tile));
     const size_t M = (size_t)n * ho * wo, n1 = M * c1, n2 = (size_t)n * h2 * w2 * c2;
     const std::vector<uint16_t> wp = pad_rows(w, 1, (size_t)cout * K, (size_t)coutPad * K);
@@ -2843,7 +2833,7 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
         p.N = n; p.H = ho; p.W = wo; p.C = c1; p.P = ho; p.Q = wo; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
         p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
-        if (tile == TILE_128x128_S3 || tile == TILE_64x64_S3) force_split_k(h, p, M, coutPad);   // (the two-source tiles that split K)
+        if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, p, M, coutPad);
         st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
     }
     st.sync(h->stream);

@@ -129,9 +129,14 @@ struct ConvParams {
 enum ConvTile { TILE_128x128 = 0, TILE_64x256 = 1, TILE_32x256 = 2, TILE_64x256_SMALLC = 3, TILE_128x256 = 5, TILE_128x128_S3 = 7, TILE_256x256_M16 = 8,
                 TILE_128x128_M16 = 12, TILE_128x128_S3_M16 = 13, TILE_128x256_M16 = 15, TILE_64x64_S3 = 16, TILE_256x256_FP8 = 20, TILE_128x128_K1 = 21, TILE_64x256_K1 = 22, TILE_128x128_FP8 = 23, TILE_64x64_FP8 = 24,
                 TILE_96x128_K1 = 27 /* the streaming tile for a 96-channel remainder (the shared head's channels 256 .. 351): multi-level form only */ };
-int conv_tile_ch(ConvTile t);
+// The forms of a tile's kernel: plain, the streaming tile's 3x3 form, split-K, multi-level, two-source, upsampled residual, fused
+// 1x1 tail. conv_igemm.hip's kConvTiles lists which tile is instantiated in which; launch_conv picks a launch's form from ConvParams.
+enum ConvForm { FORM_PLAIN, FORM_K3, FORM_SPLITK, FORM_ML, FORM_ML_SPLITK, FORM_DUAL, FORM_DUAL_SPLITK, FORM_RESUP, FORM_TAIL, CONV_FORMS };
+int conv_tile_ch(ConvTile t);   // (0: not a tile id)
 int conv_tile_m(ConvTile t);
 const char* conv_tile_symbol(ConvTile t);
+bool conv_tile_has(ConvTile t, ConvForm f);
+std::string conv_label(const ConvParams& p, ConvTile tile);   // the tile's symbol + the form's suffix ([ml], [+1x1], [3x3])
 hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream);
 hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream);
 
