@@ -5,7 +5,7 @@
  * Why it exists: the path's one collective - the weight replication of BASELINE.json configs[3] / [4] (the
  * reference has no counterpart: one process, one device, src/main.rs:63-75) - marshals ncclUniqueId BY VALUE, passes ncclUint8 = 1,
  * orders the broadcast on the handle's stream and owns the communicator's lifetime, all by hand against a dlopen'ed library
- * (csrc/engine.hip: yh_rccl_unique_id, yh_rank_broadcast_weights, yh_group_broadcast_weights). Real RCCL refuses two ranks on one GPU
+ * (csrc/rccl.hip: yh_rccl_unique_id, yh_rank_broadcast_weights, yh_group_broadcast_weights). Real RCCL refuses two ranks on one GPU
  * and the test box has one GPU, so that code had only ever run with n = 1. This stand-in implements the eight entry points the library
  * binds, with the real signatures, so that n = 2 executes on ONE device:
  *   - ranks in different processes (ncclCommInitRank) meet in a POSIX shared-memory segment named by the unique id; the broadcast

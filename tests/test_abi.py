@@ -129,7 +129,7 @@ def test_product_never_imports_oracle():
 def test_standin_librccl_builds_and_exports_what_the_library_binds(tmp_path):
     """tests/rccl_standin/librccl_standin.c (TEST infrastructure: the stand-in that lets a one-GPU box execute the n > 1 collective
     code, tests/test_gpu_rccl_standin.py) compiles with gcc against the ROCm headers and exports exactly the eight entry points
-    csrc/engine.hip binds by name - and the product never names it: libyolact_hip.so still asks the loader for librccl.so.1."""
+    csrc/rccl.hip binds by name - and the product never names it: libyolact_hip.so still asks the loader for librccl.so.1."""
     import subprocess
     src = os.path.join(ROOT, "tests", "rccl_standin", "librccl_standin.c")
     so = tmp_path / "librccl.so.1"
@@ -138,7 +138,7 @@ def test_standin_librccl_builds_and_exports_what_the_library_binds(tmp_path):
     have = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
     want = {"ncclGetUniqueId", "ncclCommInitRank", "ncclCommInitAll", "ncclCommDestroy", "ncclBroadcast", "ncclGroupStart", "ncclGroupEnd", "ncclGetErrorString"}
     assert want <= have, want - have
-    eng = open(os.path.join(ROOT, "tiny-object-detection_amd", "csrc", "engine.hip")).read()
+    eng = open(os.path.join(ROOT, "tiny-object-detection_amd", "csrc", "rccl.hip")).read()
     for sym in want:
         assert f'sym("{sym}")' in eng, sym
     assert "rccl_standin" not in eng.replace("tests/rccl_standin", "") and '"librccl.so.1"' in eng

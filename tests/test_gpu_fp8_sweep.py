@@ -48,7 +48,7 @@ class Forced:
 
     def weights(self, name, s_c):
         """The layer's weights with its input tensor's channel scales folded in along K (t = w * s_c, one f32 multiplication), then
-        one scale per output channel and E4M3 codes of t / s_w - engine.hip: refresh_fp8_scales, oracle/orc_net.c: run_conv."""
+        one scale per output channel and E4M3 codes of t / s_w - fp8.hip: refresh_fp8_scales, oracle/orc_net.c: run_conv."""
         if name not in self._wq:
             w, b = self.convs[self.idx[name]]
             t = (w.astype(np.float32) * s_c.astype(np.float32)).astype(np.float32)

@@ -2,7 +2,7 @@
 BASELINE.json configs[3] / [4] start with it; the reference has no counterpart - one process, one device, src/main.rs:63-75).
 
 Real RCCL refuses two ranks on one device and the test box has one device, so yh_rank_broadcast_weights / yh_group_broadcast_weights
-(csrc/engine.hip) had only ever executed with n = 1: the by-value ncclUniqueId, ncclUint8 = 1, the stream order of the broadcast and
+(csrc/rccl.hip) had only ever executed with n = 1: the by-value ncclUniqueId, ncclUint8 = 1, the stream order of the broadcast and
 the communicator's lifetime are marshalled by hand against a dlopen'ed library. tests/rccl_standin/librccl_standin.c implements the
 eight entry points the library binds, with the real signatures, over shared memory + hipMemcpyAsync on the caller's stream; it is
 built HERE into a temp directory and found by the loader only in the subprocesses this test starts (LD_LIBRARY_PATH; the library's

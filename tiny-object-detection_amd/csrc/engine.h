@@ -1,0 +1,240 @@
+// engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
+// Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
+// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*). DESIGN.md section 4 says what each may see.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <limits.h>
+
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "yh_internal.h"
+
+// (hidden: nothing declared here is exported from the shared library)
+namespace yh __attribute__((visibility("hidden"))) {
+
+struct ConvDesc {          // one canonical conv of the blob
+    int cout, cin, k;
+    float gain;
+    int is_conf;   // 0 plain, 1 conf head (background bias), 2 mask head (bias)
+    size_t blob_w_off, blob_b_off;  // byte offsets in the canonical blob
+};
+
+struct Panel {             // device-side repacked weights of one launched conv
+    half_t* w = nullptr;   // [coutPad][Kpad]
+    float* bias = nullptr; // [coutPad]
+    int2* rs_table = nullptr;
+    int cout = 0, coutPad = 0, Kpad = 0, cin_store = 0, k = 0;
+    ConvTile tile = TILE_128x128;
+    std::vector<int> src;  // canonical conv indices concatenated along cout
+    int kcat = -1;         // >= 0: this canonical conv's weights are appended ALONG K (two-source 1x1 form, ConvParams::x2); biases add
+    // fp8 precision: the same weights as E4M3 codes, one scale per output channel
+    bool fp8 = false;
+    uint8_t* w8 = nullptr;     // [coutPad][Kpad] E4M3
+    float* scale = nullptr;    // [coutPad]: s_x (input tensor) * s_w[ch], refreshed by the calibration
+    std::vector<float> sw;     // [coutPad] weight scales (host)
+    int in_sid = -1;           // scale id of the input tensor these weights are applied to
+};
+
+struct Buf {               // dense NHWC f16 tensor [max_batch][h][w][c] or a slice of one
+    half_t* d = nullptr;
+    int h = 0, w = 0, c = 0;       // c = row stride in elements
+    long long img_stride = 0;      // elements per image
+    half_t* zero = nullptr;        // 16-byte zero block at the end of the owning allocation
+    // fp8 precision: the same tensor as E4M3 codes (same element offsets, one byte each), the allocation's scale id
+    uint8_t* q = nullptr;
+    uint8_t* qzero = nullptr;
+    int sid = -1;
+};
+
+struct DevAlloc { void* p; size_t bytes; };   // one hipMalloc of a handle
+
+// One activation allocation (new_buf), indexed by Buf::sid: where it lies and, in fp8 handles, its scales.
+// Round 4: one activation scale per CHANNEL of every allocation an fp8 convolution reads (a per-tensor scale is the same value in
+// every channel). The channel scale is folded into the consumer's weights along K before their per-output-channel quantisation
+// (refresh_fp8_scales) and the producer's epilogue multiplies by the reciprocal table instead of a scalar: no extra pass.
+struct ActAlloc {
+    half_t* base = nullptr;        // first element
+    long long img = 0;             // elements per image
+    int c = 0;                     // channels (= row stride in elements)
+    float scale = 1.0f;            // the largest channel scale (what yh_fp8_layer_info reports)
+    bool scale_set = false;        // the scale was set by a calibration or by yh_fp8_set_layer_scale since the weights were loaded
+    std::vector<float> ch;         // [c] channel scales; empty: not set
+    float *inv_dev = nullptr, *sc_dev = nullptr;   // device tables of 1 / scale and scale ([c]; fp8 handles only)
+};
+
+enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_BILINEAR, OP_STEMPOOL };
+
+struct Op {
+    OpKind kind;
+    std::string name;      // layer name (matches the oracle's intermediate names)
+    std::string label;     // "kernel_symbol:layer"
+    Buf in, out, res;
+    bool has_res = false;
+    bool res_up = false;   // the residual is the bilinear resize of the lower-resolution tensor `res` (ConvParams::res_up)
+    int tail_op = -1;      // index of the 1x1 conv that may run in this conv's epilogue (ConvParams::w2) when the launch plan allows
+    // bottleneck chain (bneck.hip; tune.chain): on an identity block's 3x3 conv - the block's last 1x1 conv and (if any) the next
+    // block's first 1x1 conv that run inside its launch; on those two - the 3x3 conv that absorbs them
+    int chain_c = -1, chain_a = -1, in_chain = -1;
+    // ... the no-3x3 form (256 planes, layer 3): on the block's last 1x1 conv - the next block's first 1x1 conv that runs inside its
+    // launch; on that one - the conv that absorbs it
+    int xn_a = -1, in_xn = -1;
+    int fused_into = -1;   // ... and on that 1x1 conv: the index of the conv that may absorb it
+    bool side = false;     // may run on the second stream: nothing on the main stream reads its output before the step's join
+    bool dual = false;     // two-source 1x1 form: K continues over `in2` read at `stride2` (ConvParams::x2)
+    Buf in2;
+    int stride2 = 1;
+    int panel = -1;
+    int stride = 1, pad = 0, act = 0, tanh_from = INT_MAX;
+    int P = 0, Q = 0;      // output spatial
+    int nlev = 0, lev_start[5] = {0, 0, 0, 0, 0}, lev_h[5] = {0, 0, 0, 0, 0}, lev_w[5] = {0, 0, 0, 0, 0};   // multi-level input (ConvParams)
+    double flops_per_img = 0, bytes_per_img = 0, bytes_fixed = 0;
+    // fp8 precision: this conv reads E4M3 operands; what its output is written as (decided by who reads it)
+    bool fp8 = false, write_q = false, write_f16 = true;
+};
+
+// The handle's tuning with every default resolved (include/yolact_hip_debug.h: yh_tuning; -1 = default there).
+struct Tune {
+    int plan_cus, chsplit, upfuse, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, chain;
+};
+
+// A convolution is planned as one to two kernel launches; `frac` is the share of the op's
+// algorithmic work a launch does (profile attribution), `what` a label suffix.
+struct KLaunch { bool reduce; ConvParams p; ConvTile tile; double frac; const char* what; };
+
+// What op `o` becomes at batch n. Decided here only: launch_op issues the plan, the profiler lists and labels the same plan.
+struct OpLaunch {
+    enum Form { SKIP, XN, CHAIN, CONV, OTHER } form;   // SKIP: computed inside another op's launch; OTHER: not a convolution
+    int planes, tile_m;                                // XN, CHAIN: launch_bneck's arguments besides bp
+    BneckParams bp;
+    ConvParams p;                                      // CONV: plan_conv's arguments besides the panel's coutPad
+    ConvTile tile;
+};
+
+}  // namespace yh
+
+struct yh_engine {
+    yh_config cfg;
+    yh::Tune tune;
+    int dev = 0, device_cus = 256;
+    hipStream_t stream = nullptr;
+    hipStream_t side = nullptr;   // the detection tail's K1-K3 run here underneath the protonet
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_forks[4] = { nullptr, nullptr, nullptr, nullptr };   // one per fork point of a step (enqueue_all)
+    std::string err;
+
+    int S = 0, C = 0, ldh = 0;
+    int lvl[5] = { 0, 0, 0, 0, 0 }, lvl_off[5] = { 0, 0, 0, 0, 0 };
+    int cells = 0, P = 0, hp = 0, wp = 0;
+    double flops_per_frame = 0;
+
+    std::vector<yh::ConvDesc> convs;
+    size_t blob_bytes = 0;
+    std::vector<yh::Panel> panels;
+    std::vector<yh::Op> ops;
+    std::vector<yh::DevAlloc> allocs;   // everything dev_alloc handed out (freed by yh_destroy; listed by yh_debug_alloc_map)
+    std::map<std::string, yh::Buf> named;
+    std::set<std::string> fused_away;   // named tensors that production runs never write (debug_tensors = 1 materialises them)
+    // fp8 precision (yh_config.precision): per-allocation activation scales, filled by yh_fp8_calibrate
+    std::vector<yh::ActAlloc> act;      // by Buf::sid
+    std::vector<int> fp8_ops;           // indices of the ops that read E4M3 operands
+    std::set<std::string> q_only;       // named tensors that exist only as E4M3 while fp8 is active
+    bool fp8_active = false;            // the op list currently runs its fp8 form (false during calibration and in f16 engines)
+    bool fp8_ready = false;             // scales calibrated
+    unsigned* absmax_dev = nullptr;     // calibration scratch: kMaxFp8Tensors x kMaxFp8Channels channel maxima (as bit patterns)
+    static constexpr int kMaxFp8Tensors = 64, kMaxFp8Channels = 512;
+    unsigned* rowmax_dev = nullptr;           // [1024]: row maxima of a weight panel with the channel scales folded in
+
+    // Two input buffers and a copy stream: yh_set_input_* fills the buffer the running step does NOT read, so frame k+1's
+    // host -> device copy runs underneath step k (the limiter of the sharded path is host-side H2D). A step is
+    // captured once per buffer (the stem kernel's source pointer is a launch argument).
+    uint8_t* in_buf[2] = { nullptr, nullptr };
+    int in_cur = 0;                 // the buffer the next step reads
+    bool in_pending = false;        // a copy into in_buf[in_cur] has been issued that no step has waited for yet
+    hipStream_t copy = nullptr;
+    hipEvent_t in_ready[2] = { nullptr, nullptr }, in_free[2] = { nullptr, nullptr };
+    bool in_free_rec[2] = { false, false };
+    uint8_t* in_u8() const { return in_buf[in_cur]; }
+    int in_hp = 0;
+    yh::Buf in_f16, pyr, pyr_t, heads, proto;
+    float* priors_dev = nullptr;
+    std::vector<float> priors_host;
+
+    // tail workspaces / outputs
+    yh::DetectParams det{};
+    // compat-path scratch
+    uint32_t* frame_dev = nullptr;
+    float* rs_tmp = nullptr;
+    float* cells_dev = nullptr;
+    uint32_t* codes_dev = nullptr;
+    uint32_t* stitch_dev = nullptr;
+    int* diverged_dev = nullptr;
+    size_t frame_cap = 0, rs_tmp_cap = 0;
+    // output staging
+    float* out_f32 = nullptr;
+    size_t out_f32_cap = 0;
+    float* splitk_ws = nullptr;
+    static const size_t kSplitKBytes = (size_t)48 << 20;
+
+    bool weights_loaded = false, capturing = false;
+    bool worker_mode = false;   // the handle is a group member being driven from its worker thread: no capture, no allocation there
+    unsigned* side_word = nullptr;   // target of the captured side-branch memset (enqueue_all)
+    uint8_t* blob_dev = nullptr;   // the canonical blob as loaded (send / receive buffer of the RCCL weight broadcast)
+    int cur_n = 0;
+    static constexpr size_t kStageBytes = 4u << 20;   // pinned staging for small host inputs
+    uint8_t* stage[2] = { nullptr, nullptr };
+    hipEvent_t stage_ev[2] = { nullptr, nullptr };
+    int stage_idx = 0;
+    int last_conv_launches = 0;   // yh_debug_last_conv_launches
+    bool stem_fused = false;
+    int tail_fork_op = 0;   // ops[tail_fork_op..] (the protonet) do not feed the tail's K1-K3
+    int head_fork_op = 0;   // ops[head_fork_op .. tail_fork_op) are the shared prediction head; the protonet does not read them
+    float* splitk_ws_side = nullptr;   // split-K workspace of convolutions launched on the side stream
+    std::map<int, hipGraphExec_t> graphs;  // key = n*2 + with_tail
+    std::vector<std::string> prof_labels;  // storage behind the names yh_profile_run returns
+
+    int fail(int code, const std::string& m) { err = m; return code; }
+};
+
+#define HIPCHK(h, call)                                                                        \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return (h)->fail(YH_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
+    } while (0)
+
+namespace yh __attribute__((visibility("hidden"))) {
+
+// engine.hip
+std::string& create_error();   // what yh_last_error(NULL) returns: set by yh_create and by the entry points that take no handle
+size_t pad16(size_t v);
+int round_up(int v, int m);
+int out_dim(int h, int k, int s, int p);
+int blocks_of(int backbone, int layer);
+int dev_alloc(yh_engine* h, void** p, size_t bytes);
+int ensure_out_f32(yh_engine* h, size_t nfloats);
+void drop_graphs(yh_engine* h);   // captured steps bake in tuning, scales, streams: whoever changes one of those drops them
+int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, KLaunch out[3]);
+hipError_t launch_k(const KLaunch& k, hipStream_t stream);
+hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches = nullptr);
+bool conv_absorbed(yh_engine* h, const Op& o, int n);
+bool chain_active(const yh_engine* h, const Op& ob, int n);
+int plan_op(yh_engine* h, const Op& o, int n, OpLaunch* out);
+int launch_op(yh_engine* h, const Op& o, int n, bool side = false);
+int enqueue_all(yh_engine* h, int n, int with_tail);
+int wait_input(yh_engine* h);
+int run(yh_engine* h, int with_tail);
+// weights.hip
+void build_conv_table(yh_engine* h);
+int alloc_panels(yh_engine* h);
+int check_blob(yh_engine* h, const uint8_t* b, size_t nbytes);
+int upload_panels(yh_engine* h, const uint8_t* blob);
+int ensure_blob(yh_engine* h);
+// fp8.hip
+void plan_fp8(yh_engine* h);
+std::string fp8_missing(const yh_engine* h);
+int refresh_fp8_scales(yh_engine* h, int sid = -1);
+
+}  // namespace yh

@@ -5,22 +5,15 @@
 // max_batch (every layer output stays resident: 288 GB of HBM make aliasing unnecessary and every
 // intermediate inspectable), a private stream, the repacked weight panels, and the op list that
 // yh_invoke / yh_evaluate replay (optionally as a captured hipGraph).
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
-#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <map>
-#include <atomic>
-#include <set>
-#include <string>
-#include <vector>
 
-#include "yh_internal.h"
+#include "engine.h"
 
 using namespace yh;
 
@@ -35,105 +28,15 @@ const RoctxApi& roctx_api() {   // resolved once per process (C++11 static initi
     return api;
 }
 SetupAudit& setup_audit() { static SetupAudit a; return a; }
-static std::atomic<int> g_rccl_shared_device{0};
-bool rccl_shared_device_allowed() { return g_rccl_shared_device.load() != 0; }
-}  // namespace yh
 
-namespace {
-
-thread_local std::string g_create_error;
-
-struct ConvDesc {          // one canonical conv of the blob
-    int cout, cin, k;
-    float gain;
-    int is_conf;   // 0 plain, 1 conf head (background bias), 2 mask head (bias)
-    size_t blob_w_off, blob_b_off;  // byte offsets in the canonical blob
-};
-
-struct Panel {             // device-side repacked weights of one launched conv
-    half_t* w = nullptr;   // [coutPad][Kpad]
-    float* bias = nullptr; // [coutPad]
-    int2* rs_table = nullptr;
-    int cout = 0, coutPad = 0, Kpad = 0, cin_store = 0, k = 0;
-    ConvTile tile = TILE_128x128;
-    std::vector<int> src;  // canonical conv indices concatenated along cout
-    int kcat = -1;         // >= 0: this canonical conv's weights are appended ALONG K (two-source 1x1 form, ConvParams::x2); biases add
-    // fp8 precision: the same weights as E4M3 codes, one scale per output channel
-    bool fp8 = false;
-    uint8_t* w8 = nullptr;     // [coutPad][Kpad] E4M3
-    float* scale = nullptr;    // [coutPad]: s_x (input tensor) * s_w[ch], refreshed by the calibration
-    std::vector<float> sw;     // [coutPad] weight scales (host)
-    int in_sid = -1;           // scale id of the input tensor these weights are applied to
-};
-
-struct Buf {               // dense NHWC f16 tensor [max_batch][h][w][c] or a slice of one
-    half_t* d = nullptr;
-    int h = 0, w = 0, c = 0;       // c = row stride in elements
-    long long img_stride = 0;      // elements per image
-    half_t* zero = nullptr;        // 16-byte zero block at the end of the owning allocation
-    // fp8 precision: the same tensor as E4M3 codes (same element offsets, one byte each), the allocation's scale id
-    uint8_t* q = nullptr;
-    uint8_t* qzero = nullptr;
-    int sid = -1;
-};
-
-enum OpKind { OP_PRE, OP_CONV, OP_POOL, OP_BILINEAR, OP_STEMPOOL };
-
-struct Op {
-    OpKind kind;
-    std::string name;      // layer name (matches the oracle's intermediate names)
-    std::string label;     // "kernel_symbol:layer"
-    Buf in, out, res;
-    bool has_res = false;
-    bool res_up = false;   // the residual is the bilinear resize of the lower-resolution tensor `res` (ConvParams::res_up)
-    int tail_op = -1;      // index of the 1x1 conv that may run in this conv's epilogue (ConvParams::w2) when the launch plan allows
-    // bottleneck chain (bneck.hip; tune.chain): on an identity block's 3x3 conv - the block's last 1x1 conv and (if any) the next
-    // block's first 1x1 conv that run inside its launch; on those two - the 3x3 conv that absorbs them
-    int chain_c = -1, chain_a = -1, in_chain = -1;
-    // ... the no-3x3 form (256 planes, layer 3): on the block's last 1x1 conv - the next block's first 1x1 conv that runs inside its
-    // launch; on that one - the conv that absorbs it
-    int xn_a = -1, in_xn = -1;
-    int fused_into = -1;   // ... and on that 1x1 conv: the index of the conv that may absorb it
-    bool side = false;     // may run on the second stream: nothing on the main stream reads its output before the step's join
-    bool dual = false;     // two-source 1x1 form: K continues over `in2` read at `stride2` (ConvParams::x2)
-    Buf in2;
-    int stride2 = 1;
-    int panel = -1;
-    int stride = 1, pad = 0, act = 0, tanh_from = INT_MAX;
-    int P = 0, Q = 0;      // output spatial
-    int nlev = 0, lev_start[5] = {0, 0, 0, 0, 0}, lev_h[5] = {0, 0, 0, 0, 0}, lev_w[5] = {0, 0, 0, 0, 0};   // multi-level input (ConvParams)
-    double flops_per_img = 0, bytes_per_img = 0, bytes_fixed = 0;
-    // fp8 precision: this conv reads E4M3 operands; what its output is written as (decided by who reads it)
-    bool fp8 = false, write_q = false, write_f16 = true;
-};
-
+static thread_local std::string g_create_error;
+std::string& create_error() { return g_create_error; }
 size_t pad16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 int out_dim(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
 
-uint64_t splitmix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-float unit_rand(uint64_t seed, uint64_t conv, uint64_t stream, uint64_t e) {
-    const uint64_t u = splitmix(splitmix(seed + conv * 1000003ull + stream) + e);
-    return ((float)(uint32_t)(u >> 40) - 8388608.0f) * (1.0f / 8388608.0f);
-}
-uint16_t f32_to_f16_bits(float f) {  // round to nearest even, IEEE binary16
-    const _Float16 h = (_Float16)f;
-    uint16_t b;
-    memcpy(&b, &h, 2);
-    return b;
-}
+}  // namespace yh
 
-}  // namespace
-
-// The handle's tuning with every default resolved (include/yolact_hip_debug.h: yh_tuning; -1 = default there).
-struct Tune {
-    int plan_cus, chsplit, upfuse, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, chain;
-};
 static Tune resolve_tuning(const yh_tuning& t, int device_cus) {
     auto d = [](int v, int def) { return v < 0 ? def : v; };
     Tune r;
@@ -144,99 +47,6 @@ static Tune resolve_tuning(const yh_tuning& t, int device_cus) {
     return r;
 }
 
-struct yh_engine {
-    yh_config cfg;
-    Tune tune;
-    int dev = 0, device_cus = 256;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;   // the detection tail's K1-K3 run here underneath the protonet
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_forks[4] = { nullptr, nullptr, nullptr, nullptr };   // one per fork point of a step (enqueue_all)
-    std::string err;
-
-    int S = 0, C = 0, ldh = 0;
-    int lvl[5] = { 0, 0, 0, 0, 0 }, lvl_off[5] = { 0, 0, 0, 0, 0 };
-    int cells = 0, P = 0, hp = 0, wp = 0;
-    double flops_per_frame = 0;
-
-    std::vector<ConvDesc> convs;
-    size_t blob_bytes = 0;
-    std::vector<Panel> panels;
-    std::vector<Op> ops;
-    std::vector<void*> allocs;
-    std::vector<size_t> alloc_bytes;   // parallel to allocs (yh_debug_alloc_map)
-    std::map<std::string, Buf> named;
-    std::set<std::string> fused_away;   // named tensors that production runs never write (debug_tensors = 1 materialises them)
-    // fp8 precision (yh_config.precision): per-allocation activation scales, filled by yh_fp8_calibrate
-    std::vector<float> act_scale;       // by Buf::sid
-    std::vector<char> scale_set;        // by Buf::sid: the scale was set by a calibration or by yh_fp8_set_layer_scale since the weights were loaded
-    std::vector<half_t*> alloc_base;    // first element of allocation sid
-    std::vector<long long> alloc_img;   // elements per image of allocation sid
-    std::vector<int> fp8_ops;           // indices of the ops that read E4M3 operands
-    std::set<std::string> q_only;       // named tensors that exist only as E4M3 while fp8 is active
-    bool fp8_active = false;            // the op list currently runs its fp8 form (false during calibration and in f16 engines)
-    bool fp8_ready = false;             // scales calibrated
-    unsigned* absmax_dev = nullptr;     // calibration scratch: kMaxFp8Tensors x kMaxFp8Channels channel maxima (as bit patterns)
-    static constexpr int kMaxFp8Tensors = 64, kMaxFp8Channels = 512;
-    // Round 4: one activation scale per CHANNEL of every allocation an fp8 convolution reads (a per-tensor scale is the same value in
-    // every channel). The channel scale is folded into the consumer's weights along K before their per-output-channel quantisation
-    // (refresh_fp8_scales) and the producer's epilogue multiplies by the reciprocal table instead of a scalar: no extra pass.
-    std::vector<std::vector<float>> act_ch;   // by Buf::sid ([alloc_c] floats; empty: not set)
-    std::vector<int> alloc_c;                 // channels (= row stride in elements) of allocation sid
-    std::vector<float*> inv_dev, sc_dev;      // by sid: device tables of 1 / scale and scale ([alloc_c]; fp8 handles only)
-    unsigned* rowmax_dev = nullptr;           // [1024]: row maxima of a weight panel with the channel scales folded in
-
-    // Two input buffers and a copy stream: yh_set_input_* fills the buffer the running step does NOT read, so frame k+1's
-    // host -> device copy runs underneath step k (the limiter of the sharded path is host-side H2D). A step is
-    // captured once per buffer (the stem kernel's source pointer is a launch argument).
-    uint8_t* in_buf[2] = { nullptr, nullptr };
-    int in_cur = 0;                 // the buffer the next step reads
-    bool in_pending = false;        // a copy into in_buf[in_cur] has been issued that no step has waited for yet
-    hipStream_t copy = nullptr;
-    hipEvent_t in_ready[2] = { nullptr, nullptr }, in_free[2] = { nullptr, nullptr };
-    bool in_free_rec[2] = { false, false };
-    uint8_t* in_u8() const { return in_buf[in_cur]; }
-    int in_hp = 0;
-    Buf in_f16, pyr, pyr_t, heads, proto;
-    float* priors_dev = nullptr;
-    std::vector<float> priors_host;
-
-    // tail workspaces / outputs
-    DetectParams det{};
-    // compat-path scratch
-    uint32_t* frame_dev = nullptr;
-    float* rs_tmp = nullptr;
-    float* cells_dev = nullptr;
-    uint32_t* codes_dev = nullptr;
-    uint32_t* stitch_dev = nullptr;
-    int* diverged_dev = nullptr;
-    size_t frame_cap = 0, rs_tmp_cap = 0;
-    // output staging
-    float* out_f32 = nullptr;
-    size_t out_f32_cap = 0;
-    float* splitk_ws = nullptr;
-    static const size_t kSplitKBytes = (size_t)48 << 20;
-
-    bool weights_loaded = false, capturing = false;
-    bool worker_mode = false;   // the handle is a group member being driven from its worker thread: no capture, no allocation there
-    unsigned* side_word = nullptr;   // target of the captured side-branch memset (enqueue_all)
-    uint8_t* blob_dev = nullptr;   // the canonical blob as loaded (send / receive buffer of the RCCL weight broadcast)
-    int cur_n = 0;
-    static constexpr size_t kStageBytes = 4u << 20;   // pinned staging for small host inputs
-    uint8_t* stage[2] = { nullptr, nullptr };
-    hipEvent_t stage_ev[2] = { nullptr, nullptr };
-    int stage_idx = 0;
-    int last_conv_launches = 0;   // yh_debug_last_conv_launches
-    bool stem_fused = false;
-    int tail_fork_op = 0;   // ops[tail_fork_op..] (the protonet) do not feed the tail's K1-K3
-    int head_fork_op = 0;   // ops[head_fork_op .. tail_fork_op) are the shared prediction head; the protonet does not read them
-    float* splitk_ws_side = nullptr;   // split-K workspace of convolutions launched on the side stream
-    std::map<int, hipGraphExec_t> graphs;  // key = n*2 + with_tail
-    std::vector<std::string> prof_labels;  // storage behind the names yh_profile_run returns
-
-    int fail(int code, const std::string& m) { err = m; return code; }
-};
-
 namespace yh {
 void engine_set_worker_mode(yh_engine* h, bool on) { h->worker_mode = on; }
 bool engine_uses_graph(const yh_engine* h) { return h->cfg.use_graph != 0; }
@@ -245,25 +55,17 @@ bool engine_step_prepared(const yh_engine* h, int n_frames, int with_tail) {
     const int key0 = (n_frames * 2 + (with_tail ? 1 : 0)) * 2;
     return h->graphs.count(key0) && h->graphs.count(key0 | 1);
 }
-}  // namespace yh
-
-#define HIPCHK(h, call)                                                                        \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return (h)->fail(YH_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-namespace {
-
 int dev_alloc(yh_engine* h, void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) return h->fail(YH_ENOMEM, std::string("hipMalloc ") + std::to_string(bytes) + ": " + hipGetErrorString(e));
-    h->allocs.push_back(*p);
-    h->alloc_bytes.push_back(bytes);
+    h->allocs.push_back(DevAlloc{ *p, bytes });
     return YH_OK;
 }
+
+}  // namespace yh
+
+namespace {
 
 int new_buf(yh_engine* h, const char* name, int hh, int ww, int c, Buf* out) {
     Buf b;
@@ -276,13 +78,13 @@ int new_buf(yh_engine* h, const char* name, int hh, int ww, int c, Buf* out) {
     if (hipMemset(p, 0, data_bytes + 256) != hipSuccess) return h->fail(YH_EHIP, "hipMemset arena");
     b.d = (half_t*)p;
     b.zero = (half_t*)((char*)p + ((data_bytes + 15) & ~(size_t)15));
-    b.sid = (int)h->act_scale.size();
-    h->act_scale.push_back(1.0f); h->scale_set.push_back(0); h->alloc_base.push_back(b.d); h->alloc_img.push_back(b.img_stride);
-    h->act_ch.emplace_back(); h->alloc_c.push_back(c); h->inv_dev.push_back(nullptr); h->sc_dev.push_back(nullptr);
+    b.sid = (int)h->act.size();
+    h->act.emplace_back();
+    h->act.back().base = b.d; h->act.back().img = b.img_stride; h->act.back().c = c;
     if (h->cfg.precision == YH_PRECISION_FP8) {   // the E4M3 twin (288 GB of HBM: no aliasing games)
         void* t = nullptr;
         const std::vector<float> ones((size_t)c, 1.0f);
-        for (float** tab : { &h->inv_dev.back(), &h->sc_dev.back() }) {
+        for (float** tab : { &h->act.back().inv_dev, &h->act.back().sc_dev }) {
             if ((rc = dev_alloc(h, &t, (size_t)c * 4))) return rc;
             if (hipMemcpy(t, ones.data(), (size_t)c * 4, hipMemcpyHostToDevice) != hipSuccess) return h->fail(YH_EHIP, "scale table upload");
             *tab = (float*)t;
@@ -299,52 +101,18 @@ int new_buf(yh_engine* h, const char* name, int hh, int ww, int c, Buf* out) {
     return YH_OK;
 }
 
+}  // namespace
+
+namespace yh {
+
 int blocks_of(int backbone, int layer) {
     static const int r50[4] = { 3, 4, 6, 3 }, r101[4] = { 3, 4, 23, 3 };
     return backbone == YH_BACKBONE_R101 ? r101[layer] : r50[layer];
 }
 
-// Canonical conv table (DESIGN.md §Weight blob) — order defines the blob layout.
-void build_conv_table(yh_engine* h) {
-    auto add = [&](int co, int ci, int k, float g, int conf) {
-        ConvDesc d; d.cout = co; d.cin = ci; d.k = k; d.gain = g; d.is_conf = conf; d.blob_w_off = d.blob_b_off = 0;
-        h->convs.push_back(d);
-    };
-    add(64, 3, 7, 1.0f, 0);
-    int inc = 64;
-    for (int L = 0; L < 4; ++L) {
-        const int planes = 64 << L;
-        // a block's last conv: gain 0.3 in stages of up to six blocks; ResNet-101's 23-block stage scales it by sqrt(6 / blocks) so
-        // that the residual stream grows over the stage as it does in ResNet-50 (the same two f32 operations as the oracle)
-        const int nb_stage = blocks_of(h->cfg.backbone, L);
-        const float g3 = nb_stage > 6 ? 0.3f * sqrtf(6.0f / (float)nb_stage) : 0.3f;
-        for (int b = 0; b < blocks_of(h->cfg.backbone, L); ++b) {
-            add(planes, inc, 1, 1.0f, 0);
-            add(planes, planes, 3, 1.0f, 0);
-            add(planes * 4, planes, 1, g3, 0);
-            if (b == 0) add(planes * 4, inc, 1, 1.0f, 0);
-            inc = planes * 4;
-        }
-    }
-    add(256, 2048, 1, 0.2f, 0); add(256, 1024, 1, 0.2f, 0); add(256, 512, 1, 0.2f, 0);
-    for (int i = 0; i < 3; ++i) add(256, 256, 3, 0.7f, 0);
-    for (int i = 0; i < 2; ++i) add(256, 256, 3, 1.0f, 0);
-    for (int i = 0; i < 4; ++i) add(256, 256, 3, 1.0f, 0);
-    add(32, 256, 1, 1.0f, 0);
-    add(256, 256, 3, 1.0f, 0);
-    add(12, 256, 3, 2.0f, 0);
-    add(3 * h->C, 256, 3, 0.7f, 1);
-    add(96, 256, 3, 0.5f, 2);
-    size_t off = 16;
-    for (auto& d : h->convs) {
-        off += 16;
-        d.blob_w_off = off;
-        off += pad16((size_t)d.cout * d.k * d.k * d.cin * 2);
-        d.blob_b_off = off;
-        off += pad16((size_t)d.cout * 4);
-    }
-    h->blob_bytes = off;
-}
+}  // namespace yh
+
+namespace {
 
 // K from which layers with at least 128 output channels get the 8-wave tiles
 constexpr int kBigK = 256;
@@ -668,66 +436,6 @@ int build_graph_spec(yh_engine* h) {
     return YH_OK;
 }
 
-// fp8 precision: which convolutions read E4M3 operands, and what each producer therefore writes.
-// Rule: 3x3 convolutions with >= 256 input channels (a multiple of 128: one 128-byte LDS row is
-// one K step of the block-scaled MFMA) and a multiple of 256 output channels (the fp8 kernel's tile). Everything else
-// stays f16. A tensor read only by fp8 convolutions is stored only as E4M3; one with both kinds of reader (the FPN
-// laterals: pred conv and bilinear upsample) is written in both forms by its producer's epilogue.
-void plan_fp8(yh_engine* h) {
-    struct Range { int sid; long long off, len; };
-    auto range = [&](const Buf& b) { return Range{ b.sid, (long long)(b.d - h->alloc_base[b.sid]), (long long)b.h * b.w * b.c }; };
-    auto overlap = [](const Range& a, const Range& b) { return a.sid == b.sid && a.off < b.off + b.len && b.off < a.off + a.len; };
-    for (size_t i = 0; i < h->ops.size(); ++i) {
-        Op& o = h->ops[i];
-        if (o.kind != OP_CONV) continue;
-        Panel& pn = h->panels[o.panel];
-        const ConvDesc& d0 = h->convs[pn.src[0]];
-        // (yh_config.fp8_f16_layers: groups kept in f16 - bit 0 head trunk, 1 protonet, 2 FPN pred / down, 3 backbone)
-        const int keep = h->cfg.fp8_f16_layers;
-        const bool is_head = o.name.compare(0, 6, "head_t") == 0, is_proto = o.name.compare(0, 5, "proto") == 0, is_bb = o.name[0] == 'l';
-        const bool is_fpn = o.name[0] == 'p' && !is_proto;
-        if (((keep & 1) && is_head) || ((keep & 2) && is_proto) || ((keep & 4) && is_fpn) || ((keep & 8) && is_bb)) continue;
-        if (pn.k == 3 && d0.cin % 128 == 0 && d0.cin >= 256 && pn.cout % 256 == 0 && pn.coutPad % 256 == 0 && o.in.q) {
-            o.fp8 = true; pn.fp8 = true; pn.in_sid = o.in.sid;
-            h->fp8_ops.push_back((int)i);
-        }
-    }
-    for (size_t i = 0; i < h->ops.size(); ++i) {
-        Op& o = h->ops[i];
-        if (o.kind == OP_PRE) continue;
-        const Range w = range(o.out);
-        bool need_q = false, need_f16 = h->cfg.debug_tensors != 0;
-        for (size_t j = i + 1; j < h->ops.size(); ++j) {
-            const Op& c = h->ops[j];
-            if (c.kind == OP_PRE) continue;
-            if (overlap(w, range(c.in))) { if (c.fp8) need_q = true; else need_f16 = true; }
-            if (c.has_res && c.kind == OP_CONV && overlap(w, range(c.res))) need_f16 = true;
-            if (c.dual && overlap(w, range(c.in2))) need_f16 = true;
-        }
-        if (overlap(w, range(h->heads)) || overlap(w, range(h->proto))) need_f16 = true;   // engine outputs, read by the tail
-        if (!need_q && !need_f16) need_f16 = true;
-        o.write_q = need_q; o.write_f16 = need_f16;
-    }
-    // accounting (profile / roofline): E4M3 operands are one byte
-    for (Op& o : h->ops) {
-        if (o.kind != OP_CONV && o.kind != OP_BILINEAR) continue;
-        const double out_b = (o.write_f16 ? 2.0 : 0.0) + (o.write_q ? 1.0 : 0.0);
-        if (o.kind == OP_BILINEAR) { o.bytes_per_img = 2.0 * o.in.c * (double)o.in.h * o.in.w + out_b * o.in.c * (double)o.out.h * o.out.w; continue; }
-        const Panel& pn = h->panels[o.panel];
-        const ConvDesc& d0 = h->convs[pn.src[0]];
-        if (o.dual) continue;   // (f16 on both sides: the figures set at construction stand)
-        const double K = (double)pn.k * pn.k * d0.cin, in_elems = o.nlev ? (double)h->cells * d0.cin : (double)o.in.h * o.in.w * d0.cin;
-        o.bytes_per_img = (o.fp8 ? 1.0 : 2.0) * in_elems + (double)o.P * o.Q * pn.cout * (out_b + (o.has_res ? 2.0 : 0.0));
-        o.bytes_fixed = (o.fp8 ? 1.0 : 2.0) * pn.cout * K;
-        if (o.fp8) o.label = std::string(conv_tile_symbol(TILE_256x256_FP8)) + ":" + o.name;
-    }
-    for (const auto& kv : h->named) {
-        const Range r = range(kv.second);
-        for (const Op& o : h->ops)
-            if (o.kind != OP_PRE && overlap(r, range(o.out)) && !o.write_f16) h->q_only.insert(kv.first);
-    }
-}
-
 void build_priors(yh_engine* h) {
     static const float ars[3] = { 1.0f, 0.5f, 2.0f };
     h->priors_host.resize((size_t)h->P * 4);
@@ -866,9 +574,9 @@ int tail_split_tiles(const Tune& tu, int coutPad, const ConvParams& p, ConvTile 
     return mt1 >= 1 && mt1 < m_tiles ? mt1 : 0;
 }
 
-// A convolution is planned as one to two kernel launches; `frac` is the share of the op's
-// algorithmic work a launch does (profile attribution), `what` a label suffix.
-struct KLaunch { bool reduce; ConvParams p; ConvTile tile; double frac; const char* what; };
+}  // namespace
+
+namespace yh {
 
 int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, KLaunch out[3]) {
     if (p.k_slices > 1) {   // split-K: main kernel + slab reduction
@@ -923,7 +631,7 @@ hipError_t launch_k(const KLaunch& k, hipStream_t stream) {
     return k.reduce ? launch_splitk_reduce(k.p, stream) : launch_conv(k.p, k.tile, stream);
 }
 
-hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches = nullptr) {
+hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches) {
     KLaunch k[3];
     const int nk = plan_conv(tu, p, tile, coutPad, k);
     if (n_launches) *n_launches = p.k_slices > 1 ? 1 : nk;   // (the split-K reduce is not counted: include/yolact_hip.h)
@@ -934,6 +642,22 @@ hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile til
     return hipSuccess;
 }
 
+}  // namespace yh
+
+namespace {
+
+// The buffer descriptor of a conv operand: the offset of the allocation's zero block from the base has to lie in
+// [0, 0xFFFFFF00); the descriptor covers the data and that block (offset + 16 bytes). q: the tensor's E4M3 twin.
+const char* const kInputRange = "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch";
+const char* const kResidualRange = "conv residual exceeds the 4 GiB buffer-descriptor range: lower max_batch";
+int desc_range(yh_engine* h, const Buf& b, bool q, const char* msg, unsigned* zero_off, unsigned* bytes) {
+    const long long zo = q ? b.qzero - b.q : (const char*)b.zero - (const char*)b.d;
+    if (zo < 0 || zo >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, msg);
+    *zero_off = (unsigned)zo;
+    *bytes = (unsigned)zo + 16u;
+    return YH_OK;
+}
+
 int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile* tile_out = nullptr) {
     const Panel& pn = h->panels[o.panel];
     ConvParams p;
@@ -942,10 +666,7 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     p.res = o.has_res ? o.res.d : nullptr;
     p.x_img_stride = o.in.img_stride; p.y_img_stride = o.out.img_stride;
     p.res_img_stride = o.has_res ? o.res.img_stride : 0;
-    const long long zo = (const char*)o.in.zero - (const char*)o.in.d;
-    if (zo < 0 || zo >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
-    p.x_zero_off = (unsigned)zo;
-    p.x_bytes = (unsigned)zo + 16u;
+    if (desc_range(h, o.in, false, kInputRange, &p.x_zero_off, &p.x_bytes)) return YH_EINVAL;
     p.w_bytes = (unsigned)((size_t)pn.coutPad * pn.Kpad * 2);
     p.N = n; p.H = o.in.h; p.W = o.in.w; p.C = pn.cin_store;
     p.P = o.P; p.Q = o.Q; p.R = pn.k; p.S = pn.k; p.stride = o.stride; p.pad = o.pad;
@@ -957,9 +678,8 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     p.y_dense = (o.out.img_stride == pq * o.out.c) && (!o.has_res || o.res_up || o.res.img_stride == pq * o.res.c);
     if (o.res_up) { p.res_up = 1; p.res_h = o.res.h; p.res_w = o.res.w; }
     if (o.dual) {
-        const long long z2 = (const char*)o.in2.zero - (const char*)o.in2.d;
-        if (z2 < 0 || z2 >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
-        p.x2 = o.in2.d; p.x2_img_stride = o.in2.img_stride; p.x2_zero_off = (unsigned)z2; p.x2_bytes = (unsigned)z2 + 16u;
+        if (desc_range(h, o.in2, false, kInputRange, &p.x2_zero_off, &p.x2_bytes)) return YH_EINVAL;
+        p.x2 = o.in2.d; p.x2_img_stride = o.in2.img_stride;
         p.W2 = o.in2.w; p.C2 = o.in2.c; p.stride2 = o.stride2; p.k1steps = pn.cin_store / 64;
         if (h->tune.ablate & 1) { p.x2_bytes = 0; }
     }
@@ -975,13 +695,12 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     if (h->fp8_active) {
         // fp8 precision, calibrated: what this op's output is written as, and (for the K-heavy 3x3 layers) E4M3 operands
         p.y = o.write_f16 ? o.out.d : nullptr;
-        if (o.write_q) { p.y8 = o.out.q; p.y8_inv = h->inv_dev[o.out.sid]; }
+        if (o.write_q) { p.y8 = o.out.q; p.y8_inv = h->act[o.out.sid].inv_dev; }
         if (o.fp8) {
             // the loader's units stay 2 bytes: two E4M3 values (ConvParams: "fp8 form")
-            const long long zq = o.in.qzero - o.in.q;
-            if (zq < 0 || zq >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
+            if (desc_range(h, o.in, true, kInputRange, &p.x_zero_off, &p.x_bytes)) return YH_EINVAL;
             p.x = (const half_t*)o.in.q; p.w = (const half_t*)pn.w8; p.scale = pn.scale;
-            p.x_zero_off = (unsigned)zq; p.x_bytes = (unsigned)zq + 16u; p.w_bytes = (unsigned)((size_t)pn.coutPad * pn.Kpad);
+            p.w_bytes = (unsigned)((size_t)pn.coutPad * pn.Kpad);
             if (h->tune.ablate & 1) { p.x_bytes = 0; }
             if (h->tune.ablate & 2) { p.w_bytes = 0; }
             p.C = pn.cin_store / 2; p.ldw = pn.Kpad / 2; p.ksteps = pn.Kpad / 128; p.x_img_stride = o.in.img_stride / 2;
@@ -1029,6 +748,10 @@ int fill_conv_params(yh_engine* h, const Op& o, int n, ConvParams* out, ConvTile
     return YH_OK;
 }
 
+}  // namespace
+
+namespace yh {
+
 // side: the op runs on the side stream (with that stream's split-K workspace) - convolutions only
 // Is this 1x1 conv computed in the epilogue of the conv in front of it at batch n?
 bool conv_absorbed(yh_engine* h, const Op& o, int n) {
@@ -1037,9 +760,18 @@ bool conv_absorbed(yh_engine* h, const Op& o, int n) {
     return fill_conv_params(h, h->ops[o.fused_into], n, &p) == YH_OK && p.w2 != nullptr;
 }
 
+}  // namespace yh
+
+namespace {
+
+int chain_tile_m(const yh_engine* h, const Op& ob, int n);
+
+}  // namespace
+
+namespace yh {
+
 // Does the bottleneck chain headed by the 3x3 conv `ob` run as one launch at batch n? (f16 tensors only, dense rows, not when
 // every intermediate must be materialised for yh_debug_read_tensor.)
-int chain_tile_m(const yh_engine* h, const Op& ob, int n);
 bool chain_active(const yh_engine* h, const Op& ob, int n) {
     if (!(h->tune.chain & 1) || h->cfg.debug_tensors || ob.chain_c < 0 || n < 1) return false;
     // Launches too small for the big tiles fuse on 64-pixel tiles (tune.chain bit 4, part of the default): per step, interleaved
@@ -1063,6 +795,11 @@ bool chain_active(const yh_engine* h, const Op& ob, int n) {
     }
     return true;
 }
+
+}  // namespace yh
+
+namespace {
+
 int chain_tile_m(const yh_engine* h, const Op& ob, int n) {
     if (h->ops[ob.chain_c].dual) return ((long long)n * ob.P * ob.Q >= 8ll * h->tune.plan_cus * 128 || (h->tune.chain & 16)) ? 128 : 0;   // (one tile size; 0: inactive)
     const int planes = h->panels[ob.panel].cout, big = planes == 64 ? 256 : 128;
@@ -1076,17 +813,16 @@ int fill_bneck_params(yh_engine* h, const Op& ob, int n, BneckParams* out) {
     const Panel &pb = h->panels[ob.panel], &pcn = h->panels[oc.panel];
     BneckParams p;
     memset(&p, 0, sizeof p);
-    const long long zo = (const char*)ob.in.zero - (const char*)ob.in.d;
-    if (zo < 0 || zo >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
-    p.a = ob.in.d; p.a_zero_off = (unsigned)zo; p.a_bytes = (unsigned)zo + 16u; p.a_img_stride = ob.in.img_stride;
+    unsigned unused_off;
+    if (desc_range(h, ob.in, false, kInputRange, &p.a_zero_off, &p.a_bytes)) return YH_EINVAL;
+    p.a = ob.in.d; p.a_img_stride = ob.in.img_stride;
     p.N = n; p.H = ob.in.h; p.W = ob.in.w; p.P = ob.P; p.Q = ob.Q; p.stride = ob.stride; p.M = n * ob.P * ob.Q;
     p.w2 = pb.w; p.w2_bytes = (unsigned)((size_t)pb.coutPad * pb.Kpad * 2); p.bias2 = pb.bias;
     p.w3 = pcn.w; p.w3_bytes = (unsigned)((size_t)pcn.coutPad * pcn.Kpad * 2); p.bias3 = pcn.bias;
     p.res = oc.dual ? nullptr : oc.res.d; p.y = oc.out.d;
     if (oc.dual) {
-        const long long z2 = (const char*)oc.in2.zero - (const char*)oc.in2.d;
-        if (z2 < 0 || z2 >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
-        p.x2 = oc.in2.d; p.x2_bytes = (unsigned)z2 + 16u; p.x2_img_stride = oc.in2.img_stride; p.W2 = oc.in2.w; p.C2 = oc.in2.c; p.stride2 = oc.stride2;
+        if (desc_range(h, oc.in2, false, kInputRange, &unused_off, &p.x2_bytes)) return YH_EINVAL;
+        p.x2 = oc.in2.d; p.x2_img_stride = oc.in2.img_stride; p.W2 = oc.in2.w; p.C2 = oc.in2.c; p.stride2 = oc.stride2;
     }
     if (pb.Kpad != 9 * pb.cout || pcn.Kpad != pb.cout + (oc.dual ? oc.in2.c : 0) || pcn.cout != 4 * pb.cout) return h->fail(YH_EINVAL, "bottleneck chain: panel geometry mismatch at " + ob.name);
     if (ob.chain_a >= 0) {
@@ -1131,31 +867,24 @@ int fill_xn_params(yh_engine* h, const Op& oc, int n, BneckParams* out) {
     const Panel &pc = h->panels[oc.panel], &pa = h->panels[oa.panel];
     BneckParams p;
     memset(&p, 0, sizeof p);
-    const long long zo = (const char*)oc.in.zero - (const char*)oc.in.d;
-    if (zo < 0 || zo >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv input exceeds the 4 GiB buffer-descriptor range: lower max_batch");
+    unsigned unused_off;
+    if (desc_range(h, oc.in, false, kInputRange, &p.a_zero_off, &p.a_bytes)) return YH_EINVAL;
     p.no_b = 1;
-    p.a = oc.in.d; p.a_zero_off = (unsigned)zo; p.a_bytes = (unsigned)zo + 16u; p.a_img_stride = oc.in.img_stride;
+    p.a = oc.in.d; p.a_img_stride = oc.in.img_stride;
     p.N = n; p.H = oc.in.h; p.W = oc.in.w; p.P = oc.P; p.Q = oc.Q; p.stride = 1; p.M = n * oc.P * oc.Q;
     p.w3 = pc.w; p.w3_bytes = (unsigned)((size_t)pc.coutPad * pc.Kpad * 2); p.bias3 = pc.bias;
     p.res = oc.res.d; p.y = oc.out.d;
-    const long long zr = (const char*)oc.res.zero - (const char*)oc.res.d;
-    if (zr < 0 || zr >= 0xFFFFFF00ll) return h->fail(YH_EINVAL, "conv residual exceeds the 4 GiB buffer-descriptor range: lower max_batch");
-    p.res_bytes = (unsigned)zr + 16u;
+    if (desc_range(h, oc.res, false, kResidualRange, &unused_off, &p.res_bytes)) return YH_EINVAL;
     p.w1n = pa.w; p.w1n_bytes = (unsigned)((size_t)pa.coutPad * pa.Kpad * 2); p.bias1n = pa.bias;
     p.a_next = (!h->fp8_active || oa.write_f16) ? oa.out.d : nullptr;
-    if (h->fp8_active && oa.write_q) { p.a_next8 = oa.out.q; p.a_next8_inv = h->inv_dev[oa.out.sid]; }
+    if (h->fp8_active && oa.write_q) { p.a_next8 = oa.out.q; p.a_next8_inv = h->act[oa.out.sid].inv_dev; }
     *out = p;
     return YH_OK;
 }
 
-// What op `o` becomes at batch n. Decided here only: launch_op issues the plan, the profiler lists and labels the same plan.
-struct OpLaunch {
-    enum Form { SKIP, XN, CHAIN, CONV, OTHER } form;   // SKIP: computed inside another op's launch; OTHER: not a convolution
-    int planes, tile_m;                                // XN, CHAIN: launch_bneck's arguments besides bp
-    BneckParams bp;
-    ConvParams p;                                      // CONV: plan_conv's arguments besides the panel's coutPad
-    ConvTile tile;
-};
+}  // namespace
+
+namespace yh {
 
 int plan_op(yh_engine* h, const Op& o, int n, OpLaunch* out) {
     out->form = o.kind == OP_CONV ? OpLaunch::SKIP : OpLaunch::OTHER;
@@ -1172,7 +901,7 @@ int plan_op(yh_engine* h, const Op& o, int n, OpLaunch* out) {
     return fill_conv_params(h, o, n, &out->p, &out->tile);
 }
 
-int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
+int launch_op(yh_engine* h, const Op& o, int n, bool side) {
     OpLaunch pl;
     const int rc = plan_op(h, o, n, &pl);
     if (rc || pl.form == OpLaunch::SKIP) return rc;
@@ -1197,7 +926,7 @@ int launch_op(yh_engine* h, const Op& o, int n, bool side = false) {
         case OP_BILINEAR:
             if (h->fp8_active)
                 e = launch_bilinear(o.in.d, o.write_f16 ? o.out.d : nullptr, n, o.in.h, o.in.w, o.in.c, o.P, o.Q, o.in.img_stride, o.out.img_stride, h->stream,
-                                    o.write_q ? o.out.q : nullptr, o.write_q ? h->inv_dev[o.out.sid] : nullptr);
+                                    o.write_q ? o.out.q : nullptr, o.write_q ? h->act[o.out.sid].inv_dev : nullptr);
             else e = launch_bilinear(o.in.d, o.out.d, n, o.in.h, o.in.w, o.in.c, o.P, o.Q, o.in.img_stride, o.out.img_stride, h->stream);
             break;
         case OP_STEMPOOL: {
@@ -1291,14 +1020,6 @@ int enqueue_all(yh_engine* h, int n, int with_tail) {
     return YH_OK;
 }
 
-// fp8 precision: the E4M3 layers whose input tensor has no scale yet (comma-separated; empty = every tensor is set)
-std::string fp8_missing(const yh_engine* h) {
-    std::string out;
-    for (int oi : h->fp8_ops)
-        if (!h->scale_set[h->ops[oi].in.sid]) out += (out.empty() ? "" : ", ") + h->ops[oi].name;
-    return out;
-}
-
 // The step about to be enqueued on the main stream reads in_buf[in_cur]: if a copy into it is still pending on the copy
 // stream, the main stream waits for it (once per set_input).
 int wait_input(yh_engine* h) {
@@ -1307,6 +1028,10 @@ int wait_input(yh_engine* h) {
     h->in_pending = false;
     return YH_OK;
 }
+
+}  // namespace yh
+
+namespace {
 
 // Once-only work - a graph capture (hipStreamBeginCapture ... hipGraphInstantiate, and with it the first resolution of every kernel
 // of the step on this device) - happens on the thread that calls into the library, never on a group's worker thread, and a group
@@ -1331,6 +1056,10 @@ int capture_step(yh_engine* h, int n, int with_tail, hipGraphExec_t* out) {
     *out = ge;
     return YH_OK;
 }
+
+}  // namespace
+
+namespace yh {
 
 int run(yh_engine* h, int with_tail) {
     if (!h->weights_loaded) return h->fail(YH_ESTATE, "weights not loaded");
@@ -1372,151 +1101,6 @@ int run(yh_engine* h, int with_tail) {
     return YH_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// weights
-// ------------------------------------------------------------------------------------------------
-int alloc_panels(yh_engine* h) {
-    for (Panel& p : h->panels) {
-        void* q;
-        int rc;
-        if ((rc = dev_alloc(h, &q, (size_t)p.coutPad * p.Kpad * 2))) return rc;
-        p.w = (half_t*)q;
-        if ((rc = dev_alloc(h, &q, (size_t)p.coutPad * 4))) return rc;
-        p.bias = (float*)q;
-        if (p.fp8) {
-            if ((rc = dev_alloc(h, &q, (size_t)p.coutPad * p.Kpad))) return rc;
-            p.w8 = (uint8_t*)q;
-            if ((rc = dev_alloc(h, &q, (size_t)p.coutPad * 4))) return rc;
-            p.scale = (float*)q;
-        }
-        if (p.tile == TILE_64x256_SMALLC) {
-            const int nt = p.Kpad / 8, cpr = (p.k + 1) / 2;  // chunks per kernel row
-            std::vector<int2> t(nt);
-            for (int i = 0; i < nt; ++i) t[i] = i < p.k * cpr ? make_int2(i / cpr, 2 * (i % cpr)) : make_int2(1 << 20, 0);
-            if ((rc = dev_alloc(h, &q, sizeof(int2) * nt))) return rc;
-            p.rs_table = (int2*)q;
-            HIPCHK(h, hipMemcpy(q, t.data(), sizeof(int2) * nt, hipMemcpyHostToDevice));
-        }
-    }
-    return YH_OK;
-}
-
-int check_blob(yh_engine* h, const uint8_t* b, size_t nbytes) {
-    if (nbytes != h->blob_bytes) return h->fail(YH_EWEIGHTS, "weight blob size mismatch");
-    if (memcmp(b, "YHW1", 4) != 0) return h->fail(YH_EWEIGHTS, "weight blob magic mismatch");
-    uint32_t hdr[3];
-    memcpy(hdr, b + 4, 12);
-    if (hdr[0] != h->convs.size() || (int)hdr[1] != h->cfg.backbone || (int)hdr[2] != h->C)
-        return h->fail(YH_EWEIGHTS, "weight blob header does not match the architecture");
-    for (const ConvDesc& d : h->convs) {
-        uint32_t rec[4];
-        memcpy(rec, b + d.blob_w_off - 16, 16);
-        if ((int)rec[0] != d.cout || (int)rec[1] != d.cin || (int)rec[2] != d.k || (int)rec[3] != d.k)
-            return h->fail(YH_EWEIGHTS, "weight blob layer record mismatch");
-    }
-    return YH_OK;
-}
-
-// One activation scale per channel of allocation `sid` (host copy, device tables of the scale and of its reciprocal).
-int set_sid_scales(yh_engine* h, int sid, const std::vector<float>& v) {
-    if ((int)v.size() != h->alloc_c[sid] || !h->inv_dev[sid]) return h->fail(YH_EINVAL, "fp8: channel scale count does not match the tensor");
-    std::vector<float> inv(v.size());
-    float mx = 0.0f;
-    for (size_t c = 0; c < v.size(); ++c) {
-        if (!(v[c] > 0.0f) || !(v[c] < 3.0e38f)) return h->fail(YH_EINVAL, "activation scale must be a positive finite number");
-        inv[c] = 1.0f / v[c];
-        mx = v[c] > mx ? v[c] : mx;
-    }
-    HIPCHK(h, hipMemcpy(h->inv_dev[sid], inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->sc_dev[sid], v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    h->act_ch[sid] = v;
-    h->act_scale[sid] = mx;      // (what yh_fp8_layer_info reports: the largest channel scale)
-    h->scale_set[sid] = 1;
-    return YH_OK;
-}
-
-// The E4M3 weights of the fp8 convolutions that read allocation `sid` (-1: all of them): the input tensor's channel scales s[c]
-// are folded into the K axis, then one scale per output channel - t = w * s[c], s_w = max_k |t| / 448 (1 for an all-zero row),
-// codes = e4m3(t * (1 / s_w)) by the device's own conversion - and the epilogue's multiplier is s_w alone
-// (y = fma(acc, s_w[ch], bias)). The same operations in the same order as oracle/orc_net.c's fp8 forward mode.
-int refresh_fp8_scales(yh_engine* h, int sid = -1) {
-    if (!h->weights_loaded) return YH_OK;
-    for (Panel& p : h->panels) {
-        if (!p.fp8 || (sid >= 0 && p.in_sid != sid) || h->act_ch[p.in_sid].empty()) continue;
-        if (p.coutPad > 1024 || h->alloc_c[p.in_sid] != p.cin_store) return h->fail(YH_EINVAL, "fp8: weight panel geometry");
-        const float* col = h->sc_dev[p.in_sid];
-        if (launch_rowmax_scaled_f16(p.w, p.coutPad, p.Kpad, p.cin_store, col, h->rowmax_dev, h->stream) != hipSuccess) return h->fail(YH_EHIP, "weight row maxima launch failed");
-        std::vector<unsigned> bits(p.coutPad);
-        HIPCHK(h, hipMemcpyAsync(bits.data(), h->rowmax_dev, bits.size() * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        p.sw.assign(p.coutPad, 1.0f);
-        std::vector<float> inv(p.coutPad, 1.0f);
-        for (int r = 0; r < p.coutPad; ++r) {
-            float a; memcpy(&a, &bits[r], 4);
-            p.sw[r] = a > 0.0f ? a / 448.0f : 1.0f;
-            inv[r] = 1.0f / p.sw[r];
-        }
-        HIPCHK(h, hipMemcpy(p.scale, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));   // (borrowed as the 1 / s_w table for this one launch)
-        if (launch_quantize_rows_e4m3(p.w, p.w8, p.coutPad, p.Kpad, p.cin_store, col, p.scale, h->stream) != hipSuccess) return h->fail(YH_EHIP, "weight quantisation launch failed");
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(p.scale, p.sw.data(), p.sw.size() * 4, hipMemcpyHostToDevice));
-    }
-    return YH_OK;
-}
-
-int upload_panels(yh_engine* h, const uint8_t* blob) {
-    HIPCHK(h, hipSetDevice(h->dev));
-    for (Panel& p : h->panels) {
-        std::vector<uint16_t> w((size_t)p.coutPad * p.Kpad, 0);
-        std::vector<float> bias(p.coutPad, 0.0f);
-        int row0 = 0;
-        for (int s : p.src) {
-            const ConvDesc& d = h->convs[s];
-            const uint16_t* src = (const uint16_t*)(blob + d.blob_w_off);
-            const size_t K = (size_t)d.k * d.k * d.cin;
-            for (int o = 0; o < d.cout; ++o) {
-                uint16_t* dst = w.data() + (size_t)(row0 + o) * p.Kpad;
-                if (p.cin_store == d.cin) memcpy(dst, src + (size_t)o * K, K * 2);
-                else {  // stem: chunk (r, j) holds pixels s = 2j, 2j+1 with 4 channels each; s = k and c = 3 are zero
-                    const int cpr = (d.k + 1) / 2;
-                    for (int r = 0; r < d.k; ++r)
-                        for (int sx = 0; sx < d.k; ++sx)
-                            for (int c = 0; c < d.cin; ++c)
-                                dst[(size_t)(r * cpr + sx / 2) * 8 + (sx & 1) * 4 + c] = src[(size_t)o * K + ((size_t)r * d.k + sx) * d.cin + c];
-                }
-            }
-            memcpy(bias.data() + row0, blob + d.blob_b_off, (size_t)d.cout * 4);
-            row0 += d.cout;
-        }
-        if (p.kcat >= 0) {   // two-source form: the second conv's rows continue along K, its bias adds (one f32 addition)
-            const ConvDesc& d = h->convs[p.kcat];
-            const size_t K1 = (size_t)p.Kpad - d.cin;
-            const uint16_t* src = (const uint16_t*)(blob + d.blob_w_off);
-            const float* b2 = (const float*)(blob + d.blob_b_off);
-            for (int o = 0; o < d.cout; ++o) {
-                memcpy(w.data() + (size_t)o * p.Kpad + K1, src + (size_t)o * d.cin, (size_t)d.cin * 2);
-                float bb; memcpy(&bb, b2 + o, 4);
-                bias[o] = bias[o] + bb;
-            }
-        }
-        HIPCHK(h, hipMemcpy(p.w, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(p.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-        // (fp8 panels: the E4M3 codes depend on the input tensor's channel scales - refresh_fp8_scales makes them once those are known)
-    }
-    if (h->weights_loaded && h->cfg.precision == YH_PRECISION_FP8) {
-        // a RE-load: the activation scales were calibrated for the old weights - they have to be set again (a first load
-        // keeps scales that were stored with the model and set beforehand)
-        std::fill(h->scale_set.begin(), h->scale_set.end(), 0);
-        for (auto& v : h->act_ch) v.clear();
-        h->fp8_ready = false; h->fp8_active = false;
-        for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-        h->graphs.clear();
-    }
-    h->weights_loaded = true;
-    if (h->cfg.precision == YH_PRECISION_FP8) { const int rc = refresh_fp8_scales(h); if (rc) return rc; }   // (the panels whose input tensor already has its scales)
-    return YH_OK;
-}
-
 int ensure_out_f32(yh_engine* h, size_t nfloats) {
     if (nfloats <= h->out_f32_cap) return YH_OK;
     if (h->out_f32) hipFree(h->out_f32);
@@ -1527,7 +1111,12 @@ int ensure_out_f32(yh_engine* h, size_t nfloats) {
     return YH_OK;
 }
 
-}  // namespace
+void drop_graphs(yh_engine* h) {
+    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
+    h->graphs.clear();
+}
+
+}  // namespace yh
 
 // ================================================================================================
 // C ABI
@@ -1648,8 +1237,8 @@ void yh_destroy(yh_engine* h) {
     if (h->copy) hipStreamSynchronize(h->copy);   // (a frame copy that no step consumed may still be in flight)
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->side) hipStreamSynchronize(h->side);   // (every step joins the side stream into the main one; belt and braces before the frees)
-    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-    for (void* p : h->allocs) hipFree(p);
+    drop_graphs(h);
+    for (const DevAlloc& a : h->allocs) hipFree(a.p);
     if (h->out_f32) hipFree(h->out_f32);
     if (h->frame_dev) hipFree(h->frame_dev);
     if (h->rs_tmp) hipFree(h->rs_tmp);
@@ -1677,8 +1266,7 @@ int yh_set_tuning(yh_engine* h, const yh_tuning* tune) {
         return h->fail(YH_ESTATE, "upfuse, dsfuse and protofuse are fixed when the handle is created");
     HIPCHK(h, hipSetDevice(h->dev));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured plans were made under the old tuning
-    h->graphs.clear();
+    drop_graphs(h);   // captured plans were made under the old tuning
     h->tune = t;
     h->cfg.tune = *tune;
     return YH_OK;
@@ -1691,330 +1279,6 @@ int yh_get_tuning(const yh_engine* h, yh_tuning* out) {
     out->plan_cus = t.plan_cus; out->chsplit = t.chsplit; out->upfuse = t.upfuse; out->ablate = t.ablate; out->op_tile = t.op_tile; out->op_kslices = t.op_kslices;
     out->tailfork = t.tailfork; out->dsfuse = t.dsfuse; out->headfork_maxb = t.headfork_maxb; out->protofuse = t.protofuse; out->chain = t.chain;
     // (tfl_dot, tfl_graph, tfl_fuse, tfl_group belong to yh_tfl handles - yh_tfl_create_tuned - and stay -1 here: an engine handle does not carry them)
-    return YH_OK;
-}
-
-// ---- fp8 precision (configs[4]) ----------------------------------------------------------------------------
-int yh_fp8_layer_count(const yh_engine* h) { return h ? (int)h->fp8_ops.size() : YH_EINVAL; }
-
-int yh_fp8_layer_info(const yh_engine* h, int32_t i, const char** conv_name, float* act_scale) {
-    if (!h || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
-    const Op& o = h->ops[h->fp8_ops[i]];
-    if (conv_name) *conv_name = o.name.c_str();
-    if (act_scale) *act_scale = h->act_scale[o.in.sid];
-    return YH_OK;
-}
-
-static int fp8_set_scales_impl(yh_engine* h, int32_t i, const std::vector<float>& v) {
-    HIPCHK(h, hipSetDevice(h->dev));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // the scales are baked into the captured launches
-    h->graphs.clear();
-    const int sid = h->ops[h->fp8_ops[i]].in.sid;
-    const int rc = set_sid_scales(h, sid, v);
-    if (rc) return rc;
-    // the handle counts as calibrated once EVERY E4M3 input tensor has its scales (they belong to the tensor: layers that read
-    // one allocation - P3..P7 of the pyramid: p6, p7, head_t, proto0 - share them, include/yolact_hip.h)
-    h->fp8_ready = fp8_missing(h).empty(); h->fp8_active = h->fp8_ready;
-    return refresh_fp8_scales(h, sid);
-}
-
-int yh_fp8_set_layer_scale(yh_engine* h, int32_t i, float act_scale) {
-    if (!h || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
-    if (!(act_scale > 0.0f) || !(act_scale < 3.0e38f)) return h->fail(YH_EINVAL, "activation scale must be a positive finite number");
-    return fp8_set_scales_impl(h, i, std::vector<float>((size_t)h->alloc_c[h->ops[h->fp8_ops[i]].in.sid], act_scale));
-}
-
-int yh_fp8_layer_channels(const yh_engine* h, int32_t i) {
-    if (!h || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
-    return h->alloc_c[h->ops[h->fp8_ops[i]].in.sid];
-}
-
-int yh_fp8_layer_channel_scales(const yh_engine* h, int32_t i, float* scales, int32_t n) {
-    if (!h || !scales || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
-    const int sid = h->ops[h->fp8_ops[i]].in.sid;
-    if (n != h->alloc_c[sid]) return YH_EINVAL;
-    for (int c = 0; c < n; ++c) scales[c] = h->act_ch[sid].empty() ? 1.0f : h->act_ch[sid][c];
-    return YH_OK;
-}
-
-int yh_fp8_set_layer_channel_scales(yh_engine* h, int32_t i, const float* scales, int32_t n) {
-    if (!h || !scales || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
-    if (n != h->alloc_c[h->ops[h->fp8_ops[i]].in.sid]) return h->fail(YH_EINVAL, "fp8: channel scale count does not match the layer's input tensor");
-    return fp8_set_scales_impl(h, i, std::vector<float>(scales, scales + n));
-}
-
-int yh_fp8_calibrate(yh_engine* h) {
-    if (!h) return YH_EINVAL;
-    if (h->cfg.precision != YH_PRECISION_FP8) return h->fail(YH_ESTATE, "the handle was not created with YH_PRECISION_FP8");
-    if (!h->weights_loaded) return h->fail(YH_ESTATE, "weights not loaded");
-    if (h->cur_n < 1) return h->fail(YH_ESTATE, "no input set: calibration runs on the frames last set");
-    HIPCHK(h, hipSetDevice(h->dev));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
-    // 1. the f16 forward of these frames (every tensor in f16, as a YH_PRECISION_F16 handle computes it); 2. one scale per
-    // CHANNEL of every tensor that an fp8 convolution reads: max(2 max |x[.., c]|, max |x| / 16) / 448 (448: E4M3's largest finite
-    // value; the factor and the floor: headroom for frames the calibration has not seen, below; yh_config.fp8_per_tensor = 1:
-    // the tensor's maximum in every channel, no headroom - round 3's scheme). On any failure the handle keeps the scales
-    // (and the form of the forward) it had.
-    std::set<int> sids;
-    for (int oi : h->fp8_ops) sids.insert(h->ops[oi].in.sid);
-    constexpr int MT = yh_engine::kMaxFp8Tensors, MC = yh_engine::kMaxFp8Channels;
-    if ((int)sids.size() > MT) return h->fail(YH_EINVAL, "too many fp8 input tensors");
-    for (int sid : sids) if (h->alloc_c[sid] > MC) return h->fail(YH_EINVAL, "fp8 input tensor with more than 512 channels");
-    std::vector<unsigned> bits((size_t)MT * MC);
-    h->fp8_active = false;
-    const int rc = [&]() -> int {
-        int r = wait_input(h);
-        if (r) return r;
-        r = enqueue_all(h, h->cur_n, 0);
-        if (r) return r;
-        HIPCHK(h, hipMemsetAsync(h->absmax_dev, 0, bits.size() * 4, h->stream));
-        int k = 0;
-        for (int sid : sids)
-            if (launch_absmax_channels_f16(h->alloc_base[sid], (long long)h->cur_n * h->alloc_img[sid] / h->alloc_c[sid], h->alloc_c[sid], h->absmax_dev + (size_t)(k++) * MC, h->stream) != hipSuccess)
-                return h->fail(YH_EHIP, "absmax launch failed");
-        HIPCHK(h, hipMemcpyAsync(bits.data(), h->absmax_dev, bits.size() * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        k = 0;
-        for (int sid : sids) {   // (the maxima are combined as bit patterns of non-negative floats: Inf and every NaN compare above all finite values)
-            for (int c = 0; c < h->alloc_c[sid]; ++c) {
-                float a; memcpy(&a, &bits[(size_t)k * MC + c], 4);
-                if (!(a < 3.0e38f)) {
-                    std::string who;
-                    for (int oi : h->fp8_ops) if (h->ops[oi].in.sid == sid) who += (who.empty() ? "" : ", ") + h->ops[oi].name;
-                    return h->fail(YH_ESTATE, "fp8 calibration: the f16 forward of these frames overflowed (Inf / NaN) in the input tensor of " + who + "; no scale was changed");
-                }
-            }
-            ++k;
-        }
-        return YH_OK;
-    }();
-    if (rc) { h->fp8_active = h->fp8_ready; return rc; }
-    int k = 0;
-    for (int sid : sids) {
-        const int C = h->alloc_c[sid];
-        std::vector<float> v((size_t)C);
-        float amax = 0.0f;
-        for (int c = 0; c < C; ++c) { float a; memcpy(&a, &bits[(size_t)k * MC + c], 4); v[c] = a; amax = a > amax ? a : amax; }
-        // Per channel (round 5): twice the channel's own maximum, and never less than a sixteenth of the tensor's. The maxima
-        // are those of the CALIBRATION frames; a channel that is quiet there and active later saturated at 448 s[c] - calibrated on the
-        // reference's test image and evaluated on a noise frame the scheme matched 21 of the f16 oracle's 31 detections where one scale
-        // per tensor matched 25 (tests/test_gpu_fp8_sweep.py, held-out test). Headroom is free in a floating-point code: E4M3 keeps its
-        // 3-bit mantissa over 2^15 of range, the values after a ReLU span a few octaves, so a scale 2 ... 16 x larger loses no bit.
-        for (int c = 0; c < C; ++c) {
-            const float a = h->cfg.fp8_per_tensor ? amax : fmaxf(2.0f * v[c], amax * (1.0f / 16.0f));
-            v[c] = a > 0.0f ? a / 448.0f : 1.0f;
-        }
-        const int r2 = set_sid_scales(h, sid, v);
-        if (r2) return r2;
-        ++k;
-    }
-    h->fp8_ready = true; h->fp8_active = true;
-    return refresh_fp8_scales(h);
-}
-
-size_t yh_weights_nbytes(const yh_engine* h) { return h ? h->blob_bytes : 0; }
-const void* yh_weights_device_ptr(const yh_engine* h) { return h && h->weights_loaded ? h->blob_dev : nullptr; }
-
-int yh_weights_generate(const yh_engine* hc, uint64_t seed, void* blob_host, size_t nbytes) {
-    yh_engine* h = const_cast<yh_engine*>(hc);
-    if (!h || !blob_host) return YH_EINVAL;
-    if (nbytes != h->blob_bytes) return h->fail(YH_EINVAL, "blob size mismatch");
-    uint8_t* b = (uint8_t*)blob_host;
-    memset(b, 0, nbytes);
-    memcpy(b, "YHW1", 4);
-    const uint32_t hdr[3] = { (uint32_t)h->convs.size(), (uint32_t)h->cfg.backbone, (uint32_t)h->C };
-    memcpy(b + 4, hdr, 12);
-    for (size_t i = 0; i < h->convs.size(); ++i) {
-        const ConvDesc& d = h->convs[i];
-        const uint32_t rec[4] = { (uint32_t)d.cout, (uint32_t)d.cin, (uint32_t)d.k, (uint32_t)d.k };
-        memcpy(b + d.blob_w_off - 16, rec, 16);
-        const size_t ne = (size_t)d.cout * d.k * d.k * d.cin;
-        const float fan_in = (float)(d.k * d.k * d.cin);
-        const float a = d.gain * sqrtf(6.0f / fan_in);
-        uint16_t* w = (uint16_t*)(b + d.blob_w_off);
-        for (size_t e = 0; e < ne; ++e) w[e] = f32_to_f16_bits(unit_rand(seed, i, 0, e) * a);
-        float* bias = (float*)(b + d.blob_b_off);
-        for (int e = 0; e < d.cout; ++e) {
-            float v = unit_rand(seed, i, 1, (uint64_t)e) * 0.1f;
-            if (d.is_conf == 1 && (e % h->C) == 0) v = v + 10.0f;   // background logit: detections stay sparse
-            if (d.is_conf == 2) v = v + 0.1f;                         // mask head: logits not centred on their threshold
-            bias[e] = v;
-        }
-    }
-    return YH_OK;
-}
-
-// The handle's copy of the canonical blob in device memory (the send / receive buffer of the weight broadcast): allocated on first use.
-static int ensure_blob(yh_engine* h) {
-    if (h->blob_dev) return YH_OK;
-    void* q = nullptr;
-    const int rc = dev_alloc(h, &q, h->blob_bytes);
-    if (rc) return rc;
-    h->blob_dev = (uint8_t*)q;
-    return YH_OK;
-}
-static int keep_blob(yh_engine* h, const void* src, hipMemcpyKind kind) {
-    const int rc = ensure_blob(h);
-    if (rc) return rc;
-    if (src != h->blob_dev) HIPCHK(h, hipMemcpy(h->blob_dev, src, h->blob_bytes, kind));
-    return YH_OK;
-}
-
-int yh_load_weights_host(yh_engine* h, const void* blob_host, size_t nbytes) {
-    if (!h || !blob_host) return YH_EINVAL;
-    int rc = check_blob(h, (const uint8_t*)blob_host, nbytes);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->dev));
-    if ((rc = keep_blob(h, blob_host, hipMemcpyHostToDevice))) return rc;
-    return upload_panels(h, (const uint8_t*)blob_host);
-}
-
-int yh_load_weights_device(yh_engine* h, const void* blob_dev, size_t nbytes) {
-    if (!h || !blob_dev) return YH_EINVAL;
-    if (nbytes != h->blob_bytes) return h->fail(YH_EWEIGHTS, "weight blob size mismatch");
-    HIPCHK(h, hipSetDevice(h->dev));
-    std::vector<uint8_t> host(nbytes);
-    HIPCHK(h, hipMemcpy(host.data(), blob_dev, nbytes, hipMemcpyDeviceToHost));
-    int rc = check_blob(h, host.data(), nbytes);
-    if (rc) return rc;
-    if ((rc = keep_blob(h, blob_dev, hipMemcpyDeviceToDevice))) return rc;
-    return upload_panels(h, host.data());
-}
-
-// ---- multi-GPU: the path's ONE collective, behind the C ABI --------------------------------------------
-// SURVEY.md §8e / north_star: frames shard over the GPUs of a node with no per-step collective; the weights are
-// replicated once by an RCCL broadcast over xGMI. The reference's caller is a Rust process (src/main.rs:63-75),
-// not torch, so the broadcast lives here. librccl.so (573 MB) is opened on first use only; the symbols are
-// declared locally (rccl.h: ncclUniqueId = 128 opaque bytes, ncclUint8 = 1, ncclSuccess = 0).
-namespace {
-struct RcclId { char internal[YH_RCCL_ID_BYTES]; };
-typedef void* rccl_comm;
-struct Rccl {
-    void* lib = nullptr;
-    int (*GetUniqueId)(RcclId*) = nullptr;
-    int (*CommInitRank)(rccl_comm*, int, RcclId, int) = nullptr;
-    int (*CommInitAll)(rccl_comm*, int, const int*) = nullptr;
-    int (*CommDestroy)(rccl_comm) = nullptr;
-    int (*Broadcast)(const void*, void*, size_t, int, int, rccl_comm, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-    std::string err;
-};
-void rccl_open(Rccl& r);
-std::atomic<int> g_rccl_opened{0};
-std::string& rccl_path_override() { static std::string s; return s; }   // yh_debug_rccl_library (tests: the stand-in of tests/rccl_standin/, by path)
-Rccl* rccl() {   // opened once per process (thread-safe: C++11 static initialisation); a failed open is remembered with its reason
-    static Rccl r = [] { Rccl x; g_rccl_opened.store(1); rccl_open(x); return x; }();
-    return &r;
-}
-void rccl_open(Rccl& r) {
-    if (!rccl_path_override().empty()) r.lib = dlopen(rccl_path_override().c_str(), RTLD_NOW | RTLD_LOCAL);
-    else
-        for (const char* name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) {
-            r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (r.lib) break;
-        }
-    if (!r.lib) { const char* why = dlerror(); r.err = std::string("dlopen librccl.so: ") + (why ? why : "not found"); return; }
-    auto sym = [&](const char* n) { void* p = dlsym(r.lib, n); if (!p && r.err.empty()) r.err = std::string("librccl.so lacks ") + n; return p; };
-    r.GetUniqueId = (int (*)(RcclId*))sym("ncclGetUniqueId");
-    r.CommInitRank = (int (*)(rccl_comm*, int, RcclId, int))sym("ncclCommInitRank");
-    r.CommInitAll = (int (*)(rccl_comm*, int, const int*))sym("ncclCommInitAll");
-    r.CommDestroy = (int (*)(rccl_comm))sym("ncclCommDestroy");
-    r.Broadcast = (int (*)(const void*, void*, size_t, int, int, rccl_comm, hipStream_t))sym("ncclBroadcast");
-    r.GroupStart = (int (*)())sym("ncclGroupStart");
-    r.GroupEnd = (int (*)())sym("ncclGroupEnd");
-    r.GetErrorString = (const char* (*)(int))sym("ncclGetErrorString");
-}
-extern "C++" std::string rccl_msg(Rccl* r, const char* what, int rc) { return std::string(what) + ": " + (r->GetErrorString ? r->GetErrorString(rc) : "error"); }
-// after the receive: validate and repack exactly as yh_load_weights_device does
-int adopt_received_blob(yh_engine* h) {
-    std::vector<uint8_t> host(h->blob_bytes);
-    HIPCHK(h, hipMemcpy(host.data(), h->blob_dev, h->blob_bytes, hipMemcpyDeviceToHost));
-    const int rc = check_blob(h, host.data(), h->blob_bytes);
-    if (rc) return rc;
-    return upload_panels(h, host.data());
-}
-}  // namespace
-
-int yh_rccl_unique_id(void* id_out) {
-    if (!id_out) return YH_EINVAL;
-    Rccl* r = rccl();
-    if (!r->err.empty()) { g_create_error = r->err; return YH_EHIP; }
-    RcclId id;
-    const int rc = r->GetUniqueId(&id);
-    if (rc) { g_create_error = rccl_msg(r, "ncclGetUniqueId", rc); return YH_EHIP; }
-    memcpy(id_out, &id, sizeof id);
-    return YH_OK;
-}
-
-int yh_rank_broadcast_weights(yh_engine* h, const void* id_bytes, int32_t rank, int32_t nranks, int32_t root) {
-    if (!h || !id_bytes) return YH_EINVAL;
-    if (nranks < 1 || rank < 0 || rank >= nranks || root < 0 || root >= nranks) return h->fail(YH_EINVAL, "rank / nranks / root out of range");
-    if (rank == root && !h->weights_loaded) return h->fail(YH_ESTATE, "the root rank must have its weights loaded before the broadcast");
-    Rccl* r = rccl();
-    if (!r->err.empty()) return h->fail(YH_EHIP, r->err);
-    HIPCHK(h, hipSetDevice(h->dev));
-    // non-root: the receive buffer. (Round 5, the first execution with two ranks - behind the stand-in librccl of tests/rccl_standin/ -
-    // found this line as keep_blob(h, h->blob_dev, ...): the argument was read, still null, before the allocation inside, and every
-    // rank that had never held weights failed with "hipMemcpy: invalid argument" - the path could not have worked on an 8-GPU node.)
-    int rc = rank == root ? YH_OK : ensure_blob(h);
-    if (rc) return rc;
-    RcclId id;
-    memcpy(&id, id_bytes, sizeof id);
-    rccl_comm comm = nullptr;
-    int e = r->CommInitRank(&comm, nranks, id, rank);
-    if (e) return h->fail(YH_EHIP, rccl_msg(r, "ncclCommInitRank", e));
-    e = r->Broadcast(h->blob_dev, h->blob_dev, h->blob_bytes, /*ncclUint8*/ 1, root, comm, h->stream);
-    const hipError_t se = hipStreamSynchronize(h->stream);
-    r->CommDestroy(comm);
-    if (e) return h->fail(YH_EHIP, rccl_msg(r, "ncclBroadcast", e));
-    if (se != hipSuccess) return h->fail(YH_EHIP, std::string("weight broadcast: ") + hipGetErrorString(se));
-    return rank == root ? YH_OK : adopt_received_blob(h);
-}
-
-int yh_group_broadcast_weights(yh_engine** hs, int32_t n, int32_t root) {
-    if (!hs || n < 1 || root < 0 || root >= n) return YH_EINVAL;
-    for (int i = 0; i < n; ++i) if (!hs[i]) return YH_EINVAL;
-    yh_engine* h0 = hs[root];
-    if (!h0->weights_loaded) return h0->fail(YH_ESTATE, "the root handle must have its weights loaded before the broadcast");
-    for (int i = 0; i < n; ++i) {
-        if (hs[i]->blob_bytes != h0->blob_bytes) return h0->fail(YH_EINVAL, "handles of one group must share the architecture");
-        for (int j = 0; j < i; ++j) if (hs[j]->dev == hs[i]->dev && !yh::rccl_shared_device_allowed()) return h0->fail(YH_EINVAL, "one handle per device: RCCL refuses two ranks on one GPU");
-    }
-    if (n == 1) return YH_OK;
-    Rccl* r = rccl();
-    if (!r->err.empty()) return h0->fail(YH_EHIP, r->err);
-    std::vector<int> devs(n);
-    for (int i = 0; i < n; ++i) {
-        devs[i] = hs[i]->dev;
-        if (i != root) {
-            if (hipSetDevice(hs[i]->dev) != hipSuccess) return h0->fail(YH_EHIP, "hipSetDevice failed for handle " + std::to_string(i));
-            const int rc = ensure_blob(hs[i]);
-            if (rc) return h0->fail(rc, "handle " + std::to_string(i) + ": " + hs[i]->err);   // (the caller reads the ROOT handle's error)
-        }
-    }
-    std::vector<rccl_comm> comms(n, nullptr);
-    int e = r->CommInitAll(comms.data(), n, devs.data());
-    if (e) return h0->fail(YH_EHIP, rccl_msg(r, "ncclCommInitAll", e));
-    e = r->GroupStart();   // one thread drives every device: the n broadcasts must be one group
-    for (int i = 0; i < n && !e; ++i) e = r->Broadcast(hs[i]->blob_dev, hs[i]->blob_dev, h0->blob_bytes, 1, root, comms[i], hs[i]->stream);
-    const int ge = r->GroupEnd();
-    if (!e) e = ge;
-    hipError_t se = hipSuccess;
-    for (int i = 0; i < n; ++i) { hipSetDevice(hs[i]->dev); const hipError_t s1 = hipStreamSynchronize(hs[i]->stream); if (se == hipSuccess) se = s1; }
-    for (rccl_comm c : comms) if (c) r->CommDestroy(c);
-    if (e) return h0->fail(YH_EHIP, rccl_msg(r, "ncclBroadcast (group)", e));
-    if (se != hipSuccess) return h0->fail(YH_EHIP, std::string("weight broadcast: ") + hipGetErrorString(se));
-    for (int i = 0; i < n; ++i)
-        if (i != root) {
-            if (hipSetDevice(hs[i]->dev) != hipSuccess) return h0->fail(YH_EHIP, "hipSetDevice failed for handle " + std::to_string(i));
-            const int rc = adopt_received_blob(hs[i]);
-            if (rc) return h0->fail(rc, "handle " + std::to_string(i) + ": " + hs[i]->err);
-        }
     return YH_OK;
 }
 
@@ -2095,61 +1359,6 @@ int yh_prepare(yh_engine* h, int32_t n_frames, int32_t with_tail) {
     }
     h->in_cur = cur;
     return rc;
-}
-
-int yh_debug_set_cu_mask(yh_engine* h, const uint32_t* mask, int32_t n_words) {
-    if (!h || !mask || n_words < 1 || n_words > 16) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->side));
-    for (auto& kv : h->graphs) hipGraphExecDestroy(kv.second);   // captured for the old streams
-    h->graphs.clear();
-    hipStream_t ns = nullptr, nd = nullptr;
-    HIPCHK(h, hipExtStreamCreateWithCUMask(&ns, (uint32_t)n_words, mask));
-    const hipError_t e2 = hipExtStreamCreateWithCUMask(&nd, (uint32_t)n_words, mask);
-    if (e2 != hipSuccess) { hipStreamDestroy(ns); return h->fail(YH_EHIP, std::string("hipExtStreamCreateWithCUMask: ") + hipGetErrorString(e2)); }   // (the handle keeps its streams)
-    hipStreamDestroy(h->stream); hipStreamDestroy(h->side);
-    h->stream = ns; h->side = nd;
-    return YH_OK;
-}
-
-int yh_debug_run_phase(yh_engine* h, int32_t phase, int32_t reps, float* ms_total) {
-    if (!h || reps < 1 || (phase != 0 && phase != 1)) return YH_EINVAL;
-    if (!h->weights_loaded || h->cur_n < 1) return h->fail(YH_ESTATE, "weights and an input first");
-    HIPCHK(h, hipSetDevice(h->dev));
-    int rc = wait_input(h);
-    if (rc) return rc;
-    size_t p3 = h->ops.size();
-    for (size_t i = 0; i < h->ops.size(); ++i) if (h->ops[i].name == "p3") { p3 = i; break; }
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; ++r)
-        for (size_t i = 0; i < h->ops.size(); ++i) {
-            const bool second = i >= p3 || h->ops[i].side;   // p3, the FPN's P4..P7 convolutions, the head, the protonet
-            if (second != (phase == 1)) continue;
-            if ((rc = launch_op(h, h->ops[i], h->cur_n, false))) return rc;
-        }
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-    float ms = 0.0f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    if (ms_total) *ms_total = ms;
-    return YH_OK;
-}
-
-int yh_debug_rccl_library(const char* path) {
-    if (!path || !*path) return YH_EINVAL;
-    if (g_rccl_opened.load()) { g_create_error = "librccl has already been opened in this process"; return YH_ESTATE; }
-    rccl_path_override() = path;
-    return YH_OK;
-}
-
-int yh_debug_rccl_shared_device(int32_t allow) { return yh::g_rccl_shared_device.exchange(allow ? 1 : 0); }
-
-int yh_debug_setup_audit(int64_t out[4]) {
-    if (!out) return YH_EINVAL;
-    yh::SetupAudit& a = yh::setup_audit();
-    out[0] = a.setups.load(); out[1] = a.worker_jobs.load(); out[2] = a.overlaps.load(); out[3] = (int64_t)a.setup_active.load() + a.worker_active.load();
-    return YH_OK;
 }
 
 int yh_sync(yh_engine* h) {
@@ -2281,56 +1490,6 @@ int ensure_compat(yh_engine* h, int n_tiles) {
     return YH_OK;
 }
 
-// The device buffers of one single-op call: allocated (and filled - 0 behind a zero-padded input, 0xFF, the NaN pattern an
-// unwritten element shows, in an output) and uploaded in the order the call asks for them, freed when the call returns.
-// The first HIP error is kept and every step after it is skipped.
-struct OpStaging {
-    hipError_t e = hipSuccess;
-    std::vector<void*> bufs;
-    OpStaging() = default;
-    OpStaging(const OpStaging&) = delete;
-    ~OpStaging() { for (void* d : bufs) hipFree(d); }
-    bool ok() const { return e == hipSuccess; }
-    template <class T> T* alloc(size_t bytes, int fill = -1) {
-        void* d = nullptr;
-        if (ok() && (e = hipMalloc(&d, bytes)) == hipSuccess) bufs.push_back(d);
-        if (ok() && fill >= 0) e = hipMemset(d, fill, bytes);
-        return ok() ? (T*)d : nullptr;
-    }
-    void put(const void* d, const void* src, size_t bytes) { if (ok()) e = hipMemcpy((void*)d, src, bytes, hipMemcpyHostToDevice); }
-    template <class T> T* upload(const void* src, size_t bytes) { T* d = alloc<T>(bytes); put(d, src, bytes); return d; }
-    // a conv input with its zero pixel behind the data: `cap` zeroed bytes, the data first; *zero_off = where the zeros start
-    template <class T> T* upload_padded(const void* src, size_t bytes, size_t cap, unsigned* zero_off) {
-        *zero_off = (unsigned)pad16(bytes);
-        T* d = alloc<T>(cap, 0);
-        put(d, src, bytes);
-        return d;
-    }
-    void sync(hipStream_t s) { if (ok()) e = hipStreamSynchronize(s); }
-    void get(void* dst, const void* d, size_t bytes) { if (ok()) e = hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost); }
-    int status(yh_engine* h, const char* what) const { return ok() ? YH_OK : h->fail(YH_EHIP, std::string(what) + hipGetErrorString(e)); }
-};
-
-// rows of c values, zero-padded to rows of ld (input channels to the stored count, output channels to cout8) - and back
-template <class T> std::vector<T> pad_rows(const T* src, size_t rows, size_t c, size_t ld) {
-    std::vector<T> v(rows * ld, T(0));
-    for (size_t m = 0; m < rows; ++m) memcpy(&v[m * ld], &src[m * c], c * sizeof(T));
-    return v;
-}
-void unpad_rows(uint16_t* dst, const std::vector<uint16_t>& src, size_t rows, size_t c, size_t ld) {
-    for (size_t m = 0; m < rows; ++m) memcpy(&dst[m * c], &src[m * ld], c * 2);
-}
-
-// test hook (tune.op_kslices): a forced split-K of a single-op launch (the engine decides it in fill_conv_params)
-void force_split_k(yh_engine* h, ConvParams& p, size_t M, int coutPad) {
-    const int ksl = h->tune.op_kslices;
-    if (ksl < 2 || ksl > p.ksteps || (size_t)ksl * M * coutPad * 4 > yh_engine::kSplitKBytes) return;
-    p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
-    p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
-    p.partial_ld = coutPad;
-    p.partial = h->splitk_ws;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2418,597 +1577,6 @@ int yh_classify_frame_u32(yh_engine* h, uint32_t* frame, int32_t w, int32_t hh, 
     return YH_OK;
 }
 
-int yh_debug_last_conv_launches(const yh_engine* h) { return h ? h->last_conv_launches : 0; }
 const uint32_t* yh_classify_device_frame(const yh_engine* h) { return h ? h->frame_dev : nullptr; }
-
-// Is `name` the output of a conv whose 1x1 tail ran in its epilogue at the current batch size (the tensor was not written)?
-static bool absorbed_output(yh_engine* h, const char* name) {
-    if (h->cur_n < 1) return false;
-    for (const Op& o : h->ops) {
-        if (o.kind == OP_CONV && o.tail_op >= 0 && o.name == name) return conv_absorbed(h, h->ops[o.tail_op], h->cur_n);
-        if (o.kind == OP_CONV && o.chain_c >= 0 && o.name == name) return chain_active(h, o, h->cur_n);   // b stays in LDS
-    }
-    return false;
-}
-
-int yh_debug_read_tensor(yh_engine* h, const char* name, float* dst, size_t nfloats, int32_t dims[4]) {
-    if (!h || !name || !dims) return YH_EINVAL;
-    if ((h->fused_away.count(name) && !h->cfg.debug_tensors) || absorbed_output(h, name))
-        return h->fail(YH_ESTATE, std::string("the ") + name + " tensor is fused away; create the engine with debug_tensors = 1 to materialise it");
-    auto it = h->named.find(name);
-    if (it == h->named.end()) return h->fail(YH_EINVAL, std::string("unknown tensor ") + name);
-    if (h->cur_n < 1) return h->fail(YH_ESTATE, "no inference has run");
-    const Buf& b = it->second;
-    const int n = h->cur_n;
-    const size_t per = (size_t)b.h * b.w * b.c;
-    dims[0] = n; dims[1] = b.h; dims[2] = b.w; dims[3] = b.c;
-    if (!dst) return YH_OK;
-    if (nfloats < per * n) return h->fail(YH_EINVAL, "destination too small");
-    HIPCHK(h, hipSetDevice(h->dev));
-    int rc = ensure_out_f32(h, per * n);
-    if (rc) return rc;
-    for (int i = 0; i < n; ++i) {
-        hipError_t e;
-        if (h->fp8_active && h->q_only.count(name))
-            e = launch_dequant_e4m3_f32(b.q + (long long)i * b.img_stride, h->out_f32 + (size_t)i * per, (long long)per, h->sc_dev[b.sid], b.c, h->stream);
-        else e = launch_f16_to_f32(b.d + (long long)i * b.img_stride, h->out_f32 + (size_t)i * per, (long long)per, h->stream);
-        if (e != hipSuccess) return h->fail(YH_EHIP, "debug read convert");
-    }
-    HIPCHK(h, hipMemcpyAsync(dst, h->out_f32, per * n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return YH_OK;
-}
-
-int yh_debug_read_tensor_frame(yh_engine* h, const char* name, int32_t frame, float* dst, size_t nfloats, int32_t dims[4]) {
-    if (!h || !name || !dims) return YH_EINVAL;
-    if ((h->fused_away.count(name) && !h->cfg.debug_tensors) || absorbed_output(h, name))
-        return h->fail(YH_ESTATE, std::string("the ") + name + " tensor is fused away; create the engine with debug_tensors = 1 to materialise it");
-    auto it = h->named.find(name);
-    if (it == h->named.end()) return h->fail(YH_EINVAL, std::string("unknown tensor ") + name);
-    if (h->cur_n < 1) return h->fail(YH_ESTATE, "no inference has run");
-    if (frame < 0 || frame >= h->cur_n) return h->fail(YH_EINVAL, "frame out of range");
-    const Buf& b = it->second;
-    const size_t per = (size_t)b.h * b.w * b.c;
-    dims[0] = 1; dims[1] = b.h; dims[2] = b.w; dims[3] = b.c;
-    if (!dst) return YH_OK;
-    if (nfloats < per) return h->fail(YH_EINVAL, "destination too small");
-    HIPCHK(h, hipSetDevice(h->dev));
-    int rc = ensure_out_f32(h, per);
-    if (rc) return rc;
-    hipError_t ce;
-    if (h->fp8_active && h->q_only.count(name))   // fp8 precision: this tensor exists only as E4M3 codes
-        ce = launch_dequant_e4m3_f32(b.q + (long long)frame * b.img_stride, h->out_f32, (long long)per, h->sc_dev[b.sid], b.c, h->stream);
-    else ce = launch_f16_to_f32(b.d + (long long)frame * b.img_stride, h->out_f32, (long long)per, h->stream);
-    if (ce != hipSuccess) return h->fail(YH_EHIP, "debug read convert");
-    HIPCHK(h, hipMemcpyAsync(dst, h->out_f32, per * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return YH_OK;
-}
-
-// ---- audit hooks (profiles/r03_fault_audit.md): where every buffer of a handle lives, and what a captured step consists of ----
-// One line per allocation: kind, name (layer tensors by their DESIGN.md names), [base, end), size and the offsets of base and
-// end inside their 2 MiB page - the three GPU memory-access faults of round 2 all hit an address 8 KiB below a 2 MiB boundary.
-int yh_debug_alloc_map(yh_engine* h, char* out, size_t cap) {
-    if (!h || !out || cap < 2) return YH_EINVAL;
-    std::string t;
-    char ln[320];
-    auto line = [&](const char* kind, const std::string& name, const void* base, size_t bytes) {
-        const unsigned long long b = (unsigned long long)(uintptr_t)base, e = b + bytes;
-        snprintf(ln, sizeof ln, "%-7s %-14s base 0x%012llx end 0x%012llx bytes %12zu  base%%2MiB 0x%06llx  end%%2MiB 0x%06llx\n", kind, name.c_str(), b, e, bytes,
-                 b & 0x1FFFFFull, e & 0x1FFFFFull);
-        t += ln;
-    };
-    std::map<const void*, std::string> names;
-    for (const auto& kv : h->named) if (!names.count(kv.second.d)) names[kv.second.d] = kv.first;
-    for (const auto& kv : h->named) if (kv.second.q && !names.count(kv.second.q)) names[kv.second.q] = kv.first + ".e4m3";
-    names[h->in_buf[0]] = "in_u8[0]"; names[h->in_buf[1]] = "in_u8[1]"; names[h->splitk_ws] = "splitk_ws"; names[h->splitk_ws_side] = "splitk_ws_side";
-    names[h->blob_dev] = "weight_blob"; names[h->side_word] = "side_word"; names[h->priors_dev] = "priors";
-    names[h->det.cls_count] = "det.cls_count"; names[h->det.cand] = "det.cand"; names[h->det.surv_score] = "det.surv_score"; names[h->det.surv_prior] = "det.surv_prior";
-    names[h->det.surv_box] = "det.surv_box"; names[h->det.det_count] = "det.det_count"; names[h->det.dets] = "det.dets"; names[h->det.det_crop] = "det.det_crop"; names[h->det.masks] = "det.masks";
-    for (size_t i = 0; i < h->panels.size(); ++i) {
-        const Panel& p = h->panels[i];
-        const std::string nm = "panel" + std::to_string(i);
-        names[p.w] = nm + ".w"; names[p.bias] = nm + ".bias";
-        if (p.w8) names[p.w8] = nm + ".w8";
-        if (p.scale) names[p.scale] = nm + ".scale";
-        if (p.rs_table) names[p.rs_table] = nm + ".rs";
-    }
-    for (size_t i = 0; i < h->allocs.size(); ++i) {
-        auto it = names.find(h->allocs[i]);
-        line("device", it != names.end() ? it->second : "alloc" + std::to_string(i), h->allocs[i], h->alloc_bytes[i]);
-    }
-    if (h->out_f32) line("device", "out_f32", h->out_f32, h->out_f32_cap * 4);
-    if (h->frame_dev) line("device", "frame_dev", h->frame_dev, h->frame_cap);
-    if (h->rs_tmp) line("device", "rs_tmp", h->rs_tmp, h->rs_tmp_cap);
-    for (int k = 0; k < 2; ++k) if (h->stage[k]) line("pinned", "stage" + std::to_string(k), h->stage[k], yh_engine::kStageBytes);
-    snprintf(out, cap, "%s", t.c_str());
-    return (int)t.size() < (int)cap ? YH_OK : YH_EOVERFLOW;
-}
-
-// The step for the current batch size, captured (not instantiated) under the handle's current tuning: one line per graph
-// node - kernel symbol, grid, block, and for the single-struct kernels of this library the pointers and sizes in the launch
-// argument - plus node / edge / root counts. Two captures (with and without the forks) can then be diffed as text.
-int yh_debug_graph_nodes(yh_engine* h, int32_t with_tail, char* out, size_t cap) {
-    if (!h || !out || cap < 2) return YH_EINVAL;
-    if (!h->weights_loaded || h->cur_n < 1) return h->fail(YH_ESTATE, "weights and input must be set");
-    HIPCHK(h, hipSetDevice(h->dev));
-    int rc = wait_input(h);
-    if (rc) return rc;
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
-    h->capturing = true;
-    rc = enqueue_all(h, h->cur_n, with_tail);
-    h->capturing = false;
-    const hipError_t ce = hipStreamEndCapture(h->stream, &g);
-    if (rc) { if (g) hipGraphDestroy(g); return rc; }
-    if (ce != hipSuccess || !g) return h->fail(YH_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-    size_t nn = 0, ne = 0, nr = 0;
-    hipGraphGetNodes(g, nullptr, &nn);
-    hipGraphGetEdges(g, nullptr, nullptr, &ne);
-    hipGraphGetRootNodes(g, nullptr, &nr);
-    std::vector<hipGraphNode_t> nodes(nn);
-    if (nn) hipGraphGetNodes(g, nodes.data(), &nn);
-    std::string t;
-    char ln[640];
-    snprintf(ln, sizeof ln, "# nodes %zu edges %zu roots %zu (batch %d, with_tail %d)\n", nn, ne, nr, h->cur_n, with_tail);
-    t += ln;
-    std::vector<std::string> lines;
-    for (hipGraphNode_t nd : nodes) {
-        hipGraphNodeType ty;
-        if (hipGraphNodeGetType(nd, &ty) != hipSuccess) continue;
-        if (ty == hipGraphNodeTypeKernel) {
-            hipKernelNodeParams kp;
-            memset(&kp, 0, sizeof kp);
-            if (hipGraphKernelNodeGetParams(nd, &kp) != hipSuccess) { lines.push_back("kernel ?"); continue; }
-            const char* nm = hipKernelNameRefByPtr(kp.func, h->stream);
-            std::string name = nm ? nm : "?";
-            std::string args;
-            if (kp.kernelParams && kp.kernelParams[0]) {
-                if (name.find("conv_igemm_f16") != std::string::npos || name.find("splitk_reduce_f16") != std::string::npos) {
-                    const ConvParams* q = (const ConvParams*)kp.kernelParams[0];
-                    snprintf(ln, sizeof ln, " x %p w %p bias %p res %p y %p y8 %p x2 %p w2 %p y2 %p scale %p partial %s M %d C %d ksteps %d k_slices %d m_tile0 %d ch_tile0 %d n_ch_tiles %d x_bytes %u w_bytes %u",
-                             (const void*)q->x, (const void*)q->w, (const void*)q->bias, (const void*)q->res, (void*)q->y, (void*)q->y8, (const void*)q->x2, (const void*)q->w2, (void*)q->y2,
-                             (const void*)q->scale, !q->partial ? "-" : (q->partial == h->splitk_ws ? "ws_main" : (q->partial == h->splitk_ws_side ? "ws_side" : "?")), q->M, q->C, q->ksteps, q->k_slices,
-                             q->m_tile0, q->ch_tile0, q->n_ch_tiles, q->x_bytes, q->w_bytes);
-                    args = ln;
-                } else if (name.find("det_") != std::string::npos) {
-                    const DetectParams* q = (const DetectParams*)kp.kernelParams[0];
-                    snprintf(ln, sizeof ln, " heads %p proto %p cand %p dets %p masks %p n %d", (const void*)q->heads, (const void*)q->proto, (void*)q->cand, (void*)q->dets, (void*)q->masks, q->n);
-                    args = ln;
-                } else if (name.find("stem_pool_f16") != std::string::npos) {
-                    const StemPoolParams* q = (const StemPoolParams*)kp.kernelParams[0];
-                    snprintf(ln, sizeof ln, " x %p rgb %s w %p pool %p n %d", (const void*)q->x, q->rgb == h->in_buf[0] ? "in_u8[0]" : (q->rgb == h->in_buf[1] ? "in_u8[1]" : (q->rgb ? "?" : "-")), (const void*)q->w, (void*)q->pool, q->n);
-                    args = ln;
-                }
-            }
-            snprintf(ln, sizeof ln, "kernel grid %u,%u,%u block %u shmem %u %s", kp.gridDim.x, kp.gridDim.y, kp.gridDim.z, kp.blockDim.x, kp.sharedMemBytes, name.c_str());
-            lines.push_back(std::string(ln) + args);
-        } else if (ty == hipGraphNodeTypeMemset) {
-            hipMemsetParams mp;
-            memset(&mp, 0, sizeof mp);
-            hipGraphMemsetNodeGetParams(nd, &mp);
-            snprintf(ln, sizeof ln, "memset dst %s width %zu height %zu elem %u value %u", mp.dst == (void*)h->side_word ? "side_word" : (mp.dst == (void*)h->det.cls_count ? "det.cls_count" : "?"),
-                     mp.width, mp.height, mp.elementSize, mp.value);
-            lines.push_back(ln);
-        } else {
-            snprintf(ln, sizeof ln, "node type %d", (int)ty);
-            lines.push_back(ln);
-        }
-    }
-    hipGraphDestroy(g);
-    std::sort(lines.begin(), lines.end());   // (node order of a multi-branch graph is not a property of the step)
-    for (const std::string& l : lines) t += l + "\n";
-    snprintf(out, cap, "%s", t.c_str());
-    return t.size() < cap ? YH_OK : YH_EOVERFLOW;
-}
-
-// ---- measurement hooks -------------------------------------------------------------------------
-// One profile entry per KERNEL launch (so that the averages agree with rocprofv3's per-kernel stats):
-// a conv op planned as two launches (wave-quantisation tail, channel split, split-K + reduce) gives
-// two entries, its algorithmic FLOPs and bytes shared out by the rows / channels each launch covers.
-// The entries follow plan_op: a SKIP op has none (it is accounted with the launch that computes it), a CONV op one per
-// plan_conv launch, every other op one (launched through launch_op).
-struct ProfEntry { int op; int stage; OpLaunch::Form form; int tile_m; KLaunch k; };
-
-static int build_profile_entries(yh_engine* h, int n, int with_tail, std::vector<ProfEntry>* out) {
-    out->clear();
-    for (int i = 0; i < (int)h->ops.size(); ++i) {
-        OpLaunch pl;
-        const int rc = plan_op(h, h->ops[i], n, &pl);
-        if (rc) return rc;
-        KLaunch k[3] = {};
-        const int nk = pl.form == OpLaunch::CONV ? plan_conv(h->tune, pl.p, pl.tile, h->panels[h->ops[i].panel].coutPad, k)
-                                                  : (pl.form == OpLaunch::SKIP ? 0 : 1);
-        for (int j = 0; j < nk; ++j) out->push_back(ProfEntry{ i, -1, pl.form, pl.tile_m, k[j] });
-    }
-    if (with_tail)
-        for (int st = 0; st < detect_launch_count(); ++st) out->push_back(ProfEntry{ -1, st, OpLaunch::OTHER, 0, KLaunch{} });
-    return YH_OK;
-}
-
-int yh_profile_launch_count(const yh_engine* h, int32_t with_tail) {
-    if (!h) return YH_EINVAL;
-    std::vector<ProfEntry> ent;
-    yh_engine* hm = const_cast<yh_engine*>(h);
-    if (build_profile_entries(hm, h->cur_n >= 1 ? h->cur_n : h->cfg.max_batch, with_tail, &ent)) return YH_EINVAL;
-    return (int)ent.size();
-}
-
-int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, double* flops, double* bytes, const char** names) {
-    if (!h || !ms || reps < 1) return YH_EINVAL;
-    if (!h->weights_loaded || h->cur_n < 1) return h->fail(YH_ESTATE, "weights and input must be set");
-    HIPCHK(h, hipSetDevice(h->dev));
-    const int n = h->cur_n;
-    std::vector<ProfEntry> ent;
-    int rc = wait_input(h);
-    if (rc) return rc;
-    rc = build_profile_entries(h, n, with_tail, &ent);
-    if (rc) return rc;
-    const int nl = (int)ent.size();
-    std::vector<hipEvent_t> ev((size_t)nl * 2);
-    for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
-    std::vector<double> acc(nl, 0.0);
-    h->det.n = n;
-    for (int r = 0; r < reps && rc == YH_OK; ++r) {
-        for (int i = 0; i < nl && rc == YH_OK; ++i) {
-            const ProfEntry& pe = ent[i];
-            hipEventRecord(ev[2 * i], h->stream);
-            if (pe.form == OpLaunch::CONV) { if (launch_k(pe.k, h->stream) != hipSuccess) rc = h->fail(YH_EHIP, "conv launch failed in profile run"); }
-            else if (pe.op >= 0) rc = launch_op(h, h->ops[pe.op], n);
-            else if (launch_detect_stage(h->det, pe.stage, h->stream) != hipSuccess) rc = h->fail(YH_EHIP, "detect stage launch failed");
-            hipEventRecord(ev[2 * i + 1], h->stream);
-        }
-        if (rc) break;
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = h->fail(YH_EHIP, "sync failed in profile run"); break; }
-        for (int i = 0; i < nl; ++i) { float t = 0; hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]); acc[i] += t; }
-    }
-    for (auto& e : ev) hipEventDestroy(e);
-    if (rc) {   // a pass that stopped between the tail's K1 and K2 leaves candidate counts behind: clear them as run()'s error path does
-        hipStreamSynchronize(h->stream); hipStreamSynchronize(h->side);
-        hipMemset(h->det.cls_count, 0, sizeof(int) * (size_t)h->cfg.max_batch * (h->C - 1));
-        return rc;
-    }
-    h->prof_labels.assign(nl, std::string());
-    for (int i = 0; i < nl; ++i) {
-        const ProfEntry& pe = ent[i];
-        ms[i] = (float)(acc[i] / reps);
-        double fl = 0.0, by = 0.0;
-        if (pe.op >= 0) {
-            const Op& o = h->ops[pe.op];
-            const double frac = pe.form == OpLaunch::CONV ? pe.k.frac : 1.0;
-            fl = o.flops_per_img * n * frac;
-            by = (o.bytes_per_img * n + o.bytes_fixed) * frac;
-            if (pe.form == OpLaunch::CONV && pe.k.reduce) {
-                h->prof_labels[i] = "splitk_reduce_f16:" + o.name;
-                by = (double)pe.k.p.M * pe.k.p.partial_ld * 4.0 * pe.k.p.k_slices + (double)pe.k.p.M * pe.k.p.cout8 * 2.0;
-            } else if (pe.form == OpLaunch::CONV) {
-                h->prof_labels[i] = conv_label(pe.k.p, pe.k.tile) + ":" + o.name + pe.k.what;
-                if (pe.k.p.w2) {   // fused 1x1 tail: both convolutions' FLOPs; this conv's input and the tail's output
-                    const Op& t = h->ops[o.tail_op];
-                    h->prof_labels[i] += "+" + t.name;
-                    fl += t.flops_per_img * n;
-                    by += t.bytes_fixed + 2.0 * n * ((double)t.P * t.Q * h->panels[t.panel].cout - (double)o.P * o.Q * h->panels[o.panel].cout * (h->fp8_active && !o.write_f16 ? 0.0 : 1.0));
-                }
-            } else if (pe.form == OpLaunch::XN) {
-                // expand conv + next reduce conv: both convolutions' FLOPs; HBM bytes = b + residual in, y + a' out, the weights
-                const Op& oa = h->ops[o.xn_a];
-                const double px = (double)n * o.P * o.Q;
-                h->prof_labels[i] = std::string(bneck_symbol(256, pe.tile_m, true, false)) + ":" + o.name + "+" + oa.name;
-                fl += oa.flops_per_img * n;
-                by = 2.0 * px * (256.0 + 1024.0 + 1024.0) + px * 256.0 * ((oa.write_f16 || !h->fp8_active ? 2.0 : 0.0) + (h->fp8_active && oa.write_q ? 1.0 : 0.0)) + o.bytes_fixed + oa.bytes_fixed;
-            } else if (pe.form == OpLaunch::CHAIN) {
-                // a bottleneck chain: the FLOPs of its two or three convolutions; HBM bytes = a + residual in, y (+ a') out, the weights
-                const Op& oc = h->ops[o.chain_c];
-                const int planes = h->panels[o.panel].cout;
-                const double px = (double)n * o.P * o.Q;
-                h->prof_labels[i] = std::string(bneck_symbol(planes, pe.tile_m, o.chain_a >= 0, oc.dual)) + ":" + o.name + "+" + oc.name;
-                fl += oc.flops_per_img * n;
-                by = 2.0 * ((double)n * o.in.h * o.in.w * planes + px * 4.0 * planes * (oc.dual ? 1.0 : 2.0) + (oc.dual ? px * oc.in2.c : 0.0)) + o.bytes_fixed + oc.bytes_fixed;
-                if (o.chain_a >= 0) {
-                    const Op& oa = h->ops[o.chain_a];
-                    h->prof_labels[i] += "+" + oa.name;
-                    fl += oa.flops_per_img * n;
-                    by += 2.0 * px * planes + oa.bytes_fixed;
-                }
-            } else h->prof_labels[i] = o.label;
-        } else h->prof_labels[i] = detect_stage_name(pe.stage);
-        if (flops) flops[i] = fl;
-        if (bytes) bytes[i] = by;
-        if (names) names[i] = h->prof_labels[i].c_str();
-    }
-    return YH_OK;
-}
-
-int yh_time_steps(yh_engine* h, int32_t with_tail, int32_t steps, float* ms_total) {
-    if (!h || !ms_total || steps < 1) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    for (int i = 0; i < steps; ++i) { int rc = run(h, with_tail); if (rc) return rc; }
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-    HIPCHK(h, hipEventElapsedTime(ms_total, h->ev0, h->ev1));
-    return YH_OK;
-}
-
-// ---- single-op entry points (tests) ------------------------------------------------------------
-// Each one reads: validate, stage (host-side repacking, then the device buffers), fill the kernel's parameters, launch, read back.
-static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
-                          const float* bias, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
-                          const uint16_t* residual, int32_t act, uint16_t* y, const int32_t* level_sizes, int32_t nlev) {
-    if (!h || !x || !w || !bias || !y) return YH_EINVAL;
-    if (kh != kw || kh < 1 || stride < 1 || n < 1 || (cin != 3 && cin % 64 != 0) || (act < 0 || act > 2))
-        return h->fail(YH_EINVAL, "conv op: need square kernel and cin == 3 or cin % 64 == 0");
-    HIPCHK(h, hipSetDevice(h->dev));
-    const int cs = cin == 3 ? 8 : cin, k = kh;
-    // multi-level form: x is [n][cells][cin], cells = the levels' squares laid end to end (hh = cells, ww = 1)
-    const int P = nlev > 0 ? hh : out_dim(hh, k, stride, pad), Q = nlev > 0 ? 1 : out_dim(ww, k, stride, pad);
-    if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "conv op: empty output");
-    ConvTile tile = cin == 3 ? TILE_64x256_SMALLC : (cout <= 32 ? TILE_32x256 : (cout <= 64 ? TILE_64x256 : TILE_128x128));
-    const int Kpad = cin == 3 ? round_up(k * k, 8) * 8 : k * k * cin;
-    if (tile == TILE_128x128 && Kpad >= 512) tile = (cout % 256 == 0) ? TILE_256x256_M16 : TILE_128x256;
-    if (tile == TILE_128x256 && stride == 1) tile = TILE_128x256_M16;
-    if (h->tune.op_tile >= 0 && cin != 3) tile = (ConvTile)h->tune.op_tile;   // test hook: force a tile variant
-    if (conv_tile_ch(tile) == 0) return h->fail(YH_EINVAL, "conv op: tune.op_tile is not a tile id");
-    const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);
-    const size_t M = (size_t)n * P * Q;
-    // host-side staging: pad input channels, repack weights, pad output rows to cout8
-    const std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
-    std::vector<uint16_t> wp((size_t)coutPad * Kpad, 0), rs, ys(M * cout8);
-    for (int o = 0; o < cout; ++o)
-        for (int t = 0; t < k * k; ++t) memcpy(&wp[(size_t)o * Kpad + (size_t)t * cs], &w[((size_t)o * k * k + t) * cin], (size_t)cin * 2);
-    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
-    if (residual) rs = pad_rows(residual, M, cout, cout8);
-    std::vector<int2> tab;
-    if (cin == 3) { tab.resize(Kpad / 8); for (int i = 0; i < Kpad / 8; ++i) tab[i] = i < k * k ? make_int2(i / k, i % k) : make_int2(1 << 20, 0); }
-    OpStaging st;
-    unsigned zo = 0;
-    const half_t* dx = st.upload_padded<half_t>(xs.data(), xs.size() * 2, xs.size() * 2 + 64, &zo);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
-    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
-    const int2* dt = cin == 3 ? st.upload<int2>(tab.data(), tab.size() * sizeof(int2)) : nullptr;
-    if (st.ok()) {
-        ConvParams p;
-        memset(&p, 0, sizeof p);
-        p.x = dx; p.w = dw; p.bias = db; p.res = dr; p.y = dy; p.rs_table = dt;
-        p.x_img_stride = (long long)hh * ww * cs; p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
-        p.x_zero_off = zo; p.x_bytes = zo + 16u;
-        p.w_bytes = (unsigned)(wp.size() * 2);
-        p.N = n; p.H = hh; p.W = ww; p.C = cs; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
-        p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad; p.ksteps = Kpad / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
-        p.act = act == 1 ? 1 : 0; p.tanh_from = act == 2 ? 0 : INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile);
-        if (nlev > 0) {
-            p.nlev = nlev;
-            for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
-        }
-        force_split_k(h, p, M, coutPad);
-        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
-    }
-    st.sync(h->stream);
-    st.get(ys.data(), dy, ys.size() * 2);
-    if (const int rc = st.status(h, "conv op: ")) return rc;
-    unpad_rows(y, ys, M, cout, cout8);
-    return YH_OK;
-}
-
-int yh_op_conv2d_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
-                     const float* bias, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
-                     const uint16_t* residual, int32_t act, uint16_t* y) {
-    return op_conv2d_impl(h, x, n, hh, ww, cin, w, bias, cout, kh, kw, stride, pad, residual, act, y, nullptr, 0);
-}
-
-int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t ho, int32_t wo, int32_t c1,
-                          const uint16_t* x2, int32_t h2, int32_t w2, int32_t c2, int32_t stride2,
-                          const uint16_t* w, const float* bias, int32_t cout, int32_t act, uint16_t* y) {
-    if (!h || !x1 || !x2 || !w || !bias || !y) return YH_EINVAL;
-    if (n < 1 || ho < 1 || wo < 1 || c1 < 64 || c1 % 64 != 0 || c2 < 64 || c2 % 64 != 0 || stride2 < 1 || cout < 1 || cout % 8 != 0 || act < 0 || act > 1 ||
-        (ho - 1) * stride2 >= h2 || (wo - 1) * stride2 >= w2)
-        return h->fail(YH_EINVAL, "dual conv op: need c1, c2 % 64 == 0, cout % 8 == 0 and x2 covering the strided output grid");
-    HIPCHK(h, hipSetDevice(h->dev));
-    ConvTile tile = TILE_128x128;
-    if (h->tune.op_tile >= 0) tile = (ConvTile)h->tune.op_tile;
-    if (!conv_tile_has(tile, FORM_DUAL)) return h->fail(YH_EINVAL, "dual conv op: tune.op_tile is not a tile of the two-source form");
-    const int K = c1 + c2, coutPad = round_up(cout, conv_tile_ch(tile));
-    const size_t M = (size_t)n * ho * wo, n1 = M * c1, n2 = (size_t)n * h2 * w2 * c2;
-    const std::vector<uint16_t> wp = pad_rows(w, 1, (size_t)cout * K, (size_t)coutPad * K);
-    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
-    OpStaging st;
-    unsigned z1 = 0, z2 = 0;
-    const half_t* d1 = st.upload_padded<half_t>(x1, n1 * 2, n1 * 2 + 64, &z1);
-    const half_t* d2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    half_t* dy = st.alloc<half_t>(M * cout * 2, 0xFF);
-    if (st.ok()) {
-        ConvParams p;
-        memset(&p, 0, sizeof p);
-        p.x = d1; p.w = dw; p.bias = db; p.y = dy;
-        p.x_img_stride = (long long)ho * wo * c1; p.y_img_stride = (long long)ho * wo * cout;
-        p.x_zero_off = z1; p.x_bytes = z1 + 16u;
-        p.x2 = d2; p.x2_img_stride = (long long)h2 * w2 * c2;
-        p.x2_zero_off = z2; p.x2_bytes = z2 + 16u;
-        p.W2 = w2; p.C2 = c2; p.stride2 = stride2; p.k1steps = c1 / 64;
-        p.w_bytes = (unsigned)(wp.size() * 2);
-        p.N = n; p.H = ho; p.W = wo; p.C = c1; p.P = ho; p.Q = wo; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
-        p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
-        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
-        if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, p, M, coutPad);
-        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
-    }
-    st.sync(h->stream);
-    st.get(y, dy, M * cout * 2);
-    return st.status(h, "dual conv op: ");
-}
-
-int yh_op_conv2d_levels_f16(yh_engine* h, const uint16_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
-                            const uint16_t* w, const float* bias, int32_t cout, int32_t k, int32_t act, uint16_t* y) {
-    if (!level_sizes || nlev < 1 || nlev > 5 || cin % 64 != 0 || (k != 1 && k != 3)) return YH_EINVAL;
-    int cells = 0;
-    for (int l = 0; l < nlev; ++l) { if (level_sizes[l] < 1) return YH_EINVAL; cells += level_sizes[l] * level_sizes[l]; }
-    return op_conv2d_impl(h, x, n, cells, 1, cin, w, bias, cout, k, k, 1, k / 2, nullptr, act, y, level_sizes, nlev);
-}
-
-int yh_op_bilinear_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, int32_t ho, int32_t wo, uint16_t* y) {
-    if (!h || !x || !y || c % 8 != 0 || n < 1) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
-    OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, ni * 2);
-    half_t* dy = st.alloc<half_t>(no * 2);
-    if (st.ok()) st.e = launch_bilinear(dx, dy, n, hh, ww, c, ho, wo, (long long)hh * ww * c, (long long)ho * wo * c, h->stream);
-    st.sync(h->stream);
-    st.get(y, dy, no * 2);
-    return st.status(h, "bilinear op: ");
-}
-
-int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, uint16_t* y) {
-    if (!h || !x || !y || c % 8 != 0 || n < 1) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    const int ho = out_dim(hh, 3, 2, 1), wo = out_dim(ww, 3, 2, 1);
-    const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
-    OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, ni * 2);
-    half_t* dy = st.alloc<half_t>(no * 2);
-    if (st.ok()) st.e = launch_maxpool3x3s2(dx, dy, n, hh, ww, c, ho, wo, h->stream);
-    st.sync(h->stream);
-    st.get(y, dy, no * 2);
-    return st.status(h, "maxpool op: ");
-}
-
-static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
-                             uint16_t* stem_out, uint16_t* pool_out) {
-    if (!h || (!x && !rgb) || !w || !bias || !pool_out || n < 1 || S < 8 || (S & 1)) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    const int Hp = S + 8, SO = out_dim(S, 7, 2, 3), PO = out_dim(SO, 3, 2, 1);
-    // host-side staging, as the engine does it: zero-bordered 4-channel image, stem panel [64][256]
-    std::vector<uint16_t> xs((size_t)n * Hp * Hp * 4, 0), wp((size_t)64 * 256, 0);
-    if (x)
-    for (int b = 0; b < n; ++b)
-        for (int yy = 0; yy < S; ++yy)
-            for (int xx = 0; xx < S; ++xx)
-                memcpy(&xs[(((size_t)b * Hp + yy + 3) * Hp + xx + 3) * 4], &x[(((size_t)b * S + yy) * S + xx) * 3], 6);
-    for (int o = 0; o < 64; ++o)
-        for (int r = 0; r < 7; ++r)
-            for (int sx = 0; sx < 7; ++sx)
-                for (int c = 0; c < 3; ++c) wp[(size_t)o * 256 + r * 32 + sx * 4 + c] = w[(((size_t)o * 7 + r) * 7 + sx) * 3 + c];
-    const size_t ns = (size_t)n * SO * SO * 64, np = (size_t)n * PO * PO * 64;
-    OpStaging st;
-    const half_t* dx = st.alloc<half_t>(xs.size() * 2);
-    const uint8_t* drgb = rgb ? st.upload<uint8_t>(rgb, (size_t)n * S * S * 3) : nullptr;
-    st.put(dx, xs.data(), xs.size() * 2);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bias, 64 * 4);
-    half_t* ds = st.alloc<half_t>(ns * 2, 0xFF);
-    half_t* dp = st.alloc<half_t>(np * 2, 0xFF);
-    if (st.ok()) {
-        StemPoolParams sp;
-        sp.x = dx; sp.w = dw; sp.bias = db; sp.pool = dp;
-        sp.rgb = drgb; sp.S = S;
-        sp.stem = stem_out ? ds : nullptr;
-        sp.n = n; sp.Hp = Hp; sp.Wp = Hp; sp.SO = SO; sp.PO = PO; sp.tiles_y = (PO + 7) / 8; sp.tiles_x = (PO + 7) / 8;
-        sp.x_img_stride = (long long)Hp * Hp * 4; sp.pool_img_stride = (long long)PO * PO * 64; sp.stem_img_stride = (long long)SO * SO * 64;
-        st.e = launch_stem_pool(sp, h->stream);
-    }
-    st.sync(h->stream);
-    if (stem_out) st.get(stem_out, ds, ns * 2);
-    st.get(pool_out, dp, np * 2);
-    return st.status(h, "stem+pool op: ");
-}
-
-int yh_op_stem_pool_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t S, const uint16_t* w, const float* bias,
-                        uint16_t* stem_out, uint16_t* pool_out) {
-    return op_stem_pool_impl(h, x, nullptr, n, S, w, bias, stem_out, pool_out);
-}
-int yh_op_stem_pool_rgb8(yh_engine* h, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
-                         uint16_t* stem_out, uint16_t* pool_out) {
-    return op_stem_pool_impl(h, nullptr, rgb, n, S, w, bias, stem_out, pool_out);
-}
-
-// Experimental: the fp8 form of the convolution through the 256x256 tile. x: E4M3 codes
-// [n][hh][ww][cin], w: E4M3 codes [cout][k][k][cin], out = act(acc * scale[ch] + bias[ch] (+ residual)) as f16.
-int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
-                     const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
-                     const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch) {
-    if (!h || !x || !w || !scale || !bias || !y || n < 1 || k < 1 || stride < 1 || cin % 128 != 0 || (act < 0 || act > 1))
-        return h ? h->fail(YH_EINVAL, "fp8 conv op: need cin % 128 == 0") : YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    const int P = out_dim(hh, k, stride, pad), Q = out_dim(ww, k, stride, pad);
-    if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "fp8 conv op: empty output");
-    const int Kpad = k * k * cin, coutPad = round_up(cout, 256), cout8 = round_up(cout, 8);
-    const size_t M = (size_t)n * P * Q, xbytes = (size_t)n * hh * ww * cin;
-    const std::vector<uint8_t> wp = pad_rows(w, 1, (size_t)cout * Kpad, (size_t)coutPad * Kpad);   // [cout][k][k][cin] is already the panel's K order
-    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad), sp = pad_rows(scale, 1, cout, coutPad);
-    std::vector<uint16_t> rs, ys(M * cout8);
-    if (residual) rs = pad_rows(residual, M, cout, cout8);
-    OpStaging st;
-    unsigned zo = 0;
-    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size());
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    const float* dsc = st.upload<float>(sp.data(), sp.size() * 4);
-    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
-    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
-    if (st.ok()) {
-        ConvParams p;
-        memset(&p, 0, sizeof p);
-        p.x = dx; p.w = dw; p.bias = db; p.scale = dsc; p.res = dr; p.y = dy;
-        // the loader's units are 2 bytes: two fp8 values
-        p.x_img_stride = (long long)hh * ww * (cin / 2); p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
-        p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)wp.size();
-        p.N = n; p.H = hh; p.W = ww; p.C = cin / 2; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
-        p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad / 2; p.ksteps = Kpad / 128; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
-        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / 256; p.k_slices = 1;
-        st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
-        st.sync(h->stream);
-        if (st.ok() && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
-            hipEventRecord(h->ev0, h->stream);
-            for (int r = 0; r < reps && st.ok(); ++r) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
-            hipEventRecord(h->ev1, h->stream);
-            if (st.ok()) st.e = hipEventSynchronize(h->ev1);
-            float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
-            *ms_per_launch = ms / reps;
-        }
-    }
-    st.get(ys.data(), dy, ys.size() * 2);
-    if (const int rc = st.status(h, "fp8 conv op: ")) return rc;
-    unpad_rows(y, ys, M, cout, cout8);
-    return YH_OK;
-}
-
-int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_scale, uint8_t* y) {
-    if (!h || !x || !y || n < 1) return YH_EINVAL;
-    HIPCHK(h, hipSetDevice(h->dev));
-    OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, n * 2);
-    uint8_t* dy = st.alloc<uint8_t>(n);
-    if (st.ok()) st.e = launch_quantize_e4m3(dx, dy, (long long)n, inv_scale, h->stream);
-    st.sync(h->stream);
-    st.get(y, dy, n);
-    return st.status(h, "quantize op: ");
-}
-
-int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask, const uint16_t* proto, int32_t n) {
-    if (!h || !loc || !conf || !mask || !proto) return YH_EINVAL;
-    if (n < 1 || n > h->cfg.max_batch) return h->fail(YH_EINVAL, "n out of range");
-    HIPCHK(h, hipSetDevice(h->dev));
-    // interleave into the fused head rows [n][cells][ldh]
-    const int C = h->C, ldh = h->ldh;
-    std::vector<uint16_t> rows((size_t)n * h->cells * ldh, 0);
-    for (size_t r = 0; r < (size_t)n * h->cells; ++r) {
-        uint16_t* d = &rows[r * ldh];
-        memcpy(d, &loc[r * 12], 24);
-        memcpy(d + 12, &conf[r * 3 * C], (size_t)3 * C * 2);
-        memcpy(d + 12 + 3 * C, &mask[r * 96], 192);
-    }
-    HIPCHK(h, hipMemcpy(h->heads.d, rows.data(), rows.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->proto.d, proto, (size_t)n * h->hp * h->wp * 32 * 2, hipMemcpyHostToDevice));
-    h->cur_n = n;
-    h->det.n = n;
-    hipError_t e = launch_detect(h->det, h->stream);
-    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("detect: ") + hipGetErrorString(e));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return YH_OK;
-}
 
 }  // extern "C"

@@ -1,0 +1,345 @@
+// engine_ops.hip - the single-op entry points (yh_op_*): one kernel on caller-supplied tensors. Only tests call them.
+#include <string.h>
+
+#include "engine.h"
+
+using namespace yh;
+
+namespace {
+
+// The device buffers of one single-op call: allocated (and filled - 0 behind a zero-padded input, 0xFF, the NaN pattern an
+// unwritten element shows, in an output) and uploaded in the order the call asks for them, freed when the call returns.
+// The first HIP error is kept and every step after it is skipped.
+struct OpStaging {
+    hipError_t e = hipSuccess;
+    std::vector<void*> bufs;
+    OpStaging() = default;
+    OpStaging(const OpStaging&) = delete;
+    ~OpStaging() { for (void* d : bufs) hipFree(d); }
+    bool ok() const { return e == hipSuccess; }
+    template <class T> T* alloc(size_t bytes, int fill = -1) {
+        void* d = nullptr;
+        if (ok() && (e = hipMalloc(&d, bytes)) == hipSuccess) bufs.push_back(d);
+        if (ok() && fill >= 0) e = hipMemset(d, fill, bytes);
+        return ok() ? (T*)d : nullptr;
+    }
+    void put(const void* d, const void* src, size_t bytes) { if (ok()) e = hipMemcpy((void*)d, src, bytes, hipMemcpyHostToDevice); }
+    template <class T> T* upload(const void* src, size_t bytes) { T* d = alloc<T>(bytes); put(d, src, bytes); return d; }
+    // a conv input with its zero pixel behind the data: `cap` zeroed bytes, the data first; *zero_off = where the zeros start
+    template <class T> T* upload_padded(const void* src, size_t bytes, size_t cap, unsigned* zero_off) {
+        *zero_off = (unsigned)pad16(bytes);
+        T* d = alloc<T>(cap, 0);
+        put(d, src, bytes);
+        return d;
+    }
+    void sync(hipStream_t s) { if (ok()) e = hipStreamSynchronize(s); }
+    void get(void* dst, const void* d, size_t bytes) { if (ok()) e = hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost); }
+    int status(yh_engine* h, const char* what) const { return ok() ? YH_OK : h->fail(YH_EHIP, std::string(what) + hipGetErrorString(e)); }
+};
+
+// rows of c values, zero-padded to rows of ld (input channels to the stored count, output channels to cout8) - and back
+template <class T> std::vector<T> pad_rows(const T* src, size_t rows, size_t c, size_t ld) {
+    std::vector<T> v(rows * ld, T(0));
+    for (size_t m = 0; m < rows; ++m) memcpy(&v[m * ld], &src[m * c], c * sizeof(T));
+    return v;
+}
+void unpad_rows(uint16_t* dst, const std::vector<uint16_t>& src, size_t rows, size_t c, size_t ld) {
+    for (size_t m = 0; m < rows; ++m) memcpy(&dst[m * c], &src[m * ld], c * 2);
+}
+
+// test hook (tune.op_kslices): a forced split-K of a single-op launch (the engine decides it in fill_conv_params)
+void force_split_k(yh_engine* h, ConvParams& p, size_t M, int coutPad) {
+    const int ksl = h->tune.op_kslices;
+    if (ksl < 2 || ksl > p.ksteps || (size_t)ksl * M * coutPad * 4 > yh_engine::kSplitKBytes) return;
+    p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
+    p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
+    p.partial_ld = coutPad;
+    p.partial = h->splitk_ws;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- single-op entry points (tests) ------------------------------------------------------------
+// Each one reads: validate, stage (host-side repacking, then the device buffers), fill the kernel's parameters, launch, read back.
+static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
+                          const float* bias, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
+                          const uint16_t* residual, int32_t act, uint16_t* y, const int32_t* level_sizes, int32_t nlev) {
+    if (!h || !x || !w || !bias || !y) return YH_EINVAL;
+    if (kh != kw || kh < 1 || stride < 1 || n < 1 || (cin != 3 && cin % 64 != 0) || (act < 0 || act > 2))
+        return h->fail(YH_EINVAL, "conv op: need square kernel and cin == 3 or cin % 64 == 0");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int cs = cin == 3 ? 8 : cin, k = kh;
+    // multi-level form: x is [n][cells][cin], cells = the levels' squares laid end to end (hh = cells, ww = 1)
+    const int P = nlev > 0 ? hh : out_dim(hh, k, stride, pad), Q = nlev > 0 ? 1 : out_dim(ww, k, stride, pad);
+    if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "conv op: empty output");
+    ConvTile tile = cin == 3 ? TILE_64x256_SMALLC : (cout <= 32 ? TILE_32x256 : (cout <= 64 ? TILE_64x256 : TILE_128x128));
+    const int Kpad = cin == 3 ? round_up(k * k, 8) * 8 : k * k * cin;
+    if (tile == TILE_128x128 && Kpad >= 512) tile = (cout % 256 == 0) ? TILE_256x256_M16 : TILE_128x256;
+    if (tile == TILE_128x256 && stride == 1) tile = TILE_128x256_M16;
+    if (h->tune.op_tile >= 0 && cin != 3) tile = (ConvTile)h->tune.op_tile;   // test hook: force a tile variant
+    if (conv_tile_ch(tile) == 0) return h->fail(YH_EINVAL, "conv op: tune.op_tile is not a tile id");
+    const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);
+    const size_t M = (size_t)n * P * Q;
+    // host-side staging: pad input channels, repack weights, pad output rows to cout8
+    const std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
+    std::vector<uint16_t> wp((size_t)coutPad * Kpad, 0), rs, ys(M * cout8);
+    for (int o = 0; o < cout; ++o)
+        for (int t = 0; t < k * k; ++t) memcpy(&wp[(size_t)o * Kpad + (size_t)t * cs], &w[((size_t)o * k * k + t) * cin], (size_t)cin * 2);
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    if (residual) rs = pad_rows(residual, M, cout, cout8);
+    std::vector<int2> tab;
+    if (cin == 3) { tab.resize(Kpad / 8); for (int i = 0; i < Kpad / 8; ++i) tab[i] = i < k * k ? make_int2(i / k, i % k) : make_int2(1 << 20, 0); }
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(xs.data(), xs.size() * 2, xs.size() * 2 + 64, &zo);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
+    const int2* dt = cin == 3 ? st.upload<int2>(tab.data(), tab.size() * sizeof(int2)) : nullptr;
+    if (st.ok()) {
+        ConvParams p;
+        memset(&p, 0, sizeof p);
+        p.x = dx; p.w = dw; p.bias = db; p.res = dr; p.y = dy; p.rs_table = dt;
+        p.x_img_stride = (long long)hh * ww * cs; p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
+        p.x_zero_off = zo; p.x_bytes = zo + 16u;
+        p.w_bytes = (unsigned)(wp.size() * 2);
+        p.N = n; p.H = hh; p.W = ww; p.C = cs; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
+        p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad; p.ksteps = Kpad / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
+        p.act = act == 1 ? 1 : 0; p.tanh_from = act == 2 ? 0 : INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile);
+        if (nlev > 0) {
+            p.nlev = nlev;
+            for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
+        }
+        force_split_k(h, p, M, coutPad);
+        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
+    }
+    st.sync(h->stream);
+    st.get(ys.data(), dy, ys.size() * 2);
+    if (const int rc = st.status(h, "conv op: ")) return rc;
+    unpad_rows(y, ys, M, cout, cout8);
+    return YH_OK;
+}
+
+int yh_op_conv2d_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
+                     const float* bias, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
+                     const uint16_t* residual, int32_t act, uint16_t* y) {
+    return op_conv2d_impl(h, x, n, hh, ww, cin, w, bias, cout, kh, kw, stride, pad, residual, act, y, nullptr, 0);
+}
+
+int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t ho, int32_t wo, int32_t c1,
+                          const uint16_t* x2, int32_t h2, int32_t w2, int32_t c2, int32_t stride2,
+                          const uint16_t* w, const float* bias, int32_t cout, int32_t act, uint16_t* y) {
+    if (!h || !x1 || !x2 || !w || !bias || !y) return YH_EINVAL;
+    if (n < 1 || ho < 1 || wo < 1 || c1 < 64 || c1 % 64 != 0 || c2 < 64 || c2 % 64 != 0 || stride2 < 1 || cout < 1 || cout % 8 != 0 || act < 0 || act > 1 ||
+        (ho - 1) * stride2 >= h2 || (wo - 1) * stride2 >= w2)
+        return h->fail(YH_EINVAL, "dual conv op: need c1, c2 % 64 == 0, cout % 8 == 0 and x2 covering the strided output grid");
+    HIPCHK(h, hipSetDevice(h->dev));
+    ConvTile tile = TILE_128x128;
+    if (h->tune.op_tile >= 0) tile = (ConvTile)h->tune.op_tile;
+    if (!conv_tile_has(tile, FORM_DUAL)) return h->fail(YH_EINVAL, "dual conv op: tune.op_tile is not a tile of the two-source form");
+    const int K = c1 + c2, coutPad = round_up(cout, conv_tile_ch(tile));
+    const size_t M = (size_t)n * ho * wo, n1 = M * c1, n2 = (size_t)n * h2 * w2 * c2;
+    const std::vector<uint16_t> wp = pad_rows(w, 1, (size_t)cout * K, (size_t)coutPad * K);
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    OpStaging st;
+    unsigned z1 = 0, z2 = 0;
+    const half_t* d1 = st.upload_padded<half_t>(x1, n1 * 2, n1 * 2 + 64, &z1);
+    const half_t* d2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    half_t* dy = st.alloc<half_t>(M * cout * 2, 0xFF);
+    if (st.ok()) {
+        ConvParams p;
+        memset(&p, 0, sizeof p);
+        p.x = d1; p.w = dw; p.bias = db; p.y = dy;
+        p.x_img_stride = (long long)ho * wo * c1; p.y_img_stride = (long long)ho * wo * cout;
+        p.x_zero_off = z1; p.x_bytes = z1 + 16u;
+        p.x2 = d2; p.x2_img_stride = (long long)h2 * w2 * c2;
+        p.x2_zero_off = z2; p.x2_bytes = z2 + 16u;
+        p.W2 = w2; p.C2 = c2; p.stride2 = stride2; p.k1steps = c1 / 64;
+        p.w_bytes = (unsigned)(wp.size() * 2);
+        p.N = n; p.H = ho; p.W = wo; p.C = c1; p.P = ho; p.Q = wo; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
+        p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
+        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
+        if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, p, M, coutPad);
+        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
+    }
+    st.sync(h->stream);
+    st.get(y, dy, M * cout * 2);
+    return st.status(h, "dual conv op: ");
+}
+
+int yh_op_conv2d_levels_f16(yh_engine* h, const uint16_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
+                            const uint16_t* w, const float* bias, int32_t cout, int32_t k, int32_t act, uint16_t* y) {
+    if (!level_sizes || nlev < 1 || nlev > 5 || cin % 64 != 0 || (k != 1 && k != 3)) return YH_EINVAL;
+    int cells = 0;
+    for (int l = 0; l < nlev; ++l) { if (level_sizes[l] < 1) return YH_EINVAL; cells += level_sizes[l] * level_sizes[l]; }
+    return op_conv2d_impl(h, x, n, cells, 1, cin, w, bias, cout, k, k, 1, k / 2, nullptr, act, y, level_sizes, nlev);
+}
+
+int yh_op_bilinear_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, int32_t ho, int32_t wo, uint16_t* y) {
+    if (!h || !x || !y || c % 8 != 0 || n < 1) return YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, ni * 2);
+    half_t* dy = st.alloc<half_t>(no * 2);
+    if (st.ok()) st.e = launch_bilinear(dx, dy, n, hh, ww, c, ho, wo, (long long)hh * ww * c, (long long)ho * wo * c, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, no * 2);
+    return st.status(h, "bilinear op: ");
+}
+
+int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, uint16_t* y) {
+    if (!h || !x || !y || c % 8 != 0 || n < 1) return YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int ho = out_dim(hh, 3, 2, 1), wo = out_dim(ww, 3, 2, 1);
+    const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, ni * 2);
+    half_t* dy = st.alloc<half_t>(no * 2);
+    if (st.ok()) st.e = launch_maxpool3x3s2(dx, dy, n, hh, ww, c, ho, wo, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, no * 2);
+    return st.status(h, "maxpool op: ");
+}
+
+static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
+                             uint16_t* stem_out, uint16_t* pool_out) {
+    if (!h || (!x && !rgb) || !w || !bias || !pool_out || n < 1 || S < 8 || (S & 1)) return YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int Hp = S + 8, SO = out_dim(S, 7, 2, 3), PO = out_dim(SO, 3, 2, 1);
+    // host-side staging, as the engine does it: zero-bordered 4-channel image, stem panel [64][256]
+    std::vector<uint16_t> xs((size_t)n * Hp * Hp * 4, 0), wp((size_t)64 * 256, 0);
+    if (x)
+    for (int b = 0; b < n; ++b)
+        for (int yy = 0; yy < S; ++yy)
+            for (int xx = 0; xx < S; ++xx)
+                memcpy(&xs[(((size_t)b * Hp + yy + 3) * Hp + xx + 3) * 4], &x[(((size_t)b * S + yy) * S + xx) * 3], 6);
+    for (int o = 0; o < 64; ++o)
+        for (int r = 0; r < 7; ++r)
+            for (int sx = 0; sx < 7; ++sx)
+                for (int c = 0; c < 3; ++c) wp[(size_t)o * 256 + r * 32 + sx * 4 + c] = w[(((size_t)o * 7 + r) * 7 + sx) * 3 + c];
+    const size_t ns = (size_t)n * SO * SO * 64, np = (size_t)n * PO * PO * 64;
+    OpStaging st;
+    const half_t* dx = st.alloc<half_t>(xs.size() * 2);
+    const uint8_t* drgb = rgb ? st.upload<uint8_t>(rgb, (size_t)n * S * S * 3) : nullptr;
+    st.put(dx, xs.data(), xs.size() * 2);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bias, 64 * 4);
+    half_t* ds = st.alloc<half_t>(ns * 2, 0xFF);
+    half_t* dp = st.alloc<half_t>(np * 2, 0xFF);
+    if (st.ok()) {
+        StemPoolParams sp;
+        sp.x = dx; sp.w = dw; sp.bias = db; sp.pool = dp;
+        sp.rgb = drgb; sp.S = S;
+        sp.stem = stem_out ? ds : nullptr;
+        sp.n = n; sp.Hp = Hp; sp.Wp = Hp; sp.SO = SO; sp.PO = PO; sp.tiles_y = (PO + 7) / 8; sp.tiles_x = (PO + 7) / 8;
+        sp.x_img_stride = (long long)Hp * Hp * 4; sp.pool_img_stride = (long long)PO * PO * 64; sp.stem_img_stride = (long long)SO * SO * 64;
+        st.e = launch_stem_pool(sp, h->stream);
+    }
+    st.sync(h->stream);
+    if (stem_out) st.get(stem_out, ds, ns * 2);
+    st.get(pool_out, dp, np * 2);
+    return st.status(h, "stem+pool op: ");
+}
+
+int yh_op_stem_pool_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t S, const uint16_t* w, const float* bias,
+                        uint16_t* stem_out, uint16_t* pool_out) {
+    return op_stem_pool_impl(h, x, nullptr, n, S, w, bias, stem_out, pool_out);
+}
+int yh_op_stem_pool_rgb8(yh_engine* h, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
+                         uint16_t* stem_out, uint16_t* pool_out) {
+    return op_stem_pool_impl(h, nullptr, rgb, n, S, w, bias, stem_out, pool_out);
+}
+
+// Experimental: the fp8 form of the convolution through the 256x256 tile. x: E4M3 codes
+// [n][hh][ww][cin], w: E4M3 codes [cout][k][k][cin], out = act(acc * scale[ch] + bias[ch] (+ residual)) as f16.
+int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
+                     const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                     const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch) {
+    if (!h || !x || !w || !scale || !bias || !y || n < 1 || k < 1 || stride < 1 || cin % 128 != 0 || (act < 0 || act > 1))
+        return h ? h->fail(YH_EINVAL, "fp8 conv op: need cin % 128 == 0") : YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int P = out_dim(hh, k, stride, pad), Q = out_dim(ww, k, stride, pad);
+    if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "fp8 conv op: empty output");
+    const int Kpad = k * k * cin, coutPad = round_up(cout, 256), cout8 = round_up(cout, 8);
+    const size_t M = (size_t)n * P * Q, xbytes = (size_t)n * hh * ww * cin;
+    const std::vector<uint8_t> wp = pad_rows(w, 1, (size_t)cout * Kpad, (size_t)coutPad * Kpad);   // [cout][k][k][cin] is already the panel's K order
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad), sp = pad_rows(scale, 1, cout, coutPad);
+    std::vector<uint16_t> rs, ys(M * cout8);
+    if (residual) rs = pad_rows(residual, M, cout, cout8);
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size());
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    const float* dsc = st.upload<float>(sp.data(), sp.size() * 4);
+    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
+    if (st.ok()) {
+        ConvParams p;
+        memset(&p, 0, sizeof p);
+        p.x = dx; p.w = dw; p.bias = db; p.scale = dsc; p.res = dr; p.y = dy;
+        // the loader's units are 2 bytes: two fp8 values
+        p.x_img_stride = (long long)hh * ww * (cin / 2); p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
+        p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)wp.size();
+        p.N = n; p.H = hh; p.W = ww; p.C = cin / 2; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
+        p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad / 2; p.ksteps = Kpad / 128; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
+        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / 256; p.k_slices = 1;
+        st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+        st.sync(h->stream);
+        if (st.ok() && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
+            hipEventRecord(h->ev0, h->stream);
+            for (int r = 0; r < reps && st.ok(); ++r) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+            hipEventRecord(h->ev1, h->stream);
+            if (st.ok()) st.e = hipEventSynchronize(h->ev1);
+            float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
+            *ms_per_launch = ms / reps;
+        }
+    }
+    st.get(ys.data(), dy, ys.size() * 2);
+    if (const int rc = st.status(h, "fp8 conv op: ")) return rc;
+    unpad_rows(y, ys, M, cout, cout8);
+    return YH_OK;
+}
+
+int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_scale, uint8_t* y) {
+    if (!h || !x || !y || n < 1) return YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, n * 2);
+    uint8_t* dy = st.alloc<uint8_t>(n);
+    if (st.ok()) st.e = launch_quantize_e4m3(dx, dy, (long long)n, inv_scale, h->stream);
+    st.sync(h->stream);
+    st.get(y, dy, n);
+    return st.status(h, "quantize op: ");
+}
+
+int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask, const uint16_t* proto, int32_t n) {
+    if (!h || !loc || !conf || !mask || !proto) return YH_EINVAL;
+    if (n < 1 || n > h->cfg.max_batch) return h->fail(YH_EINVAL, "n out of range");
+    HIPCHK(h, hipSetDevice(h->dev));
+    // interleave into the fused head rows [n][cells][ldh]
+    const int C = h->C, ldh = h->ldh;
+    std::vector<uint16_t> rows((size_t)n * h->cells * ldh, 0);
+    for (size_t r = 0; r < (size_t)n * h->cells; ++r) {
+        uint16_t* d = &rows[r * ldh];
+        memcpy(d, &loc[r * 12], 24);
+        memcpy(d + 12, &conf[r * 3 * C], (size_t)3 * C * 2);
+        memcpy(d + 12 + 3 * C, &mask[r * 96], 192);
+    }
+    HIPCHK(h, hipMemcpy(h->heads.d, rows.data(), rows.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->proto.d, proto, (size_t)n * h->hp * h->wp * 32 * 2, hipMemcpyHostToDevice));
+    h->cur_n = n;
+    h->det.n = n;
+    hipError_t e = launch_detect(h->det, h->stream);
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("detect: ") + hipGetErrorString(e));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return YH_OK;
+}
+
+}  // extern "C"
