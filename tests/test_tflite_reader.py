@@ -46,7 +46,7 @@ def test_reader_rejects_garbage_without_crashing(built):
 
 def _structural_mutants(rng):
     """(description, model) pairs: builder models broken in exactly the ways the plan builder (tflite_exec.hip:
-    prepare) would otherwise trip over: operand indices, arity, ranks, zero strides / dilations / multipliers."""
+    prepare, OpPrep) would otherwise trip over: operand indices, arity, ranks, zero strides / dilations / multipliers."""
     out = []
 
     def mut(code, what, fn, **kw):

@@ -14,7 +14,7 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
         yh::TflModel m;
         const bool ok = m.parse(b.data(), b.size());
-        // what the plan builder computes from a validated file (tflite_exec.hip: prepare / same_pad): must be safe
+        // what the plan builder computes from a validated file (tflite_exec.hip: OpPrep::conv / same_pad): must be safe
         long long sink = 0;
         if (ok)
             for (const yh::TflOp& op : m.ops)

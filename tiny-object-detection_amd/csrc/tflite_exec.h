@@ -1,0 +1,75 @@
+// tflite_exec.h — what the TFLite executor's two units share: the kernels' parameter structs and one launcher per kernel family
+// (tflite_kernels.hip: the device code; tflite_exec.hip: the plan and the C ABI). Not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// (hidden: nothing declared here is exported from the shared library)
+namespace yh __attribute__((visibility("hidden"))) {
+
+// Operators folded into their producer at plan time (round 4, yh_tuning.tfl_fuse): the producer computes its own uint8 output
+// value exactly as TFLite does - in a register - and the element-wise operators that consumed it (QUANTIZE / RELU / RELU6 as a
+// requantisation, TANH as its 256-entry table, ADD with its other operand read from memory) run on that value before the one
+// store: the same integers in the same order, no intermediate tensor, no launch. A CONCATENATION part with the output's own
+// quantisation is written by its producer straight into the concatenated tensor, a PAD in front of a convolution becomes that
+// convolution's padding (a padded tap holds the zero point: (x - zx) = 0, the tap TFLite's kernels skip).
+struct PostStep { int kind; int zi, zo, m, s, lo, hi; const uint8_t* lut; };   // 1 requantise, 2 table, 3 the ADD below
+struct PostOps {
+    int n;
+    PostStep st[3];
+    const uint8_t* other; long long other_s;    // ADD: the other operand (same shape), bytes per image
+    int q_is_a, za, zb, m1, s1, m2, s2, mo, so, azo, alo, ahi;
+};
+
+// A convolution: the host's one record of it (tflite_exec.hip: Prepared) and the argument of every kernel but the int8 MFMA ones
+struct ConvQ {
+    const uint8_t *x, *w; const int* bias; uint8_t* y;
+    int H, W, Ci, Ho, Wo, Co, kh, kw, sh, sw, ph, pw, dh, dw, dm;
+    int zx, zw, zo, mult, shift, lo, hi;
+    const int* wsum;   // [Co][kh*kw]: sum of the raw weight bytes of one tap (dot-product kernel), or nullptr
+    // batch plan (yh_tfl_set_batch): the grid's last used dimension is the image; activations are image-major
+    long long xs, ys;  // bytes per image of x / y
+    PostOps po;
+};
+// The argument of the int8 MFMA kernels, built from the record for one image count when a launch or a group is made (conv_i8_args)
+struct ConvI8 {
+    const uint8_t* x; const uint8_t* wq; const int* cterm; uint8_t* y;   // wq: [CoPad][K] bytes w ^ 0x80, K = (r, s, c); cterm: [CoPad]
+    int H, W, Ci, Ho, Wo, Co, kh, kw, sh, sw, ph, pw, dh, dw;
+    int zx, zw, zo, mult, shift, lo, hi, K, M;
+    long long xs, ys;
+    PostOps po;
+};
+struct AddQ { const uint8_t *a, *b; uint8_t* y; long long n; int za, zb, zo, m1, s1, m2, s2, mo, so, lo, hi; };
+struct PadQ { const uint8_t* x; uint8_t* y; int id[4], od[4], before[4]; int fill; };
+struct ResizeQ { const uint8_t* x; uint8_t* y; int H, W, C, Ho, Wo; float hs, ws; int half_pixel; long long ys; PostOps po; };
+// copy one concat input [outer][inner] into the output at column `off` of rows of `row` elements
+struct CatQ { const uint8_t* x; uint8_t* y; long long outer; int inner, row, off, esz; int rescale; float sc, bias; int zo; };
+
+constexpr int kPx8MaxK = 512;   // taps x input channels a launch of tfl_conv_u8_px8 can hold (16 KB of LDS)
+constexpr int kMaxGroup = 16;   // convolutions of one tfl_conv_i8_direct_group launch
+
+// One launcher per kernel family. `nb` = the images of this invoke: the per-image structs are launched over nb images (a grid
+// dimension, or nb x the elements of an image-major activation); a ConvI8 holds its image count in M. Launch errors are left to
+// the caller's hipGetLastError().
+// CONV_2D: the dot-product kernel where p.wsum is set, else (dot) the 8-channels-per-lane kernel while its weights fit LDS, else one lane per element
+void launch_conv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s);
+// DEPTHWISE_CONV_2D: (dot) four channels per lane where the layer allows it, else one lane per element
+void launch_dwconv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s);
+void launch_conv_i8_mfma(const ConvI8& q, hipStream_t s);
+// The register-fed int8 kernel is built in a table of forms (ring depth, whole K in one pass, compile-time extent).
+int conv_i8_direct_form(int kh, int kw, int Ci);   // the table row a convolution runs, < 0: the table has none for it
+bool conv_i8_direct_pays(const ConvI8& q);         // this launch is faster register-fed than on the LDS tiles
+void launch_conv_i8_direct(int form, const ConvI8& q, hipStream_t s);
+// ... several convolutions of one form as one launch: parameter blocks and tile prefix table in device memory, `tiles` workgroups
+void launch_conv_i8_direct_group(int form, const ConvI8* probs, const int* tile_start, int nprob, int tiles, hipStream_t s);
+void launch_add_u8(const AddQ& p, unsigned nb, hipStream_t s);
+void launch_requant_u8(const uint8_t* x, uint8_t* y, long long n, int zi, int zo, int m, int sh, int lo, int hi, hipStream_t s);
+void launch_quantize_f32(const float* x, uint8_t* y, long long n, float scale, int zo, hipStream_t s);
+void launch_dequantize_u8(const uint8_t* x, float* y, long long n, float scale, int z, hipStream_t s);
+void launch_lut_u8(const uint8_t* x, uint8_t* y, long long n, const uint8_t* lut, hipStream_t s);
+void launch_pad_u8(const PadQ& p, unsigned nb, hipStream_t s);
+void launch_resize_bilinear_u8(const ResizeQ& p, unsigned nb, hipStream_t s);
+void launch_concat_part(const CatQ& p, unsigned nb, hipStream_t s);
+void launch_copy_bytes(const uint8_t* x, uint8_t* y, long long n, hipStream_t s);
+
+}  // namespace yh
