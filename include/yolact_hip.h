@@ -346,6 +346,28 @@ int yh_scene_append_classified(yh_scene* h, const uint16_t* depth_host, const ui
 /* scene.rs:284-330: height map u32 [h][w], world / connections0 / connections1 f32 [h][w][4], balls f32 [100][4]
  * = (mean x, mean y, pixel count, 0). Any pointer may be NULL. Waits for the frame. */
 int yh_scene_read(yh_scene* h, uint32_t* map, float* world, float* conn0, float* conn1, float* balls);
+/* modify_path (src/path.rs:25-120) on the fields of the last appended frame, which stay on the device: the multi-source cost
+ * field from the targets over the 4-connected pixel grid - an edge costs the scene's connection length plus the height step
+ * (path.rs:59) -, every pixel's successor, and the route from the start pixel to a target. The reference's function cannot run
+ * (it indexes 224 x 224 arrays by x + y * 480); what is computed is the definition of DESIGN.md section 11 "Path planner".
+ * targets_xy: n_targets pixels (x, y), or NULL: the first n_targets balls that have pixels, in id order, at their truncated
+ * means (balls[..3], path.rs:37-38; scene.rs:321), those outside the frame dropped. (start_x, start_y): the robot's pixel
+ * (START_NODE, path.rs:93: (400, 479) at 640 x 480). Synchronous: returns when the route is known. The planner's buffers are
+ * allocated at the first plan on a handle. YH_ESTATE: no frame yet, the last frame was appended in YH_COMPAT_STRICT (its
+ * connections are all distances to world(0,0): no planner is defined on them), or targets_xy is NULL and no ball is usable;
+ * YH_EINVAL: n_targets < 1, a target or the start outside the frame, or (W + H) * (2 * max(H, 101) + 1) >= 2^24. A call refused
+ * with YH_EINVAL or YH_ESTATE has touched nothing: an earlier plan of the same frame stays readable. A call that fails later
+ * (YH_EHIP) leaves no plan. */
+int yh_scene_plan(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                  int32_t start_x, int32_t start_y);
+/* The last plan (path.rs:93-119: the walk from START_NODE, Path.directions): cost f32 [h][w], next i32 [h][w] (linear index
+ * y * w + x of the successor, -1 at targets), path_xy i32 [cap][2] (the route's pixels, start and target included),
+ * directions f32 [cap][2] = (magnitude, rotation) per step of the route (*path_len - 1 pairs, what Path::serialize sends,
+ * path.rs:17-21); any pointer may be NULL. *path_len = nodes on the route. YH_EOVERFLOW (and *path_len set, nothing copied)
+ * if path_capacity < *path_len while path_xy or directions is asked for; YH_ESTATE before a plan, or when a frame was
+ * appended since the plan. */
+int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy, float* directions,
+                       int32_t path_capacity, int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

@@ -1,0 +1,38 @@
+// scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels) and scene_path.hip (the planner on its fields).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "yh_internal.h"
+
+struct yh_scene_path;   // the planner's buffers and last plan (scene_path.hip); allocated at the first yh_scene_plan
+
+struct yh_scene {
+    int dev = 0, W = 0, H = 0, band_h = 64;
+    hipStream_t stream = nullptr;
+    hipEvent_t copied = nullptr;
+    std::string err;
+    uint16_t* depth = nullptr;
+    uint8_t* cls_id = nullptr;
+    uint32_t* frame = nullptr;
+    uint32_t* map = nullptr;
+    float4 *world = nullptr, *conn0 = nullptr, *conn1 = nullptr, *balls = nullptr;
+    long long* ball_acc = nullptr;
+    uint32_t *terrain_tab = nullptr, *robot_tab = nullptr;
+    bool ran = false;
+    // what the last append ran on (yh_scene_time replays exactly this)
+    const uint8_t* last_cls = nullptr;
+    const uint32_t* last_frame = nullptr;
+    int last_frame_mode = 0, last_mode = 0;
+    uint64_t frames = 0;   // appends (and yh_scene_set_fields) so far: a plan belongs to the frame it was made on
+    yh_scene_path* path = nullptr;
+    int fail(int code, const std::string& m) { err = m; return code; }
+};
+
+#define SCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (h)->fail(YH_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
+
+namespace yh {
+void scene_path_free(yh_scene* h);   // yh_scene_destroy: the planner's buffers (the handle's device is current, its stream idle)
+}

@@ -22,6 +22,7 @@
 
 #include <string>
 
+#include "scene.h"
 #include "yh_internal.h"
 
 using namespace yh;
@@ -273,28 +274,6 @@ thread_local std::string g_scene_create_error;
 
 }  // namespace
 
-struct yh_scene {
-    int dev = 0, W = 0, H = 0, band_h = 64;
-    hipStream_t stream = nullptr;
-    hipEvent_t copied = nullptr;
-    std::string err;
-    uint16_t* depth = nullptr;
-    uint8_t* cls_id = nullptr;
-    uint32_t* frame = nullptr;
-    uint32_t* map = nullptr;
-    float4 *world = nullptr, *conn0 = nullptr, *conn1 = nullptr, *balls = nullptr;
-    long long* ball_acc = nullptr;
-    uint32_t *terrain_tab = nullptr, *robot_tab = nullptr;
-    bool ran = false;
-    // what the last append ran on (yh_scene_time replays exactly this)
-    const uint8_t* last_cls = nullptr;
-    const uint32_t* last_frame = nullptr;
-    int last_frame_mode = 0, last_mode = 0;
-    int fail(int code, const std::string& m) { err = m; return code; }
-};
-
-#define SCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (h)->fail(YH_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
 namespace {
 int run_scene(yh_scene* h, const uint16_t* depth_dev, const uint8_t* cls_dev, const uint32_t* frame_dev, int frame_mode, int mode) {
     SceneParams p;
@@ -382,6 +361,7 @@ void yh_scene_destroy(yh_scene* h) {
     if (!h) return;
     hipSetDevice(h->dev);
     if (h->stream) hipStreamSynchronize(h->stream);
+    scene_path_free(h);
     void* bufs[] = { h->depth, h->cls_id, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);
     if (h->copied) hipEventDestroy(h->copied);
@@ -398,6 +378,7 @@ int yh_scene_append(yh_scene* h, const uint16_t* depth_host, const uint8_t* clas
     SCHK(h, hipMemcpyAsync(h->cls_id, class_id_host, npx * 2, hipMemcpyHostToDevice, h->stream));
     const int rc = host_sources_done(h, depth_host, class_id_host);
     if (rc) return rc;
+    ++h->frames;
     return run_scene(h, h->depth, h->cls_id, nullptr, 0, mode);
 }
 
@@ -411,6 +392,7 @@ int yh_scene_append_classified(yh_scene* h, const uint16_t* depth_host, const ui
     if (!frame_on_device) { SCHK(h, hipMemcpyAsync(h->frame, frame, npx * 4, hipMemcpyHostToDevice, h->stream)); fdev = h->frame; }
     const int rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame);
     if (rc) return rc;
+    ++h->frames;
     return run_scene(h, h->depth, nullptr, fdev, mode == YH_COMPAT_STRICT ? 0 : 1, mode);
 }
 

@@ -1,0 +1,481 @@
+// scene_path.hip — modify_path (src/path.rs:25-120 of the reference) on the scene's device-resident fields: the multi-source cost
+// field from the balls over the 4-connected pixel grid, the successor field, and the route from the robot's pixel as the
+// (magnitude, rotation) pairs GetPath serialises (path.rs:17-21). What is computed is the definition frozen in DESIGN.md §11
+// "Path planner" and restated in tests/path_ref.py (the reference's function indexes 224 x 224 arrays by x + y * 480 and panics):
+//   d[t] = 0 at targets, elsewhere d[v] = min over neighbours u of fl(fl(d[u] + c(v,u)) + |h[v] - h[u]|), all f32, this association
+//   (path.rs:59's left-to-right sum; the unit builds with -ffp-contract=off and the sum has no product to contract anyway).
+// Every c >= 1 in SANE, so fl(d + w) > d while d < 2^24: the equations have ONE solution and any relaxation order reaches it bit
+// for bit - every value a relaxation ever writes is the cost of a real path evaluated in that association, values only decrease,
+// and the set of f32 values is finite. That is what lets the solver below be asynchronous and still be tested with array_equal.
+//
+// Launches of one plan (yh_scene_plan):
+//   path_weights   one lane per pixel: conn0 / conn1 / map -> one float4 per pixel (right length, right height step, down length,
+//                  down height step): the solver reads 16 B per pixel instead of 32 B of connections + the map, length and step
+//                  stay apart for the two roundings.
+//   path_fill      cost = +inf, path_targets: cost = 0. The host flags round 0's tiles: each target's own tile, and the tile across
+//                  every tile border the target lies on - a target's drop from +inf to 0 is a lowered border cell like any other,
+//                  and a neighbour whose border sees nothing but targets (a wall of targets along a tile border) would otherwise
+//                  never be flagged.
+//   path_round     x rounds. A workgroup owns a SP_TW x SP_TH tile of the cost field with a one-cell halo in LDS; a lane owns a
+//                  2 x 2 block of cells whose twelve edge terms sit in registers. It relaxes in place (chaotic relaxation: a lane
+//                  reads its eight outer neighbours from LDS, sweeps its four cells forwards and backwards in registers, stores
+//                  what got smaller) SP_INNER times between workgroup votes, until a vote finds nothing changed: the tile's local
+//                  fixed point for the halo it loaded. Cells that changed go back with atomicMin on the u32 view (non-negative f32
+//                  order as their bits). Only a tile whose halo may have changed runs: a tile that lowered a cell of its border
+//                  flags that neighbour for the NEXT round (two flag arrays, by round parity) and counts it once. No workgroup
+//                  ever waits for another one: a round is a launch, the host enqueues SP_BATCH of them and reads the batch's
+//                  counters back once (rounds past convergence find no flag and exit at once).
+//   path_next      one lane per pixel: the first neighbour in the order (left, right, up, down) whose candidate equals d[v] bitwise.
+//   path_walk      one wave: chases `next` from the start through a 32 x 32 window of it held in LDS (reloaded when the route leaves
+//                  it: ~1 global round trip per >= 16 steps instead of one per step), then its 64 lanes write the directions.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "scene.h"
+#include "yh_internal.h"
+
+using namespace yh;
+
+#ifndef SP_TW
+#define SP_TW 32   // tile width and height (even). Measured alternatives: DESIGN.md §11
+#endif
+#ifndef SP_TH
+#define SP_TH 32
+#endif
+#ifndef SP_INNER
+#define SP_INNER 4   // sweeps between two workgroup votes
+#endif
+#ifndef SP_BATCH
+#define SP_BATCH 16   // rounds enqueued per host read of the counters
+#endif
+#define SP_NT ((SP_TW / 2) * (SP_TH / 2))
+#define SP_P (SP_TW + 2)
+#define SP_WS 32   // path_walk's window
+#define SP_INF __uint_as_float(0x7f800000u)
+
+static_assert(SP_TW % 2 == 0 && SP_TH % 2 == 0 && SP_NT % 64 == 0 && SP_NT <= 1024, "tile: whole waves of 2 x 2 blocks");
+
+struct yh_scene_path {
+    float* cost = nullptr;       // [H][W]
+    int32_t* next = nullptr;     // [H][W]
+    float4* edge = nullptr;      // [H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
+    uint32_t* flags = nullptr;   // [2][ntiles]
+    uint32_t* cnt = nullptr;     // [SP_BATCH + 1]: cnt[j + 1] = tiles flagged by round j of the batch
+    int32_t* targets = nullptr;  // [targets_cap] linear indices
+    int32_t targets_cap = 0;
+    int2* nodes = nullptr;       // [W * H] the route
+    float2* dirs = nullptr;      // [W * H]
+    int32_t* walk_out = nullptr; // [2]: length, status
+    uint32_t* host = nullptr;    // pinned: SP_BATCH + 1 counters, then walk_out
+    int tx = 0, ty = 0;
+    // the last plan
+    bool planned = false;
+    uint64_t frame = 0;
+    std::vector<int32_t> last_targets;
+    std::vector<uint32_t> flags0;   // round 0's tile flags, built on the host
+    int32_t start = 0, path_len = 0;
+    long long rounds = 0, tile_runs = 0;
+};
+
+namespace {
+
+struct PathParams {
+    int W, H, tx, ntiles;
+    const uint32_t* map;
+    const float4 *conn0, *conn1;
+    float4* edge;
+    float* cost;
+    int32_t* next;
+    uint32_t* flags;
+};
+
+__device__ __forceinline__ float cand(float dn, float len, float dh) { return __fadd_rn(__fadd_rn(dn, len), dh); }
+
+__global__ __launch_bounds__(256) void path_weights(const PathParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.W * p.H) return;
+    const int x = i % p.W, y = i / p.W;
+    const float h = (float)p.map[i];
+    const float hr = x + 1 < p.W ? fabsf(__fsub_rn(h, (float)p.map[i + 1])) : 0.0f;
+    const float hd = y + 1 < p.H ? fabsf(__fsub_rn(h, (float)p.map[i + p.W])) : 0.0f;
+    p.edge[i] = make_float4(x + 1 < p.W ? p.conn0[i].z : -1.0f, hr, y + 1 < p.H ? p.conn1[i].x : -1.0f, hd);
+}
+
+__global__ __launch_bounds__(256) void path_fill(const PathParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < p.W * p.H) p.cost[i] = SP_INF;
+    if (i < 2 * p.ntiles) p.flags[i] = 0u;
+}
+
+__global__ __launch_bounds__(256) void path_targets(const PathParams p, const int32_t* targets, int n) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    p.cost[targets[k]] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void path_mark_targets(const PathParams p, const int32_t* targets, int n) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) p.next[targets[k]] = -1;
+}
+
+__global__ __launch_bounds__(SP_NT) void path_round(const PathParams p, int parity, uint32_t* cnt_next) {
+    __shared__ float dl[(SP_TH + 2) * SP_P];
+    __shared__ uint32_t active, border;
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.y * p.tx + blockIdx.x;
+    uint32_t* mine = p.flags + parity * p.ntiles;
+    uint32_t* theirs = p.flags + (parity ^ 1) * p.ntiles;
+    if (tid == 0) { active = mine[tile]; border = 0u; }
+    __syncthreads();
+    if (!active) return;   // (workgroup-uniform)
+    if (tid == 0) mine[tile] = 0u;   // this array is next read two rounds on; nobody sets it during this round
+    const int x0 = blockIdx.x * SP_TW, y0 = blockIdx.y * SP_TH;
+    for (int i = tid; i < (SP_TH + 2) * SP_P; i += SP_NT) {
+        const int ly = i / SP_P, lx = i - ly * SP_P;
+        const int gx = x0 + lx - 1, gy = y0 + ly - 1;
+        dl[i] = gx >= 0 && gx < p.W && gy >= 0 && gy < p.H ? p.cost[(size_t)gy * p.W + gx] : SP_INF;
+    }
+    // this lane's 2 x 2 block: a b / c d. Edge terms: (length, |dh|); an edge with an end off the frame (by the frame's geometry,
+    // whatever the fields say) has length +inf: such a candidate is never smaller, a cell off the frame (ragged tiles) keeps its
+    // +inf and is never stored
+    const int cx = 2 * (tid % (SP_TW / 2)), cy = 2 * (tid / (SP_TW / 2));
+    const int gx = x0 + cx, gy = y0 + cy;
+    const bool in_a = gx < p.W && gy < p.H, in_b = gx + 1 < p.W && gy < p.H, in_c = gx < p.W && gy + 1 < p.H, in_d = gx + 1 < p.W && gy + 1 < p.H;
+    const bool has_l = gx > 0, has_r = gx + 2 < p.W, has_u = gy > 0, has_d = gy + 2 < p.H;
+    const float4 none = make_float4(-1.0f, 0.0f, -1.0f, 0.0f);
+    const size_t ga = (size_t)gy * p.W + gx;
+    const float4 ea = in_a ? p.edge[ga] : none, eb = in_b ? p.edge[ga + 1] : none;
+    const float4 ec = in_c ? p.edge[ga + p.W] : none, ed = in_d ? p.edge[ga + p.W + 1] : none;
+    const float4 ela = has_l && in_a ? p.edge[ga - 1] : none, elc = has_l && in_c ? p.edge[ga + p.W - 1] : none;
+    const float4 eua = has_u && in_a ? p.edge[ga - p.W] : none, eub = has_u && in_b ? p.edge[ga - p.W + 1] : none;
+#define SP_LEN(ok, v) ((ok) && (v) >= 0.0f ? (v) : SP_INF)
+    const float l_ab = SP_LEN(in_a && in_b, ea.x), h_ab = ea.y, l_cd = SP_LEN(in_c && in_d, ec.x), h_cd = ec.y;   // inside the block
+    const float l_ac = SP_LEN(in_a && in_c, ea.z), h_ac = ea.w, l_bd = SP_LEN(in_b && in_d, eb.z), h_bd = eb.w;
+    const float l_la = SP_LEN(has_l && in_a, ela.x), h_la = ela.y, l_lc = SP_LEN(has_l && in_c, elc.x), h_lc = elc.y;   // to the left of a, c
+    const float l_rb = SP_LEN(has_r && in_b, eb.x), h_rb = eb.y, l_rd = SP_LEN(has_r && in_d, ed.x), h_rd = ed.y;       // to the right of b, d
+    const float l_ua = SP_LEN(has_u && in_a, eua.z), h_ua = eua.w, l_ub = SP_LEN(has_u && in_b, eub.z), h_ub = eub.w;   // above a, b
+    const float l_dc = SP_LEN(has_d && in_c, ec.z), h_dc = ec.w, l_dd = SP_LEN(has_d && in_d, ed.z), h_dd = ed.w;       // below c, d
+#undef SP_LEN
+    const int ia = (cy + 1) * SP_P + cx + 1, ib = ia + 1, ic = ia + SP_P, id = ic + 1;
+    __syncthreads();
+    // other lanes store between two of this lane's reads: relaxed workgroup-scope atomics, so that every read is a read (and stays a
+    // ds_read: a volatile access would go through the flat path)
+#define SP_LD(i) __hip_atomic_load(&dl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define SP_ST(i, v) __hip_atomic_store(&dl[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+    float va = SP_LD(ia), vb = SP_LD(ib), vc = SP_LD(ic), vd = SP_LD(id);
+    const float oa = va, ob = vb, oc = vc, od = vd;
+    int any;
+    do {
+        int ch = 0;
+#pragma unroll
+        for (int k = 0; k < SP_INNER; ++k) {
+            const float na_l = SP_LD(ia - 1), nc_l = SP_LD(ic - 1), nb_r = SP_LD(ib + 1), nd_r = SP_LD(id + 1);
+            const float na_u = SP_LD(ia - SP_P), nb_u = SP_LD(ib - SP_P), nc_d = SP_LD(ic + SP_P), nd_d = SP_LD(id + SP_P);
+            float a = fminf(va, fminf(cand(na_l, l_la, h_la), cand(na_u, l_ua, h_ua)));
+            float b = fminf(vb, fminf(cand(nb_r, l_rb, h_rb), cand(nb_u, l_ub, h_ub)));
+            float c = fminf(vc, fminf(cand(nc_l, l_lc, h_lc), cand(nc_d, l_dc, h_dc)));
+            float d = fminf(vd, fminf(cand(nd_r, l_rd, h_rd), cand(nd_d, l_dd, h_dd)));
+            a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));       // forwards a, b, c, d
+            b = fminf(b, fminf(cand(a, l_ab, h_ab), cand(d, l_bd, h_bd)));
+            c = fminf(c, fminf(cand(a, l_ac, h_ac), cand(d, l_cd, h_cd)));
+            d = fminf(d, fminf(cand(b, l_bd, h_bd), cand(c, l_cd, h_cd)));
+            c = fminf(c, cand(d, l_cd, h_cd));                                   // and back
+            b = fminf(b, cand(d, l_bd, h_bd));
+            a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));
+            if (a < va) { SP_ST(ia, a); va = a; ch = 1; }
+            if (b < vb) { SP_ST(ib, b); vb = b; ch = 1; }
+            if (c < vc) { SP_ST(ic, c); vc = c; ch = 1; }
+            if (d < vd) { SP_ST(id, d); vd = d; ch = 1; }
+        }
+        any = __syncthreads_or(ch);
+    } while (any);
+#undef SP_LD
+#undef SP_ST
+    // back to the field, and which borders moved
+    uint32_t* cu = reinterpret_cast<uint32_t*>(p.cost);
+    const bool ca = va < oa, cb = vb < ob, cc = vc < oc, cd = vd < od;
+    if (ca && in_a) atomicMin(cu + ga, __float_as_uint(va));
+    if (cb && in_b) atomicMin(cu + ga + 1, __float_as_uint(vb));
+    if (cc && in_c) atomicMin(cu + ga + p.W, __float_as_uint(vc));
+    if (cd && in_d) atomicMin(cu + ga + p.W + 1, __float_as_uint(vd));
+    uint32_t m = 0u;
+    if (cx == 0 && (ca || cc)) m |= 1u;
+    if (cx == SP_TW - 2 && (cb || cd)) m |= 2u;
+    if (cy == 0 && (ca || cb)) m |= 4u;
+    if (cy == SP_TH - 2 && (cc || cd)) m |= 8u;
+    if (m) atomicOr(&border, m);
+    __syncthreads();
+    if (tid < 4 && ((border >> tid) & 1u)) {
+        const int bx = (int)blockIdx.x + (tid == 0 ? -1 : tid == 1 ? 1 : 0), by = (int)blockIdx.y + (tid == 2 ? -1 : tid == 3 ? 1 : 0);
+        if (bx >= 0 && bx < p.tx && by >= 0 && by < (int)gridDim.y && atomicExch(theirs + by * p.tx + bx, 1u) == 0u) atomicAdd(cnt_next, 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void path_next(const PathParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.W * p.H) return;
+    const int x = i % p.W, y = i / p.W;
+    const uint32_t dv = __float_as_uint(p.cost[i]);
+    const float4 e = p.edge[i];
+    int nx = -1;
+    // (in reverse, so that the first of the order left, right, up, down wins)
+    if (y + 1 < p.H && __float_as_uint(cand(p.cost[i + p.W], e.z, e.w)) == dv) nx = i + p.W;
+    if (y > 0) { const float4 u = p.edge[i - p.W]; if (__float_as_uint(cand(p.cost[i - p.W], u.z, u.w)) == dv) nx = i - p.W; }
+    if (x + 1 < p.W && __float_as_uint(cand(p.cost[i + 1], e.x, e.y)) == dv) nx = i + 1;
+    if (x > 0) { const float4 l = p.edge[i - 1]; if (__float_as_uint(cand(p.cost[i - 1], l.x, l.y)) == dv) nx = i - 1; }
+    p.next[i] = nx;
+}
+
+// out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk did not end within W * H nodes (costs
+// strictly decrease along `next`, so this cannot happen on SANE fields; the bound is what keeps the loop finite on any input)
+__global__ __launch_bounds__(64) void path_walk(const PathParams p, int start, int2* nodes, float2* dirs, int32_t* out) {
+    __shared__ int win[SP_WS * SP_WS];
+    const int lane = threadIdx.x, npx = p.W * p.H;
+    int cx = start % p.W, cy = start / p.W, n = 0;
+    bool done = false, lost = false;
+    while (!done && !lost) {   // (wave-uniform)
+        const int wx0 = max(0, min(cx - SP_WS / 2, p.W - SP_WS)), wy0 = max(0, min(cy - SP_WS / 2, p.H - SP_WS));
+        for (int i = lane; i < SP_WS * SP_WS; i += 64) {
+            const int gx = wx0 + i % SP_WS, gy = wy0 + i / SP_WS;
+            win[i] = gx < p.W && gy < p.H ? p.next[(size_t)gy * p.W + gx] : -1;
+        }
+        __syncthreads();
+        while (true) {
+            if (n >= npx) { lost = true; break; }
+            if (lane == 0) nodes[n] = make_int2(cx, cy);
+            ++n;
+            const int nx = win[(cy - wy0) * SP_WS + (cx - wx0)];
+            if (nx < 0) { done = true; break; }
+            cx = nx % p.W; cy = nx / p.W;
+            if (cx < wx0 || cx >= wx0 + SP_WS || cy < wy0 || cy >= wy0 + SP_WS) break;
+        }
+        __syncthreads();
+    }
+    __threadfence();
+    __syncthreads();
+    // directions[i] = (d[n_i] - d[n_i+1], rot_i): rot_0 = 0, else the angle at n_i between n_i-1 and n_i+1 - on a 4-grid without
+    // backtracking pi when straight, pi / 2 for a turn (the two constants, not a device acosf)
+    for (int i = lane; i + 1 < n; i += 64) {
+        const int2 a = nodes[i], b = nodes[i + 1];
+        const float mag = __fsub_rn(p.cost[(size_t)a.y * p.W + a.x], p.cost[(size_t)b.y * p.W + b.x]);
+        float rot = 0.0f;
+        if (i > 0) {
+            const int2 z = nodes[i - 1];
+            rot = (z.x + b.x == 2 * a.x && z.y + b.y == 2 * a.y) ? 3.14159274f : 1.57079637f;
+        }
+        dirs[i] = make_float2(mag, rot);
+    }
+    if (lane == 0) { out[0] = n; out[1] = lost ? 1 : 0; }
+}
+
+int ensure_buffers(yh_scene* h) {
+    yh_scene_path* q = h->path;
+    const size_t npx = (size_t)h->W * h->H;
+    q->tx = (h->W + SP_TW - 1) / SP_TW; q->ty = (h->H + SP_TH - 1) / SP_TH;
+    SCHK(h, hipMalloc((void**)&q->cost, npx * 4));
+    SCHK(h, hipMalloc((void**)&q->next, npx * 4));
+    SCHK(h, hipMalloc((void**)&q->edge, npx * 16));
+    SCHK(h, hipMalloc((void**)&q->flags, (size_t)2 * q->tx * q->ty * 4));
+    SCHK(h, hipMalloc((void**)&q->cnt, (SP_BATCH + 1) * 4));
+    SCHK(h, hipMalloc((void**)&q->nodes, npx * sizeof(int2)));
+    SCHK(h, hipMalloc((void**)&q->dirs, npx * sizeof(float2)));
+    SCHK(h, hipMalloc((void**)&q->walk_out, 2 * 4));
+    SCHK(h, hipHostMalloc((void**)&q->host, (SP_BATCH + 3) * 4, hipHostMallocDefault));
+    return YH_OK;
+}
+
+// the whole plan on the handle's stream; returns when the route's length is known (the batches' counter reads are host waits anyway)
+int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
+    yh_scene_path* q = h->path;
+    const int n = (int)targets.size();
+    if (n > q->targets_cap) {
+        if (q->targets) { SCHK(h, hipStreamSynchronize(h->stream)); SCHK(h, hipFree(q->targets)); q->targets = nullptr; q->targets_cap = 0; }
+        SCHK(h, hipMalloc((void**)&q->targets, (size_t)n * 4));
+        q->targets_cap = n;
+    }
+    PathParams p;
+    p.W = h->W; p.H = h->H; p.tx = q->tx; p.ntiles = q->tx * q->ty;
+    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
+    const int npx = h->W * h->H;
+    const dim3 px((unsigned)((std::max(npx, 2 * p.ntiles) + 255) / 256)), tg((unsigned)((n + 255) / 256)), tiles((unsigned)q->tx, (unsigned)q->ty);
+    SCHK(h, hipMemcpyAsync(q->targets, targets.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(path_weights, px, dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(path_fill, px, dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(path_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
+    // round 0's work list (flag array 0): the rule path_round applies to every later decrease - a lowered cell on a tile's border
+    // flags the tile across that border - applied to the targets' drop from +inf to 0, plus the targets' own tiles
+    q->flags0.assign((size_t)p.ntiles, 0u);
+    long long active = 0;
+    auto flag = [&](int bx, int by) {
+        if (bx < 0 || bx >= q->tx || by < 0 || by >= q->ty) return;
+        uint32_t& f = q->flags0[(size_t)by * q->tx + bx];
+        if (!f) { f = 1u; ++active; }
+    };
+    for (int t : targets) {
+        const int x = t % h->W, y = t / h->W, bx = x / SP_TW, by = y / SP_TH;
+        flag(bx, by);
+        if (x % SP_TW == 0) flag(bx - 1, by);
+        if (x % SP_TW == SP_TW - 1) flag(bx + 1, by);
+        if (y % SP_TH == 0) flag(bx, by - 1);
+        if (y % SP_TH == SP_TH - 1) flag(bx, by + 1);
+    }
+    SCHK(h, hipMemcpyAsync(q->flags, q->flags0.data(), (size_t)p.ntiles * 4, hipMemcpyHostToDevice, h->stream));
+    q->rounds = 0; q->tile_runs = 0;
+    const long long cap = (long long)npx;   // costs only decrease over a finite set: this never fires
+    long long round = 0;
+    while (active) {
+        if (round >= cap) return h->fail(YH_EHIP, "path solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
+        SCHK(h, hipMemsetAsync(q->cnt, 0, (SP_BATCH + 1) * 4, h->stream));
+        for (int j = 0; j < SP_BATCH; ++j, ++round)
+            hipLaunchKernelGGL(path_round, tiles, dim3(SP_NT), 0, h->stream, p, (int)(round & 1), q->cnt + j + 1);
+        SCHK(h, hipGetLastError());
+        SCHK(h, hipMemcpyAsync(q->host, q->cnt, (SP_BATCH + 1) * 4, hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        q->host[0] = (uint32_t)active;   // tiles that ran in round j of the batch: host[j]
+        for (int j = 0; j < SP_BATCH; ++j) if (q->host[j]) { ++q->rounds; q->tile_runs += q->host[j]; }
+        active = q->host[SP_BATCH];
+    }
+    hipLaunchKernelGGL(path_next, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(path_mark_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
+    hipLaunchKernelGGL(path_walk, dim3(1), dim3(64), 0, h->stream, p, (int)start, q->nodes, q->dirs, q->walk_out);
+    SCHK(h, hipGetLastError());
+    int32_t* wo = reinterpret_cast<int32_t*>(q->host + SP_BATCH + 1);
+    SCHK(h, hipMemcpyAsync(wo, q->walk_out, 2 * 4, hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    if (wo[1]) return h->fail(YH_EHIP, "path walk: no target within W*H steps (fields not those of a SANE frame?)");
+    q->path_len = wo[0];
+    return YH_OK;
+}
+
+}  // namespace
+
+namespace yh {
+void scene_path_free(yh_scene* h) {
+    yh_scene_path* q = h->path;
+    if (!q) return;
+    void* bufs[] = { q->cost, q->next, q->edge, q->flags, q->cnt, q->targets, q->nodes, q->dirs, q->walk_out };
+    for (void* b : bufs) if (b) hipFree(b);
+    if (q->host) hipHostFree(q->host);
+    delete q;
+    h->path = nullptr;
+}
+}  // namespace yh
+
+extern "C" {
+
+int yh_scene_plan(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y) {
+    if (!h) return YH_EINVAL;
+    if (n_targets < 1) return h->fail(YH_EINVAL, "n_targets < 1");
+    if (!h->ran) return h->fail(YH_ESTATE, "no frame has been appended");
+    if (h->last_mode != YH_COMPAT_SANE)
+        return h->fail(YH_ESTATE, "the last frame was appended in YH_COMPAT_STRICT: its connections are all distances to world(0,0) "
+                                  "(pt_cloud_weights.comp:32), no planner is defined on them; append in YH_COMPAT_SANE");
+    const long long W = h->W, H = h->H;
+    if ((W + H) * (2 * std::max(H, 101LL) + 1) >= (1LL << 24))
+        return h->fail(YH_EINVAL, "frame too large for the planner: (W + H) * (2 * max(H, 101) + 1) must stay below 2^24 (f32 costs stay exact steps apart)");
+    if (start_x < 0 || start_x >= W || start_y < 0 || start_y >= H) return h->fail(YH_EINVAL, "start outside the frame");
+    SCHK(h, hipSetDevice(h->dev));
+    std::vector<int32_t> targets;
+    if (targets_xy) {
+        for (int k = 0; k < n_targets; ++k) {
+            const int x = targets_xy[2 * k], y = targets_xy[2 * k + 1];
+            if (x < 0 || x >= W || y < 0 || y >= H) return h->fail(YH_EINVAL, "target " + std::to_string(k) + " outside the frame");
+            targets.push_back((int32_t)(y * W + x));
+        }
+    } else {
+        // balls[..3] (path.rs:37), means truncated as `as i32` does (scene.rs:321); here: the first n_targets balls that have pixels
+        float balls[100][4];
+        SCHK(h, hipMemcpyAsync(balls, h->balls, sizeof(balls), hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        int taken = 0;
+        for (int k = 0; k < 100 && taken < n_targets; ++k) {
+            if (!(balls[k][2] > 0.0f)) continue;
+            ++taken;
+            const int x = (int)balls[k][0], y = (int)balls[k][1];
+            if (x >= 0 && x < W && y >= 0 && y < H) targets.push_back((int32_t)(y * W + x));
+        }
+        if (targets.empty()) return h->fail(YH_ESTATE, "no target given and the frame has no ball inside it");
+    }
+    int rc = YH_OK;
+    if (!h->path) {   // the planner's buffers are allocated at the first plan: a handle that never plans pays nothing
+        h->path = new yh_scene_path();
+        rc = ensure_buffers(h);
+        if (rc) { scene_path_free(h); return rc; }
+    }
+    h->path->planned = false;
+    rc = run_plan(h, targets, (int32_t)(start_y * W + start_x));
+    if (rc) return rc;
+    h->path->planned = true; h->path->frame = h->frames; h->path->last_targets = targets; h->path->start = (int32_t)(start_y * W + start_x);
+    return YH_OK;
+}
+
+int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy, float* directions, int32_t path_capacity, int32_t* path_len) {
+    if (!h) return YH_EINVAL;
+    yh_scene_path* q = h->path;
+    if (!q || !q->planned) return h->fail(YH_ESTATE, "no plan has been made");
+    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the plan: plan again");
+    if (path_len) *path_len = q->path_len;
+    if ((path_xy || directions) && path_capacity < q->path_len)
+        return h->fail(YH_EOVERFLOW, "path_capacity " + std::to_string(path_capacity) + " < the route's " + std::to_string(q->path_len) + " nodes");
+    SCHK(h, hipSetDevice(h->dev));
+    const size_t npx = (size_t)h->W * h->H;
+    if (cost) SCHK(h, hipMemcpyAsync(cost, q->cost, npx * 4, hipMemcpyDeviceToHost, h->stream));
+    if (next) SCHK(h, hipMemcpyAsync(next, q->next, npx * 4, hipMemcpyDeviceToHost, h->stream));
+    if (path_xy) SCHK(h, hipMemcpyAsync(path_xy, q->nodes, (size_t)q->path_len * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
+    if (directions && q->path_len > 1) SCHK(h, hipMemcpyAsync(directions, q->dirs, (size_t)(q->path_len - 1) * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return YH_OK;
+}
+
+int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, const float* conn1) {
+    if (!h || !map || !conn0 || !conn1) return YH_EINVAL;
+    // what the planner assumes of SANE fields and the frozen definition reads from the other end: every in-frame length >= 1
+    // (a finite number), left == the left neighbour's right, up == the upper neighbour's down
+    for (int y = 0; y < h->H; ++y)
+        for (int x = 0; x < h->W; ++x) {
+            const size_t i = (size_t)y * h->W + x;
+            const bool okr = x + 1 >= h->W || (conn0[4 * i + 2] >= 1.0f && conn0[4 * i + 2] < 3.0e38f && conn0[4 * i + 2] == conn1[4 * (i + 1) + 2]);
+            const bool okd = y + 1 >= h->H || (conn1[4 * i] >= 1.0f && conn1[4 * i] < 3.0e38f && conn1[4 * i] == conn0[4 * (i + h->W)]);
+            if (!okr || !okd)
+                return h->fail(YH_EINVAL, "fields are not those of a SANE frame at pixel (" + std::to_string(x) + ", " + std::to_string(y) + "): the " +
+                                              (okr ? "down" : "right") + " length must be a finite number >= 1 and equal the neighbour's entry for the same edge");
+        }
+    SCHK(h, hipSetDevice(h->dev));
+    const size_t npx = (size_t)h->W * h->H;
+    SCHK(h, hipMemcpyAsync(h->map, map, npx * 4, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipMemcpyAsync(h->conn0, conn0, npx * 16, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipMemcpyAsync(h->conn1, conn1, npx * 16, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipMemsetAsync(h->world, 0, npx * 16, h->stream));
+    SCHK(h, hipMemsetAsync(h->balls, 0, 100 * 16, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    h->ran = true; h->last_mode = YH_COMPAT_SANE; h->last_cls = h->cls_id; h->last_frame = nullptr; h->last_frame_mode = 0;
+    ++h->frames;
+    return YH_OK;
+}
+
+int yh_scene_plan_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs) {
+    if (!h || reps < 1 || !ms_per_plan) return YH_EINVAL;
+    yh_scene_path* q = h->path;
+    if (!q || !q->planned) return h->fail(YH_ESTATE, "no plan has been made");
+    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the plan: plan again");
+    SCHK(h, hipSetDevice(h->dev));
+    hipEvent_t a, b;
+    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
+    SCHK(h, hipEventRecord(a, h->stream));
+    for (int r = 0; r < reps; ++r) { const int rc = run_plan(h, q->last_targets, q->start); if (rc) { hipEventDestroy(a); hipEventDestroy(b); return rc; } }
+    SCHK(h, hipEventRecord(b, h->stream));
+    SCHK(h, hipEventSynchronize(b));
+    float ms = 0;
+    hipEventElapsedTime(&ms, a, b);
+    hipEventDestroy(a); hipEventDestroy(b);
+    *ms_per_plan = ms / reps;   // (the host's waits for the batches' counters are inside: what a caller of yh_scene_plan waits for)
+    if (rounds) *rounds = (int32_t)q->rounds;
+    if (tile_runs) *tile_runs = (int32_t)q->tile_runs;
+    return YH_OK;
+}
+
+}  // extern "C"

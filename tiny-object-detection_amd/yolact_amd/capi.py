@@ -147,6 +147,10 @@ SYMBOLS = [
     ("yh_scene_append_classified", _i, [_vp, _vp, _vp, _i, _i]),
     ("yh_scene_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_time", _i, [_vp, _i, C.POINTER(_f)]),
+    ("yh_scene_plan", _i, [_vp, _vp, _i, _i, _i]),
+    ("yh_scene_plan_read", _i, [_vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_set_fields", _i, [_vp, _vp, _vp, _vp]),
+    ("yh_scene_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
@@ -759,6 +763,54 @@ class Scene:
         ms = C.c_float()
         self._chk(self.L.yh_scene_time(self.h, reps, C.byref(ms)))
         return ms.value
+
+    def plan(self, targets=None, n_targets=3, start=None):
+        """modify_path (src/path.rs:25-120) on the last appended frame. targets: (x, y) pixels, or None: the first n_targets balls
+        (balls[..3], path.rs:37). start: the robot's pixel (x, y); None: the reference's START_NODE, (400, 479), at 640x480 only."""
+        if start is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
+            start = (400, 479)
+        if targets is None:
+            self._chk(self.L.yh_scene_plan(self.h, None, n_targets, start[0], start[1]))
+        else:
+            t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+            self._chk(self.L.yh_scene_plan(self.h, _p(t), len(t), start[0], start[1]))
+
+    def read_plan(self, fields=True):
+        """The last plan: path int32 [L][2] (x, y) from the start to a target, directions f32 [L - 1][2] (magnitude, rotation), and
+        with fields=True cost f32 [H][W] and next int32 [H][W] (linear index of the successor, -1 at targets)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_scene_plan_read(self.h, None, None, None, None, 0, C.byref(n)))
+        out = dict(path=np.zeros((n.value, 2), np.int32))
+        dirs = np.zeros((n.value, 2), np.float32)
+        if fields:
+            out["cost"] = np.zeros((self.H, self.W), np.float32)
+            out["next"] = np.zeros((self.H, self.W), np.int32)
+        self._chk(self.L.yh_scene_plan_read(self.h, _p(out["cost"]) if fields else None, _p(out["next"]) if fields else None,
+                                            _p(out["path"]), _p(dirs), n.value, C.byref(n)))
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        return out
+
+    def set_fields(self, map, conn0, conn1):
+        """Test hook: host fields as if a SANE frame had produced them (layouts of read())."""
+        m = np.ascontiguousarray(map, np.uint32)
+        c0, c1 = np.ascontiguousarray(conn0, np.float32), np.ascontiguousarray(conn1, np.float32)
+        assert m.shape == (self.H, self.W) and c0.shape == (self.H, self.W, 4) and c1.shape == (self.H, self.W, 4)
+        self._chk(self.L.yh_scene_set_fields(self.h, _p(m), _p(c0), _p(c1)))
+
+    def plan_time(self, reps=20):
+        """Replays the last plan: dict(ms_per_plan, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
+
+
+def serialize_path(directions, created_secs):
+    """Path::serialize (src/path.rs:17-21), byte for byte: `created` as big-endian u64 seconds since the epoch, then every
+    (magnitude, rotation) pair as two big-endian f32 - what the reference answers to GetPath (path.rs:167-169)."""
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 2)
+    return int(created_secs).to_bytes(8, "big") + d.astype(">f4").tobytes()
 
 
 def tfl_validate(model_bytes):

@@ -1,0 +1,44 @@
+"""The path planner (yh_scene_plan: modify_path on the scene's device-resident fields) at 640x480: milliseconds per plan, solver
+rounds and tile executions, for a camera-like frame (robots + balls, planned to its balls from the reference's START_NODE) and for
+the serpentine maze of tests/path_ref.py (a geodesic that crosses the frame 60 times). Per case: one warm-up plan, then `sets`
+repetitions of yh_scene_plan_time(reps) (device events around whole plans, the host's counter reads inside) and the host's own wall
+clock around Scene.plan(); the scene back-end's time per frame beside it.
+Usage: python tools/time_path.py [sets] [reps]"""
+import os, socket, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import yolact_amd as ya
+import path_ref as R
+sets = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+H, W = 480, 640
+print(f"box {socket.gethostname()}, {ya.version()}")
+sc = ya.Scene(W, H)
+
+
+def report(name, plan):
+    plan()                                                        # warm-up: buffers, code objects
+    out = sc.read_plan(fields=False)
+    runs = [sc.plan_time(reps) for _ in range(sets)]
+    wall = []
+    for _ in range(sets):
+        t0 = time.perf_counter(); plan(); wall.append((time.perf_counter() - t0) * 1e3)
+    ms = sorted(r["ms_per_plan"] for r in runs)
+    print(f"plan 640x480, {name}: {ms[len(ms) // 2]:.3f} ms per plan (median of {sets} x {reps}; min {ms[0]:.3f}, max {ms[-1]:.3f}), "
+          f"host wall per Scene.plan() {sorted(wall)[len(wall) // 2]:.3f} ms, {runs[0]['rounds']} rounds, {runs[0]['tile_runs']} tile runs, "
+          f"route of {len(out['path'])} nodes")
+
+
+rng = np.random.default_rng(0)
+depth = rng.integers(200, 4000, (H, W)).astype(np.uint16)
+ci = np.zeros((H, W, 2), np.uint8)
+ci[100:220, 150:330, 0] = 1; ci[260:330, 380:520, 0] = 2; ci[60:75, 60:80] = (3, 4); ci[400:420, 500:530] = (3, 9)
+sc.append(depth, ci, ya.COMPAT_SANE)
+print(f"scene 640x480, robots + balls: {sc.time(30):.3f} ms per frame")
+sc.append(depth, ci, ya.COMPAT_SANE)
+report("camera-like frame, 2 balls", lambda: sc.plan())
+hmap, start, target = R.serpentine(H, W)
+sc.set_fields(hmap, *R.sane_connections(hmap))
+report("serpentine maze, 1 target", lambda: sc.plan(targets=[target], start=start))
