@@ -368,6 +368,37 @@ int yh_scene_plan(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the 
  * appended since the plan. */
 int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy, float* directions,
                        int32_t path_capacity, int32_t* path_len);
+/* The tour: which target first, then which, and the whole route (DESIGN.md section 11 "Tour"; path.rs:38 "Dijkstra's algorithm
+ * with 3 targets", :35,:66 ball[node]). K <= YH_TOUR_MAX distinct targets, chosen as yh_scene_plan chooses them (explicit pixels,
+ * or NULL: the first n_targets balls; of those a ball outside the frame, or on an earlier ball's pixel, is dropped). Per target
+ * t_b the single-target cost field d_b and successor field next_b of yh_scene_plan (K fields solved in the same launches), the
+ * label of the nearest target per pixel, the leg matrix, the visiting order of least total cost (all K! orders, on the host from
+ * the leg matrix, f32 sums left to right, ties to the lexicographically smallest) and the legs' walks joined into one route.
+ * Synchronous. The tour's buffers are allocated at the first tour on a handle, sized by the K in use (they only grow), and are
+ * not the single plan's: yh_scene_plan and yh_scene_plan_tour do not disturb each other's results. Errors as yh_scene_plan, and
+ * YH_EINVAL for n_targets > YH_TOUR_MAX and for two equal explicit targets. A call refused with YH_EINVAL or YH_ESTATE has
+ * touched nothing: an earlier tour of the same frame stays readable. A call that fails later (YH_EHIP) leaves no tour. */
+#define YH_TOUR_MAX 6
+int yh_scene_plan_tour(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                       int32_t start_x, int32_t start_y);
+/* The last tour; any pointer may be NULL. With K = *n_targets (<= YH_TOUR_MAX; size the small arrays for YH_TOUR_MAX):
+ *   targets_xy i32 [K][2]   the targets in use, t_0 .. t_{K-1}
+ *   order      i32 [K]      the visiting order o: indices into targets_xy
+ *   legs       f32 [K+1][K] legs[0][b] = d_b[start], legs[1 + a][b] = d_b[t_a]: the cost to travel FROM t_a TO t_b (diagonal 0)
+ *   total      f32          the order's total, fl(..fl(legs[0][o_0] + legs[1 + o_0][o_1]) + ..)
+ *   cost       f32 [K][h][w], next i32 [K][h][w]   field b has the single target t_b (next_b is -1 at t_b only)
+ *   label      u8  [h][w]   the smallest b with d_b[v] == min over b of d_b[v]
+ *   path_xy    i32 [cap][2] the joined route: start .. t_{o_0} .. t_{o_1} .., a junction node once; a leg whose start is its own
+ *                           target adds no node. *path_len = its nodes
+ *   directions f32 [cap][2] (magnitude, rotation) per step, *path_len - 1 pairs: the magnitude of a step inside leg j is the
+ *                           difference of d_{o_j}; rotation 0 at step 0 and where the route reverses (at a junction only),
+ *                           float32(pi) when straight, float32(pi / 2) for a turn
+ *   leg_ends   i32 [K]      index in path_xy of the node where leg j ends (t_{o_j})
+ * YH_EOVERFLOW (and *path_len set, nothing copied) if path_capacity < *path_len while path_xy or directions is asked for;
+ * YH_ESTATE before a tour, or when a frame was appended since the tour. */
+int yh_scene_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs, float* total,
+                       float* cost, int32_t* next, uint8_t* label, int32_t* path_xy, float* directions, int32_t* leg_ends,
+                       int32_t path_capacity, int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

@@ -1,13 +1,16 @@
-// scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels) and scene_path.hip (the planner on its fields).
+// scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields) and
+// scene_tour.hip (the tour over several targets).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "yh_internal.h"
 
 struct yh_scene_path;   // the planner's buffers and last plan (scene_path.hip); allocated at the first yh_scene_plan
+struct yh_scene_tour;   // the tour's buffers and last tour (scene_tour.hip); allocated at the first yh_scene_plan_tour
 
 struct yh_scene {
     int dev = 0, W = 0, H = 0, band_h = 64;
@@ -28,6 +31,7 @@ struct yh_scene {
     int last_frame_mode = 0, last_mode = 0;
     uint64_t frames = 0;   // appends (and yh_scene_set_fields) so far: a plan belongs to the frame it was made on
     yh_scene_path* path = nullptr;
+    yh_scene_tour* tour = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
 };
 
@@ -35,4 +39,7 @@ struct yh_scene {
 
 namespace yh {
 void scene_path_free(yh_scene* h);   // yh_scene_destroy: the planner's buffers (the handle's device is current, its stream idle)
+void scene_tour_free(yh_scene* h);
+// yh_scene_plan's checks (frame, mode, size guard, start, targets) and its choice of targets, as linear indices; touches nothing
+int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets);
 }

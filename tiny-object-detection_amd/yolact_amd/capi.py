@@ -9,6 +9,7 @@ _LIB = None
 
 OK, EINVAL, EHIP, ENOMEM, EWEIGHTS, ESTATE, EDIVERGE, EOVERFLOW = 0, -1, -2, -3, -4, -5, -6, -7
 COMPAT_STRICT, COMPAT_SANE = 0, 1
+TOUR_MAX = 6   # YH_TOUR_MAX
 
 
 class YhError(RuntimeError):
@@ -151,6 +152,9 @@ SYMBOLS = [
     ("yh_scene_plan_read", _i, [_vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_set_fields", _i, [_vp, _vp, _vp, _vp]),
     ("yh_scene_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_plan_tour", _i, [_vp, _vp, _i, _i, _i]),
+    ("yh_scene_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
@@ -804,6 +808,46 @@ class Scene:
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def plan_tour(self, targets=None, n_targets=3, start=None):
+        """The tour (DESIGN.md §11 "Tour"): one cost field per target solved in the same launches, the visiting order of least
+        total cost and the joined route. targets, n_targets (at most TOUR_MAX, distinct) and start as plan()."""
+        if start is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
+            start = (400, 479)
+        if targets is None:
+            self._chk(self.L.yh_scene_plan_tour(self.h, None, n_targets, start[0], start[1]))
+        else:
+            t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+            self._chk(self.L.yh_scene_plan_tour(self.h, _p(t), len(t), start[0], start[1]))
+
+    def read_tour(self, fields=False):
+        """The last tour: targets int32 [K][2], order int32 [K] (indices into targets), legs f32 [K + 1][K] (row 0 from the start,
+        row 1 + a from target a; column b = to target b), total f32, path int32 [L][2], directions f32 [L - 1][2], leg_ends int32 [K]
+        (index in path where each leg ends); with fields=True also cost f32 [K][H][W], next int32 [K][H][W], label uint8 [H][W]."""
+        k, n, total = C.c_int32(), C.c_int32(), C.c_float()
+        self._chk(self.L.yh_scene_tour_read(self.h, C.byref(k), None, None, None, None, None, None, None, None, None, None, 0, C.byref(n)))
+        K = k.value
+        out = dict(targets=np.zeros((K, 2), np.int32), order=np.zeros(K, np.int32), legs=np.zeros((K + 1, K), np.float32),
+                   path=np.zeros((n.value, 2), np.int32), leg_ends=np.zeros(K, np.int32))
+        dirs = np.zeros((n.value, 2), np.float32)
+        if fields:
+            out["cost"] = np.zeros((K, self.H, self.W), np.float32)
+            out["next"] = np.zeros((K, self.H, self.W), np.int32)
+            out["label"] = np.zeros((self.H, self.W), np.uint8)
+        f = lambda name: _p(out[name]) if fields else None
+        self._chk(self.L.yh_scene_tour_read(self.h, C.byref(k), _p(out["targets"]), _p(out["order"]), _p(out["legs"]), C.byref(total),
+                                            f("cost"), f("next"), f("label"), _p(out["path"]), _p(dirs), _p(out["leg_ends"]), n.value, C.byref(n)))
+        out["total"] = np.float32(total.value)
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        return out
+
+    def tour_time(self, reps=20):
+        """Replays the last tour: dict(ms_per_tour, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_tour_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_tour=ms.value, rounds=r.value, tile_runs=t.value)
 
 
 def serialize_path(directions, created_secs):
