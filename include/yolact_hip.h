@@ -360,6 +360,17 @@ int yh_scene_read(yh_scene* h, uint32_t* map, float* world, float* conn0, float*
  * (YH_EHIP) leaves no plan. */
 int yh_scene_plan(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
                   int32_t start_x, int32_t start_y);
+/* yh_scene_plan on the 4- or the 8-connected pixel grid (DESIGN.md section 11 "Diagonals"); yh_scene_plan is this function
+ * with connectivity 4. With 8 the four diagonal lengths of the connections join the graph (up-left conn1[..][3], up-right
+ * conn0[..][1], down-left conn1[..][1], down-right conn0[..][3]; the same cost equation, the minimum over up to eight
+ * neighbours), the successor is the first neighbour in the order (left, right, up, down, up-left, up-right, down-left,
+ * down-right) that achieves the cost, and a rotation is float32((4 - k) * pi / 4) for k in 0 .. 4 steps of 45 degrees between
+ * the heading into a node and the heading out of it: pi, 3 pi / 4, pi / 2, pi / 4, 0. The plan remembers its connectivity
+ * (yh_scene_plan_time replays it). Errors as yh_scene_plan, and YH_EINVAL for a connectivity other than 4 or 8; YH_ESTATE for 8
+ * on fields uploaded through yh_scene_set_fields whose diagonal lengths are not all finite, >= 1 and equal at both ends
+ * (frames appended in YH_COMPAT_SANE always are). A refused call has touched nothing. */
+int yh_scene_plan_conn(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                       int32_t start_x, int32_t start_y, int32_t connectivity /* 4 or 8 */);
 /* The last plan (path.rs:93-119: the walk from START_NODE, Path.directions): cost f32 [h][w], next i32 [h][w] (linear index
  * y * w + x of the successor, -1 at targets), path_xy i32 [cap][2] (the route's pixels, start and target included),
  * directions f32 [cap][2] = (magnitude, rotation) per step of the route (*path_len - 1 pairs, what Path::serialize sends,
@@ -381,6 +392,11 @@ int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy
 #define YH_TOUR_MAX 6
 int yh_scene_plan_tour(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
                        int32_t start_x, int32_t start_y);
+/* yh_scene_plan_tour with every field, successor and rotation taken on the 4- or the 8-connected grid, as yh_scene_plan_conn
+ * defines them; labels, leg matrix, order and joining are unchanged. yh_scene_plan_tour is this function with connectivity 4.
+ * The tour remembers its connectivity (yh_scene_tour_time replays it). Errors as yh_scene_plan_tour and yh_scene_plan_conn. */
+int yh_scene_plan_tour_conn(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                            int32_t start_x, int32_t start_y, int32_t connectivity /* 4 or 8 */);
 /* The last tour; any pointer may be NULL. With K = *n_targets (<= YH_TOUR_MAX; size the small arrays for YH_TOUR_MAX):
  *   targets_xy i32 [K][2]   the targets in use, t_0 .. t_{K-1}
  *   order      i32 [K]      the visiting order o: indices into targets_xy
@@ -392,7 +408,7 @@ int yh_scene_plan_tour(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL:
  *                           target adds no node. *path_len = its nodes
  *   directions f32 [cap][2] (magnitude, rotation) per step, *path_len - 1 pairs: the magnitude of a step inside leg j is the
  *                           difference of d_{o_j}; rotation 0 at step 0 and where the route reverses (at a junction only),
- *                           float32(pi) when straight, float32(pi / 2) for a turn
+ *                           float32(pi) when straight, float32(pi / 2) for a turn (8-connected: also 3 pi / 4 and pi / 4)
  *   leg_ends   i32 [K]      index in path_xy of the node where leg j ends (t_{o_j})
  * YH_EOVERFLOW (and *path_len set, nothing copied) if path_capacity < *path_len while path_xy or directions is asked for;
  * YH_ESTATE before a tour, or when a frame was appended since the tour. */

@@ -112,12 +112,14 @@ int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame);
 /* Test hook: uploads host fields (height map u32 [h][w], connections0 / connections1 f32 [h][w][4], laid out as yh_scene_read
  * returns them) as if a YH_COMPAT_SANE frame had produced them, so that yh_scene_plan runs on constructed mazes. The planner reads
  * conn0[..][2] (right) and conn1[..][0] (down) and takes left / up from the neighbour, as SANE's symmetry allows: YH_EINVAL (nothing
- * uploaded) unless every in-frame right / down length is finite, >= 1 and equal to the neighbour's left / up entry. world and balls are zeroed; it counts as a new frame. A yh_scene_time after it replays the handle's own input buffers and
+ * uploaded) unless every in-frame right / down length is finite, >= 1 and equal to the neighbour's left / up entry. The diagonal entries
+ * (conn0[..][1], [3], conn1[..][1], [3]) are no reason to refuse: whether every in-frame one is finite, >= 1 and equal to the
+ * other end's entry is recorded, and an 8-connected plan or tour on fields that fail it returns YH_ESTATE. world and balls are zeroed; it counts as a new frame. A yh_scene_time after it replays the handle's own input buffers and
  * overwrites the fields. */
 int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, const float* conn1);
 /* Measurement hook: replays the last yh_scene_plan `reps` times: mean milliseconds per plan between two events on the handle's
  * stream (the host's reads of the solver's counters fall inside, as they do for a caller), the solver's rounds (launches in
- * which some tile ran) and tile executions of one plan. */
+ * which some tile ran) and tile executions of one plan. The replay has the plan's connectivity. */
 int yh_scene_plan_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs);
 /* The same for the last yh_scene_plan_tour (the host's choice of the order and the walks fall inside too): rounds = launches in
  * which some tile of some field ran, tile_runs summed over the fields. */

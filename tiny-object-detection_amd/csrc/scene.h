@@ -30,6 +30,10 @@ struct yh_scene {
     const uint32_t* last_frame = nullptr;
     int last_frame_mode = 0, last_mode = 0;
     uint64_t frames = 0;   // appends (and yh_scene_set_fields) so far: a plan belongs to the frame it was made on
+    // whether every in-frame diagonal length of the last frame is finite, >= 1 and equal to the other end's entry (what an
+    // 8-connected plan assumes): a SANE append makes them so, yh_scene_set_fields records what it was given
+    bool diag_ok = true;
+    std::string diag_why;
     yh_scene_path* path = nullptr;
     yh_scene_tour* tour = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
@@ -42,4 +46,6 @@ void scene_path_free(yh_scene* h);   // yh_scene_destroy: the planner's buffers 
 void scene_tour_free(yh_scene* h);
 // yh_scene_plan's checks (frame, mode, size guard, start, targets) and its choice of targets, as linear indices; touches nothing
 int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets);
+// what an 8-connected plan or tour asks of the last frame's diagonal lengths (YH_ESTATE and why if they fail it); touches nothing
+int scene_plan_diagonals(yh_scene* h);
 }

@@ -293,6 +293,7 @@ int run_scene(yh_scene* h, const uint16_t* depth_dev, const uint8_t* cls_dev, co
     SCHK(h, hipGetLastError());
     h->ran = true;
     h->last_cls = cls_dev; h->last_frame = frame_dev; h->last_frame_mode = frame_mode; h->last_mode = mode;
+    h->diag_ok = true; h->diag_why.clear();   // (a frame's own diagonals: both ends hold the same length, sqrt((1 + dy^2) + 1))
     return YH_OK;
 }
 

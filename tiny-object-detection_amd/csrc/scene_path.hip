@@ -30,6 +30,10 @@
 //                  it: ~1 global round trip per >= 16 steps instead of one per step), then its 64 lanes write the directions.
 // The tile relaxation, the successor rule and the chase are device functions of scene_path_dev.h: scene_tour.hip (yh_scene_plan_tour)
 // runs the same ones over K single-target fields.
+// yh_scene_plan_conn(.., 8) searches the 8-connected grid (DESIGN.md §11 "Diagonals"): path_weights<8> also writes the down-right and
+// down-left terms (a second float4 per pixel, allocated at the first such plan), path_round<8> relaxes over them and wakes the
+// diagonally adjacent tile when a corner cell drops, path_next<8> orders (left, right, up, down, up-left, up-right, down-left,
+// down-right), and the walk's rotations are pi, 3 pi / 4, pi / 2, pi / 4. The <4> forms are the code described above.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -47,6 +51,7 @@ struct yh_scene_path {
     float* cost = nullptr;       // [H][W]
     int32_t* next = nullptr;     // [H][W]
     float4* edge = nullptr;      // [H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
+    float4* edge2 = nullptr;     // [H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected plan
     uint32_t* flags = nullptr;   // [2][ntiles]
     uint32_t* cnt = nullptr;     // [SP_BATCH + 1]: cnt[j + 1] = tiles flagged by round j of the batch
     int32_t* targets = nullptr;  // [targets_cap] linear indices
@@ -61,12 +66,13 @@ struct yh_scene_path {
     uint64_t frame = 0;
     std::vector<int32_t> last_targets;
     std::vector<uint32_t> flags0;   // round 0's tile flags, built on the host
-    int32_t start = 0, path_len = 0;
+    int32_t start = 0, path_len = 0, conn = 4;
     long long rounds = 0, tile_runs = 0;
 };
 
 namespace {
 
+template <int CONN>
 __global__ __launch_bounds__(256) void path_weights(const PathParams p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= p.W * p.H) return;
@@ -74,7 +80,14 @@ __global__ __launch_bounds__(256) void path_weights(const PathParams p) {
     const float h = (float)p.map[i];
     const float hr = x + 1 < p.W ? fabsf(__fsub_rn(h, (float)p.map[i + 1])) : 0.0f;
     const float hd = y + 1 < p.H ? fabsf(__fsub_rn(h, (float)p.map[i + p.W])) : 0.0f;
-    p.edge[i] = make_float4(x + 1 < p.W ? p.conn0[i].z : -1.0f, hr, y + 1 < p.H ? p.conn1[i].x : -1.0f, hd);
+    const float4 c0 = p.conn0[i], c1 = p.conn1[i];
+    p.edge[i] = make_float4(x + 1 < p.W ? c0.z : -1.0f, hr, y + 1 < p.H ? c1.x : -1.0f, hd);
+    if constexpr (CONN == 8) {
+        const bool dr = x + 1 < p.W && y + 1 < p.H, dl = x > 0 && y + 1 < p.H;
+        const float hdr = dr ? fabsf(__fsub_rn(h, (float)p.map[i + p.W + 1])) : 0.0f;
+        const float hdl = dl ? fabsf(__fsub_rn(h, (float)p.map[i + p.W - 1])) : 0.0f;
+        p.edge2[i] = make_float4(dr ? c0.w : -1.0f, hdr, dl ? c1.y : -1.0f, hdl);
+    }
 }
 
 __global__ __launch_bounds__(256) void path_fill(const PathParams p) {
@@ -94,13 +107,15 @@ __global__ __launch_bounds__(256) void path_mark_targets(const PathParams p, con
     if (k < n) p.next[targets[k]] = -1;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(SP_NT) void path_round(const PathParams p, int parity, uint32_t* cnt_next) {
-    relax_tile(p, p.cost, p.flags + parity * p.ntiles, p.flags + (parity ^ 1) * p.ntiles, cnt_next);
+    relax_tile<CONN>(p, p.cost, p.flags + parity * p.ntiles, p.flags + (parity ^ 1) * p.ntiles, cnt_next);
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void path_next(const PathParams p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < p.W * p.H) p.next[i] = successor(p, p.cost, i);
+    if (i < p.W * p.H) p.next[i] = successor(around<CONN>(p, i), p.cost, i);
 }
 
 // out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk did not end within W * H nodes (costs
@@ -110,16 +125,11 @@ __global__ __launch_bounds__(64) void path_walk(const PathParams p, int start, i
     bool lost;
     const int n = chase(p.next, p.W, p.H, start, nodes, lost);
     // directions[i] = (d[n_i] - d[n_i+1], rot_i): rot_0 = 0, else the angle at n_i between n_i-1 and n_i+1 - on a 4-grid without
-    // backtracking pi when straight, pi / 2 for a turn (the two constants, not a device acosf)
+    // backtracking pi when straight, pi / 2 for a turn; with diagonals 3 pi / 4 and pi / 4 too (constants, not a device acosf)
     for (int i = lane; i + 1 < n; i += 64) {
         const int2 a = nodes[i], b = nodes[i + 1];
         const float mag = __fsub_rn(p.cost[(size_t)a.y * p.W + a.x], p.cost[(size_t)b.y * p.W + b.x]);
-        float rot = 0.0f;
-        if (i > 0) {
-            const int2 z = nodes[i - 1];
-            rot = (z.x + b.x == 2 * a.x && z.y + b.y == 2 * a.y) ? 3.14159274f : 1.57079637f;
-        }
-        dirs[i] = make_float2(mag, rot);
+        dirs[i] = make_float2(mag, i > 0 ? rotation(nodes[i - 1], a, b) : 0.0f);
     }
     if (lane == 0) { out[0] = n; out[1] = lost ? 1 : 0; }
 }
@@ -141,9 +151,10 @@ int ensure_buffers(yh_scene* h) {
 }
 
 // the whole plan on the handle's stream; returns when the route's length is known (the batches' counter reads are host waits anyway)
-int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
+int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, int conn) {
     yh_scene_path* q = h->path;
     const int n = (int)targets.size();
+    if (conn == 8 && !q->edge2) SCHK(h, hipMalloc((void**)&q->edge2, (size_t)h->W * h->H * 16));
     if (n > q->targets_cap) {
         if (q->targets) { SCHK(h, hipStreamSynchronize(h->stream)); SCHK(h, hipFree(q->targets)); q->targets = nullptr; q->targets_cap = 0; }
         SCHK(h, hipMalloc((void**)&q->targets, (size_t)n * 4));
@@ -151,15 +162,16 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
     }
     PathParams p;
     p.W = h->W; p.H = h->H; p.tx = q->tx; p.ntiles = q->tx * q->ty;
-    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
+    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.edge2 = conn == 8 ? q->edge2 : nullptr; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
     const int npx = h->W * h->H;
     const dim3 px((unsigned)((std::max(npx, 2 * p.ntiles) + 255) / 256)), tg((unsigned)((n + 255) / 256)), tiles((unsigned)q->tx, (unsigned)q->ty);
     SCHK(h, hipMemcpyAsync(q->targets, targets.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    path_weights_launch(p, h->stream);
+    path_weights_launch(p, conn, h->stream);
     hipLaunchKernelGGL(path_fill, px, dim3(256), 0, h->stream, p);
     hipLaunchKernelGGL(path_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
     // round 0's work list (flag array 0): the rule path_round applies to every later decrease - a lowered cell on a tile's border
-    // flags the tile across that border - applied to the targets' drop from +inf to 0, plus the targets' own tiles
+    // flags the tile across that border, and with diagonals a lowered corner cell the tile diagonally across - applied to the
+    // targets' drop from +inf to 0, plus the targets' own tiles
     q->flags0.assign((size_t)p.ntiles, 0u);
     long long active = 0;
     auto flag = [&](int bx, int by) {
@@ -167,14 +179,7 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
         uint32_t& f = q->flags0[(size_t)by * q->tx + bx];
         if (!f) { f = 1u; ++active; }
     };
-    for (int t : targets) {
-        const int x = t % h->W, y = t / h->W, bx = x / SP_TW, by = y / SP_TH;
-        flag(bx, by);
-        if (x % SP_TW == 0) flag(bx - 1, by);
-        if (x % SP_TW == SP_TW - 1) flag(bx + 1, by);
-        if (y % SP_TH == 0) flag(bx, by - 1);
-        if (y % SP_TH == SP_TH - 1) flag(bx, by + 1);
-    }
+    for (int t : targets) round0_flags(t % h->W, t / h->W, conn, flag);
     SCHK(h, hipMemcpyAsync(q->flags, q->flags0.data(), (size_t)p.ntiles * 4, hipMemcpyHostToDevice, h->stream));
     q->rounds = 0; q->tile_runs = 0;
     const long long cap = (long long)npx;   // costs only decrease over a finite set: this never fires
@@ -183,7 +188,7 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
         if (round >= cap) return h->fail(YH_EHIP, "path solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
         SCHK(h, hipMemsetAsync(q->cnt, 0, (SP_BATCH + 1) * 4, h->stream));
         for (int j = 0; j < SP_BATCH; ++j, ++round)
-            hipLaunchKernelGGL(path_round, tiles, dim3(SP_NT), 0, h->stream, p, (int)(round & 1), q->cnt + j + 1);
+            hipLaunchKernelGGL(conn == 8 ? path_round<8> : path_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, (int)(round & 1), q->cnt + j + 1);
         SCHK(h, hipGetLastError());
         SCHK(h, hipMemcpyAsync(q->host, q->cnt, (SP_BATCH + 1) * 4, hipMemcpyDeviceToHost, h->stream));
         SCHK(h, hipStreamSynchronize(h->stream));
@@ -191,7 +196,7 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
         for (int j = 0; j < SP_BATCH; ++j) if (q->host[j]) { ++q->rounds; q->tile_runs += q->host[j]; }
         active = q->host[SP_BATCH];
     }
-    hipLaunchKernelGGL(path_next, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(conn == 8 ? path_next<8> : path_next<4>, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p);
     hipLaunchKernelGGL(path_mark_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
     hipLaunchKernelGGL(path_walk, dim3(1), dim3(64), 0, h->stream, p, (int)start, q->nodes, q->dirs, q->walk_out);
     SCHK(h, hipGetLastError());
@@ -206,8 +211,8 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
 }  // namespace
 
 namespace yh {
-void path_weights_launch(const PathParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(path_weights, dim3((unsigned)((p.W * p.H + 255) / 256)), dim3(256), 0, s, p);
+void path_weights_launch(const PathParams& p, int conn, hipStream_t s) {
+    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)((p.W * p.H + 255) / 256)), dim3(256), 0, s, p);
 }
 
 // What yh_scene_plan and yh_scene_plan_tour check before they touch anything, and the targets they run on (linear indices)
@@ -246,10 +251,15 @@ int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
     return YH_OK;
 }
 
+int scene_plan_diagonals(yh_scene* h) {
+    if (h->diag_ok) return YH_OK;
+    return h->fail(YH_ESTATE, "the uploaded fields allow 4-connected plans only: " + h->diag_why);
+}
+
 void scene_path_free(yh_scene* h) {
     yh_scene_path* q = h->path;
     if (!q) return;
-    void* bufs[] = { q->cost, q->next, q->edge, q->flags, q->cnt, q->targets, q->nodes, q->dirs, q->walk_out };
+    void* bufs[] = { q->cost, q->next, q->edge, q->edge2, q->flags, q->cnt, q->targets, q->nodes, q->dirs, q->walk_out };
     for (void* b : bufs) if (b) hipFree(b);
     if (q->host) hipHostFree(q->host);
     delete q;
@@ -260,10 +270,16 @@ void scene_path_free(yh_scene* h) {
 extern "C" {
 
 int yh_scene_plan(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y) {
+    return yh_scene_plan_conn(h, targets_xy, n_targets, start_x, start_y, 4);
+}
+
+int yh_scene_plan_conn(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, int32_t connectivity) {
     if (!h) return YH_EINVAL;
+    if (connectivity != 4 && connectivity != 8) return h->fail(YH_EINVAL, "connectivity " + std::to_string(connectivity) + ": 4 or 8");
     std::vector<int32_t> targets;
     int rc = scene_plan_targets(h, targets_xy, n_targets, start_x, start_y, targets);
     if (rc) return rc;
+    if (connectivity == 8 && (rc = scene_plan_diagonals(h))) return rc;
     const long long W = h->W;
     if (!h->path) {   // the planner's buffers are allocated at the first plan: a handle that never plans pays nothing
         h->path = new yh_scene_path();
@@ -271,8 +287,9 @@ int yh_scene_plan(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int
         if (rc) { scene_path_free(h); return rc; }
     }
     h->path->planned = false;
-    rc = run_plan(h, targets, (int32_t)(start_y * W + start_x));
+    rc = run_plan(h, targets, (int32_t)(start_y * W + start_x), connectivity);
     if (rc) return rc;
+    h->path->conn = connectivity;
     h->path->planned = true; h->path->frame = h->frames; h->path->last_targets = targets; h->path->start = (int32_t)(start_y * W + start_x);
     return YH_OK;
 }
@@ -308,6 +325,21 @@ int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, co
                 return h->fail(YH_EINVAL, "fields are not those of a SANE frame at pixel (" + std::to_string(x) + ", " + std::to_string(y) + "): the " +
                                               (okr ? "down" : "right") + " length must be a finite number >= 1 and equal the neighbour's entry for the same edge");
         }
+    // the diagonals are no reason to refuse: what is recorded is whether an 8-connected plan may read them the same way (the
+    // down-right and down-left entry of the upper pixel for both directions)
+    bool diag_ok = true;
+    std::string diag_why;
+    for (int y = 0; y + 1 < h->H && diag_ok; ++y)
+        for (int x = 0; x < h->W && diag_ok; ++x) {
+            const size_t i = (size_t)y * h->W + x;
+            const bool okr = x + 1 >= h->W || (conn0[4 * i + 3] >= 1.0f && conn0[4 * i + 3] < 3.0e38f && conn0[4 * i + 3] == conn1[4 * (i + h->W + 1) + 3]);
+            const bool okl = x < 1 || (conn1[4 * i + 1] >= 1.0f && conn1[4 * i + 1] < 3.0e38f && conn1[4 * i + 1] == conn0[4 * (i + h->W - 1) + 1]);
+            if (!okr || !okl) {
+                diag_ok = false;
+                diag_why = std::string("the down-") + (okr ? "left" : "right") + " length of pixel (" + std::to_string(x) + ", " + std::to_string(y) +
+                           ") is not a finite number >= 1 equal to the other end's entry for the same edge";
+            }
+        }
     SCHK(h, hipSetDevice(h->dev));
     const size_t npx = (size_t)h->W * h->H;
     SCHK(h, hipMemcpyAsync(h->map, map, npx * 4, hipMemcpyHostToDevice, h->stream));
@@ -317,6 +349,7 @@ int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, co
     SCHK(h, hipMemsetAsync(h->balls, 0, 100 * 16, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
     h->ran = true; h->last_mode = YH_COMPAT_SANE; h->last_cls = h->cls_id; h->last_frame = nullptr; h->last_frame_mode = 0;
+    h->diag_ok = diag_ok; h->diag_why = diag_why;
     ++h->frames;
     return YH_OK;
 }
@@ -330,7 +363,7 @@ int yh_scene_plan_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* r
     hipEvent_t a, b;
     SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
     SCHK(h, hipEventRecord(a, h->stream));
-    for (int r = 0; r < reps; ++r) { const int rc = run_plan(h, q->last_targets, q->start); if (rc) { hipEventDestroy(a); hipEventDestroy(b); return rc; } }
+    for (int r = 0; r < reps; ++r) { const int rc = run_plan(h, q->last_targets, q->start, q->conn); if (rc) { hipEventDestroy(a); hipEventDestroy(b); return rc; } }
     SCHK(h, hipEventRecord(b, h->stream));
     SCHK(h, hipEventSynchronize(b));
     float ms = 0;

@@ -31,20 +31,38 @@ struct PathParams {
     const uint32_t* map;
     const float4 *conn0, *conn1;
     float4* edge;
+    float4* edge2;   // 8-connected plans only (else nullptr)
     float* cost;
     int32_t* next;
     uint32_t* flags;
 };
 
-// path_weights (scene_path.hip) on stream s: p.map, p.conn0, p.conn1 -> p.edge. The edge terms do not depend on the targets: a tour
+// path_weights (scene_path.hip) on stream s: p.map, p.conn0, p.conn1 -> p.edge, and with conn == 8 -> p.edge2 (down-right length,
+// down-right |dh|, down-left length, down-left |dh|; length -1 off the frame). The edge terms do not depend on the targets: a tour
 // computes them once for all its fields.
-void path_weights_launch(const PathParams& p, hipStream_t s);
+void path_weights_launch(const PathParams& p, int conn, hipStream_t s);
+
+// Round 0's tiles for a target at (x, y), through flag(tile x, tile y) (which ignores tiles outside the grid): its own tile, the tile
+// across every tile border it lies on and, with diagonals, the tile diagonally across a tile corner it lies on.
+template <class F>
+inline void round0_flags(int x, int y, int conn, F&& flag) {
+    const int bx = x / SP_TW, by = y / SP_TH;
+    const int sx = x % SP_TW == 0 ? -1 : x % SP_TW == SP_TW - 1 ? 1 : 0, sy = y % SP_TH == 0 ? -1 : y % SP_TH == SP_TH - 1 ? 1 : 0;
+    flag(bx, by);
+    if (sx) flag(bx + sx, by);
+    if (sy) flag(bx, by + sy);
+    if (conn == 8 && sx && sy) flag(bx + sx, by + sy);
+}
 
 __device__ __forceinline__ float cand(float dn, float len, float dh) { return __fadd_rn(__fadd_rn(dn, len), dh); }
 
 // One workgroup of SP_NT lanes, tile (blockIdx.x, blockIdx.y) of the field `cost`: if `mine` flags the tile, relax it to its local
 // fixed point for the halo it loads, write back what got smaller, flag in `theirs` the tiles across every border that moved and
-// count each newly flagged one in *cnt_next.
+// count each newly flagged one in *cnt_next. CONN = 4: the straight edges; CONN = 8: the diagonals too - a lane reads the twelve
+// cells round its 2 x 2 block (the halo has the corners), sweeps six inner and twenty outer edges, all fifty-two edge terms in
+// registers (a workgroup is one wave per SIMD: the register file is not what limits it), and a lowered CORNER cell flags the tile
+// diagonally across as well: that tile reads the cell in its halo, and neither side tile has to lower anything because of it.
+template <int CONN>
 __device__ __forceinline__ void relax_tile(const PathParams& p, float* cost, uint32_t* mine, uint32_t* theirs, uint32_t* cnt_next) {
     __shared__ float dl[(SP_TH + 2) * SP_P];
     __shared__ uint32_t active, border;
@@ -80,6 +98,29 @@ __device__ __forceinline__ void relax_tile(const PathParams& p, float* cost, uin
     const float l_rb = SP_LEN(has_r && in_b, eb.x), h_rb = eb.y, l_rd = SP_LEN(has_r && in_d, ed.x), h_rd = ed.y;       // to the right of b, d
     const float l_ua = SP_LEN(has_u && in_a, eua.z), h_ua = eua.w, l_ub = SP_LEN(has_u && in_b, eub.z), h_ub = eub.w;   // above a, b
     const float l_dc = SP_LEN(has_d && in_c, ec.z), h_dc = ec.w, l_dd = SP_LEN(has_d && in_d, ed.z), h_dd = ed.w;       // below c, d
+    // the diagonals: (length, |dh|) of the pixel's down-right and down-left edge; an up-left / up-right edge is the upper pixel's
+    float l_ad = 0, h_ad = 0, l_bc = 0, h_bc = 0;                                          // inside the block
+    float l_ula = 0, h_ula = 0, l_ura = 0, h_ura = 0, l_dla = 0, h_dla = 0;                // a: up-left, up-right (above b), down-left (left of c)
+    float l_ulb = 0, h_ulb = 0, l_urb = 0, h_urb = 0, l_drb = 0, h_drb = 0;                // b: up-left (above a), up-right, down-right (right of d)
+    float l_ulc = 0, h_ulc = 0, l_dlc = 0, h_dlc = 0, l_drc = 0, h_drc = 0;                // c: up-left (left of a), down-left, down-right (below d)
+    float l_urd = 0, h_urd = 0, l_dld = 0, h_dld = 0, l_drd = 0, h_drd = 0;                // d: up-right (right of b), down-left (below c), down-right
+    if constexpr (CONN == 8) {
+        const bool has_r1 = gx + 1 < p.W;   // (the column of b and d)
+        const float4 fa = in_a ? p.edge2[ga] : none, fb = in_b ? p.edge2[ga + 1] : none;
+        const float4 fc = in_c ? p.edge2[ga + p.W] : none, fd = in_d ? p.edge2[ga + p.W + 1] : none;
+        const float4 fla = has_l && in_a ? p.edge2[ga - 1] : none, frb = has_r && in_b ? p.edge2[ga + 2] : none;
+        const float4 ful = has_u && has_l && in_a ? p.edge2[ga - p.W - 1] : none, fua = has_u && in_a ? p.edge2[ga - p.W] : none;
+        const float4 fub = has_u && in_b ? p.edge2[ga - p.W + 1] : none, fur = has_u && has_r && in_b ? p.edge2[ga - p.W + 2] : none;
+        l_ad = SP_LEN(in_a && in_d, fa.x); h_ad = fa.y; l_bc = SP_LEN(in_b && in_c, fb.z); h_bc = fb.w;
+        l_ula = SP_LEN(has_u && has_l && in_a, ful.x); h_ula = ful.y; l_ura = SP_LEN(has_u && in_a && has_r1, fub.z); h_ura = fub.w;
+        l_dla = SP_LEN(has_l && in_c, fa.z); h_dla = fa.w;
+        l_ulb = SP_LEN(has_u && in_b, fua.x); h_ulb = fua.y; l_urb = SP_LEN(has_u && has_r && in_b, fur.z); h_urb = fur.w;
+        l_drb = SP_LEN(has_r && in_d, fb.x); h_drb = fb.y;
+        l_ulc = SP_LEN(has_l && in_c, fla.x); h_ulc = fla.y; l_dlc = SP_LEN(has_l && has_d && in_c, fc.z); h_dlc = fc.w;
+        l_drc = SP_LEN(has_d && in_d, fc.x); h_drc = fc.y;
+        l_urd = SP_LEN(has_r && in_d, frb.z); h_urd = frb.w; l_dld = SP_LEN(has_d && in_d, fd.z); h_dld = fd.w;
+        l_drd = SP_LEN(has_r && has_d && in_d, fd.x); h_drd = fd.y;
+    }
 #undef SP_LEN
     const int ia = (cy + 1) * SP_P + cx + 1, ib = ia + 1, ic = ia + SP_P, id = ic + 1;
     __syncthreads();
@@ -100,13 +141,28 @@ __device__ __forceinline__ void relax_tile(const PathParams& p, float* cost, uin
             float b = fminf(vb, fminf(cand(nb_r, l_rb, h_rb), cand(nb_u, l_ub, h_ub)));
             float c = fminf(vc, fminf(cand(nc_l, l_lc, h_lc), cand(nc_d, l_dc, h_dc)));
             float d = fminf(vd, fminf(cand(nd_r, l_rd, h_rd), cand(nd_d, l_dd, h_dd)));
-            a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));       // forwards a, b, c, d
-            b = fminf(b, fminf(cand(a, l_ab, h_ab), cand(d, l_bd, h_bd)));
-            c = fminf(c, fminf(cand(a, l_ac, h_ac), cand(d, l_cd, h_cd)));
-            d = fminf(d, fminf(cand(b, l_bd, h_bd), cand(c, l_cd, h_cd)));
-            c = fminf(c, cand(d, l_cd, h_cd));                                   // and back
-            b = fminf(b, cand(d, l_bd, h_bd));
-            a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));
+            if constexpr (CONN == 8) {
+                const float n_ul = SP_LD(ia - SP_P - 1), n_ur = SP_LD(ib - SP_P + 1), n_dl = SP_LD(ic + SP_P - 1), n_dr = SP_LD(id + SP_P + 1);
+                a = fminf(a, fminf(cand(n_ul, l_ula, h_ula), fminf(cand(nb_u, l_ura, h_ura), cand(nc_l, l_dla, h_dla))));
+                b = fminf(b, fminf(cand(na_u, l_ulb, h_ulb), fminf(cand(n_ur, l_urb, h_urb), cand(nd_r, l_drb, h_drb))));
+                c = fminf(c, fminf(cand(na_l, l_ulc, h_ulc), fminf(cand(n_dl, l_dlc, h_dlc), cand(nd_d, l_drc, h_drc))));
+                d = fminf(d, fminf(cand(nb_r, l_urd, h_urd), fminf(cand(nc_d, l_dld, h_dld), cand(n_dr, l_drd, h_drd))));
+                a = fminf(a, fminf(fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)), cand(d, l_ad, h_ad)));   // forwards a, b, c, d
+                b = fminf(b, fminf(fminf(cand(a, l_ab, h_ab), cand(d, l_bd, h_bd)), cand(c, l_bc, h_bc)));
+                c = fminf(c, fminf(fminf(cand(a, l_ac, h_ac), cand(d, l_cd, h_cd)), cand(b, l_bc, h_bc)));
+                d = fminf(d, fminf(fminf(cand(b, l_bd, h_bd), cand(c, l_cd, h_cd)), cand(a, l_ad, h_ad)));
+                c = fminf(c, cand(d, l_cd, h_cd));                                                           // and back
+                b = fminf(b, fminf(cand(d, l_bd, h_bd), cand(c, l_bc, h_bc)));
+                a = fminf(a, fminf(fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)), cand(d, l_ad, h_ad)));
+            } else {
+                a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));       // forwards a, b, c, d
+                b = fminf(b, fminf(cand(a, l_ab, h_ab), cand(d, l_bd, h_bd)));
+                c = fminf(c, fminf(cand(a, l_ac, h_ac), cand(d, l_cd, h_cd)));
+                d = fminf(d, fminf(cand(b, l_bd, h_bd), cand(c, l_cd, h_cd)));
+                c = fminf(c, cand(d, l_cd, h_cd));                                   // and back
+                b = fminf(b, cand(d, l_bd, h_bd));
+                a = fminf(a, fminf(cand(b, l_ab, h_ab), cand(c, l_ac, h_ac)));
+            }
             if (a < va) { SP_ST(ia, a); va = a; ch = 1; }
             if (b < vb) { SP_ST(ib, b); vb = b; ch = 1; }
             if (c < vc) { SP_ST(ic, c); vc = c; ch = 1; }
@@ -128,26 +184,70 @@ __device__ __forceinline__ void relax_tile(const PathParams& p, float* cost, uin
     if (cx == SP_TW - 2 && (cb || cd)) m |= 2u;
     if (cy == 0 && (ca || cb)) m |= 4u;
     if (cy == SP_TH - 2 && (cc || cd)) m |= 8u;
+    if constexpr (CONN == 8) {   // the four corner cells: bits 4 .. 7 = up-left, up-right, down-left, down-right
+        if (cx == 0 && cy == 0 && ca) m |= 16u;
+        if (cx == SP_TW - 2 && cy == 0 && cb) m |= 32u;
+        if (cx == 0 && cy == SP_TH - 2 && cc) m |= 64u;
+        if (cx == SP_TW - 2 && cy == SP_TH - 2 && cd) m |= 128u;
+    }
     if (m) atomicOr(&border, m);
     __syncthreads();
-    if (tid < 4 && ((border >> tid) & 1u)) {
-        const int bx = (int)blockIdx.x + (tid == 0 ? -1 : tid == 1 ? 1 : 0), by = (int)blockIdx.y + (tid == 2 ? -1 : tid == 3 ? 1 : 0);
+    if (tid < CONN && ((border >> tid) & 1u)) {
+        const int sx = tid == 0 ? -1 : tid == 1 ? 1 : tid < 4 ? 0 : (tid & 1) ? 1 : -1, sy = tid < 2 ? 0 : tid == 2 ? -1 : tid == 3 ? 1 : tid < 6 ? -1 : 1;
+        const int bx = (int)blockIdx.x + sx, by = (int)blockIdx.y + sy;
         if (bx >= 0 && bx < p.tx && by >= 0 && by < (int)gridDim.y && atomicExch(theirs + by * p.tx + bx, 1u) == 0u) atomicAdd(cnt_next, 1u);
     }
 }
 
-// next[i] of the field `cost`: the first neighbour in the order (left, right, up, down) whose candidate equals d[i] bitwise, -1 if none
-__device__ __forceinline__ int successor(const PathParams& p, const float* cost, int i) {
+// The edges of pixel i in the successor's order (left, right, up, down, up-left, up-right, down-left, down-right; the first CONN of
+// them): the neighbour's linear index (-1 off the frame) and the edge's terms. Read once per pixel, whatever the number of fields.
+template <int CONN>
+struct Around { int at[CONN]; float len[CONN], dh[CONN]; };
+
+template <int CONN>
+__device__ __forceinline__ Around<CONN> around(const PathParams& p, int i) {
     const int x = i % p.W, y = i / p.W;
+    const bool l = x > 0, r = x + 1 < p.W, u = y > 0, d = y + 1 < p.H;
+    Around<CONN> e;
+    auto put = [&](int k, bool ok, int at, float len, float dh) { e.at[k] = ok ? at : -1; e.len[k] = len; e.dh[k] = dh; };
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 own = p.edge[i], le = l ? p.edge[i - 1] : none, up = u ? p.edge[i - p.W] : none;
+    put(0, l, i - 1, le.x, le.y);
+    put(1, r, i + 1, own.x, own.y);
+    put(2, u, i - p.W, up.z, up.w);
+    put(3, d, i + p.W, own.z, own.w);
+    if constexpr (CONN == 8) {
+        const float4 own2 = p.edge2[i], ul = u && l ? p.edge2[i - p.W - 1] : none, ur = u && r ? p.edge2[i - p.W + 1] : none;
+        put(4, u && l, i - p.W - 1, ul.x, ul.y);
+        put(5, u && r, i - p.W + 1, ur.z, ur.w);
+        put(6, d && l, i + p.W - 1, own2.z, own2.w);
+        put(7, d && r, i + p.W + 1, own2.x, own2.y);
+    }
+    return e;
+}
+
+// next[i] of the field `cost`: the first neighbour in that order whose candidate equals d[i] bitwise, -1 if none
+template <int CONN>
+__device__ __forceinline__ int successor(const Around<CONN>& e, const float* cost, int i) {
     const uint32_t dv = __float_as_uint(cost[i]);
-    const float4 e = p.edge[i];
     int nx = -1;
-    // (in reverse, so that the first of the order left, right, up, down wins)
-    if (y + 1 < p.H && __float_as_uint(cand(cost[i + p.W], e.z, e.w)) == dv) nx = i + p.W;
-    if (y > 0) { const float4 u = p.edge[i - p.W]; if (__float_as_uint(cand(cost[i - p.W], u.z, u.w)) == dv) nx = i - p.W; }
-    if (x + 1 < p.W && __float_as_uint(cand(cost[i + 1], e.x, e.y)) == dv) nx = i + 1;
-    if (x > 0) { const float4 l = p.edge[i - 1]; if (__float_as_uint(cand(cost[i - 1], l.x, l.y)) == dv) nx = i - 1; }
+    // (in reverse, so that the first of the order wins)
+#pragma unroll
+    for (int k = CONN - 1; k >= 0; --k)
+        if (e.at[k] >= 0 && __float_as_uint(cand(cost[e.at[k]], e.len[k], e.dh[k])) == dv) nx = e.at[k];
     return nx;
+}
+
+// rot_i at node a between the step z -> a and the step a -> b (each to one of the eight neighbours): with k the number of 45-degree
+// steps between the two headings, float32((4 - k) * pi / 4): pi straight on, pi / 2 for a right angle (all a 4-connected route has),
+// 0 for a reversal (at a tour's junction only). Five constants, no device acosf.
+__device__ __forceinline__ float rotation(int2 z, int2 a, int2 b) {
+    // heading (dx, dy) -> 0 .. 7 round the compass, 4 bits each at 4 * (3 * (dy + 1) + (dx + 1))
+    const uint64_t compass = 0x5ull | 0x6ull << 4 | 0x7ull << 8 | 0x4ull << 12 | 0x0ull << 20 | 0x3ull << 24 | 0x2ull << 28 | 0x1ull << 32;
+    const int in = (int)(compass >> (4 * (3 * (a.y - z.y + 1) + (a.x - z.x + 1)))) & 7, out = (int)(compass >> (4 * (3 * (b.y - a.y + 1) + (b.x - a.x + 1)))) & 7;
+    const int t = (in - out) & 7, k = t > 4 ? 8 - t : t;
+    constexpr double pi = 3.14159265358979323846;
+    return k == 0 ? (float)pi : k == 1 ? (float)(3.0 * pi / 4.0) : k == 2 ? (float)(pi / 2.0) : k == 3 ? (float)(pi / 4.0) : 0.0f;
 }
 
 // One wave chases `next` from `start` through a SP_WS x SP_WS window of it held in LDS (reloaded when the route leaves it) and

@@ -18,7 +18,7 @@
 //                  its flag test as idle tiles do. No workgroup waits for another one.
 //   tour_legs      after every batch of rounds: the K (K + 1) entries of the leg matrix into the block the host reads the batch's
 //                  counters from, so the matrix arrives with the last counters (earlier batches' copies are ignored).
-//   tour_next      one lane per pixel: next_b for the K fields and the label.
+//   tour_next      one lane per pixel: next_b for the K fields and the label (the pixel's edge terms read once for all of them).
 //   (host)         the order: all K! <= 720 permutations from the leg matrix.
 //   tour_walk      K waves, one per leg: leg j chases next_{o_j} from the start (j = 0) or from t_{o_{j-1}} into its own segment.
 //   tour_join      the segments into one node list (a junction node once) and the directions over it.
@@ -43,6 +43,7 @@ struct yh_scene_tour {
     int32_t* next = nullptr;     // [K][H][W]
     uint8_t* label = nullptr;    // [H][W]
     float4* edge = nullptr;      // [H][W], as yh_scene_path::edge
+    float4* edge2 = nullptr;     // [H][W], as yh_scene_path::edge2: allocated at the first 8-connected tour
     uint32_t* flags = nullptr;   // [2][K][ntiles]
     uint32_t* cnt = nullptr;     // [SP_BATCH + 1] counters, then YH_TOUR_MAX (YH_TOUR_MAX + 1) legs (f32)
     int2* segs = nullptr;        // [K][W * H] the legs' walks
@@ -56,7 +57,7 @@ struct yh_scene_tour {
     uint64_t frame = 0;
     std::vector<int32_t> targets;   // linear indices, t_0 .. t_{K-1}
     std::vector<uint32_t> flags0;   // round 0's tile flags [K][ntiles], built on the host
-    int32_t start = 0, path_len = 0;
+    int32_t start = 0, path_len = 0, conn = 4;
     int32_t order[YH_TOUR_MAX], leg_ends[YH_TOUR_MAX];
     float legs[(YH_TOUR_MAX + 1) * YH_TOUR_MAX], total = 0.0f;
     long long rounds = 0, tile_runs = 0;
@@ -77,9 +78,10 @@ __global__ __launch_bounds__(256) void tour_fill(const PathParams p, const TourP
     if (i < 2 * pts.K * p.ntiles) p.flags[i] = 0u;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(SP_NT) void tour_round(const PathParams p, int K, int parity, uint32_t* cnt_next) {
     const int b = blockIdx.z;
-    relax_tile(p, p.cost + (size_t)b * p.W * p.H, p.flags + (size_t)(parity * K + b) * p.ntiles, p.flags + (size_t)((parity ^ 1) * K + b) * p.ntiles, cnt_next);
+    relax_tile<CONN>(p, p.cost + (size_t)b * p.W * p.H, p.flags + (size_t)(parity * K + b) * p.ntiles, p.flags + (size_t)((parity ^ 1) * K + b) * p.ntiles, cnt_next);
 }
 
 __global__ __launch_bounds__(64) void tour_legs(const PathParams p, const TourPoints pts, float* legs) {
@@ -89,14 +91,16 @@ __global__ __launch_bounds__(64) void tour_legs(const PathParams p, const TourPo
     legs[e] = p.cost[(size_t)b * p.W * p.H + (a == 0 ? pts.start : pts.t[a - 1])];
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void tour_next(const PathParams p, const TourPoints pts, uint8_t* label) {
     const int i = blockIdx.x * 256 + threadIdx.x, npx = p.W * p.H;
     if (i >= npx) return;
+    const Around<CONN> e = around<CONN>(p, i);
     float best = SP_INF;
     int lab = 0;
     for (int b = 0; b < pts.K; ++b) {
         const float* cost = p.cost + (size_t)b * npx;
-        p.next[(size_t)b * npx + i] = i == pts.t[b] ? -1 : successor(p, cost, i);
+        p.next[(size_t)b * npx + i] = i == pts.t[b] ? -1 : successor(e, cost, i);
         const float d = cost[i];
         if (d < best) { best = d; lab = b; }   // (strictly: the smallest b among equals)
     }
@@ -138,12 +142,8 @@ __global__ __launch_bounds__(256) void tour_join(const PathParams p, const TourL
         const float* cost = p.cost + (size_t)field * npx;
         const int2 b = node(g + 1);
         const float mag = __fsub_rn(cost[(size_t)a.y * p.W + a.x], cost[(size_t)b.y * p.W + b.x]);
-        float rot = 0.0f;   // step 0, and a reversal (n_{g-1} == n_{g+1}: at a junction only)
-        if (g > 0) {
-            const int2 z = node(g - 1);
-            if (z.x != b.x || z.y != b.y) rot = (z.x + b.x == 2 * a.x && z.y + b.y == 2 * a.y) ? 3.14159274f : 1.57079637f;
-        }
-        dirs[g] = make_float2(mag, rot);
+        // (0 at step 0, and at a reversal, n_{g-1} == n_{g+1}: at a junction only)
+        dirs[g] = make_float2(mag, g > 0 ? rotation(node(g - 1), a, b) : 0.0f);
     }
 }
 
@@ -195,17 +195,18 @@ float best_order(const float* legs, int K, int32_t* order) {
 }
 
 // the whole tour on the handle's stream; returns when the route's length is known
-int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
+int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, int conn) {
     yh_scene_tour* q = h->tour;
     const int K = (int)targets.size(), npx = h->W * h->H;
+    if (conn == 8 && !q->edge2) SCHK(h, hipMalloc((void**)&q->edge2, (size_t)npx * 16));
     PathParams p;
     p.W = h->W; p.H = h->H; p.tx = q->tx; p.ntiles = q->tx * q->ty;
-    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
+    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.edge2 = conn == 8 ? q->edge2 : nullptr; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
     TourPoints pts;
     pts.K = K; pts.start = start;
     for (int b = 0; b < YH_TOUR_MAX; ++b) pts.t[b] = b < K ? targets[b] : -1;
     const dim3 px((unsigned)((std::max(npx, 2 * K * p.ntiles) + 255) / 256)), tiles((unsigned)q->tx, (unsigned)q->ty, (unsigned)K);
-    path_weights_launch(p, h->stream);
+    path_weights_launch(p, conn, h->stream);
     hipLaunchKernelGGL(tour_fill, px, dim3(256), 0, h->stream, p, pts);
     // round 0's work list, per field (flag array 0, [K][ntiles]): scene_path.hip's rule for that field's one target
     q->flags0.assign((size_t)K * p.ntiles, 0u);
@@ -216,12 +217,7 @@ int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
             uint32_t& f = q->flags0[(size_t)b * p.ntiles + (size_t)by * q->tx + bx];
             if (!f) { f = 1u; ++active; }
         };
-        const int x = targets[b] % h->W, y = targets[b] / h->W, bx = x / SP_TW, by = y / SP_TH;
-        flag(bx, by);
-        if (x % SP_TW == 0) flag(bx - 1, by);
-        if (x % SP_TW == SP_TW - 1) flag(bx + 1, by);
-        if (y % SP_TH == 0) flag(bx, by - 1);
-        if (y % SP_TH == SP_TH - 1) flag(bx, by + 1);
+        round0_flags(targets[b] % h->W, targets[b] / h->W, conn, flag);
     }
     SCHK(h, hipMemcpyAsync(q->flags, q->flags0.data(), q->flags0.size() * 4, hipMemcpyHostToDevice, h->stream));
     q->rounds = 0; q->tile_runs = 0;
@@ -232,7 +228,7 @@ int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
         if (round >= cap) return h->fail(YH_EHIP, "tour solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
         SCHK(h, hipMemsetAsync(q->cnt, 0, (SP_BATCH + 1) * 4, h->stream));
         for (int j = 0; j < SP_BATCH; ++j, ++round)
-            hipLaunchKernelGGL(tour_round, tiles, dim3(SP_NT), 0, h->stream, p, K, (int)(round & 1), q->cnt + j + 1);
+            hipLaunchKernelGGL(conn == 8 ? tour_round<8> : tour_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, K, (int)(round & 1), q->cnt + j + 1);
         hipLaunchKernelGGL(tour_legs, dim3(1), dim3(64), 0, h->stream, p, pts, legs_dev);
         SCHK(h, hipGetLastError());
         SCHK(h, hipMemcpyAsync(q->host, q->cnt, kCntWords * 4, hipMemcpyDeviceToHost, h->stream));
@@ -241,7 +237,7 @@ int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start) {
         for (int j = 0; j < SP_BATCH; ++j) if (q->host[j]) { ++q->rounds; q->tile_runs += q->host[j]; }
         active = q->host[SP_BATCH];
     }
-    hipLaunchKernelGGL(tour_next, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p, pts, q->label);
+    hipLaunchKernelGGL(conn == 8 ? tour_next<8> : tour_next<4>, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p, pts, q->label);
     // the order, from the matrix the last batch's read brought; then the legs are independent: leg j's field and start are fixed
     memcpy(q->legs, q->host + SP_BATCH + 1, (size_t)(K + 1) * K * 4);
     q->total = best_order(q->legs, K, q->order);
@@ -274,7 +270,7 @@ void scene_tour_free(yh_scene* h) {
     yh_scene_tour* q = h->tour;
     if (!q) return;
     free_fields(q);
-    void* bufs[] = { q->label, q->edge, q->cnt, q->walk_out };
+    void* bufs[] = { q->label, q->edge, q->edge2, q->cnt, q->walk_out };
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (q->host) (void)hipHostFree(q->host);
     delete q;
@@ -285,7 +281,12 @@ void scene_tour_free(yh_scene* h) {
 extern "C" {
 
 int yh_scene_plan_tour(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y) {
+    return yh_scene_plan_tour_conn(h, targets_xy, n_targets, start_x, start_y, 4);
+}
+
+int yh_scene_plan_tour_conn(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, int32_t connectivity) {
     if (!h) return YH_EINVAL;
+    if (connectivity != 4 && connectivity != 8) return h->fail(YH_EINVAL, "connectivity " + std::to_string(connectivity) + ": 4 or 8");
     if (n_targets > YH_TOUR_MAX) return h->fail(YH_EINVAL, "n_targets " + std::to_string(n_targets) + " > YH_TOUR_MAX = " + std::to_string(YH_TOUR_MAX));
     std::vector<int32_t> chosen, targets;
     int rc = scene_plan_targets(h, targets_xy, n_targets, start_x, start_y, chosen);
@@ -295,14 +296,16 @@ int yh_scene_plan_tour(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
         // (a ball on an earlier ball's pixel is dropped)
         if (targets_xy) return h->fail(YH_EINVAL, "duplicate target (" + std::to_string(t % h->W) + ", " + std::to_string(t / h->W) + "): a tour's targets are distinct pixels");
     }
+    if (connectivity == 8 && (rc = scene_plan_diagonals(h))) return rc;
     if (!h->tour) h->tour = new yh_scene_tour();   // the tour's buffers are allocated at the first tour: a handle that never tours pays nothing
     rc = ensure_buffers(h, (int)targets.size());
     if (rc) { scene_tour_free(h); return rc; }
     yh_scene_tour* q = h->tour;
     q->planned = false;
     const int32_t start = (int32_t)((long long)start_y * h->W + start_x);
-    rc = run_tour(h, targets, start);
+    rc = run_tour(h, targets, start, connectivity);
     if (rc) return rc;
+    q->conn = connectivity;
     q->planned = true; q->frame = h->frames; q->targets = targets; q->start = start;
     return YH_OK;
 }
@@ -346,7 +349,7 @@ int yh_scene_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* r
     SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
     SCHK(h, hipEventRecord(a, h->stream));
     for (int r = 0; r < reps; ++r) {
-        const int rc = run_tour(h, q->targets, q->start);
+        const int rc = run_tour(h, q->targets, q->start, q->conn);
         if (rc) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); q->planned = false; return rc; }
     }
     SCHK(h, hipEventRecord(b, h->stream));

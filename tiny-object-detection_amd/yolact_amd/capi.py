@@ -149,10 +149,12 @@ SYMBOLS = [
     ("yh_scene_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_time", _i, [_vp, _i, C.POINTER(_f)]),
     ("yh_scene_plan", _i, [_vp, _vp, _i, _i, _i]),
+    ("yh_scene_plan_conn", _i, [_vp, _vp, _i, _i, _i, _i]),
     ("yh_scene_plan_read", _i, [_vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_set_fields", _i, [_vp, _vp, _vp, _vp]),
     ("yh_scene_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_scene_plan_tour", _i, [_vp, _vp, _i, _i, _i]),
+    ("yh_scene_plan_tour_conn", _i, [_vp, _vp, _i, _i, _i, _i]),
     ("yh_scene_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
@@ -768,18 +770,19 @@ class Scene:
         self._chk(self.L.yh_scene_time(self.h, reps, C.byref(ms)))
         return ms.value
 
-    def plan(self, targets=None, n_targets=3, start=None):
+    def plan(self, targets=None, n_targets=3, start=None, connectivity=4):
         """modify_path (src/path.rs:25-120) on the last appended frame. targets: (x, y) pixels, or None: the first n_targets balls
-        (balls[..3], path.rs:37). start: the robot's pixel (x, y); None: the reference's START_NODE, (400, 479), at 640x480 only."""
+        (balls[..3], path.rs:37). start: the robot's pixel (x, y); None: the reference's START_NODE, (400, 479), at 640x480 only.
+        connectivity: 4, or 8 to use the scene's diagonal lengths too (DESIGN.md §11 "Diagonals")."""
         if start is None:
             if (self.W, self.H) != (640, 480):
                 raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
             start = (400, 479)
         if targets is None:
-            self._chk(self.L.yh_scene_plan(self.h, None, n_targets, start[0], start[1]))
+            self._chk(self.L.yh_scene_plan_conn(self.h, None, n_targets, start[0], start[1], connectivity))
         else:
             t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
-            self._chk(self.L.yh_scene_plan(self.h, _p(t), len(t), start[0], start[1]))
+            self._chk(self.L.yh_scene_plan_conn(self.h, _p(t), len(t), start[0], start[1], connectivity))
 
     def read_plan(self, fields=True):
         """The last plan: path int32 [L][2] (x, y) from the start to a target, directions f32 [L - 1][2] (magnitude, rotation), and
@@ -809,18 +812,18 @@ class Scene:
         self._chk(self.L.yh_scene_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
 
-    def plan_tour(self, targets=None, n_targets=3, start=None):
+    def plan_tour(self, targets=None, n_targets=3, start=None, connectivity=4):
         """The tour (DESIGN.md §11 "Tour"): one cost field per target solved in the same launches, the visiting order of least
-        total cost and the joined route. targets, n_targets (at most TOUR_MAX, distinct) and start as plan()."""
+        total cost and the joined route. targets, n_targets (at most TOUR_MAX, distinct), start and connectivity as plan()."""
         if start is None:
             if (self.W, self.H) != (640, 480):
                 raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
             start = (400, 479)
         if targets is None:
-            self._chk(self.L.yh_scene_plan_tour(self.h, None, n_targets, start[0], start[1]))
+            self._chk(self.L.yh_scene_plan_tour_conn(self.h, None, n_targets, start[0], start[1], connectivity))
         else:
             t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
-            self._chk(self.L.yh_scene_plan_tour(self.h, _p(t), len(t), start[0], start[1]))
+            self._chk(self.L.yh_scene_plan_tour_conn(self.h, _p(t), len(t), start[0], start[1], connectivity))
 
     def read_tour(self, fields=False):
         """The last tour: targets int32 [K][2], order int32 [K] (indices into targets), legs f32 [K + 1][K] (row 0 from the start,

@@ -3,19 +3,42 @@ rounds and tile executions, for a camera-like frame (robots + balls, planned to 
 the serpentine maze of tests/path_ref.py (a geodesic that crosses the frame 60 times). Per case: one warm-up plan, then `sets`
 repetitions of yh_scene_plan_time(reps) (device events around whole plans, the host's counter reads inside) and the host's own wall
 clock around Scene.plan(); the scene back-end's time per frame beside it.
-Usage: python tools/time_path.py [sets] [reps]"""
-import os, socket, sys, time
+Usage: python tools/time_path.py [sets] [reps] [--connectivity 4|8] [--lib <other libyolact_hip.so>]
+--lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
+LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box; a build without
+yh_scene_plan_conn plans through yh_scene_plan (connectivity 4 only)."""
+import ctypes, os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import yolact_amd as ya
+from yolact_amd import capi
 import path_ref as R
-sets = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+args, conn, lib = [], 4, None
+it = iter(sys.argv[1:])
+for a in it:
+    if a == "--connectivity": conn = int(next(it))
+    elif a == "--lib": lib = os.path.abspath(next(it))
+    else: args.append(a)
+sets = int(args[0]) if len(args) > 0 else 5
+reps = int(args[1]) if len(args) > 1 else 20
+if lib:
+    capi.lib_path = lambda: lib
+has_conn = hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_plan_conn")
+if not has_conn:
+    assert conn == 4, "this build has no yh_scene_plan_conn"
+    capi.SYMBOLS = [s for s in capi.SYMBOLS if not s[0].endswith("_conn")]
+import yolact_amd as ya
 H, W = 480, 640
-print(f"box {socket.gethostname()}, {ya.version()}")
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, connectivity {conn}")
 sc = ya.Scene(W, H)
+
+
+def plan_on(targets, start):
+    if has_conn:
+        return sc.plan(targets=targets, start=start, connectivity=conn)
+    t = None if targets is None else np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+    sc._chk(sc.L.yh_scene_plan(sc.h, None if t is None else t.ctypes.data_as(ctypes.c_void_p), 3 if t is None else len(t), start[0], start[1]))
 
 
 def report(name, plan):
@@ -26,7 +49,7 @@ def report(name, plan):
     for _ in range(sets):
         t0 = time.perf_counter(); plan(); wall.append((time.perf_counter() - t0) * 1e3)
     ms = sorted(r["ms_per_plan"] for r in runs)
-    print(f"plan 640x480, {name}: {ms[len(ms) // 2]:.3f} ms per plan (median of {sets} x {reps}; min {ms[0]:.3f}, max {ms[-1]:.3f}), "
+    print(f"plan 640x480, {conn}-connected, {name}: {ms[len(ms) // 2]:.3f} ms per plan (median of {sets} x {reps}; min {ms[0]:.3f}, max {ms[-1]:.3f}), "
           f"host wall per Scene.plan() {sorted(wall)[len(wall) // 2]:.3f} ms, {runs[0]['rounds']} rounds, {runs[0]['tile_runs']} tile runs, "
           f"route of {len(out['path'])} nodes")
 
@@ -38,7 +61,7 @@ ci[100:220, 150:330, 0] = 1; ci[260:330, 380:520, 0] = 2; ci[60:75, 60:80] = (3,
 sc.append(depth, ci, ya.COMPAT_SANE)
 print(f"scene 640x480, robots + balls: {sc.time(30):.3f} ms per frame")
 sc.append(depth, ci, ya.COMPAT_SANE)
-report("camera-like frame, 2 balls", lambda: sc.plan())
+report("camera-like frame, 2 balls", lambda: plan_on(None, (400, 479)))
 hmap, start, target = R.serpentine(H, W)
 sc.set_fields(hmap, *R.sane_connections(hmap))
-report("serpentine maze, 1 target", lambda: sc.plan(targets=[target], start=start))
+report("serpentine maze, 1 target", lambda: plan_on([target], start))

@@ -3,11 +3,12 @@
 milliseconds per tour, solver rounds and tile executions (median of `sets` x yh_scene_tour_time(reps); the maze with reps / 4),
 and beside them what a host had to do before: K single-target yh_scene_plan calls one after the other (the sum of their medians by
 yh_scene_plan_time; the read-backs and the stitching a host would add are NOT in it).
-    python tools/time_tour.py [sets = 5] [reps = 20]
-    python tools/time_tour.py --ab <other libyolact_hip.so> [passes = 2] [sets] [reps]
+    python tools/time_tour.py [--connectivity 4|8] [sets = 5] [reps = 20]
+    python tools/time_tour.py [--connectivity 4|8] --ab <other libyolact_hip.so> [passes = 2] [sets] [reps]
+--connectivity 8: the tours and the single-target plans beside them on the 8-connected grid (DESIGN.md §11 "Diagonals").
 --ab alternates this build and another one (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
 LIBDIR=lib_old` in a checkout of it) process by process on one box; the other build need not have the tour: it runs the
-sequential plans only."""
+sequential plans only. A build without the _conn entry points runs with connectivity 4 only, through yh_scene_plan(_tour)."""
 import json, os, socket, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +24,7 @@ def median(xs):
     return sorted(xs)[len(xs) // 2]
 
 
-def child(lib, sets, reps):
+def child(lib, sets, reps, conn):
     """One process, one build: a JSON line per (case, K)."""
     from yolact_amd import capi
     import path_ref as R
@@ -34,8 +35,19 @@ def child(lib, sets, reps):
     has_tour = hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_plan_tour")
     if not has_tour:
         capi.SYMBOLS = [s for s in capi.SYMBOLS if "tour" not in s[0]]
+    has_conn = hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_plan_conn")
+    if not has_conn:
+        assert conn == 4, "this build has no yh_scene_plan_conn"
+        capi.SYMBOLS = [s for s in capi.SYMBOLS if not s[0].endswith("_conn")]
     import yolact_amd as ya
     sc = ya.Scene(W, H)
+
+    def plan(entry, targets, start):   # Scene.plan / Scene.plan_tour, or on a build without connectivity the entry point it has
+        if has_conn:
+            return (sc.plan_tour if entry == "yh_scene_plan_tour" else sc.plan)(targets=targets, start=start, connectivity=conn)
+        t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+        sc._chk(getattr(sc.L, entry)(sc.h, t.ctypes.data_as(ctypes.c_void_p), len(t), start[0], start[1]))
+
     hmap, end0, end1 = R.serpentine(H, W)
     MAZE["targets"][:2] = [end0, end1]
     for name, case, r in (("camera", CAMERA, reps), ("maze", MAZE, max(1, reps // 4))):
@@ -45,14 +57,14 @@ def child(lib, sets, reps):
             sc.set_fields(hmap, *R.sane_connections(hmap))
         single = []
         for t in case["targets"]:
-            sc.plan(targets=[t], start=case["start"])                             # warm-up: buffers, code objects
+            plan("yh_scene_plan", [t], case["start"])                             # warm-up: buffers, code objects
             runs = [sc.plan_time(r) for _ in range(sets)]
             single.append(dict(ms=median([x["ms_per_plan"] for x in runs]), rounds=runs[0]["rounds"], tile_runs=runs[0]["tile_runs"]))
         for K in KS:
-            row = dict(box=socket.gethostname(), case=name, K=K, seq_ms=sum(s["ms"] for s in single[:K]), seq_rounds=[s["rounds"] for s in single[:K]],
+            row = dict(box=socket.gethostname(), case=name, conn=conn, K=K, seq_ms=sum(s["ms"] for s in single[:K]), seq_rounds=[s["rounds"] for s in single[:K]],
                        seq_tile_runs=sum(s["tile_runs"] for s in single[:K]))
             if has_tour:
-                sc.plan_tour(targets=case["targets"][:K], start=case["start"])
+                plan("yh_scene_plan_tour", case["targets"][:K], case["start"])
                 out = sc.read_tour()
                 runs = [sc.tour_time(r) for _ in range(sets)]
                 ms = sorted(x["ms_per_tour"] for x in runs)
@@ -64,28 +76,33 @@ def child(lib, sets, reps):
 def show(tag, row):
     tour = (f"tour {row['tour_ms']:.3f} ms ({row['tour_min']:.3f}-{row['tour_max']:.3f}), {row['rounds']} rounds, {row['tile_runs']} tile runs, "
             f"order {row['order']}, route of {row['route']} nodes | ") if "tour_ms" in row else ""
-    print(f"{tag}{row['case']:6s} K={row['K']}: {tour}{row['K']} single-target plans one by one {row['seq_ms']:.3f} ms, rounds {row['seq_rounds']}, "
+    print(f"{tag}{row['case']:6s} {row['conn']}-connected K={row['K']}: {tour}{row['K']} single-target plans one by one {row['seq_ms']:.3f} ms, rounds {row['seq_rounds']}, "
           f"{row['seq_tile_runs']} tile runs", flush=True)
 
 
-def run_child(lib, sets, reps):
-    out = subprocess.run([sys.executable, __file__, "--child", lib, str(sets), str(reps)], capture_output=True, text=True, check=True).stdout
+def run_child(lib, sets, reps, conn):
+    out = subprocess.run([sys.executable, __file__, "--child", lib, str(sets), str(reps), str(conn)], capture_output=True, text=True, check=True).stdout
     return [json.loads(l) for l in out.splitlines() if l.startswith("{")]
 
 
 if __name__ == "__main__":
     a = sys.argv[1:]
+    conn = 4
+    if "--connectivity" in a:
+        i = a.index("--connectivity")
+        conn = int(a[i + 1])
+        del a[i:i + 2]
     if a and a[0] == "--child":
-        child(a[1], int(a[2]), int(a[3]))
+        child(a[1], int(a[2]), int(a[3]), int(a[4]))
     elif a and a[0] == "--ab":
         other = os.path.abspath(a[1])
         passes = int(a[2]) if len(a) > 2 else 2
         sets, reps = (int(a[3]) if len(a) > 3 else 5), (int(a[4]) if len(a) > 4 else 20)
         for r in range(passes):
             for tag, lib in (("this ", ""), ("other", other)):
-                for row in run_child(lib, sets, reps):
+                for row in run_child(lib, sets, reps, conn):
                     show(f"pass {r} {tag} [{row['box']}] ", row)
     else:
         sets, reps = (int(a[0]) if a else 5), (int(a[1]) if len(a) > 1 else 20)
-        for row in run_child("", sets, reps):
+        for row in run_child("", sets, reps, conn):
             show(f"[{row['box']}] ", row)
