@@ -275,6 +275,34 @@ int yh_num_priors(const yh_engine* h);
 /* Copies the P x 4 prior table (cx,cy,w,h) to host memory. */
 int yh_read_priors(const yh_engine* h, float* dst_host, size_t nfloats);
 
+/* ---- instance frame: the detections of the last yh_evaluate painted for the scene (DESIGN.md section 11 "Instance frame") -----
+ * What the reference's stop-gap stands in for (src/yolact.rs:1-5 "shoddy replacements", :108 "TODO differentiate between
+ * instances", :126 "TODO use confidence to shape mask"; pt_cloud.comp:119): frame `frame` of the last batch, its detections in the
+ * rank order yh_read_detections returns, rasterised on the device into a width x height frame of class << 24 | id << 16 (low 16 bits
+ * zero) - the layout yh_scene_append_classified(.., frame_on_device = 1, YH_COMPAT_SANE) reads.
+ *   class_map  u8 [num_classes - 1], every value 0 .. 3: foreground class -> the scene's class (0 terrain, 1 red robot, 2 blue robot,
+ *              3 ball); NULL: the reference's model, 0 -> 1, 1 -> 2, 2 -> 3, everything else 0 (yolact.rs:99-101, :113-115).
+ *   eligible   class_map[class_id] != 0 and score >= min_score; any other detection paints nothing and occludes nothing.
+ *   id         the number of eligible detections of the same output class with smaller rank (ball 0 is the most confident ball);
+ *              an occluded detection keeps its id.
+ *   mask       the binary mask (Hp x Wp) resized bilinearly with half-pixel centres and thresholded at > 0.5, in exact integers:
+ *              nx = max((2x+1) Wp - W, 0), u0 = nx div 2W, fx = nx mod 2W, u1 = min(u0 + 1, Wp - 1), the same along y; S = (2W-fx)
+ *              (2H-fy) M[v0][u0] + fx (2H-fy) M[v0][u1] + (2W-fx) fy M[v1][u0] + fx fy M[v1][u1]; on iff S > 2 W H (a tie is off).
+ *   pixel      the value of the eligible detection of smallest rank whose resized mask is on there, or 0.
+ * Synchronous, as yh_classify_frame_u32 is: on return the device frame and the instance table are complete (a scene handle on
+ * another stream may read the frame), and out_host, if not NULL, holds the width * height pixels. YH_ESTATE: the handle's last step
+ * was not a yh_evaluate (nothing run, yh_invoke only, or new input set since); YH_EINVAL: frame outside the last batch, a size outside
+ * 1 .. 4096, a class_map value above 3, a NaN min_score. A refused call has touched nothing: an earlier instance frame stays
+ * readable. The buffers are allocated at the first call, only grow, and are freed by yh_destroy. */
+int yh_instance_frame(yh_engine* h, int32_t frame, int32_t width, int32_t height, const uint8_t* class_map, float min_score,
+                      uint32_t* out_host /* or NULL */);
+/* Device copy of the last instance frame (NULL before one); valid until the next yh_instance_frame on the handle. */
+const uint32_t* yh_instance_device_frame(const yh_engine* h);
+/* The instance table of the last instance frame: i32 [m][4] = (detection rank, output class, id, pixels won), one row per eligible
+ * detection in rank order, rows with 0 pixels included. *n_instances = m; table may be NULL (the count alone). YH_EOVERFLOW (the
+ * count set, nothing copied) if capacity < m rows; YH_ESTATE before an instance frame. */
+int yh_instance_read(yh_engine* h, int32_t* n_instances, int32_t* table, int32_t capacity);
+
 /* ---- reference-compat path: Yolact::classify (src/yolact.rs:39-41, :192-234) --------------- */
 
 /* In-place classify of one packed camera frame: `frame` holds width*height u32 pixels packed

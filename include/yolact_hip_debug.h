@@ -216,6 +216,14 @@ int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int3
 int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask,
                  const uint16_t* proto, int32_t n);
 
+/* The instance frame (yh_instance_frame) on caller-provided detections: n <= max_dets binary masks u8 [n][hp][wp] (hp, wp in
+ * 1 .. 4096), class ids i32 [n] (0 .. num_classes - 2) and scores f32 [n] in rank order, all in host memory; the same kernels run,
+ * so the definition can be checked at tiny shapes without a network. out_host: width * height pixels; table / table_capacity /
+ * n_instances as yh_instance_read (which, like yh_instance_device_frame, then shows this frame). */
+int yh_op_instance_frame(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
+                         int32_t width, int32_t height, const uint8_t* class_map, float min_score, uint32_t* out_host, int32_t* table,
+                         int32_t table_capacity, int32_t* n_instances);
+
 #ifdef __cplusplus
 }
 #endif

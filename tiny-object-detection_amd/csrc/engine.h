@@ -1,6 +1,6 @@
 // engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
 // Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
-// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*). DESIGN.md section 4 says what each may see.
+// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -172,6 +172,17 @@ struct yh_engine {
     uint32_t* stitch_dev = nullptr;
     int* diverged_dev = nullptr;
     size_t frame_cap = 0, rs_tmp_cap = 0;
+    // instance frame (instance.hip): allocated at the first yh_instance_frame, grow only
+    bool dets_valid = false;        // the handle's last step was a yh_evaluate: det holds that batch's detections
+    uint4* inst_bits = nullptr;     // [hp * wp] 128-bit sets at prototype resolution
+    uint32_t* inst_frame = nullptr; // [height][width] class << 24 | id << 16
+    uint32_t* inst_meta = nullptr;  // [2][128]: packed value per rank (0: not eligible), pixels won per rank
+    uint8_t* inst_cmap = nullptr;   // [C - 1] the call's class map
+    size_t inst_bits_cap = 0, inst_frame_cap = 0;
+    std::vector<uint8_t> inst_cmap_host;
+    uint32_t inst_meta_host[256] = {};   // where inst_meta is read back to (a member: the copy is asynchronous)
+    std::vector<int32_t> inst_table;   // [inst_rows][4] = (rank, class, id, pixels) of the last instance frame
+    int inst_rows = -1;             // -1: no instance frame yet
     // output staging
     float* out_f32 = nullptr;
     size_t out_f32_cap = 0;
@@ -232,6 +243,11 @@ int alloc_panels(yh_engine* h);
 int check_blob(yh_engine* h, const uint8_t* b, size_t nbytes);
 int upload_panels(yh_engine* h, const uint8_t* blob);
 int ensure_blob(yh_engine* h);
+// instance.hip
+const char* instance_check(int width, int height, const uint8_t* class_map, int ncls, float min_score);   // nullptr: fine
+int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
+                 int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host);
+void instance_free(yh_engine* h);
 // fp8.hip
 void plan_fp8(yh_engine* h);
 std::string fp8_missing(const yh_engine* h);

@@ -1062,6 +1062,7 @@ int capture_step(yh_engine* h, int n, int with_tail, hipGraphExec_t* out) {
 namespace yh {
 
 int run(yh_engine* h, int with_tail) {
+    h->dets_valid = false;
     if (!h->weights_loaded) return h->fail(YH_ESTATE, "weights not loaded");
     if (h->cur_n < 1) return h->fail(YH_ESTATE, "no input set");
     if (h->cfg.precision == YH_PRECISION_FP8 && !h->fp8_ready) {
@@ -1077,6 +1078,7 @@ int run(yh_engine* h, int with_tail) {
     if (!h->cfg.use_graph) {
         rc = enqueue_all(h, n, with_tail);
         if (rc) { hipStreamSynchronize(h->stream); hipStreamSynchronize(h->side); hipMemset(h->det.cls_count, 0, sizeof(int) * (size_t)h->cfg.max_batch * (h->C - 1)); }
+        h->dets_valid = rc == YH_OK && with_tail;
         return rc;
     }
     const int key = (n * 2 + (with_tail ? 1 : 0)) * 2 + h->in_cur;
@@ -1098,6 +1100,7 @@ int run(yh_engine* h, int with_tail) {
         it = h->graphs.find(key);
     }
     HIPCHK(h, hipGraphLaunch(it->second, h->stream));
+    h->dets_valid = with_tail != 0;
     return YH_OK;
 }
 
@@ -1241,6 +1244,7 @@ void yh_destroy(yh_engine* h) {
     for (const DevAlloc& a : h->allocs) hipFree(a.p);
     if (h->out_f32) hipFree(h->out_f32);
     if (h->frame_dev) hipFree(h->frame_dev);
+    instance_free(h);
     if (h->rs_tmp) hipFree(h->rs_tmp);
     if (h->cells_dev) hipFree(h->cells_dev);
     if (h->codes_dev) hipFree(h->codes_dev);
@@ -1332,6 +1336,7 @@ static int set_input(yh_engine* h, const uint8_t* src, int n, hipMemcpyKind kind
     h->in_cur = nb;
     h->in_pending = true;
     h->cur_n = n;
+    h->dets_valid = false;   // (yh_instance_frame: the detections are no longer those of the frames set)
     return YH_OK;
 }
 int yh_set_input_u8(yh_engine* h, const uint8_t* rgb_host, int32_t n) { return set_input(h, rgb_host, n, hipMemcpyHostToDevice); }

@@ -29,6 +29,7 @@ int yh_debug_set_cu_mask(yh_engine* h, const uint32_t* mask, int32_t n_words) {
 int yh_debug_run_phase(yh_engine* h, int32_t phase, int32_t reps, float* ms_total) {
     if (!h || reps < 1 || (phase != 0 && phase != 1)) return YH_EINVAL;
     if (!h->weights_loaded || h->cur_n < 1) return h->fail(YH_ESTATE, "weights and an input first");
+    h->dets_valid = false;
     HIPCHK(h, hipSetDevice(h->dev));
     int rc = wait_input(h);
     if (rc) return rc;
@@ -257,6 +258,7 @@ int yh_profile_launch_count(const yh_engine* h, int32_t with_tail) {
 int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, double* flops, double* bytes, const char** names) {
     if (!h || !ms || reps < 1) return YH_EINVAL;
     if (!h->weights_loaded || h->cur_n < 1) return h->fail(YH_ESTATE, "weights and input must be set");
+    h->dets_valid = false;
     HIPCHK(h, hipSetDevice(h->dev));
     const int n = h->cur_n;
     std::vector<ProfEntry> ent;

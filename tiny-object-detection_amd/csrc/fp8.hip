@@ -205,6 +205,7 @@ int yh_fp8_calibrate(yh_engine* h) {
     for (int sid : sids) if (h->act[sid].c > MC) return h->fail(YH_EINVAL, "fp8 input tensor with more than 512 channels");
     std::vector<unsigned> bits((size_t)MT * MC);
     h->fp8_active = false;
+    h->dets_valid = false;
     const int rc = [&]() -> int {
         int r = wait_input(h);
         if (r) return r;

@@ -74,6 +74,26 @@ std::vector<std::vector<float>> Yolact::classify_tile_outputs(const std::uint8_t
     return results;
 }
 
+void Yolact::evaluate(const std::uint8_t* rgb_frames, int n) {
+    if (!engine_) expect_failed("evaluate", "the detection tail belongs to the YOLACT engine");
+    if (yh_set_input_u8(engine_, rgb_frames, n) != YH_OK) expect_failed("must data", yh_last_error(engine_));   // :161-162
+    if (yh_evaluate(engine_) != YH_OK) expect_failed("invoke failed", yh_last_error(engine_));                  // :163
+}
+
+std::vector<std::int32_t> Yolact::instance_frame(int frame, int width, int height, const std::uint8_t* class_map, float min_score,
+                                                 std::uint32_t* frame_out) {
+    if (!engine_) expect_failed("instance_frame", "the detection tail belongs to the YOLACT engine");
+    if (yh_instance_frame(engine_, frame, width, height, class_map, min_score, frame_out) != YH_OK)
+        expect_failed("instance frame failed", yh_last_error(engine_));
+    std::int32_t m = 0;
+    if (yh_instance_read(engine_, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    std::vector<std::int32_t> table(static_cast<std::size_t>(m) * 4);
+    if (yh_instance_read(engine_, &m, table.data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    return table;
+}
+
+const std::uint32_t* Yolact::instance_device_frame() const { return engine_ ? yh_instance_device_frame(engine_) : nullptr; }
+
 // ---- YolactGroup ---------------------------------------------------------------------------------------------------
 YolactGroup YolactGroup::init(const GroupOptions& opt) {
     YolactGroup y;

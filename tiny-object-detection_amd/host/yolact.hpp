@@ -47,6 +47,18 @@ public:
     // (:166-188) and returns them; results[4] is what postprocess reads (:91).
     std::vector<std::vector<float>> classify_tile_outputs(const std::uint8_t* rgb_tile);
 
+    // The fused path on the YOLACT engine (absent in the reference, yolact.rs:3-5): n <= 2 frames of u8 RGB [n][S][S][3] through
+    // the network and the detection tail (yh_set_input_u8 + yh_evaluate) ...
+    void evaluate(const std::uint8_t* rgb_frames, int n);
+    // ... and frame `frame` of that batch painted as width x height pixels of class << 24 | id << 16 on the device
+    // (yh_instance_frame: what yolact.rs:108 "TODO differentiate between instances" asks for). class_map: one value 0..3 per
+    // foreground class, or nullptr for the reference's model; frame_out: width * height pixels, or nullptr to leave the frame on the
+    // device (instance_device_frame() -> yh_scene_append_classified(.., 1, YH_COMPAT_SANE)). Returns the instance table, four
+    // values per eligible detection: rank, output class, id, pixels won.
+    std::vector<std::int32_t> instance_frame(int frame, int width, int height, const std::uint8_t* class_map = nullptr,
+                                             float min_score = 0.0f, std::uint32_t* frame_out = nullptr);
+    const std::uint32_t* instance_device_frame() const;
+
     static std::string version();      // edgetpu::version(), scene.rs:62
 
 private:

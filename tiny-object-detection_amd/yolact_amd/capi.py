@@ -158,6 +158,9 @@ SYMBOLS = [
     ("yh_scene_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
+    ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
+    ("yh_instance_device_frame", _vp, [_vp]),
+    ("yh_instance_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_last_conv_launches", _i, [_vp]),
@@ -178,6 +181,7 @@ SYMBOLS = [
     ("yh_op_bilinear_f16", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     ("yh_op_maxpool3x3s2_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     ("yh_op_detect", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    ("yh_op_instance_frame", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, C.POINTER(_i)]),
 ]
 
 
@@ -440,6 +444,52 @@ class Engine:
 
     def flops_per_frame(self):
         return self.L.yh_flops_per_frame(self.h)
+
+    # ---- instance frame (DESIGN.md §11 "Instance frame")
+    def _class_map(self, class_map):
+        if class_map is None:
+            return None
+        cm = np.ascontiguousarray(class_map, np.uint8)
+        assert cm.shape == (self.cfg.num_classes - 1,), "class_map: one value per foreground class"
+        return cm
+
+    def instance_frame(self, frame, width, height, class_map=None, min_score=0.0, read=True):
+        """yh_instance_frame: the detections of frame `frame` of the last evaluate painted into a height x width uint32 frame of
+        class << 24 | id << 16 on the device (instance_device_frame; the table: instances). class_map: uint8 [num_classes - 1] with
+        values 0..3, None: the reference's model (foreground 0, 1, 2 -> 1, 2, 3). read=False leaves the frame on the device."""
+        cm = self._class_map(class_map)
+        out = np.zeros((height, width), np.uint32) if read else None
+        self._chk(self.L.yh_instance_frame(self.h, frame, width, height, _p(cm) if cm is not None else None, C.c_float(min_score),
+                                           _p(out) if read else None))
+        return out
+
+    def instance_device_frame(self):
+        """Device pointer of the last instance frame (for Scene.append_classified(..., mode=COMPAT_SANE)); None before one."""
+        return self.L.yh_instance_device_frame(self.h)
+
+    def instances(self):
+        """The last instance frame's table: int32 [m][4] = (detection rank, output class, id, pixels won)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_instance_read(self.h, C.byref(n), None, 0))
+        t = np.zeros((n.value, 4), np.int32)
+        self._chk(self.L.yh_instance_read(self.h, C.byref(n), _p(t), n.value))
+        return t
+
+    def op_instance_frame(self, masks, class_ids, scores, width, height, class_map=None, min_score=0.0):
+        """yh_op_instance_frame: the instance frame's kernels on caller-provided masks uint8 [n][hp][wp], class ids and scores in
+        rank order. Returns (frame uint32 [height][width], table int32 [m][4])."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        n, hp, wp = masks.shape
+        ids = np.ascontiguousarray(class_ids, np.int32).reshape(n)
+        sc = np.ascontiguousarray(scores, np.float32).reshape(n)
+        cm = self._class_map(class_map)
+        out = np.zeros((height, width), np.uint32)
+        table = np.zeros((self.cfg.max_dets, 4), np.int32)
+        m = C.c_int32()
+        self._chk(self.L.yh_op_instance_frame(self.h, _p(masks), _p(ids), _p(sc), n, hp, wp, width, height,
+                                              _p(cm) if cm is not None else None, C.c_float(min_score), _p(out), _p(table),
+                                              len(table), C.byref(m)))
+        return out, table[:m.value].copy()
 
     # ---- reference-compat path
     def classify_device_frame(self):
