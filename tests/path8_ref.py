@@ -1,139 +1,11 @@
-"""The planner on the 8-connected grid (DESIGN.md §11 "Diagonals"), restated on the CPU for tests/test_scene_path8.py on top of
-path_ref: the same pixels, equation and association, fl(fl(d[u] + c(v,u)) + |h[v] - h[u]|), the minimum over up to eight neighbours.
-
-Edge lengths of v = (x, y), layouts of Scene.read(): the four straight ones as path_ref has them, up-left conn1[y,x,3], up-right
-conn0[y,x,1], down-left conn1[y,x,1], down-right conn0[y,x,3]; off-frame entries are never edges. Neighbour order: left, right,
-up, down, up-left, up-right, down-left, down-right (path_ref's order is a prefix: ties prefer straight moves). A SANE diagonal is
-sqrt((1 + dy^2) + 1) >= sqrt(2) >= 1, so path_ref's uniqueness argument carries over and two solvers give the same bits.
-Rotations: with k in 0 .. 4 the number of 45-degree steps between the heading into a node and the heading out of it,
-float32((4 - k) * pi / 4)."""
-import heapq
-
+"""What is specific to the diagonals (DESIGN.md §11 "Diagonals") in the CPU restatement for tests/test_scene_path8.py; the planner itself,
+for either connectivity, is path_ref's: fields built from one length per edge, a synchronous emulation of the device solver's tile
+rounds, and the constructed fields on which a solver without the corner rule stops early."""
 import numpy as np
 
 import path_ref as R
 
 INF = R.INF
-# (dx, dy) of the neighbour u of v, in the successor's order
-STEPS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, -1), (-1, 1), (1, 1))
-ROT = tuple(np.float32((4 - k) * np.pi / 4) for k in range(5))      # pi, 3 pi / 4, pi / 2, pi / 4, 0
-_COMPASS = {(1, 0): 0, (1, 1): 1, (0, 1): 2, (-1, 1): 3, (-1, 0): 4, (-1, -1): 5, (0, -1): 6, (1, -1): 7}
-
-
-def _lengths(conn0, conn1):
-    """The length of v's edge towards each of its eight neighbours, in the order of STEPS."""
-    return (conn1[..., 2], conn0[..., 2], conn0[..., 0], conn1[..., 0], conn1[..., 3], conn0[..., 1], conn1[..., 1], conn0[..., 3])
-
-
-def _windows(H, W, dx, dy):
-    """(slices of v, slices of u = v + (dx, dy)) over the pixels v whose neighbour u lies in the frame."""
-    ys = slice(max(0, -dy), H - max(0, dy)), slice(max(0, dy), H - max(0, -dy))
-    xs = slice(max(0, -dx), W - max(0, dx)), slice(max(0, dx), W - max(0, -dx))
-    return (ys[0], xs[0]), (ys[1], xs[1])
-
-
-def candidates8(d, hmap, conn0, conn1):
-    """The eight candidates of every pixel, in the order of STEPS; +inf where the frame ends."""
-    H, W = d.shape
-    h = hmap.astype(np.float32)
-    out = []
-    for (dx, dy), c in zip(STEPS, _lengths(conn0, conn1)):
-        o = np.full(d.shape, INF, np.float32)
-        v, u = _windows(H, W, dx, dy)
-        o[v] = (d[u] + c[v]) + np.abs(h[v] - h[u])
-        assert o.dtype == np.float32
-        out.append(o)
-    return out
-
-
-def jacobi8(hmap, conn0, conn1, targets):
-    """Whole-grid sweeps to the fixed point; returns (d, sweeps)."""
-    t = R._target_mask(hmap.shape, targets)
-    d = np.where(t, np.float32(0), INF).astype(np.float32)
-    sweeps = 0
-    while True:
-        new = np.minimum.reduce([d] + candidates8(d, hmap, conn0, conn1))
-        new[t] = 0
-        sweeps += 1
-        if np.array_equal(new, d):
-            return d, sweeps
-        d = new
-
-
-def dijkstra8(hmap, conn0, conn1, targets):
-    """Heap Dijkstra from all targets; python floats that always hold f32 values."""
-    H, W = hmap.shape
-    h = hmap.astype(np.float32).ravel().tolist()
-    lens = [c.astype(np.float32).ravel().tolist() for c in _lengths(conn0, conn1)]
-    d = [float("inf")] * (H * W)
-    heap = []
-    for x, y in targets:
-        d[y * W + x] = 0.0
-        heap.append((0.0, y * W + x))
-    heapq.heapify(heap)
-    done = [False] * (H * W)
-    while heap:
-        du, u = heapq.heappop(heap)
-        if done[u]:
-            continue
-        done[u] = True
-        x, y = u % W, u // W
-        # relaxing v from u uses v's own edge towards u: v = u - step, for every step that leads from a pixel of the frame to u
-        for (dx, dy), c in zip(STEPS, lens):
-            vx, vy = x - dx, y - dy
-            if 0 <= vx < W and 0 <= vy < H:
-                v = vy * W + vx
-                cv = R._f32(R._f32(du + c[v]) + abs(h[v] - h[u]))
-                if cv < d[v]:
-                    d[v] = cv
-                    heapq.heappush(heap, (cv, v))
-    return np.array(d, np.float32).reshape(H, W)
-
-
-def equation_residual8(d, hmap, conn0, conn1, targets):
-    """Pixels at which d does NOT satisfy its defining equations (0 at targets, the minimum candidate elsewhere), bitwise."""
-    t = R._target_mask(d.shape, targets)
-    want = np.minimum.reduce(candidates8(d, hmap, conn0, conn1))
-    want[t] = 0
-    return int((want.view(np.uint32) != d.view(np.uint32)).sum())
-
-
-def successors8(d, hmap, conn0, conn1, targets):
-    """next[v]: linear index of the first neighbour (order of STEPS) whose candidate equals d[v] bitwise; -1 at targets."""
-    H, W = d.shape
-    idx = np.arange(H * W, dtype=np.int32).reshape(H, W)
-    nxt = np.full((H, W), -1, np.int32)
-    for c, (dx, dy) in reversed(list(zip(candidates8(d, hmap, conn0, conn1), STEPS))):
-        hit = (c.view(np.uint32) == d.view(np.uint32)) & np.isfinite(c)
-        nxt[hit] = idx[hit] + (dy * W + dx)
-    nxt[R._target_mask(d.shape, targets)] = -1
-    return nxt
-
-
-def rotation(before, at, after):
-    """rot at the node `at` between the steps before -> at and at -> after (each to one of the eight neighbours)."""
-    a = _COMPASS[(int(at[0] - before[0]), int(at[1] - before[1]))]
-    b = _COMPASS[(int(after[0] - at[0]), int(after[1] - at[1]))]
-    k = (a - b) % 8
-    return ROT[min(k, 8 - k)]
-
-
-def walk8(d, nxt, start):
-    """(path int32 [L][2] of (x, y) from start to a target, directions f32 [L-1][2] of (magnitude, rotation))."""
-    H, W = d.shape
-    node = start[1] * W + start[0]
-    nodes = [node]
-    while nxt.flat[node] >= 0:
-        node = int(nxt.flat[node])
-        nodes.append(node)
-        assert len(nodes) <= H * W
-    path = np.array([(n % W, n // W) for n in nodes], np.int32).reshape(-1, 2)
-    dirs = np.zeros((len(nodes) - 1, 2), np.float32)
-    for i in range(len(nodes) - 1):
-        dirs[i, 0] = d.flat[nodes[i]] - d.flat[nodes[i + 1]]
-        if i > 0:
-            dirs[i, 1] = rotation(path[i - 1], path[i], path[i + 1])
-    return path, dirs
 
 
 def fields_from_edges(Rt, D, DR, DL, hmap=None):
@@ -196,7 +68,7 @@ def tile_rounds(hmap, conn0, conn1, targets, T=32, corner_flags=True):
             iy, ix = slice(y0 - wy.start, y1 - wy.start), slice(x0 - wx.start, x1 - wx.start)          # the tile inside that window
             loc = snap[wy, wx].copy()
             while True:
-                new = np.minimum.reduce([loc] + candidates8(loc, hmap[wy, wx], conn0[wy, wx], conn1[wy, wx]))
+                new = np.minimum.reduce([loc] + R.candidates(loc, hmap[wy, wx], conn0[wy, wx], conn1[wy, wx], 8))
                 if np.array_equal(new[iy, ix], loc[iy, ix]):
                     break
                 loc[iy, ix] = new[iy, ix]                         # (the halo stays what the snapshot had)

@@ -5,7 +5,13 @@ fl(fl(d[u] + c(v,u)) + |h[v] - h[u]|) (path.rs:59's left-to-right sum).
 Fields are those of Scene.read(): map u32 [H][W], conn0 / conn1 f32 [H][W][4]. Edge lengths of v = (x, y): left conn1[y,x,2],
 right conn0[y,x,2], up conn0[y,x,0], down conn1[y,x,0]; off-frame entries are never edges. Neighbour order: left, right, up, down.
 Two independent solvers (a heap Dijkstra and whole-grid Jacobi sweeps) give the same bits: every c >= 1 makes fl(d + w) > d
-while d < 2^24, so the equations have one solution."""
+while d < 2^24, so the equations have one solution.
+
+Every function takes conn = 4 or 8, the grid's connectivity (DESIGN.md §11 "Diagonals"): with 8 the minimum is over up to eight
+neighbours, the order continues up-left conn1[y,x,3], up-right conn0[y,x,1], down-left conn1[y,x,1], down-right conn0[y,x,3] (the
+4-connected order is a prefix: ties prefer straight moves). A SANE diagonal is sqrt((1 + dy^2) + 1) >= sqrt(2) >= 1, so the
+uniqueness argument carries over. Rotations: with k in 0 .. 4 the number of 45-degree steps between the heading into a node and the
+heading out of it, float32((4 - k) * pi / 4): pi straight on, pi / 2 for a right angle (all a 4-connected route has)."""
 import ctypes
 import heapq
 
@@ -13,6 +19,10 @@ import numpy as np
 
 INF = np.float32(np.inf)
 PI, HALF_PI = np.float32(np.pi), np.float32(np.pi / 2)
+# (dx, dy) of the neighbour u of v, in the successor's order; the first conn of them are the grid's
+STEPS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, -1), (-1, 1), (1, 1))
+ROT = tuple(np.float32((4 - k) * np.pi / 4) for k in range(5))      # pi, 3 pi / 4, pi / 2, pi / 4, 0
+_COMPASS = {(1, 0): 0, (1, 1): 1, (0, 1): 2, (-1, 1): 3, (-1, 0): 4, (-1, -1): 5, (0, -1): 6, (1, -1): 7}
 
 
 def size_ok(W, H):
@@ -42,19 +52,29 @@ def sane_connections(hmap):
     return conn0, conn1
 
 
-def _edges(hmap, conn0, conn1):
-    return hmap.astype(np.float32), conn1[..., 2], conn0[..., 2], conn0[..., 0], conn1[..., 0]
+def _lengths(conn0, conn1):
+    """The length of v's edge towards each of its eight neighbours, in the order of STEPS."""
+    return (conn1[..., 2], conn0[..., 2], conn0[..., 0], conn1[..., 0], conn1[..., 3], conn0[..., 1], conn1[..., 1], conn0[..., 3])
 
 
-def candidates(d, hmap, conn0, conn1):
-    """The four candidates of every pixel, in the order left, right, up, down; +inf where the frame ends."""
-    h, cl, cr, cu, cd = _edges(hmap, conn0, conn1)
-    out = [np.full(d.shape, INF, np.float32) for _ in range(4)]
-    out[0][:, 1:] = (d[:, :-1] + cl[:, 1:]) + np.abs(h[:, 1:] - h[:, :-1])
-    out[1][:, :-1] = (d[:, 1:] + cr[:, :-1]) + np.abs(h[:, :-1] - h[:, 1:])
-    out[2][1:, :] = (d[:-1, :] + cu[1:, :]) + np.abs(h[1:, :] - h[:-1, :])
-    out[3][:-1, :] = (d[1:, :] + cd[:-1, :]) + np.abs(h[:-1, :] - h[1:, :])
-    assert all(o.dtype == np.float32 for o in out)
+def _windows(H, W, dx, dy):
+    """(slices of v, slices of u = v + (dx, dy)) over the pixels v whose neighbour u lies in the frame."""
+    ys = slice(max(0, -dy), H - max(0, dy)), slice(max(0, dy), H - max(0, -dy))
+    xs = slice(max(0, -dx), W - max(0, dx)), slice(max(0, dx), W - max(0, -dx))
+    return (ys[0], xs[0]), (ys[1], xs[1])
+
+
+def candidates(d, hmap, conn0, conn1, conn=4):
+    """The conn candidates of every pixel, in the order of STEPS; +inf where the frame ends."""
+    H, W = d.shape
+    h = hmap.astype(np.float32)
+    out = []
+    for (dx, dy), c in zip(STEPS[:conn], _lengths(conn0, conn1)):
+        o = np.full(d.shape, INF, np.float32)
+        v, u = _windows(H, W, dx, dy)
+        o[v] = (d[u] + c[v]) + np.abs(h[v] - h[u])
+        assert o.dtype == np.float32
+        out.append(o)
     return out
 
 
@@ -65,13 +85,13 @@ def _target_mask(shape, targets):
     return m
 
 
-def jacobi(hmap, conn0, conn1, targets):
+def jacobi(hmap, conn0, conn1, targets, conn=4):
     """Whole-grid sweeps to the fixed point; returns (d, sweeps)."""
     t = _target_mask(hmap.shape, targets)
     d = np.where(t, np.float32(0), INF).astype(np.float32)
     sweeps = 0
     while True:
-        new = np.minimum.reduce([d] + candidates(d, hmap, conn0, conn1))
+        new = np.minimum.reduce([d] + candidates(d, hmap, conn0, conn1, conn))
         new[t] = 0
         sweeps += 1
         if np.array_equal(new, d):
@@ -86,10 +106,11 @@ def _f32(x):   # a double sum of two f32 values, rounded to f32, is their f32 su
     return _c_float(x).value
 
 
-def dijkstra(hmap, conn0, conn1, targets):
+def dijkstra(hmap, conn0, conn1, targets, conn=4):
     """Heap Dijkstra from all targets; python floats that always hold f32 values."""
     H, W = hmap.shape
-    h, cl, cr, cu, cd = (a.astype(np.float32).ravel().tolist() for a in _edges(hmap, conn0, conn1))
+    h = hmap.astype(np.float32).ravel().tolist()
+    lens = [c.astype(np.float32).ravel().tolist() for c in _lengths(conn0, conn1)]
     d = [float("inf")] * (H * W)
     heap = []
     for x, y in targets:
@@ -103,52 +124,49 @@ def dijkstra(hmap, conn0, conn1, targets):
             continue
         done[u] = True
         x, y = u % W, u // W
-        # relaxing v from u uses v's own edge towards u: v right of u goes LEFT to reach u, and so on
-        if x + 1 < W:
-            v = u + 1
-            c = _f32(_f32(du + cl[v]) + abs(h[v] - h[u]))
-            if c < d[v]:
-                d[v] = c; heapq.heappush(heap, (c, v))
-        if x > 0:
-            v = u - 1
-            c = _f32(_f32(du + cr[v]) + abs(h[v] - h[u]))
-            if c < d[v]:
-                d[v] = c; heapq.heappush(heap, (c, v))
-        if y + 1 < H:
-            v = u + W
-            c = _f32(_f32(du + cu[v]) + abs(h[v] - h[u]))
-            if c < d[v]:
-                d[v] = c; heapq.heappush(heap, (c, v))
-        if y > 0:
-            v = u - W
-            c = _f32(_f32(du + cd[v]) + abs(h[v] - h[u]))
-            if c < d[v]:
-                d[v] = c; heapq.heappush(heap, (c, v))
+        # relaxing v from u uses v's own edge towards u: v = u - step, for every step that leads from a pixel of the frame to u
+        for (dx, dy), c in zip(STEPS[:conn], lens):
+            vx, vy = x - dx, y - dy
+            if 0 <= vx < W and 0 <= vy < H:
+                v = vy * W + vx
+                cv = _f32(_f32(du + c[v]) + abs(h[v] - h[u]))
+                if cv < d[v]:
+                    d[v] = cv
+                    heapq.heappush(heap, (cv, v))
     return np.array(d, np.float32).reshape(H, W)
 
 
-def equation_residual(d, hmap, conn0, conn1, targets):
+def equation_residual(d, hmap, conn0, conn1, targets, conn=4):
     """Pixels at which d does NOT satisfy its defining equations (0 at targets, the minimum candidate elsewhere), bitwise."""
     t = _target_mask(d.shape, targets)
-    want = np.minimum.reduce(candidates(d, hmap, conn0, conn1))
+    want = np.minimum.reduce(candidates(d, hmap, conn0, conn1, conn))
     want[t] = 0
     return int((want.view(np.uint32) != d.view(np.uint32)).sum())
 
 
-def successors(d, hmap, conn0, conn1, targets):
-    """next[v]: linear index of the first neighbour (left, right, up, down) whose candidate equals d[v] bitwise; -1 at targets."""
+def successors(d, hmap, conn0, conn1, targets, conn=4):
+    """next[v]: linear index of the first neighbour (order of STEPS) whose candidate equals d[v] bitwise; -1 at targets."""
     H, W = d.shape
     idx = np.arange(H * W, dtype=np.int32).reshape(H, W)
     nxt = np.full((H, W), -1, np.int32)
-    for c, off in reversed(list(zip(candidates(d, hmap, conn0, conn1), (-1, 1, -W, W)))):
+    for c, (dx, dy) in reversed(list(zip(candidates(d, hmap, conn0, conn1, conn), STEPS))):
         hit = (c.view(np.uint32) == d.view(np.uint32)) & np.isfinite(c)
-        nxt[hit] = idx[hit] + off
+        nxt[hit] = idx[hit] + (dy * W + dx)
     nxt[_target_mask(d.shape, targets)] = -1
     return nxt
 
 
-def walk(d, nxt, start):
-    """(path int32 [L][2] of (x, y) from start to a target, directions f32 [L-1][2] of (magnitude, rotation))."""
+def rotation(before, at, after):
+    """rot at the node `at` between the steps before -> at and at -> after (each to one of the eight neighbours)."""
+    a = _COMPASS[(int(at[0] - before[0]), int(at[1] - before[1]))]
+    b = _COMPASS[(int(after[0] - at[0]), int(after[1] - at[1]))]
+    k = (a - b) % 8
+    return ROT[min(k, 8 - k)]
+
+
+def walk(d, nxt, start, conn=4):
+    """(path int32 [L][2] of (x, y) from start to a target, directions f32 [L-1][2] of (magnitude, rotation)); every step is one of
+    the grid's first conn."""
     H, W = d.shape
     node = start[1] * W + start[0]
     nodes = [node]
@@ -160,9 +178,9 @@ def walk(d, nxt, start):
     dirs = np.zeros((len(nodes) - 1, 2), np.float32)
     for i in range(len(nodes) - 1):
         dirs[i, 0] = d.flat[nodes[i]] - d.flat[nodes[i + 1]]
+        assert tuple(int(v) for v in path[i + 1] - path[i]) in STEPS[:conn]
         if i > 0:
-            straight = (path[i - 1] + path[i + 1] == 2 * path[i]).all()
-            dirs[i, 1] = PI if straight else HALF_PI
+            dirs[i, 1] = rotation(path[i - 1], path[i], path[i + 1])
     return path, dirs
 
 

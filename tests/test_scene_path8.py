@@ -1,6 +1,6 @@
 """The planner and the tour on the 8-connected grid (yh_scene_plan_conn / yh_scene_plan_tour_conn with connectivity 8; DESIGN.md
-§11 "Diagonals"). CPU part: the restatement (tests/path8_ref.py) against itself - two solvers bit for bit -, closed forms, hand
-cases for every rotation constant, and the tile-round emulation that shows what a solver without the corner rule gets wrong.
+§11 "Diagonals"). CPU part: the restatement (tests/path_ref.py with conn=8, tests/path8_ref.py) against itself - two solvers bit for
+bit -, closed forms, hand cases for every rotation constant, and the tile-round emulation that shows what a solver without the corner rule gets wrong.
 GPU part (-m gpu): the HIP solver's fields bit-equal to the restatement on the engine's own scene fields and on constructed ones
 (the late corner among them), successors, routes, the tour, the life cycle and every error."""
 import os
@@ -52,31 +52,31 @@ def test_dijkstra8_equals_jacobi8_bit_for_bit():
     H, W = 40, 56
     f = _random_fields(rng, H, W)
     targets = [(5, 7), (50, 30)]
-    a = P.dijkstra8(*f, targets)
-    b, sweeps = P.jacobi8(*f, targets)
+    a = R.dijkstra(*f, targets, conn=8)
+    b, sweeps = R.jacobi(*f, targets, conn=8)
     assert np.array_equal(_bits(a), _bits(b)) and sweeps > 10
-    assert P.equation_residual8(a, *f, targets) == 0
+    assert R.equation_residual(a, *f, targets, conn=8) == 0
     c0, c1 = f[1], f[2]
     assert (c0[1:, :-1, 1] >= 1).all() and (c0[:-1, :-1, 3] >= 1).all()                       # every SANE diagonal is >= 1
     assert np.array_equal(c0[1:, :-1, 1], c1[:-1, 1:, 1]) and np.array_equal(c0[:-1, :-1, 3], c1[1:, 1:, 3])   # and symmetric
     d4 = R.dijkstra(*f, targets)                                                                # every 4-path is an 8-path
     assert (a <= d4).all() and (a < d4).sum() > H * W // 2
-    assert P.equation_residual8(d4, *f, targets) > 0 and R.equation_residual(a, *f, targets) > 0
+    assert R.equation_residual(d4, *f, targets, conn=8) > 0 and R.equation_residual(a, *f, targets) > 0
 
 
 def test_flat_map_diagonal_sums_and_the_tie_that_prefers_the_straight_move():
     f = T.flat_fields(5, 5)
-    d = P.dijkstra8(*f, [(0, 0)])
-    assert np.array_equal(_bits(d), _bits(P.jacobi8(*f, [(0, 0)])[0]))
+    d = R.dijkstra(*f, [(0, 0)], conn=8)
+    assert np.array_equal(_bits(d), _bits(R.jacobi(*f, [(0, 0)], conn=8)[0]))
     s = np.float32(0)
     for k in range(1, 5):
         s = np.float32(s + np.float32(np.sqrt(np.float32(2))))
         assert _bits(d[k, k]) == _bits(s)
     root2 = np.float32(np.sqrt(np.float32(2)))
     assert _bits(d[1, 2]) == _bits(np.float32(root2 + np.float32(1)))                          # d(2, 1): x = 2, y = 1
-    cands = P.candidates8(d, *f)
+    cands = R.candidates(d, *f, conn=8)
     assert _bits(cands[0][1, 2]) == _bits(d[1, 2]) and _bits(cands[4][1, 2]) == _bits(d[1, 2])  # left and up-left tie ...
-    nxt = P.successors8(d, *f, [(0, 0)])
+    nxt = R.successors(d, *f, [(0, 0)], conn=8)
     assert nxt[1, 2] == 1 * 5 + 1                                                              # ... and left wins
     assert nxt[0, 0] == -1 and nxt[3, 3] == 2 * 5 + 2
 
@@ -86,10 +86,10 @@ def test_three_nodes_by_hand_turn_by_135_degrees():
     goes east, then south-west: three 45-degree steps between the headings, rot_1 = float32(pi / 4)."""
     f = _route_fields(3, 3, [(0, 0), (1, 0), (0, 1)])
     assert f[2][0, 0, 0] == 100 and f[1][0, 0, 3] == 100 and f[1][0, 0, 2] == 1 and f[2][0, 1, 1] == 1
-    d = P.dijkstra8(*f, [(0, 1)])
+    d = R.dijkstra(*f, [(0, 1)], conn=8)
     assert d[0, 0] == 2 and d[0, 1] == 1
-    nxt = P.successors8(d, *f, [(0, 1)])
-    path, dirs = P.walk8(d, nxt, (0, 0))
+    nxt = R.successors(d, *f, [(0, 1)], conn=8)
+    path, dirs = R.walk(d, nxt, (0, 0), conn=8)
     assert path.tolist() == [[0, 0], [1, 0], [0, 1]]
     assert np.array_equal(_bits(dirs), _bits(np.array([[1, 0], [1, PI4]], np.float32)))
     assert float(PI4) == 0.7853981852531433
@@ -97,20 +97,31 @@ def test_three_nodes_by_hand_turn_by_135_degrees():
 
 def test_staircase_route_has_three_quarter_and_half_turns():
     f = _route_fields(6, 6, STAIRS)
-    d = P.dijkstra8(*f, [STAIRS[-1]])
-    path, dirs = P.walk8(d, P.successors8(d, *f, [STAIRS[-1]]), STAIRS[0])
+    d = R.dijkstra(*f, [STAIRS[-1]], conn=8)
+    path, dirs = R.walk(d, R.successors(d, *f, [STAIRS[-1]], conn=8), STAIRS[0], conn=8)
     assert path.tolist() == [list(p) for p in STAIRS]
     assert np.array_equal(_bits(dirs[:, 1]), _bits(np.array(STAIRS_ROT, np.float32))) and (dirs[:, 0] == 1).all()
-    assert [float(r) for r in P.ROT] == [float(PI), float(PI34), float(PI2), float(PI4), 0.0]
-    assert P.rotation((0, 0), (1, 0), (0, 0)) == 0 and P.rotation((0, 0), (1, 1), (2, 2)) == PI   # a reversal; straight on a diagonal
+    assert [float(r) for r in R.ROT] == [float(PI), float(PI34), float(PI2), float(PI4), 0.0]
+    assert R.rotation((0, 0), (1, 0), (0, 0)) == 0 and R.rotation((0, 0), (1, 1), (2, 2)) == PI   # a reversal; straight on a diagonal
 
 
 def test_walk8_on_a_four_connected_route_is_path_refs_walk():
+    """The rotation table on a route without diagonals, against the 4-connected rule written out: pi where the route goes straight
+    on, pi / 2 where it turns, 0 at step 0; the magnitudes are the cost differences."""
     f = _random_fields(np.random.default_rng(2), 20, 30)
     d = R.dijkstra(*f, [(3, 4)])
     nxt = R.successors(d, *f, [(3, 4)])
-    a, b = R.walk(d, nxt, (28, 17)), P.walk8(d, nxt, (28, 17))
-    assert np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    path, dirs = R.walk(d, nxt, (28, 17), conn=8)
+    assert tuple(path[0]) == (28, 17) and tuple(path[-1]) == (3, 4) and (np.abs(np.diff(path, axis=0)).sum(1) == 1).all()
+    assert np.array_equal(path[1:, 1] * 30 + path[1:, 0], nxt[path[:-1, 1], path[:-1, 0]])      # the walk follows next
+    straight = (path[:-2] + path[2:] == 2 * path[1:-1]).all(1)
+    assert straight.any() and not straight.all()
+    want = np.concatenate([[np.float32(0)], np.where(straight, PI, PI2)]).astype(np.float32)
+    assert np.array_equal(_bits(dirs[:, 1]), _bits(want))
+    cost = d[path[:, 1], path[:, 0]]
+    assert np.array_equal(_bits(dirs[:, 0]), _bits(cost[:-1] - cost[1:]))
+    four = R.walk(d, nxt, (28, 17))                                                             # and the default is the same walk
+    assert np.array_equal(four[0], path) and np.array_equal(_bits(four[1]), _bits(dirs))
 
 
 def test_late_corner_needs_the_corner_rule():
@@ -118,7 +129,7 @@ def test_late_corner_needs_the_corner_rule():
     without it it stops after 4 with the whole diagonal tile wrong but finite - so the GPU case on these fields catches a solver
     that lacks the rule. A random field does not: without the rule the emulation still gets it right."""
     f = P.late_corner()
-    want = P.dijkstra8(*f, [(0, 0)])
+    want = R.dijkstra(*f, [(0, 0)], conn=8)
     assert want[31, 31] == 48.5 and want[32, 32] == 50.0
     d, rounds = P.tile_rounds(*f, [(0, 0)])
     assert np.array_equal(_bits(d), _bits(want)) and rounds == 5
@@ -127,7 +138,7 @@ def test_late_corner_needs_the_corner_rule():
     assert rounds == 4 and wrong.sum() == 1024 and wrong[32:, 32:].all() and d[32, 32] == 5047.5 and np.isfinite(d).all()
     g = _random_fields(np.random.default_rng(11), 40, 56)
     d, _ = P.tile_rounds(*g, [(5, 7), (50, 30)], corner_flags=False)
-    assert np.array_equal(_bits(d), _bits(P.dijkstra8(*g, [(5, 7), (50, 30)])))
+    assert np.array_equal(_bits(d), _bits(R.dijkstra(*g, [(5, 7), (50, 30)], conn=8)))
 
 
 def test_conn_symbols_are_declared_and_bound():
@@ -173,13 +184,13 @@ def _same(a, b):
     return set(a) == set(b) and all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a)
 
 
-def _check_plan8(got, f, targets, start):
-    """cost, next, path and directions of an 8-connected plan against the restatement on the fields f = (map, conn0, conn1)."""
-    want = P.dijkstra8(*f, targets)
+def _check_plan(got, f, targets, start, conn=8):
+    """cost, next, path and directions of a plan (8-connected unless said) against the restatement on the fields f = (map, conn0, conn1)."""
+    want = R.dijkstra(*f, targets, conn=conn)
     assert np.array_equal(_bits(got["cost"]), _bits(want))
-    nxt = P.successors8(want, *f, targets)
+    nxt = R.successors(want, *f, targets, conn=conn)
     assert np.array_equal(got["next"], nxt)
-    path, dirs = P.walk8(want, nxt, start)
+    path, dirs = R.walk(want, nxt, start, conn=conn)
     assert np.array_equal(got["path"], path) and np.array_equal(_bits(got["directions"]), _bits(dirs))
     return want
 
@@ -192,12 +203,12 @@ def _check_plan8(got, f, targets, start):
     (33, 33, [(30, 2)], (1, 32)),                  # the corner tile is 1 x 1
 ])
 def test_cost_field_bit_equal_to_dijkstra8(built, H, W, targets, start):
-    """The engine's own Scene.read() fields go through path8_ref's Dijkstra; the device field must have the same bits."""
+    """The engine's own Scene.read() fields go through path_ref's Dijkstra; the device field must have the same bits."""
     sc = _scene(H, W, H * 1000 + W)
     f = sc.read()
     sc.plan(targets=targets, start=start, connectivity=8)
     got = sc.read_plan()
-    want = _check_plan8(got, (f["map"], f["conn0"], f["conn1"]), targets, start)
+    want = _check_plan(got, (f["map"], f["conn0"], f["conn1"]), targets, start)
     print(f"{W}x{H}: max cost {want.max()}, {sc.plan_time(1)}")
     sc.close()
 
@@ -215,17 +226,17 @@ def test_full_frame_satisfies_its_equations_at_every_pixel(built):
     d = got["cost"]
     assert np.isfinite(d).all() and d.max() < 2 ** 24
     assert all(d[y, x] == 0 for x, y in tg) and (d == 0).sum() == len(tg)
-    assert P.equation_residual8(d, f["map"], f["conn0"], f["conn1"], tg) == 0
+    assert R.equation_residual(d, f["map"], f["conn0"], f["conn1"], tg, conn=8) == 0
     # the route: next is the first of the eight achieving equality, costs strictly decrease, directions are walk8's
-    nxt = P.successors8(d, f["map"], f["conn0"], f["conn1"], tg)
+    nxt = R.successors(d, f["map"], f["conn0"], f["conn1"], tg, conn=8)
     assert np.array_equal(got["next"], nxt) and (nxt == -1).sum() == len(tg)
-    path, dirs = P.walk8(d, nxt, (400, 479))
+    path, dirs = R.walk(d, nxt, (400, 479), conn=8)
     assert np.array_equal(got["path"], path) and np.array_equal(_bits(got["directions"]), _bits(dirs))
     cost = d[path[:, 1], path[:, 0]]
     assert (np.diff(cost) < 0).all() and cost[-1] == 0 and tuple(path[-1]) in tg
     steps = np.abs(np.diff(path, axis=0))
     assert (steps.max(1) == 1).all() and (steps.sum(1) == 2).any()                  # neighbours, some of them diagonal
-    assert set(np.unique(_bits(dirs[1:, 1]))) <= {int(r.view(np.uint32)) for r in P.ROT[:4]}
+    assert set(np.unique(_bits(dirs[1:, 1]))) <= {int(r.view(np.uint32)) for r in R.ROT[:4]}
     print(f"route of {len(path)} nodes, {sc.plan_time(1)}")
     sc.close()
 
@@ -238,7 +249,7 @@ def test_late_corner_on_the_device(built):
     sc = _fields_scene(f)
     sc.plan(targets=[(0, 0)], start=(63, 63), connectivity=8)
     got = sc.read_plan()
-    want = _check_plan8(got, f, [(0, 0)], (63, 63))
+    want = _check_plan(got, f, [(0, 0)], (63, 63))
     assert got["cost"][31, 31] == 48.5 and got["cost"][32, 32] == 50.0 and want[32, 32] == 50.0
     stats = sc.plan_time(1)
     print(f"late corner: {stats}")
@@ -255,7 +266,7 @@ def test_targets_on_tile_corners(built, targets):
     sc.plan(targets=targets, start=(5, 60), connectivity=8)
     got = sc.read_plan()
     assert np.isfinite(got["cost"]).all()
-    _check_plan8(got, f, targets, (5, 60))
+    _check_plan(got, f, targets, (5, 60))
     sc.close()
 
 
@@ -266,7 +277,7 @@ def test_hand_routes_on_the_device(built):
     sc = _fields_scene(f)
     sc.plan(targets=[(0, 1)], start=(0, 0), connectivity=8)
     got = sc.read_plan()
-    _check_plan8(got, f, [(0, 1)], (0, 0))
+    _check_plan(got, f, [(0, 1)], (0, 0))
     assert got["path"].tolist() == [[0, 0], [1, 0], [0, 1]]
     assert np.array_equal(_bits(got["directions"]), _bits(np.array([[1, 0], [1, PI4]], np.float32)))
     sc.plan(targets=[(0, 1)], start=(0, 0))                                         # 4-connected: straight down the edge of 100
@@ -276,35 +287,10 @@ def test_hand_routes_on_the_device(built):
     sc = _fields_scene(f)
     sc.plan(targets=[STAIRS[-1]], start=STAIRS[0], connectivity=8)
     got = sc.read_plan()
-    _check_plan8(got, f, [STAIRS[-1]], STAIRS[0])
+    _check_plan(got, f, [STAIRS[-1]], STAIRS[0])
     assert got["path"].tolist() == [list(p) for p in STAIRS]
     assert np.array_equal(_bits(got["directions"][:, 1]), _bits(np.array(STAIRS_ROT, np.float32)))
     sc.close()
-
-
-def _tour8(f, targets, start):
-    """tour_ref.tour's logic on 8-connected fields: path8_ref's fields, successors, walks and rotations; labels, legs and order are
-    tour_ref's own functions."""
-    cost = np.stack([P.dijkstra8(*f, [t]) for t in targets])
-    nxt = np.stack([P.successors8(cost[b], *f, [t]) for b, t in enumerate(targets)])
-    legs = T.leg_matrix(cost, targets, start)
-    order, total = T.best_order(legs)
-    nodes, field_of_step, leg_ends, at = [tuple(start)], [], [], tuple(start)
-    for b in order:
-        seg, _ = P.walk8(cost[b], nxt[b], at)
-        assert tuple(seg[-1]) == tuple(targets[b])
-        for n in seg[1:]:
-            nodes.append(tuple(int(v) for v in n)); field_of_step.append(b)
-        leg_ends.append(len(nodes) - 1)
-        at = tuple(targets[b])
-    dirs = np.zeros((len(nodes) - 1, 2), np.float32)
-    for i, b in enumerate(field_of_step):
-        (x0, y0), (x1, y1) = nodes[i], nodes[i + 1]
-        dirs[i, 0] = cost[b, y0, x0] - cost[b, y1, x1]
-        if i > 0:
-            dirs[i, 1] = P.rotation(nodes[i - 1], nodes[i], nodes[i + 1])             # (0.0 where the route reverses)
-    return dict(cost=cost, next=nxt, label=T.labels(cost), legs=legs, order=list(order), total=total,
-                path=np.array(nodes, np.int32).reshape(-1, 2), directions=dirs, leg_ends=leg_ends)
 
 
 @pytest.mark.gpu
@@ -318,7 +304,7 @@ def test_tour_on_the_eight_connected_grid(built, H, W, targets, start):
     f = (r["map"], r["conn0"], r["conn1"])
     sc.plan_tour(targets=targets, start=start, connectivity=8)
     got = sc.read_tour(fields=True)
-    want = _tour8(f, targets, start)
+    want = T.tour(*f, targets, start, conn=8)
     K = len(targets)
     assert got["targets"].tolist() == [list(t) for t in targets]
     for b in range(K):
@@ -328,12 +314,12 @@ def test_tour_on_the_eight_connected_grid(built, H, W, targets, start):
     assert np.array_equal(_bits(np.minimum.reduce(got["cost"])), _bits(sc.read_plan()["cost"]))
     assert np.array_equal(got["label"], want["label"])
     assert np.array_equal(_bits(got["legs"]), _bits(want["legs"])) and (np.diag(got["legs"][1:]) == 0).all()
-    assert got["order"].tolist() == want["order"] and _bits(got["total"]) == _bits(want["total"])
-    assert np.array_equal(got["path"], want["path"]) and got["leg_ends"].tolist() == want["leg_ends"]
+    assert got["order"].tolist() == want["order"].tolist() and _bits(got["total"]) == _bits(want["total"])
+    assert np.array_equal(got["path"], want["path"]) and got["leg_ends"].tolist() == want["leg_ends"].tolist()
     assert np.array_equal(_bits(got["directions"]), _bits(want["directions"]))
     stats = sc.tour_time(1)
     assert _same(got, sc.read_tour(fields=True))                                   # the replay has the tour's connectivity
-    print(f"{W}x{H}: K = {K}, order {want['order']}, total {want['total']}, route of {len(want['path'])} nodes, {stats}")
+    print(f"{W}x{H}: K = {K}, order {want['order'].tolist()}, total {want['total']}, route of {len(want['path'])} nodes, {stats}")
     sc.close()
 
 
@@ -380,6 +366,60 @@ def test_four_eight_and_tour_do_not_disturb_one_another(built):
     sc.plan(targets=tg, start=start)                                               # and 4 after 8 is what it was before any 8
     assert _same(p4, sc.read_plan())
     assert np.array_equal(_bits(p4["cost"]), _bits(np.minimum.reduce(t4["cost"])))
+    sc.close()
+
+
+@pytest.mark.gpu
+def test_one_solver_state_serves_kinds_connectivities_and_field_counts(built):
+    """Plans and tours share the solver's buffers (edge terms, tile flags [2][F][ntiles], counters, read-back block): on ONE handle a
+    tour of 6 fields, a plan, a tour of 2 (the flag array's layout shrinks), a plan to a tile corner, both replays, a tour of 5 (it
+    grows again), connectivities mixed. 64 x 64: 2 x 2 tiles; two targets of the first tour face each other across the tile border
+    x = 31 | 32. After every step the run just made equals the restatement bit for bit and the other kind's last result reads back
+    byte for byte what it was."""
+    f = _random_fields(np.random.default_rng(6464), 64, 64, 30)
+    sc = _fields_scene(f)
+    start = (5, 60)
+    last, wants = {}, {}
+
+    def check(kind, targets, conn):
+        """the last run of `kind` against the restatement; the other kind's last result unchanged"""
+        got = sc.read_tour(fields=True) if kind == "tour" else sc.read_plan()
+        if kind == "plan":
+            _check_plan(got, f, targets, start, conn)
+        else:
+            key = (tuple(targets), conn)
+            want = wants[key] = wants.get(key) or T.tour(*f, targets, start, conn=conn)
+            assert got["targets"].tolist() == want["targets"].tolist()
+            assert np.array_equal(_bits(got["cost"]), _bits(want["cost"])) and np.array_equal(got["next"], want["next"])
+            assert np.array_equal(got["label"], want["label"]) and np.array_equal(_bits(got["legs"]), _bits(want["legs"]))
+            assert got["order"].tolist() == want["order"].tolist() and _bits(got["total"]) == _bits(want["total"])
+            assert np.array_equal(got["path"], want["path"]) and got["leg_ends"].tolist() == want["leg_ends"].tolist()
+            assert np.array_equal(_bits(got["directions"]), _bits(want["directions"]))
+        last[kind] = got
+        other = "plan" if kind == "tour" else "tour"
+        if other in last:
+            assert _same(last[other], sc.read_tour(fields=True) if other == "tour" else sc.read_plan()), f"{kind} disturbed the last {other}"
+
+    tour6 = [(31, 20), (32, 20), (3, 3), (60, 5), (10, 50), (55, 58)]
+    sc.plan_tour(targets=tour6, start=start, connectivity=8)
+    check("tour", tour6, 8)
+    plan3 = [(0, 0), (63, 63), (20, 33)]
+    sc.plan(targets=plan3, start=start, connectivity=4)
+    check("plan", plan3, 4)
+    tour2 = [(40, 10), (7, 32)]
+    sc.plan_tour(targets=tour2, start=start, connectivity=4)
+    check("tour", tour2, 4)
+    sc.plan(targets=[(31, 31)], start=start, connectivity=8)
+    check("plan", [(31, 31)], 8)
+    stats = [sc.tour_time(2)]
+    check("tour", tour2, 4)
+    stats.append(sc.plan_time(2))
+    check("plan", [(31, 31)], 8)
+    assert stats[0]["rounds"] >= 1 and stats[1]["rounds"] >= 1
+    tour5 = [(32, 32), (31, 0), (0, 31), (63, 32), (16, 16)]
+    sc.plan_tour(targets=tour5, start=start, connectivity=8)
+    check("tour", tour5, 8)
+    print(f"replays: {stats}")
     sc.close()
 
 
@@ -431,13 +471,13 @@ def test_errors(built):
     sc.append(depth, ci, ya.COMPAT_SANE)
     sc.plan(targets=tg, start=start, connectivity=8)
     r = sc.read()
-    assert np.array_equal(_bits(sc.read_plan()["cost"]), _bits(P.dijkstra8(r["map"], r["conn0"], r["conn1"], tg)))
+    assert np.array_equal(_bits(sc.read_plan()["cost"]), _bits(R.dijkstra(r["map"], r["conn0"], r["conn1"], tg, conn=8)))
     sc.close()
 
 
 @pytest.mark.gpu
 def test_plan8_beats_the_cpu_restatement(built):
-    """As test_plan_beats_the_cpu_restatement: an 8-connected plan at 640 x 480 must beat path8_ref's numpy Jacobi solve of the same
+    """As test_plan_beats_the_cpu_restatement: an 8-connected plan at 640 x 480 must beat path_ref's numpy Jacobi solve of the same
     field, timed here on the same box. A floor that catches a broken work list, not a target (tools/time_path.py measures)."""
     H, W = 480, 640
     sc = _scene(H, W, 13)
@@ -449,7 +489,7 @@ def test_plan8_beats_the_cpu_restatement(built):
     gpu_s = time.perf_counter() - t0
     got = sc.read_plan()
     t0 = time.perf_counter()
-    want, sweeps = P.jacobi8(f["map"], f["conn0"], f["conn1"], tg)
+    want, sweeps = R.jacobi(f["map"], f["conn0"], f["conn1"], tg, conn=8)
     cpu_s = time.perf_counter() - t0
     stats = sc.plan_time(10)
     print(f"plan8 640x480: host wall {gpu_s * 1e3:.3f} ms, {stats}; numpy Jacobi {cpu_s:.2f} s in {sweeps} sweeps")

@@ -1,6 +1,6 @@
 """The tour planner's frozen definition (DESIGN.md §11 "Tour"), restated on the CPU for tests/test_scene_tour.py on top of
 path_ref: K <= TOUR_MAX distinct targets, one single-target cost field d_b and successor field next_b per target (path_ref's,
-unchanged), the label of the nearest target per pixel, the leg matrix, the best visiting order and the joined route.
+unchanged, for the connectivity conn = 4 or 8), the label of the nearest target per pixel, the leg matrix, the best visiting order and the joined route.
 
 legs f32 [K + 1][K]: legs[0][b] = d_b[start], legs[1 + a][b] = d_b[t_a] - the cost to travel FROM t_a TO t_b (costs accumulate
 from the target outward, so d_b[t_a] and d_a[t_b] differ in their last bits: the direction is part of the definition).
@@ -24,10 +24,10 @@ def distinct(targets):
     return out
 
 
-def fields(hmap, conn0, conn1, targets):
+def fields(hmap, conn0, conn1, targets, conn=4):
     """(cost f32 [K][H][W], next i32 [K][H][W]): field b has the single target t_b; other targets are ordinary pixels of it."""
-    cost = np.stack([R.dijkstra(hmap, conn0, conn1, [t]) for t in targets])
-    nxt = np.stack([R.successors(cost[b], hmap, conn0, conn1, [t]) for b, t in enumerate(targets)])
+    cost = np.stack([R.dijkstra(hmap, conn0, conn1, [t], conn) for t in targets])
+    nxt = np.stack([R.successors(cost[b], hmap, conn0, conn1, [t], conn) for b, t in enumerate(targets)])
     return cost, nxt
 
 
@@ -74,14 +74,15 @@ def nearest_first(legs):
     return tuple(order)
 
 
-def route(cost, nxt, targets, order, start):
+def route(cost, nxt, targets, order, start, conn=4):
     """(path i32 [L][2], directions f32 [L - 1][2], leg_ends i32 [K]): the legs' walks joined, a junction node once; a leg whose
     start is its own target adds no node. Step i inside leg j has magnitude d_{o_j}[n_i] - d_{o_j}[n_{i+1}]; rot_0 = 0, else
-    float32(pi) when straight, float32(pi / 2) for a turn, 0.0 when n_{i-1} == n_{i+1} (a reversal, at a junction only)."""
+    path_ref.rotation: on the 4-connected grid float32(pi) when straight, float32(pi / 2) for a turn; 0.0 when n_{i-1} == n_{i+1} (a
+    reversal, at a junction only)."""
     nodes, field_of_step, leg_ends = [tuple(start)], [], []
     at = tuple(start)
     for b in order:
-        seg, _ = R.walk(cost[b], nxt[b], at)
+        seg, _ = R.walk(cost[b], nxt[b], at, conn)
         assert tuple(seg[-1]) == tuple(targets[b])
         for n in seg[1:]:
             nodes.append(tuple(int(v) for v in n)); field_of_step.append(b)
@@ -93,21 +94,18 @@ def route(cost, nxt, targets, order, start):
         (x0, y0), (x1, y1) = nodes[i], nodes[i + 1]
         dirs[i, 0] = cost[b, y0, x0] - cost[b, y1, x1]
         if i > 0:
-            if nodes[i - 1] == nodes[i + 1]:
-                dirs[i, 1] = 0.0
-            else:
-                dirs[i, 1] = R.PI if (path[i - 1] + path[i + 1] == 2 * path[i]).all() else R.HALF_PI
+            dirs[i, 1] = R.rotation(nodes[i - 1], nodes[i], nodes[i + 1])
     return path, dirs, np.array(leg_ends, np.int32)
 
 
-def tour(hmap, conn0, conn1, targets, start):
+def tour(hmap, conn0, conn1, targets, start, conn=4):
     """Everything yh_scene_tour_read returns, as a dict."""
     targets = [tuple(t) for t in targets]
     assert 1 <= len(targets) <= TOUR_MAX and len(set(targets)) == len(targets)
-    cost, nxt = fields(hmap, conn0, conn1, targets)
+    cost, nxt = fields(hmap, conn0, conn1, targets, conn)
     legs = leg_matrix(cost, targets, start)
     order, total = best_order(legs)
-    path, dirs, leg_ends = route(cost, nxt, targets, order, start)
+    path, dirs, leg_ends = route(cost, nxt, targets, order, start, conn)
     return dict(targets=np.array(targets, np.int32).reshape(-1, 2), order=np.array(order, np.int32), legs=legs, total=total, cost=cost,
                 next=nxt, label=labels(cost), path=path, directions=dirs, leg_ends=leg_ends)
 

@@ -9,33 +9,16 @@
 // and the set of f32 values is finite. That is what lets the solver below be asynchronous and still be tested with array_equal.
 //
 // Launches of one plan (yh_scene_plan):
-//   path_weights   one lane per pixel: conn0 / conn1 / map -> one float4 per pixel (right length, right height step, down length,
-//                  down height step): the solver reads 16 B per pixel instead of 32 B of connections + the map, length and step
-//                  stay apart for the two roundings.
-//   path_fill      cost = +inf, path_targets: cost = 0. The host flags round 0's tiles: each target's own tile, and the tile across
-//                  every tile border the target lies on - a target's drop from +inf to 0 is a lowered border cell like any other,
-//                  and a neighbour whose border sees nothing but targets (a wall of targets along a tile border) would otherwise
-//                  never be flagged.
-//   path_round     x rounds. A workgroup owns a SP_TW x SP_TH tile of the cost field with a one-cell halo in LDS; a lane owns a
-//                  2 x 2 block of cells whose twelve edge terms sit in registers. It relaxes in place (chaotic relaxation: a lane
-//                  reads its eight outer neighbours from LDS, sweeps its four cells forwards and backwards in registers, stores
-//                  what got smaller) SP_INNER times between workgroup votes, until a vote finds nothing changed: the tile's local
-//                  fixed point for the halo it loaded. Cells that changed go back with atomicMin on the u32 view (non-negative f32
-//                  order as their bits). Only a tile whose halo may have changed runs: a tile that lowered a cell of its border
-//                  flags that neighbour for the NEXT round (two flag arrays, by round parity) and counts it once. No workgroup
-//                  ever waits for another one: a round is a launch, the host enqueues SP_BATCH of them and reads the batch's
-//                  counters back once (rounds past convergence find no flag and exit at once).
+//   path_weights, then after path_fill (cost = +inf) and path_targets (cost = 0) field_round x rounds: scene_solve.hip's, which
+//                  relaxes the one field tile by tile to its fixed point, the targets its seeds.
 //   path_next      one lane per pixel: the first neighbour in the order (left, right, up, down) whose candidate equals d[v] bitwise.
 //   path_walk      one wave: chases `next` from the start through a 32 x 32 window of it held in LDS (reloaded when the route leaves
 //                  it: ~1 global round trip per >= 16 steps instead of one per step), then its 64 lanes write the directions.
-// The tile relaxation, the successor rule and the chase are device functions of scene_path_dev.h: scene_tour.hip (yh_scene_plan_tour)
-// runs the same ones over K single-target fields.
-// yh_scene_plan_conn(.., 8) searches the 8-connected grid (DESIGN.md §11 "Diagonals"): path_weights<8> also writes the down-right and
-// down-left terms (a second float4 per pixel, allocated at the first such plan), path_round<8> relaxes over them and wakes the
-// diagonally adjacent tile when a corner cell drops, path_next<8> orders (left, right, up, down, up-left, up-right, down-left,
-// down-right), and the walk's rotations are pi, 3 pi / 4, pi / 2, pi / 4. The <4> forms are the code described above.
+// scene_tour.hip (yh_scene_plan_tour) runs the same solver and the same device functions (scene_path_dev.h) over K single-target fields.
+// yh_scene_plan_conn(.., 8) searches the 8-connected grid (DESIGN.md §11 "Diagonals"): the solver relaxes over the diagonal terms too
+// and wakes the diagonally adjacent tile when a corner cell drops, path_next<8> orders (left, right, up, down, up-left, up-right,
+// down-left, down-right), and the walk's rotations are pi, 3 pi / 4, pi / 2, pi / 4. The <4> forms are the code described above.
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -47,53 +30,20 @@
 
 using namespace yh;
 
-struct yh_scene_path {
+struct yh_scene_path : SolveLast {   // (the route, the start, the connectivity and whether a plan exists: SolveLast)
     float* cost = nullptr;       // [H][W]
     int32_t* next = nullptr;     // [H][W]
-    float4* edge = nullptr;      // [H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
-    float4* edge2 = nullptr;     // [H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected plan
-    uint32_t* flags = nullptr;   // [2][ntiles]
-    uint32_t* cnt = nullptr;     // [SP_BATCH + 1]: cnt[j + 1] = tiles flagged by round j of the batch
     int32_t* targets = nullptr;  // [targets_cap] linear indices
     int32_t targets_cap = 0;
-    int2* nodes = nullptr;       // [W * H] the route
-    float2* dirs = nullptr;      // [W * H]
     int32_t* walk_out = nullptr; // [2]: length, status
-    uint32_t* host = nullptr;    // pinned: SP_BATCH + 1 counters, then walk_out
-    int tx = 0, ty = 0;
-    // the last plan
-    bool planned = false;
-    uint64_t frame = 0;
     std::vector<int32_t> last_targets;
-    std::vector<uint32_t> flags0;   // round 0's tile flags, built on the host
-    int32_t start = 0, path_len = 0, conn = 4;
-    long long rounds = 0, tile_runs = 0;
 };
 
 namespace {
 
-template <int CONN>
-__global__ __launch_bounds__(256) void path_weights(const PathParams p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.W * p.H) return;
-    const int x = i % p.W, y = i / p.W;
-    const float h = (float)p.map[i];
-    const float hr = x + 1 < p.W ? fabsf(__fsub_rn(h, (float)p.map[i + 1])) : 0.0f;
-    const float hd = y + 1 < p.H ? fabsf(__fsub_rn(h, (float)p.map[i + p.W])) : 0.0f;
-    const float4 c0 = p.conn0[i], c1 = p.conn1[i];
-    p.edge[i] = make_float4(x + 1 < p.W ? c0.z : -1.0f, hr, y + 1 < p.H ? c1.x : -1.0f, hd);
-    if constexpr (CONN == 8) {
-        const bool dr = x + 1 < p.W && y + 1 < p.H, dl = x > 0 && y + 1 < p.H;
-        const float hdr = dr ? fabsf(__fsub_rn(h, (float)p.map[i + p.W + 1])) : 0.0f;
-        const float hdl = dl ? fabsf(__fsub_rn(h, (float)p.map[i + p.W - 1])) : 0.0f;
-        p.edge2[i] = make_float4(dr ? c0.w : -1.0f, hdr, dl ? c1.y : -1.0f, hdl);
-    }
-}
-
 __global__ __launch_bounds__(256) void path_fill(const PathParams p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < p.W * p.H) p.cost[i] = SP_INF;
-    if (i < 2 * p.ntiles) p.flags[i] = 0u;
 }
 
 __global__ __launch_bounds__(256) void path_targets(const PathParams p, const int32_t* targets, int n) {
@@ -105,11 +55,6 @@ __global__ __launch_bounds__(256) void path_targets(const PathParams p, const in
 __global__ __launch_bounds__(256) void path_mark_targets(const PathParams p, const int32_t* targets, int n) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k < n) p.next[targets[k]] = -1;
-}
-
-template <int CONN>
-__global__ __launch_bounds__(SP_NT) void path_round(const PathParams p, int parity, uint32_t* cnt_next) {
-    relax_tile<CONN>(p, p.cost, p.flags + parity * p.ntiles, p.flags + (parity ^ 1) * p.ntiles, cnt_next);
 }
 
 template <int CONN>
@@ -137,16 +82,11 @@ __global__ __launch_bounds__(64) void path_walk(const PathParams p, int start, i
 int ensure_buffers(yh_scene* h) {
     yh_scene_path* q = h->path;
     const size_t npx = (size_t)h->W * h->H;
-    q->tx = (h->W + SP_TW - 1) / SP_TW; q->ty = (h->H + SP_TH - 1) / SP_TH;
     SCHK(h, hipMalloc((void**)&q->cost, npx * 4));
     SCHK(h, hipMalloc((void**)&q->next, npx * 4));
-    SCHK(h, hipMalloc((void**)&q->edge, npx * 16));
-    SCHK(h, hipMalloc((void**)&q->flags, (size_t)2 * q->tx * q->ty * 4));
-    SCHK(h, hipMalloc((void**)&q->cnt, (SP_BATCH + 1) * 4));
     SCHK(h, hipMalloc((void**)&q->nodes, npx * sizeof(int2)));
     SCHK(h, hipMalloc((void**)&q->dirs, npx * sizeof(float2)));
     SCHK(h, hipMalloc((void**)&q->walk_out, 2 * 4));
-    SCHK(h, hipHostMalloc((void**)&q->host, (SP_BATCH + 3) * 4, hipHostMallocDefault));
     return YH_OK;
 }
 
@@ -154,53 +94,26 @@ int ensure_buffers(yh_scene* h) {
 int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, int conn) {
     yh_scene_path* q = h->path;
     const int n = (int)targets.size();
-    if (conn == 8 && !q->edge2) SCHK(h, hipMalloc((void**)&q->edge2, (size_t)h->W * h->H * 16));
     if (n > q->targets_cap) {
         if (q->targets) { SCHK(h, hipStreamSynchronize(h->stream)); SCHK(h, hipFree(q->targets)); q->targets = nullptr; q->targets_cap = 0; }
         SCHK(h, hipMalloc((void**)&q->targets, (size_t)n * 4));
         q->targets_cap = n;
     }
-    PathParams p;
-    p.W = h->W; p.H = h->H; p.tx = q->tx; p.ntiles = q->tx * q->ty;
-    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.edge2 = conn == 8 ? q->edge2 : nullptr; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
     const int npx = h->W * h->H;
-    const dim3 px((unsigned)((std::max(npx, 2 * p.ntiles) + 255) / 256)), tg((unsigned)((n + 255) / 256)), tiles((unsigned)q->tx, (unsigned)q->ty);
+    const dim3 px((unsigned)((npx + 255) / 256)), tg((unsigned)((n + 255) / 256));
     SCHK(h, hipMemcpyAsync(q->targets, targets.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    path_weights_launch(p, conn, h->stream);
+    PathParams p;
+    int rc = solve_begin(h, conn, 1, p);
+    if (rc) return rc;
+    p.cost = q->cost; p.next = q->next;
     hipLaunchKernelGGL(path_fill, px, dim3(256), 0, h->stream, p);
     hipLaunchKernelGGL(path_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
-    // round 0's work list (flag array 0): the rule path_round applies to every later decrease - a lowered cell on a tile's border
-    // flags the tile across that border, and with diagonals a lowered corner cell the tile diagonally across - applied to the
-    // targets' drop from +inf to 0, plus the targets' own tiles
-    q->flags0.assign((size_t)p.ntiles, 0u);
-    long long active = 0;
-    auto flag = [&](int bx, int by) {
-        if (bx < 0 || bx >= q->tx || by < 0 || by >= q->ty) return;
-        uint32_t& f = q->flags0[(size_t)by * q->tx + bx];
-        if (!f) { f = 1u; ++active; }
-    };
-    for (int t : targets) round0_flags(t % h->W, t / h->W, conn, flag);
-    SCHK(h, hipMemcpyAsync(q->flags, q->flags0.data(), (size_t)p.ntiles * 4, hipMemcpyHostToDevice, h->stream));
-    q->rounds = 0; q->tile_runs = 0;
-    const long long cap = (long long)npx;   // costs only decrease over a finite set: this never fires
-    long long round = 0;
-    while (active) {
-        if (round >= cap) return h->fail(YH_EHIP, "path solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
-        SCHK(h, hipMemsetAsync(q->cnt, 0, (SP_BATCH + 1) * 4, h->stream));
-        for (int j = 0; j < SP_BATCH; ++j, ++round)
-            hipLaunchKernelGGL(conn == 8 ? path_round<8> : path_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, (int)(round & 1), q->cnt + j + 1);
-        SCHK(h, hipGetLastError());
-        SCHK(h, hipMemcpyAsync(q->host, q->cnt, (SP_BATCH + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        q->host[0] = (uint32_t)active;   // tiles that ran in round j of the batch: host[j]
-        for (int j = 0; j < SP_BATCH; ++j) if (q->host[j]) { ++q->rounds; q->tile_runs += q->host[j]; }
-        active = q->host[SP_BATCH];
-    }
-    hipLaunchKernelGGL(conn == 8 ? path_next<8> : path_next<4>, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p);
+    if ((rc = solve_rounds(h, p, conn, 1, targets, "path"))) return rc;
+    hipLaunchKernelGGL(conn == 8 ? path_next<8> : path_next<4>, px, dim3(256), 0, h->stream, p);
     hipLaunchKernelGGL(path_mark_targets, tg, dim3(256), 0, h->stream, p, q->targets, n);
     hipLaunchKernelGGL(path_walk, dim3(1), dim3(64), 0, h->stream, p, (int)start, q->nodes, q->dirs, q->walk_out);
     SCHK(h, hipGetLastError());
-    int32_t* wo = reinterpret_cast<int32_t*>(q->host + SP_BATCH + 1);
+    int32_t* wo = reinterpret_cast<int32_t*>(h->solve->host + kSolveCnt + kSolveTail);
     SCHK(h, hipMemcpyAsync(wo, q->walk_out, 2 * 4, hipMemcpyDeviceToHost, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
     if (wo[1]) return h->fail(YH_EHIP, "path walk: no target within W*H steps (fields not those of a SANE frame?)");
@@ -211,10 +124,6 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, in
 }  // namespace
 
 namespace yh {
-void path_weights_launch(const PathParams& p, int conn, hipStream_t s) {
-    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)((p.W * p.H + 255) / 256)), dim3(256), 0, s, p);
-}
-
 // What yh_scene_plan and yh_scene_plan_tour check before they touch anything, and the targets they run on (linear indices)
 int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets) {
     if (n_targets < 1) return h->fail(YH_EINVAL, "n_targets < 1");
@@ -259,9 +168,8 @@ int scene_plan_diagonals(yh_scene* h) {
 void scene_path_free(yh_scene* h) {
     yh_scene_path* q = h->path;
     if (!q) return;
-    void* bufs[] = { q->cost, q->next, q->edge, q->edge2, q->flags, q->cnt, q->targets, q->nodes, q->dirs, q->walk_out };
+    void* bufs[] = { q->cost, q->next, q->targets, q->nodes, q->dirs, q->walk_out };
     for (void* b : bufs) if (b) hipFree(b);
-    if (q->host) hipHostFree(q->host);
     delete q;
     h->path = nullptr;
 }
@@ -296,20 +204,9 @@ int yh_scene_plan_conn(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
 
 int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy, float* directions, int32_t path_capacity, int32_t* path_len) {
     if (!h) return YH_EINVAL;
-    yh_scene_path* q = h->path;
-    if (!q || !q->planned) return h->fail(YH_ESTATE, "no plan has been made");
-    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the plan: plan again");
-    if (path_len) *path_len = q->path_len;
-    if ((path_xy || directions) && path_capacity < q->path_len)
-        return h->fail(YH_EOVERFLOW, "path_capacity " + std::to_string(path_capacity) + " < the route's " + std::to_string(q->path_len) + " nodes");
-    SCHK(h, hipSetDevice(h->dev));
-    const size_t npx = (size_t)h->W * h->H;
-    if (cost) SCHK(h, hipMemcpyAsync(cost, q->cost, npx * 4, hipMemcpyDeviceToHost, h->stream));
-    if (next) SCHK(h, hipMemcpyAsync(next, q->next, npx * 4, hipMemcpyDeviceToHost, h->stream));
-    if (path_xy) SCHK(h, hipMemcpyAsync(path_xy, q->nodes, (size_t)q->path_len * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
-    if (directions && q->path_len > 1) SCHK(h, hipMemcpyAsync(directions, q->dirs, (size_t)(q->path_len - 1) * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    SCHK(h, hipStreamSynchronize(h->stream));
-    return YH_OK;
+    const yh_scene_path* q = h->path;
+    const size_t bytes = (size_t)h->W * h->H * 4;
+    return solve_read(h, "plan", "plan again", q, { { cost, q ? q->cost : nullptr, bytes }, { next, q ? q->next : nullptr, bytes } }, path_xy, directions, path_capacity, path_len);
 }
 
 int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, const float* conn1) {
@@ -357,22 +254,9 @@ int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, co
 int yh_scene_plan_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs) {
     if (!h || reps < 1 || !ms_per_plan) return YH_EINVAL;
     yh_scene_path* q = h->path;
-    if (!q || !q->planned) return h->fail(YH_ESTATE, "no plan has been made");
-    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the plan: plan again");
-    SCHK(h, hipSetDevice(h->dev));
-    hipEvent_t a, b;
-    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
-    SCHK(h, hipEventRecord(a, h->stream));
-    for (int r = 0; r < reps; ++r) { const int rc = run_plan(h, q->last_targets, q->start, q->conn); if (rc) { hipEventDestroy(a); hipEventDestroy(b); return rc; } }
-    SCHK(h, hipEventRecord(b, h->stream));
-    SCHK(h, hipEventSynchronize(b));
-    float ms = 0;
-    hipEventElapsedTime(&ms, a, b);
-    hipEventDestroy(a); hipEventDestroy(b);
-    *ms_per_plan = ms / reps;   // (the host's waits for the batches' counters are inside: what a caller of yh_scene_plan waits for)
-    if (rounds) *rounds = (int32_t)q->rounds;
-    if (tile_runs) *tile_runs = (int32_t)q->tile_runs;
-    return YH_OK;
+    // (a failed replay has overwritten part of the last plan: it is gone)
+    auto run = [&] { const int rc = run_plan(h, q->last_targets, q->start, q->conn); if (rc) q->planned = false; return rc; };
+    return solve_time(h, "plan", "plan again", q, reps, run, ms_per_plan, rounds, tile_runs);
 }
 
 }  // extern "C"

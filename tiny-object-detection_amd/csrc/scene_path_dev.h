@@ -1,9 +1,13 @@
-// scene_path_dev.h — the planner's device code shared by scene_path.hip (one multi-source field, yh_scene_plan) and
-// scene_tour.hip (K single-target fields relaxed in the same launches, yh_scene_plan_tour): the tile relaxation, the successor
-// rule and the windowed chase. What they compute and why it is unique is said at the head of scene_path.hip.
+// scene_path_dev.h — what scene_path.hip (one multi-source field, yh_scene_plan) and scene_tour.hip (K single-target fields,
+// yh_scene_plan_tour) share: the field solver of scene_solve.hip, declared here, and the planner's device code - the tile relaxation, the
+// successor rule and the windowed chase. What they compute and why it is unique is said at the head of scene_path.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <functional>
+#include <initializer_list>
+#include <vector>
 
 #ifndef SP_TW
 #define SP_TW 32   // tile width and height (even). Measured alternatives: DESIGN.md §11
@@ -24,6 +28,20 @@
 
 static_assert(SP_TW % 2 == 0 && SP_TH % 2 == 0 && SP_NT % 64 == 0 && SP_NT <= 1024, "tile: whole waves of 2 x 2 blocks");
 
+struct yh_scene;
+// ---- host side (this struct and the solve_* declarations below). The solver's state (yh_scene::solve, scene_solve.hip): allocated at
+// the first plan or tour of a handle, shared by both kinds and both connectivities - every run recomputes the edge terms.
+struct yh_scene_solve {
+    float4* edge = nullptr;      // [H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
+    float4* edge2 = nullptr;     // [H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected run
+    uint32_t* flags = nullptr;   // [2][F][ntiles], by round parity; sized for cap_f fields, grows only
+    uint32_t* cnt = nullptr;     // [kSolveCnt] counters, then kSolveTail words for the caller's after-batch kernel
+    uint32_t* host = nullptr;    // pinned: the cnt block as read back, then kSolveWalk words for the caller's walk results
+    std::vector<uint32_t> flags0;   // [2][F][ntiles]: round 0's tile flags, built on the host, and the zeroes of the other parity
+    int cap_f = 0, tx = 0, ty = 0;
+    long long rounds = 0, tile_runs = 0;   // of the last run
+};
+
 namespace yh {
 
 struct PathParams {
@@ -37,10 +55,30 @@ struct PathParams {
     uint32_t* flags;
 };
 
-// path_weights (scene_path.hip) on stream s: p.map, p.conn0, p.conn1 -> p.edge, and with conn == 8 -> p.edge2 (down-right length,
-// down-right |dh|, down-left length, down-left |dh|; length -1 off the frame). The edge terms do not depend on the targets: a tour
-// computes them once for all its fields.
-void path_weights_launch(const PathParams& p, int conn, hipStream_t s);
+constexpr int kSolveCnt = SP_BATCH + 1, kSolveTail = 42, kSolveWalk = 12;   // cnt[j + 1] = tiles flagged by round j of the batch
+
+// What a kind of run (plan, tour) remembers of its last one, as far as the shared time and read code needs it
+struct SolveLast {
+    bool planned = false;
+    uint64_t frame = 0;
+    int32_t start = 0, path_len = 0, conn = 4;
+    int2* nodes = nullptr;    // the route
+    float2* dirs = nullptr;
+};
+struct SolveCopy { void* dst; const void* src; size_t bytes; };   // a device array a read hands out (skipped if dst is null)
+
+// Allocates what F fields of connectivity conn need, fills p (but cost and next: the caller's), enqueues path_weights (once for all fields)
+int solve_begin(yh_scene* h, int conn, int F, PathParams& p);
+// Relaxes the F fields at p.cost, which the caller has filled (+inf, 0 at the seeds), to their fixed points. seeds: the pixels that
+// start at 0, equally many per field, field by field. who: "path" or "tour", for the error text. after(tail), if given, enqueues
+// the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) arrives in host[kSolveCnt ..] with the counters.
+int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words = 0,
+                 const std::function<void(uint32_t*)>& after = nullptr);
+// run() reps times between two events; a failing run's code is returned as it is. kind, again: for the error texts ("plan", "plan again")
+int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast* q, int reps, const std::function<int()>& run, float* ms, int32_t* rounds, int32_t* tile_runs);
+// The checks of the read entry points (a run of this frame exists, the capacity holds the route), then the copies
+int solve_read(yh_scene* h, const char* kind, const char* again, const SolveLast* q, std::initializer_list<SolveCopy> fields, int32_t* path_xy, float* directions,
+               int32_t path_capacity, int32_t* path_len);
 
 // Round 0's tiles for a target at (x, y), through flag(tile x, tile y) (which ignores tiles outside the grid): its own tile, the tile
 // across every tile border it lies on and, with diagonals, the tile diagonally across a tile corner it lies on.

@@ -9,15 +9,12 @@
 // A plan is bound by serial depth (a round is as long as its slowest tile, ~42 of 300 workgroups have work), so the K fields relax in
 // the SAME launches, the field as grid z: a tour's rounds are those of its slowest field, not their sum.
 //
-// Launches of one tour:
-//   path_weights   (scene_path.hip) once: the edge terms are shared by all fields.
-//   tour_fill      cost[b] = +inf, 0 at t_b; flags = 0. The host flags round 0's tiles per field by scene_path.hip's rule applied to
-//                  that field's one target: its own tile, and the tile across every tile border it lies on.
-//   tour_round     x rounds, grid (tiles x, tiles y, K): relax_tile on field z with field z's flags ([2][K][ntiles]); the counters sum
-//                  over the fields, rounds are launched while any field has a flagged tile, a tile of a converged field exits on
-//                  its flag test as idle tiles do. No workgroup waits for another one.
-//   tour_legs      after every batch of rounds: the K (K + 1) entries of the leg matrix into the block the host reads the batch's
-//                  counters from, so the matrix arrives with the last counters (earlier batches' copies are ignored).
+// Launches of one tour (the solver and its buffers are scene_solve.hip's, shared with scene_path.hip):
+//   path_weights   (scene_solve.hip) once: the edge terms are shared by all fields.
+//   tour_fill      cost[b] = +inf, 0 at t_b.
+//   field_round    x rounds, grid (tiles x, tiles y, K) (scene_solve.hip): field b's one seed is t_b.
+//   tour_legs      after every batch of rounds (the solver's after-batch hook): the K (K + 1) entries of the leg matrix into the tail of
+//                  the block the host reads the batch's counters from: it arrives with the last counters (earlier copies are ignored).
 //   tour_next      one lane per pixel: next_b for the K fields and the label (the pixel's edge terms read once for all of them).
 //   (host)         the order: all K! <= 720 permutations from the leg matrix.
 //   tour_walk      K waves, one per leg: leg j chases next_{o_j} from the start (j = 0) or from t_{o_{j-1}} into its own segment.
@@ -37,36 +34,22 @@ using namespace yh;
 
 #define ST_JOIN_BLOCKS 120   // tour_join's grid (its lanes stride over the route)
 
-struct yh_scene_tour {
+struct yh_scene_tour : SolveLast {   // (the joined route [K * W * H], the start, the connectivity and whether a tour exists: SolveLast)
     int cap_k = 0;               // the buffers below are sized for this many fields; they only grow
     float* cost = nullptr;       // [K][H][W]
     int32_t* next = nullptr;     // [K][H][W]
     uint8_t* label = nullptr;    // [H][W]
-    float4* edge = nullptr;      // [H][W], as yh_scene_path::edge
-    float4* edge2 = nullptr;     // [H][W], as yh_scene_path::edge2: allocated at the first 8-connected tour
-    uint32_t* flags = nullptr;   // [2][K][ntiles]
-    uint32_t* cnt = nullptr;     // [SP_BATCH + 1] counters, then YH_TOUR_MAX (YH_TOUR_MAX + 1) legs (f32)
     int2* segs = nullptr;        // [K][W * H] the legs' walks
-    int2* nodes = nullptr;       // [K * W * H] the joined route
-    float2* dirs = nullptr;      // [K * W * H]
     int32_t* walk_out = nullptr; // [2 * YH_TOUR_MAX]: nodes of leg j, then status of leg j
-    uint32_t* host = nullptr;    // pinned: the cnt block, then walk_out
-    int tx = 0, ty = 0;
-    // the last tour
-    bool planned = false;
-    uint64_t frame = 0;
-    std::vector<int32_t> targets;   // linear indices, t_0 .. t_{K-1}
-    std::vector<uint32_t> flags0;   // round 0's tile flags [K][ntiles], built on the host
-    int32_t start = 0, path_len = 0, conn = 4;
+    std::vector<int32_t> targets;   // of the last tour: linear indices, t_0 .. t_{K-1}
     int32_t order[YH_TOUR_MAX], leg_ends[YH_TOUR_MAX];
     float legs[(YH_TOUR_MAX + 1) * YH_TOUR_MAX], total = 0.0f;
-    long long rounds = 0, tile_runs = 0;
 };
 
 namespace {
 
 constexpr int kLegsMax = (YH_TOUR_MAX + 1) * YH_TOUR_MAX;
-constexpr int kCntWords = SP_BATCH + 1 + kLegsMax;
+static_assert(kLegsMax <= kSolveTail && 2 * YH_TOUR_MAX <= kSolveWalk, "the leg matrix and walk_out ride in the solver's read-back block");
 
 struct TourPoints { int32_t K, start, t[YH_TOUR_MAX]; };             // the start and the targets, linear indices
 struct TourLegs { int32_t K, field[YH_TOUR_MAX], from[YH_TOUR_MAX]; };   // leg j walks next_{field[j]} from pixel from[j]
@@ -75,13 +58,6 @@ __global__ __launch_bounds__(256) void tour_fill(const PathParams p, const TourP
     const int i = blockIdx.x * 256 + threadIdx.x, npx = p.W * p.H;
     if (i < npx)
         for (int b = 0; b < pts.K; ++b) p.cost[(size_t)b * npx + i] = i == pts.t[b] ? 0.0f : SP_INF;
-    if (i < 2 * pts.K * p.ntiles) p.flags[i] = 0u;
-}
-
-template <int CONN>
-__global__ __launch_bounds__(SP_NT) void tour_round(const PathParams p, int K, int parity, uint32_t* cnt_next) {
-    const int b = blockIdx.z;
-    relax_tile<CONN>(p, p.cost + (size_t)b * p.W * p.H, p.flags + (size_t)(parity * K + b) * p.ntiles, p.flags + (size_t)((parity ^ 1) * K + b) * p.ntiles, cnt_next);
 }
 
 __global__ __launch_bounds__(64) void tour_legs(const PathParams p, const TourPoints pts, float* legs) {
@@ -148,9 +124,9 @@ __global__ __launch_bounds__(256) void tour_join(const PathParams p, const TourL
 }
 
 void free_fields(yh_scene_tour* q) {
-    void* bufs[] = { q->cost, q->next, q->flags, q->segs, q->nodes, q->dirs };
+    void* bufs[] = { q->cost, q->next, q->segs, q->nodes, q->dirs };
     for (void* b : bufs) if (b) (void)hipFree(b);
-    q->cost = nullptr; q->next = nullptr; q->flags = nullptr; q->segs = nullptr; q->nodes = nullptr; q->dirs = nullptr;
+    q->cost = nullptr; q->next = nullptr; q->segs = nullptr; q->nodes = nullptr; q->dirs = nullptr;
     q->cap_k = 0;
 }
 
@@ -158,21 +134,14 @@ void free_fields(yh_scene_tour* q) {
 int ensure_buffers(yh_scene* h, int K) {
     yh_scene_tour* q = h->tour;
     const size_t npx = (size_t)h->W * h->H;
-    if (!q->edge) {
-        q->tx = (h->W + SP_TW - 1) / SP_TW; q->ty = (h->H + SP_TH - 1) / SP_TH;
-        SCHK(h, hipMalloc((void**)&q->edge, npx * 16));
-        SCHK(h, hipMalloc((void**)&q->label, npx));
-        SCHK(h, hipMalloc((void**)&q->cnt, kCntWords * 4));
-        SCHK(h, hipMalloc((void**)&q->walk_out, 2 * YH_TOUR_MAX * 4));
-        SCHK(h, hipHostMalloc((void**)&q->host, (kCntWords + 2 * YH_TOUR_MAX) * 4, hipHostMallocDefault));
-    }
+    if (!q->label) SCHK(h, hipMalloc((void**)&q->label, npx));
+    if (!q->walk_out) SCHK(h, hipMalloc((void**)&q->walk_out, 2 * YH_TOUR_MAX * 4));
     if (K <= q->cap_k) return YH_OK;
     SCHK(h, hipStreamSynchronize(h->stream));
     free_fields(q);
     q->planned = false;   // (the last tour lived in them)
     SCHK(h, hipMalloc((void**)&q->cost, K * npx * 4));
     SCHK(h, hipMalloc((void**)&q->next, K * npx * 4));
-    SCHK(h, hipMalloc((void**)&q->flags, (size_t)2 * K * q->tx * q->ty * 4));
     SCHK(h, hipMalloc((void**)&q->segs, K * npx * sizeof(int2)));
     SCHK(h, hipMalloc((void**)&q->nodes, K * npx * sizeof(int2)));
     SCHK(h, hipMalloc((void**)&q->dirs, K * npx * sizeof(float2)));
@@ -198,48 +167,19 @@ float best_order(const float* legs, int K, int32_t* order) {
 int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, int conn) {
     yh_scene_tour* q = h->tour;
     const int K = (int)targets.size(), npx = h->W * h->H;
-    if (conn == 8 && !q->edge2) SCHK(h, hipMalloc((void**)&q->edge2, (size_t)npx * 16));
-    PathParams p;
-    p.W = h->W; p.H = h->H; p.tx = q->tx; p.ntiles = q->tx * q->ty;
-    p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = q->edge; p.edge2 = conn == 8 ? q->edge2 : nullptr; p.cost = q->cost; p.next = q->next; p.flags = q->flags;
     TourPoints pts;
     pts.K = K; pts.start = start;
     for (int b = 0; b < YH_TOUR_MAX; ++b) pts.t[b] = b < K ? targets[b] : -1;
-    const dim3 px((unsigned)((std::max(npx, 2 * K * p.ntiles) + 255) / 256)), tiles((unsigned)q->tx, (unsigned)q->ty, (unsigned)K);
-    path_weights_launch(p, conn, h->stream);
-    hipLaunchKernelGGL(tour_fill, px, dim3(256), 0, h->stream, p, pts);
-    // round 0's work list, per field (flag array 0, [K][ntiles]): scene_path.hip's rule for that field's one target
-    q->flags0.assign((size_t)K * p.ntiles, 0u);
-    long long active = 0;
-    for (int b = 0; b < K; ++b) {
-        auto flag = [&](int bx, int by) {
-            if (bx < 0 || bx >= q->tx || by < 0 || by >= q->ty) return;
-            uint32_t& f = q->flags0[(size_t)b * p.ntiles + (size_t)by * q->tx + bx];
-            if (!f) { f = 1u; ++active; }
-        };
-        round0_flags(targets[b] % h->W, targets[b] / h->W, conn, flag);
-    }
-    SCHK(h, hipMemcpyAsync(q->flags, q->flags0.data(), q->flags0.size() * 4, hipMemcpyHostToDevice, h->stream));
-    q->rounds = 0; q->tile_runs = 0;
-    const long long cap = (long long)npx;   // costs only decrease over a finite set: this never fires
-    long long round = 0;
-    float* legs_dev = reinterpret_cast<float*>(q->cnt + SP_BATCH + 1);
-    while (active) {
-        if (round >= cap) return h->fail(YH_EHIP, "tour solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
-        SCHK(h, hipMemsetAsync(q->cnt, 0, (SP_BATCH + 1) * 4, h->stream));
-        for (int j = 0; j < SP_BATCH; ++j, ++round)
-            hipLaunchKernelGGL(conn == 8 ? tour_round<8> : tour_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, K, (int)(round & 1), q->cnt + j + 1);
-        hipLaunchKernelGGL(tour_legs, dim3(1), dim3(64), 0, h->stream, p, pts, legs_dev);
-        SCHK(h, hipGetLastError());
-        SCHK(h, hipMemcpyAsync(q->host, q->cnt, kCntWords * 4, hipMemcpyDeviceToHost, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        q->host[0] = (uint32_t)active;   // tiles (of all fields) that ran in round j of the batch: host[j]
-        for (int j = 0; j < SP_BATCH; ++j) if (q->host[j]) { ++q->rounds; q->tile_runs += q->host[j]; }
-        active = q->host[SP_BATCH];
-    }
+    PathParams p;
+    int rc = solve_begin(h, conn, K, p);
+    if (rc) return rc;
+    p.cost = q->cost; p.next = q->next;
+    hipLaunchKernelGGL(tour_fill, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p, pts);
+    auto legs = [&](uint32_t* tail) { hipLaunchKernelGGL(tour_legs, dim3(1), dim3(64), 0, h->stream, p, pts, reinterpret_cast<float*>(tail)); };
+    if ((rc = solve_rounds(h, p, conn, K, targets, "tour", kLegsMax, legs))) return rc;
     hipLaunchKernelGGL(conn == 8 ? tour_next<8> : tour_next<4>, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p, pts, q->label);
     // the order, from the matrix the last batch's read brought; then the legs are independent: leg j's field and start are fixed
-    memcpy(q->legs, q->host + SP_BATCH + 1, (size_t)(K + 1) * K * 4);
+    memcpy(q->legs, h->solve->host + kSolveCnt, (size_t)(K + 1) * K * 4);
     q->total = best_order(q->legs, K, q->order);
     TourLegs lg;
     lg.K = K;
@@ -250,7 +190,7 @@ int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, in
     hipLaunchKernelGGL(tour_walk, dim3((unsigned)K), dim3(64), 0, h->stream, p, lg, q->segs, q->walk_out);
     hipLaunchKernelGGL(tour_join, dim3(ST_JOIN_BLOCKS), dim3(256), 0, h->stream, p, lg, q->segs, q->walk_out, q->nodes, q->dirs);
     SCHK(h, hipGetLastError());
-    int32_t* wo = reinterpret_cast<int32_t*>(q->host + kCntWords);
+    int32_t* wo = reinterpret_cast<int32_t*>(h->solve->host + kSolveCnt + kSolveTail);
     SCHK(h, hipMemcpyAsync(wo, q->walk_out, 2 * YH_TOUR_MAX * 4, hipMemcpyDeviceToHost, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
     int32_t at = 0;
@@ -270,9 +210,8 @@ void scene_tour_free(yh_scene* h) {
     yh_scene_tour* q = h->tour;
     if (!q) return;
     free_fields(q);
-    void* bufs[] = { q->label, q->edge, q->edge2, q->cnt, q->walk_out };
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    if (q->host) (void)hipHostFree(q->host);
+    if (q->label) (void)hipFree(q->label);
+    if (q->walk_out) (void)hipFree(q->walk_out);
     delete q;
     h->tour = nullptr;
 }
@@ -313,13 +252,12 @@ int yh_scene_plan_tour_conn(yh_scene* h, const int32_t* targets_xy, int32_t n_ta
 int yh_scene_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs, float* total, float* cost, int32_t* next,
                        uint8_t* label, int32_t* path_xy, float* directions, int32_t* leg_ends, int32_t path_capacity, int32_t* path_len) {
     if (!h) return YH_EINVAL;
-    yh_scene_tour* q = h->tour;
-    if (!q || !q->planned) return h->fail(YH_ESTATE, "no tour has been made");
-    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the tour: plan the tour again");
-    if (path_len) *path_len = q->path_len;
-    if ((path_xy || directions) && path_capacity < q->path_len)
-        return h->fail(YH_EOVERFLOW, "path_capacity " + std::to_string(path_capacity) + " < the route's " + std::to_string(q->path_len) + " nodes");
-    const int K = (int)q->targets.size();
+    const yh_scene_tour* q = h->tour;
+    const int K = q ? (int)q->targets.size() : 0;
+    const size_t npx = (size_t)h->W * h->H;
+    const int rc = solve_read(h, "tour", "plan the tour again", q, { { cost, q ? q->cost : nullptr, K * npx * 4 }, { next, q ? q->next : nullptr, K * npx * 4 }, { label, q ? q->label : nullptr, npx } },
+                              path_xy, directions, path_capacity, path_len);
+    if (rc) return rc;
     if (n_targets) *n_targets = K;
     for (int b = 0; b < K; ++b) {
         if (targets_xy) { targets_xy[2 * b] = q->targets[b] % h->W; targets_xy[2 * b + 1] = q->targets[b] / h->W; }
@@ -328,39 +266,15 @@ int yh_scene_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int
     }
     if (legs) memcpy(legs, q->legs, (size_t)(K + 1) * K * 4);
     if (total) *total = q->total;
-    SCHK(h, hipSetDevice(h->dev));
-    const size_t npx = (size_t)h->W * h->H;
-    if (cost) SCHK(h, hipMemcpyAsync(cost, q->cost, K * npx * 4, hipMemcpyDeviceToHost, h->stream));
-    if (next) SCHK(h, hipMemcpyAsync(next, q->next, K * npx * 4, hipMemcpyDeviceToHost, h->stream));
-    if (label) SCHK(h, hipMemcpyAsync(label, q->label, npx, hipMemcpyDeviceToHost, h->stream));
-    if (path_xy) SCHK(h, hipMemcpyAsync(path_xy, q->nodes, (size_t)q->path_len * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
-    if (directions && q->path_len > 1) SCHK(h, hipMemcpyAsync(directions, q->dirs, (size_t)(q->path_len - 1) * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    SCHK(h, hipStreamSynchronize(h->stream));
     return YH_OK;
 }
 
 int yh_scene_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* rounds, int32_t* tile_runs) {
     if (!h || reps < 1 || !ms_per_tour) return YH_EINVAL;
     yh_scene_tour* q = h->tour;
-    if (!q || !q->planned) return h->fail(YH_ESTATE, "no tour has been made");
-    if (q->frame != h->frames) return h->fail(YH_ESTATE, "a newer frame has been appended since the tour: plan the tour again");
-    SCHK(h, hipSetDevice(h->dev));
-    hipEvent_t a, b;
-    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
-    SCHK(h, hipEventRecord(a, h->stream));
-    for (int r = 0; r < reps; ++r) {
-        const int rc = run_tour(h, q->targets, q->start, q->conn);
-        if (rc) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); q->planned = false; return rc; }
-    }
-    SCHK(h, hipEventRecord(b, h->stream));
-    SCHK(h, hipEventSynchronize(b));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    *ms_per_tour = ms / reps;   // (the host's waits for the batches' counters and its choice of the order are inside)
-    if (rounds) *rounds = (int32_t)q->rounds;
-    if (tile_runs) *tile_runs = (int32_t)q->tile_runs;
-    return YH_OK;
+    // (a failed replay has overwritten part of the last tour: it is gone; the host's choice of the order is inside the time)
+    auto run = [&] { const int rc = run_tour(h, q->targets, q->start, q->conn); if (rc) q->planned = false; return rc; };
+    return solve_time(h, "tour", "plan the tour again", q, reps, run, ms_per_tour, rounds, tile_runs);
 }
 
 }  // extern "C"
