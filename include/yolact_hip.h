@@ -443,6 +443,29 @@ int yh_scene_plan_tour_conn(yh_scene* h, const int32_t* targets_xy /* [n][2] or 
 int yh_scene_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs, float* total,
                        float* cost, int32_t* next, uint8_t* label, int32_t* path_xy, float* directions, int32_t* leg_ends,
                        int32_t path_capacity, int32_t* path_len);
+/* The turn-aware plan (DESIGN.md section 11 "Turns"): yh_scene_plan_conn(.., 8)'s graph over states (pixel, heading) with a price
+ * for turning in place, so that the route handed to a drive base does not zig-zag between near-equal headings. Heading h in 0 .. 7
+ * is the compass index 0 right (1, 0), 1 down-right, 2 down, 3 down-left, 4 left, 5 up-left, 6 up (0, -1), 7 up-right; h + 1 is
+ * clockwise on the image (y down), indices wrap. State (v, h) may drive to (v + s_h, h) for the 8-connected plan's edge term of
+ * that direction, fl(fl(d[h][v + s_h] + length) + height step), or turn to (v, h - 1) or (v, h + 1) for fl(d + turn_price).
+ * d f32 [8][h][w] is 0 at every target in every layer (arrive facing any way) and the minimum candidate elsewhere; act u8
+ * [8][h][w] is 255 at targets, else the first of (drive = 0, turn to h - 1 = 1, turn to h + 1 = 2) whose candidate equals d
+ * bitwise. The route follows act from (start, start_heading): turns in place add no node. Targets, start and every other rule as
+ * yh_scene_plan_conn with connectivity 8. Synchronous. Errors as yh_scene_plan_conn(.., 8), and YH_EINVAL for a heading outside
+ * 0 .. 7, for a turn price that is NaN, infinite or outside [1, 1024], and where (W + H) * (2 * max(H, 101) + 1) + 8 * 1024 >=
+ * 2^24. A call refused with YH_EINVAL or YH_ESTATE has touched nothing: an earlier turn plan of the same frame stays readable. A
+ * call that fails later (YH_EHIP) leaves no turn plan. The turn plan's buffers (cost 32, action 8, route and turns 20 bytes per
+ * pixel) are its own, allocated at the first call on a handle: a plan, a tour and a turn plan do not disturb each other's results. */
+int yh_scene_plan_turn(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                       int32_t start_x, int32_t start_y, int32_t start_heading /* 0 .. 7 */, float turn_price /* per 45 degrees */);
+/* The last turn plan; any pointer may be NULL. cost f32 [8][h][w], act u8 [8][h][w], path_xy i32 [cap][2] (the pixels visited,
+ * start and target included), and per drive step i of the route (*path_len - 1 of them): turns i32 [cap], the signed number of
+ * 45-degree steps made at node i before driving (+ towards h + 1; a reversal is -4, never more than 4 either way), and directions
+ * f32 [cap][2] = (the drive edge alone, d[h_i][n_i] - d[h_i][n_i+1] with h_i the heading driven; float32((4 - |turns[i]|) * pi /
+ * 4), at step 0 too: the start has a heading). YH_EOVERFLOW (and *path_len set, nothing copied) if path_capacity < *path_len
+ * while path_xy, directions or turns is asked for; YH_ESTATE before a turn plan, or when a frame was appended since. */
+int yh_scene_turn_read(yh_scene* h, float* cost, uint8_t* act, int32_t* path_xy, float* directions, int32_t* turns,
+                       int32_t path_capacity, int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

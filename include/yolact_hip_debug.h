@@ -124,6 +124,9 @@ int yh_scene_plan_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* r
 /* The same for the last yh_scene_plan_tour (the host's choice of the order and the walks fall inside too): rounds = launches in
  * which some tile of some field ran, tile_runs summed over the fields. */
 int yh_scene_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* rounds, int32_t* tile_runs);
+/* The same for the last yh_scene_plan_turn, replayed with its start heading and turn price: rounds and tile runs of the
+ * eight-layer field (a tile run relaxes the tile in all eight layers). */
+int yh_scene_turn_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs);
 
 /* Test hook: copies the named intermediate tensor of the last forward (layer names of DESIGN.md:
  * "stem", "pool", "c2".."c5", "lat3".."lat5", "p3".."p7", "proto0".."proto3", "proto_up", "head_t0"..) to

@@ -1,5 +1,5 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
-// scene_tour.hip (the tour over several targets) and scene_solve.hip (the field solver both of them run on).
+// scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan) and scene_solve.hip (the field solver they run on).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 
 struct yh_scene_path;   // the planner's fields, route and last plan (scene_path.hip); allocated at the first yh_scene_plan
 struct yh_scene_tour;   // the tour's fields, route and last tour (scene_tour.hip); allocated at the first yh_scene_plan_tour
+struct yh_scene_turn;   // the turn-aware planner's fields, route and last turn plan (scene_turn.hip); allocated at the first yh_scene_plan_turn
 struct yh_scene_solve;  // the solver's buffers, one set for both (scene_path_dev.h, scene_solve.hip); allocated at the first of either
 
 struct yh_scene {
@@ -37,6 +38,7 @@ struct yh_scene {
     std::string diag_why;
     yh_scene_path* path = nullptr;
     yh_scene_tour* tour = nullptr;
+    yh_scene_turn* turn = nullptr;
     yh_scene_solve* solve = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -46,6 +48,7 @@ struct yh_scene {
 namespace yh {
 void scene_path_free(yh_scene* h);   // yh_scene_destroy: the planner's buffers (the handle's device is current, its stream idle)
 void scene_tour_free(yh_scene* h);
+void scene_turn_free(yh_scene* h);
 void scene_solve_free(yh_scene* h);
 // yh_scene_plan's checks (frame, mode, size guard, start, targets) and its choice of targets, as linear indices; touches nothing
 int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets);

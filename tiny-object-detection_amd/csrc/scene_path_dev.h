@@ -1,6 +1,7 @@
 // scene_path_dev.h — what scene_path.hip (one multi-source field, yh_scene_plan) and scene_tour.hip (K single-target fields,
 // yh_scene_plan_tour) share: the field solver of scene_solve.hip, declared here, and the planner's device code - the tile relaxation, the
-// successor rule and the windowed chase. What they compute and why it is unique is said at the head of scene_path.hip.
+// successor rule and the windowed chase. scene_turn.hip (the turn-aware plan, yh_scene_plan_turn) runs its own round kernel through the
+// same host loop (SolveRound) and takes its edge terms through around<8>. What they compute and why it is unique is said at the head of scene_path.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,14 +67,18 @@ struct SolveLast {
     float2* dirs = nullptr;
 };
 struct SolveCopy { void* dst; const void* src; size_t bytes; };   // a device array a read hands out (skipped if dst is null)
+// A round kernel other than field_round (the turn planner's, scene_turn.hip): launch(tiles, parity, cnt_next) enqueues one round over
+// the grid of tiles with the flags of that parity; states: the states per pixel, which scale the round cap
+struct SolveRound { std::function<void(const dim3&, int, uint32_t*)> launch; int states; };
 
 // Allocates what F fields of connectivity conn need, fills p (but cost and next: the caller's), enqueues path_weights (once for all fields)
 int solve_begin(yh_scene* h, int conn, int F, PathParams& p);
 // Relaxes the F fields at p.cost, which the caller has filled (+inf, 0 at the seeds), to their fixed points. seeds: the pixels that
 // start at 0, equally many per field, field by field. who: "path" or "tour", for the error text. after(tail), if given, enqueues
 // the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) arrives in host[kSolveCnt ..] with the counters.
+// own, if given, is the round kernel in place of field_round<conn> (round 0's flags still follow conn).
 int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words = 0,
-                 const std::function<void(uint32_t*)>& after = nullptr);
+                 const std::function<void(uint32_t*)>& after = nullptr, const SolveRound* own = nullptr);
 // run() reps times between two events; a failing run's code is returned as it is. kind, again: for the error texts ("plan", "plan again")
 int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast* q, int reps, const std::function<int()>& run, float* ms, int32_t* rounds, int32_t* tile_runs);
 // The checks of the read entry points (a run of this frame exists, the capacity holds the route), then the copies

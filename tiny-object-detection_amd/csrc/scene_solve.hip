@@ -81,7 +81,7 @@ int solve_begin(yh_scene* h, int conn, int F, PathParams& p) {
 }
 
 int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words,
-                 const std::function<void(uint32_t*)>& after) {
+                 const std::function<void(uint32_t*)>& after, const SolveRound* own) {
     yh_scene_solve* s = h->solve;
     // round 0's work list: parity 0 of [2][F][ntiles]; parity 1 goes up in the same copy, all zero
     const size_t per = seeds.size() / F, nflags = (size_t)F * p.ntiles;
@@ -98,14 +98,15 @@ int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::v
     }
     SCHK(h, hipMemcpyAsync(s->flags, s->flags0.data(), 2 * nflags * 4, hipMemcpyHostToDevice, h->stream));
     s->rounds = 0; s->tile_runs = 0;
-    const long long cap = (long long)h->W * h->H;   // costs only decrease over a finite set: this never fires
+    const long long cap = (long long)h->W * h->H * (own ? own->states : 1);   // costs only decrease over a finite set: this never fires
     const dim3 tiles((unsigned)s->tx, (unsigned)s->ty, (unsigned)F);
     long long round = 0;
     while (active) {
-        if (round >= cap) return h->fail(YH_EHIP, std::string(who) + " solver: round cap W*H reached without convergence (fields not those of a SANE frame?)");
+        if (round >= cap) return h->fail(YH_EHIP, std::string(who) + " solver: round cap " + (own ? std::to_string(own->states) + "*" : "") + "W*H reached without convergence (fields not those of a SANE frame?)");
         SCHK(h, hipMemsetAsync(s->cnt, 0, kSolveCnt * 4, h->stream));
         for (int j = 0; j < SP_BATCH; ++j, ++round)
-            hipLaunchKernelGGL(conn == 8 ? field_round<8> : field_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, F, (int)(round & 1), s->cnt + j + 1);
+            if (own) own->launch(tiles, (int)(round & 1), s->cnt + j + 1);
+            else hipLaunchKernelGGL(conn == 8 ? field_round<8> : field_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, F, (int)(round & 1), s->cnt + j + 1);
         if (after) after(s->cnt + kSolveCnt);
         SCHK(h, hipGetLastError());
         SCHK(h, hipMemcpyAsync(s->host, s->cnt, (size_t)(kSolveCnt + tail_words) * 4, hipMemcpyDeviceToHost, h->stream));

@@ -157,6 +157,9 @@ SYMBOLS = [
     ("yh_scene_plan_tour_conn", _i, [_vp, _vp, _i, _i, _i, _i]),
     ("yh_scene_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_plan_turn", _i, [_vp, _vp, _i, _i, _i, _i, _f]),
+    ("yh_scene_turn_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
@@ -901,6 +904,44 @@ class Scene:
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_tour_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_tour=ms.value, rounds=r.value, tile_runs=t.value)
+
+
+    def plan_turn(self, targets=None, n_targets=3, start=None, heading=6, turn_price=2.0):
+        """The turn-aware plan (DESIGN.md §11 "Turns"): the 8-connected planner over states (pixel, heading) with turn_price per
+        45 degrees turned in place. targets, n_targets, start as plan(); heading: the start heading 0 .. 7 (0 right, clockwise on
+        the image; 6, the default, is up: the camera looks up the bird's-eye map from START_NODE)."""
+        if start is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
+            start = (400, 479)
+        if targets is None:
+            self._chk(self.L.yh_scene_plan_turn(self.h, None, n_targets, start[0], start[1], heading, turn_price))
+        else:
+            t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+            self._chk(self.L.yh_scene_plan_turn(self.h, _p(t), len(t), start[0], start[1], heading, turn_price))
+
+    def read_turn(self, fields=True):
+        """The last turn plan: path int32 [L][2], directions f32 [L - 1][2] (magnitude, rotation), turns int32 [L - 1] (signed
+        45-degree steps made before each drive), and with fields=True cost f32 [8][H][W] and act uint8 [8][H][W] (0 drive, 1 turn
+        to h - 1, 2 turn to h + 1, 255 at targets)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_scene_turn_read(self.h, None, None, None, None, None, 0, C.byref(n)))
+        out = dict(path=np.zeros((n.value, 2), np.int32))
+        dirs, turns = np.zeros((n.value, 2), np.float32), np.zeros(n.value, np.int32)
+        if fields:
+            out["cost"] = np.zeros((8, self.H, self.W), np.float32)
+            out["act"] = np.zeros((8, self.H, self.W), np.uint8)
+        self._chk(self.L.yh_scene_turn_read(self.h, _p(out["cost"]) if fields else None, _p(out["act"]) if fields else None,
+                                            _p(out["path"]), _p(dirs), _p(turns), n.value, C.byref(n)))
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        out["turns"] = turns[:max(n.value - 1, 0)]
+        return out
+
+    def turn_time(self, reps=20):
+        """Replays the last turn plan: dict(ms_per_plan, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_turn_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
 
 
 def serialize_path(directions, created_secs):

@@ -1,4 +1,4 @@
-"""Registers / spills / LDS of every kernel in lib/libyolact_hip.so (code-object metadata), optionally filtered by substrings.
+"""Registers / spills / LDS / scratch bytes of every kernel in lib/libyolact_hip.so (code-object metadata), optionally filtered by substrings.
 Usage: python tools/kernel_meta.py [substr ...]"""
 import os, re, subprocess, sys, tempfile, shutil, glob
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +17,6 @@ try:
             dem = subprocess.run(["c++filt", name.group(1)], capture_output=True, text=True).stdout.strip()
             dem = dem.replace("void yh::", "").replace("(yh::ConvParams)", "").replace("(yh::BneckParams)", "")
             if all(s in dem for s in sys.argv[1:]):
-                print(f"vgpr {f('vgpr_count'):>3} spill {f('vgpr_spill_count'):>3} lds {f('group_segment_fixed_size'):>6}  {dem[:150]}")
+                print(f"vgpr {f('vgpr_count'):>3} spill {f('vgpr_spill_count'):>3} lds {f('group_segment_fixed_size'):>6} scratch {f('private_segment_fixed_size'):>4}  {dem[:150]}")
 finally:
     shutil.rmtree(tmp)
