@@ -303,6 +303,30 @@ const uint32_t* yh_instance_device_frame(const yh_engine* h);
  * count set, nothing copied) if capacity < m rows; YH_ESTATE before an instance frame. */
 int yh_instance_read(yh_engine* h, int32_t* n_instances, int32_t* table, int32_t capacity);
 
+/* ---- instance tracks: ids that persist from frame to frame (DESIGN.md section 11 "Instance tracks") ---------------------------
+ * yh_instance_frame's id is the detection's place among its class in THIS frame's score order, so two balls swap ids whenever their
+ * scores cross. yh_instance_track is the same call with the ids taken from the handle's tracker instead: 128 slots, each with a
+ * class, an id, an age (tracked calls since it was last matched) and its last seen mask at prototype resolution. Per call, on the
+ * device: the overlap I of every live slot's mask with every eligible detection's, the candidate pairs of equal class with I > 0
+ * and 1000 I >= iou_permille (area_slot + area_det - I), matched greedily by largest I / U (ties: smaller age, rank, slot); an
+ * unmatched slot ages and dies when age > max_age; an unmatched detection takes the smallest free slot (the oldest lost slots make
+ * room if need be) and the smallest id no live slot of its class holds, so a ball that returns within max_age calls gets its id
+ * back and a newcomer never takes it. The frame and the instance table are yh_instance_frame's with the track id in the id's
+ * place; on an empty tracker they are exactly yh_instance_frame's.
+ * States and errors are yh_instance_frame's, plus YH_EINVAL for iou_permille outside 1 .. 1000 or max_age outside 0 .. 255. A
+ * refused call has touched nothing (tracker, frame, tables); a call that fails later leaves an empty tracker and no frame. On
+ * return yh_instance_device_frame and yh_instance_read show this frame. yh_instance_frame neither reads nor changes the tracker.
+ * The tracker is created at the first tracked call and freed by yh_destroy. */
+int yh_instance_track(yh_engine* h, int32_t frame, int32_t width, int32_t height, const uint8_t* class_map, float min_score,
+                      int32_t iou_permille, int32_t max_age, uint32_t* out_host /* or NULL */);
+/* The tracker after the last tracked call: i32 [m][6] = (slot, output class, id, age, area at prototype resolution, detection rank
+ * in that call or -1), one row per live slot in slot order. Conventions of yh_instance_read: table may be NULL, YH_EOVERFLOW (the
+ * count set, nothing copied) if capacity < m rows; YH_ESTATE before any tracked call. */
+int yh_instance_tracks_read(yh_engine* h, int32_t* n_tracks, int32_t* table, int32_t capacity);
+/* Empties the tracker (the next tracked call sees no slot; a track table already readable becomes empty). Valid at any time, also
+ * before the first tracked call; the instance frame is not touched. */
+int yh_instance_track_reset(yh_engine* h);
+
 /* ---- reference-compat path: Yolact::classify (src/yolact.rs:39-41, :192-234) --------------- */
 
 /* In-place classify of one packed camera frame: `frame` holds width*height u32 pixels packed

@@ -226,6 +226,12 @@ int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const 
 int yh_op_instance_frame(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
                          int32_t width, int32_t height, const uint8_t* class_map, float min_score, uint32_t* out_host, int32_t* table,
                          int32_t table_capacity, int32_t* n_instances);
+/* A tracked call (yh_instance_track) on caller-provided detections: yh_op_instance_frame's arguments plus iou_permille and max_age;
+ * the same kernels run, on the handle's tracker, so successive calls form a sequence that can be checked at tiny shapes without a
+ * network (a call at another hp x wp starts from an empty tracker). The track table is then read with yh_instance_tracks_read. */
+int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
+                         int32_t width, int32_t height, const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age,
+                         uint32_t* out_host, int32_t* table, int32_t table_capacity, int32_t* n_instances);
 
 #ifdef __cplusplus
 }

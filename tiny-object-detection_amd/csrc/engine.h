@@ -1,6 +1,6 @@
 // engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
 // Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
-// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
+// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip and instance_track.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -183,6 +183,16 @@ struct yh_engine {
     uint32_t inst_meta_host[256] = {};   // where inst_meta is read back to (a member: the copy is asynchronous)
     std::vector<int32_t> inst_table;   // [inst_rows][4] = (rank, class, id, pixels) of the last instance frame
     int inst_rows = -1;             // -1: no instance frame yet
+    // instance tracks (instance_track.hip): allocated at the first yh_instance_track, freed by yh_destroy
+    uint4* trk_img = nullptr;       // T [hp * wp]: bit s = slot s's last seen mask is on there
+    uint32_t* trk_ov = nullptr;     // I [128][128] then A [128]: zeroed on the stream by every tracked call
+    int32_t* trk_state = nullptr;   // slots [128][4] = (class or 0, id, age, area), rank of slot, slot of rank, keep [4]
+    size_t trk_img_cap = 0;
+    int trk_hp = 0, trk_wp = 0;     // the prototype size T was built at
+    bool trk_live = false;          // false: the next tracked call starts from an empty tracker
+    int32_t trk_host[640] = {};     // where the slots and their ranks are read back to (a member: the copy is asynchronous)
+    std::vector<int32_t> trk_table; // [trk_rows][6] = (slot, class, id, age, area, rank or -1) after the last tracked call
+    int trk_rows = -1;              // -1: no tracked call yet
     // output staging
     float* out_f32 = nullptr;
     size_t out_f32_cap = 0;
@@ -245,9 +255,17 @@ int upload_panels(yh_engine* h, const uint8_t* blob);
 int ensure_blob(yh_engine* h);
 // instance.hip
 const char* instance_check(int width, int height, const uint8_t* class_map, int ncls, float min_score);   // nullptr: fine
+struct InstTrack { int iou_permille, max_age; };   // a tracked call's parameters (instance_run: nullptr = yh_instance_frame's ids)
 int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
-                 int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host);
+                 int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrack* trk = nullptr);
 void instance_free(yh_engine* h);
+// instance_track.hip: the stages instance_run puts between inst_pack and inst_paint, behind the read-back and behind the wait
+const char* track_check(int iou_permille, int max_age);   // nullptr: fine
+int track_enqueue(yh_engine* h, int hp, int wp, const InstTrack& trk);
+int track_readback(yh_engine* h);
+void track_finish(yh_engine* h);
+void track_drop(yh_engine* h);   // an empty tracker (a tracked call that failed, yh_instance_track_reset)
+void track_free(yh_engine* h);
 // fp8.hip
 void plan_fp8(yh_engine* h);
 std::string fp8_missing(const yh_engine* h);

@@ -343,16 +343,19 @@ int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const 
     return YH_OK;
 }
 
-// The instance frame's kernels (instance.hip) on caller-provided masks of any hp x wp: what yh_instance_frame runs on the tail's.
-int yh_op_instance_frame(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
-                         int32_t width, int32_t height, const uint8_t* class_map, float min_score, uint32_t* out_host, int32_t* table,
-                         int32_t table_capacity, int32_t* n_instances) {
+// The instance frame's kernels (instance.hip) on caller-provided masks of any hp x wp: what yh_instance_frame runs on the tail's
+// (trk: what yh_instance_track runs, instance_track.hip's kernels between them).
+static int op_instance_impl(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp,
+                            int32_t wp, int32_t width, int32_t height, const uint8_t* class_map, float min_score, uint32_t* out_host,
+                            int32_t* table, int32_t table_capacity, int32_t* n_instances, const InstTrack* trk) {
     if (!h || !out_host || !n_instances || (n > 0 && (!masks || !class_ids || !scores))) return YH_EINVAL;
     if (n < 0 || n > h->cfg.max_dets) return h->fail(YH_EINVAL, "instance frame op: n outside 0 .. max_dets");
     if (hp < 1 || hp > 4096 || wp < 1 || wp > 4096) return h->fail(YH_EINVAL, "instance frame op: hp and wp must be in 1 .. 4096");
     for (int d = 0; d < n; ++d)
         if (class_ids[d] < 0 || class_ids[d] >= h->C - 1) return h->fail(YH_EINVAL, "instance frame op: class id out of range");
     if (const char* why = instance_check(width, height, class_map, h->C - 1, min_score)) return h->fail(YH_EINVAL, why);
+    if (trk)
+        if (const char* why = track_check(trk->iou_permille, trk->max_age)) return h->fail(YH_EINVAL, why);
     HIPCHK(h, hipSetDevice(h->dev));
     const size_t px = (size_t)hp * wp;
     std::vector<yh_detection> dets((size_t)(n > 0 ? n : 1));
@@ -364,9 +367,27 @@ int yh_op_instance_frame(yh_engine* h, const uint8_t* masks, const int32_t* clas
     if (n > 0) st.put(dm, masks, (size_t)n * px);
     const yh_detection* dd = st.upload<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
     const int* dc = st.upload<int>(&n, sizeof(int));
-    if (const int rc = st.status(h, "instance frame op: ")) return rc;
-    if (const int rc = instance_run(h, dm, dd, dc, h->cfg.max_dets, hp, wp, width, height, class_map, min_score, out_host)) return rc;
+    if (const int rc = st.status(h, "instance frame op: ")) {
+        if (trk) track_drop(h);
+        return rc;
+    }
+    if (const int rc = instance_run(h, dm, dd, dc, h->cfg.max_dets, hp, wp, width, height, class_map, min_score, out_host, trk)) return rc;
     return yh_instance_read(h, n_instances, table, table_capacity);
+}
+
+int yh_op_instance_frame(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
+                         int32_t width, int32_t height, const uint8_t* class_map, float min_score, uint32_t* out_host, int32_t* table,
+                         int32_t table_capacity, int32_t* n_instances) {
+    return op_instance_impl(h, masks, class_ids, scores, n, hp, wp, width, height, class_map, min_score, out_host, table, table_capacity,
+                            n_instances, nullptr);
+}
+
+int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, int32_t n, int32_t hp, int32_t wp,
+                         int32_t width, int32_t height, const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age,
+                         uint32_t* out_host, int32_t* table, int32_t table_capacity, int32_t* n_instances) {
+    const InstTrack trk = { iou_permille, max_age };
+    return op_instance_impl(h, masks, class_ids, scores, n, hp, wp, width, height, class_map, min_score, out_host, table, table_capacity,
+                            n_instances, &trk);
 }
 
 }  // extern "C"

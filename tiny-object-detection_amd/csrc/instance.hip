@@ -153,8 +153,10 @@ const char* instance_check(int width, int height, const uint8_t* class_map, int 
     return nullptr;
 }
 
-int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
-                 int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host) {
+// One call: inst_pack, for a tracked call the tracker's kernels (instance_track.hip: inst_match rewrites the values inst_paint
+// reads), inst_paint, then the one wait behind the read-back of the table (and of the slots).
+static int run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp, int width,
+               int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrack* trk) {
     const int ncls = h->C - 1, px = hp * wp;
     const size_t npx = (size_t)width * height;
     int rc;
@@ -174,6 +176,7 @@ int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, c
     const dim3 gp((unsigned)((px + 4 * kPackLanes - 1) / (4 * kPackLanes)), kRanks / 32);
     hipLaunchKernelGGL(inst_pack, gp, dim3(kPackLanes), 0, h->stream, masks, dets, count, max_n, px, (const uint8_t*)h->inst_cmap, ncls,
                        min_score, (uint32_t*)h->inst_bits, h->inst_meta);
+    if (trk && (rc = track_enqueue(h, hp, wp, *trk))) return rc;
     const dim3 gq((unsigned)((width + kPaintX - 1) / kPaintX), (unsigned)((height + kPaintY - 1) / kPaintY));
     hipLaunchKernelGGL(inst_paint, gq, dim3(kPaintX, kPaintY), 0, h->stream, (const uint4*)h->inst_bits, hp, wp, width, height, h->inst_meta,
                        h->inst_frame);
@@ -181,8 +184,10 @@ int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, c
     uint32_t* meta = h->inst_meta_host;
     static_assert(sizeof h->inst_meta_host == 2 * kRanks * 4, "inst_meta_host holds the values and the counts of every rank");
     HIPCHK(h, hipMemcpyAsync(meta, h->inst_meta, sizeof h->inst_meta_host, hipMemcpyDeviceToHost, h->stream));
+    if (trk && (rc = track_readback(h))) return rc;
     if (out_host) HIPCHK(h, hipMemcpyAsync(out_host, h->inst_frame, npx * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (trk) track_finish(h);
     h->inst_table.clear();
     for (int d = 0; d < kRanks; ++d)
         if (meta[d] != 0) {
@@ -193,11 +198,19 @@ int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, c
     return YH_OK;
 }
 
+int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
+                 int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrack* trk) {
+    const int rc = run(h, masks, dets, count, max_n, hp, wp, width, height, class_map, min_score, out_host, trk);
+    if (rc != YH_OK && trk) track_drop(h);   // a tracked call that failed leaves an empty tracker (and, as any failed call, no frame)
+    return rc;
+}
+
 void instance_free(yh_engine* h) {
     if (h->inst_bits) hipFree(h->inst_bits);
     if (h->inst_frame) hipFree(h->inst_frame);
     if (h->inst_meta) hipFree(h->inst_meta);
     if (h->inst_cmap) hipFree(h->inst_cmap);
+    track_free(h);
 }
 
 }  // namespace yh

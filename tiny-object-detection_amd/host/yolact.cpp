@@ -94,6 +94,32 @@ std::vector<std::int32_t> Yolact::instance_frame(int frame, int width, int heigh
 
 const std::uint32_t* Yolact::instance_device_frame() const { return engine_ ? yh_instance_device_frame(engine_) : nullptr; }
 
+std::vector<std::int32_t> Yolact::instance_track(int frame, int width, int height, const std::uint8_t* class_map, float min_score,
+                                                 int iou_permille, int max_age, std::uint32_t* frame_out) {
+    if (!engine_) expect_failed("instance_track", "the detection tail belongs to the YOLACT engine");
+    if (yh_instance_track(engine_, frame, width, height, class_map, min_score, iou_permille, max_age, frame_out) != YH_OK)
+        expect_failed("instance track failed", yh_last_error(engine_));
+    std::int32_t m = 0;
+    if (yh_instance_read(engine_, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    std::vector<std::int32_t> table(static_cast<std::size_t>(m) * 4);
+    if (yh_instance_read(engine_, &m, table.data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    return table;
+}
+
+std::vector<std::int32_t> Yolact::tracks() {
+    if (!engine_) expect_failed("tracks", "the detection tail belongs to the YOLACT engine");
+    std::int32_t m = 0;
+    if (yh_instance_tracks_read(engine_, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    std::vector<std::int32_t> table(static_cast<std::size_t>(m) * 6);
+    if (yh_instance_tracks_read(engine_, &m, table.data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    return table;
+}
+
+void Yolact::track_reset() {
+    if (!engine_) expect_failed("track_reset", "the detection tail belongs to the YOLACT engine");
+    if (yh_instance_track_reset(engine_) != YH_OK) expect_failed("track reset failed", yh_last_error(engine_));
+}
+
 // ---- YolactGroup ---------------------------------------------------------------------------------------------------
 YolactGroup YolactGroup::init(const GroupOptions& opt) {
     YolactGroup y;

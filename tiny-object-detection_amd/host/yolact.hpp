@@ -58,6 +58,14 @@ public:
     std::vector<std::int32_t> instance_frame(int frame, int width, int height, const std::uint8_t* class_map = nullptr,
                                              float min_score = 0.0f, std::uint32_t* frame_out = nullptr);
     const std::uint32_t* instance_device_frame() const;
+    // The same with ids that persist from frame to frame (yh_instance_track): the detections are matched to the engine's tracker by
+    // mask overlap (IoU >= iou_permille / 1000), a track that is not seen lives max_age further calls. The instance table carries
+    // the track ids. tracks(): six values per live track - slot, output class, id, age, area, rank in the last call or -1.
+    std::vector<std::int32_t> instance_track(int frame, int width, int height, const std::uint8_t* class_map = nullptr,
+                                             float min_score = 0.0f, int iou_permille = 300, int max_age = 2,
+                                             std::uint32_t* frame_out = nullptr);
+    std::vector<std::int32_t> tracks();
+    void track_reset();
 
     static std::string version();      // edgetpu::version(), scene.rs:62
 

@@ -164,6 +164,9 @@ SYMBOLS = [
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
     ("yh_instance_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
+    ("yh_instance_track", _i, [_vp, _i, _i, _i, _vp, _f, _i, _i, _vp]),
+    ("yh_instance_tracks_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
+    ("yh_instance_track_reset", _i, [_vp]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_last_conv_launches", _i, [_vp]),
@@ -185,6 +188,7 @@ SYMBOLS = [
     ("yh_op_maxpool3x3s2_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     ("yh_op_detect", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
     ("yh_op_instance_frame", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_op_instance_track", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(_i)]),
 ]
 
 
@@ -492,6 +496,49 @@ class Engine:
         self._chk(self.L.yh_op_instance_frame(self.h, _p(masks), _p(ids), _p(sc), n, hp, wp, width, height,
                                               _p(cm) if cm is not None else None, C.c_float(min_score), _p(out), _p(table),
                                               len(table), C.byref(m)))
+        return out, table[:m.value].copy()
+
+    # ---- instance tracks (DESIGN.md §11 "Instance tracks")
+    @staticmethod
+    def _permille(min_iou):
+        return int(round(float(min_iou) * 1000.0))
+
+    def instance_track(self, frame, width, height, class_map=None, min_score=0.0, min_iou=0.3, max_age=2, read=True):
+        """yh_instance_track: instance_frame with ids that persist - the detections are matched to the handle's tracker by mask
+        overlap (IoU >= min_iou, rounded to per-mille), a track that is not seen lives max_age further calls. The instance table
+        (instances) carries the track ids; the tracker itself: tracks."""
+        cm = self._class_map(class_map)
+        out = np.zeros((height, width), np.uint32) if read else None
+        self._chk(self.L.yh_instance_track(self.h, frame, width, height, _p(cm) if cm is not None else None, C.c_float(min_score),
+                                           self._permille(min_iou), int(max_age), _p(out) if read else None))
+        return out
+
+    def tracks(self):
+        """The tracker after the last tracked call: int32 [m][6] = (slot, output class, id, age, area, rank or -1)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_instance_tracks_read(self.h, C.byref(n), None, 0))
+        t = np.zeros((n.value, 6), np.int32)
+        self._chk(self.L.yh_instance_tracks_read(self.h, C.byref(n), _p(t), n.value))
+        return t
+
+    def track_reset(self):
+        """yh_instance_track_reset: an empty tracker."""
+        self._chk(self.L.yh_instance_track_reset(self.h))
+
+    def op_instance_track(self, masks, class_ids, scores, width, height, class_map=None, min_score=0.0, min_iou=0.3, max_age=2):
+        """yh_op_instance_track: a tracked call on caller-provided masks uint8 [n][hp][wp], class ids and scores in rank order;
+        successive calls form the sequence. Returns (frame uint32 [height][width], instance table int32 [m][4])."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        n, hp, wp = masks.shape
+        ids = np.ascontiguousarray(class_ids, np.int32).reshape(n)
+        sc = np.ascontiguousarray(scores, np.float32).reshape(n)
+        cm = self._class_map(class_map)
+        out = np.zeros((height, width), np.uint32)
+        table = np.zeros((self.cfg.max_dets, 4), np.int32)
+        m = C.c_int32()
+        self._chk(self.L.yh_op_instance_track(self.h, _p(masks), _p(ids), _p(sc), n, hp, wp, width, height,
+                                              _p(cm) if cm is not None else None, C.c_float(min_score), self._permille(min_iou),
+                                              int(max_age), _p(out), _p(table), len(table), C.byref(m)))
         return out, table[:m.value].copy()
 
     # ---- reference-compat path
