@@ -135,6 +135,16 @@ int yh_scene_turn_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* r
 int yh_debug_read_tensor(yh_engine* h, const char* name, float* dst_host, size_t nfloats, int32_t dims[4]);
 /* Same for ONE frame of the batch (dims receives {1,h,w,c}): a batch-64 tensor is gigabytes as f32. */
 int yh_debug_read_tensor_frame(yh_engine* h, const char* name, int32_t frame, float* dst_host, size_t nfloats, int32_t dims[4]);
+/* Test hook, fp8 precision: the raw OCP E4M3 codes of the named tensor's E4M3 twin for ONE frame, as the last step wrote them (NHWC, one
+ * byte per element, no decoding); dims receives {1,h,w,c}; dst may be NULL to ask for the dims. The value of a code is
+ * table[code] * s[channel] with the channel scales of the tensor's allocation (yh_fp8_layer_channel_scales of a layer that reads it).
+ * Pyramid level slices ("p3".."p7") work as in yh_debug_read_tensor. YH_ESTATE (with a reason in yh_last_error) when the handle does
+ * not run its fp8 forward (f16 precision, scales not set) or the plan does not write that form of this tensor. */
+int yh_debug_read_tensor_e4m3(yh_engine* h, const char* name, int32_t frame, uint8_t* dst, size_t n, int32_t dims[4]);
+/* Test hook, fp8 precision: E4M3 layer layer_index's (yh_fp8_layer_info) weight codes as its kernel reads them, codes[cout][k*k*cin]
+ * (K index = tap * cin + c), and the per-output-channel scales s_w[cout] of its epilogue; dims receives {cout, k*k*cin}; codes / s_w
+ * may be NULL. YH_ESTATE while no weights are loaded or the layer's input tensor has no scales. */
+int yh_debug_fp8_weights(yh_engine* h, int32_t layer_index, uint8_t* codes, float* s_w, int32_t dims[2]);
 /* Test hook: number of conv kernel launches the last yh_op_conv2d_f16 on this handle was planned as
  * (1 = single launch, 2 = two-phase or channel-split plan; the split-K reduce is not counted). */
 int yh_debug_last_conv_launches(const yh_engine* h);
@@ -206,6 +216,10 @@ int yh_op_stem_pool_rgb8(yh_engine* h, const uint8_t* rgb, int32_t n, int32_t S,
 /* The quantiser of the fp8 forward (the producers' epilogues apply the same conversion): y[i] = OCP FP8 E4M3 code of
  * x[i] * inv_scale (x: f16 bits), round to nearest even, saturating at +-448, NaN -> 0x7F | sign. */
 int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_scale, uint8_t* y);
+/* The calibration's kernel (yh_fp8_calibrate) on caller data: out_bits[c] = the bit pattern of max over rows of |x[r][c]| as f32, x:
+ * [rows][C] f16 bits in host memory. A NaN in a channel wins (a NaN pattern comes back), Inf lies above every finite value.
+ * YH_EINVAL for a C the kernel's launcher rejects (C % 8 != 0 or 256 % (C / 8) != 0). */
+int yh_op_absmax_channels_f16(yh_engine* h, const uint16_t* x, int64_t rows, int32_t C, uint32_t* out_bits);
 /* One fp8 convolution on the 256 x 256 tile the YH_PRECISION_FP8 forward uses: x[n][hh][ww][cin] and w[cout][k][k][cin]
  * are E4M3 codes (cin % 128 == 0), f32 accumulation on the block-scaled MFMA with unit block scales,
  * y = act(acc * scale[ch] + bias[ch] + residual) rounded to f16. If reps > 0, *ms_per_launch receives the mean

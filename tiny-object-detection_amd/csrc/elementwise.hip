@@ -264,32 +264,35 @@ __global__ __launch_bounds__(256) void rowmax_scaled_f16(const half_t* __restric
     __syncthreads();
     if (threadIdx.x == 0) { m = red[0]; for (int i = 1; i < 4; ++i) m = red[i] > m ? red[i] : m; out[blockIdx.x] = __float_as_uint(m); }
 }
-// max |x| per CHANNEL of an f16 tensor [rows][C] (C a multiple of 8, 256 % (C / 8) == 0), combined with atomicMax on bit patterns
+// max |x| per CHANNEL of an f16 tensor [rows][C] (C a multiple of 8, 256 % (C / 8) == 0), combined with atomicMax on bit patterns.
+// The maximum is taken on the bit patterns of |x| as f32 from the first load on: as unsigned integers they order like the values,
+// Inf lies above every finite value and every NaN above Inf - a NaN anywhere in a channel WINS, and the caller's "not below 3e38" test
+// (yh_fp8_calibrate) sees it. (A float compare a > m drops a NaN: a channel with a NaN and no Inf used to calibrate from its finite values.)
 __global__ __launch_bounds__(256) void absmax_channels_f16(const half_t* __restrict__ x, long long rows, int C, unsigned* __restrict__ out) {
     const int c8 = C >> 3, cg = threadIdx.x % c8, rl = threadIdx.x / c8, rpb = 256 / c8;
-    float m[8];
+    unsigned m[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) m[e] = 0.0f;
+    for (int e = 0; e < 8; ++e) m[e] = 0u;
     for (long long r = (long long)blockIdx.x * rpb + rl; r < rows; r += (long long)gridDim.x * rpb) {
         const half8 v = *(const half8*)(x + r * C + cg * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const float a = fabsf((float)v[e]); m[e] = a > m[e] ? a : m[e]; }   // (NaN never wins)
+        for (int e = 0; e < 8; ++e) { const unsigned a = __float_as_uint((float)v[e]) & 0x7FFFFFFFu; m[e] = a > m[e] ? a : m[e]; }
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) atomicMax(out + cg * 8 + e, __float_as_uint(m[e]));
+    for (int e = 0; e < 8; ++e) atomicMax(out + cg * 8 + e, m[e]);
 }
 
-// max |x| over an f16 range, as the bit pattern of a non-negative float (monotone as unsigned): one atomicMax per wave
+// max |x| over an f16 range, as the bit pattern of a non-negative float (monotone as unsigned; a NaN wins, as above): one atomicMax per wave
 __global__ __launch_bounds__(256) void absmax_f16(const half_t* __restrict__ x, long long n8, unsigned* __restrict__ out) {
-    float m = 0.0f;
+    unsigned m = 0u;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
         const half8 v = *(const half8*)(x + i * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const float a = fabsf((float)v[e]); m = a > m ? a : m; }   // (NaN never wins)
+        for (int e = 0; e < 8; ++e) { const unsigned a = __float_as_uint((float)v[e]) & 0x7FFFFFFFu; m = a > m ? a : m; }
     }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const float o = __shfl_xor(m, d); m = o > m ? o : m; }
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+    for (int d = 32; d >= 1; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)m, d); m = o > m ? o : m; }
+    if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 
 __global__ __launch_bounds__(256) void dequant_e4m3_f32(const uint8_t* __restrict__ x, float* __restrict__ y, long long n, const float* __restrict__ scale_ch, int C) {

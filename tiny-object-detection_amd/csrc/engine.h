@@ -142,7 +142,7 @@ struct yh_engine {
     std::vector<int> fp8_ops;           // indices of the ops that read E4M3 operands
     std::set<std::string> q_only;       // named tensors that exist only as E4M3 while fp8 is active
     bool fp8_active = false;            // the op list currently runs its fp8 form (false during calibration and in f16 engines)
-    bool fp8_ready = false;             // scales calibrated
+    bool fp8_ready = false;             // every E4M3 layer's input tensor has its scales (no E4M3 layer in the plan: once the weights are loaded)
     unsigned* absmax_dev = nullptr;     // calibration scratch: kMaxFp8Tensors x kMaxFp8Channels channel maxima (as bit patterns)
     static constexpr int kMaxFp8Tensors = 64, kMaxFp8Channels = 512;
     unsigned* rowmax_dev = nullptr;           // [1024]: row maxima of a weight panel with the channel scales folded in
@@ -269,6 +269,7 @@ void track_free(yh_engine* h);
 // fp8.hip
 void plan_fp8(yh_engine* h);
 std::string fp8_missing(const yh_engine* h);
+bool fp8_writes_codes(const yh_engine* h, const Buf& b);
 int refresh_fp8_scales(yh_engine* h, int sid = -1);
 
 }  // namespace yh

@@ -319,6 +319,22 @@ int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_sca
     return st.status(h, "quantize op: ");
 }
 
+int yh_op_absmax_channels_f16(yh_engine* h, const uint16_t* x, int64_t rows, int32_t C, uint32_t* out_bits) {
+    if (!h || !x || !out_bits || rows < 1 || C < 1) return YH_EINVAL;
+    HIPCHK(h, hipSetDevice(h->dev));
+    OpStaging st;
+    const half_t* dx = st.upload<half_t>(x, (size_t)rows * C * 2);
+    unsigned* dm = st.alloc<unsigned>((size_t)C * 4);
+    if (st.ok()) st.e = hipMemsetAsync(dm, 0, (size_t)C * 4, h->stream);   // (on the kernel's stream, as the calibration does: its atomicMax starts from these zeros)
+    if (st.ok()) {
+        st.e = launch_absmax_channels_f16(dx, (long long)rows, C, dm, h->stream);
+        if (st.e == hipErrorInvalidValue) return h->fail(YH_EINVAL, "absmax op: C must be a multiple of 8 with 256 % (C / 8) == 0");   // (nothing was launched)
+    }
+    st.sync(h->stream);
+    st.get(out_bits, dm, (size_t)C * 4);
+    return st.status(h, "absmax op: ");
+}
+
 int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask, const uint16_t* proto, int32_t n) {
     if (!h || !loc || !conf || !mask || !proto) return YH_EINVAL;
     if (n < 1 || n > h->cfg.max_batch) return h->fail(YH_EINVAL, "n out of range");

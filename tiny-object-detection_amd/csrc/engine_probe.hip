@@ -106,6 +106,26 @@ int yh_debug_read_tensor_frame(yh_engine* h, const char* name, int32_t frame, fl
     return read_tensor(h, name, true, frame, dst, nfloats, dims);
 }
 
+// The raw codes of the named tensor's E4M3 twin (one frame), as the last step wrote them: no decoding in between.
+int yh_debug_read_tensor_e4m3(yh_engine* h, const char* name, int32_t frame, uint8_t* dst, size_t n, int32_t dims[4]) {
+    if (!h || !name || !dims) return YH_EINVAL;
+    auto it = h->named.find(name);
+    if (it == h->named.end()) return h->fail(YH_EINVAL, std::string("unknown tensor ") + name);
+    if (h->cfg.precision != YH_PRECISION_FP8 || !h->fp8_active) return h->fail(YH_ESTATE, std::string("no E4M3 form of ") + name + ": the handle does not run its fp8 forward (precision, scales)");
+    if (h->cur_n < 1) return h->fail(YH_ESTATE, "no inference has run");
+    if (frame < 0 || frame >= h->cur_n) return h->fail(YH_EINVAL, "frame out of range");
+    const Buf& b = it->second;
+    if (absorbed_output(h, name) || !fp8_writes_codes(h, b)) return h->fail(YH_ESTATE, std::string("the plan writes no E4M3 form of ") + name);
+    const size_t per = (size_t)b.h * b.w * b.c;
+    dims[0] = 1; dims[1] = b.h; dims[2] = b.w; dims[3] = b.c;
+    if (!dst) return YH_OK;
+    if (n < per) return h->fail(YH_EINVAL, "destination too small");
+    HIPCHK(h, hipSetDevice(h->dev));
+    HIPCHK(h, hipMemcpyAsync(dst, b.q + (long long)frame * b.img_stride, per, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return YH_OK;
+}
+
 // ---- audit hooks (profiles/r03_fault_audit.md): where every buffer of a handle lives, and what a captured step consists of ----
 // One line per allocation: kind, name (layer tensors by their DESIGN.md names), [base, end), size and the offsets of base and
 // end inside their 2 MiB page - the three GPU memory-access faults of round 2 all hit an address 8 KiB below a 2 MiB boundary.

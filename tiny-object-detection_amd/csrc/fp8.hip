@@ -69,6 +69,22 @@ void plan_fp8(yh_engine* h) {
     }
 }
 
+// Does the plan write the E4M3 form of every element of tensor `b` (a named tensor or a slice of one)? True when at least one op
+// writes into its range and every op that does has write_q (yh_debug_read_tensor_e4m3: codes nobody wrote are not a result).
+bool fp8_writes_codes(const yh_engine* h, const Buf& b) {
+    if (!b.q || b.sid < 0) return false;
+    const long long off = b.d - h->act[b.sid].base, len = (long long)b.h * b.w * b.c;
+    int writers = 0;
+    for (const Op& o : h->ops) {
+        if (o.kind == OP_PRE || o.out.sid != b.sid) continue;
+        const long long ooff = o.out.d - h->act[b.sid].base, olen = (long long)o.out.h * o.out.w * o.out.c;
+        if (!(off < ooff + olen && ooff < off + len)) continue;
+        if (!o.write_q) return false;
+        ++writers;
+    }
+    return writers > 0;
+}
+
 // fp8 precision: the E4M3 layers whose input tensor has no scale yet (comma-separated; empty = every tensor is set)
 std::string fp8_missing(const yh_engine* h) {
     std::string out;
@@ -185,6 +201,23 @@ int yh_fp8_set_layer_channel_scales(yh_engine* h, int32_t i, const float* scales
     return fp8_set_scales_impl(h, i, std::vector<float>(scales, scales + n));
 }
 
+// Test hook: E4M3 layer i's weight codes as the kernel reads them, [cout][k * k * cin], and the per-output-channel scales of its
+// epilogue, both read back from the device.
+int yh_debug_fp8_weights(yh_engine* h, int32_t i, uint8_t* codes, float* s_w, int32_t dims[2]) {
+    if (!h || !dims || i < 0 || i >= (int)h->fp8_ops.size()) return YH_EINVAL;
+    const Op& o = h->ops[h->fp8_ops[i]];
+    const Panel& p = h->panels[o.panel];
+    if (!h->weights_loaded) return h->fail(YH_ESTATE, "fp8 weights of " + o.name + ": no weights are loaded");
+    if (!h->act[p.in_sid].scale_set || h->act[p.in_sid].ch.empty()) return h->fail(YH_ESTATE, "fp8 weights of " + o.name + ": its input tensor has no scales yet");
+    const int K = p.k * p.k * p.cin_store;
+    dims[0] = p.cout; dims[1] = K;
+    HIPCHK(h, hipSetDevice(h->dev));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (codes) HIPCHK(h, hipMemcpy2D(codes, (size_t)K, p.w8, (size_t)p.Kpad, (size_t)K, (size_t)p.cout, hipMemcpyDeviceToHost));
+    if (s_w) HIPCHK(h, hipMemcpy(s_w, p.scale, (size_t)p.cout * 4, hipMemcpyDeviceToHost));
+    return YH_OK;
+}
+
 int yh_fp8_calibrate(yh_engine* h) {
     if (!h) return YH_EINVAL;
     if (h->cfg.precision != YH_PRECISION_FP8) return h->fail(YH_ESTATE, "the handle was not created with YH_PRECISION_FP8");
@@ -193,7 +226,8 @@ int yh_fp8_calibrate(yh_engine* h) {
     HIPCHK(h, hipSetDevice(h->dev));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     drop_graphs(h);
-    // 1. the f16 forward of these frames (every tensor in f16, as a YH_PRECISION_F16 handle computes it); 2. one scale per
+    // 1. the f16 forward of these frames (every tensor in f16, bit for bit what a YH_PRECISION_F16 handle with the same tuning and
+    // debug_tensors computes: tests/test_gpu_fp8_exact.py); a NaN or an Inf in a tensor an E4M3 layer reads refuses the call; 2. one scale per
     // CHANNEL of every tensor that an fp8 convolution reads: max(2 max |x[.., c]|, max |x| / 16) / 448 (448: E4M3's largest finite
     // value; the factor and the floor: headroom for frames the calibration has not seen, below; yh_config.fp8_per_tensor = 1:
     // the tensor's maximum in every channel, no headroom - round 3's scheme). On any failure the handle keeps the scales
@@ -219,7 +253,7 @@ int yh_fp8_calibrate(yh_engine* h) {
         HIPCHK(h, hipMemcpyAsync(bits.data(), h->absmax_dev, bits.size() * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         k = 0;
-        for (int sid : sids) {   // (the maxima are combined as bit patterns of non-negative floats: Inf and every NaN compare above all finite values)
+        for (int sid : sids) {   // (absmax_channels_f16 takes the maxima on bit patterns: Inf and every NaN lie above all finite values and win)
             for (int c = 0; c < h->act[sid].c; ++c) {
                 float a; memcpy(&a, &bits[(size_t)k * MC + c], 4);
                 if (!(a < 3.0e38f)) {

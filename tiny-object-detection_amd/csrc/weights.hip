@@ -163,7 +163,13 @@ int upload_panels(yh_engine* h, const uint8_t* blob) {
         drop_graphs(h);
     }
     h->weights_loaded = true;
-    if (h->cfg.precision == YH_PRECISION_FP8) { const int rc = refresh_fp8_scales(h); if (rc) return rc; }   // (the panels whose input tensor already has its scales)
+    if (h->cfg.precision == YH_PRECISION_FP8) {
+        // a handle whose plan has NO E4M3 layer (yh_config.fp8_f16_layers = 15) has no scale to wait for: it is ready as soon as its
+        // weights are (nothing else would ever set fp8_ready: yh_fp8_set_layer_scale has no layer to be called with)
+        if (h->fp8_ops.empty()) { h->fp8_ready = true; h->fp8_active = true; }
+        const int rc = refresh_fp8_scales(h);   // (the panels whose input tensor already has its scales)
+        if (rc) return rc;
+    }
     return YH_OK;
 }
 

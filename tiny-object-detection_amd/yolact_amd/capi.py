@@ -169,6 +169,8 @@ SYMBOLS = [
     ("yh_instance_track_reset", _i, [_vp]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
+    ("yh_debug_read_tensor_e4m3", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
+    ("yh_debug_fp8_weights", _i, [_vp, _i, _vp, _vp, C.POINTER(_i * 2)]),
     ("yh_debug_last_conv_launches", _i, [_vp]),
     ("yh_debug_alloc_map", _i, [_vp, C.c_char_p, _sz]),
     ("yh_debug_setup_audit", _i, [C.POINTER(C.c_int64 * 4)]),
@@ -180,6 +182,7 @@ SYMBOLS = [
     ("yh_op_stem_pool_f16", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("yh_op_stem_pool_rgb8", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("yh_op_quantize_e4m3", _i, [_vp, _vp, _sz, C.c_float, _vp]),
+    ("yh_op_absmax_channels_f16", _i, [_vp, _vp, C.c_int64, _i, _vp]),
     ("yh_op_conv2d_fp8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     ("yh_op_conv2d_dual_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     ("yh_op_conv2d_levels_f16", _i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
@@ -581,6 +584,23 @@ class Engine:
         self._chk(self.L.yh_debug_read_tensor_frame(self.h, name.encode(), frame, _p(out), out.size, C.byref(d)))
         return out
 
+    def tensor_e4m3(self, name, frame):
+        """One frame of a named intermediate's E4M3 twin as raw codes, uint8 [h][w][c] (test hook; YhError ESTATE where the fp8 plan
+        does not write that form)."""
+        d = (C.c_int32 * 4)()
+        self._chk(self.L.yh_debug_read_tensor_e4m3(self.h, name.encode(), frame, None, 0, C.byref(d)))
+        out = np.empty(tuple(d)[1:], np.uint8)
+        self._chk(self.L.yh_debug_read_tensor_e4m3(self.h, name.encode(), frame, _p(out), out.size, C.byref(d)))
+        return out
+
+    def fp8_weights(self, layer_index):
+        """(codes uint8 [cout][k*k*cin], s_w f32 [cout]) of E4M3 layer layer_index as its kernel reads them (test hook)."""
+        d = (C.c_int32 * 2)()
+        self._chk(self.L.yh_debug_fp8_weights(self.h, layer_index, None, None, C.byref(d)))
+        codes, sw = np.empty((d[0], d[1]), np.uint8), np.empty(d[0], np.float32)
+        self._chk(self.L.yh_debug_fp8_weights(self.h, layer_index, _p(codes), _p(sw), C.byref(d)))
+        return codes, sw
+
     # ---- measurement hooks
     def profile(self, with_tail=True, reps=5):
         nl = self.L.yh_profile_launch_count(self.h, 1 if with_tail else 0)
@@ -710,6 +730,14 @@ class Engine:
         y = np.zeros(xb.shape, np.uint8)
         self._chk(self.L.yh_op_quantize_e4m3(self.h, _p(xb), xb.size, C.c_float(inv_scale), _p(y)))
         return y
+
+    def op_absmax_channels_f16(self, x_f16_bits):
+        """x: uint16 [rows][C] of f16 bit patterns -> uint32 [C], the bit patterns of max_r |x[r][c]| as f32 (the calibration's kernel)."""
+        xb = np.ascontiguousarray(x_f16_bits, np.uint16)
+        rows, c = xb.shape
+        out = np.zeros(c, np.uint32)
+        self._chk(self.L.yh_op_absmax_channels_f16(self.h, _p(xb), rows, c, _p(out)))
+        return out
 
     def op_detect(self, loc, conf, mask, proto):
         n = loc.shape[0]
