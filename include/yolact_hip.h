@@ -490,6 +490,47 @@ int yh_scene_plan_turn(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL:
  * while path_xy, directions or turns is asked for; YH_ESTATE before a turn plan, or when a frame was appended since. */
 int yh_scene_turn_read(yh_scene* h, float* cost, uint8_t* act, int32_t* path_xy, float* directions, int32_t* turns,
                        int32_t path_capacity, int32_t* path_len);
+/* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
+ * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
+ * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame
+ * taken from the grid, and the planner's field is unique, so frames that share the solver's rounds cannot change each other.
+ * Sizes as yh_scene_create; max_frames 1 .. 256. create allocates the staged inputs and the scene fields of max_frames frames (58
+ * bytes per pixel and frame) and builds the bump tables once; the planner's buffers (40, with connectivity 8 56 bytes per pixel and
+ * frame) are allocated at the first plan. */
+typedef struct yh_scene_batch yh_scene_batch;
+int yh_scene_batch_create(int32_t device, int32_t width, int32_t height, int32_t max_frames, yh_scene_batch** out);
+void yh_scene_batch_destroy(yh_scene_batch* h);
+const char* yh_scene_batch_last_error(const yh_scene_batch* h);
+/* Copies one frame into slot `slot` of the handle's own input buffers: depth u16 [h][w] from the host, and the packed u32 frame
+ * [h][w] from the host or (frame_on_device = 1) from a device pointer, as yh_scene_append_classified takes it (a (class, id) image
+ * packed as class << 24 | id << 16 | id << 8 | class reads the same in both modes). On return the caller's buffers, host or device,
+ * are free again: a device source - which must be complete when the call is made, as yh_instance_device_frame and
+ * yh_classify_device_frame are - is copied on the handle's stream and waited for, so each can be staged before the next
+ * yh_instance_frame / yh_classify_frame_u32 overwrites it. A slot stays staged until it is staged again. YH_EINVAL for a slot
+ * outside 0 .. max_frames - 1. */
+int yh_scene_batch_stage(yh_scene_batch* h, int32_t slot, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device);
+/* Runs frames 0 .. n_frames - 1 as staged, asynchronously on the handle's stream; STRICT and SANE read the frame exactly as
+ * yh_scene_append_classified does. YH_EINVAL for n_frames outside 1 .. max_frames or a bad mode, YH_ESTATE (naming the slot) if one
+ * of those slots has never been staged. Each append is a new frame generation: an earlier plan becomes unreadable. */
+int yh_scene_batch_append(yh_scene_batch* h, int32_t n_frames, int32_t compat_mode);
+/* One frame of the last append, laid out as yh_scene_read; any pointer may be NULL. Waits for the frame. YH_ESTATE before an
+ * append, YH_EINVAL for frame >= the last n_frames. */
+int yh_scene_batch_read(yh_scene_batch* h, int32_t frame, uint32_t* map, float* world, float* conn0, float* conn1, float* balls);
+/* yh_scene_plan_conn for every frame of the last append in the same launches: the batch takes the solver rounds of its slowest
+ * frame, not their sum. targets_xy: n_targets pixels per frame (all inside the frame, else YH_EINVAL; duplicates allowed), or NULL:
+ * each frame's own first n_targets balls by yh_scene_plan's rule (one read-back of the n ball tables; frames may end up with
+ * different numbers of targets). starts_xy: every frame's start. status, if not NULL, receives per frame YH_OK, or YH_ESTATE for a
+ * frame with no usable ball: that frame gets no plan, the others are planned, and the call returns YH_OK - unless NO frame has a
+ * target: then YH_ESTATE. Every other check is yh_scene_plan_conn's (YH_ESTATE after a STRICT append, the size guard, a start
+ * outside the frame, a connectivity other than 4 or 8) and YH_EINVAL for starts_xy NULL; they are made for all frames before
+ * anything is touched, so a refused call leaves an earlier plan of the same append readable. A call that fails later (YH_EHIP)
+ * leaves no plan. Synchronous. */
+int yh_scene_batch_plan(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_targets][2] or NULL: each frame's balls */, int32_t n_targets,
+                        const int32_t* starts_xy /* [n][2] */, int32_t connectivity /* 4 or 8 */, int32_t* status /* [n] or NULL */);
+/* One frame of the last plan, as yh_scene_plan_read (YH_EOVERFLOW with *path_len set included). YH_ESTATE for a frame whose status
+ * was YH_ESTATE, before a plan, and after a newer append; YH_EINVAL for a frame outside the last append. */
+int yh_scene_batch_plan_read(yh_scene_batch* h, int32_t frame, float* cost, int32_t* next, int32_t* path_xy, float* directions,
+                             int32_t path_capacity, int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

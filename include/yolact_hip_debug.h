@@ -127,6 +127,16 @@ int yh_scene_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* r
 /* The same for the last yh_scene_plan_turn, replayed with its start heading and turn price: rounds and tile runs of the
  * eight-layer field (a tile run relaxes the tile in all eight layers). */
 int yh_scene_turn_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs);
+/* Measurement hook: mean device milliseconds per BATCH over `reps` re-runs of the last yh_scene_batch_append (its n_frames and
+ * mode) from the staged slots as they are now. It counts as an append: an earlier plan becomes unreadable. */
+int yh_scene_batch_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch);
+/* yh_scene_plan_time for the last yh_scene_batch_plan: milliseconds per batch; rounds = launches in which some tile of some frame
+ * ran (those of the slowest frame), tile_runs summed over the frames. */
+int yh_scene_batch_plan_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
+/* yh_scene_set_fields for one frame of a batch, with the same checks, so that constructed mazes can sit beside easy frames. The first
+ * use after create or an append starts a new batch whose n is the highest frame set + 1 (a plan refuses, YH_ESTATE, while a frame
+ * below n has been given no fields). It counts as a YH_COMPAT_SANE append (a new frame generation). */
+int yh_scene_batch_set_fields(yh_scene_batch* h, int32_t frame, const uint32_t* map, const float* conn0, const float* conn1);
 
 /* Test hook: copies the named intermediate tensor of the last forward (layer names of DESIGN.md:
  * "stem", "pool", "c2".."c5", "lat3".."lat5", "p3".."p7", "proto0".."proto3", "proto_up", "head_t0"..) to

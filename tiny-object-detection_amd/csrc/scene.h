@@ -1,5 +1,6 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
-// scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan) and scene_solve.hip (the field solver they run on).
+// scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_solve.hip (the field solver they run on)
+// and scene_batch.hip (yh_scene_batch: N frames per launch; its handle holds one of these as its core, the arrays those of N frames).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,6 +53,14 @@ void scene_turn_free(yh_scene* h);
 void scene_solve_free(yh_scene* h);
 // yh_scene_plan's checks (frame, mode, size guard, start, targets) and its choice of targets, as linear indices; touches nothing
 int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets);
+// its two halves, for a caller that checks several frames and reads their balls back once (scene_batch.hip)
+int scene_plan_checks(yh_scene* h, int32_t n_targets, int32_t start_x, int32_t start_y);
+int scene_plan_choose(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, const float (*balls)[4], std::vector<int32_t>& targets);
+// yh_scene_set_fields' host-side check (YH_EINVAL and why), and whether the diagonals allow 8-connected plans; touches nothing
+int scene_check_fields(yh_scene* h, const float* conn0, const float* conn1, bool& diag_ok, std::string& diag_why);
+// scene.hip: waits until host sources a, b (either may be null) of copies enqueued on the stream may be reused; the bump tables of a handle
+int host_sources_done(yh_scene* h, const void* a, const void* b);
+hipError_t scene_tables_build(yh_scene* h);
 // what an 8-connected plan or tour asks of the last frame's diagonal lengths (YH_ESTATE and why if they fail it); touches nothing
 int scene_plan_diagonals(yh_scene* h);
 }

@@ -58,26 +58,9 @@ __global__ __launch_bounds__(256) void path_mark_targets(const PathParams p, con
 }
 
 template <int CONN>
-__global__ __launch_bounds__(256) void path_next(const PathParams p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < p.W * p.H) p.next[i] = successor(around<CONN>(p, i), p.cost, i);
-}
+__global__ __launch_bounds__(256) void path_next(const PathParams p) { next_body<CONN>(p); }
 
-// out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk did not end within W * H nodes (costs
-// strictly decrease along `next`, so this cannot happen on SANE fields; the bound is what keeps the loop finite on any input)
-__global__ __launch_bounds__(64) void path_walk(const PathParams p, int start, int2* nodes, float2* dirs, int32_t* out) {
-    const int lane = threadIdx.x;
-    bool lost;
-    const int n = chase(p.next, p.W, p.H, start, nodes, lost);
-    // directions[i] = (d[n_i] - d[n_i+1], rot_i): rot_0 = 0, else the angle at n_i between n_i-1 and n_i+1 - on a 4-grid without
-    // backtracking pi when straight, pi / 2 for a turn; with diagonals 3 pi / 4 and pi / 4 too (constants, not a device acosf)
-    for (int i = lane; i + 1 < n; i += 64) {
-        const int2 a = nodes[i], b = nodes[i + 1];
-        const float mag = __fsub_rn(p.cost[(size_t)a.y * p.W + a.x], p.cost[(size_t)b.y * p.W + b.x]);
-        dirs[i] = make_float2(mag, i > 0 ? rotation(nodes[i - 1], a, b) : 0.0f);
-    }
-    if (lane == 0) { out[0] = n; out[1] = lost ? 1 : 0; }
-}
+__global__ __launch_bounds__(64) void path_walk(const PathParams p, int start, int2* nodes, float2* dirs, int32_t* out) { walk_body(p, start, nodes, dirs, out); }
 
 int ensure_buffers(yh_scene* h) {
     yh_scene_path* q = h->path;
@@ -124,8 +107,8 @@ int run_plan(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, in
 }  // namespace
 
 namespace yh {
-// What yh_scene_plan and yh_scene_plan_tour check before they touch anything, and the targets they run on (linear indices)
-int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets) {
+// What every plan checks of the frame and the start before it touches anything (yh_scene_plan, yh_scene_plan_tour, yh_scene_batch_plan)
+int scene_plan_checks(yh_scene* h, int32_t n_targets, int32_t start_x, int32_t start_y) {
     if (n_targets < 1) return h->fail(YH_EINVAL, "n_targets < 1");
     if (!h->ran) return h->fail(YH_ESTATE, "no frame has been appended");
     if (h->last_mode != YH_COMPAT_SANE)
@@ -135,7 +118,12 @@ int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
     if ((W + H) * (2 * std::max(H, 101LL) + 1) >= (1LL << 24))
         return h->fail(YH_EINVAL, "frame too large for the planner: (W + H) * (2 * max(H, 101) + 1) must stay below 2^24 (f32 costs stay exact steps apart)");
     if (start_x < 0 || start_x >= W || start_y < 0 || start_y >= H) return h->fail(YH_EINVAL, "start outside the frame");
-    SCHK(h, hipSetDevice(h->dev));
+    return YH_OK;
+}
+
+// The targets a plan runs on, as linear indices: the given pixels, or (targets_xy null) the first n_targets balls of `balls` that have pixels
+int scene_plan_choose(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, const float (*balls)[4], std::vector<int32_t>& targets) {
+    const long long W = h->W, H = h->H;
     targets.clear();
     if (targets_xy) {
         for (int k = 0; k < n_targets; ++k) {
@@ -145,9 +133,6 @@ int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
         }
     } else {
         // balls[..3] (path.rs:37), means truncated as `as i32` does (scene.rs:321); here: the first n_targets balls that have pixels
-        float balls[100][4];
-        SCHK(h, hipMemcpyAsync(balls, h->balls, sizeof(balls), hipMemcpyDeviceToHost, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
         int taken = 0;
         for (int k = 0; k < 100 && taken < n_targets; ++k) {
             if (!(balls[k][2] > 0.0f)) continue;
@@ -157,6 +142,51 @@ int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets
         }
         if (targets.empty()) return h->fail(YH_ESTATE, "no target given and the frame has no ball inside it");
     }
+    return YH_OK;
+}
+
+// What yh_scene_plan and yh_scene_plan_tour check before they touch anything, and the targets they run on (linear indices)
+int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets) {
+    const int rc = scene_plan_checks(h, n_targets, start_x, start_y);
+    if (rc) return rc;
+    SCHK(h, hipSetDevice(h->dev));
+    float balls[100][4];
+    if (!targets_xy) {
+        SCHK(h, hipMemcpyAsync(balls, h->balls, sizeof(balls), hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return scene_plan_choose(h, targets_xy, n_targets, balls, targets);
+}
+
+// yh_scene_set_fields' host-side check of uploaded fields (also yh_scene_batch_set_fields'): YH_EINVAL unless the straight lengths are
+// those of a SANE frame; diag_ok / diag_why: whether an 8-connected plan may read the diagonals
+int scene_check_fields(yh_scene* h, const float* conn0, const float* conn1, bool& diag_ok, std::string& diag_why) {
+    // what the planner assumes of SANE fields and the frozen definition reads from the other end: every in-frame length >= 1
+    // (a finite number), left == the left neighbour's right, up == the upper neighbour's down
+    for (int y = 0; y < h->H; ++y)
+        for (int x = 0; x < h->W; ++x) {
+            const size_t i = (size_t)y * h->W + x;
+            const bool okr = x + 1 >= h->W || (conn0[4 * i + 2] >= 1.0f && conn0[4 * i + 2] < 3.0e38f && conn0[4 * i + 2] == conn1[4 * (i + 1) + 2]);
+            const bool okd = y + 1 >= h->H || (conn1[4 * i] >= 1.0f && conn1[4 * i] < 3.0e38f && conn1[4 * i] == conn0[4 * (i + h->W)]);
+            if (!okr || !okd)
+                return h->fail(YH_EINVAL, "fields are not those of a SANE frame at pixel (" + std::to_string(x) + ", " + std::to_string(y) + "): the " +
+                                              (okr ? "down" : "right") + " length must be a finite number >= 1 and equal the neighbour's entry for the same edge");
+        }
+    // the diagonals are no reason to refuse: what is recorded is whether an 8-connected plan may read them the same way (the
+    // down-right and down-left entry of the upper pixel for both directions)
+    diag_ok = true;
+    diag_why.clear();
+    for (int y = 0; y + 1 < h->H && diag_ok; ++y)
+        for (int x = 0; x < h->W && diag_ok; ++x) {
+            const size_t i = (size_t)y * h->W + x;
+            const bool okr = x + 1 >= h->W || (conn0[4 * i + 3] >= 1.0f && conn0[4 * i + 3] < 3.0e38f && conn0[4 * i + 3] == conn1[4 * (i + h->W + 1) + 3]);
+            const bool okl = x < 1 || (conn1[4 * i + 1] >= 1.0f && conn1[4 * i + 1] < 3.0e38f && conn1[4 * i + 1] == conn0[4 * (i + h->W - 1) + 1]);
+            if (!okr || !okl) {
+                diag_ok = false;
+                diag_why = std::string("the down-") + (okr ? "left" : "right") + " length of pixel (" + std::to_string(x) + ", " + std::to_string(y) +
+                           ") is not a finite number >= 1 equal to the other end's entry for the same edge";
+            }
+        }
     return YH_OK;
 }
 
@@ -211,32 +241,10 @@ int yh_scene_plan_read(yh_scene* h, float* cost, int32_t* next, int32_t* path_xy
 
 int yh_scene_set_fields(yh_scene* h, const uint32_t* map, const float* conn0, const float* conn1) {
     if (!h || !map || !conn0 || !conn1) return YH_EINVAL;
-    // what the planner assumes of SANE fields and the frozen definition reads from the other end: every in-frame length >= 1
-    // (a finite number), left == the left neighbour's right, up == the upper neighbour's down
-    for (int y = 0; y < h->H; ++y)
-        for (int x = 0; x < h->W; ++x) {
-            const size_t i = (size_t)y * h->W + x;
-            const bool okr = x + 1 >= h->W || (conn0[4 * i + 2] >= 1.0f && conn0[4 * i + 2] < 3.0e38f && conn0[4 * i + 2] == conn1[4 * (i + 1) + 2]);
-            const bool okd = y + 1 >= h->H || (conn1[4 * i] >= 1.0f && conn1[4 * i] < 3.0e38f && conn1[4 * i] == conn0[4 * (i + h->W)]);
-            if (!okr || !okd)
-                return h->fail(YH_EINVAL, "fields are not those of a SANE frame at pixel (" + std::to_string(x) + ", " + std::to_string(y) + "): the " +
-                                              (okr ? "down" : "right") + " length must be a finite number >= 1 and equal the neighbour's entry for the same edge");
-        }
-    // the diagonals are no reason to refuse: what is recorded is whether an 8-connected plan may read them the same way (the
-    // down-right and down-left entry of the upper pixel for both directions)
     bool diag_ok = true;
     std::string diag_why;
-    for (int y = 0; y + 1 < h->H && diag_ok; ++y)
-        for (int x = 0; x < h->W && diag_ok; ++x) {
-            const size_t i = (size_t)y * h->W + x;
-            const bool okr = x + 1 >= h->W || (conn0[4 * i + 3] >= 1.0f && conn0[4 * i + 3] < 3.0e38f && conn0[4 * i + 3] == conn1[4 * (i + h->W + 1) + 3]);
-            const bool okl = x < 1 || (conn1[4 * i + 1] >= 1.0f && conn1[4 * i + 1] < 3.0e38f && conn1[4 * i + 1] == conn0[4 * (i + h->W - 1) + 1]);
-            if (!okr || !okl) {
-                diag_ok = false;
-                diag_why = std::string("the down-") + (okr ? "left" : "right") + " length of pixel (" + std::to_string(x) + ", " + std::to_string(y) +
-                           ") is not a finite number >= 1 equal to the other end's entry for the same edge";
-            }
-        }
+    const int rc = scene_check_fields(h, conn0, conn1, diag_ok, diag_why);
+    if (rc) return rc;
     SCHK(h, hipSetDevice(h->dev));
     const size_t npx = (size_t)h->W * h->H;
     SCHK(h, hipMemcpyAsync(h->map, map, npx * 4, hipMemcpyHostToDevice, h->stream));

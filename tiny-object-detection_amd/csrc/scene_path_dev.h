@@ -73,12 +73,16 @@ struct SolveRound { std::function<void(const dim3&, int, uint32_t*)> launch; int
 
 // Allocates what F fields of connectivity conn need, fills p (but cost and next: the caller's), enqueues path_weights (once for all fields)
 int solve_begin(yh_scene* h, int conn, int F, PathParams& p);
+// solve_begin without the launch, for a handle whose scene fields and edge terms are those of `frames` frames one after the other (a
+// handle always asks for the same number): the caller enqueues its own path_weights over them (scene_batch.hip)
+int solve_alloc(yh_scene* h, int conn, int F, int frames, PathParams& p);
 // Relaxes the F fields at p.cost, which the caller has filled (+inf, 0 at the seeds), to their fixed points. seeds: the pixels that
 // start at 0, equally many per field, field by field. who: "path" or "tour", for the error text. after(tail), if given, enqueues
 // the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) arrives in host[kSolveCnt ..] with the counters.
-// own, if given, is the round kernel in place of field_round<conn> (round 0's flags still follow conn).
+// own, if given, is the round kernel in place of field_round<conn> (round 0's flags still follow conn). field_of, if given, is the
+// ragged form: seed k belongs to field (*field_of)[k], any number per field - a field without a seed flags nothing and its tiles exit at once.
 int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words = 0,
-                 const std::function<void(uint32_t*)>& after = nullptr, const SolveRound* own = nullptr);
+                 const std::function<void(uint32_t*)>& after = nullptr, const SolveRound* own = nullptr, const std::vector<int32_t>* field_of = nullptr);
 // run() reps times between two events; a failing run's code is returned as it is. kind, again: for the error texts ("plan", "plan again")
 int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast* q, int reps, const std::function<int()>& run, float* ms, int32_t* rounds, int32_t* tile_runs);
 // The checks of the read entry points (a run of this frame exists, the capacity holds the route), then the copies
@@ -281,6 +285,13 @@ __device__ __forceinline__ int successor(const Around<CONN>& e, const float* cos
     return nx;
 }
 
+// next[] of pixel blockIdx.x * 256 + threadIdx.x (scene_path.hip: path_next)
+template <int CONN>
+__device__ __forceinline__ void next_body(const PathParams& p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < p.W * p.H) p.next[i] = successor(around<CONN>(p, i), p.cost, i);
+}
+
 // rot_i at node a between the step z -> a and the step a -> b (each to one of the eight neighbours): with k the number of 45-degree
 // steps between the two headings, float32((4 - k) * pi / 4): pi straight on, pi / 2 for a right angle (all a 4-connected route has),
 // 0 for a reversal (at a tour's junction only). Five constants, no device acosf.
@@ -324,6 +335,42 @@ __device__ __forceinline__ int chase(const int32_t* next, int W, int H, int star
     __threadfence();
     __syncthreads();
     return n;
+}
+
+// The edge terms of pixel blockIdx.x * 256 + threadIdx.x (scene_solve.hip: path_weights)
+template <int CONN>
+__device__ __forceinline__ void weights_body(const PathParams& p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.W * p.H) return;
+    const int x = i % p.W, y = i / p.W;
+    const float h = (float)p.map[i];
+    const float hr = x + 1 < p.W ? fabsf(__fsub_rn(h, (float)p.map[i + 1])) : 0.0f;
+    const float hd = y + 1 < p.H ? fabsf(__fsub_rn(h, (float)p.map[i + p.W])) : 0.0f;
+    const float4 c0 = p.conn0[i], c1 = p.conn1[i];
+    p.edge[i] = make_float4(x + 1 < p.W ? c0.z : -1.0f, hr, y + 1 < p.H ? c1.x : -1.0f, hd);
+    if constexpr (CONN == 8) {
+        const bool dr = x + 1 < p.W && y + 1 < p.H, dl = x > 0 && y + 1 < p.H;
+        const float hdr = dr ? fabsf(__fsub_rn(h, (float)p.map[i + p.W + 1])) : 0.0f;
+        const float hdl = dl ? fabsf(__fsub_rn(h, (float)p.map[i + p.W - 1])) : 0.0f;
+        p.edge2[i] = make_float4(dr ? c0.w : -1.0f, hdr, dl ? c1.y : -1.0f, hdl);
+    }
+}
+
+// One wave (scene_path.hip: path_walk): the route from `start` and its directions.
+// out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk did not end within W * H nodes (costs
+// strictly decrease along `next`, so this cannot happen on SANE fields; the bound is what keeps the loop finite on any input)
+__device__ __forceinline__ void walk_body(const PathParams& p, int start, int2* nodes, float2* dirs, int32_t* out) {
+    const int lane = threadIdx.x;
+    bool lost;
+    const int n = chase(p.next, p.W, p.H, start, nodes, lost);
+    // directions[i] = (d[n_i] - d[n_i+1], rot_i): rot_0 = 0, else the angle at n_i between n_i-1 and n_i+1 - on a 4-grid without
+    // backtracking pi when straight, pi / 2 for a turn; with diagonals 3 pi / 4 and pi / 4 too (constants, not a device acosf)
+    for (int i = lane; i + 1 < n; i += 64) {
+        const int2 a = nodes[i], b = nodes[i + 1];
+        const float mag = __fsub_rn(p.cost[(size_t)a.y * p.W + a.x], p.cost[(size_t)b.y * p.W + b.x]);
+        dirs[i] = make_float2(mag, i > 0 ? rotation(nodes[i - 1], a, b) : 0.0f);
+    }
+    if (lane == 0) { out[0] = n; out[1] = lost ? 1 : 0; }
 }
 
 }  // namespace yh

@@ -27,22 +27,7 @@ using namespace yh;
 namespace {
 
 template <int CONN>
-__global__ __launch_bounds__(256) void path_weights(const PathParams p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.W * p.H) return;
-    const int x = i % p.W, y = i / p.W;
-    const float h = (float)p.map[i];
-    const float hr = x + 1 < p.W ? fabsf(__fsub_rn(h, (float)p.map[i + 1])) : 0.0f;
-    const float hd = y + 1 < p.H ? fabsf(__fsub_rn(h, (float)p.map[i + p.W])) : 0.0f;
-    const float4 c0 = p.conn0[i], c1 = p.conn1[i];
-    p.edge[i] = make_float4(x + 1 < p.W ? c0.z : -1.0f, hr, y + 1 < p.H ? c1.x : -1.0f, hd);
-    if constexpr (CONN == 8) {
-        const bool dr = x + 1 < p.W && y + 1 < p.H, dl = x > 0 && y + 1 < p.H;
-        const float hdr = dr ? fabsf(__fsub_rn(h, (float)p.map[i + p.W + 1])) : 0.0f;
-        const float hdl = dl ? fabsf(__fsub_rn(h, (float)p.map[i + p.W - 1])) : 0.0f;
-        p.edge2[i] = make_float4(dr ? c0.w : -1.0f, hdr, dl ? c1.y : -1.0f, hdl);
-    }
-}
+__global__ __launch_bounds__(256) void path_weights(const PathParams p) { weights_body<CONN>(p); }
 
 template <int CONN>
 __global__ __launch_bounds__(SP_NT) void field_round(const PathParams p, int F, int parity, uint32_t* cnt_next) {
@@ -60,13 +45,13 @@ int last_ok(yh_scene* h, const char* kind, const char* again, const SolveLast* q
 
 namespace yh {
 
-int solve_begin(yh_scene* h, int conn, int F, PathParams& p) {
+int solve_alloc(yh_scene* h, int conn, int F, int frames, PathParams& p) {
     if (!h->solve) h->solve = new yh_scene_solve();
     yh_scene_solve* s = h->solve;
     const size_t npx = (size_t)h->W * h->H;
     s->tx = (h->W + SP_TW - 1) / SP_TW; s->ty = (h->H + SP_TH - 1) / SP_TH;
-    if (!s->edge) SCHK(h, hipMalloc((void**)&s->edge, npx * 16));
-    if (conn == 8 && !s->edge2) SCHK(h, hipMalloc((void**)&s->edge2, npx * 16));
+    if (!s->edge) SCHK(h, hipMalloc((void**)&s->edge, frames * npx * 16));
+    if (conn == 8 && !s->edge2) SCHK(h, hipMalloc((void**)&s->edge2, frames * npx * 16));
     if (!s->cnt) SCHK(h, hipMalloc((void**)&s->cnt, (kSolveCnt + kSolveTail) * 4));
     if (!s->host) SCHK(h, hipHostMalloc((void**)&s->host, (kSolveCnt + kSolveTail + kSolveWalk) * 4, hipHostMallocDefault));
     if (F > s->cap_f) {
@@ -76,20 +61,26 @@ int solve_begin(yh_scene* h, int conn, int F, PathParams& p) {
     }
     p.W = h->W; p.H = h->H; p.tx = s->tx; p.ntiles = s->tx * s->ty;
     p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = s->edge; p.edge2 = conn == 8 ? s->edge2 : nullptr; p.flags = s->flags;
-    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p);
+    return YH_OK;
+}
+
+int solve_begin(yh_scene* h, int conn, int F, PathParams& p) {
+    const int rc = solve_alloc(h, conn, F, 1, p);
+    if (rc) return rc;
+    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)(((size_t)h->W * h->H + 255) / 256)), dim3(256), 0, h->stream, p);
     return YH_OK;
 }
 
 int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words,
-                 const std::function<void(uint32_t*)>& after, const SolveRound* own) {
+                 const std::function<void(uint32_t*)>& after, const SolveRound* own, const std::vector<int32_t>* field_of) {
     yh_scene_solve* s = h->solve;
     // round 0's work list: parity 0 of [2][F][ntiles]; parity 1 goes up in the same copy, all zero
     const size_t per = seeds.size() / F, nflags = (size_t)F * p.ntiles;
-    if (F < 1 || per < 1 || per * F != seeds.size()) return h->fail(YH_EINVAL, std::string(who) + " solver: the seeds are not equally many per field");
+    if (field_of ? F < 1 || field_of->size() != seeds.size() : F < 1 || per < 1 || per * F != seeds.size()) return h->fail(YH_EINVAL, std::string(who) + " solver: the seeds are not equally many per field");
     s->flags0.assign(2 * nflags, 0u);
     long long active = 0;
     for (size_t k = 0; k < seeds.size(); ++k) {
-        uint32_t* f0 = s->flags0.data() + (k / per) * p.ntiles;
+        uint32_t* f0 = s->flags0.data() + (field_of ? (size_t)(*field_of)[k] : k / per) * p.ntiles;
         round0_flags(seeds[k] % h->W, seeds[k] / h->W, conn, [&](int bx, int by) {
             if (bx < 0 || bx >= s->tx || by < 0 || by >= s->ty) return;
             uint32_t& f = f0[(size_t)by * s->tx + bx];

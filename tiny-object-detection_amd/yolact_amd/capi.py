@@ -160,6 +160,17 @@ SYMBOLS = [
     ("yh_scene_plan_turn", _i, [_vp, _vp, _i, _i, _i, _i, _f]),
     ("yh_scene_turn_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
+    ("yh_scene_batch_destroy", None, [_vp]),
+    ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
+    ("yh_scene_batch_stage", _i, [_vp, _i, _vp, _vp, _i]),
+    ("yh_scene_batch_append", _i, [_vp, _i, _i]),
+    ("yh_scene_batch_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_batch_plan", _i, [_vp, _vp, _i, _vp, _i, _vp]),
+    ("yh_scene_batch_plan_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_batch_time", _i, [_vp, _i, C.POINTER(_f)]),
+    ("yh_scene_batch_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_batch_set_fields", _i, [_vp, _i, _vp, _vp, _vp]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
@@ -1017,6 +1028,115 @@ class Scene:
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_turn_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
+
+
+class SceneBatch:
+    """RAII wrapper of yh_scene_batch: N frames appended and planned in one set of launches; frame b equals a Scene fed that frame alone."""
+
+    def __init__(self, width=640, height=480, max_frames=8, device=0):
+        self.L = load_library()
+        h = C.c_void_p()
+        rc = self.L.yh_scene_batch_create(device, width, height, max_frames, C.byref(h))
+        if rc != OK:
+            raise YhError(rc, self.L.yh_scene_batch_last_error(None).decode())
+        self.h, self.W, self.H, self.max_frames, self.n = h, width, height, max_frames, 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.yh_scene_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != OK:
+            raise YhError(rc, self.L.yh_scene_batch_last_error(self.h).decode())
+
+    @staticmethod
+    def pack(cls_id):
+        """A (class, id) byte image [h][w][2] as the packed u32 frame both compat modes read the same: class << 24 | id << 16 | id << 8 | class."""
+        ci = np.ascontiguousarray(cls_id, np.uint8).astype(np.uint32)
+        return np.ascontiguousarray(ci[..., 0] << 24 | ci[..., 1] << 16 | ci[..., 1] << 8 | ci[..., 0])
+
+    def stage(self, slot, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None):
+        """One frame into slot `slot`: depth u16 [h][w] and one of frame_u32 (host, packed), frame_dev_ptr (device, packed) or cls_id
+        ((class, id) bytes [h][w][2], packed here). The sources are free again on return."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        if frame_dev_ptr is not None:
+            self._chk(self.L.yh_scene_batch_stage(self.h, slot, _p(depth), C.c_void_p(frame_dev_ptr), 1))
+            return
+        f = self.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+        assert f.size == self.W * self.H
+        self._chk(self.L.yh_scene_batch_stage(self.h, slot, _p(depth), _p(f), 0))
+
+    def append(self, n, mode=COMPAT_STRICT):
+        self._chk(self.L.yh_scene_batch_append(self.h, n, mode))
+        self.n, self._fields = n, False
+
+    def read(self, b):
+        out = dict(map=np.zeros((self.H, self.W), np.uint32), world=np.zeros((self.H, self.W, 4), np.float32),
+                   conn0=np.zeros((self.H, self.W, 4), np.float32), conn1=np.zeros((self.H, self.W, 4), np.float32),
+                   balls=np.zeros((100, 4), np.float32))
+        self._chk(self.L.yh_scene_batch_read(self.h, b, _p(out["map"]), _p(out["world"]), _p(out["conn0"]), _p(out["conn1"]), _p(out["balls"])))
+        return out
+
+    def plan(self, targets=None, n_targets=3, starts=None, connectivity=4):
+        """Plans every frame of the last append (Scene.plan per frame, in shared launches). targets: [n][k] (x, y) pixels, or None:
+        each frame's first n_targets balls. starts: [n] (x, y); None: the reference's START_NODE per frame, at 640x480 only.
+        Returns the status list: OK, or ESTATE for a frame without a usable ball (it has no plan)."""
+        n = self.n
+        if starts is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("starts=None is the reference's START_NODE at 640x480; give the starts for other sizes")
+            starts = [(400, 479)] * n
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1, 2)
+        assert len(s) == n
+        status = np.zeros(max(n, 1), np.int32)
+        if targets is None:
+            self._chk(self.L.yh_scene_batch_plan(self.h, None, n_targets, _p(s), connectivity, _p(status)))
+        else:
+            t = np.ascontiguousarray(targets, np.int32)
+            assert t.ndim == 3 and t.shape[0] == n and t.shape[2] == 2
+            self._chk(self.L.yh_scene_batch_plan(self.h, _p(t), t.shape[1], _p(s), connectivity, _p(status)))
+        return [int(v) for v in status[:n]]
+
+    def read_plan(self, b, fields=True):
+        """Frame b of the last plan, as Scene.read_plan."""
+        n = C.c_int32()
+        self._chk(self.L.yh_scene_batch_plan_read(self.h, b, None, None, None, None, 0, C.byref(n)))
+        out = dict(path=np.zeros((n.value, 2), np.int32))
+        dirs = np.zeros((n.value, 2), np.float32)
+        if fields:
+            out["cost"] = np.zeros((self.H, self.W), np.float32)
+            out["next"] = np.zeros((self.H, self.W), np.int32)
+        self._chk(self.L.yh_scene_batch_plan_read(self.h, b, _p(out["cost"]) if fields else None, _p(out["next"]) if fields else None,
+                                                  _p(out["path"]), _p(dirs), n.value, C.byref(n)))
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        return out
+
+    def time(self, reps=20):
+        """Replays the last append: ms per batch."""
+        ms = C.c_float()
+        self._chk(self.L.yh_scene_batch_time(self.h, reps, C.byref(ms)))
+        return ms.value
+
+    def plan_time(self, reps=20):
+        """Replays the last plan: dict(ms_per_batch, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_batch_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def set_fields(self, b, map, conn0, conn1):
+        """Test hook: host fields for frame b as if a SANE frame had produced them (layouts of read())."""
+        m = np.ascontiguousarray(map, np.uint32)
+        c0, c1 = np.ascontiguousarray(conn0, np.float32), np.ascontiguousarray(conn1, np.float32)
+        assert m.shape == (self.H, self.W) and c0.shape == (self.H, self.W, 4) and c1.shape == (self.H, self.W, 4)
+        first = not getattr(self, "_fields", False)
+        self._chk(self.L.yh_scene_batch_set_fields(self.h, b, _p(m), _p(c0), _p(c1)))
+        self.n = b + 1 if first else max(self.n, b + 1)
+        self._fields = True
 
 
 def serialize_path(directions, created_secs):

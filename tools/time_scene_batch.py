@@ -1,0 +1,74 @@
+"""The scene batch (yh_scene_batch, DESIGN.md §11 "Scene batch") against the single handle at 640x480, for n = 1, 2, 4, 8, 16, 64 frames:
+the camera-like frame of tools/time_path.py (robots + two balls) with a different depth seed per slot. Per n: milliseconds PER FRAME of
+the append (yh_scene_batch_time: device events round whole batches) and of the plan with connectivity 4 and 8 (yh_scene_batch_plan_time:
+the host's counter reads inside, as for a caller), with the solver's rounds and tile runs; beside them the same frames through ONE
+Scene handle, call after call (append, yh_scene_time, plan, yh_scene_plan_time per frame; the sums divided by n), and the host's wall
+clock round stage + append + plan of the batch and round append + plan of the n single frames. Batch and single alternate set by set;
+medians over the sets.
+Usage: python tools/time_scene_batch.py [sets] [reps]"""
+import os, socket, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
+import yolact_amd as ya
+sets = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+H, W = 480, 640
+print(f"box {socket.gethostname()}, {ya.version()}, {sets} sets x {reps} reps")
+
+
+def frame(seed):
+    depth = np.random.default_rng(seed).integers(200, 4000, (H, W)).astype(np.uint16)
+    ci = np.zeros((H, W, 2), np.uint8)
+    ci[100:220, 150:330, 0] = 1; ci[260:330, 380:520, 0] = 2; ci[60:75, 60:80] = (3, 4); ci[400:420, 500:530] = (3, 9)
+    return depth, ya.SceneBatch.pack(ci)
+
+
+med = lambda v: sorted(v)[len(v) // 2]
+sc = ya.Scene(W, H)
+for n in (1, 2, 4, 8, 16, 64):
+    frames = [frame(b) for b in range(n)]
+    sb = ya.SceneBatch(W, H, n)
+
+    def batch_set():
+        t0 = time.perf_counter()
+        for b in range(n):
+            sb.stage(b, *frames[b])
+        sb.append(n, ya.COMPAT_SANE)
+        sb.plan(connectivity=4)
+        out = dict(wall=(time.perf_counter() - t0) * 1e3)
+        out["append"] = sb.time(reps) / n
+        for conn in (4, 8):
+            sb.plan(connectivity=conn)
+            out[conn] = sb.plan_time(reps)
+        return out
+
+    def single_set():
+        t0 = time.perf_counter()
+        for d, f in frames:
+            sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
+            sc.plan(connectivity=4)
+        out = dict(wall=(time.perf_counter() - t0) * 1e3, append=0.0)
+        out[4] = dict(ms=0.0, rounds=0, tile_runs=0); out[8] = dict(ms=0.0, rounds=0, tile_runs=0)
+        for d, f in frames:
+            sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
+            out["append"] += sc.time(reps) / n
+            for conn in (4, 8):
+                sc.plan(connectivity=conn)
+                s = sc.plan_time(reps)
+                out[conn]["ms"] += s["ms_per_plan"] / n
+                out[conn]["rounds"] = max(out[conn]["rounds"], s["rounds"]); out[conn]["tile_runs"] += s["tile_runs"]
+        return out
+
+    batch_set(); single_set()                                     # warm-up: buffers, code objects
+    B, S = [], []
+    for _ in range(sets):
+        B.append(batch_set()); S.append(single_set())
+    print(f"n = {n}")
+    print(f"  append, ms per frame:            batch {med([b['append'] for b in B]):.4f}   single {med([s['append'] for s in S]):.4f}")
+    for conn in (4, 8):
+        print(f"  plan {conn}-connected, ms per frame:  batch {med([b[conn]['ms_per_batch'] for b in B]) / n:.4f} ({B[0][conn]['rounds']} rounds, {B[0][conn]['tile_runs']} tile runs)"
+              f"   single {med([s[conn]['ms'] for s in S]):.4f} (at most {S[0][conn]['rounds']} rounds, {S[0][conn]['tile_runs']} tile runs in all)")
+    wb, ws = med([b["wall"] for b in B]), med([s["wall"] for s in S])
+    print(f"  host wall, stage + append + plan (4-connected) of the n frames: batch {wb:.3f} ms   single {ws:.3f} ms   ratio {wb / ws:.3f}")
+    sb.close()
