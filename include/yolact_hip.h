@@ -327,6 +327,25 @@ int yh_instance_tracks_read(yh_engine* h, int32_t* n_tracks, int32_t* table, int
  * before the first tracked call; the instance frame is not touched. */
 int yh_instance_track_reset(yh_engine* h);
 
+/* ---- instance batch: the instance frames of n frames of a step in one pair of launches (DESIGN.md section 11 "Instance batch") --
+ * Frames first_frame .. first_frame + n_frames - 1 of the last yh_evaluate painted at once: frame b of the batch has exactly the
+ * packed frame and the instance table yh_instance_frame(h, first_frame + b, width, height, class_map, min_score, ..) gives - the
+ * same device code runs per frame. One upload of the class map, one read-back, one wait, whatever n_frames is. out_host, if not
+ * NULL, receives the n_frames * width * height pixels, frame after frame.
+ * States and errors are yh_instance_frame's, plus YH_EINVAL for n_frames < 1 or first_frame + n_frames beyond the last step's
+ * batch. Synchronous. Everything is checked before anything is touched: a refused call leaves the earlier batch's frames, tables
+ * and pointer as they were; a call that fails later leaves no batch. The batch has buffers of its own (allocated at the first
+ * call, grow only, freed by yh_destroy): it does not disturb yh_instance_device_frame, yh_instance_read or the tracker, and
+ * yh_instance_frame / yh_instance_track do not disturb the batch. Tracking is not batched: a tracker's calls are sequential. */
+int yh_instance_batch(yh_engine* h, int32_t first_frame, int32_t n_frames, int32_t width, int32_t height, const uint8_t* class_map,
+                      float min_score, uint32_t* out_host /* [n][H][W] or NULL */);
+/* Device copy of the last batch's frames [n][H][W] (NULL before a batch); valid until the next yh_instance_batch on the handle.
+ * It is what yh_scene_batch_stage_frames(.., frames_on_device = 1) takes. */
+const uint32_t* yh_instance_batch_device_frames(const yh_engine* h);
+/* The instance table of frame `frame` (0 .. n - 1) of the last batch, with yh_instance_read's conventions: table may be NULL,
+ * YH_EOVERFLOW (the count set, nothing copied) if capacity < m rows, YH_ESTATE before a batch; YH_EINVAL for a frame outside it. */
+int yh_instance_batch_read(yh_engine* h, int32_t frame, int32_t* n_instances, int32_t* table, int32_t capacity);
+
 /* ---- reference-compat path: Yolact::classify (src/yolact.rs:39-41, :192-234) --------------- */
 
 /* In-place classify of one packed camera frame: `frame` holds width*height u32 pixels packed
@@ -509,6 +528,13 @@ const char* yh_scene_batch_last_error(const yh_scene_batch* h);
  * yh_instance_frame / yh_classify_frame_u32 overwrites it. A slot stays staged until it is staged again. YH_EINVAL for a slot
  * outside 0 .. max_frames - 1. */
 int yh_scene_batch_stage(yh_scene_batch* h, int32_t slot, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device);
+/* yh_scene_batch_stage for slots first_slot .. first_slot + n_frames - 1 at once: depth u16 [n][h][w] from the host and the packed
+ * frames u32 [n][h][w] from the host or (frames_on_device = 1) from a device pointer such as yh_instance_batch_device_frames. The slot
+ * buffers are contiguous, so this is one depth copy and one frame copy on the handle's stream, then the waits yh_scene_batch_stage
+ * makes: on return the caller's buffers are free again. The slots are marked staged only on success. YH_EINVAL for n_frames < 1 or a
+ * range outside 0 .. max_frames - 1. */
+int yh_scene_batch_stage_frames(yh_scene_batch* h, int32_t first_slot, int32_t n_frames, const uint16_t* depth_host /* [n][H][W] */,
+                                const uint32_t* frames /* [n][H][W] */, int32_t frames_on_device);
 /* Runs frames 0 .. n_frames - 1 as staged, asynchronously on the handle's stream; STRICT and SANE read the frame exactly as
  * yh_scene_append_classified does. YH_EINVAL for n_frames outside 1 .. max_frames or a bad mode, YH_ESTATE (naming the slot) if one
  * of those slots has never been staged. Each append is a new frame generation: an earlier plan becomes unreadable. */

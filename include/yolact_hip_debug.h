@@ -257,6 +257,15 @@ int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* clas
                          int32_t width, int32_t height, const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age,
                          uint32_t* out_host, int32_t* table, int32_t table_capacity, int32_t* n_instances);
 
+/* yh_op_instance_frame for n_frames frames of caller-provided detections at once (yh_instance_batch's kernels): masks u8
+ * [n_frames][n_dets][hp][wp], class ids i32 and scores f32 [n_frames][n_dets] in rank order per frame, counts i32 [n_frames], each in
+ * 0 .. n_dets, with n_dets <= max_dets and n_frames in 1 .. 64. The mask slots past a frame's count are overwritten with 0xFF in the
+ * upload, so a kernel that read them would paint them. out_host: n_frames * width * height pixels, or NULL; the tables are read with
+ * yh_instance_batch_read (yh_instance_batch_device_frames then shows this batch). */
+int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                         int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height, const uint8_t* class_map,
+                         float min_score, uint32_t* out_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
 // Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
-// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip and instance_track.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
+// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip, instance_batch.hip and instance_track.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -183,6 +183,16 @@ struct yh_engine {
     uint32_t inst_meta_host[256] = {};   // where inst_meta is read back to (a member: the copy is asynchronous)
     std::vector<int32_t> inst_table;   // [inst_rows][4] = (rank, class, id, pixels) of the last instance frame
     int inst_rows = -1;             // -1: no instance frame yet
+    // instance batch (instance_batch.hip): its own buffers, allocated at the first yh_instance_batch, grow only
+    uint4* instb_bits = nullptr;      // [n][hp * wp]
+    uint32_t* instb_frames = nullptr; // [n][height][width]
+    uint32_t* instb_meta = nullptr;   // [n][2][128]
+    uint8_t* instb_cmap = nullptr;    // [C - 1]
+    size_t instb_bits_cap = 0, instb_frames_cap = 0, instb_meta_cap = 0, instb_cmap_cap = 0;
+    std::vector<uint8_t> instb_cmap_host;
+    std::vector<uint32_t> instb_meta_host;          // [n][2][128] as read back
+    std::vector<std::vector<int32_t>> instb_tables; // per frame of the last batch: [rows][4]
+    int instb_n = -1;                 // frames of the last batch; -1: no batch
     // instance tracks (instance_track.hip): allocated at the first yh_instance_track, freed by yh_destroy
     uint4* trk_img = nullptr;       // T [hp * wp]: bit s = slot s's last seen mask is on there
     uint32_t* trk_ov = nullptr;     // I [128][128] then A [128]: zeroed on the stream by every tracked call
@@ -259,6 +269,13 @@ struct InstTrack { int iou_permille, max_age; };   // a tracked call's parameter
 int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
                  int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrack* trk = nullptr);
 void instance_free(yh_engine* h);
+int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes);   // a device buffer that only grows (the old one is freed)
+void instance_class_map(const uint8_t* class_map, int ncls, std::vector<uint8_t>& out);   // the call's class map, NULL resolved
+void instance_table(const uint32_t* meta, std::vector<int32_t>& table);   // meta [2][128] as read back -> rows (rank, class, id, pixels)
+// instance_batch.hip: n frames in one pair of launches; frame b reads masks + b max_n px, dets + b max_n, count + b
+int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,
+                       int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host);
+void instance_batch_free(yh_engine* h);
 // instance_track.hip: the stages instance_run puts between inst_pack and inst_paint, behind the read-back and behind the wait
 const char* track_check(int iou_permille, int max_age);   // nullptr: fine
 int track_enqueue(yh_engine* h, int hp, int wp, const InstTrack& trk);

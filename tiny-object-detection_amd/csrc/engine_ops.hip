@@ -406,4 +406,38 @@ int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* clas
                             n_instances, &trk);
 }
 
+// The instance batch's kernels (instance_batch.hip) on caller-provided detections of n_frames frames, n_dets slots each: what
+// yh_instance_batch runs on the tail's. The slots past a frame's count are uploaded as 0xFF: a kernel that read them would paint them.
+int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                         int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height, const uint8_t* class_map,
+                         float min_score, uint32_t* out_host) {
+    if (!h || !counts || (n_dets > 0 && (!masks || !class_ids || !scores))) return YH_EINVAL;
+    if (n_frames < 1 || n_frames > 64) return h->fail(YH_EINVAL, "instance batch op: n_frames outside 1 .. 64");
+    if (n_dets < 0 || n_dets > h->cfg.max_dets) return h->fail(YH_EINVAL, "instance batch op: n_dets outside 0 .. max_dets");
+    if (hp < 1 || hp > 4096 || wp < 1 || wp > 4096) return h->fail(YH_EINVAL, "instance batch op: hp and wp must be in 1 .. 4096");
+    for (int b = 0; b < n_frames; ++b) {
+        if (counts[b] < 0 || counts[b] > n_dets) return h->fail(YH_EINVAL, "instance batch op: a count outside 0 .. n_dets");
+        for (int d = 0; d < counts[b]; ++d)
+            if (class_ids[(size_t)b * n_dets + d] < 0 || class_ids[(size_t)b * n_dets + d] >= h->C - 1)
+                return h->fail(YH_EINVAL, "instance batch op: class id out of range");
+    }
+    if (const char* why = instance_check(width, height, class_map, h->C - 1, min_score)) return h->fail(YH_EINVAL, why);
+    HIPCHK(h, hipSetDevice(h->dev));
+    const size_t px = (size_t)hp * wp, slots = (size_t)n_frames * n_dets;
+    std::vector<yh_detection> dets(slots + 1);
+    memset(dets.data(), 0, dets.size() * sizeof(yh_detection));
+    std::vector<uint8_t> ms(slots * px + 1, 0xFF);
+    for (int b = 0; b < n_frames; ++b) {
+        const size_t o = (size_t)b * n_dets;
+        if (counts[b] > 0) memcpy(&ms[o * px], &masks[o * px], (size_t)counts[b] * px);
+        for (int d = 0; d < counts[b]; ++d) { dets[o + d].class_id = class_ids[o + d]; dets[o + d].score = scores[o + d]; }
+    }
+    OpStaging st;
+    const uint8_t* dm = st.upload<uint8_t>(ms.data(), ms.size());
+    const yh_detection* dd = st.upload<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
+    const int* dc = st.upload<int>(counts, (size_t)n_frames * sizeof(int));
+    if (const int rc = st.status(h, "instance batch op: ")) return rc;
+    return instance_batch_run(h, dm, dd, dc, n_dets, n_frames, hp, wp, width, height, class_map, min_score, out_host);
+}
+
 }  // extern "C"

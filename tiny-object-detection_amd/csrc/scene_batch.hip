@@ -261,6 +261,25 @@ int yh_scene_batch_stage(yh_scene_batch* hb, int32_t slot, const uint16_t* depth
     return YH_OK;
 }
 
+// The slot buffers are contiguous ([max_frames][H][W]): n slots are one depth copy and one frame copy, then yh_scene_batch_stage's waits.
+int yh_scene_batch_stage_frames(yh_scene_batch* hb, int32_t first_slot, int32_t n_frames, const uint16_t* depth_host, const uint32_t* frames,
+                                int32_t frames_on_device) {
+    if (!hb || !depth_host || !frames) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (n_frames < 1) return h->fail(YH_EINVAL, "n_frames " + std::to_string(n_frames) + " is below 1");
+    if (first_slot < 0 || first_slot >= hb->max_frames || n_frames > hb->max_frames - first_slot)
+        return h->fail(YH_EINVAL, "slots " + std::to_string(first_slot) + " .. " + std::to_string((long long)first_slot + n_frames - 1) + " outside 0 .. " + std::to_string(hb->max_frames - 1));
+    SCHK(h, hipSetDevice(h->dev));
+    const size_t npx = (size_t)h->W * h->H;
+    SCHK(h, hipMemcpyAsync(h->depth + first_slot * npx, depth_host, n_frames * npx * 2, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipMemcpyAsync(h->frame + first_slot * npx, frames, n_frames * npx * 4, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    const int rc = host_sources_done(h, depth_host, frames_on_device ? nullptr : frames);
+    if (rc) return rc;
+    if (frames_on_device) SCHK(h, hipStreamSynchronize(h->stream));   // the caller's device frames are free again (the next yh_instance_batch overwrites them)
+    std::fill(hb->staged.begin() + first_slot, hb->staged.begin() + first_slot + n_frames, (uint8_t)1);
+    return YH_OK;
+}
+
 int yh_scene_batch_append(yh_scene_batch* hb, int32_t n_frames, int32_t mode) {
     if (!hb) return YH_EINVAL;
     yh_scene* h = &hb->core;

@@ -94,6 +94,23 @@ std::vector<std::int32_t> Yolact::instance_frame(int frame, int width, int heigh
 
 const std::uint32_t* Yolact::instance_device_frame() const { return engine_ ? yh_instance_device_frame(engine_) : nullptr; }
 
+std::vector<std::vector<std::int32_t>> Yolact::instance_batch(int first, int n, int width, int height, const std::uint8_t* class_map,
+                                                              float min_score, std::uint32_t* frames_out) {
+    if (!engine_) expect_failed("instance_batch", "the detection tail belongs to the YOLACT engine");
+    if (yh_instance_batch(engine_, first, n, width, height, class_map, min_score, frames_out) != YH_OK)
+        expect_failed("instance batch failed", yh_last_error(engine_));
+    std::vector<std::vector<std::int32_t>> tables(static_cast<std::size_t>(n));
+    for (int b = 0; b < n; ++b) {
+        std::int32_t m = 0;
+        if (yh_instance_batch_read(engine_, b, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+        tables[b].resize(static_cast<std::size_t>(m) * 4);
+        if (yh_instance_batch_read(engine_, b, &m, tables[b].data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    }
+    return tables;
+}
+
+const std::uint32_t* Yolact::instance_batch_device_frames() const { return engine_ ? yh_instance_batch_device_frames(engine_) : nullptr; }
+
 std::vector<std::int32_t> Yolact::instance_track(int frame, int width, int height, const std::uint8_t* class_map, float min_score,
                                                  int iou_permille, int max_age, std::uint32_t* frame_out) {
     if (!engine_) expect_failed("instance_track", "the detection tail belongs to the YOLACT engine");

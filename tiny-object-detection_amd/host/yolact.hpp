@@ -58,6 +58,12 @@ public:
     std::vector<std::int32_t> instance_frame(int frame, int width, int height, const std::uint8_t* class_map = nullptr,
                                              float min_score = 0.0f, std::uint32_t* frame_out = nullptr);
     const std::uint32_t* instance_device_frame() const;
+    // Frames first .. first + n - 1 of that batch painted in one pair of launches (yh_instance_batch): frame b is what
+    // instance_frame(first + b, ..) gives. frames_out: n * width * height pixels, or nullptr to leave them on the device
+    // (instance_batch_device_frames() -> yh_scene_batch_stage_frames(.., 1)). Returns the n instance tables.
+    std::vector<std::vector<std::int32_t>> instance_batch(int first, int n, int width, int height, const std::uint8_t* class_map = nullptr,
+                                                          float min_score = 0.0f, std::uint32_t* frames_out = nullptr);
+    const std::uint32_t* instance_batch_device_frames() const;
     // The same with ids that persist from frame to frame (yh_instance_track): the detections are matched to the engine's tracker by
     // mask overlap (IoU >= iou_permille / 1000), a track that is not seen lives max_age further calls. The instance table carries
     // the track ids. tracks(): six values per live track - slot, output class, id, age, area, rank in the last call or -1.

@@ -164,6 +164,7 @@ SYMBOLS = [
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
     ("yh_scene_batch_stage", _i, [_vp, _i, _vp, _vp, _i]),
+    ("yh_scene_batch_stage_frames", _i, [_vp, _i, _i, _vp, _vp, _i]),
     ("yh_scene_batch_append", _i, [_vp, _i, _i]),
     ("yh_scene_batch_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_batch_plan", _i, [_vp, _vp, _i, _vp, _i, _vp]),
@@ -175,6 +176,9 @@ SYMBOLS = [
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
     ("yh_instance_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
+    ("yh_instance_batch", _i, [_vp, _i, _i, _i, _i, _vp, _f, _vp]),
+    ("yh_instance_batch_device_frames", _vp, [_vp]),
+    ("yh_instance_batch_read", _i, [_vp, _i, C.POINTER(_i), _vp, _i]),
     ("yh_instance_track", _i, [_vp, _i, _i, _i, _vp, _f, _i, _i, _vp]),
     ("yh_instance_tracks_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
     ("yh_instance_track_reset", _i, [_vp]),
@@ -203,6 +207,7 @@ SYMBOLS = [
     ("yh_op_detect", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
     ("yh_op_instance_frame", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_op_instance_track", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_op_instance_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
 ]
 
 
@@ -511,6 +516,44 @@ class Engine:
                                               _p(cm) if cm is not None else None, C.c_float(min_score), _p(out), _p(table),
                                               len(table), C.byref(m)))
         return out, table[:m.value].copy()
+
+    # ---- instance batch (DESIGN.md §11 "Instance batch")
+    def instance_batch(self, first, n, width, height, class_map=None, min_score=0.0, read=True):
+        """yh_instance_batch: frames first .. first + n - 1 of the last evaluate painted in one pair of launches; frame b equals
+        instance_frame(first + b, ...). Returns uint32 [n][height][width], or None with read=False (the frames stay on the device:
+        instance_batch_device_frames; the tables: instances_of)."""
+        cm = self._class_map(class_map)
+        out = np.zeros((max(n, 0), height, width), np.uint32) if read else None
+        self._chk(self.L.yh_instance_batch(self.h, first, n, width, height, _p(cm) if cm is not None else None, C.c_float(min_score),
+                                           _p(out) if read else None))
+        return out
+
+    def instance_batch_device_frames(self):
+        """Device pointer of the last batch's frames [n][height][width] (for SceneBatch.stage_frames); None before one."""
+        return self.L.yh_instance_batch_device_frames(self.h)
+
+    def instances_of(self, b):
+        """The instance table of frame b of the last batch: int32 [m][4] = (detection rank, output class, id, pixels won)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_instance_batch_read(self.h, b, C.byref(n), None, 0))
+        t = np.zeros((n.value, 4), np.int32)
+        self._chk(self.L.yh_instance_batch_read(self.h, b, C.byref(n), _p(t), n.value))
+        return t
+
+    def op_instance_batch(self, masks, class_ids, scores, counts, width, height, class_map=None, min_score=0.0):
+        """yh_op_instance_batch: the batch's kernels on caller-provided masks uint8 [n_frames][n_dets][hp][wp], class ids and scores
+        [n_frames][n_dets] in rank order per frame, counts [n_frames]. Returns (frames uint32 [n_frames][height][width], the list of
+        the frames' tables)."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        nf, nd, hp, wp = masks.shape
+        ids = np.ascontiguousarray(class_ids, np.int32).reshape(nf, nd)
+        sc = np.ascontiguousarray(scores, np.float32).reshape(nf, nd)
+        cnt = np.ascontiguousarray(counts, np.int32).reshape(nf)
+        cm = self._class_map(class_map)
+        out = np.zeros((nf, height, width), np.uint32)
+        self._chk(self.L.yh_op_instance_batch(self.h, _p(masks), _p(ids), _p(sc), _p(cnt), nf, nd, hp, wp, width, height,
+                                              _p(cm) if cm is not None else None, C.c_float(min_score), _p(out)))
+        return out, [self.instances_of(b) for b in range(nf)]
 
     # ---- instance tracks (DESIGN.md §11 "Instance tracks")
     @staticmethod
@@ -1070,6 +1113,25 @@ class SceneBatch:
         f = self.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
         assert f.size == self.W * self.H
         self._chk(self.L.yh_scene_batch_stage(self.h, slot, _p(depth), _p(f), 0))
+
+    def stage_frames(self, first_slot, depths, frames_u32=None, frames_dev_ptr=None):
+        """n frames into slots first_slot .. first_slot + n - 1 in one call: depths u16 [n][h][w] and one of frames_u32 (host, packed
+        [n][h][w]) or frames_dev_ptr (device, packed [n][h][w]: Engine.instance_batch_device_frames). The sources are free again on return."""
+        depths = np.ascontiguousarray(depths, np.uint16)
+        if depths.ndim != 3 or depths.shape[1:] != (self.H, self.W):
+            raise ValueError(f"depths: need [n][{self.H}][{self.W}], got {depths.shape}")
+        n = depths.shape[0]
+        if (frames_u32 is None) == (frames_dev_ptr is None):
+            raise ValueError("give exactly one of frames_u32 and frames_dev_ptr")
+        if frames_dev_ptr is not None:
+            if not frames_dev_ptr:
+                raise ValueError("frames_dev_ptr is null")
+            self._chk(self.L.yh_scene_batch_stage_frames(self.h, first_slot, n, _p(depths), C.c_void_p(frames_dev_ptr), 1))
+            return
+        f = np.ascontiguousarray(frames_u32, np.uint32)
+        if f.size != n * self.W * self.H:
+            raise ValueError(f"frames_u32: need {n} frames of {self.H} x {self.W}, got {f.shape}")
+        self._chk(self.L.yh_scene_batch_stage_frames(self.h, first_slot, n, _p(depths), _p(f), 0))
 
     def append(self, n, mode=COMPAT_STRICT):
         self._chk(self.L.yh_scene_batch_append(self.h, n, mode))
