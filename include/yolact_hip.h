@@ -557,6 +557,24 @@ int yh_scene_batch_plan(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_ta
  * was YH_ESTATE, before a plan, and after a newer append; YH_EINVAL for a frame outside the last append. */
 int yh_scene_batch_plan_read(yh_scene_batch* h, int32_t frame, float* cost, int32_t* next, int32_t* path_xy, float* directions,
                              int32_t path_capacity, int32_t* path_len);
+/* yh_scene_plan_turn for every frame of the last append in shared solver rounds (DESIGN.md section 11 "Scene batch: turns"): frame b
+ * has exactly the results of yh_scene_plan_turn on a yh_scene fed that frame alone with the same targets, start, start heading and
+ * turn price - cost, act, route, turns and directions, bit for bit. targets_xy, n_targets, starts_xy and status as
+ * yh_scene_batch_plan; start_headings: every frame's start heading, 0 .. 7; turn_price: one price per call (a property of the drive
+ * base, not of the frame). The checks are yh_scene_plan_turn's, made for all frames before anything is touched: YH_EINVAL for
+ * starts_xy or start_headings NULL, a heading outside 0 .. 7 (the text names the frame), a turn price that is NaN, infinite or
+ * outside [1, 1024], a target or start outside the frame, n_targets < 1 and the turn planner's size guard; YH_ESTATE before an
+ * append, after a STRICT append, for a frame whose uploaded diagonals allow 4-connected plans only, and when no frame has a target.
+ * A refused call leaves an earlier turn plan of the same append readable; a call that fails later (YH_EHIP) leaves none. The turn
+ * plan's buffers (60 bytes per pixel and frame, for max_frames frames) are its own, allocated at the first call: the batch's plan
+ * and its turn plan do not disturb each other's results. Synchronous. */
+int yh_scene_batch_plan_turn(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_targets][2] or NULL */, int32_t n_targets,
+                             const int32_t* starts_xy /* [n][2] */, const int32_t* start_headings /* [n], 0 .. 7 */,
+                             float turn_price, int32_t* status /* [n] or NULL */);
+/* One frame of the last batched turn plan, as yh_scene_turn_read (YH_EOVERFLOW with *path_len set included). YH_ESTATE for a frame
+ * whose status was YH_ESTATE, before a turn plan, and after a newer append; YH_EINVAL for a frame outside the last append. */
+int yh_scene_batch_turn_read(yh_scene_batch* h, int32_t frame, float* cost, uint8_t* act, int32_t* path_xy, float* directions,
+                             int32_t* turns, int32_t path_capacity, int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

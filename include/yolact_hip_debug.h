@@ -133,6 +133,9 @@ int yh_scene_batch_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch);
 /* yh_scene_plan_time for the last yh_scene_batch_plan: milliseconds per batch; rounds = launches in which some tile of some frame
  * ran (those of the slowest frame), tile_runs summed over the frames. */
 int yh_scene_batch_plan_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
+/* The same for the last yh_scene_batch_plan_turn, replayed with its start headings and turn price: rounds and tile runs of the
+ * frames' eight-layer fields. */
+int yh_scene_batch_turn_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
 /* yh_scene_set_fields for one frame of a batch, with the same checks, so that constructed mazes can sit beside easy frames. The first
  * use after create or an append starts a new batch whose n is the highest frame set + 1 (a plan refuses, YH_ESTATE, while a frame
  * below n has been given no fields). It counts as a YH_COMPAT_SANE append (a new frame generation). */

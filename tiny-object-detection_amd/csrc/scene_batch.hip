@@ -13,7 +13,8 @@
 //
 // The handle holds a yh_scene as its core: device, size, stream, error text, bump tables, the frame generation and mode - and array
 // pointers that are frame 0 of the batch's [max_frames][...] arrays. That is what lets the single handle's host code (the plan's checks
-// and choice of targets, the fields check, the solver's loop, its read and time) run on a batch unchanged.
+// and choice of targets, the fields check, the solver's loop, its read and time) run on a batch unchanged. The handle itself is
+// scene_batch.h's; the turn-aware plan over the batch (yh_scene_batch_plan_turn) is scene_batch_turn.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,35 +22,12 @@
 #include <vector>
 
 #include "scene.h"
+#include "scene_batch.h"
 #include "scene_dev.h"
 #include "scene_path_dev.h"
 #include "yh_internal.h"
 
 using namespace yh;
-
-struct yh_scene_batch {
-    yh_scene core;
-    int max_frames = 0;
-    int n = 0;                          // frames of the last append (or the highest frame given to yh_scene_batch_set_fields + 1)
-    int append_n = 0, append_mode = 0;  // the last append proper (yh_scene_batch_time replays it)
-    bool from_fields = false;           // the current frames came through yh_scene_batch_set_fields
-    std::vector<uint8_t> staged, fields_set, diag_ok;   // per slot / frame
-    std::vector<std::string> diag_why;
-    // the planner (allocated at the first plan, for max_frames frames)
-    float* cost = nullptr;        // [max][H][W]
-    int32_t* next = nullptr;      // [max][H][W]
-    int2* nodes = nullptr;        // [max][W*H]
-    float2* dirs = nullptr;       // [max][W*H]
-    int32_t* walk_out = nullptr;  // [max][2]: length, status
-    int32_t* starts = nullptr;    // [max] linear index, -1: no plan for this frame
-    int32_t* seeds = nullptr;     // [seeds_cap][2]: linear index, frame
-    int32_t seeds_cap = 0;
-    int32_t* host_walk = nullptr; // pinned [max][2]
-    SolveLast last;               // planned, frame generation, connectivity of the last plan
-    std::vector<int32_t> status, path_len, last_seeds, last_field, last_starts;
-    std::vector<int32_t> pairs;   // last_seeds and last_field interleaved, as uploaded
-    int fail(int code, const std::string& m) { return core.fail(code, m); }
-};
 
 namespace {
 
@@ -174,7 +152,7 @@ int run_plan(yh_scene_batch* hb, int conn) {
     p.cost = hb->cost; p.next = hb->next;
     const size_t npx = (size_t)h->W * h->H;
     const dim3 px((unsigned)((npx + 255) / 256), 1, (unsigned)n), sd((unsigned)((ns + 255) / 256));
-    hipLaunchKernelGGL(conn == 8 ? batch_weights<8> : batch_weights<4>, px, dim3(256), 0, h->stream, p);
+    scene_batch_weights(h, p, conn, n);
     SCHK(h, hipMemsetD32Async((hipDeviceptr_t)hb->cost, 0x7f800000, n * npx, h->stream));   // +inf
     hipLaunchKernelGGL(batch_seeds, sd, dim3(256), 0, h->stream, p, hb->seeds, ns, 0);
     const SolveRound round{ [&](const dim3& tiles, int parity, uint32_t* cnt_next) {
@@ -197,6 +175,13 @@ int run_plan(yh_scene_batch* hb, int conn) {
 }
 
 }  // namespace
+
+namespace yh {
+void scene_batch_weights(yh_scene* h, const PathParams& p, int conn, int n) {
+    const dim3 px((unsigned)(((size_t)h->W * h->H + 255) / 256), 1, (unsigned)n);
+    hipLaunchKernelGGL(conn == 8 ? batch_weights<8> : batch_weights<4>, px, dim3(256), 0, h->stream, p);
+}
+}  // namespace yh
 
 extern "C" {
 
@@ -238,6 +223,7 @@ void yh_scene_batch_destroy(yh_scene_batch* hb) {
     hipSetDevice(h->dev);
     if (h->stream) hipStreamSynchronize(h->stream);
     free_planner(hb);
+    scene_batch_turn_free(hb);
     scene_solve_free(h);
     void* bufs[] = { h->depth, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);

@@ -172,6 +172,9 @@ SYMBOLS = [
     ("yh_scene_batch_time", _i, [_vp, _i, C.POINTER(_f)]),
     ("yh_scene_batch_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_scene_batch_set_fields", _i, [_vp, _i, _vp, _vp, _vp]),
+    ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
+    ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
@@ -1188,6 +1191,48 @@ class SceneBatch:
         """Replays the last plan: dict(ms_per_batch, rounds, tile_runs)."""
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_batch_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def plan_turn(self, targets=None, n_targets=3, starts=None, headings=6, turn_price=2.0):
+        """The turn-aware plan (Scene.plan_turn) of every frame of the last append in shared solver rounds. targets, n_targets,
+        starts as plan(); headings: the start heading 0 .. 7, one int for all frames or a list of n; turn_price: one per call.
+        Returns the status list: OK, or ESTATE for a frame without a usable ball (it has no turn plan)."""
+        n = self.n
+        if starts is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("starts=None is the reference's START_NODE at 640x480; give the starts for other sizes")
+            starts = [(400, 479)] * n
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1, 2)
+        hd = np.full(max(n, 1), headings, np.int32) if np.isscalar(headings) else np.ascontiguousarray(headings, np.int32).reshape(-1)
+        assert len(s) == n and len(hd) >= n
+        status = np.zeros(max(n, 1), np.int32)
+        if targets is None:
+            self._chk(self.L.yh_scene_batch_plan_turn(self.h, None, n_targets, _p(s), _p(hd), turn_price, _p(status)))
+        else:
+            t = np.ascontiguousarray(targets, np.int32)
+            assert t.ndim == 3 and t.shape[0] == n and t.shape[2] == 2
+            self._chk(self.L.yh_scene_batch_plan_turn(self.h, _p(t), t.shape[1], _p(s), _p(hd), turn_price, _p(status)))
+        return [int(v) for v in status[:n]]
+
+    def read_turn(self, b, fields=True):
+        """Frame b of the last turn plan, as Scene.read_turn."""
+        n = C.c_int32()
+        self._chk(self.L.yh_scene_batch_turn_read(self.h, b, None, None, None, None, None, 0, C.byref(n)))
+        out = dict(path=np.zeros((n.value, 2), np.int32))
+        dirs, turns = np.zeros((n.value, 2), np.float32), np.zeros(n.value, np.int32)
+        if fields:
+            out["cost"] = np.zeros((8, self.H, self.W), np.float32)
+            out["act"] = np.zeros((8, self.H, self.W), np.uint8)
+        self._chk(self.L.yh_scene_batch_turn_read(self.h, b, _p(out["cost"]) if fields else None, _p(out["act"]) if fields else None,
+                                                  _p(out["path"]), _p(dirs), _p(turns), n.value, C.byref(n)))
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        out["turns"] = turns[:max(n.value - 1, 0)]
+        return out
+
+    def turn_time(self, reps=20):
+        """Replays the last turn plan: dict(ms_per_batch, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_batch_turn_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
 
     def set_fields(self, b, map, conn0, conn1):

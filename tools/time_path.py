@@ -31,6 +31,8 @@ has_conn = hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_plan_conn")
 if not hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_plan_turn"):
     assert tau is None, "this build has no yh_scene_plan_turn"
     capi.SYMBOLS = [s for s in capi.SYMBOLS if "_turn" not in s[0]]
+if not hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_batch_plan_turn"):
+    capi.SYMBOLS = [s for s in capi.SYMBOLS if not s[0].startswith("yh_scene_batch_") or "turn" not in s[0]]
 if not hasattr(ctypes.CDLL(capi.lib_path()), "yh_scene_batch_create"):
     capi.SYMBOLS = [s for s in capi.SYMBOLS if "_scene_batch_" not in s[0]]
 if not has_conn:

@@ -5,16 +5,24 @@ the host's counter reads inside, as for a caller), with the solver's rounds and 
 Scene handle, call after call (append, yh_scene_time, plan, yh_scene_plan_time per frame; the sums divided by n), and the host's wall
 clock round stage + append + plan of the batch and round append + plan of the n single frames. Batch and single alternate set by set;
 medians over the sets.
-Usage: python tools/time_scene_batch.py [sets] [reps]"""
+--turn-price P: the plan columns are the batched turn-aware plan instead (yh_scene_batch_plan_turn with price P per 45 degrees,
+DESIGN.md §11 "Scene batch: turns"; yh_scene_batch_turn_time) beside the same frames through Scene.plan_turn (yh_scene_turn_time per
+frame), every frame from the reference's START_NODE facing up; the host wall is then stage + append + turn plan.
+Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
 import yolact_amd as ya
-sets = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+args, tau = [], None
+it = iter(sys.argv[1:])
+for a in it:
+    if a == "--turn-price": tau = float(next(it))
+    else: args.append(a)
+sets = int(args[0]) if len(args) > 0 else 5
+reps = int(args[1]) if len(args) > 1 else 20
 H, W = 480, 640
-print(f"box {socket.gethostname()}, {ya.version()}, {sets} sets x {reps} reps")
+print(f"box {socket.gethostname()}, {ya.version()}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else ""))
 
 
 def frame(seed):
@@ -35,9 +43,13 @@ for n in (1, 2, 4, 8, 16, 64):
         for b in range(n):
             sb.stage(b, *frames[b])
         sb.append(n, ya.COMPAT_SANE)
-        sb.plan(connectivity=4)
+        sb.plan_turn(turn_price=tau) if tau else sb.plan(connectivity=4)
         out = dict(wall=(time.perf_counter() - t0) * 1e3)
         out["append"] = sb.time(reps) / n
+        if tau:
+            sb.plan_turn(turn_price=tau)
+            out["turn"] = sb.turn_time(reps)
+            return out
         for conn in (4, 8):
             sb.plan(connectivity=conn)
             out[conn] = sb.plan_time(reps)
@@ -47,12 +59,18 @@ for n in (1, 2, 4, 8, 16, 64):
         t0 = time.perf_counter()
         for d, f in frames:
             sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
-            sc.plan(connectivity=4)
+            sc.plan_turn(turn_price=tau) if tau else sc.plan(connectivity=4)
         out = dict(wall=(time.perf_counter() - t0) * 1e3, append=0.0)
-        out[4] = dict(ms=0.0, rounds=0, tile_runs=0); out[8] = dict(ms=0.0, rounds=0, tile_runs=0)
+        out[4] = dict(ms=0.0, rounds=0, tile_runs=0); out[8] = dict(ms=0.0, rounds=0, tile_runs=0); out["turn"] = dict(ms=0.0, rounds=0, tile_runs=0)
         for d, f in frames:
             sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
             out["append"] += sc.time(reps) / n
+            if tau:
+                sc.plan_turn(turn_price=tau)
+                s = sc.turn_time(reps)
+                out["turn"]["ms"] += s["ms_per_plan"] / n
+                out["turn"]["rounds"] = max(out["turn"]["rounds"], s["rounds"]); out["turn"]["tile_runs"] += s["tile_runs"]
+                continue
             for conn in (4, 8):
                 sc.plan(connectivity=conn)
                 s = sc.plan_time(reps)
@@ -66,9 +84,12 @@ for n in (1, 2, 4, 8, 16, 64):
         B.append(batch_set()); S.append(single_set())
     print(f"n = {n}")
     print(f"  append, ms per frame:            batch {med([b['append'] for b in B]):.4f}   single {med([s['append'] for s in S]):.4f}")
-    for conn in (4, 8):
+    if tau:
+        print(f"  turn plan, price {tau}, ms per frame:  batch {med([b['turn']['ms_per_batch'] for b in B]) / n:.4f} ({B[0]['turn']['rounds']} rounds, {B[0]['turn']['tile_runs']} tile runs)"
+              f"   single {med([s['turn']['ms'] for s in S]):.4f} (at most {S[0]['turn']['rounds']} rounds, {S[0]['turn']['tile_runs']} tile runs in all)")
+    for conn in (() if tau else (4, 8)):
         print(f"  plan {conn}-connected, ms per frame:  batch {med([b[conn]['ms_per_batch'] for b in B]) / n:.4f} ({B[0][conn]['rounds']} rounds, {B[0][conn]['tile_runs']} tile runs)"
               f"   single {med([s[conn]['ms'] for s in S]):.4f} (at most {S[0][conn]['rounds']} rounds, {S[0][conn]['tile_runs']} tile runs in all)")
     wb, ws = med([b["wall"] for b in B]), med([s["wall"] for s in S])
-    print(f"  host wall, stage + append + plan (4-connected) of the n frames: batch {wb:.3f} ms   single {ws:.3f} ms   ratio {wb / ws:.3f}")
+    print(f"  host wall, stage + append + {'turn plan' if tau else 'plan (4-connected)'} of the n frames: batch {wb:.3f} ms   single {ws:.3f} ms   ratio {wb / ws:.3f}")
     sb.close()
