@@ -58,7 +58,10 @@ typedef struct yh_tuning {
     int32_t tfl_group;       /* TFLite path: 1 (default) independent register-fed convolutions of one kernel form at one depth of the plan's
                               * graph as ONE launch (the prediction head's convolutions over the pyramid levels: 23 launches become 3), the
                               * plan in depth order; 0: one launch per convolution in file order. Same bytes */
-    int32_t reserved[17];    /* ignored by the library (the slots of retired fields: DESIGN.md §9) */
+    int32_t op_xgap;         /* single-op conv entry points: the staged input keeps this many extra f16 elements (a multiple of 8,
+                              * filled with ones) behind every image, so x_img_stride is not the dense H * W * C (0: dense) */
+    int32_t op_tanh_from;    /* single-op conv entry points with act = 2: tanh on the channels from this one on (0: all of them) */
+    int32_t reserved[15];    /* ignored by the library (the slots of retired fields: DESIGN.md §9) */
 } yh_tuning;
 
 #ifdef __cplusplus

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void bneck_chain_f16(const BneckParams p) {
 #pragma unroll
         for (int d = 0; d < XL; ++d) {
             const int mm = m0 + rb + 32 * d, m = mm < p.M ? mm : 0;
-            const int n = m / PQ, rem = m - n * PQ, op = rem / p.Q, oq = rem - op * p.Q;
+            const int n = (int)divmagic_div((unsigned)m, p.dpq), rem = m - n * PQ, op = (int)divmagic_div((unsigned)rem, p.dq), oq = rem - op * p.Q;
             const unsigned off = (unsigned)((int)(n * p.x2_img_stride) + (op * p.W2 + oq) * p.stride2 * (64 * KT2) + lc * 8) * 2u;
 #pragma unroll
             for (int kt = 0; kt < KT2; ++kt)
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void bneck_chain_f16(const BneckParams p) {
     for (int d = 0; d < XL; ++d) {
         const int m = m0 + rb + 32 * d;
         if (m < p.M) {
-            const int n = m / PQ, rem = m - n * PQ, op = rem / p.Q, oq = rem - op * p.Q;
+            const int n = (int)divmagic_div((unsigned)m, p.dpq), rem = m - n * PQ, op = (int)divmagic_div((unsigned)rem, p.dq), oq = rem - op * p.Q;
             xih[d] = op * p.stride - 1;
             xiw[d] = oq * p.stride - 1;
             xbase[d] = (int)(n * p.a_img_stride) + (xih[d] * p.W + xiw[d]) * PL + lc * 8;
@@ -621,8 +621,16 @@ const char* bneck_symbol(int planes, int tm, bool next, bool dual) {
     return c ? c->symbol : "?";
 }
 
+// m / (P * Q) and rem / Q as multiplier and shift (divmagic.h); the rows the kernels form are m < M + the largest tile's 256
+hipError_t bneck_set_geometry(BneckParams& p) {
+    if (p.P < 1 || p.Q < 1 || (long long)p.M + 256 >= kDivMagicLimit) return hipErrorInvalidValue;
+    return divmagic_make((long long)p.P * p.Q, &p.dpq) && divmagic_make(p.Q, &p.dq) ? hipSuccess : hipErrorInvalidValue;
+}
+
 hipError_t launch_bneck(const BneckParams& p, int planes, int tm, hipStream_t stream) {
     if (p.M < 1 || (p.stride != 1 && p.stride != 2)) return hipErrorInvalidValue;
+    // (a multiplier made by divmagic_make is at least 2^31: zero means bneck_set_geometry was not run on these parameters, or refused them)
+    if (p.dpq.mul == 0 || p.dq.mul == 0) return hipErrorInvalidValue;
     const int ntiles = (p.M + tm - 1) / tm;
     const dim3 grid((unsigned)ntiles);
     if (p.no_b) {   // expand conv + residual + next reduce conv of a 256-plane block; b is a tensor (p.a)

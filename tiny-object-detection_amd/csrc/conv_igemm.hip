@@ -19,6 +19,8 @@
 // block kept at the end of every activation allocation (inside the descriptor's range).
 // Epilogue: accumulators -> LDS as f32 [m][ch] (lane holds 4 consecutive channels per register
 // quad), then whole 16-byte f16 channel groups are written with coalesced row stores.
+#include <string.h>
+#include <type_traits>
 #include <utility>
 
 #include "yh_internal.h"
@@ -55,7 +57,7 @@ __device__ __forceinline__ half8 load_residual(const ConvParams& p, int m, int c
 }
 __device__ __forceinline__ half8 bilinear_residual(const ConvParams& p, int m, int ch) {
 #pragma clang fp contract(off)
-    const int PQ = p.P * p.Q, n = m / PQ, rem = m - n * PQ, oy = rem / p.Q, ox = rem - oy * p.Q;
+    const int PQ = p.P * p.Q, n = (int)divmagic_div((unsigned)m, p.geo.pq), rem = m - n * PQ, oy = (int)divmagic_div((unsigned)rem, p.geo.q), ox = rem - oy * p.Q;
     const float sy = (float)p.res_h / (float)p.P, sx = (float)p.res_w / (float)p.Q;
     float fy = ((float)oy + 0.5f) * sy - 0.5f;
     fy = fy < 0.0f ? 0.0f : fy;
@@ -77,6 +79,16 @@ __device__ __forceinline__ half8 bilinear_residual(const ConvParams& p, int m, i
         o[e] = (half_t)(hy * top + ly * bot);
     }
     return o;
+}
+
+template <int BYTES>
+__device__ __forceinline__ void kernarg_warm() {
+    typedef __attribute__((address_space(4))) const unsigned kernarg_word;
+    kernarg_word* ka = (kernarg_word*)__builtin_amdgcn_kernarg_segment_ptr();
+    unsigned any = 0;
+#pragma unroll
+    for (int o = 0; o < BYTES; o += 64) any |= ka[o / 4];
+    asm volatile("" ::"s"(any));
 }
 
 template <int MT, class ACC>
@@ -101,14 +113,19 @@ __device__ __forceinline__ ACC mfma_f16(const half8 a, const half8 b, const ACC 
 //      writes and the 16-lane fragment reads are both conflict free) - no f32 staging, no rounds - and the eight waves
 //      run the 32 x 256 second convolution on it with v_mfma_f32_16x16x32_f16 (weights = A straight from L2: 16 KB in
 //      all). The first conv's output never leaves the CU.
-template <int TCH, int TM, int WCH, int WM, bool SMALLC, int STAGES, int EPI, bool SPLITK = false, int MT = 32, bool ML = false, bool FP8 = false, bool RESUP = false, bool DUAL = false, bool TAIL = false, bool K3 = false>
+template <int TCH, int TM, int WCH, int WM, bool SMALLC, int STAGES, int EPI, bool SPLITK = false, int MT = 32, bool ML = false, bool FP8 = false, int GEO = 0, bool DUAL = false, bool TAIL = false, bool K3 = false>
 __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvParams p) {
+    // GEO: the form's row geometry - 0 general, 1 RESUP (the residual is upsampled in the epilogue), 2 LIN (dense 1x1 input)
+    constexpr bool RESUP = GEO == 1, LIN = GEO == 2;
     static_assert(!ML || !SMALLC, "multi-level input: ordinary channel counts only");
     static_assert(!TAIL || (TCH == 256 && TM == 256 && WCH * WM == 8 && MT == 16 && !SPLITK && !RESUP && !DUAL && !ML), "fused 1x1 tail: the 256 x 256 tile of 16x16x32 MFMAs");
     static_assert(!DUAL || (!ML && !SMALLC && !FP8 && !RESUP), "two-source form: plain 1x1 convolutions");
+    // LIN: the dense 1x1 form (ConvParams::x_dense) of the streaming tiles - row m's source offset is m * C, its bounds test m < M:
+    // no division, no (y, x) per staged row. A template flag like K3: as a run-time branch it would sit in every form's prologue.
+    static_assert(!LIN || (STAGES == 1 && !ML && !SMALLC && !SPLITK && !RESUP && !DUAL && !TAIL && !K3 && !FP8), "dense 1x1 form: plain launches of the streaming tiles");
     // K3: the 3x3 specialisation of the streaming tile (kernel extent known at compile time) - a kernel symbol of its own,
     // so that the MFMA-leaning 3x3 launches and the HBM-bound 1x1 launches of that tile are told apart in every profile
-    const int kR = K3 ? 3 : p.R, kS = K3 ? 3 : p.S;
+    const int kR = K3 ? 3 : (LIN ? 1 : p.R), kS = K3 ? 3 : (LIN ? 1 : p.S);
     constexpr int NW = WCH * WM, NT = NW * 64, RSTEP = NW * 8;  // waves, threads, rows per DMA pass
     constexpr int WTC = TCH / WCH, WTM = TM / WM;  // wave tile
     constexpr int TC = WTC / MT, TMT = WTM / MT;   // MFMA tiles per wave
@@ -126,6 +143,13 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
 
+    // The parameters are read where they are used, in a dozen and more scalar loads spread over the prologue and the epilogue, each
+    // group waited for on its own; a wave's first touch of a 64-byte line of the kernel-argument segment costs an L2 round trip
+    // (the latency-bound launches of small batches paid ~1 us for them). One dword of every line is asked for up front, all under
+    // a single wait, so the later loads hit the scalar cache. This answers how THIS compiler places the loads (profiles/
+    // conv_geometry_ab.txt section 6: 12 loads in 3 groups before, 29-42 in 13-20 without the division blocks): measure again
+    // with and without it when the toolchain changes.
+    kernarg_warm<sizeof(ConvParams)>();
     // XCD-aware bijective remap: consecutive work ids (which share activation rows / weight
     // panels) land on one XCD's L2 instead of being dealt round-robin over the eight.
     const int nwg = gridDim.x, bid = blockIdx.x;
@@ -133,13 +157,14 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     int tile_id = wg, kslice = 0, kt0 = 0, nk_total = p.ksteps;
     if (SPLITK) {  // slice is the slow index: neighbours share the K range (weights / activations in L2)
-        const int ntiles = nwg / p.k_slices;
-        kslice = wg / ntiles;
+        const int ntiles = p.geo.ntiles;   // (= nwg / k_slices)
+        kslice = (int)divmagic_div((unsigned)wg, p.geo.nt);
         tile_id = wg - kslice * ntiles;
         kt0 = kslice * p.ksteps_per_slice;
         nk_total = p.ksteps - kt0 < p.ksteps_per_slice ? p.ksteps - kt0 : p.ksteps_per_slice;
     }
-    const int ch_tile = tile_id % p.n_ch_tiles + p.ch_tile0, m_tile = tile_id / p.n_ch_tiles + p.m_tile0;
+    const int m_tile_l = (int)divmagic_div((unsigned)tile_id, p.geo.nch);
+    const int ch_tile = tile_id - m_tile_l * p.n_ch_tiles + p.ch_tile0, m_tile = m_tile_l + p.m_tile0;
 
     const int tid = threadIdx.x, chunk = tid & 7, rb = tid >> 3;
     const int PQ = p.P * p.Q;
@@ -149,36 +174,44 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
     // physical 16-byte chunk (tid & 7) of row (tid >> 3) + 32 i, so the XOR swizzle moves to the
     // SOURCE side: it fetches logical chunk lc = (tid & 7) ^ ((row >> 1) & 7).
     const int lc = chunk ^ ((rb >> 1) & 7);
+    // (divisions by P * Q, Q and a level's width: multiply-high and shift, divmagic.h)
+    // LIN: xbase alone - the row's offset m * C + this lane's chunk, or -1 past M.
+    // WFIRST: in the one-stage loop the weight pieces of k-step 0, which need none of this, are issued in front of it.
+    constexpr bool WFIRST = STAGES == 1 && !SPLITK;
     int xbase[XL], xih[XL], xiw[XL];
     int xH[ML ? XL : 1], xW[ML ? XL : 1];   // ML: the row's own level geometry (stride 1 only)
+    auto stage_rows = [&]() {
 #pragma unroll
     for (int i = 0; i < XL; ++i) {
         const int m = m_tile * TM + rb + RSTEP * i;
-        if (ML) { xH[i] = 1; xW[i] = 1; }
-        if (m < p.M) {
-            const int n = m / PQ, rem = m - n * PQ;
-            if (ML) {
-                int st = 0, hh = p.lev_h[0], ww = p.lev_w[0];
+        if constexpr (LIN) { xbase[i] = m < p.M ? m * p.C + lc * 8 : -1; continue; }
+        // (written as selects: a row past M computes row 0's geometry and discards it - with the divisions gone there is
+        // nothing left worth a divergent block per staged row)
+        const bool in = m < p.M;
+        const int mm = in ? m : 0;
+        const int n = (int)divmagic_div((unsigned)mm, p.geo.pq), rem = mm - n * PQ;
+        if constexpr (ML) {
+            int st = 0, hh = p.lev_h[0], ww = p.lev_w[0];
+            DivMagic dw = p.geo.lev[0];
 #pragma unroll
-                for (int L = 1; L < 5; ++L)
-                    if (L < p.nlev && rem >= p.lev_start[L]) { st = p.lev_start[L]; hh = p.lev_h[L]; ww = p.lev_w[L]; }
-                const int local = rem - st, op = local / ww, oq = local - op * ww;
-                xih[i] = op - p.pad;
-                xiw[i] = oq - p.pad;
-                xH[i] = hh; xW[i] = ww;
-                xbase[i] = (int)(n * p.x_img_stride) + (st + xih[i] * ww + xiw[i]) * p.C + lc * 8;
-                continue;
-            }
-            const int op = rem / p.Q, oq = rem - op * p.Q;
-            xih[i] = op * p.stride - p.pad;
-            xiw[i] = oq * p.stride - p.pad;
-            xbase[i] = (int)(n * p.x_img_stride) + (xih[i] * p.W + xiw[i]) * p.C + (SMALLC ? 0 : lc * 8);
+            for (int L = 1; L < 5; ++L)
+                if (L < p.nlev && rem >= p.lev_start[L]) { st = p.lev_start[L]; hh = p.lev_h[L]; ww = p.lev_w[L]; dw = p.geo.lev[L]; }
+            const int local = rem - st, op = (int)divmagic_div((unsigned)local, dw), oq = local - op * ww;
+            const int ih = op - p.pad, iw = oq - p.pad;
+            xih[i] = in ? ih : -(1 << 24);
+            xiw[i] = in ? iw : 0;
+            xH[i] = in ? hh : 1; xW[i] = in ? ww : 1;
+            xbase[i] = in ? (int)(n * p.x_img_stride) + (st + ih * ww + iw) * p.C + lc * 8 : 0;
         } else {
-            xih[i] = -(1 << 24);
-            xiw[i] = 0;
-            xbase[i] = 0;
+            const int op = (int)divmagic_div((unsigned)rem, p.geo.q), oq = rem - op * p.Q;
+            const int ih = op * p.stride - p.pad, iw = oq * p.stride - p.pad;
+            xih[i] = in ? ih : -(1 << 24);
+            xiw[i] = in ? iw : 0;
+            xbase[i] = in ? (int)(n * p.x_img_stride) + (ih * p.W + iw) * p.C + (SMALLC ? 0 : lc * 8) : 0;
         }
     }
+    };
+    if (!WFIRST) stage_rows();
     __amdgpu_buffer_rsrc_t xrsrc =
         __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
     unsigned x_zero_off = p.x_zero_off;
@@ -193,9 +226,9 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
     // position of the NEXT tile to load along K
     int kr = 0, ks = 0, kc = 0, kt_load = kt0;
     if (SPLITK && !SMALLC) {
-        const int taps = kR * kS, cb = kt0 / taps, rs = kt0 - cb * taps;
+        const int taps = kR * kS, cb = (int)divmagic_div((unsigned)kt0, p.geo.taps), rs = kt0 - cb * taps;
         kc = cb << 6;
-        kr = rs / kS;
+        kr = (int)divmagic_div((unsigned)rs, p.geo.s);
         ks = rs - kr * kS;
     }
     // DUAL: from k-step k1steps on, the rows come from the second tensor (1x1, no padding: a row is in the image or past M)
@@ -203,11 +236,11 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const int m = m_tile * TM + rb + RSTEP * i;
-            if (m < p.M) {
-                const int n = m / PQ, rem = m - n * PQ, op = rem / p.Q, oq = rem - op * p.Q;
-                xbase[i] = (int)(n * p.x2_img_stride) + (op * p.W2 + oq) * p.stride2 * p.C2 + lc * 8;
-                xih[i] = 0;
-            }
+            const bool in = m < p.M;
+            const int mm = in ? m : 0;
+            const int n = (int)divmagic_div((unsigned)mm, p.geo.pq), rem = mm - n * PQ, op = (int)divmagic_div((unsigned)rem, p.geo.q), oq = rem - op * p.Q;
+            xbase[i] = in ? (int)(n * p.x2_img_stride) + (op * p.W2 + oq) * p.stride2 * p.C2 + lc * 8 : xbase[i];
+            xih[i] = in ? 0 : xih[i];
             xiw[i] = 0;
         }
         xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x2, 0, (int)p.x2_bytes, 0x00020000);
@@ -242,6 +275,11 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
                                                      (int)(wbase + (unsigned)((RSTEP * d) * p.ldw + t_wk) * 2u), 0, 0, 0);
         } else {
             const int i = d - WL;
+            if constexpr (LIN) {   // (1x1: the tap offset is the channel chunk alone)
+                const unsigned voff = xbase[i] >= 0 ? (unsigned)(xbase[i] + kc_cur) * 2u : x_zero_off;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, dstw + TCH * 128 + i * (RSTEP * 128), 16, (int)voff, 0, 0, 0);
+                return;
+            }
             const bool ok = ML ? ((unsigned)(xih[i] + t_r) < (unsigned)xH[i] && (unsigned)(xiw[i] + t_s) < (unsigned)xW[i])
                                : ((unsigned)(xih[i] + t_r) < (unsigned)p.H && (unsigned)(xiw[i] + t_s) < (unsigned)p.W);
             // padded taps read the 16-byte zero block that ends every activation allocation
@@ -298,7 +336,7 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
             yo = (long long)m * p.ldy + ch;
             ro = (long long)m * p.ldres + ch;
         } else {
-            const int n = m / PQ, rem = m - n * PQ;
+            const int n = (int)divmagic_div((unsigned)m, p.geo.pq), rem = m - n * PQ;
             yo = n * p.y_img_stride + (long long)rem * p.ldy + ch;
             ro = n * p.res_img_stride + (long long)rem * p.ldres + ch;
         }
@@ -361,9 +399,18 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
         // One LDS stage, no overlap inside the workgroup: for the HBM-bound 1x1 layers (K <= 256, one to
         // four steps) what hides latency is the number of workgroups per CU, and 34 KB of LDS (with the
         // split epilogue) lets four of them live on a CU instead of two.
+        if (WFIRST && nk_total > 0) {   // k-step 0: the weight pieces go out before the row geometry is worked out
+            tile_begin();
+#pragma unroll
+            for (int d = 0; d < WL; ++d) tile_part(0, d);
+            stage_rows();
+#pragma unroll
+            for (int d = WL; d < NDMA; ++d) tile_part(0, d);
+            tile_end();
+        }
         for (int kt = 0; kt < nk_total; ++kt) {
             if (kt) __syncthreads();   // every wave is done reading the previous tile
-            load_tile(0);
+            if (kt || !WFIRST) load_tile(0);
             __syncthreads();           // vmcnt(0) + barrier: the tile has landed and is visible
 #pragma unroll
             for (int kk = 0; kk < KS; ++kk) {
@@ -553,6 +600,8 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
     // loop they were re-loaded behind every store)
     f32x4 inv0 = { 0.0f, 0.0f, 0.0f, 0.0f }, inv1 = inv0;
     if (p.y8 && ch_ok) { inv0 = *(const f32x4*)(p.y8_inv + ch); inv1 = *(const f32x4*)(p.y8_inv + ch + 4); }
+    // (launch- and tile-uniform: tanh_from, y8, the tile's last channel)
+    const bool tile_special = p.y8 != nullptr || p.tanh_from < p.ch_base + (ch_tile + 1) * TCH;
     float scale8[FP8 ? 8 : 1];
     if (FP8) {
         const f32x4 s0 = *(const f32x4*)(p.scale + ch), s1 = *(const f32x4*)(p.scale + ch + 4);
@@ -604,7 +653,10 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
             }
             return;
         }
-        if (ch_ok) {
+        // SPECIAL: the tile holds tanh channels or the tensor is also written as E4M3 - both known per tile (tile_special is a
+        // scalar condition); the plain path carries neither the per-element tanh guards nor the fp8 block.
+        auto store_rows = [&](auto special) {
+            constexpr bool SPECIAL = decltype(special)::value;
 #pragma unroll
             for (int pass = 0; pass < NPASS; ++pass) {
                 const int m_l = pass * RPP + rr, m = m_tile * TM + h * EROWS + m_l;
@@ -626,22 +678,28 @@ __global__ __launch_bounds__(WCH * WM * 64, 2) void conv_igemm_f16(const ConvPar
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.0f);
                     }
-                    if (ch + 8 > p.tanh_from) {
+                    if constexpr (SPECIAL) {
+                        if (ch + 8 > p.tanh_from) {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            if (ch + e >= p.tanh_from) v[e] = spec_tanhf(v[e]);
+                            for (int e = 0; e < 8; ++e)
+                                if (ch + e >= p.tanh_from) v[e] = spec_tanhf(v[e]);
+                        }
                     }
                     half8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
                     if (p.y) *(half8*)(p.y + yo) = o;
-                    if (p.y8) {   // fp8 precision: this tensor feeds an fp8 convolution (quantised from the f16-rounded value)
+                    if constexpr (SPECIAL) if (p.y8) {   // fp8 precision: this tensor feeds an fp8 convolution (quantised from the f16-rounded value)
                         const unsigned lo = e4m3_pack4((float)o[0] * inv0[0], (float)o[1] * inv0[1], (float)o[2] * inv0[2], (float)o[3] * inv0[3]);
                         const unsigned hi = e4m3_pack4((float)o[4] * inv1[0], (float)o[5] * inv1[1], (float)o[6] * inv1[2], (float)o[7] * inv1[3]);
                         *(uint2*)(p.y8 + yo) = make_uint2(lo, hi);
                     }
                 }
             }
+        };
+        if (ch_ok) {
+            if (tile_special) store_rows(std::true_type{});
+            else store_rows(std::false_type{});
         }
         if (h + 1 < EPI) __syncthreads();
     }
@@ -892,11 +950,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_f16(const ConvParams p) {
     const int groups = p.cout8 >> 3;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)p.M * groups) return;
-    const int m = (int)(t / groups), ch = (int)(t - (long long)m * groups) * 8;
+    const int m = (int)divmagic_div((unsigned)t, p.geo.groups), ch = (int)(t - (long long)m * groups) * 8;
     long long yo, ro;
     if (p.y_dense) { yo = (long long)m * p.ldy + ch; ro = (long long)m * p.ldres + ch; }
     else {
-        const int PQ = p.P * p.Q, n = m / PQ, rem = m - n * PQ;
+        const int PQ = p.P * p.Q, n = (int)divmagic_div((unsigned)m, p.geo.pq), rem = m - n * PQ;
         yo = n * p.y_img_stride + (long long)rem * p.ldy + ch;
         ro = n * p.res_img_stride + (long long)rem * p.ldres + ch;
     }
@@ -955,7 +1013,7 @@ struct Tile {
     static constexpr ConvKernel kernel() {
         if constexpr (!(FORMS >> F & 1)) return nullptr;
         else return conv_igemm_f16<TCH, TM, WCH, WM, SMALLC, STAGES, EPI, F == FORM_SPLITK || F == FORM_ML_SPLITK || F == FORM_DUAL_SPLITK, MT,
-                                   F == FORM_ML || F == FORM_ML_SPLITK, FP8, F == FORM_RESUP, F == FORM_DUAL || F == FORM_DUAL_SPLITK, F == FORM_TAIL, F == FORM_K3>;
+                                   F == FORM_ML || F == FORM_ML_SPLITK, FP8, F == FORM_RESUP ? 1 : (F == FORM_LIN ? 2 : 0), F == FORM_DUAL || F == FORM_DUAL_SPLITK, F == FORM_TAIL, F == FORM_K3>;
     }
     template <int... F>
     static constexpr ConvTileRow row(ConvTile id, const char* symbol, std::integer_sequence<int, F...>) { return { id, TCH, TM, 64 * WCH * WM, FP8, symbol, { kernel<F>()... } }; }
@@ -963,7 +1021,7 @@ struct Tile {
 };
 
 constexpr unsigned PLAIN = 1u << FORM_PLAIN, K3 = 1u << FORM_K3, SPLITK = 1u << FORM_SPLITK, ML = 1u << FORM_ML, ML_SPLITK = 1u << FORM_ML_SPLITK,
-                   DUAL = 1u << FORM_DUAL, DUAL_SPLITK = 1u << FORM_DUAL_SPLITK, RESUP = 1u << FORM_RESUP, TAIL = 1u << FORM_TAIL;
+                   DUAL = 1u << FORM_DUAL, DUAL_SPLITK = 1u << FORM_DUAL_SPLITK, RESUP = 1u << FORM_RESUP, TAIL = 1u << FORM_TAIL, LIN = 1u << FORM_LIN;
 constexpr unsigned RING_FORMS = PLAIN | SPLITK | ML | ML_SPLITK | DUAL | DUAL_SPLITK | RESUP;   // the latency-bound 3-stage tiles
 // Tile<TCH, TM, WCH, WM, SMALLC, STAGES, EPI, MT, FP8, forms>::row(id, symbol); a launch runs 64 * WCH * WM threads. The rows' order
 // is the kernels' order in the code object, which can move step time by a few tenths of a percent.
@@ -980,8 +1038,8 @@ constexpr ConvTileRow kConvTiles[] = {
     Tile<128, 256, 2, 4, false, 2, 2, 16, false, PLAIN | ML>::row(TILE_128x256_M16, "conv_igemm_f16<128,256,2,4,0,2,mfma16>"),
     Tile<64,  64,  2, 2, false, 3, 1, 32, false, RING_FORMS>::row(TILE_64x64_S3, "conv_igemm_f16<64,64,2,2,0,3>"),
     Tile<256, 256, 2, 4, false, 2, 2, 16, true,  PLAIN | ML | TAIL>::row(TILE_256x256_FP8, "conv_igemm_fp8<256,256,2,4>"),
-    Tile<128, 128, 2, 2, false, 1, 2, 32, false, PLAIN | K3 | ML | DUAL | RESUP>::row(TILE_128x128_K1, "conv_igemm_f16<128,128,2,2,0,1>"),
-    Tile<64,  256, 1, 4, false, 1, 2, 32, false, PLAIN>::row(TILE_64x256_K1, "conv_igemm_f16<64,256,1,4,0,1>"),
+    Tile<128, 128, 2, 2, false, 1, 2, 32, false, PLAIN | K3 | ML | DUAL | RESUP | LIN>::row(TILE_128x128_K1, "conv_igemm_f16<128,128,2,2,0,1>"),
+    Tile<64,  256, 1, 4, false, 1, 2, 32, false, PLAIN | LIN>::row(TILE_64x256_K1, "conv_igemm_f16<64,256,1,4,0,1>"),
     // launches with few 256 x 256 tiles (small batches): four times the workgroups, two per CU
     Tile<128, 128, 2, 2, false, 2, 1, 16, true,  PLAIN | ML>::row(TILE_128x128_FP8, "conv_igemm_fp8<128,128,2,2>"),
     // ... and with at most two 128 x 128 tiles per CU: sixteen times the workgroups
@@ -1008,7 +1066,37 @@ static ConvForm conv_form(const ConvParams& p, ConvTile tile) {
     if (p.x2) return split ? FORM_DUAL_SPLITK : FORM_DUAL;
     if (split) return FORM_SPLITK;
     if (p.res_up) return FORM_RESUP;
+    if (p.x_dense && conv_tile_has(tile, FORM_LIN)) return FORM_LIN;
     return p.R == 3 && p.S == 3 && conv_tile_has(tile, FORM_K3) ? FORM_K3 : FORM_PLAIN;
+}
+
+// The launch's geometry record (ConvParams::geo, x_dense) as its other fields imply it; false: outside divmagic.h's range.
+static bool conv_geometry(const ConvParams& p, ConvTile tile, ConvParams::Geo* g, int* x_dense) {
+    const ConvTileRow& r = conv_row(tile);
+    memset(g, 0, sizeof *g);
+    if (r.tm < 1 || p.M < 1 || p.P < 1 || p.Q < 1 || p.n_ch_tiles < 1) return false;
+    const long long pq = (long long)p.P * p.Q, groups = p.cout8 >> 3;
+    // dividends: a row index m < M + the tile's rows; the reduce kernel's element index < M * groups; work ids < the grid
+    const int slices = p.k_slices > 1 ? p.k_slices : 1;
+    const long long ntiles = (long long)((p.M + r.tm - 1) / r.tm - p.m_tile0) * p.n_ch_tiles;
+    if ((long long)p.M + r.tm >= kDivMagicLimit || ntiles < 1 || ntiles * slices >= kDivMagicLimit) return false;
+    if (slices > 1 && (groups < 1 || (long long)p.M * groups >= kDivMagicLimit)) return false;
+    bool ok = divmagic_make(pq, &g->pq) && divmagic_make(p.Q, &g->q) && divmagic_make(p.n_ch_tiles, &g->nch) && divmagic_make(ntiles, &g->nt) &&
+              divmagic_make(p.R * p.S > 0 ? p.R * p.S : 1, &g->taps) && divmagic_make(p.S > 0 ? p.S : 1, &g->s) && divmagic_make(groups > 0 ? groups : 1, &g->groups);
+    for (int l = 0; l < 5; ++l) ok = ok && divmagic_make(l < p.nlev ? p.lev_w[l] : 1, &g->lev[l]);
+    g->ntiles = (int)ntiles;
+    g->tile = ok ? (int)tile + 1 : 0;
+    // (the dense form keeps m * C + a lane's chunk in an int whose sign marks the rows past M: every offset it can form stays below 2^31)
+    *x_dense = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.nlev == 0 && !p.rs_table && (long long)p.H * p.W == pq && p.x_img_stride == pq * p.C &&
+               ((long long)p.M + r.tm) * p.C + 64 < kDivMagicLimit;
+    return ok;
+}
+hipError_t conv_set_geometry(ConvParams& p, int tile) {
+    return conv_geometry(p, (ConvTile)tile, &p.geo, &p.x_dense) ? hipSuccess : hipErrorInvalidValue;
+}
+// Was the record made for this tile and this grid? (A compare of two ints per launch; the record itself is computed once, by the plan.)
+static bool conv_geometry_matches(const ConvParams& p, ConvTile tile, int n_m_tiles) {
+    return p.geo.tile == (int)tile + 1 && p.geo.ntiles == n_m_tiles * p.n_ch_tiles;
 }
 
 // Parameters a form cannot take.
@@ -1037,6 +1125,8 @@ std::string conv_label(const ConvParams& p, ConvTile tile) {
 }
 
 hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream) {
+    // (the plan-time record holds this kernel's two divisors; its element index is below M * cout8 / 8)
+    if (p.cout8 < 8 || p.geo.tile == 0 || (long long)p.M * (p.cout8 >> 3) >= kDivMagicLimit) return hipErrorInvalidValue;
     const long long work = (long long)p.M * (p.cout8 >> 3);
     hipLaunchKernelGGL(splitk_reduce_f16, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, p);
     return hipGetLastError();
@@ -1049,6 +1139,7 @@ hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream) {
     if (!r.kernel[f] || conv_form_rejects(p, f) || (r.fp8 && !p.scale)) return hipErrorInvalidValue;
     const int n_m_tiles = (p.M + r.tm - 1) / r.tm - p.m_tile0;
     if (n_m_tiles < 1) return hipErrorInvalidValue;
+    if (!conv_geometry_matches(p, tile, n_m_tiles)) return hipErrorInvalidValue;   // conv_set_geometry was not run on these parameters, or refused them
     const int slices = p.k_slices > 1 ? p.k_slices : 1;   // (the split-K forms' grid also splits K)
     hipLaunchKernelGGL(r.kernel[f], dim3((unsigned)(n_m_tiles * p.n_ch_tiles * slices)), dim3(r.threads), 0, stream, p);
     return hipGetLastError();

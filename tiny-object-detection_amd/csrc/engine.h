@@ -97,7 +97,7 @@ struct Op {
 
 // The handle's tuning with every default resolved (include/yolact_hip_debug.h: yh_tuning; -1 = default there).
 struct Tune {
-    int plan_cus, chsplit, upfuse, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, chain;
+    int plan_cus, chsplit, upfuse, ablate, op_tile, op_kslices, tailfork, dsfuse, headfork_maxb, protofuse, chain, op_xgap, op_tanh_from;
 };
 
 // A convolution is planned as one to two kernel launches; `frac` is the share of the op's

@@ -44,6 +44,7 @@ static Tune resolve_tuning(const yh_tuning& t, int device_cus) {
     r.chsplit = d(t.chsplit, 1); r.upfuse = d(t.upfuse, 1); r.ablate = d(t.ablate, 0); r.op_tile = t.op_tile; r.op_kslices = d(t.op_kslices, 0);
     r.tailfork = d(t.tailfork, 1); r.dsfuse = d(t.dsfuse, 1); r.headfork_maxb = d(t.headfork_maxb, 1 << 20); r.protofuse = d(t.protofuse, 1);
     r.chain = d(t.chain, 17);
+    r.op_xgap = d(t.op_xgap, 0); r.op_tanh_from = d(t.op_tanh_from, 0);
     return r;
 }
 
@@ -578,11 +579,19 @@ int tail_split_tiles(const Tune& tu, int coutPad, const ConvParams& p, ConvTile 
 
 namespace yh {
 
+// plan_conv's last step: each launch's geometry record, now that its tile, rows and channel tiles are final. A launch the record
+// cannot describe keeps a zeroed one, which launch_conv refuses.
+static int with_geometry(KLaunch* out, int n) {
+    for (int i = 0; i < n; ++i)
+        if (conv_set_geometry(out[i].p, out[i].tile) != hipSuccess) { memset(&out[i].p.geo, 0, sizeof out[i].p.geo); out[i].p.x_dense = 0; }
+    return n;
+}
+
 int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, KLaunch out[3]) {
     if (p.k_slices > 1) {   // split-K: main kernel + slab reduction
         out[0] = KLaunch{ false, p, tile, 1.0, "/splitk" };
         out[1] = KLaunch{ true, p, tile, 0.0, "" };
-        return 2;
+        return with_geometry(out, 2);
     }
     // channel split: 384 padded output channels (the shared head's 351) = one 256-wide tile on the
     // fastest kernel + one 128-wide tile, instead of three 128-wide ones (tune.chsplit = 0: off).
@@ -607,13 +616,13 @@ int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, K
         if (streaming && p.nlev > 0 && chsplit == 1 && p.cout8 <= 352) {
             b.ch_tile0 = 0; b.ch_base = 256;
             out[na] = KLaunch{ false, b, TILE_96x128_K1, 128.0 / 384.0, "/ch256-351" };
-            return na + 1;
+            return with_geometry(out, na + 1);
         }
         out[na] = KLaunch{ false, b, streaming ? TILE_128x128_K1 : TILE_128x128, 128.0 / 384.0, "/ch256-383" };
-        return na + 1;
+        return with_geometry(out, na + 1);
     }
     const int mt1 = tail_split_tiles(tu, coutPad, p, tile);
-    if (mt1 == 0) { out[0] = KLaunch{ false, p, tile, 1.0, "" }; return 1; }
+    if (mt1 == 0) { out[0] = KLaunch{ false, p, tile, 1.0, "" }; return with_geometry(out, 1); }
     // two-phase launch: whole rounds of the big tile, then the remaining rows on 128 x 128 tiles whose
     // 16x16x32 MFMA form accumulates every output element in the same order as the big tile does,
     // so a row's bits do not depend on which phase computed it
@@ -624,7 +633,7 @@ int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, K
     const long long tb = (long long)((p.M - a.M + 127) / 128) * b.n_ch_tiles;
     out[0] = KLaunch{ false, a, tile, (double)a.M / p.M, "/rounds" };
     out[1] = KLaunch{ false, b, tb <= tu.plan_cus ? TILE_128x128_S3_M16 : TILE_128x128_M16, (double)(p.M - a.M) / p.M, "/tail" };
-    return 2;
+    return with_geometry(out, 2);
 }
 
 hipError_t launch_k(const KLaunch& k, hipStream_t stream) {
@@ -831,6 +840,7 @@ int fill_bneck_params(yh_engine* h, const Op& ob, int n, BneckParams* out) {
         if (pa.Kpad != 4 * pb.cout || pa.cout != pb.cout) return h->fail(YH_EINVAL, "bottleneck chain: next conv geometry mismatch at " + oa.name);
         p.w1n = pa.w; p.w1n_bytes = (unsigned)((size_t)pa.coutPad * pa.Kpad * 2); p.bias1n = pa.bias; p.a_next = oa.out.d;
     }
+    if (bneck_set_geometry(p) != hipSuccess) return h->fail(YH_EINVAL, "bottleneck chain: row geometry out of range at " + ob.name);
     *out = p;
     return YH_OK;
 }
@@ -878,6 +888,7 @@ int fill_xn_params(yh_engine* h, const Op& oc, int n, BneckParams* out) {
     p.w1n = pa.w; p.w1n_bytes = (unsigned)((size_t)pa.coutPad * pa.Kpad * 2); p.bias1n = pa.bias;
     p.a_next = (!h->fp8_active || oa.write_f16) ? oa.out.d : nullptr;
     if (h->fp8_active && oa.write_q) { p.a_next8 = oa.out.q; p.a_next8_inv = h->act[oa.out.sid].inv_dev; }
+    if (bneck_set_geometry(p) != hipSuccess) return h->fail(YH_EINVAL, "bottleneck launch: row geometry out of range at " + oc.name);
     *out = p;
     return YH_OK;
 }
@@ -1282,6 +1293,7 @@ int yh_get_tuning(const yh_engine* h, yh_tuning* out) {
     const Tune& t = h->tune;
     out->plan_cus = t.plan_cus; out->chsplit = t.chsplit; out->upfuse = t.upfuse; out->ablate = t.ablate; out->op_tile = t.op_tile; out->op_kslices = t.op_kslices;
     out->tailfork = t.tailfork; out->dsfuse = t.dsfuse; out->headfork_maxb = t.headfork_maxb; out->protofuse = t.protofuse; out->chain = t.chain;
+    out->op_xgap = t.op_xgap; out->op_tanh_from = t.op_tanh_from;
     // (tfl_dot, tfl_graph, tfl_fuse, tfl_group belong to yh_tfl handles - yh_tfl_create_tuned - and stay -1 here: an engine handle does not carry them)
     return YH_OK;
 }

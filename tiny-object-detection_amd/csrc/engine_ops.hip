@@ -83,7 +83,16 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);
     const size_t M = (size_t)n * P * Q;
     // host-side staging: pad input channels, repack weights, pad output rows to cout8
-    const std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
+    // (test hook, tune.op_xgap: every image is followed by `gap` elements of 1.0, so the image stride is not the dense H * W * C)
+    const int gap = h->tune.op_xgap;
+    if (gap % 8 != 0) return h->fail(YH_EINVAL, "conv op: tune.op_xgap must be a multiple of 8");
+    const size_t img = (size_t)hh * ww * cs;
+    std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
+    if (gap > 0) {
+        std::vector<uint16_t> g((img + gap) * n, 0x3C00);
+        for (int b = 0; b < n; ++b) memcpy(&g[b * (img + gap)], &xs[b * img], img * 2);
+        xs.swap(g);
+    }
     std::vector<uint16_t> wp((size_t)coutPad * Kpad, 0), rs, ys(M * cout8);
     for (int o = 0; o < cout; ++o)
         for (int t = 0; t < k * k; ++t) memcpy(&wp[(size_t)o * Kpad + (size_t)t * cs], &w[((size_t)o * k * k + t) * cin], (size_t)cin * 2);
@@ -103,12 +112,12 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
         ConvParams p;
         memset(&p, 0, sizeof p);
         p.x = dx; p.w = dw; p.bias = db; p.res = dr; p.y = dy; p.rs_table = dt;
-        p.x_img_stride = (long long)hh * ww * cs; p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
+        p.x_img_stride = (long long)(img + gap); p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = p.y_img_stride;
         p.x_zero_off = zo; p.x_bytes = zo + 16u;
         p.w_bytes = (unsigned)(wp.size() * 2);
         p.N = n; p.H = hh; p.W = ww; p.C = cs; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
         p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad; p.ksteps = Kpad / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
-        p.act = act == 1 ? 1 : 0; p.tanh_from = act == 2 ? 0 : INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile);
+        p.act = act == 1 ? 1 : 0; p.tanh_from = act == 2 ? h->tune.op_tanh_from : INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile);
         if (nlev > 0) {
             p.nlev = nlev;
             for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
@@ -290,7 +299,8 @@ int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int3
         p.N = n; p.H = hh; p.W = ww; p.C = cin / 2; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
         p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad / 2; p.ksteps = Kpad / 128; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / 256; p.k_slices = 1;
-        st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+        st.e = conv_set_geometry(p, TILE_256x256_FP8);
+        if (st.ok()) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
         st.sync(h->stream);
         if (st.ok() && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
             hipEventRecord(h->ev0, h->stream);

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "divmagic.h"
 #include "../../include/yolact_hip_debug.h"   // (the public header + the named tuning fields, measurement / test entry points)
 
 namespace yh {
@@ -121,7 +122,22 @@ struct ConvParams {
     int ksteps_per_slice;
     int partial_ld;       // row stride of the partial slabs in floats (coutPad)
     float* partial;       // [k_slices][M][partial_ld] f32 workspace
+    // Plan-time geometry (conv_set_geometry fills it once the launch's tile, M and channel tiles are final - plan_conv's last step;
+    // launch_conv refuses a launch without a record, or with one made for another tile or grid): every divisor the kernels divide a row index or a work id by, as a
+    // multiplier and a shift (divmagic.h), and whether a row's source offset is linear in m.
+    struct Geo {
+        DivMagic pq, q, lev[5];   // m / (P * Q), rem / Q, a level's local cell / lev_w
+        DivMagic nch, nt;         // tile_id / n_ch_tiles; split-K: work id / tiles per slice
+        DivMagic taps, s;         // split-K: first k-step / (R * S), tap / S
+        DivMagic groups;          // splitk_reduce_f16: element / (cout8 / 8)
+        int ntiles;               // tiles per K slice (the grid / k_slices)
+        int tile;                 // the ConvTile id the record was made for, + 1 (0: no record)
+    } geo;
+    int x_dense;          // 1: 1x1, stride 1, no padding, x_img_stride == P*Q*C - the source offset of row m is m*C and m < M is its bounds test
 };
+// Fills p.geo and p.x_dense for a launch of `tile`. hipErrorInvalidValue: a divisor or a dividend (m < M + the tile's rows, the
+// reduce kernel's M * cout8 / 8) lies outside divmagic.h's proven range.
+hipError_t conv_set_geometry(ConvParams& p, int tile);
 
 // (ids 4, 6, 9-11, 14, 17, 25, 26 belonged to retired experiments: a 256x128 ring tile, the 256 x 256 tile on 32x32x16 MFMAs, the X3W2
 // ring, the shared-patch 3x3 kernel, rings of four, the fp8 ring of three, register-fed 32 x 32 tiles - DESIGN.md §4, §9, §12;
@@ -131,7 +147,8 @@ enum ConvTile { TILE_128x128 = 0, TILE_64x256 = 1, TILE_32x256 = 2, TILE_64x256_
                 TILE_96x128_K1 = 27 /* the streaming tile for a 96-channel remainder (the shared head's channels 256 .. 351): multi-level form only */ };
 // The forms of a tile's kernel: plain, the streaming tile's 3x3 form, split-K, multi-level, two-source, upsampled residual, fused
 // 1x1 tail. conv_igemm.hip's kConvTiles lists which tile is instantiated in which; launch_conv picks a launch's form from ConvParams.
-enum ConvForm { FORM_PLAIN, FORM_K3, FORM_SPLITK, FORM_ML, FORM_ML_SPLITK, FORM_DUAL, FORM_DUAL_SPLITK, FORM_RESUP, FORM_TAIL, CONV_FORMS };
+// FORM_LIN: the streaming tiles' form for plain launches with ConvParams::x_dense (no row arithmetic: the source offset is m * C).
+enum ConvForm { FORM_PLAIN, FORM_K3, FORM_SPLITK, FORM_ML, FORM_ML_SPLITK, FORM_DUAL, FORM_DUAL_SPLITK, FORM_RESUP, FORM_TAIL, FORM_LIN, CONV_FORMS };
 int conv_tile_ch(ConvTile t);   // (0: not a tile id)
 int conv_tile_m(ConvTile t);
 const char* conv_tile_symbol(ConvTile t);
@@ -171,7 +188,9 @@ struct BneckParams {
     unsigned res_bytes;     // ... its residual rows travel by LDS-DMA: the buffer-descriptor range of res
     uint8_t* a_next8;
     const float* a_next8_inv;   // [planes] reciprocal scales, one per channel of a'
+    DivMagic dpq, dq;       // m / (P * Q), rem / Q (bneck_set_geometry; launch_bneck refuses a chain launch without them)
 };
+hipError_t bneck_set_geometry(BneckParams& p);   // hipErrorInvalidValue: outside divmagic.h's proven range
 hipError_t launch_bneck(const BneckParams& p, int planes, int tm, hipStream_t stream);
 const char* bneck_symbol(int planes, int tm, bool next, bool dual = false);
 

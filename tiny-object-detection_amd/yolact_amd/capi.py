@@ -23,11 +23,11 @@ PRECISION_F16, PRECISION_FP8 = 0, 1
 # yh_tuning (include/yolact_hip_debug.h): per-handle measurement / test knobs, -1 = the library's default; the reserved
 # slots that follow them are not named here, so tune= cannot set them
 TUNING_FIELDS = ("plan_cus", "chsplit", "upfuse", "ablate", "op_tile", "op_kslices", "tfl_dot", "tfl_graph", "tailfork", "dsfuse",
-                 "headfork_maxb", "protofuse", "chain", "tfl_fuse", "tfl_group")
+                 "headfork_maxb", "protofuse", "chain", "tfl_fuse", "tfl_group", "op_xgap", "op_tanh_from")
 
 
 class Tuning(C.Structure):
-    _fields_ = [(f, C.c_int32) for f in TUNING_FIELDS] + [("reserved", C.c_int32 * 17)]
+    _fields_ = [(f, C.c_int32) for f in TUNING_FIELDS] + [("reserved", C.c_int32 * 15)]
 
     @classmethod
     def of(cls, **kw):
