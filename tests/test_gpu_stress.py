@@ -92,7 +92,9 @@ def test_stem_pool_random_sizes(eng, oracle):
 def test_tail_random_heads_bit_exact(built, oracle, S, C, top_k, max_dets):
     """Seeded random head tensors through yh_op_detect against the oracle, bit for bit: candidate counts from
     zero to every prior of a class (more than the 4 096 keys the class kernel stages in LDS at S = 320:
-    the unstaged radix-select path), exact score ties, top_k and max_dets that are not powers of two."""
+    the unstaged radix-select path), exact score ties, top_k and max_dets that are not powers of two.
+    (The deterministic cases - every NMS pair, scores on the threshold, the limits of top_k and max_dets, crop
+    windows - are in tests/test_gpu_tail_edges.py.)"""
     import yolact_amd as ya
     eng = ya.Engine(input_size=S, max_batch=2, use_graph=False, num_classes=C, top_k=top_k, max_dets=max_dets)
     P, hp = eng.P, eng.hp
