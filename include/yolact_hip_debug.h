@@ -209,6 +209,24 @@ int yh_op_conv2d_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int
 int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t ho, int32_t wo, int32_t c1,
                           const uint16_t* x2, int32_t h2, int32_t w2, int32_t c2, int32_t stride2,
                           const uint16_t* w, const float* bias, int32_t cout, int32_t act, uint16_t* y);
+/* One bottleneck launch of csrc/bneck.hip on caller tensors (dense host arrays, f16 as bits), the only way to run a row of
+ * kBneckChains or bneck_xn_f16 without a network around it:
+ *   b  = relu(conv3x3(a; stride, pad 1) + bias2)            a [n][hh][ww][planes], w2 [planes][3][3][planes], stride 1 or 2
+ *   y  = relu(w3 [b ; x2] + bias3 (+ res))                   w3 [4 planes][planes (+ 64)], y [M][4 planes], M = n P Q
+ *   a' = relu(w1n y + bias1n)                                w1n [planes][4 planes], a_next [M][planes]
+ * planes 64 / 128 with tile_m, w1n != NULL (the next block's reduce conv) and x2 != NULL (the stage's first block) select the row
+ * of kBneckChains; either res [M][4 planes] (identity shortcut) or x2 [n][h2][w2][64] read at stride2 (pixel (p, q) <- (p stride2,
+ * q stride2)) together with w1n. a_next is written iff w1n is given. planes 256, tile_m 64: bneck_xn_f16 - a IS b, [n][hh][ww][256]
+ * (w2, bias2, stride unused), res and w1n required, and a' goes to a_next and / or, as E4M3 codes of a' * inv_scale[channel],
+ * to a_next8 [M][256] (at least one of the two). YH_EINVAL with a message, and no launch, for a combination launch_bneck has no
+ * kernel for. tune.op_xgap: every image of a is followed by that many elements of 1.0 (chains only: bneck_xn_f16 reads dense
+ * rows and refuses a gap). Every output is staged with 256 guard rows of 0xFF behind row M - 1: YH_EOVERFLOW with a message if the
+ * launch changed one of their bytes. */
+int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t* a, int32_t n, int32_t hh, int32_t ww,
+                    const uint16_t* w2, const float* bias2, int32_t stride, const uint16_t* w3, const float* bias3,
+                    const uint16_t* res, const uint16_t* x2, int32_t h2, int32_t w2w, int32_t stride2,
+                    const uint16_t* w1n, const float* bias1n, uint16_t* y, uint16_t* a_next, uint8_t* a_next8,
+                    const float* inv_scale);
 /* Bilinear resize (align_corners = false) of an NHWC f16 tensor, optional accumulate into dst. */
 int yh_op_bilinear_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c,
                        int32_t ho, int32_t wo, uint16_t* y);

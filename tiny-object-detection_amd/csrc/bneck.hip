@@ -17,7 +17,8 @@
 // order as conv_igemm_f16's streaming tiles (k = 64-channel chunk outer, taps inner, four 16-deep slices per step), the
 // epilogues apply the same f32 operations in the same order (acc + bias, + residual, max 0, round to f16), and the
 // intermediates are rounded to f16 exactly where the separate launches store them. tests/test_gpu_bneck.py compares the
-// fused engine with the unfused one bit for bit.
+// fused engine with the unfused one bit for bit (the square maps of a whole network); tests/test_gpu_bneck_op.py runs every row
+// of kBneckChains and bneck_xn_f16 alone (yh_op_bneck_f16) on ragged, non-square and tiny shapes, exact against a numpy reference.
 //
 // LDS (one array; PL = 64, TM = 256: 80 KB -> two workgroups per CU):
 //   [0, A)        phase 1: weight tile [PL][128 B] + activation tile [TM][128 B] of the current k-step (single stage, as the
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void bneck_chain_f16(const BneckParams p) {
 // __shared__ arrays give it alias scopes to try), is vmcnt(0) - it would drain the next step's DMAs every step (seen in the ISA).
 //
 // Same MFMA products in the same order and the same f32 epilogue operations as the two separate launches: bit-identical to them
-// (tests/test_gpu_bneck.py).
+// (tests/test_gpu_bneck.py; alone and against an independent reference: tests/test_gpu_bneck_op.py).
 __global__ __launch_bounds__(512, 1) void bneck_xn_f16(const BneckParams p) {
     constexpr int PL = 256, TM = 64, KT = 4, C4 = 1024, NOC = 16;
     constexpr int W2_BYTES = KT * 64 * 128, W3_BYTES = PL * 128, ST_BYTES = TM * 128;   // 32 KB, 32 KB, 8 KB

@@ -181,6 +181,99 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
     return st.status(h, "dual conv op: ");
 }
 
+// One launch of bneck.hip (a row of kBneckChains, or bneck_xn_f16 for 256 planes) on caller tensors. The host arrays are already
+// the kernels' panels: w2 [planes][(r, s, c)], w3 [4 planes][planes (+ 64)], w1n [planes][4 planes].
+int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t* a, int32_t n, int32_t hh, int32_t ww,
+                    const uint16_t* w2, const float* bias2, int32_t stride, const uint16_t* w3, const float* bias3,
+                    const uint16_t* res, const uint16_t* x2, int32_t h2, int32_t w2w, int32_t stride2,
+                    const uint16_t* w1n, const float* bias1n, uint16_t* y, uint16_t* a_next, uint8_t* a_next8,
+                    const float* inv_scale) {
+    if (!h || !a || !w3 || !bias3 || !y) return YH_EINVAL;
+    if (planes != 64 && planes != 128 && planes != 256) return h->fail(YH_EINVAL, "bneck op: planes must be 64, 128 or 256");
+    if (n < 1 || hh < 1 || ww < 1) return h->fail(YH_EINVAL, "bneck op: empty input");
+    const bool xn = planes == 256, dual = x2 != nullptr, next = w1n != nullptr;
+    const int gap = h->tune.op_xgap;
+    if (gap < 0 || gap % 8 != 0) return h->fail(YH_EINVAL, "bneck op: tune.op_xgap must be a multiple of 8");
+    if (next && !bias1n) return h->fail(YH_EINVAL, "bneck op: w1n without bias1n");
+    int P = hh, Q = ww;
+    if (xn) {
+        if (tile_m != 64) return h->fail(YH_EINVAL, "bneck op: bneck_xn_f16 runs on 64-pixel tiles");
+        if (dual || !res || !next) return h->fail(YH_EINVAL, "bneck op: bneck_xn_f16 needs res and w1n, and has no two-source form");
+        if (!a_next && !a_next8) return h->fail(YH_EINVAL, "bneck op: bneck_xn_f16 needs a_next or a_next8");
+        if (a_next8 && !inv_scale) return h->fail(YH_EINVAL, "bneck op: a_next8 without inv_scale");
+        if (gap) return h->fail(YH_EINVAL, "bneck op: bneck_xn_f16 reads dense rows, tune.op_xgap must be 0");
+    } else {
+        if (!w2 || !bias2 || (stride != 1 && stride != 2)) return h->fail(YH_EINVAL, "bneck op: a chain needs w2, bias2 and stride 1 or 2");
+        if (a_next8) return h->fail(YH_EINVAL, "bneck op: only bneck_xn_f16 writes E4M3 codes");
+        if (dual && res) return h->fail(YH_EINVAL, "bneck op: the two-source form has no identity shortcut (x2 and res given)");
+        if (dual && !next) return h->fail(YH_EINVAL, "bneck op: the two-source form needs w1n");
+        if (!dual && !res) return h->fail(YH_EINVAL, "bneck op: need res or x2");
+        if (next != (a_next != nullptr)) return h->fail(YH_EINVAL, "bneck op: a_next goes with w1n");
+        if (!strcmp(bneck_symbol(planes, tile_m, next, dual), "?")) return h->fail(YH_EINVAL, "bneck op: no bneck_chain_f16 for this planes, tile_m, w1n, x2");
+        P = out_dim(hh, 3, stride, 1); Q = out_dim(ww, 3, stride, 1);
+        if (dual && (stride2 < 1 || h2 < 1 || w2w < 1 || (long long)(P - 1) * stride2 >= h2 || (long long)(Q - 1) * stride2 >= w2w))
+            return h->fail(YH_EINVAL, "bneck op: x2 must cover the strided output grid");
+    }
+    HIPCHK(h, hipSetDevice(h->dev));
+    constexpr size_t kGuardRows = 256;
+    const int C4 = 4 * planes, C2 = dual ? 64 : 0;
+    const size_t M = (size_t)n * P * Q, img = (size_t)hh * ww * planes, n2 = dual ? (size_t)n * h2 * w2w * 64 : 0;
+    std::vector<uint16_t> as((img + gap) * n, 0x3C00);   // (test hook, tune.op_xgap: ones behind every image)
+    for (int b = 0; b < n; ++b) memcpy(&as[b * (img + gap)], &a[b * img], img * 2);
+    const size_t ny = M * C4, nan_ = M * planes, gy = kGuardRows * C4, ga = kGuardRows * planes;
+    OpStaging st;
+    BneckParams p;
+    memset(&p, 0, sizeof p);
+    unsigned z2 = 0;
+    p.a = st.upload_padded<half_t>(as.data(), as.size() * 2, as.size() * 2 + 64, &p.a_zero_off);
+    p.a_bytes = p.a_zero_off + 16u; p.a_img_stride = (long long)(img + gap);
+    p.N = n; p.H = hh; p.W = ww; p.P = P; p.Q = Q; p.stride = xn ? 1 : stride; p.M = (int)M; p.no_b = xn ? 1 : 0;
+    if (!xn) {
+        p.w2_bytes = (unsigned)((size_t)planes * 9 * planes * 2);
+        p.w2 = st.upload<half_t>(w2, p.w2_bytes); p.bias2 = st.upload<float>(bias2, (size_t)planes * 4);
+    }
+    p.w3_bytes = (unsigned)((size_t)C4 * (planes + C2) * 2);
+    p.w3 = st.upload<half_t>(w3, p.w3_bytes); p.bias3 = st.upload<float>(bias3, (size_t)C4 * 4);
+    if (res) { p.res_bytes = (unsigned)(ny * 2); p.res = st.upload<half_t>(res, ny * 2); }
+    if (dual) {
+        p.x2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
+        p.x2_bytes = z2 + 16u; p.x2_img_stride = (long long)h2 * w2w * 64; p.W2 = w2w; p.C2 = 64; p.stride2 = stride2;
+    }
+    if (next) {
+        p.w1n_bytes = (unsigned)((size_t)planes * C4 * 2);
+        p.w1n = st.upload<half_t>(w1n, p.w1n_bytes); p.bias1n = st.upload<float>(bias1n, (size_t)planes * 4);
+    }
+    // outputs: 0xFF everywhere, kGuardRows rows behind row M - 1 that no launch may touch
+    p.y = st.alloc<half_t>((ny + gy) * 2, 0xFF);
+    if (a_next) p.a_next = st.alloc<half_t>((nan_ + ga) * 2, 0xFF);
+    if (a_next8) { p.a_next8 = st.alloc<uint8_t>(nan_ + ga, 0xFF); p.a_next8_inv = st.upload<float>(inv_scale, (size_t)planes * 4); }
+    if (st.ok()) {
+        if (bneck_set_geometry(p) != hipSuccess) return h->fail(YH_EINVAL, "bneck op: row geometry out of range");
+        st.e = launch_bneck(p, planes, tile_m, h->stream);
+        if (st.e == hipErrorInvalidValue) return h->fail(YH_EINVAL, "bneck op: launch_bneck has no kernel for these parameters");   // (nothing was launched)
+    }
+    st.sync(h->stream);
+    std::vector<uint16_t> ys(ny + gy), an(a_next ? nan_ + ga : 0);
+    std::vector<uint8_t> a8(a_next8 ? nan_ + ga : 0);
+    st.get(ys.data(), p.y, ys.size() * 2);
+    if (a_next) st.get(an.data(), p.a_next, an.size() * 2);
+    if (a_next8) st.get(a8.data(), p.a_next8, a8.size());
+    if (const int rc = st.status(h, "bneck op: ")) return rc;
+    const auto touched = [](const void* v, size_t from, size_t to) {
+        const uint8_t* b = (const uint8_t*)v;
+        for (size_t i = from; i < to; ++i) if (b[i] != 0xFF) return true;
+        return false;
+    };
+    const char* const sym = bneck_symbol(planes, tile_m, next, dual);
+    if (touched(ys.data(), ny * 2, ys.size() * 2)) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored y rows past M");
+    if (a_next && touched(an.data(), nan_ * 2, an.size() * 2)) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored a_next rows past M");
+    if (a_next8 && touched(a8.data(), nan_, a8.size())) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored a_next8 rows past M");
+    memcpy(y, ys.data(), ny * 2);
+    if (a_next) memcpy(a_next, an.data(), nan_ * 2);
+    if (a_next8) memcpy(a_next8, a8.data(), nan_);
+    return YH_OK;
+}
+
 int yh_op_conv2d_levels_f16(yh_engine* h, const uint16_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
                             const uint16_t* w, const float* bias, int32_t cout, int32_t k, int32_t act, uint16_t* y) {
     if (!level_sizes || nlev < 1 || nlev > 5 || cin % 64 != 0 || (k != 1 && k != 3)) return YH_EINVAL;

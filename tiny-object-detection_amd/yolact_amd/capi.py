@@ -203,6 +203,7 @@ SYMBOLS = [
     ("yh_op_absmax_channels_f16", _i, [_vp, _vp, C.c_int64, _i, _vp]),
     ("yh_op_conv2d_fp8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     ("yh_op_conv2d_dual_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    ("yh_op_bneck_f16", _i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_op_conv2d_levels_f16", _i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     ("yh_op_conv2d_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     ("yh_op_bilinear_f16", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -727,6 +728,29 @@ class Engine:
         y = np.zeros((n, ho, wo, cout), np.uint16)
         self._chk(self.L.yh_op_conv2d_dual_f16(self.h, _p(x1b), n, ho, wo, c1, _p(x2b), h2, w2, c2, stride2, _p(wb), _p(bias), cout, act, _p(y)))
         return y.view(np.float16).astype(np.float32)
+
+    def op_bneck(self, planes, tile_m, a, w3, bias3, w2=None, bias2=None, stride=1, res=None, x2=None, stride2=1, w1n=None, bias1n=None,
+                 want_a_next=None, inv_scale=None):
+        """One launch of csrc/bneck.hip (yh_op_bneck_f16): a [n][H][W][planes], w2 [planes][3][3][planes], w3 [4 planes][planes (+ 64)],
+        res [n][P][Q][4 planes] or x2 [n][H2][W2][64] at stride2, w1n [planes][4 planes]; planes 256: a is b, inv_scale [256] asks for the
+        E4M3 codes of a'. want_a_next (default: w1n given) asks for a' as f16. -> dict(y [n][P][Q][4 planes] f32, a_next f32 or None,
+        a_next8 uint8 or None)."""
+        n, hh, ww, _ = a.shape
+        P, Q = (hh, ww) if planes == 256 else ((hh - 1) // stride + 1, (ww - 1) // stride + 1)
+        f = lambda v: None if v is None else _f16_bits(v)
+        g = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        q = lambda v: None if v is None else _p(v)
+        ab, w2b, w3b, rb, x2b, w1b = f(a), f(w2), f(w3), f(res), f(x2), f(w1n)
+        b2, b3, b1, inv = g(bias2), g(bias3), g(bias1n), g(inv_scale)
+        if want_a_next is None:
+            want_a_next = w1n is not None
+        y = np.zeros((n, P, Q, 4 * planes), np.uint16)
+        an = np.zeros((n, P, Q, planes), np.uint16) if want_a_next else None
+        a8 = np.zeros((n, P, Q, planes), np.uint8) if inv is not None else None
+        h2, w2w = (x2.shape[1], x2.shape[2]) if x2 is not None else (0, 0)
+        self._chk(self.L.yh_op_bneck_f16(self.h, planes, tile_m, q(ab), n, hh, ww, q(w2b), q(b2), stride, q(w3b), q(b3), q(rb), q(x2b), h2, w2w,
+                                         stride2, q(w1b), q(b1), q(y), q(an), q(a8), q(inv)))
+        return dict(y=_bits_f32(y, y.shape), a_next=None if an is None else _bits_f32(an, an.shape), a_next8=a8)
 
     def op_conv2d_levels(self, x, level_sizes, w, bias, act=0):
         """x [n][cells][cin] with cells = sum(s*s for s in level_sizes); w [cout][k][k][cin] -> [n][cells][cout] f32."""
