@@ -509,6 +509,43 @@ int yh_scene_plan_turn(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL:
  * while path_xy, directions or turns is asked for; YH_ESTATE before a turn plan, or when a frame was appended since. */
 int yh_scene_turn_read(yh_scene* h, float* cost, uint8_t* act, int32_t* path_xy, float* directions, int32_t* turns,
                        int32_t path_capacity, int32_t* path_len);
+/* The turn-aware tour (DESIGN.md section 11 "Turn tour"): yh_scene_plan_tour's question - which target first, then which, and the
+ * whole route - answered on yh_scene_plan_turn's graph, so that the route can be followed by a drive base. Everything not said here
+ * is yh_scene_plan_turn's (states, headings, edge terms, turn_price, the size guard, the action rule, turns and directions) and
+ * yh_scene_plan_tour's (K <= YH_TOUR_MAX distinct targets and how they are chosen, all K! orders on the host, the joining). Per
+ * target t_b the turn plan's cost field d_b f32 [8][h][w] and action field act_b u8 [8][h][w] with the single target t_b (0 and 255
+ * at t_b in all eight layers; K fields solved in the same launches, the edge terms computed once), the label of the nearest target
+ * per state, and the leg table with rows r = 0 .. 8 K: row 0 is the state (start, start_heading), row 1 + 8 a + g the state (t_a,
+ * g); legs[r][b] = d_b at row r's state, arrive[r][b] = the heading with which the walk along act_b from that state reaches t_b
+ * (the row's own heading where its pixel is t_b). An order's total starts from row 0: tot = fl(tot + legs[row][o_j]), then the row
+ * becomes that of (t_{o_j}, arrive[row][o_j]) - each leg is the turn plan's route from the state in which the leg before ended,
+ * the arrival heading taken as it comes (what chaining yh_scene_plan_turn gives), not optimised over. The order of least total,
+ * compared in f32, ties to the lexicographically smallest; its legs' walks joined. Synchronous. Errors as yh_scene_plan_turn and
+ * yh_scene_plan_tour together. A call refused with YH_EINVAL or YH_ESTATE has touched nothing: an earlier turn tour of the same
+ * frame stays readable. A call that fails later (YH_EHIP, a walk that meets no target included) leaves no turn tour. The buffers
+ * (per target 32 bytes of cost, 8 of actions and 40 of route per pixel) are the turn tour's own, allocated at the first call on a
+ * handle and sized by the K in use (they only grow): a plan, a tour, a turn plan and a turn tour do not disturb each other's results. */
+int yh_scene_plan_turn_tour(yh_scene* h, const int32_t* targets_xy /* [n][2] or NULL: the frame's balls */, int32_t n_targets,
+                            int32_t start_x, int32_t start_y, int32_t start_heading /* 0 .. 7 */, float turn_price /* per 45 degrees */);
+/* The last turn tour; any pointer may be NULL. With K = *n_targets (<= YH_TOUR_MAX; size the small arrays for YH_TOUR_MAX):
+ *   targets_xy   i32 [K][2]      the targets in use, t_0 .. t_{K-1}
+ *   order        i32 [K]         the visiting order o: indices into targets_xy
+ *   legs         f32 [1+8K][K]   arrive u8 [1+8K][K]: the leg table described above
+ *   total        f32             the order's total
+ *   leg_headings i32 [K]         the heading with which leg j arrives at t_{o_j} - the heading leg j + 1 starts with
+ *   cost         f32 [K][8][h][w], act u8 [K][8][h][w]   field b has the single target t_b
+ *   label        u8  [8][h][w]   the smallest b with d_b[g][v] == min over b of d_b[g][v]
+ *   path_xy      i32 [cap][2]    the joined route: start .. t_{o_0} .. t_{o_1} .., a junction node once; a leg that starts on its own
+ *                                target adds no node and passes its heading on. A pixel may recur across legs: *path_len <= K w h
+ *   turns        i32 [cap]       per drive step i (*path_len - 1 of them) the signed 45-degree steps made at node i before driving; at
+ *                                a junction counted from the heading the leg before arrived with, in the next leg's action field
+ *   directions   f32 [cap][2]    (d_{o_j}[h_i][n_i] - d_{o_j}[h_i][n_i+1], float32((4 - |turns[i]|) * pi / 4)), j the leg of step i
+ *   leg_ends     i32 [K]         index in path_xy of the node where leg j ends (t_{o_j})
+ * YH_EOVERFLOW (and *path_len set, nothing copied) if path_capacity < *path_len while path_xy, directions or turns is asked for;
+ * YH_ESTATE before a turn tour, or when a frame was appended since. */
+int yh_scene_turn_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs, uint8_t* arrive,
+                            float* total, int32_t* leg_headings, float* cost, uint8_t* act, uint8_t* label, int32_t* path_xy,
+                            float* directions, int32_t* turns, int32_t* leg_ends, int32_t path_capacity, int32_t* path_len);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

@@ -130,6 +130,10 @@ int yh_scene_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* r
 /* The same for the last yh_scene_plan_turn, replayed with its start heading and turn price: rounds and tile runs of the
  * eight-layer field (a tile run relaxes the tile in all eight layers). */
 int yh_scene_turn_time(yh_scene* h, int32_t reps, float* ms_per_plan, int32_t* rounds, int32_t* tile_runs);
+/* The same for the last yh_scene_plan_turn_tour, replayed with its start heading and turn price (the read of the leg table, the
+ * host's choice of the order and the walks fall inside): rounds = launches in which some tile of some field ran, tile_runs summed
+ * over the fields (a tile run relaxes the tile in all eight layers of one field). */
+int yh_scene_turn_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32_t* rounds, int32_t* tile_runs);
 /* Measurement hook: mean device milliseconds per BATCH over `reps` re-runs of the last yh_scene_batch_append (its n_frames and
  * mode) from the staged slots as they are now. It counts as an append: an earlier plan becomes unreadable. */
 int yh_scene_batch_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch);

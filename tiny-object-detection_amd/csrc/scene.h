@@ -1,5 +1,6 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
-// scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_solve.hip (the field solver they run on)
+// scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_turn_tour.hip (the turn-aware tour),
+// scene_solve.hip (the field solver they run on)
 // and scene_batch.hip / scene_batch_turn.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle holds one of these as its
 // core, the arrays those of N frames).
 #pragma once
@@ -14,6 +15,7 @@
 struct yh_scene_path;   // the planner's fields, route and last plan (scene_path.hip); allocated at the first yh_scene_plan
 struct yh_scene_tour;   // the tour's fields, route and last tour (scene_tour.hip); allocated at the first yh_scene_plan_tour
 struct yh_scene_turn;   // the turn-aware planner's fields, route and last turn plan (scene_turn.hip); allocated at the first yh_scene_plan_turn
+struct yh_scene_turn_tour;   // the turn-aware tour's fields, leg table and route (scene_turn_tour.hip); allocated at the first yh_scene_plan_turn_tour
 struct yh_scene_solve;  // the solver's buffers, one set for both (scene_path_dev.h, scene_solve.hip); allocated at the first of either
 
 struct yh_scene {
@@ -41,6 +43,7 @@ struct yh_scene {
     yh_scene_path* path = nullptr;
     yh_scene_tour* tour = nullptr;
     yh_scene_turn* turn = nullptr;
+    yh_scene_turn_tour* turn_tour = nullptr;
     yh_scene_solve* solve = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -51,6 +54,7 @@ namespace yh {
 void scene_path_free(yh_scene* h);   // yh_scene_destroy: the planner's buffers (the handle's device is current, its stream idle)
 void scene_tour_free(yh_scene* h);
 void scene_turn_free(yh_scene* h);
+void scene_turn_tour_free(yh_scene* h);
 void scene_solve_free(yh_scene* h);
 // yh_scene_plan's checks (frame, mode, size guard, start, targets) and its choice of targets, as linear indices; touches nothing
 int scene_plan_targets(yh_scene* h, const int32_t* targets_xy, int32_t n_targets, int32_t start_x, int32_t start_y, std::vector<int32_t>& targets);

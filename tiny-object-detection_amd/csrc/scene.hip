@@ -164,6 +164,7 @@ void yh_scene_destroy(yh_scene* h) {
     scene_path_free(h);
     scene_tour_free(h);
     scene_turn_free(h);
+    scene_turn_tour_free(h);
     scene_solve_free(h);
     void* bufs[] = { h->depth, h->cls_id, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);

@@ -1,6 +1,7 @@
 // scene_turn_dev.h — the turn-aware planner's device code (DESIGN.md §11 "Turns"), shared by scene_turn.hip (yh_scene_plan_turn: one
-// frame) and scene_batch_turn.hip (yh_scene_batch_plan_turn: N frames per launch, the frame from blockIdx.z): the compass, the round
-// over a tile of all eight layers, the action rule and the walk. What they compute and why it is unique is said at the head of
+// frame), scene_batch_turn.hip (yh_scene_batch_plan_turn: N frames per launch, the frame from blockIdx.z) and scene_turn_tour.hip
+// (yh_scene_plan_turn_tour: one field per target, the field from blockIdx.z): the compass, the round over a tile of all eight layers,
+// the action rule, the chase along the action field and the walk. What they compute and why it is unique is said at the head of
 // scene_turn.hip. A body reads the frame it works on through p (cost [8][H][W], edge, edge2, W, H, tx) and through the pointers it is
 // given; it knows nothing of a batch.
 #pragma once
@@ -156,16 +157,11 @@ __device__ __forceinline__ void turn_round_body(const PathParams& p, float tau, 
     }
 }
 
-// act[h][i] of pixel i = blockIdx.x * 256 + threadIdx.x, its edge terms read once for the eight headings: the first of (drive, turn
-// to h - 1, turn to h + 1) whose candidate equals d[h][i] bitwise
-__device__ __forceinline__ void turn_act_body(const PathParams& p, float tau, uint8_t* act) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.W * p.H) return;
-    const size_t npx = (size_t)p.W * p.H;
-    const Around<8> e = around<8>(p, i);
-    float d[8];
+// act[h][i] of pixel i for the eight headings of the field `cost`, e the pixel's edge terms: the first of (drive, turn to h - 1, turn
+// to h + 1) whose candidate equals d[h][i] bitwise. d: the pixel's eight costs, for a caller that goes on with them.
+__device__ __forceinline__ void turn_act_pixel(const Around<8>& e, const float* cost, size_t npx, int i, float tau, uint8_t* act, float (&d)[8]) {
 #pragma unroll
-    for (int h = 0; h < 8; ++h) d[h] = p.cost[h * npx + i];
+    for (int h = 0; h < 8; ++h) d[h] = cost[h * npx + i];
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
         const uint32_t dv = __float_as_uint(d[h]);
@@ -173,9 +169,17 @@ __device__ __forceinline__ void turn_act_body(const PathParams& p, float tau, ui
         int a = ACT_NONE;   // (in reverse, so that the first of the order wins)
         if (__float_as_uint(__fadd_rn(d[(h + 1) & 7], tau)) == dv) a = ACT_CW;
         if (__float_as_uint(__fadd_rn(d[(h + 7) & 7], tau)) == dv) a = ACT_CCW;
-        if (e.at[k] >= 0 && __float_as_uint(cand(p.cost[h * npx + e.at[k]], e.len[k], e.dh[k])) == dv) a = ACT_DRIVE;
+        if (e.at[k] >= 0 && __float_as_uint(cand(cost[h * npx + e.at[k]], e.len[k], e.dh[k])) == dv) a = ACT_DRIVE;
         act[h * npx + i] = (uint8_t)a;
     }
+}
+
+// act[h][i] of pixel i = blockIdx.x * 256 + threadIdx.x, its edge terms read once for the eight headings
+__device__ __forceinline__ void turn_act_body(const PathParams& p, float tau, uint8_t* act) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.W * p.H) return;
+    float d[8];
+    turn_act_pixel(around<8>(p, i), p.cost, (size_t)p.W * p.H, i, tau, act, d);
 }
 
 __device__ __forceinline__ float turn_rot(int k) {   // float32((4 - k) * pi / 4)
@@ -183,20 +187,22 @@ __device__ __forceinline__ float turn_rot(int k) {   // float32((4 - k) * pi / 4
     return k == 0 ? (float)pi : k == 1 ? (float)(3.0 * pi / 4.0) : k == 2 ? (float)(pi / 2.0) : k == 3 ? (float)(pi / 4.0) : 0.0f;
 }
 
-// One wave follows act from (start, heading) through a 32 x 32 x 8 window of it in LDS, writes a node per drive and the turns made
-// before it; then its lanes write the directions.
-// out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk was lost: no target within 8 W H actions, an
-// action that is none, or a drive off the frame (costs strictly decrease along act, so none of this happens at a solution; the
-// bounds are what keeps the loop finite and the stores inside their arrays on any input)
-__device__ __forceinline__ void turn_walk_body(const PathParams& p, const uint8_t* act, int start, int heading, int2* nodes, int32_t* turns, float2* dirs, int32_t* out) {
+// One wave follows act from (start, heading) through a 32 x 32 x 8 window of it in LDS. STORE: it writes a node per drive and the
+// turns made before it (else nodes and turns are not touched: the chase of an entry of the turn tour's leg table). Returns the nodes
+// on the route (start and target included); heading is the one it arrived with; lost: no target within 8 W H actions, an action that
+// is none, or a drive off the frame (costs strictly decrease along act, so none of this happens at a solution; the bounds are what
+// keeps the loop finite and the stores inside their arrays on any input). What it stored is visible to the whole wave on return.
+template <bool STORE>
+__device__ __forceinline__ int turn_chase(const uint8_t* act, int W, int H, int start, int& heading, int2* nodes, int32_t* turns, bool& lost) {
     __shared__ uint8_t win[8 * SP_WS * SP_WS];
-    const int lane = threadIdx.x, W = p.W, H = p.H;
+    const int lane = threadIdx.x;
     const size_t npx = (size_t)W * H;
     const long long cap = 8ll * W * H;
     int cx = start % W, cy = start / W, hd = heading & 7, t = 0, n = 1;
     long long actions = 0;
-    bool done = false, lost = false;
-    if (lane == 0) nodes[0] = make_int2(cx, cy);
+    bool done = false;
+    lost = false;
+    if (STORE && lane == 0) nodes[0] = make_int2(cx, cy);
     while (!done && !lost) {   // (wave-uniform)
         const int wx0 = max(0, min(cx - SP_WS / 2, W - SP_WS)), wy0 = max(0, min(cy - SP_WS / 2, H - SP_WS));
         for (int i = lane; i < 8 * SP_WS * SP_WS; i += 64) {
@@ -214,7 +220,7 @@ __device__ __forceinline__ void turn_walk_body(const PathParams& p, const uint8_
             if (a == ACT_CW) { hd = (hd + 1) & 7; ++t; continue; }
             const int nx = cx + head_dx(hd), ny = cy + head_dy(hd);
             if (a != ACT_DRIVE || nx < 0 || nx >= W || ny < 0 || ny >= H || (size_t)n >= npx) { lost = true; break; }
-            if (lane == 0) { turns[n - 1] = t; nodes[n] = make_int2(nx, ny); }
+            if (STORE && lane == 0) { turns[n - 1] = t; nodes[n] = make_int2(nx, ny); }
             ++n; t = 0; cx = nx; cy = ny;
             if (cx < wx0 || cx >= wx0 + SP_WS || cy < wy0 || cy >= wy0 + SP_WS) break;
         }
@@ -222,6 +228,17 @@ __device__ __forceinline__ void turn_walk_body(const PathParams& p, const uint8_
     }
     __threadfence();
     __syncthreads();
+    heading = hd;
+    return n;
+}
+
+// One wave: the route along act from (start, heading), then its lanes write the directions.
+// out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk was lost (turn_chase)
+__device__ __forceinline__ void turn_walk_body(const PathParams& p, const uint8_t* act, int start, int heading, int2* nodes, int32_t* turns, float2* dirs, int32_t* out) {
+    const int lane = threadIdx.x, W = p.W;
+    const size_t npx = (size_t)W * p.H;
+    bool lost;
+    const int n = turn_chase<true>(act, W, p.H, start, heading, nodes, turns, lost);
     // directions[i] = (d[h_i][n_i] - d[h_i][n_i+1], rot of |turns[i]|): the drive edge alone, h_i the heading driven
     if (!lost)
         for (int i = lane; i + 1 < n; i += 64) {

@@ -160,6 +160,9 @@ SYMBOLS = [
     ("yh_scene_plan_turn", _i, [_vp, _vp, _i, _i, _i, _i, _f]),
     ("yh_scene_turn_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_plan_turn_tour", _i, [_vp, _vp, _i, _i, _i, _i, _f]),
+    ("yh_scene_turn_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_turn_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
@@ -1098,6 +1101,51 @@ class Scene:
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_turn_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_plan=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def plan_turn_tour(self, targets=None, n_targets=3, start=None, heading=6, turn_price=2.0):
+        """The turn-aware tour (DESIGN.md §11 "Turn tour"): one turn-plan field per target solved in the same launches, the visiting
+        order of least total cost with every leg starting in the heading the leg before arrived with, and the joined route.
+        targets, n_targets (at most TOUR_MAX, distinct) and start as plan_tour(); heading and turn_price as plan_turn()."""
+        if start is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("start=None is the reference's START_NODE at 640x480; give the start for other sizes")
+            start = (400, 479)
+        if targets is None:
+            self._chk(self.L.yh_scene_plan_turn_tour(self.h, None, n_targets, start[0], start[1], heading, turn_price))
+        else:
+            t = np.ascontiguousarray(targets, np.int32).reshape(-1, 2)
+            self._chk(self.L.yh_scene_plan_turn_tour(self.h, _p(t), len(t), start[0], start[1], heading, turn_price))
+
+    def read_turn_tour(self, fields=True):
+        """The last turn tour: targets int32 [K][2], order int32 [K], legs f32 [1 + 8K][K] and arrive uint8 [1 + 8K][K] (row 0 the
+        start state, row 1 + 8a + h the state (target a, heading h); column b = to target b: the cost, the heading on arrival),
+        total f32, leg_headings int32 [K], path int32 [L][2], directions f32 [L - 1][2], turns int32 [L - 1], leg_ends int32 [K];
+        with fields=True also cost f32 [K][8][H][W], act uint8 [K][8][H][W], label uint8 [8][H][W]."""
+        k, n, total = C.c_int32(), C.c_int32(), C.c_float()
+        self._chk(self.L.yh_scene_turn_tour_read(self.h, C.byref(k), None, None, None, None, None, None, None, None, None, None, None, None, None, 0, C.byref(n)))
+        K = k.value
+        out = dict(targets=np.zeros((K, 2), np.int32), order=np.zeros(K, np.int32), legs=np.zeros((1 + 8 * K, K), np.float32),
+                   arrive=np.zeros((1 + 8 * K, K), np.uint8), leg_headings=np.zeros(K, np.int32), path=np.zeros((n.value, 2), np.int32),
+                   leg_ends=np.zeros(K, np.int32))
+        dirs, turns = np.zeros((n.value, 2), np.float32), np.zeros(n.value, np.int32)
+        if fields:
+            out["cost"] = np.zeros((K, 8, self.H, self.W), np.float32)
+            out["act"] = np.zeros((K, 8, self.H, self.W), np.uint8)
+            out["label"] = np.zeros((8, self.H, self.W), np.uint8)
+        f = lambda name: _p(out[name]) if fields else None
+        self._chk(self.L.yh_scene_turn_tour_read(self.h, C.byref(k), _p(out["targets"]), _p(out["order"]), _p(out["legs"]), _p(out["arrive"]), C.byref(total),
+                                                 _p(out["leg_headings"]), f("cost"), f("act"), f("label"), _p(out["path"]), _p(dirs), _p(turns),
+                                                 _p(out["leg_ends"]), n.value, C.byref(n)))
+        out["total"] = np.float32(total.value)
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        out["turns"] = turns[:max(n.value - 1, 0)]
+        return out
+
+    def turn_tour_time(self, reps=20):
+        """Replays the last turn tour: dict(ms_per_tour, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_turn_tour_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_tour=ms.value, rounds=r.value, tile_runs=t.value)
 
 
 class SceneBatch:
