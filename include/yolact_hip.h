@@ -612,6 +612,30 @@ int yh_scene_batch_plan_turn(yh_scene_batch* h, const int32_t* targets_xy /* [n]
  * whose status was YH_ESTATE, before a turn plan, and after a newer append; YH_EINVAL for a frame outside the last append. */
 int yh_scene_batch_turn_read(yh_scene_batch* h, int32_t frame, float* cost, uint8_t* act, int32_t* path_xy, float* directions,
                              int32_t* turns, int32_t path_capacity, int32_t* path_len);
+/* yh_scene_plan_turn_tour for every frame of the last append in shared solver rounds (DESIGN.md section 11 "Scene batch: turn
+ * tours"): frame b has exactly the results of yh_scene_plan_turn_tour on a yh_scene fed that frame alone with the same targets, start,
+ * start heading and turn price - every output of yh_scene_turn_tour_read, bit for bit. n_targets (<= YH_TOUR_MAX) is one number per
+ * call; frame b uses K_b <= n_targets of them: with targets_xy NULL its first n_targets balls that have pixels, a ball on an earlier
+ * ball's pixel dropped; a frame with no usable ball gets no tour and status[b] = YH_ESTATE, the others are planned. starts_xy,
+ * start_headings, turn_price and status as yh_scene_batch_plan_turn. The checks are yh_scene_batch_plan_turn's and the tour's, made
+ * for all frames before anything is touched: YH_EINVAL also for n_targets > YH_TOUR_MAX and for two equal explicit targets in one
+ * frame (the text names the frame). A refused call leaves an earlier batched turn tour of the same append readable; a call that
+ * fails later (YH_EHIP: a lost chase or walk, the text names the frame and the entry or leg) leaves none.
+ * The turn tour's buffers are its own, allocated at the first call for max_frames frames x the largest n_targets used so far; they
+ * only grow (growing drops the last batched turn tour). They take 80 bytes per pixel, frame and target (cost 32, act 8, the legs'
+ * walks 20, the joined route 20) plus 8 per pixel and frame for the label: 640 x 480 with max_frames = 64 and n_targets = 6 is
+ * 9.6 GB - size max_frames and n_targets accordingly. The batch's plan, turn plan and turn tour do not disturb each other's
+ * results. Two waits per call, whatever n. Synchronous. */
+int yh_scene_batch_plan_turn_tour(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_targets][2] or NULL */, int32_t n_targets,
+                                  const int32_t* starts_xy /* [n][2] */, const int32_t* start_headings /* [n], 0 .. 7 */,
+                                  float turn_price, int32_t* status /* [n] or NULL */);
+/* One frame of the last batched turn tour, as yh_scene_turn_tour_read (YH_EOVERFLOW with *path_len set and nothing copied included).
+ * YH_ESTATE for a frame whose status was YH_ESTATE, before a batched turn tour, and after a newer append; YH_EINVAL for a frame
+ * outside the last append. */
+int yh_scene_batch_turn_tour_read(yh_scene_batch* h, int32_t frame, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs,
+                                  uint8_t* arrive, float* total, int32_t* leg_headings, float* cost, uint8_t* act, uint8_t* label,
+                                  int32_t* path_xy, float* directions, int32_t* turns, int32_t* leg_ends, int32_t path_capacity,
+                                  int32_t* path_len);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

@@ -143,6 +143,10 @@ int yh_scene_batch_plan_time(yh_scene_batch* h, int32_t reps, float* ms_per_batc
 /* The same for the last yh_scene_batch_plan_turn, replayed with its start headings and turn price: rounds and tile runs of the
  * frames' eight-layer fields. */
 int yh_scene_batch_turn_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
+/* The same for the last yh_scene_batch_plan_turn_tour, replayed with its targets, start states and turn price (the read of the leg
+ * tables, the host's choice of every frame's order and the walks fall inside): rounds = launches in which some tile of some field
+ * of some frame ran, tile_runs summed over all fields. */
+int yh_scene_batch_turn_tour_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
 /* yh_scene_set_fields for one frame of a batch, with the same checks, so that constructed mazes can sit beside easy frames. The first
  * use after create or an append starts a new batch whose n is the highest frame set + 1 (a plan refuses, YH_ESTATE, while a frame
  * below n has been given no fields). It counts as a YH_COMPAT_SANE append (a new frame generation). */

@@ -1,7 +1,7 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
 // scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_turn_tour.hip (the turn-aware tour),
 // scene_solve.hip (the field solver they run on)
-// and scene_batch.hip / scene_batch_turn.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle holds one of these as its
+// and scene_batch.hip / scene_batch_turn.hip / scene_batch_turn_tour.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle holds one of these as its
 // core, the arrays those of N frames).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
-// scene_batch.h — the scene batch handle (yh_scene_batch), shared by scene_batch.hip (stage, append, the plain plan) and
-// scene_batch_turn.hip (the turn-aware plan over the batch).
+// scene_batch.h — the scene batch handle (yh_scene_batch), shared by scene_batch.hip (stage, append, the plain plan),
+// scene_batch_turn.hip (the turn-aware plan over the batch) and scene_batch_turn_tour.hip (the turn-aware tour over the batch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 #include "scene_path_dev.h"
 
 struct yh_scene_batch_turn;   // the turn plan's fields, routes and last call (scene_batch_turn.hip); allocated at the first yh_scene_batch_plan_turn
+struct yh_scene_batch_turn_tour;   // the turn tour's fields, tables, routes and last call (scene_batch_turn_tour.hip); allocated at the first yh_scene_batch_plan_turn_tour
 
 struct yh_scene_batch {
     yh_scene core;
@@ -34,6 +35,7 @@ struct yh_scene_batch {
     std::vector<int32_t> status, path_len, last_seeds, last_field, last_starts;
     std::vector<int32_t> pairs;   // last_seeds and last_field interleaved, as uploaded
     yh_scene_batch_turn* turn = nullptr;   // the turn-aware plan (scene_batch_turn.hip)
+    yh_scene_batch_turn_tour* turn_tour = nullptr;   // the turn-aware tour (scene_batch_turn_tour.hip)
     int fail(int code, const std::string& m) { return core.fail(code, m); }
 };
 
@@ -42,4 +44,5 @@ namespace yh {
 void scene_batch_weights(yh_scene* h, const PathParams& p, int conn, int n);
 // yh_scene_batch_destroy: the turn plan's buffers (the handle's device is current, its stream idle)
 void scene_batch_turn_free(yh_scene_batch* hb);
+void scene_batch_turn_tour_free(yh_scene_batch* hb);   // the same for the turn tour's
 }

@@ -14,7 +14,8 @@
 // The handle holds a yh_scene as its core: device, size, stream, error text, bump tables, the frame generation and mode - and array
 // pointers that are frame 0 of the batch's [max_frames][...] arrays. That is what lets the single handle's host code (the plan's checks
 // and choice of targets, the fields check, the solver's loop, its read and time) run on a batch unchanged. The handle itself is
-// scene_batch.h's; the turn-aware plan over the batch (yh_scene_batch_plan_turn) is scene_batch_turn.hip.
+// scene_batch.h's; the turn-aware plan over the batch (yh_scene_batch_plan_turn) is scene_batch_turn.hip, the turn-aware tour
+// (yh_scene_batch_plan_turn_tour) scene_batch_turn_tour.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -224,6 +225,7 @@ void yh_scene_batch_destroy(yh_scene_batch* hb) {
     if (h->stream) hipStreamSynchronize(h->stream);
     free_planner(hb);
     scene_batch_turn_free(hb);
+    scene_batch_turn_tour_free(hb);
     scene_solve_free(h);
     void* bufs[] = { h->depth, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);

@@ -178,6 +178,9 @@ SYMBOLS = [
     ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_batch_plan_turn_tour", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
+    ("yh_scene_batch_turn_tour_read", _i, [_vp, _i, C.POINTER(_i), _vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_batch_turn_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
@@ -1305,6 +1308,56 @@ class SceneBatch:
         """Replays the last turn plan: dict(ms_per_batch, rounds, tile_runs)."""
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_batch_turn_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def plan_turn_tour(self, targets=None, n_targets=3, starts=None, headings=6, turn_price=2.0):
+        """The turn-aware tour (Scene.plan_turn_tour) of every frame of the last append in shared solver rounds. targets: [n][k]
+        (x, y) pixels, k at most TOUR_MAX and distinct within a frame, or None: each frame's first n_targets balls (a ball on an
+        earlier ball's pixel dropped, so frames may have fewer). starts, headings and turn_price as plan_turn().
+        Returns the status list: OK, or ESTATE for a frame without a usable ball (it has no turn tour)."""
+        n = self.n
+        if starts is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("starts=None is the reference's START_NODE at 640x480; give the starts for other sizes")
+            starts = [(400, 479)] * n
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1, 2)
+        hd = np.full(max(n, 1), headings, np.int32) if np.isscalar(headings) else np.ascontiguousarray(headings, np.int32).reshape(-1)
+        assert len(s) == n and len(hd) >= n
+        status = np.zeros(max(n, 1), np.int32)
+        if targets is None:
+            self._chk(self.L.yh_scene_batch_plan_turn_tour(self.h, None, n_targets, _p(s), _p(hd), turn_price, _p(status)))
+        else:
+            t = np.ascontiguousarray(targets, np.int32)
+            assert t.ndim == 3 and t.shape[0] == n and t.shape[2] == 2
+            self._chk(self.L.yh_scene_batch_plan_turn_tour(self.h, _p(t), t.shape[1], _p(s), _p(hd), turn_price, _p(status)))
+        return [int(v) for v in status[:n]]
+
+    def read_turn_tour(self, b, fields=True):
+        """Frame b of the last turn tour, as Scene.read_turn_tour."""
+        k, n, total = C.c_int32(), C.c_int32(), C.c_float()
+        self._chk(self.L.yh_scene_batch_turn_tour_read(self.h, b, C.byref(k), None, None, None, None, None, None, None, None, None, None, None, None, None, 0, C.byref(n)))
+        K = k.value
+        out = dict(targets=np.zeros((K, 2), np.int32), order=np.zeros(K, np.int32), legs=np.zeros((1 + 8 * K, K), np.float32),
+                   arrive=np.zeros((1 + 8 * K, K), np.uint8), leg_headings=np.zeros(K, np.int32), path=np.zeros((n.value, 2), np.int32),
+                   leg_ends=np.zeros(K, np.int32))
+        dirs, turns = np.zeros((n.value, 2), np.float32), np.zeros(n.value, np.int32)
+        if fields:
+            out["cost"] = np.zeros((K, 8, self.H, self.W), np.float32)
+            out["act"] = np.zeros((K, 8, self.H, self.W), np.uint8)
+            out["label"] = np.zeros((8, self.H, self.W), np.uint8)
+        f = lambda name: _p(out[name]) if fields else None
+        self._chk(self.L.yh_scene_batch_turn_tour_read(self.h, b, C.byref(k), _p(out["targets"]), _p(out["order"]), _p(out["legs"]), _p(out["arrive"]),
+                                                       C.byref(total), _p(out["leg_headings"]), f("cost"), f("act"), f("label"), _p(out["path"]), _p(dirs),
+                                                       _p(turns), _p(out["leg_ends"]), n.value, C.byref(n)))
+        out["total"] = np.float32(total.value)
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        out["turns"] = turns[:max(n.value - 1, 0)]
+        return out
+
+    def turn_tour_time(self, reps=20):
+        """Replays the last turn tour: dict(ms_per_batch, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_batch_turn_tour_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
 
     def set_fields(self, b, map, conn0, conn1):
