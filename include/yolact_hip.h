@@ -336,7 +336,8 @@ int yh_instance_track_reset(yh_engine* h);
  * batch. Synchronous. Everything is checked before anything is touched: a refused call leaves the earlier batch's frames, tables
  * and pointer as they were; a call that fails later leaves no batch. The batch has buffers of its own (allocated at the first
  * call, grow only, freed by yh_destroy): it does not disturb yh_instance_device_frame, yh_instance_read or the tracker, and
- * yh_instance_frame / yh_instance_track do not disturb the batch. Tracking is not batched: a tracker's calls are sequential. */
+ * yh_instance_frame / yh_instance_track do not disturb the batch. The batch with ids that persist is yh_instance_track_batch
+ * below; a plain batch after a tracked one replaces its frames and leaves every tracker alone. */
 int yh_instance_batch(yh_engine* h, int32_t first_frame, int32_t n_frames, int32_t width, int32_t height, const uint8_t* class_map,
                       float min_score, uint32_t* out_host /* [n][H][W] or NULL */);
 /* Device copy of the last batch's frames [n][H][W] (NULL before a batch); valid until the next yh_instance_batch on the handle.
@@ -345,6 +346,33 @@ const uint32_t* yh_instance_batch_device_frames(const yh_engine* h);
 /* The instance table of frame `frame` (0 .. n - 1) of the last batch, with yh_instance_read's conventions: table may be NULL,
  * YH_EOVERFLOW (the count set, nothing copied) if capacity < m rows, YH_ESTATE before a batch; YH_EINVAL for a frame outside it. */
 int yh_instance_batch_read(yh_engine* h, int32_t frame, int32_t* n_instances, int32_t* table, int32_t capacity);
+
+/* ---- instance track batch: a step's frames tracked per camera stream, one wait (DESIGN.md section 11 "Instance track batch") ---
+ * The handle holds a bank of YH_TRACK_STREAMS_MAX trackers; stream 0 is the one yh_instance_track, yh_instance_tracks_read and
+ * yh_instance_track_reset use. yh_instance_track_batch on frames first_frame .. first_frame + n_frames - 1 is exactly this: for
+ * b = 0 .. n_frames - 1 in order, a yh_instance_track call on frame first_frame + b against the tracker of streams[b]. Frame b's
+ * packed frame and instance table are that call's, its track table is that tracker's right after that call, and every tracker ends
+ * in the state those calls leave; trackers of different streams never see each other. Single and batched calls on stream 0
+ * continue each other in both directions. Frames of different streams share launches, frames of one stream are a chain on the
+ * device: there is one wait, whatever n_frames is.
+ * A tracked batch is an instance batch: its frames and instance tables replace the last batch's (yh_instance_batch_device_frames,
+ * yh_instance_batch_read, with the track id in the id's place); yh_instance_device_frame and yh_instance_read are not touched.
+ * States and errors are yh_instance_batch's, plus yh_instance_track's for iou_permille and max_age, plus YH_EINVAL for a stream
+ * outside 0 .. YH_TRACK_STREAMS_MAX - 1 (the message names the frame). Everything is checked before anything is touched: a
+ * refused call leaves the previous batch (frames, tables, pointer, track tables) and every tracker as they were; a call that
+ * fails later leaves no batch and empties every tracker it named. A stream's tracker is created at its first use and freed by
+ * yh_destroy. */
+#define YH_TRACK_STREAMS_MAX 64
+int yh_instance_track_batch(yh_engine* h, int32_t first_frame, int32_t n_frames, int32_t width, int32_t height,
+                            const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age,
+                            const int32_t* streams /* [n_frames], each 0 .. YH_TRACK_STREAMS_MAX - 1, or NULL: all 0 */,
+                            uint32_t* out_host /* [n][H][W] or NULL */);
+/* The tracker of frame `frame`'s stream right after that frame of the last tracked batch: i32 [m][6], yh_instance_tracks_read's
+ * layout and conventions. YH_ESTATE if the handle's last instance batch was not a tracked one (a plain yh_instance_batch since
+ * replaces the frames); YH_EINVAL for a frame outside the batch. */
+int yh_instance_track_batch_read(yh_engine* h, int32_t frame, int32_t* n_tracks, int32_t* table, int32_t capacity);
+/* Empties one stream's tracker, as yh_instance_track_reset does stream 0's; stream -1: all of them. Valid at any time. */
+int yh_instance_track_reset_stream(yh_engine* h, int32_t stream);
 
 /* ---- reference-compat path: Yolact::classify (src/yolact.rs:39-41, :192-234) --------------- */
 

@@ -297,6 +297,14 @@ int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* clas
 int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
                          int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height, const uint8_t* class_map,
                          float min_score, uint32_t* out_host);
+/* A tracked batch (yh_instance_track_batch) on caller-provided detections: yh_op_instance_batch's arguments and limits plus
+ * iou_permille, max_age and streams i32 [n_frames] (or NULL: all 0); the same kernels run, against the handle's bank of trackers, so
+ * successive calls - and yh_op_instance_track calls on stream 0 between them - form the sequences. A stream whose tracker was
+ * built at another hp x wp starts empty. The track tables are read with yh_instance_track_batch_read. */
+int yh_op_instance_track_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                               int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height,
+                               const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age, const int32_t* streams,
+                               uint32_t* out_host);
 
 #ifdef __cplusplus
 }

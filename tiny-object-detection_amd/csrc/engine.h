@@ -1,6 +1,7 @@
 // engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
 // Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
-// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip, instance_batch.hip and instance_track.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
+// (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip, instance_batch.hip, instance_track.hip and
+// instance_track_batch.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -50,6 +51,19 @@ struct Buf {               // dense NHWC f16 tensor [max_batch][h][w][c] or a sl
 };
 
 struct DevAlloc { void* p; size_t bytes; };   // one hipMalloc of a handle
+
+// One tracker of the handle's bank (instance_track.hip): stream 0 is yh_instance_track's, the others are reached through
+// yh_instance_track_batch only. Device buffers are allocated at the stream's first use and freed by yh_destroy.
+struct TrkStream {
+    uint4* img = nullptr;           // T [hp * wp]: bit s = slot s's last seen mask is on there
+    int32_t* state = nullptr;       // slots [128][4] = (class or 0, id, age, area), rank of slot, slot of rank, keep [4]
+    size_t img_cap = 0;
+    int hp = 0, wp = 0;             // the prototype size T was built at
+    bool live = false;              // false: the next tracked call starts from an empty tracker
+    std::vector<int32_t> table;     // [rows][6] = (slot, class, id, age, area, rank or -1) after the stream's last tracked frame
+    int rows = -1;                  // -1: no tracked call on this stream yet
+};
+constexpr int kTrkStreams = 64;     // YH_TRACK_STREAMS_MAX
 
 // One activation allocation (new_buf), indexed by Buf::sid: where it lies and, in fp8 handles, its scales.
 // Round 4: one activation scale per CHANNEL of every allocation an fp8 convolution reads (a per-tensor scale is the same value in
@@ -193,16 +207,19 @@ struct yh_engine {
     std::vector<uint32_t> instb_meta_host;          // [n][2][128] as read back
     std::vector<std::vector<int32_t>> instb_tables; // per frame of the last batch: [rows][4]
     int instb_n = -1;                 // frames of the last batch; -1: no batch
-    // instance tracks (instance_track.hip): allocated at the first yh_instance_track, freed by yh_destroy
-    uint4* trk_img = nullptr;       // T [hp * wp]: bit s = slot s's last seen mask is on there
+    // instance tracks (instance_track.hip): the bank of trackers, stream 0 the one yh_instance_track advances
+    yh::TrkStream trk[yh::kTrkStreams];
     uint32_t* trk_ov = nullptr;     // I [128][128] then A [128]: zeroed on the stream by every tracked call
-    int32_t* trk_state = nullptr;   // slots [128][4] = (class or 0, id, age, area), rank of slot, slot of rank, keep [4]
-    size_t trk_img_cap = 0;
-    int trk_hp = 0, trk_wp = 0;     // the prototype size T was built at
-    bool trk_live = false;          // false: the next tracked call starts from an empty tracker
     int32_t trk_host[640] = {};     // where the slots and their ranks are read back to (a member: the copy is asynchronous)
-    std::vector<int32_t> trk_table; // [trk_rows][6] = (slot, class, id, age, area, rank or -1) after the last tracked call
-    int trk_rows = -1;              // -1: no tracked call yet
+    // instance track batch (instance_track_batch.hip): a tracked batch is an instance batch (instb_*) plus these, grow only
+    uint32_t* trkb_ov = nullptr;    // [n][128 * 128 + 128]: I and A of every frame, zeroed on the stream by every tracked batch
+    int32_t* trkb_snap = nullptr;   // [n][640]: the slots and their ranks of the frame's stream right after that frame
+    void* trkb_desc = nullptr;      // the call's (round, entry) descriptors
+    size_t trkb_ov_cap = 0, trkb_snap_cap = 0, trkb_desc_cap = 0;
+    std::vector<uint8_t> trkb_desc_host;             // (members: the copies are asynchronous)
+    std::vector<int32_t> trkb_snap_host;
+    std::vector<std::vector<int32_t>> trkb_tables;  // per frame of the last tracked batch: [rows][6]
+    int trkb_n = -1;                // frames of the last batch if it was a tracked one; -1: it was not (or there is none)
     // output staging
     float* out_f32 = nullptr;
     size_t out_f32_cap = 0;
@@ -273,16 +290,28 @@ int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes);   // a dev
 void instance_class_map(const uint8_t* class_map, int ncls, std::vector<uint8_t>& out);   // the call's class map, NULL resolved
 void instance_table(const uint32_t* meta, std::vector<int32_t>& table);   // meta [2][128] as read back -> rows (rank, class, id, pixels)
 // instance_batch.hip: n frames in one pair of launches; frame b reads masks + b max_n px, dets + b max_n, count + b
+struct InstTrackBatch { InstTrack p; const int32_t* streams; };   // a tracked batch: streams [n] or nullptr (all 0); checked by the caller
 int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,
-                       int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host);
+                       int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host,
+                       const InstTrackBatch* trk = nullptr);
 void instance_batch_free(yh_engine* h);
 // instance_track.hip: the stages instance_run puts between inst_pack and inst_paint, behind the read-back and behind the wait
 const char* track_check(int iou_permille, int max_age);   // nullptr: fine
+int track_prepare(yh_engine* h, int stream, int hp, int wp);   // the stream's T and state exist; not live or another size: emptied on the stream
 int track_enqueue(yh_engine* h, int hp, int wp, const InstTrack& trk);
 int track_readback(yh_engine* h);
 void track_finish(yh_engine* h);
-void track_drop(yh_engine* h);   // an empty tracker (a tracked call that failed, yh_instance_track_reset)
+void track_rows(const int32_t* st, std::vector<int32_t>& table);   // the slots and their ranks as read back -> rows (slot, class, id, age, area, rank)
+void track_drop(yh_engine* h, int stream = 0);   // an empty tracker (a tracked call that failed, yh_instance_track_reset)
 void track_free(yh_engine* h);
+// instance_track_batch.hip: the stages instance_batch_run puts between inst_batch_pack and inst_batch_paint, behind the read-back
+// and behind the wait, for n frames each on its stream's tracker
+std::string track_batch_check(int n, const int32_t* streams);   // empty: fine
+int track_batch_enqueue(yh_engine* h, int n, int hp, int wp, const InstTrackBatch& trk);
+int track_batch_readback(yh_engine* h, int n);
+void track_batch_finish(yh_engine* h, int n, const InstTrackBatch& trk);
+void track_batch_drop(yh_engine* h, int n, const InstTrackBatch& trk);   // empties every tracker the call named
+void track_batch_free(yh_engine* h);
 // fp8.hip
 void plan_fp8(yh_engine* h);
 std::string fp8_missing(const yh_engine* h);

@@ -511,9 +511,10 @@ int yh_op_instance_track(yh_engine* h, const uint8_t* masks, const int32_t* clas
 
 // The instance batch's kernels (instance_batch.hip) on caller-provided detections of n_frames frames, n_dets slots each: what
 // yh_instance_batch runs on the tail's. The slots past a frame's count are uploaded as 0xFF: a kernel that read them would paint them.
-int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
-                         int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height, const uint8_t* class_map,
-                         float min_score, uint32_t* out_host) {
+// (trk: what yh_instance_track_batch runs, instance_track_batch.hip's rounds between the two launches, on the handle's bank.)
+static int op_instance_batch_impl(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                                  int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height,
+                                  const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrackBatch* trk) {
     if (!h || !counts || (n_dets > 0 && (!masks || !class_ids || !scores))) return YH_EINVAL;
     if (n_frames < 1 || n_frames > 64) return h->fail(YH_EINVAL, "instance batch op: n_frames outside 1 .. 64");
     if (n_dets < 0 || n_dets > h->cfg.max_dets) return h->fail(YH_EINVAL, "instance batch op: n_dets outside 0 .. max_dets");
@@ -525,6 +526,11 @@ int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* clas
                 return h->fail(YH_EINVAL, "instance batch op: class id out of range");
     }
     if (const char* why = instance_check(width, height, class_map, h->C - 1, min_score)) return h->fail(YH_EINVAL, why);
+    if (trk) {
+        if (const char* why = track_check(trk->p.iou_permille, trk->p.max_age)) return h->fail(YH_EINVAL, why);
+        const std::string why = track_batch_check(n_frames, trk->streams);
+        if (!why.empty()) return h->fail(YH_EINVAL, why);
+    }
     HIPCHK(h, hipSetDevice(h->dev));
     const size_t px = (size_t)hp * wp, slots = (size_t)n_frames * n_dets;
     std::vector<yh_detection> dets(slots + 1);
@@ -539,8 +545,27 @@ int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* clas
     const uint8_t* dm = st.upload<uint8_t>(ms.data(), ms.size());
     const yh_detection* dd = st.upload<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
     const int* dc = st.upload<int>(counts, (size_t)n_frames * sizeof(int));
-    if (const int rc = st.status(h, "instance batch op: ")) return rc;
-    return instance_batch_run(h, dm, dd, dc, n_dets, n_frames, hp, wp, width, height, class_map, min_score, out_host);
+    if (const int rc = st.status(h, "instance batch op: ")) {
+        if (trk) track_batch_drop(h, n_frames, *trk);
+        return rc;
+    }
+    return instance_batch_run(h, dm, dd, dc, n_dets, n_frames, hp, wp, width, height, class_map, min_score, out_host, trk);
+}
+
+int yh_op_instance_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                         int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height, const uint8_t* class_map,
+                         float min_score, uint32_t* out_host) {
+    return op_instance_batch_impl(h, masks, class_ids, scores, counts, n_frames, n_dets, hp, wp, width, height, class_map, min_score,
+                                  out_host, nullptr);
+}
+
+int yh_op_instance_track_batch(yh_engine* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                               int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height,
+                               const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age, const int32_t* streams,
+                               uint32_t* out_host) {
+    const InstTrackBatch trk = { { iou_permille, max_age }, streams };
+    return op_instance_batch_impl(h, masks, class_ids, scores, counts, n_frames, n_dets, hp, wp, width, height, class_map, min_score,
+                                  out_host, &trk);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // single call's kernel runs (instance_dev.h) - there is no second definition of anything. One upload of the class map, one read-back
 // of n x 1 KB of values and counts (and of the frames, if the caller wants them on the host), one wait. The buffers are the
 // batch's own: a batch neither reads nor writes what yh_instance_frame, yh_instance_track and their readers use, and those calls
-// leave the batch alone. Tracking is not batched: a tracker follows one stream through time (instance_track.hip).
+// leave the batch alone. A tracked batch (yh_instance_track_batch, instance_track_batch.hip) is this call with the trackers' rounds
+// between the two launches: each frame is matched against the tracker of its camera stream, frames of one stream in batch order.
 #include <string.h>
 
 #include "engine.h"
@@ -37,12 +38,15 @@ __global__ void __launch_bounds__(kInstPaintX * kInstPaintY) inst_batch_paint(co
 
 namespace yh {
 
-int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,
-                       int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host) {
+// One call: inst_batch_pack, for a tracked batch the trackers' rounds (instance_track_batch.hip: inst_track_match rewrites the values
+// inst_batch_paint reads), inst_batch_paint, then the one wait behind the read-back of the tables (and of the slots).
+static int run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,
+               int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrackBatch* trk) {
     const int ncls = h->C - 1, px = hp * wp;
     const size_t npx = (size_t)width * height, meta_words = (size_t)n * 2 * kInstRanks;
     int rc;
     h->instb_n = -1;   // (until this batch is complete there is none: the buffers below may move)
+    h->trkb_n = -1;
     if ((rc = instance_grow(h, (void**)&h->instb_bits, &h->instb_bits_cap, (size_t)n * px * 16))) return rc;
     if ((rc = instance_grow(h, (void**)&h->instb_frames, &h->instb_frames_cap, (size_t)n * npx * 4))) return rc;
     if ((rc = instance_grow(h, (void**)&h->instb_meta, &h->instb_meta_cap, meta_words * 4))) return rc;
@@ -53,17 +57,27 @@ int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* d
     const dim3 gp((unsigned)((px + 4 * kInstPackLanes - 1) / (4 * kInstPackLanes)), kInstRanks / 32, (unsigned)n);
     hipLaunchKernelGGL(inst_batch_pack, gp, dim3(kInstPackLanes), 0, h->stream, masks, dets, count, max_n, px, (const uint8_t*)h->instb_cmap,
                        ncls, min_score, (uint32_t*)h->instb_bits, h->instb_meta);
+    if (trk && (rc = track_batch_enqueue(h, n, hp, wp, *trk))) return rc;
     const dim3 gq((unsigned)((width + kInstPaintX - 1) / kInstPaintX), (unsigned)((height + kInstPaintY - 1) / kInstPaintY), (unsigned)n);
     hipLaunchKernelGGL(inst_batch_paint, gq, dim3(kInstPaintX, kInstPaintY), 0, h->stream, (const uint4*)h->instb_bits, hp, wp, width, height,
                        h->instb_meta, h->instb_frames);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(h->instb_meta_host.data(), h->instb_meta, meta_words * 4, hipMemcpyDeviceToHost, h->stream));
+    if (trk && (rc = track_batch_readback(h, n))) return rc;
     if (out_host) HIPCHK(h, hipMemcpyAsync(out_host, h->instb_frames, (size_t)n * npx * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->instb_tables.resize((size_t)n);
     for (int b = 0; b < n; ++b) instance_table(h->instb_meta_host.data() + (size_t)b * 2 * kInstRanks, h->instb_tables[b]);
+    if (trk) track_batch_finish(h, n, *trk);
     h->instb_n = n;
     return YH_OK;
+}
+
+int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,
+                       int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrackBatch* trk) {
+    const int rc = run(h, masks, dets, count, max_n, n, hp, wp, width, height, class_map, min_score, out_host, trk);
+    if (rc != YH_OK && trk) track_batch_drop(h, n, *trk);   // a tracked batch that failed leaves no batch and empties every tracker it named
+    return rc;
 }
 
 void instance_batch_free(yh_engine* h) {

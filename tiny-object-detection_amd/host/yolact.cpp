@@ -132,9 +132,34 @@ std::vector<std::int32_t> Yolact::tracks() {
     return table;
 }
 
-void Yolact::track_reset() {
+void Yolact::track_reset(int stream) {
     if (!engine_) expect_failed("track_reset", "the detection tail belongs to the YOLACT engine");
-    if (yh_instance_track_reset(engine_) != YH_OK) expect_failed("track reset failed", yh_last_error(engine_));
+    if (yh_instance_track_reset_stream(engine_, stream) != YH_OK) expect_failed("track reset failed", yh_last_error(engine_));
+}
+
+std::vector<std::vector<std::int32_t>> Yolact::instance_track_batch(int first, int n, int width, int height, const std::uint8_t* class_map,
+                                                                    float min_score, int iou_permille, int max_age,
+                                                                    const std::int32_t* streams, std::uint32_t* frames_out) {
+    if (!engine_) expect_failed("instance_track_batch", "the detection tail belongs to the YOLACT engine");
+    if (yh_instance_track_batch(engine_, first, n, width, height, class_map, min_score, iou_permille, max_age, streams, frames_out) != YH_OK)
+        expect_failed("instance track batch failed", yh_last_error(engine_));
+    std::vector<std::vector<std::int32_t>> tables(static_cast<std::size_t>(n));
+    for (int b = 0; b < n; ++b) {
+        std::int32_t m = 0;
+        if (yh_instance_batch_read(engine_, b, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+        tables[b].resize(static_cast<std::size_t>(m) * 4);
+        if (yh_instance_batch_read(engine_, b, &m, tables[b].data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    }
+    return tables;
+}
+
+std::vector<std::int32_t> Yolact::tracks_of(int b) {
+    if (!engine_) expect_failed("tracks_of", "the detection tail belongs to the YOLACT engine");
+    std::int32_t m = 0;
+    if (yh_instance_track_batch_read(engine_, b, &m, nullptr, 0) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    std::vector<std::int32_t> table(static_cast<std::size_t>(m) * 6);
+    if (yh_instance_track_batch_read(engine_, b, &m, table.data(), m) != YH_OK) expect_failed("must data", yh_last_error(engine_));
+    return table;
 }
 
 // ---- YolactGroup ---------------------------------------------------------------------------------------------------

@@ -71,7 +71,17 @@ public:
                                              float min_score = 0.0f, int iou_permille = 300, int max_age = 2,
                                              std::uint32_t* frame_out = nullptr);
     std::vector<std::int32_t> tracks();
-    void track_reset();
+    // stream: a tracker of the engine's bank (0: instance_track's), -1: all of them (yh_instance_track_reset_stream)
+    void track_reset(int stream = 0);
+    // instance_batch with ids that persist (yh_instance_track_batch): frame b is what instance_track(first + b, ..) gives on the
+    // tracker of streams[b] (nullptr: all on stream 0), the calls made in batch order, with one wait. Returns the n instance tables;
+    // the frames are instance_batch_device_frames(). tracks_of(b): the tracker of frame b's stream right after frame b.
+    std::vector<std::vector<std::int32_t>> instance_track_batch(int first, int n, int width, int height,
+                                                                const std::uint8_t* class_map = nullptr, float min_score = 0.0f,
+                                                                int iou_permille = 300, int max_age = 2,
+                                                                const std::int32_t* streams = nullptr,
+                                                                std::uint32_t* frames_out = nullptr);
+    std::vector<std::int32_t> tracks_of(int b);
 
     static std::string version();      // edgetpu::version(), scene.rs:62
 

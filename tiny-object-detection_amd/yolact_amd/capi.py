@@ -191,6 +191,9 @@ SYMBOLS = [
     ("yh_instance_track", _i, [_vp, _i, _i, _i, _vp, _f, _i, _i, _vp]),
     ("yh_instance_tracks_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
     ("yh_instance_track_reset", _i, [_vp]),
+    ("yh_instance_track_batch", _i, [_vp, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp]),
+    ("yh_instance_track_batch_read", _i, [_vp, _i, C.POINTER(_i), _vp, _i]),
+    ("yh_instance_track_reset_stream", _i, [_vp, _i]),
     ("yh_debug_read_tensor", _i, [_vp, C.c_char_p, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_frame", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_read_tensor_e4m3", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
@@ -218,6 +221,7 @@ SYMBOLS = [
     ("yh_op_instance_frame", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_op_instance_track", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_op_instance_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
+    ("yh_op_instance_track_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp]),
 ]
 
 
@@ -588,9 +592,9 @@ class Engine:
         self._chk(self.L.yh_instance_tracks_read(self.h, C.byref(n), _p(t), n.value))
         return t
 
-    def track_reset(self):
-        """yh_instance_track_reset: an empty tracker."""
-        self._chk(self.L.yh_instance_track_reset(self.h))
+    def track_reset(self, stream=0):
+        """yh_instance_track_reset_stream: an empty tracker for one stream of the bank (0: instance_track's), None: for all."""
+        self._chk(self.L.yh_instance_track_reset_stream(self.h, -1 if stream is None else int(stream)))
 
     def op_instance_track(self, masks, class_ids, scores, width, height, class_map=None, min_score=0.0, min_iou=0.3, max_age=2):
         """yh_op_instance_track: a tracked call on caller-provided masks uint8 [n][hp][wp], class ids and scores in rank order;
@@ -607,6 +611,56 @@ class Engine:
                                               _p(cm) if cm is not None else None, C.c_float(min_score), self._permille(min_iou),
                                               int(max_age), _p(out), _p(table), len(table), C.byref(m)))
         return out, table[:m.value].copy()
+
+    # ---- instance track batch (DESIGN.md §11 "Instance track batch")
+    @staticmethod
+    def _streams(streams, n):
+        if streams is None:
+            return None
+        st = np.ascontiguousarray(streams, np.int32)
+        assert st.shape == (n,), "streams: one value per frame"
+        return st
+
+    def instance_track_batch(self, first, n, width, height, class_map=None, min_score=0.0, min_iou=0.3, max_age=2, streams=None,
+                             read=True):
+        """yh_instance_track_batch: frames first .. first + n - 1 of the last evaluate tracked with one wait; frame b is what
+        instance_track(first + b, ...) gives on the tracker of streams[b] (None: all on stream 0, instance_track's), the calls made
+        in batch order. A tracked batch is an instance batch: returns uint32 [n][height][width], or None with read=False
+        (instance_batch_device_frames; the tables: instances_of; the trackers: tracks_of)."""
+        cm = self._class_map(class_map)
+        st = self._streams(streams, n)
+        out = np.zeros((max(n, 0), height, width), np.uint32) if read else None
+        self._chk(self.L.yh_instance_track_batch(self.h, first, n, width, height, _p(cm) if cm is not None else None,
+                                                 C.c_float(min_score), self._permille(min_iou), int(max_age),
+                                                 _p(st) if st is not None else None, _p(out) if read else None))
+        return out
+
+    def tracks_of(self, b):
+        """The tracker of frame b's stream right after frame b of the last tracked batch: int32 [m][6] = (slot, output class, id,
+        age, area, rank or -1)."""
+        n = C.c_int32()
+        self._chk(self.L.yh_instance_track_batch_read(self.h, b, C.byref(n), None, 0))
+        t = np.zeros((n.value, 6), np.int32)
+        self._chk(self.L.yh_instance_track_batch_read(self.h, b, C.byref(n), _p(t), n.value))
+        return t
+
+    def op_instance_track_batch(self, masks, class_ids, scores, counts, width, height, class_map=None, min_score=0.0, min_iou=0.3,
+                                max_age=2, streams=None):
+        """yh_op_instance_track_batch: a tracked batch on caller-provided masks uint8 [n_frames][n_dets][hp][wp], class ids and scores
+        [n_frames][n_dets] in rank order per frame, counts [n_frames], against the handle's bank of trackers. Returns (frames uint32
+        [n_frames][height][width], the list of the frames' instance tables, the list of their track tables)."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        nf, nd, hp, wp = masks.shape
+        ids = np.ascontiguousarray(class_ids, np.int32).reshape(nf, nd)
+        sc = np.ascontiguousarray(scores, np.float32).reshape(nf, nd)
+        cnt = np.ascontiguousarray(counts, np.int32).reshape(nf)
+        cm = self._class_map(class_map)
+        st = self._streams(streams, nf)
+        out = np.zeros((nf, height, width), np.uint32)
+        self._chk(self.L.yh_op_instance_track_batch(self.h, _p(masks), _p(ids), _p(sc), _p(cnt), nf, nd, hp, wp, width, height,
+                                                    _p(cm) if cm is not None else None, C.c_float(min_score), self._permille(min_iou),
+                                                    int(max_age), _p(st) if st is not None else None, _p(out)))
+        return out, [self.instances_of(b) for b in range(nf)], [self.tracks_of(b) for b in range(nf)]
 
     # ---- reference-compat path
     def classify_device_frame(self):
