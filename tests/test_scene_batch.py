@@ -340,3 +340,47 @@ def test_a_batch_of_eight_beats_eight_single_frames(built):
     print(f"append + plan of {n} frames: batch {mb:.3f} ms, {n} singles {ms:.3f} ms, ratio {mb / ms:.3f}")
     assert mb < ms
     sb.close(); sc.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["plan4", "plan8", "turn", "turn_tour"])
+def test_a_scene_is_the_batch_of_one(built, kind):
+    """One driver plans for both handles, so a Scene and a SceneBatch of one frame given the same fields return the same arrays AND
+    the same solver counters - the same numbers, not merely within SP_BATCH of each other. 40 x 36: 2 x 2 tiles of 32 x 32, ragged on
+    both axes; one target on the corner pixel of tile (0, 0), the other across both borders in tile (1, 1). Each kind stays pinned to
+    its restatement (path_ref, path8_ref through path_ref's conn = 8, turn_ref, turn_tour_ref). (The counters are those of two runs
+    of the asynchronous solver: should they ever differ by a round, the cause is the border race DESIGN.md §11 "Scene batch"
+    describes, not the driver.)"""
+    import yolact_amd as ya
+    from test_scene_batch_turn import _check_turn
+    from test_scene_path8 import _check_plan, _random_fields
+    from test_scene_turn_tour import _check
+    W, H, tau = 40, 36, 2.0
+    f = _random_fields(np.random.default_rng(4036), H, W)
+    targets, start, heading = [(31, 31), (32, 33)], (2, 34), 6
+    sc, sb = ya.Scene(W, H), ya.SceneBatch(W, H, 1)
+    sc.set_fields(*f)
+    sb.set_fields(0, *f)
+    if kind in ("plan4", "plan8"):
+        conn = int(kind[-1])
+        sc.plan(targets=targets, start=start, connectivity=conn)
+        assert sb.plan(targets=[targets], starts=[start], connectivity=conn) == [ya.capi.OK]
+        one, got, t_one, t_got = sc.read_plan(), sb.read_plan(0), sc.plan_time(1), sb.plan_time(1)
+        _check_plan(got, f, targets, start, conn=conn)
+    elif kind == "turn":
+        sc.plan_turn(targets=targets, start=start, heading=heading, turn_price=tau)
+        assert sb.plan_turn(targets=[targets], starts=[start], headings=[heading], turn_price=tau) == [ya.capi.OK]
+        one, got, t_one, t_got = sc.read_turn(), sb.read_turn(0), sc.turn_time(1), sb.turn_time(1)
+        _check_turn(got, f, targets, start, heading, tau)
+    else:
+        sc.plan_turn_tour(targets=targets, start=start, heading=heading, turn_price=tau)
+        assert sb.plan_turn_tour(targets=[targets], starts=[start], headings=[heading], turn_price=tau) == [ya.capi.OK]
+        one, got, t_one, t_got = sc.read_turn_tour(), sb.read_turn_tour(0), sc.turn_tour_time(1), sb.turn_tour_time(1)
+        _check(got, f, targets, start, heading, tau)
+    assert one.keys() == got.keys()
+    for k in one:
+        a, b = np.asarray(one[k]), np.asarray(got[k])
+        assert a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b)), k
+    print(f"{kind}: scene {t_one}, batch of one {t_got}")
+    assert t_one["rounds"] == t_got["rounds"] and t_one["tile_runs"] == t_got["tile_runs"]
+    sb.close(); sc.close()

@@ -1,25 +1,29 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
 // scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_turn_tour.hip (the turn-aware tour),
-// scene_solve.hip (the field solver they run on)
-// and scene_batch.hip / scene_batch_turn.hip / scene_batch_turn_tour.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle holds one of these as its
-// core, the arrays those of N frames).
+// scene_solve.hip (the field solver they run on) and scene_batch.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle
+// holds one of these as its core, the arrays those of N frames). The three planners that exist for both handles (plan, turn plan,
+// turn tour) have ONE driver each, over max_frames frames: a yh_scene is the batch of one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "yh_internal.h"
 
-struct yh_scene_path;   // the planner's fields, route and last plan (scene_path.hip); allocated at the first yh_scene_plan
+struct yh_scene_path;   // the planner's fields, routes and last plan, frame-major (scene_path.hip); allocated at the first plan
 struct yh_scene_tour;   // the tour's fields, route and last tour (scene_tour.hip); allocated at the first yh_scene_plan_tour
-struct yh_scene_turn;   // the turn-aware planner's fields, route and last turn plan (scene_turn.hip); allocated at the first yh_scene_plan_turn
-struct yh_scene_turn_tour;   // the turn-aware tour's fields, leg table and route (scene_turn_tour.hip); allocated at the first yh_scene_plan_turn_tour
+struct yh_scene_turn;   // the turn-aware planner's fields, routes and last turn plan, frame-major (scene_turn.hip); allocated at the first turn plan
+struct yh_scene_turn_tour;   // the turn-aware tour's fields, leg tables and routes, frame-major (scene_turn_tour.hip); allocated at the first turn tour
+struct yh_scene_batch;  // scene_batch.h
 struct yh_scene_solve;  // the solver's buffers, one set for both (scene_path_dev.h, scene_solve.hip); allocated at the first of either
 
 struct yh_scene {
     int dev = 0, W = 0, H = 0, band_h = 64;
+    int max_frames = 1;    // frames the arrays below (and the planners') hold one after the other: 1, or what yh_scene_batch_create was given
+    bool batch = false;    // the core of a yh_scene_batch: the planners' error texts name the frame
     hipStream_t stream = nullptr;
     hipEvent_t copied = nullptr;
     std::string err;
@@ -46,6 +50,7 @@ struct yh_scene {
     yh_scene_turn_tour* turn_tour = nullptr;
     yh_scene_solve* solve = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
+    std::string frame_tag(int b) const { return batch ? "frame " + std::to_string(b) + ": " : std::string(); }
 };
 
 #define SCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (h)->fail(YH_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
@@ -66,6 +71,17 @@ int scene_check_fields(yh_scene* h, const float* conn0, const float* conn1, bool
 // scene.hip: waits until host sources a, b (either may be null) of copies enqueued on the stream may be reused; the bump tables of a handle
 int host_sources_done(yh_scene* h, const void* a, const void* b);
 hipError_t scene_tables_build(yh_scene* h);
-// what an 8-connected plan or tour asks of the last frame's diagonal lengths (YH_ESTATE and why if they fail it); touches nothing
-int scene_plan_diagonals(yh_scene* h);
+// what an 8-connected plan or tour asks of a frame's diagonal lengths (YH_ESTATE and why if they fail it: ok and why are the
+// scene's diag_ok / diag_why, or those of a batch's frame); touches nothing
+int scene_plan_diagonals(yh_scene* h, bool ok, const std::string& why);
+// the turn planners' checks of their own arguments, one text each for all four turn entry points; touch nothing
+int scene_turn_heading(yh_scene* h, int32_t heading);
+int scene_turn_price(yh_scene* h, float turn_price);
+int scene_turn_size(yh_scene* h);
+// What the three batched plans do before they touch anything (scene_batch.hip): every check of every frame (headings, if given,
+// are the turn planners': their size guard and every frame's diagonals are checked too; otherwise the diagonals only for
+// connectivity 8), one read-back of the balls, the choice of targets per frame - each(b, targets) takes frame b's and may refuse them -
+// and st[b] = YH_ESTATE for a frame without a usable ball (each is not called for it). A refusal names its frame.
+int scene_batch_frames(yh_scene_batch* hb, const int32_t* targets_xy, int32_t n_targets, const int32_t* starts_xy, const int32_t* headings, int connectivity,
+                       std::vector<int32_t>& st, const std::function<int(int, const std::vector<int32_t>&)>& each);
 }

@@ -1,7 +1,8 @@
-// scene_path_dev.h — what scene_path.hip (one multi-source field, yh_scene_plan) and scene_tour.hip (K single-target fields,
-// yh_scene_plan_tour) share: the field solver of scene_solve.hip, declared here, and the planner's device code - the tile relaxation, the
-// successor rule and the windowed chase. scene_turn.hip (the turn-aware plan, yh_scene_plan_turn) runs its own round kernel through the
-// same host loop (SolveRound) and takes its edge terms through around<8>. What they compute and why it is unique is said at the head of scene_path.hip.
+// scene_path_dev.h — what scene_path.hip (one multi-source field per frame, yh_scene_plan and yh_scene_batch_plan) and scene_tour.hip
+// (K single-target fields, yh_scene_plan_tour) share: the field solver of scene_solve.hip, declared here, what the frame-major planner
+// states have in common, and the planner's device code - the tile relaxation, the successor rule and the windowed chase. scene_turn.hip
+// and scene_turn_tour.hip (the turn-aware plan and tour) run their own round kernel through the same host loop (SolveRound) and take
+// their edge terms through around<8>. What they compute and why it is unique is said at the head of scene_path.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,11 +34,11 @@ struct yh_scene;
 // ---- host side (this struct and the solve_* declarations below). The solver's state (yh_scene::solve, scene_solve.hip): allocated at
 // the first plan or tour of a handle, shared by both kinds and both connectivities - every run recomputes the edge terms.
 struct yh_scene_solve {
-    float4* edge = nullptr;      // [H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
-    float4* edge2 = nullptr;     // [H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected run
+    float4* edge = nullptr;      // [max_frames][H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
+    float4* edge2 = nullptr;     // [max_frames][H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected run
     uint32_t* flags = nullptr;   // [2][F][ntiles], by round parity; sized for cap_f fields, grows only
     uint32_t* cnt = nullptr;     // [kSolveCnt] counters, then kSolveTail words for the caller's after-batch kernel
-    uint32_t* host = nullptr;    // pinned: the cnt block as read back, then kSolveWalk words for the caller's walk results
+    uint32_t* host = nullptr;    // pinned: the cnt block as read back, then kSolveWalk words for the plain tour's walk results (scene_tour.hip)
     std::vector<uint32_t> flags0;   // [2][F][ntiles]: round 0's tile flags, built on the host, and the zeroes of the other parity
     int cap_f = 0, tx = 0, ty = 0;
     long long rounds = 0, tile_runs = 0;   // of the last run
@@ -71,13 +72,33 @@ struct SolveCopy { void* dst; const void* src; size_t bytes; };   // a device ar
 // the grid of tiles with the flags of that parity; states: the states per pixel, which scale the round cap
 struct SolveRound { std::function<void(const dim3&, int, uint32_t*)> launch; int states; };
 
-// Allocates what F fields of connectivity conn need, fills p (but cost and next: the caller's), enqueues path_weights (once for all fields)
-int solve_begin(yh_scene* h, int conn, int F, PathParams& p);
-// solve_begin without the launch, for a handle whose scene fields and edge terms are those of `frames` frames one after the other (a
-// handle always asks for the same number): the caller enqueues its own path_weights over them (scene_batch.hip)
-int solve_alloc(yh_scene* h, int conn, int F, int frames, PathParams& p);
+// The per-call inputs of a frame-major planner state - seeds [ns][2] (pixel, field), then starts [n], then headings [n] or the
+// turn tour's points and legs - as one pinned block the host fills and its device copy: they go up in ONE copy, and the kernels
+// take pointers into dev. Both grow only. reserve waits for the stream before it frees a block that is too small.
+struct PlanInputs { int32_t *host = nullptr, *dev = nullptr; size_t cap = 0; };
+int plan_inputs_reserve(yh_scene* h, PlanInputs& in, size_t words);
+void plan_inputs_free(PlanInputs& in);
+// What the three frame-major planner states (plan, turn plan, turn tour) have in common: the routes, the inputs of the last call
+// (the replay of *_time runs exactly these) and its per-frame results. A yh_scene holds one frame, a yh_scene_batch's core max_frames.
+struct PlanFrames {
+    int2* nodes = nullptr;         // [max][route_stride] the routes
+    float2* dirs = nullptr;
+    int32_t* walk_out = nullptr;   // per frame: length, status (the turn tour: 4 * YH_TOUR_MAX words)
+    PlanInputs in;
+    SolveLast last;                // planned, frame generation, connectivity
+    int n = 0;                     // frames of the last call
+    std::vector<int32_t> status, path_len, last_seeds, last_field;   // per frame; per seed: its pixel and its solver field
+};
+// in.host filled with the seed pairs of q; returns the words they take (the caller appends the rest and uploads)
+size_t plan_inputs_seeds(PlanFrames& q);
+// Frame `frame`'s part of q's last call, as the read code takes it: YH_ESTATE ("it has no <what>") if that frame had no ball
+int solve_frame(yh_scene* h, const PlanFrames* q, int frame, size_t route_stride, const char* what, SolveLast& one);
+
+// Allocates what F fields of connectivity conn need on a handle of h->max_frames frames, fills p (but cost and next: the caller's),
+// enqueues path_weights over the first n frames (once for all fields of a frame)
+int solve_begin(yh_scene* h, int conn, int F, int n, PathParams& p);
 // Relaxes the F fields at p.cost, which the caller has filled (+inf, 0 at the seeds), to their fixed points. seeds: the pixels that
-// start at 0, equally many per field, field by field. who: "path" or "tour", for the error text. after(tail), if given, enqueues
+// start at 0, equally many per field, field by field. who: the kind of run ("path", "tour", "batch turn", ..), for the error text. after(tail), if given, enqueues
 // the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) arrives in host[kSolveCnt ..] with the counters.
 // own, if given, is the round kernel in place of field_round<conn> (round 0's flags still follow conn). field_of, if given, is the
 // ragged form: seed k belongs to field (*field_of)[k], any number per field - a field without a seed flags nothing and its tiles exit at once.
@@ -85,9 +106,10 @@ int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::v
                  const std::function<void(uint32_t*)>& after = nullptr, const SolveRound* own = nullptr, const std::vector<int32_t>* field_of = nullptr);
 // run() reps times between two events; a failing run's code is returned as it is. kind, again: for the error texts ("plan", "plan again")
 int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast* q, int reps, const std::function<int()>& run, float* ms, int32_t* rounds, int32_t* tile_runs);
-// The checks of the read entry points (a run of this frame exists, the capacity holds the route), then the copies
+// The checks of the read entry points (a run of this frame exists, the capacity holds the route - also asked for if per_node, an array
+// among `fields` that is as long as the route), then the copies
 int solve_read(yh_scene* h, const char* kind, const char* again, const SolveLast* q, std::initializer_list<SolveCopy> fields, int32_t* path_xy, float* directions,
-               int32_t path_capacity, int32_t* path_len);
+               int32_t path_capacity, int32_t* path_len, bool per_node = false);
 
 // Round 0's tiles for a target at (x, y), through flag(tile x, tile y) (which ignores tiles outside the grid): its own tile, the tile
 // across every tile border it lies on and, with diagonals, the tile diagonally across a tile corner it lies on.
@@ -100,6 +122,24 @@ inline void round0_flags(int x, int y, int conn, F&& flag) {
     if (sy) flag(bx, by + sy);
     if (conn == 8 && sx && sy) flag(bx + sx, by + sy);
 }
+
+// Frame b of a frame-major batch (b = blockIdx.z; a yh_scene has the one frame 0): the scene's fields and the edge terms advance
+// by W H, cost by cost_stride: W H for the plain plan, 8 W H for the turn plan, Kmax 8 W H for the turn tour, 0 where there is no
+// cost yet (path_weights). next is the plain plan's alone: its kernels advance it themselves (scene_path.hip).
+__device__ __forceinline__ PathParams frame_of(const PathParams& p, int b, size_t cost_stride) {
+    PathParams q = p;
+    const size_t npx = (size_t)p.W * p.H;
+    q.map += b * npx; q.conn0 += b * npx; q.conn1 += b * npx; q.edge += b * npx; q.cost += b * cost_stride;
+    if (q.edge2) q.edge2 += b * npx;   // (8-connected runs only)
+    return q;
+}
+
+// Before the body of a one-wave walk kernel (turn_walk, tt_walk): the code that follows starts on a 64-byte instruction cache line,
+// whatever the kernel's entry sequence was. One wave steps through a route for tens of milliseconds in a maze, and how its loops lie
+// in the instruction cache shows: with the same instructions, the longer entry of the frame-major kernels (the frame advance) made
+// turn_walk 3.5 % and tt_walk 8 % slower than the parent commit's one-frame forms; started on a cache line they run as those did
+// ("One driver per kind"; tt_arrive ran 5 % slower with it than without and is left where it falls).
+#define SP_BODY_ON_CACHE_LINE() asm volatile(".p2align 6")
 
 __device__ __forceinline__ float cand(float dn, float len, float dh) { return __fadd_rn(__fadd_rn(dn, len), dh); }
 
@@ -285,7 +325,7 @@ __device__ __forceinline__ int successor(const Around<CONN>& e, const float* cos
     return nx;
 }
 
-// next[] of pixel blockIdx.x * 256 + threadIdx.x (scene_path.hip: path_next)
+// next[] of pixel blockIdx.x * 256 + threadIdx.x (scene_path.hip: plan_next)
 template <int CONN>
 __device__ __forceinline__ void next_body(const PathParams& p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -356,7 +396,7 @@ __device__ __forceinline__ void weights_body(const PathParams& p) {
     }
 }
 
-// One wave (scene_path.hip: path_walk): the route from `start` and its directions.
+// One wave (scene_path.hip: plan_walk): the route from `start` and its directions.
 // out[0] = nodes on the route (start and target included), out[1] = 0, or 1 if the walk did not end within W * H nodes (costs
 // strictly decrease along `next`, so this cannot happen on SANE fields; the bound is what keeps the loop finite on any input)
 __device__ __forceinline__ void walk_body(const PathParams& p, int start, int2* nodes, float2* dirs, int32_t* out) {

@@ -1,11 +1,12 @@
-// scene_solve.hip — the field solver behind yh_scene_plan (scene_path.hip: one field, n targets) and yh_scene_plan_tour
-// (scene_tour.hip: K fields, one target each): the edge terms, the rounds of tile relaxation to the fixed point of DESIGN.md §11
-// "Path planner", and what the two kinds' time and read entry points have in common. Its state hangs off the scene handle
-// (yh_scene::solve, scene_path_dev.h): one set of buffers for both kinds and both connectivities.
-//   path_weights   one lane per pixel: conn0 / conn1 / map -> one float4 per pixel (right length, right height step, down length,
-//                  down height step; <8>: a second one for down-right and down-left): the solver reads 16 B per pixel instead of
-//                  32 B of connections + the map, length and step stay apart for the two roundings.
-//   field_round    x rounds, grid (tiles x, tiles y, F): relax_tile (scene_path_dev.h) on field z with field z's flags: a flagged
+// scene_solve.hip — the field solver behind every planner (scene_path.hip: one field per frame, n targets; scene_tour.hip: K fields,
+// one target each; scene_turn.hip and scene_turn_tour.hip with their own round kernel): the edge terms, the rounds of tile relaxation
+// to the fixed point of DESIGN.md §11 "Path planner", and what the kinds' time and read entry points and their frame-major states
+// have in common. Its state hangs off the scene handle (yh_scene::solve, scene_path_dev.h): one set of buffers for all kinds and
+// both connectivities, the edge terms those of the handle's max_frames frames.
+//   path_weights   one lane per pixel, the frame from blockIdx.z: conn0 / conn1 / map -> one float4 per pixel (right length, right
+//                  height step, down length, down height step; <8>: a second one for down-right and down-left): the solver reads
+//                  16 B per pixel instead of 32 B of connections + the map, length and step stay apart for the two roundings.
+//   field_round    (the plain tour's; the plans' round kernels are their units') x rounds, grid (tiles x, tiles y, F): relax_tile (scene_path_dev.h) on field z with field z's flags: a flagged
 //                  tile relaxes in LDS to its local fixed point for the halo it loaded, and cells that changed go back with atomicMin
 //                  on the u32 view (non-negative f32 order as their bits). Only a tile whose halo may have changed runs: a tile that
 //                  lowered a cell of its border flags that neighbour for the NEXT round (two flag arrays, by round parity) and
@@ -27,7 +28,7 @@ using namespace yh;
 namespace {
 
 template <int CONN>
-__global__ __launch_bounds__(256) void path_weights(const PathParams p) { weights_body<CONN>(p); }
+__global__ __launch_bounds__(256) void path_weights(const PathParams p) { weights_body<CONN>(frame_of(p, blockIdx.z, 0)); }
 
 template <int CONN>
 __global__ __launch_bounds__(SP_NT) void field_round(const PathParams p, int F, int parity, uint32_t* cnt_next) {
@@ -45,10 +46,10 @@ int last_ok(yh_scene* h, const char* kind, const char* again, const SolveLast* q
 
 namespace yh {
 
-int solve_alloc(yh_scene* h, int conn, int F, int frames, PathParams& p) {
+int solve_begin(yh_scene* h, int conn, int F, int n, PathParams& p) {
     if (!h->solve) h->solve = new yh_scene_solve();
     yh_scene_solve* s = h->solve;
-    const size_t npx = (size_t)h->W * h->H;
+    const size_t npx = (size_t)h->W * h->H, frames = (size_t)h->max_frames;
     s->tx = (h->W + SP_TW - 1) / SP_TW; s->ty = (h->H + SP_TH - 1) / SP_TH;
     if (!s->edge) SCHK(h, hipMalloc((void**)&s->edge, frames * npx * 16));
     if (conn == 8 && !s->edge2) SCHK(h, hipMalloc((void**)&s->edge2, frames * npx * 16));
@@ -61,13 +62,37 @@ int solve_alloc(yh_scene* h, int conn, int F, int frames, PathParams& p) {
     }
     p.W = h->W; p.H = h->H; p.tx = s->tx; p.ntiles = s->tx * s->ty;
     p.map = h->map; p.conn0 = h->conn0; p.conn1 = h->conn1; p.edge = s->edge; p.edge2 = conn == 8 ? s->edge2 : nullptr; p.flags = s->flags;
+    p.cost = nullptr; p.next = nullptr;
+    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)((npx + 255) / 256), 1, (unsigned)n), dim3(256), 0, h->stream, p);
     return YH_OK;
 }
 
-int solve_begin(yh_scene* h, int conn, int F, PathParams& p) {
-    const int rc = solve_alloc(h, conn, F, 1, p);
-    if (rc) return rc;
-    hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)(((size_t)h->W * h->H + 255) / 256)), dim3(256), 0, h->stream, p);
+int plan_inputs_reserve(yh_scene* h, PlanInputs& in, size_t words) {
+    if (words <= in.cap) return YH_OK;
+    if (in.cap) SCHK(h, hipStreamSynchronize(h->stream));
+    plan_inputs_free(in);
+    SCHK(h, hipHostMalloc((void**)&in.host, words * 4, hipHostMallocDefault));
+    SCHK(h, hipMalloc((void**)&in.dev, words * 4));
+    in.cap = words;
+    return YH_OK;
+}
+
+void plan_inputs_free(PlanInputs& in) {
+    if (in.host) (void)hipHostFree(in.host);
+    if (in.dev) (void)hipFree(in.dev);
+    in = PlanInputs();
+}
+
+size_t plan_inputs_seeds(PlanFrames& q) {
+    for (size_t k = 0; k < q.last_seeds.size(); ++k) { q.in.host[2 * k] = q.last_seeds[k]; q.in.host[2 * k + 1] = q.last_field[k]; }
+    return 2 * q.last_seeds.size();
+}
+
+int solve_frame(yh_scene* h, const PlanFrames* q, int frame, size_t route_stride, const char* what, SolveLast& one) {
+    one = q ? q->last : SolveLast();
+    if (!one.planned || one.frame != h->frames) return YH_OK;   // (solve_read says which)
+    if (q->status[frame] != YH_OK) return h->fail(YH_ESTATE, "frame " + std::to_string(frame) + " had no ball inside it: it has no " + what);
+    one.path_len = q->path_len[frame]; one.nodes = q->nodes + frame * route_stride; one.dirs = q->dirs + frame * route_stride;
     return YH_OK;
 }
 
@@ -128,11 +153,11 @@ int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast
 }
 
 int solve_read(yh_scene* h, const char* kind, const char* again, const SolveLast* q, std::initializer_list<SolveCopy> fields, int32_t* path_xy, float* directions,
-               int32_t path_capacity, int32_t* path_len) {
+               int32_t path_capacity, int32_t* path_len, bool per_node) {
     const int rc = last_ok(h, kind, again, q);
     if (rc) return rc;
     if (path_len) *path_len = q->path_len;
-    if ((path_xy || directions) && path_capacity < q->path_len)
+    if ((path_xy || directions || per_node) && path_capacity < q->path_len)
         return h->fail(YH_EOVERFLOW, "path_capacity " + std::to_string(path_capacity) + " < the route's " + std::to_string(q->path_len) + " nodes");
     SCHK(h, hipSetDevice(h->dev));
     for (const SolveCopy& c : fields) if (c.dst) SCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));

@@ -171,7 +171,7 @@ int run_tour(yh_scene* h, const std::vector<int32_t>& targets, int32_t start, in
     pts.K = K; pts.start = start;
     for (int b = 0; b < YH_TOUR_MAX; ++b) pts.t[b] = b < K ? targets[b] : -1;
     PathParams p;
-    int rc = solve_begin(h, conn, K, p);
+    int rc = solve_begin(h, conn, K, 1, p);
     if (rc) return rc;
     p.cost = q->cost; p.next = q->next;
     hipLaunchKernelGGL(tour_fill, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, p, pts);
@@ -235,7 +235,7 @@ int yh_scene_plan_tour_conn(yh_scene* h, const int32_t* targets_xy, int32_t n_ta
         // (a ball on an earlier ball's pixel is dropped)
         if (targets_xy) return h->fail(YH_EINVAL, "duplicate target (" + std::to_string(t % h->W) + ", " + std::to_string(t / h->W) + "): a tour's targets are distinct pixels");
     }
-    if (connectivity == 8 && (rc = scene_plan_diagonals(h))) return rc;
+    if (connectivity == 8 && (rc = scene_plan_diagonals(h, h->diag_ok, h->diag_why))) return rc;
     if (!h->tour) h->tour = new yh_scene_tour();   // the tour's buffers are allocated at the first tour: a handle that never tours pays nothing
     rc = ensure_buffers(h, (int)targets.size());
     if (rc) { scene_tour_free(h); return rc; }

@@ -1,6 +1,6 @@
-// scene_turn_dev.h — the turn-aware planner's device code (DESIGN.md §11 "Turns"), shared by scene_turn.hip (yh_scene_plan_turn: one
-// frame), scene_batch_turn.hip (yh_scene_batch_plan_turn: N frames per launch, the frame from blockIdx.z) and scene_turn_tour.hip
-// (yh_scene_plan_turn_tour: one field per target, the field from blockIdx.z): the compass, the round over a tile of all eight layers,
+// scene_turn_dev.h — the turn-aware planner's device code (DESIGN.md §11 "Turns"), shared by scene_turn.hip (yh_scene_plan_turn and
+// yh_scene_batch_plan_turn: n frames per launch, the frame from blockIdx.z) and scene_turn_tour.hip (yh_scene_plan_turn_tour and
+// yh_scene_batch_plan_turn_tour: one field per frame and target, the field from blockIdx.z): the compass, the round over a tile of all eight layers,
 // the action rule, the chase along the action field and the walk. What they compute and why it is unique is said at the head of
 // scene_turn.hip. A body reads the frame it works on through p (cost [8][H][W], edge, edge2, W, H, tx) and through the pointers it is
 // given; it knows nothing of a batch.
@@ -10,7 +10,12 @@
 
 #include "scene_path_dev.h"
 
+struct yh_scene;
+
 namespace yh {
+
+// scene_turn.hip: the turn planners' one round kernel as solve_rounds takes it - field z of F = n kmax fields, kmax per frame
+SolveRound scene_turn_round(yh_scene* h, const PathParams& p, float tau, int kmax, int F);
 
 constexpr int TL = (SP_TH + 2) * SP_P;   // one layer of the tile with its halo
 constexpr int ACT_DRIVE = 0, ACT_CCW = 1, ACT_CW = 2, ACT_NONE = 3, ACT_TARGET = 255;
@@ -22,12 +27,6 @@ __host__ __device__ constexpr int head_dy(int h) { return (int)((0x00012221u >> 
 __host__ __device__ constexpr int head_edge(int h) { return (int)((0x52406371u >> (4 * h)) & 7u); }
 static_assert(head_dx(0) == 1 && head_dy(0) == 0 && head_dx(3) == -1 && head_dy(3) == 1 && head_dx(6) == 0 && head_dy(6) == -1 && head_dx(7) == 1 && head_dy(7) == -1, "compass");
 static_assert(head_edge(0) == 1 && head_edge(1) == 7 && head_edge(2) == 3 && head_edge(3) == 6 && head_edge(4) == 0 && head_edge(5) == 4 && head_edge(6) == 2 && head_edge(7) == 5, "compass");
-
-// +inf in state blockIdx.x * 256 + threadIdx.x of the eight layers at p.cost
-__device__ __forceinline__ void turn_fill_body(const PathParams& p) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (size_t)8 * p.W * p.H) p.cost[i] = SP_INF;
-}
 
 // One round of the turn field at p.cost: tile (blockIdx.x, blockIdx.y), flagged in `mine`; neighbours are flagged in `theirs`. As
 // relax_tile<8> with eight layers: the lane's block is a b / c d = q 0 1 / 2 3, V[h][q] its 32 values, L / D[q][h] the (length, |dh|)

@@ -1,6 +1,6 @@
-// scene_turn_tour_dev.h — the turn-aware tour's device code and its order search (DESIGN.md §11 "Turn tour"), shared by
-// scene_turn_tour.hip (yh_scene_plan_turn_tour: one frame, the field from blockIdx.z) and scene_batch_turn_tour.hip
-// (yh_scene_batch_plan_turn_tour: N frames per launch, the frame from blockIdx.z): the action-and-label rule, an entry of the leg
+// scene_turn_tour_dev.h — the turn-aware tour's device code and its order search (DESIGN.md §11 "Turn tour"), for
+// scene_turn_tour.hip (yh_scene_plan_turn_tour and yh_scene_batch_plan_turn_tour: n frames per launch, the frame from blockIdx.z;
+// a scene is the batch of one): the action-and-label rule, an entry of the leg
 // table, a leg's walk, the join of the legs, and the choice of the order on the host. What they compute is said at the head of
 // scene_turn_tour.hip. A body reads the frame it works on through p (cost [K][8][H][W], edge, edge2, W, H) and through the pointers
 // it is given, all of them that frame's own; it knows nothing of a batch.

@@ -1,9 +1,12 @@
 """Registers / spills / LDS / scratch bytes of every kernel in lib/libyolact_hip.so (code-object metadata), optionally filtered by substrings.
-Usage: python tools/kernel_meta.py [substr ...]"""
+Usage: python tools/kernel_meta.py [--lib DIR] [substr ...]   (DIR: another build's library directory, e.g. lib_old, under the package)"""
 import os, re, subprocess, sys, tempfile, shutil, glob
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-so = os.path.join(ROOT, "tiny-object-detection_amd", "lib", "libyolact_hip.so")
+args = sys.argv[1:]
+libdir = "lib"
+if args[:1] == ["--lib"]: libdir, args = args[1], args[2:]
+so = os.path.join(ROOT, "tiny-object-detection_amd", libdir, "libyolact_hip.so")
 tmp = tempfile.mkdtemp()
 try:
     dst = os.path.join(tmp, "lib.so"); shutil.copy(so, dst)
@@ -16,7 +19,7 @@ try:
             f = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, blk) or [None, "?"])[1]
             dem = subprocess.run(["c++filt", name.group(1)], capture_output=True, text=True).stdout.strip()
             dem = dem.replace("void yh::", "").replace("(yh::ConvParams)", "").replace("(yh::BneckParams)", "")
-            if all(s in dem for s in sys.argv[1:]):
-                print(f"vgpr {f('vgpr_count'):>3} spill {f('vgpr_spill_count'):>3} lds {f('group_segment_fixed_size'):>6} scratch {f('private_segment_fixed_size'):>4}  {dem[:150]}")
+            if all(s in dem for s in args):
+                print(f"vgpr {f('vgpr_count'):>3} sgpr {f('sgpr_count'):>3} spill {f('vgpr_spill_count'):>3} lds {f('group_segment_fixed_size'):>6} scratch {f('private_segment_fixed_size'):>4}  {dem[:150]}")
 finally:
     shutil.rmtree(tmp)

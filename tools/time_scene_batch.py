@@ -12,26 +12,32 @@ frame), every frame from the reference's START_NODE facing up; the host wall is 
 tours"; yh_scene_batch_turn_tour_time) beside the same frames through Scene.plan_turn_tour (yh_scene_turn_tour_time per frame), to the
 first K of tools/time_tour.py's six camera targets in every frame (--targets K, default 3); the host wall is then stage + append +
 turn tour. --frames n,n,..: those batch sizes only.
-Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P [--turn-tour [--targets K]]] [--frames n,n,..]"""
+--lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
+LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box.
+Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P [--turn-tour [--targets K]]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
-import yolact_amd as ya
-args, tau, tour, K, sizes = [], None, False, 3, (1, 2, 4, 8, 16, 64)
+from yolact_amd import capi
+args, tau, tour, K, sizes, lib = [], None, False, 3, (1, 2, 4, 8, 16, 64), None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--turn-price": tau = float(next(it))
     elif a == "--turn-tour": tour = True
     elif a == "--targets": K = int(next(it))
     elif a == "--frames": sizes = tuple(int(v) for v in next(it).split(","))
+    elif a == "--lib": lib = os.path.abspath(next(it))
     else: args.append(a)
 sets = int(args[0]) if len(args) > 0 else 5
 reps = int(args[1]) if len(args) > 1 else 20
 if tour and not tau: sys.exit("--turn-tour needs --turn-price P")
+if lib:
+    capi.lib_path = lambda: lib
+import yolact_amd as ya
 H, W = 480, 640
 TARGETS = [(70, 67), (515, 410), (320, 40), (600, 100), (30, 440), (250, 300)][:K]   # tools/time_tour.py's camera targets
-print(f"box {socket.gethostname()}, {ya.version()}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else ""))
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else ""))
 
 
 def frame(seed):
