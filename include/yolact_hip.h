@@ -622,6 +622,31 @@ int yh_scene_batch_plan(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_ta
  * was YH_ESTATE, before a plan, and after a newer append; YH_EINVAL for a frame outside the last append. */
 int yh_scene_batch_plan_read(yh_scene_batch* h, int32_t frame, float* cost, int32_t* next, int32_t* path_xy, float* directions,
                              int32_t path_capacity, int32_t* path_len);
+/* yh_scene_plan_tour_conn for every frame of the last append in shared solver rounds (DESIGN.md section 11 "Scene batch: tours"):
+ * frame b has exactly the results of yh_scene_plan_tour_conn on a yh_scene of the same size fed that frame alone with the same
+ * targets, start and connectivity - every output of yh_scene_tour_read, bit for bit. n_targets (<= YH_TOUR_MAX) is one number per
+ * call; frame b uses K_b <= n_targets of them: with targets_xy NULL its first n_targets balls that have pixels, a ball outside the
+ * frame or on an earlier ball's pixel dropped; explicit targets must all lie inside the frame and be distinct. targets_xy, starts_xy
+ * and status as yh_scene_batch_plan: a frame with no usable ball gets no tour and status[b] = YH_ESTATE, the others are planned and
+ * the call returns YH_OK - unless NO frame has a target: then YH_ESTATE. The checks are yh_scene_batch_plan's and the tour's, made
+ * for all frames before anything is touched: YH_EINVAL for n_targets < 1 or > YH_TOUR_MAX, starts_xy NULL, a target or start outside
+ * the frame, two equal explicit targets in one frame (the text names the frame), a connectivity other than 4 or 8 and the planner's
+ * size guard; YH_ESTATE before an append, after a STRICT append, and with connectivity 8 for a frame whose uploaded diagonals allow
+ * 4-connected plans only. A refused call leaves an earlier batched tour of the same append readable; a call that fails later
+ * (YH_EHIP, a lost walk included: the text names the frame and the leg) leaves none.
+ * The tour's buffers are its own, allocated at the first call for max_frames frames x the largest n_targets used so far; they only
+ * grow (growing drops the last batched tour). They take 32 bytes per pixel, frame and target (cost 4, next 4, the legs' walks 8,
+ * the joined route 16) plus 1 per pixel and frame for the label: 640 x 480 with max_frames = 64 and n_targets = 6 is 3.8 GB - size
+ * max_frames and n_targets accordingly. The batch's plan, tour, turn plan and turn tour do not disturb each other's results. Beyond
+ * the solver's batches of rounds, one wait per call, whatever n. Synchronous. */
+int yh_scene_batch_plan_tour(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_targets][2] or NULL */, int32_t n_targets,
+                             const int32_t* starts_xy /* [n][2] */, int32_t connectivity /* 4 or 8 */, int32_t* status /* [n] or NULL */);
+/* One frame of the last batched tour, as yh_scene_tour_read (YH_EOVERFLOW with *path_len set and nothing copied included).
+ * YH_ESTATE for a frame whose status was YH_ESTATE, before a batched tour, and after a newer append; YH_EINVAL for a frame outside
+ * the last append. */
+int yh_scene_batch_tour_read(yh_scene_batch* h, int32_t frame, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs,
+                             float* total, float* cost, int32_t* next, uint8_t* label, int32_t* path_xy, float* directions,
+                             int32_t* leg_ends, int32_t path_capacity, int32_t* path_len);
 /* yh_scene_plan_turn for every frame of the last append in shared solver rounds (DESIGN.md section 11 "Scene batch: turns"): frame b
  * has exactly the results of yh_scene_plan_turn on a yh_scene fed that frame alone with the same targets, start, start heading and
  * turn price - cost, act, route, turns and directions, bit for bit. targets_xy, n_targets, starts_xy and status as
@@ -652,7 +677,7 @@ int yh_scene_batch_turn_read(yh_scene_batch* h, int32_t frame, float* cost, uint
  * The turn tour's buffers are its own, allocated at the first call for max_frames frames x the largest n_targets used so far; they
  * only grow (growing drops the last batched turn tour). They take 80 bytes per pixel, frame and target (cost 32, act 8, the legs'
  * walks 20, the joined route 20) plus 8 per pixel and frame for the label: 640 x 480 with max_frames = 64 and n_targets = 6 is
- * 9.6 GB - size max_frames and n_targets accordingly. The batch's plan, turn plan and turn tour do not disturb each other's
+ * 9.6 GB - size max_frames and n_targets accordingly. The batch's plan, tour, turn plan and turn tour do not disturb each other's
  * results. Two waits per call, whatever n. Synchronous. */
 int yh_scene_batch_plan_turn_tour(yh_scene_batch* h, const int32_t* targets_xy /* [n][n_targets][2] or NULL */, int32_t n_targets,
                                   const int32_t* starts_xy /* [n][2] */, const int32_t* start_headings /* [n], 0 .. 7 */,

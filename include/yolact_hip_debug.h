@@ -147,6 +147,10 @@ int yh_scene_batch_turn_time(yh_scene_batch* h, int32_t reps, float* ms_per_batc
  * tables, the host's choice of every frame's order and the walks fall inside): rounds = launches in which some tile of some field
  * of some frame ran, tile_runs summed over all fields. */
 int yh_scene_batch_turn_tour_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
+/* The same for the last yh_scene_batch_plan_tour, replayed with its targets, starts and connectivity (the host's choice of every
+ * frame's order and the walks fall inside): rounds = launches in which some tile of some field of some frame ran, tile_runs summed
+ * over all fields. */
+int yh_scene_batch_tour_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);
 /* yh_scene_set_fields for one frame of a batch, with the same checks, so that constructed mazes can sit beside easy frames. The first
  * use after create or an append starts a new batch whose n is the highest frame set + 1 (a plan refuses, YH_ESTATE, while a frame
  * below n has been given no fields). It counts as a YH_COMPAT_SANE append (a new frame generation). */

@@ -1,8 +1,8 @@
 // scene.h — the scene handle, shared by scene.hip (the two shaders as HIP kernels), scene_path.hip (the planner on its fields),
 // scene_tour.hip (the tour over several targets), scene_turn.hip (the turn-aware plan), scene_turn_tour.hip (the turn-aware tour),
 // scene_solve.hip (the field solver they run on) and scene_batch.hip (yh_scene_batch, scene_batch.h: N frames per launch; its handle
-// holds one of these as its core, the arrays those of N frames). The three planners that exist for both handles (plan, turn plan,
-// turn tour) have ONE driver each, over max_frames frames: a yh_scene is the batch of one.
+// holds one of these as its core, the arrays those of N frames). The four planners (plan, tour, turn plan, turn tour) exist for
+// both handles and have ONE driver each, over max_frames frames: a yh_scene is the batch of one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,7 +14,7 @@
 #include "yh_internal.h"
 
 struct yh_scene_path;   // the planner's fields, routes and last plan, frame-major (scene_path.hip); allocated at the first plan
-struct yh_scene_tour;   // the tour's fields, route and last tour (scene_tour.hip); allocated at the first yh_scene_plan_tour
+struct yh_scene_tour;   // the tour's fields, routes and last tour, frame-major (scene_tour.hip); allocated at the first tour
 struct yh_scene_turn;   // the turn-aware planner's fields, routes and last turn plan, frame-major (scene_turn.hip); allocated at the first turn plan
 struct yh_scene_turn_tour;   // the turn-aware tour's fields, leg tables and routes, frame-major (scene_turn_tour.hip); allocated at the first turn tour
 struct yh_scene_batch;  // scene_batch.h
@@ -78,7 +78,7 @@ int scene_plan_diagonals(yh_scene* h, bool ok, const std::string& why);
 int scene_turn_heading(yh_scene* h, int32_t heading);
 int scene_turn_price(yh_scene* h, float turn_price);
 int scene_turn_size(yh_scene* h);
-// What the three batched plans do before they touch anything (scene_batch.hip): every check of every frame (headings, if given,
+// What the four batched plans do before they touch anything (scene_batch.hip): every check of every frame (headings, if given,
 // are the turn planners': their size guard and every frame's diagonals are checked too; otherwise the diagonals only for
 // connectivity 8), one read-back of the balls, the choice of targets per frame - each(b, targets) takes frame b's and may refuse them -
 // and st[b] = YH_ESTATE for a frame without a usable ball (each is not called for it). A refusal names its frame.

@@ -1,5 +1,5 @@
 // scene_batch.h — the scene batch handle (yh_scene_batch): what is about frames as such. Its planners are its core's (scene.h): the
-// plan, turn plan and turn tour of a batch are the drivers of scene_path.hip, scene_turn.hip and scene_turn_tour.hip run over the
+// plan, tour, turn plan and turn tour of a batch are the drivers of scene_path.hip, scene_tour.hip, scene_turn.hip and scene_turn_tour.hip run over the
 // core's max_frames frames, and their yh_scene_batch_* entry points stand next to the yh_scene_* ones in those units.
 #pragma once
 #include <hip/hip_runtime.h>

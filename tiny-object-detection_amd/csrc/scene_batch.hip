@@ -8,7 +8,7 @@
 //
 // The handle holds a yh_scene as its core: device, size, stream, error text, bump tables, the frame generation and mode - and array
 // pointers that are frame 0 of the batch's [max_frames][...] arrays. The planners hang off that core and are the single handle's:
-// yh_scene_batch_plan, _plan_turn and _plan_turn_tour (scene_path.hip, scene_turn.hip, scene_turn_tour.hip) run the one driver of
+// yh_scene_batch_plan, _plan_tour, _plan_turn and _plan_turn_tour (scene_path.hip, scene_tour.hip, scene_turn.hip, scene_turn_tour.hip) run the one driver of
 // their kind over the core's frames, after scene_batch_frames below has checked every frame and chosen its targets.
 #include <hip/hip_runtime.h>
 
@@ -144,6 +144,7 @@ void yh_scene_batch_destroy(yh_scene_batch* hb) {
     hipSetDevice(h->dev);
     if (h->stream) hipStreamSynchronize(h->stream);
     scene_path_free(h);
+    scene_tour_free(h);
     scene_turn_free(h);
     scene_turn_tour_free(h);
     scene_solve_free(h);

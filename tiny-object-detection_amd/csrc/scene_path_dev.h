@@ -37,8 +37,8 @@ struct yh_scene_solve {
     float4* edge = nullptr;      // [max_frames][H][W]: right length, right |dh|, down length, down |dh| (length -1 off the frame)
     float4* edge2 = nullptr;     // [max_frames][H][W]: down-right length, |dh|, down-left length, |dh|; allocated at the first 8-connected run
     uint32_t* flags = nullptr;   // [2][F][ntiles], by round parity; sized for cap_f fields, grows only
-    uint32_t* cnt = nullptr;     // [kSolveCnt] counters, then kSolveTail words for the caller's after-batch kernel
-    uint32_t* host = nullptr;    // pinned: the cnt block as read back, then kSolveWalk words for the plain tour's walk results (scene_tour.hip)
+    uint32_t* cnt = nullptr;     // [kSolveCnt] counters, then kSolveTail words per frame of max_frames for the caller's after-batch kernel
+    uint32_t* host = nullptr;    // pinned: the cnt block as read back
     std::vector<uint32_t> flags0;   // [2][F][ntiles]: round 0's tile flags, built on the host, and the zeroes of the other parity
     int cap_f = 0, tx = 0, ty = 0;
     long long rounds = 0, tile_runs = 0;   // of the last run
@@ -57,7 +57,7 @@ struct PathParams {
     uint32_t* flags;
 };
 
-constexpr int kSolveCnt = SP_BATCH + 1, kSolveTail = 42, kSolveWalk = 12;   // cnt[j + 1] = tiles flagged by round j of the batch
+constexpr int kSolveCnt = SP_BATCH + 1, kSolveTail = 42;   // cnt[j + 1] = tiles flagged by round j of the batch; the tail: words per frame
 
 // What a kind of run (plan, tour) remembers of its last one, as far as the shared time and read code needs it
 struct SolveLast {
@@ -78,7 +78,7 @@ struct SolveRound { std::function<void(const dim3&, int, uint32_t*)> launch; int
 struct PlanInputs { int32_t *host = nullptr, *dev = nullptr; size_t cap = 0; };
 int plan_inputs_reserve(yh_scene* h, PlanInputs& in, size_t words);
 void plan_inputs_free(PlanInputs& in);
-// What the three frame-major planner states (plan, turn plan, turn tour) have in common: the routes, the inputs of the last call
+// What the four frame-major planner states (plan, tour, turn plan, turn tour) have in common: the routes, the inputs of the last call
 // (the replay of *_time runs exactly these) and its per-frame results. A yh_scene holds one frame, a yh_scene_batch's core max_frames.
 struct PlanFrames {
     int2* nodes = nullptr;         // [max][route_stride] the routes
@@ -99,11 +99,14 @@ int solve_frame(yh_scene* h, const PlanFrames* q, int frame, size_t route_stride
 int solve_begin(yh_scene* h, int conn, int F, int n, PathParams& p);
 // Relaxes the F fields at p.cost, which the caller has filled (+inf, 0 at the seeds), to their fixed points. seeds: the pixels that
 // start at 0, equally many per field, field by field. who: the kind of run ("path", "tour", "batch turn", ..), for the error text. after(tail), if given, enqueues
-// the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) arrives in host[kSolveCnt ..] with the counters.
-// own, if given, is the round kernel in place of field_round<conn> (round 0's flags still follow conn). field_of, if given, is the
-// ragged form: seed k belongs to field (*field_of)[k], any number per field - a field without a seed flags nothing and its tiles exit at once.
+// the caller's kernel after each batch's rounds: what it writes to tail[0 .. tail_words) (at most max_frames * kSolveTail words) arrives
+// in host[kSolveCnt ..] with the counters. own, if given, is the round kernel in place of field_round<conn> over F fields of one frame
+// (round 0's flags still follow conn). field_of, if given, is the ragged form: seed k belongs to field (*field_of)[k], any number per field - a field without a seed flags nothing and its tiles exit at once.
 int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::vector<int32_t>& seeds, const char* who, int tail_words = 0,
                  const std::function<void(uint32_t*)>& after = nullptr, const SolveRound* own = nullptr, const std::vector<int32_t>* field_of = nullptr);
+// The plain tour's round kernel (field_round<conn>, scene_solve.hip) over F = n kmax fields: field z relaxes with the edge terms of
+// frame z / kmax
+SolveRound solve_field_round(yh_scene* h, const PathParams& p, int conn, int kmax, int F);
 // run() reps times between two events; a failing run's code is returned as it is. kind, again: for the error texts ("plan", "plan again")
 int solve_time(yh_scene* h, const char* kind, const char* again, const SolveLast* q, int reps, const std::function<int()>& run, float* ms, int32_t* rounds, int32_t* tile_runs);
 // The checks of the read entry points (a run of this frame exists, the capacity holds the route - also asked for if per_node, an array
@@ -124,8 +127,8 @@ inline void round0_flags(int x, int y, int conn, F&& flag) {
 }
 
 // Frame b of a frame-major batch (b = blockIdx.z; a yh_scene has the one frame 0): the scene's fields and the edge terms advance
-// by W H, cost by cost_stride: W H for the plain plan, 8 W H for the turn plan, Kmax 8 W H for the turn tour, 0 where there is no
-// cost yet (path_weights). next is the plain plan's alone: its kernels advance it themselves (scene_path.hip).
+// by W H, cost by cost_stride: W H for the plain plan, Kmax W H for the tour, 8 W H for the turn plan, Kmax 8 W H for the turn tour,
+// 0 where there is no cost yet (path_weights) or the caller advances it by field (field_round). next is the plain plan's alone: its kernels advance it themselves (scene_path.hip).
 __device__ __forceinline__ PathParams frame_of(const PathParams& p, int b, size_t cost_stride) {
     PathParams q = p;
     const size_t npx = (size_t)p.W * p.H;
@@ -138,7 +141,8 @@ __device__ __forceinline__ PathParams frame_of(const PathParams& p, int b, size_
 // whatever the kernel's entry sequence was. One wave steps through a route for tens of milliseconds in a maze, and how its loops lie
 // in the instruction cache shows: with the same instructions, the longer entry of the frame-major kernels (the frame advance) made
 // turn_walk 3.5 % and tt_walk 8 % slower than the parent commit's one-frame forms; started on a cache line they run as those did
-// ("One driver per kind"; tt_arrive ran 5 % slower with it than without and is left where it falls).
+// ("One driver per kind"; tt_arrive ran 5 % and the plain tour's tour_walk 6 % slower with it than without:
+// they are left where they fall).
 #define SP_BODY_ON_CACHE_LINE() asm volatile(".p2align 6")
 
 __device__ __forceinline__ float cand(float dn, float len, float dh) { return __fadd_rn(__fadd_rn(dn, len), dh); }

@@ -6,7 +6,8 @@
 //   path_weights   one lane per pixel, the frame from blockIdx.z: conn0 / conn1 / map -> one float4 per pixel (right length, right
 //                  height step, down length, down height step; <8>: a second one for down-right and down-left): the solver reads
 //                  16 B per pixel instead of 32 B of connections + the map, length and step stay apart for the two roundings.
-//   field_round    (the plain tour's; the plans' round kernels are their units') x rounds, grid (tiles x, tiles y, F): relax_tile (scene_path_dev.h) on field z with field z's flags: a flagged
+//   field_round    (the plain tour's; the plans' round kernels are their units') x rounds, grid (tiles x, tiles y, F = n Kmax): relax_tile
+//                  (scene_path_dev.h) on field z with field z's flags and the edge terms of frame z / Kmax: a flagged
 //                  tile relaxes in LDS to its local fixed point for the halo it loaded, and cells that changed go back with atomicMin
 //                  on the u32 view (non-negative f32 order as their bits). Only a tile whose halo may have changed runs: a tile that
 //                  lowered a cell of its border flags that neighbour for the NEXT round (two flag arrays, by round parity) and
@@ -30,10 +31,11 @@ namespace {
 template <int CONN>
 __global__ __launch_bounds__(256) void path_weights(const PathParams p) { weights_body<CONN>(frame_of(p, blockIdx.z, 0)); }
 
+// field z = blockIdx.z of F = n kmax: field z % kmax of frame z / kmax, with that frame's edge terms and its own cost field and flags
 template <int CONN>
-__global__ __launch_bounds__(SP_NT) void field_round(const PathParams p, int F, int parity, uint32_t* cnt_next) {
-    const int b = blockIdx.z;
-    relax_tile<CONN>(p, p.cost + (size_t)b * p.W * p.H, p.flags + (size_t)(parity * F + b) * p.ntiles, p.flags + (size_t)((parity ^ 1) * F + b) * p.ntiles, cnt_next);
+__global__ __launch_bounds__(SP_NT) void field_round(const PathParams p, int kmax, int F, int parity, uint32_t* cnt_next) {
+    const int z = blockIdx.z;
+    relax_tile<CONN>(frame_of(p, z / kmax, 0), p.cost + (size_t)z * p.W * p.H, p.flags + (size_t)(parity * F + z) * p.ntiles, p.flags + (size_t)((parity ^ 1) * F + z) * p.ntiles, cnt_next);
 }
 
 int last_ok(yh_scene* h, const char* kind, const char* again, const SolveLast* q) {
@@ -53,8 +55,8 @@ int solve_begin(yh_scene* h, int conn, int F, int n, PathParams& p) {
     s->tx = (h->W + SP_TW - 1) / SP_TW; s->ty = (h->H + SP_TH - 1) / SP_TH;
     if (!s->edge) SCHK(h, hipMalloc((void**)&s->edge, frames * npx * 16));
     if (conn == 8 && !s->edge2) SCHK(h, hipMalloc((void**)&s->edge2, frames * npx * 16));
-    if (!s->cnt) SCHK(h, hipMalloc((void**)&s->cnt, (kSolveCnt + kSolveTail) * 4));
-    if (!s->host) SCHK(h, hipHostMalloc((void**)&s->host, (kSolveCnt + kSolveTail + kSolveWalk) * 4, hipHostMallocDefault));
+    if (!s->cnt) SCHK(h, hipMalloc((void**)&s->cnt, (kSolveCnt + frames * kSolveTail) * 4));
+    if (!s->host) SCHK(h, hipHostMalloc((void**)&s->host, (kSolveCnt + frames * kSolveTail) * 4, hipHostMallocDefault));
     if (F > s->cap_f) {
         if (s->flags) { SCHK(h, hipStreamSynchronize(h->stream)); SCHK(h, hipFree(s->flags)); s->flags = nullptr; s->cap_f = 0; }
         SCHK(h, hipMalloc((void**)&s->flags, (size_t)2 * F * s->tx * s->ty * 4));
@@ -65,6 +67,12 @@ int solve_begin(yh_scene* h, int conn, int F, int n, PathParams& p) {
     p.cost = nullptr; p.next = nullptr;
     hipLaunchKernelGGL(conn == 8 ? path_weights<8> : path_weights<4>, dim3((unsigned)((npx + 255) / 256), 1, (unsigned)n), dim3(256), 0, h->stream, p);
     return YH_OK;
+}
+
+SolveRound solve_field_round(yh_scene* h, const PathParams& p, int conn, int kmax, int F) {
+    return SolveRound{ [=](const dim3& tiles, int parity, uint32_t* cnt_next) {
+        hipLaunchKernelGGL(conn == 8 ? field_round<8> : field_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, kmax, F, parity, cnt_next);
+    }, 1 };
 }
 
 int plan_inputs_reserve(yh_scene* h, PlanInputs& in, size_t words) {
@@ -114,15 +122,15 @@ int solve_rounds(yh_scene* h, const PathParams& p, int conn, int F, const std::v
     }
     SCHK(h, hipMemcpyAsync(s->flags, s->flags0.data(), 2 * nflags * 4, hipMemcpyHostToDevice, h->stream));
     s->rounds = 0; s->tile_runs = 0;
-    const long long cap = (long long)h->W * h->H * (own ? own->states : 1);   // costs only decrease over a finite set: this never fires
+    const SolveRound round_kernel = own ? *own : solve_field_round(h, p, conn, F, F);   // (no kernel given: F fields of one frame)
+    const long long cap = (long long)h->W * h->H * round_kernel.states;   // costs only decrease over a finite set: this never fires
     const dim3 tiles((unsigned)s->tx, (unsigned)s->ty, (unsigned)F);
     long long round = 0;
     while (active) {
-        if (round >= cap) return h->fail(YH_EHIP, std::string(who) + " solver: round cap " + (own ? std::to_string(own->states) + "*" : "") + "W*H reached without convergence (fields not those of a SANE frame?)");
+        if (round >= cap) return h->fail(YH_EHIP, std::string(who) + " solver: round cap " + (round_kernel.states > 1 ? std::to_string(round_kernel.states) + "*" : "") + "W*H reached without convergence (fields not those of a SANE frame?)");
         SCHK(h, hipMemsetAsync(s->cnt, 0, kSolveCnt * 4, h->stream));
         for (int j = 0; j < SP_BATCH; ++j, ++round)
-            if (own) own->launch(tiles, (int)(round & 1), s->cnt + j + 1);
-            else hipLaunchKernelGGL(conn == 8 ? field_round<8> : field_round<4>, tiles, dim3(SP_NT), 0, h->stream, p, F, (int)(round & 1), s->cnt + j + 1);
+            round_kernel.launch(tiles, (int)(round & 1), s->cnt + j + 1);
         if (after) after(s->cnt + kSolveCnt);
         SCHK(h, hipGetLastError());
         SCHK(h, hipMemcpyAsync(s->host, s->cnt, (size_t)(kSolveCnt + tail_words) * 4, hipMemcpyDeviceToHost, h->stream));

@@ -181,6 +181,9 @@ SYMBOLS = [
     ("yh_scene_batch_plan_turn_tour", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_tour_read", _i, [_vp, _i, C.POINTER(_i), _vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_batch_plan_tour", _i, [_vp, _vp, _i, _vp, _i, _vp]),
+    ("yh_scene_batch_tour_read", _i, [_vp, _i, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    ("yh_scene_batch_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
@@ -1320,6 +1323,52 @@ class SceneBatch:
         """Replays the last plan: dict(ms_per_batch, rounds, tile_runs)."""
         ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
         self._chk(self.L.yh_scene_batch_plan_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
+        return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
+
+    def plan_tour(self, targets=None, n_targets=3, starts=None, connectivity=4):
+        """The tour (Scene.plan_tour) of every frame of the last append in shared solver rounds. targets: [n][k] (x, y) pixels, k at
+        most TOUR_MAX and distinct within a frame, or None: each frame's first n_targets balls (a ball on an earlier ball's pixel
+        dropped, so frames may have fewer). starts and connectivity as plan().
+        Returns the status list: OK, or ESTATE for a frame without a usable ball (it has no tour)."""
+        n = self.n
+        if starts is None:
+            if (self.W, self.H) != (640, 480):
+                raise ValueError("starts=None is the reference's START_NODE at 640x480; give the starts for other sizes")
+            starts = [(400, 479)] * n
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1, 2)
+        assert len(s) == n
+        status = np.zeros(max(n, 1), np.int32)
+        if targets is None:
+            self._chk(self.L.yh_scene_batch_plan_tour(self.h, None, n_targets, _p(s), connectivity, _p(status)))
+        else:
+            t = np.ascontiguousarray(targets, np.int32)
+            assert t.ndim == 3 and t.shape[0] == n and t.shape[2] == 2
+            self._chk(self.L.yh_scene_batch_plan_tour(self.h, _p(t), t.shape[1], _p(s), connectivity, _p(status)))
+        return [int(v) for v in status[:n]]
+
+    def read_tour(self, b, fields=False):
+        """Frame b of the last tour, as Scene.read_tour."""
+        k, n, total = C.c_int32(), C.c_int32(), C.c_float()
+        self._chk(self.L.yh_scene_batch_tour_read(self.h, b, C.byref(k), None, None, None, None, None, None, None, None, None, None, 0, C.byref(n)))
+        K = k.value
+        out = dict(targets=np.zeros((K, 2), np.int32), order=np.zeros(K, np.int32), legs=np.zeros((K + 1, K), np.float32),
+                   path=np.zeros((n.value, 2), np.int32), leg_ends=np.zeros(K, np.int32))
+        dirs = np.zeros((n.value, 2), np.float32)
+        if fields:
+            out["cost"] = np.zeros((K, self.H, self.W), np.float32)
+            out["next"] = np.zeros((K, self.H, self.W), np.int32)
+            out["label"] = np.zeros((self.H, self.W), np.uint8)
+        f = lambda name: _p(out[name]) if fields else None
+        self._chk(self.L.yh_scene_batch_tour_read(self.h, b, C.byref(k), _p(out["targets"]), _p(out["order"]), _p(out["legs"]), C.byref(total),
+                                                  f("cost"), f("next"), f("label"), _p(out["path"]), _p(dirs), _p(out["leg_ends"]), n.value, C.byref(n)))
+        out["total"] = np.float32(total.value)
+        out["directions"] = dirs[:max(n.value - 1, 0)]
+        return out
+
+    def tour_time(self, reps=20):
+        """Replays the last tour: dict(ms_per_batch, rounds, tile_runs)."""
+        ms, r, t = C.c_float(), C.c_int32(), C.c_int32()
+        self._chk(self.L.yh_scene_batch_tour_time(self.h, reps, C.byref(ms), C.byref(r), C.byref(t)))
         return dict(ms_per_batch=ms.value, rounds=r.value, tile_runs=t.value)
 
     def plan_turn(self, targets=None, n_targets=3, starts=None, headings=6, turn_price=2.0):

@@ -11,20 +11,26 @@ frame), every frame from the reference's START_NODE facing up; the host wall is 
 --turn-tour (with --turn-price P): the batched turn-aware tour instead (yh_scene_batch_plan_turn_tour, DESIGN.md §11 "Scene batch: turn
 tours"; yh_scene_batch_turn_tour_time) beside the same frames through Scene.plan_turn_tour (yh_scene_turn_tour_time per frame), to the
 first K of tools/time_tour.py's six camera targets in every frame (--targets K, default 3); the host wall is then stage + append +
-turn tour. --frames n,n,..: those batch sizes only.
+turn tour.
+--tour [--connectivity 8]: the batched plain tour instead (yh_scene_batch_plan_tour, DESIGN.md §11 "Scene batch: tours";
+yh_scene_batch_tour_time) beside the same frames through one Scene.plan_tour (yh_scene_tour_time per frame), to the first K of the same
+camera targets (--targets K, default 3) on the 4- or 8-connected grid, for n = 1, 2, 8, 16, 64; the host wall is then stage + append + tour.
+--frames n,n,..: those batch sizes only.
 --lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
 LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box.
-Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P [--turn-tour [--targets K]]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
+Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
 from yolact_amd import capi
-args, tau, tour, K, sizes, lib = [], None, False, 3, (1, 2, 4, 8, 16, 64), None
+args, tau, tour, plain, conn_tour, K, sizes, lib = [], None, False, False, 4, 3, None, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--turn-price": tau = float(next(it))
     elif a == "--turn-tour": tour = True
+    elif a == "--tour": plain = True
+    elif a == "--connectivity": conn_tour = int(next(it))
     elif a == "--targets": K = int(next(it))
     elif a == "--frames": sizes = tuple(int(v) for v in next(it).split(","))
     elif a == "--lib": lib = os.path.abspath(next(it))
@@ -32,12 +38,15 @@ for a in it:
 sets = int(args[0]) if len(args) > 0 else 5
 reps = int(args[1]) if len(args) > 1 else 20
 if tour and not tau: sys.exit("--turn-tour needs --turn-price P")
+if plain and tau: sys.exit("--tour is the plain tour: no --turn-price")
+if sizes is None: sizes = (1, 2, 8, 16, 64) if plain else (1, 2, 4, 8, 16, 64)
+own = tau or plain   # the plan columns are one kind of its own instead of the plan with connectivity 4 and 8
 if lib:
     capi.lib_path = lambda: lib
 import yolact_amd as ya
 H, W = 480, 640
 TARGETS = [(70, 67), (515, 410), (320, 40), (600, 100), (30, 440), (250, 300)][:K]   # tools/time_tour.py's camera targets
-print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else ""))
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
 
 
 def frame(seed):
@@ -52,21 +61,23 @@ sc = ya.Scene(W, H)
 for n in sizes:
     frames = [frame(b) for b in range(n)]
     sb = ya.SceneBatch(W, H, n)
-    kind = "turn tour" if tour else "turn plan"
+    kind = "tour" if plain else "turn tour" if tour else "turn plan"
     batch_turn = (lambda: sb.plan_turn_tour(targets=[TARGETS] * n, turn_price=tau)) if tour else (lambda: sb.plan_turn(turn_price=tau))
     single_turn = (lambda: sc.plan_turn_tour(targets=TARGETS, turn_price=tau)) if tour else (lambda: sc.plan_turn(turn_price=tau))
+    if plain:
+        batch_turn, single_turn = (lambda: sb.plan_tour(targets=[TARGETS] * n, connectivity=conn_tour)), (lambda: sc.plan_tour(targets=TARGETS, connectivity=conn_tour))
 
     def batch_set():
         t0 = time.perf_counter()
         for b in range(n):
             sb.stage(b, *frames[b])
         sb.append(n, ya.COMPAT_SANE)
-        batch_turn() if tau else sb.plan(connectivity=4)
+        batch_turn() if own else sb.plan(connectivity=4)
         out = dict(wall=(time.perf_counter() - t0) * 1e3)
         out["append"] = sb.time(reps) / n
-        if tau:
+        if own:
             batch_turn()
-            out["turn"] = sb.turn_tour_time(reps) if tour else sb.turn_time(reps)
+            out["turn"] = sb.tour_time(reps) if plain else sb.turn_tour_time(reps) if tour else sb.turn_time(reps)
             return out
         for conn in (4, 8):
             sb.plan(connectivity=conn)
@@ -77,16 +88,16 @@ for n in sizes:
         t0 = time.perf_counter()
         for d, f in frames:
             sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
-            single_turn() if tau else sc.plan(connectivity=4)
+            single_turn() if own else sc.plan(connectivity=4)
         out = dict(wall=(time.perf_counter() - t0) * 1e3, append=0.0)
         out[4] = dict(ms=0.0, rounds=0, tile_runs=0); out[8] = dict(ms=0.0, rounds=0, tile_runs=0); out["turn"] = dict(ms=0.0, rounds=0, tile_runs=0)
         for d, f in frames:
             sc.append_classified(d, frame_u32=f, mode=ya.COMPAT_SANE)
             out["append"] += sc.time(reps) / n
-            if tau:
+            if own:
                 single_turn()
-                s = sc.turn_tour_time(reps) if tour else sc.turn_time(reps)
-                out["turn"]["ms"] += s["ms_per_tour" if tour else "ms_per_plan"] / n
+                s = sc.tour_time(reps) if plain else sc.turn_tour_time(reps) if tour else sc.turn_time(reps)
+                out["turn"]["ms"] += s["ms_per_tour" if tour or plain else "ms_per_plan"] / n
                 out["turn"]["rounds"] = max(out["turn"]["rounds"], s["rounds"]); out["turn"]["tile_runs"] += s["tile_runs"]
                 continue
             for conn in (4, 8):
@@ -102,12 +113,12 @@ for n in sizes:
         B.append(batch_set()); S.append(single_set())
     print(f"n = {n}")
     print(f"  append, ms per frame:            batch {med([b['append'] for b in B]):.4f}   single {med([s['append'] for s in S]):.4f}")
-    if tau:
-        print(f"  {kind}, price {tau}, ms per frame:  batch {med([b['turn']['ms_per_batch'] for b in B]) / n:.4f} ({B[0]['turn']['rounds']} rounds, {B[0]['turn']['tile_runs']} tile runs)"
+    if own:
+        print(f"  {kind}, {f'{conn_tour}-connected' if plain else f'price {tau}'}, ms per frame:  batch {med([b['turn']['ms_per_batch'] for b in B]) / n:.4f} ({B[0]['turn']['rounds']} rounds, {B[0]['turn']['tile_runs']} tile runs)"
               f"   single {med([s['turn']['ms'] for s in S]):.4f} (at most {S[0]['turn']['rounds']} rounds, {S[0]['turn']['tile_runs']} tile runs in all)")
-    for conn in (() if tau else (4, 8)):
+    for conn in (() if own else (4, 8)):
         print(f"  plan {conn}-connected, ms per frame:  batch {med([b[conn]['ms_per_batch'] for b in B]) / n:.4f} ({B[0][conn]['rounds']} rounds, {B[0][conn]['tile_runs']} tile runs)"
               f"   single {med([s[conn]['ms'] for s in S]):.4f} (at most {S[0][conn]['rounds']} rounds, {S[0][conn]['tile_runs']} tile runs in all)")
     wb, ws = med([b["wall"] for b in B]), med([s["wall"] for s in S])
-    print(f"  host wall, stage + append + {kind if tau else 'plan (4-connected)'} of the n frames: batch {wb:.3f} ms   single {ws:.3f} ms   ratio {wb / ws:.3f}")
+    print(f"  host wall, stage + append + {kind if own else 'plan (4-connected)'} of the n frames: batch {wb:.3f} ms   single {ws:.3f} ms   ratio {wb / ws:.3f}")
     sb.close()
