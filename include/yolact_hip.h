@@ -574,6 +574,39 @@ int yh_scene_plan_turn_tour(yh_scene* h, const int32_t* targets_xy /* [n][2] or 
 int yh_scene_turn_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy, int32_t* order, float* legs, uint8_t* arrive,
                             float* total, int32_t* leg_headings, float* cost, uint8_t* act, uint8_t* label, int32_t* path_xy,
                             float* directions, int32_t* turns, int32_t* leg_ends, int32_t path_capacity, int32_t* path_len);
+/* ---- scene memory (DESIGN.md section 11 "Scene memory"): map and balls carried across frames by the robot's motion -----------
+ * A yh_scene holds a memory: M, u32 [h][w], and a ball table B[100] of (x, y, count, age) i32, count = 0 meaning empty. It is empty
+ * after create and after yh_scene_memory_reset; yh_scene_append, yh_scene_append_classified, yh_scene_set_fields and the planners
+ * leave it untouched. yh_scene_append_memory is yh_scene_append_classified(.., YH_COMPAT_SANE) - the same inputs, the same stamps N
+ * and frame balls - followed by, all in integers (64-bit intermediates), bit-exact:
+ *   carry   for every map pixel (x, y), with gather_q16 = (a, b, c, d, e, f): sx = floor((a x + b y + c + 2^15) / 2^16),
+ *           sy = floor((d x + e y + f + 2^15) / 2^16); P = M[sy][sx] inside the frame, else 0; P' = (P * keep) >> 8
+ *           (keep 0 .. 256: 256 never fades, 0 keeps nothing);
+ *   fuse    F = max(N, P') is the handle's map and the new M; world, connections0 and connections1 are those of a SANE frame
+ *           whose height map is F, bit for bit;
+ *   balls   carry_q16 (the same formula; it maps a PREVIOUS-map pixel to a current-map pixel, the other direction from
+ *           gather_q16). An id the frame sees: B[k] = ((int)mean x, (int)mean y, count, 0), balls[k] the frame's own row. An id it
+ *           does not see, with B[k].count > 0 and B[k].age + 1 <= ball_max_age (0 .. 255): (x', y') = carry(B[k].x, B[k].y); the
+ *           entry is cleared if |x'| or |y'| >= 2^20, otherwise B[k] = (x', y', count, age + 1) and balls[k] = (x', y', count, age)
+ *           as floats - age as it was before this frame - if (x', y') lies inside the frame, zeros if not: a remembered ball
+ *           behind the robot stays in B and comes back when the robot turns, and meanwhile takes none of the n_targets of a plan
+ *           on the frame's balls. Every other entry is cleared, its balls[k] zeros.
+ * Ball ids carry meaning from frame to frame only when they are TRACK ids (yh_instance_track's frames); the ids of
+ * yh_instance_frame are per-frame detection indices, and a memory of those joins unrelated balls.
+ * Any six int32 values are a valid motion (affine, not only rigid); where it comes from is the caller's business (odometry).
+ * It counts as a new frame (earlier plans become unreadable) in YH_COMPAT_SANE, and every planner runs on it as on any other.
+ * With an empty memory, or keep = 0 and ball_max_age = 0, every output equals yh_scene_append_classified(.., YH_COMPAT_SANE)'s.
+ * Asynchronous on the handle's stream; host buffers (depth, a host frame, the two motions) are free again on return.
+ * YH_EINVAL with nothing touched, the memory included, for a null pointer, keep outside 0 .. 256 or ball_max_age outside 0 .. 255;
+ * a call that fails later (YH_EHIP) leaves no frame and an empty memory. The memory's buffers (three maps) are allocated at the
+ * first memory append. */
+int yh_scene_append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device,
+                           const int32_t* gather_q16 /* [6] */, const int32_t* carry_q16 /* [6] */, int32_t keep, int32_t ball_max_age);
+/* The memory as the last memory append left it: map_mem u32 [h][w], balls_mem i32 [100][4] = (x, y, count, age). Either pointer may
+ * be NULL. Waits. Zeros before any memory append and after a reset. */
+int yh_scene_memory_read(yh_scene* h, uint32_t* map_mem, int32_t* balls_mem /* [100][4] */);
+/* Empties the memory (asynchronous on the handle's stream). The last frame's fields and plans stay as they are. */
+int yh_scene_memory_reset(yh_scene* h);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

@@ -112,6 +112,11 @@ int yh_tfl_tensor_read(yh_tfl* h, int32_t tensor, void* dst, size_t nbytes);   /
  * the compat mode of that append (a device frame given to yh_scene_append_classified must still be valid). The re-runs
  * overwrite the outputs with the same values. */
 int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame);
+/* The same for a frame that came from yh_scene_append_memory (yh_scene_time refuses such a frame with YH_ESTATE and names this
+ * hook): its launches - stamps, ball memory, fuse - replayed with its inputs and motions on the memory as it was BEFORE that
+ * append, so the re-runs rewrite the outputs and the memory with the same values and commit nothing. YH_ESTATE unless the
+ * handle's last frame is a memory append (a plain append, yh_scene_set_fields or yh_scene_memory_reset since ends that). */
+int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame);
 /* Test hook: uploads host fields (height map u32 [h][w], connections0 / connections1 f32 [h][w][4], laid out as yh_scene_read
  * returns them) as if a YH_COMPAT_SANE frame had produced them, so that yh_scene_plan runs on constructed mazes. The planner reads
  * conn0[..][2] (right) and conn1[..][0] (down) and takes left / up from the neighbour, as SANE's symmetry allows: YH_EINVAL (nothing

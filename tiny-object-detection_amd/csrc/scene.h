@@ -19,6 +19,8 @@ struct yh_scene_turn;   // the turn-aware planner's fields, routes and last turn
 struct yh_scene_turn_tour;   // the turn-aware tour's fields, leg tables and routes, frame-major (scene_turn_tour.hip); allocated at the first turn tour
 struct yh_scene_batch;  // scene_batch.h
 struct yh_scene_solve;  // the solver's buffers, one set for both (scene_path_dev.h, scene_solve.hip); allocated at the first of either
+struct yh_scene_memory; // the scene memory: map and ball table carried across frames (scene_memory.hip); allocated at the first memory append
+namespace yh { struct SceneParams; }   // scene_dev.h
 
 struct yh_scene {
     int dev = 0, W = 0, H = 0, band_h = 64;
@@ -49,6 +51,7 @@ struct yh_scene {
     yh_scene_turn* turn = nullptr;
     yh_scene_turn_tour* turn_tour = nullptr;
     yh_scene_solve* solve = nullptr;
+    yh_scene_memory* memory = nullptr;
     int fail(int code, const std::string& m) { err = m; return code; }
     std::string frame_tag(int b) const { return batch ? "frame " + std::to_string(b) + ": " : std::string(); }
 };
@@ -71,6 +74,12 @@ int scene_check_fields(yh_scene* h, const float* conn0, const float* conn1, bool
 // scene.hip: waits until host sources a, b (either may be null) of copies enqueued on the stream may be reused; the bump tables of a handle
 int host_sources_done(yh_scene* h, const void* a, const void* b);
 hipError_t scene_tables_build(yh_scene* h);
+// scene.hip: the first two stages of a frame on the handle's stream - p.map and p.ball_acc cleared, the bumps stamped into p.map, the
+// ball means into p.balls (run_scene's own first half; the memory append stamps into a buffer of its own)
+int scene_stamp(yh_scene* h, const SceneParams& p);
+// scene_memory.hip: the memory's buffers (yh_scene_destroy); whether the handle's last frame came from yh_scene_append_memory
+void scene_memory_free(yh_scene* h);
+bool scene_memory_is_last(const yh_scene* h);
 // what an 8-connected plan or tour asks of a frame's diagonal lengths (YH_ESTATE and why if they fail it: ok and why are the
 // scene's diag_ok / diag_why, or those of a batch's frame); touches nothing
 int scene_plan_diagonals(yh_scene* h, bool ok, const std::string& why);

@@ -73,12 +73,9 @@ int run_scene(yh_scene* h, const uint16_t* depth_dev, const uint8_t* cls_dev, co
     p.W = h->W; p.H = h->H; p.mode = mode; p.band_h = h->band_h;
     p.terrain_tab = h->terrain_tab; p.robot_tab = h->robot_tab;
     p.map = h->map; p.world = h->world; p.conn0 = h->conn0; p.conn1 = h->conn1; p.ball_acc = h->ball_acc; p.balls = h->balls;
-    const size_t npx = (size_t)h->W * h->H;
-    SCHK(h, hipMemsetAsync(h->map, 0, npx * 4, h->stream));
-    SCHK(h, hipMemsetAsync(h->ball_acc, 0, 300 * sizeof(long long), h->stream));
+    const int rc = scene_stamp(h, p);
+    if (rc) return rc;
     const dim3 grid((unsigned)((h->W + 7) / 8), (unsigned)((h->H + 7) / 8)), block(8, 8);   // [80,60,1] x 8x8 at 640x480 (scene.rs:245,:256)
-    hipLaunchKernelGGL(scene_cloud_strips, dim3((unsigned)((h->W + SC_CW - 1) / SC_CW), (unsigned)((h->H + h->band_h - 1) / h->band_h)), dim3(512), 0, h->stream, p);
-    hipLaunchKernelGGL(scene_balls, dim3(1), dim3(128), 0, h->stream, p);
     hipLaunchKernelGGL(scene_world, grid, block, 0, h->stream, p);
     hipLaunchKernelGGL(scene_conn1, grid, block, 0, h->stream, p);
     hipLaunchKernelGGL(scene_conn0, grid, block, 0, h->stream, p);
@@ -92,6 +89,14 @@ int run_scene(yh_scene* h, const uint16_t* depth_dev, const uint8_t* cls_dev, co
 }  // namespace
 
 namespace yh {
+int scene_stamp(yh_scene* h, const SceneParams& p) {
+    SCHK(h, hipMemsetAsync(p.map, 0, (size_t)p.W * p.H * 4, h->stream));
+    SCHK(h, hipMemsetAsync(p.ball_acc, 0, 300 * sizeof(long long), h->stream));
+    hipLaunchKernelGGL(scene_cloud_strips, dim3((unsigned)((p.W + SC_CW - 1) / SC_CW), (unsigned)((p.H + p.band_h - 1) / p.band_h)), dim3(512), 0, h->stream, p);
+    hipLaunchKernelGGL(scene_balls, dim3(1), dim3(128), 0, h->stream, p);
+    return YH_OK;
+}
+
 // copy_from_slice semantics for host inputs (as yh_set_input_u8): the caller's buffers are free again when the call
 // returns. The runtime has staged a copy from PAGEABLE memory by then; from pinned / registered memory the DMA is still
 // reading, so wait for the copies (not for the kernels behind them: the event sits between the two).
@@ -166,6 +171,7 @@ void yh_scene_destroy(yh_scene* h) {
     scene_turn_free(h);
     scene_turn_tour_free(h);
     scene_solve_free(h);
+    scene_memory_free(h);
     void* bufs[] = { h->depth, h->cls_id, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);
     if (h->copied) hipEventDestroy(h->copied);
@@ -217,6 +223,8 @@ int yh_scene_read(yh_scene* h, uint32_t* map, float* world, float* conn0, float*
 int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!h->ran) return h->fail(YH_ESTATE, "no frame has been appended");
+    if (scene_memory_is_last(h))
+        return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory: yh_scene_memory_time replays it");
     SCHK(h, hipSetDevice(h->dev));
     hipEvent_t a, b;
     SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));

@@ -1,0 +1,201 @@
+// scene_memory.hip — the scene memory (DESIGN.md section 11 "Scene memory"): a yh_scene handle carries its height map and its balls
+// from frame to frame by the robot's motion, so that the planners see what the camera saw, not only what it sees now.
+// yh_scene_append_memory is yh_scene_append_classified(.., YH_COMPAT_SANE) with two stages replaced:
+//   stamps        scene_cloud_strips + scene_balls, unchanged (scene.hip: scene_stamp), but into the memory's own stamp buffer N;
+//   scene_balls_memory   one small workgroup: the ball table B carried by carry_q16, aged, merged with the frame's balls;
+//   scene_fuse    ONE launch in place of scene_world + scene_conn1 + scene_conn0: F = max(N, fade(M gathered by gather_q16)) per tile
+//                 with a one-pixel halo in LDS; F (to the map and to the next memory), world, conn0, conn1 written from there.
+// N, the old M and the new M are three buffers: a workgroup's halo reads N and the old M of pixels whose F a neighbour is writing.
+// The two memory buffers (and the two ball tables) swap at every memory append, so the previous state survives the append:
+// yh_scene_memory_time replays the same launches on it and rewrites the same bits.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <string>
+
+#include "scene.h"
+#include "scene_dev.h"
+#include "scene_memory_dev.h"
+#include "yh_internal.h"
+
+using namespace yh;
+
+struct MemoryCall {   // what one memory append runs on, besides the depth image in the handle's buffer
+    const uint32_t* frame = nullptr;   // device
+    int g[6] = {}, c[6] = {}, keep = 0, max_age = 0;
+};
+
+struct yh_scene_memory {
+    uint32_t* stamp = nullptr;             // N [H][W]
+    uint32_t* map[2] = { nullptr, nullptr };   // M [H][W]: map[cur] is the memory, map[cur ^ 1] what it was before the last memory append
+    int4* tab[2] = { nullptr, nullptr };   // B [100], likewise
+    int cur = 0;
+    bool stale = true;                     // the buffers are cleared before their next use: fresh ones, or a memory append failed half-way (YH_EHIP)
+    // the last memory append, for yh_scene_memory_time (frame == 0: none to replay); the handle's last frame is that append
+    // while h->frames == frame (every append and yh_scene_set_fields counts h->frames up)
+    uint64_t frame = 0;
+    MemoryCall last;
+};
+
+namespace {
+
+__global__ __launch_bounds__(256) void scene_fuse(const SceneFuseParams p) { fuse_body(p); }
+__global__ __launch_bounds__(128) void scene_balls_memory(const SceneBallsMemParams p) { balls_memory_body(p); }
+
+int memory_clear(yh_scene* h, yh_scene_memory* m) {
+    const size_t npx = (size_t)h->W * h->H;
+    for (int i = 0; i < 2; ++i) {
+        SCHK(h, hipMemsetAsync(m->map[i], 0, npx * 4, h->stream));
+        SCHK(h, hipMemsetAsync(m->tab[i], 0, 100 * sizeof(int4), h->stream));
+    }
+    m->stale = false;
+    m->frame = 0;
+    return YH_OK;
+}
+
+// the memory's buffers, at the first memory append: a handle that never remembers pays nothing
+int memory_reserve(yh_scene* h) {
+    if (!h->memory) h->memory = new yh_scene_memory();
+    yh_scene_memory* m = h->memory;
+    const size_t npx = (size_t)h->W * h->H;
+    if (!m->stamp) SCHK(h, hipMalloc((void**)&m->stamp, npx * 4));
+    for (int i = 0; i < 2; ++i) {
+        if (!m->map[i]) SCHK(h, hipMalloc((void**)&m->map[i], npx * 4));
+        if (!m->tab[i]) SCHK(h, hipMalloc((void**)&m->tab[i], 100 * sizeof(int4)));
+    }
+    return m->stale ? memory_clear(h, m) : YH_OK;
+}
+
+// the launches of one memory append: reads map[from] / tab[from], writes map[from ^ 1] / tab[from ^ 1] and the handle's fields
+int run_memory(yh_scene* h, const MemoryCall& q, int from) {
+    yh_scene_memory* m = h->memory;
+    SceneParams p;
+    p.depth = h->depth; p.cls_id = nullptr; p.frame = q.frame; p.frame_mode = 1;
+    p.W = h->W; p.H = h->H; p.mode = YH_COMPAT_SANE; p.band_h = h->band_h;
+    p.terrain_tab = h->terrain_tab; p.robot_tab = h->robot_tab;
+    p.map = m->stamp; p.world = h->world; p.conn0 = h->conn0; p.conn1 = h->conn1; p.ball_acc = h->ball_acc; p.balls = h->balls;
+    const int rc = scene_stamp(h, p);
+    if (rc) return rc;
+    SceneBallsMemParams b;
+    b.ball_acc = h->ball_acc; b.balls = h->balls; b.tab_prev = m->tab[from]; b.tab_next = m->tab[from ^ 1];
+    b.W = h->W; b.H = h->H; b.max_age = q.max_age;
+    SceneFuseParams f;
+    f.stamp = m->stamp; f.mem_prev = m->map[from]; f.mem_next = m->map[from ^ 1];
+    f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
+    f.W = h->W; f.H = h->H; f.keep = q.keep;
+    for (int i = 0; i < 6; ++i) { b.c[i] = q.c[i]; f.g[i] = q.g[i]; }
+    hipLaunchKernelGGL(scene_balls_memory, dim3(1), dim3(128), 0, h->stream, b);
+    hipLaunchKernelGGL(scene_fuse, dim3((unsigned)((h->W + SF_TW - 1) / SF_TW), (unsigned)((h->H + SF_TH - 1) / SF_TH)), dim3(256), 0, h->stream, f);
+    SCHK(h, hipGetLastError());
+    return YH_OK;
+}
+
+int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q) {
+    SCHK(h, hipSetDevice(h->dev));
+    int rc = memory_reserve(h);
+    if (rc) return rc;
+    const size_t npx = (size_t)h->W * h->H;
+    SCHK(h, hipMemcpyAsync(h->depth, depth_host, npx * 2, hipMemcpyHostToDevice, h->stream));
+    q.frame = frame;
+    if (!frame_on_device) { SCHK(h, hipMemcpyAsync(h->frame, frame, npx * 4, hipMemcpyHostToDevice, h->stream)); q.frame = h->frame; }
+    if ((rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame))) return rc;
+    yh_scene_memory* m = h->memory;
+    if ((rc = run_memory(h, q, m->cur))) return rc;
+    m->cur ^= 1;
+    m->last = q;
+    return YH_OK;
+}
+
+}  // namespace
+
+namespace yh {
+void scene_memory_free(yh_scene* h) {
+    yh_scene_memory* m = h->memory;
+    if (!m) return;
+    void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1] };
+    for (void* b : bufs) if (b) hipFree(b);
+    delete m;
+    h->memory = nullptr;
+}
+
+bool scene_memory_is_last(const yh_scene* h) { return h->memory && h->memory->frame != 0 && h->memory->frame == h->frames; }
+}  // namespace yh
+
+extern "C" {
+
+int yh_scene_append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device,
+                           const int32_t* gather_q16, const int32_t* carry_q16, int32_t keep, int32_t ball_max_age) {
+    if (!h || !depth_host || !frame || !gather_q16 || !carry_q16) return YH_EINVAL;
+    if (keep < 0 || keep > 256) return h->fail(YH_EINVAL, "keep outside 0 .. 256");
+    if (ball_max_age < 0 || ball_max_age > 255) return h->fail(YH_EINVAL, "ball_max_age outside 0 .. 255");
+    MemoryCall q;
+    for (int i = 0; i < 6; ++i) { q.g[i] = gather_q16[i]; q.c[i] = carry_q16[i]; }
+    q.keep = keep; q.max_age = ball_max_age;
+    ++h->frames;   // (earlier plans are of another frame, whatever becomes of this one)
+    const int rc = append_memory(h, depth_host, frame, frame_on_device, q);
+    yh_scene_memory* m = h->memory;
+    if (rc) {
+        // a call that fails after its checks leaves no frame and an empty memory
+        h->ran = false;
+        if (m) { m->stale = true; m->frame = 0; }
+        return rc;
+    }
+    m->frame = h->frames;
+    h->ran = true;
+    h->last_cls = nullptr; h->last_frame = m->last.frame; h->last_frame_mode = 1; h->last_mode = YH_COMPAT_SANE;
+    h->diag_ok = true; h->diag_why.clear();   // (F is a height map like any other: both ends of a diagonal hold the same length)
+    return YH_OK;
+}
+
+int yh_scene_memory_read(yh_scene* h, uint32_t* map_mem, int32_t* balls_mem) {
+    if (!h) return YH_EINVAL;
+    SCHK(h, hipSetDevice(h->dev));
+    const size_t npx = (size_t)h->W * h->H;
+    yh_scene_memory* m = h->memory;
+    if (!m) {   // no memory append yet: empty
+        if (map_mem) memset(map_mem, 0, npx * 4);
+        if (balls_mem) memset(balls_mem, 0, 100 * 4 * sizeof(int32_t));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        return YH_OK;
+    }
+    if (m->stale) { const int rc = memory_reserve(h); if (rc) return rc; }
+    if (map_mem) SCHK(h, hipMemcpyAsync(map_mem, m->map[m->cur], npx * 4, hipMemcpyDeviceToHost, h->stream));
+    if (balls_mem) SCHK(h, hipMemcpyAsync(balls_mem, m->tab[m->cur], 100 * sizeof(int4), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return YH_OK;
+}
+
+int yh_scene_memory_reset(yh_scene* h) {
+    if (!h) return YH_EINVAL;
+    yh_scene_memory* m = h->memory;
+    if (!m) return YH_OK;
+    SCHK(h, hipSetDevice(h->dev));
+    m->stale = true;   // (should the clearing fail, it is made again before the next use)
+    m->frame = 0;      // (nothing to replay: the state the last memory append started from is gone)
+    return memory_reserve(h);
+}
+
+int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
+    if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
+    if (!scene_memory_is_last(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    yh_scene_memory* m = h->memory;
+    hipEvent_t a, b;
+    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
+    SCHK(h, hipEventRecord(a, h->stream));
+    // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
+    // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
+    for (int r = 0; r < reps; ++r) {
+        const int rc = run_memory(h, m->last, m->cur ^ 1);
+        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; return rc; }
+    }
+    SCHK(h, hipEventRecord(b, h->stream));
+    SCHK(h, hipEventSynchronize(b));
+    float ms = 0;
+    hipEventElapsedTime(&ms, a, b);
+    hipEventDestroy(a); hipEventDestroy(b);
+    *ms_per_frame = ms / reps;
+    return YH_OK;
+}
+
+}  // extern "C"

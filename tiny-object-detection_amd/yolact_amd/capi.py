@@ -163,6 +163,10 @@ SYMBOLS = [
     ("yh_scene_plan_turn_tour", _i, [_vp, _vp, _i, _i, _i, _i, _f]),
     ("yh_scene_turn_tour_read", _i, [_vp, C.POINTER(_i), _vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_turn_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_scene_append_memory", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i]),
+    ("yh_scene_memory_read", _i, [_vp, _vp, _vp]),
+    ("yh_scene_memory_reset", _i, [_vp]),
+    ("yh_scene_memory_time", _i, [_vp, _i, C.POINTER(_f)]),
     ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
@@ -991,6 +995,25 @@ class Group:
         return out, (masks[:nd.value] if want_masks else None)
 
 
+def scene_motion(dx=0.0, dy=0.0, dtheta=0.0, pivot=None, size=(640, 480)):
+    """(gather_q16, carry_q16) for Scene.append_memory, as two lists of six ints, from what the robot did between two frames as the
+    map saw it: carry takes a previous-map pixel p to the current-map pixel R(dtheta) (p - pivot) + pivot + (dx, dy) - x to the right,
+    y down, dtheta in radians turning x towards y -, gather is its inverse. pivot: the robot's own pixel; None: the start pixel
+    (W * 5 / 8, H - 1) of a frame of `size` = (W, H). Coefficients are int(round(v * 65536)). A convenience: where the motion comes
+    from (odometry) is the caller's business, and any twelve integers are valid."""
+    import math
+    px, py = ((size[0] * 5) // 8, size[1] - 1) if pivot is None else pivot
+    c, s = math.cos(dtheta), math.sin(dtheta)
+    tx, ty = px - c * px + s * py + dx, py - s * px - c * py + dy           # carry: p' = R p + t
+    carry = (c, -s, tx, s, c, ty)
+    gather = (c, s, -(c * tx + s * ty), -s, c, s * tx - c * ty)             # p = R^T (p' - t)
+    q = lambda v: [int(round(x * 65536)) for x in v]
+    return q(gather), q(carry)
+
+
+SCENE_IDENTITY_Q16 = (65536, 0, 0, 0, 65536, 0)
+
+
 class Scene:
     """RAII wrapper of yh_scene: append_scene's two compute dispatches (src/scene.rs:147-331) on the GPU."""
 
@@ -1040,6 +1063,36 @@ class Scene:
     def time(self, reps=20):
         ms = C.c_float()
         self._chk(self.L.yh_scene_time(self.h, reps, C.byref(ms)))
+        return ms.value
+
+    def append_memory(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, motion=None, keep=224, ball_max_age=30):
+        """A frame fused into the handle's memory (DESIGN.md §11 "Scene memory"): the frame as append_classified(.., COMPAT_SANE) takes
+        it - or cls_id, (class, id) bytes [h][w][2], packed here - and motion = (gather_q16, carry_q16), six ints each (scene_motion);
+        None: the identity. keep 0 .. 256: how much of a remembered height survives a frame, in 256ths."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        g, c = (SCENE_IDENTITY_Q16, SCENE_IDENTITY_Q16) if motion is None else motion
+        g, c = np.array(g, np.int32), np.array(c, np.int32)   # (a value outside int32 raises here)
+        assert g.shape == (6,) and c.shape == (6,)
+        if frame_dev_ptr is not None:
+            self._chk(self.L.yh_scene_append_memory(self.h, _p(depth), C.c_void_p(frame_dev_ptr), 1, _p(g), _p(c), keep, ball_max_age))
+            return
+        f = SceneBatch.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+        assert f.size == self.W * self.H
+        self._chk(self.L.yh_scene_append_memory(self.h, _p(depth), _p(f), 0, _p(g), _p(c), keep, ball_max_age))
+
+    def read_memory(self):
+        """The memory as the last memory append left it: map u32 [h][w], balls i32 [100][4] = (x, y, count, age); zeros while empty."""
+        out = dict(map=np.zeros((self.H, self.W), np.uint32), balls=np.zeros((100, 4), np.int32))
+        self._chk(self.L.yh_scene_memory_read(self.h, _p(out["map"]), _p(out["balls"])))
+        return out
+
+    def memory_reset(self):
+        self._chk(self.L.yh_scene_memory_reset(self.h))
+
+    def memory_time(self, reps=20):
+        ms = C.c_float()
+        self._chk(self.L.yh_scene_memory_time(self.h, reps, C.byref(ms)))
         return ms.value
 
     def plan(self, targets=None, n_targets=3, start=None, connectivity=4):

@@ -1,5 +1,7 @@
 """The scene back-end (yh_scene_*: shaders/pt_cloud.comp + pt_cloud_weights.comp as HIP kernels) on one 640x480 frame:
-device milliseconds per frame (five launches), for a terrain-only frame and one with robots and balls."""
+device milliseconds per frame (five launches), for a terrain-only frame and one with robots and balls.
+--memory: the memory append (yh_scene_append_memory: stamps, ball memory and ONE fuse launch) against the plain append on the same
+frames, in one process: the two alternated, one warm-up each, the median of five runs of 30 frames, and the spread of each."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,11 +10,44 @@ import yolact_amd as ya
 H, W = 480, 640
 rng = np.random.default_rng(0)
 depth = rng.integers(200, 4000, (H, W)).astype(np.uint16)
-sc = ya.Scene(W, H)
-for name, robots in (("terrain only", False), ("robots + balls", True)):
-    ci = np.zeros((H, W, 2), np.uint8)
-    if robots:
-        ci[100:220, 150:330, 0] = 1; ci[260:330, 380:520, 0] = 2; ci[60:75, 60:80] = (3, 4); ci[400:420, 500:530] = (3, 9)
-    sc.append(depth, ci, ya.COMPAT_SANE)
-    out = sc.read()
-    print(f"scene 640x480, {name}: {sc.time(30):.3f} ms per frame (map max {out['map'].max()}, {int((out['balls'][:, 2] > 0).sum())} balls)")
+
+
+def frames():
+    for name, robots in (("terrain only", False), ("robots + balls", True)):
+        ci = np.zeros((H, W, 2), np.uint8)
+        if robots:
+            ci[100:220, 150:330, 0] = 1; ci[260:330, 380:520, 0] = 2; ci[60:75, 60:80] = (3, 4); ci[400:420, 500:530] = (3, 9)
+        yield name, ci
+
+
+def memory_table(runs=5, reps=30):
+    """rows of (frame, median ms plain, median ms memory, ratio of the medians, (max - min) / median of plain, of memory)"""
+    plain, mem = ya.Scene(W, H), ya.Scene(W, H)
+    motion = ya.scene_motion(3.0, -2.0, 0.05)           # a small turn and a step: gathers that cross rows, most sources inside the frame
+    rows = []
+    for name, ci in frames():
+        plain.append(depth, ci, ya.COMPAT_SANE)
+        mem.append_memory(depth, cls_id=ci, motion=motion)   # the memory is filled: the replayed append fuses this frame into it
+        mem.append_memory(depth, cls_id=ci, motion=motion)
+        plain.time(reps); mem.memory_time(reps)              # one warm-up each
+        tp, tm = [], []
+        for _ in range(runs):
+            tp.append(plain.time(reps)); tm.append(mem.memory_time(reps))
+        mp, mm = float(np.median(tp)), float(np.median(tm))
+        rows.append((name, mp, mm, mm / mp, (max(tp) - min(tp)) / mp, (max(tm) - min(tm)) / mm))
+    plain.close(); mem.close()
+    return rows
+
+
+if __name__ == "__main__":
+    if "--memory" in sys.argv[1:]:
+        print(f"scene {W}x{H}: plain append (yh_scene_time) against memory append (yh_scene_memory_time), ms per frame, median of 5 x 30 frames")
+        print(f"{'frame':<16} {'plain':>8} {'memory':>8} {'ratio':>7} {'spread plain':>13} {'spread memory':>14}")
+        for name, mp, mm, ratio, sp, sm in memory_table():
+            print(f"{name:<16} {mp:8.4f} {mm:8.4f} {ratio:7.3f} {100 * sp:12.1f}% {100 * sm:13.1f}%")
+    else:
+        sc = ya.Scene(W, H)
+        for name, ci in frames():
+            sc.append(depth, ci, ya.COMPAT_SANE)
+            out = sc.read()
+            print(f"scene 640x480, {name}: {sc.time(30):.3f} ms per frame (map max {out['map'].max()}, {int((out['balls'][:, 2] > 0).sum())} balls)")
