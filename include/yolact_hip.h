@@ -722,6 +722,40 @@ int yh_scene_batch_turn_tour_read(yh_scene_batch* h, int32_t frame, int32_t* n_t
                                   uint8_t* arrive, float* total, int32_t* leg_headings, float* cost, uint8_t* act, uint8_t* label,
                                   int32_t* path_xy, float* directions, int32_t* turns, int32_t* leg_ends, int32_t path_capacity,
                                   int32_t* path_len);
+/* ---- scene batch: memory (DESIGN.md section 11 "Scene batch: memory"): a memory per camera stream, carried in the batch ----------
+ * A yh_scene_batch holds a bank of YH_SCENE_STREAMS_MAX memories, each what a yh_scene holds ("scene memory" above: a map M u32
+ * [h][w] and a ball table B[100] of (x, y, count, age)), each empty after create and after a reset. yh_scene_batch_append_memory on
+ * slots 0 .. n_frames - 1 as staged is EXACTLY this: for b = 0 .. n_frames - 1 in order, a yh_scene_append_memory call on a yh_scene
+ * of the same size that holds the memory of streams[b], fed slot b's depth and packed frame, gather_q16[b], carry_q16[b], keep and
+ * ball_max_age. Frame b's map, world, connections0, connections1 and balls are that call's (yh_scene_batch_read), every stream named
+ * in the call ends in the state those calls leave, a stream not named is untouched, and batched calls on a stream continue each other
+ * from call to call. keep and ball_max_age are one value per call (properties of the robot, as turn_price is). The step itself is
+ * the one defined in the "scene memory" section; nothing about it is redefined here. Ball ids carry meaning across frames only as
+ * TRACK ids: the batched producer is yh_instance_track_batch, whose streams are these streams.
+ * Frames of different streams share launches; frames of one stream form a chain on the device: with R the most frames one stream has
+ * in the call, R + 5 launches, whatever n. It counts as a YH_COMPAT_SANE append of n_frames frames (earlier plans become unreadable,
+ * all four batched planners run on the fused frames; with targets_xy NULL a remembered ball inside the frame is a target by the
+ * usual rule, one outside the frame is not). yh_scene_batch_append and yh_scene_batch_set_fields leave the bank alone.
+ * Checks, for every frame before anything is touched: YH_EINVAL for a null handle or null motion arrays, n_frames outside
+ * 1 .. max_frames, keep outside 0 .. 256, ball_max_age outside 0 .. 255, a stream outside the bank (the text names the frame);
+ * YH_ESTATE, naming the slot, for a slot that was never staged. A refused call leaves frames, plans and every memory as they were; a
+ * call that fails later (YH_EHIP) leaves no frame and empties the memories of the streams it named. Asynchronous on the handle's
+ * stream; the caller's arrays are free again on return. The stamps' own array (4 bytes per pixel and frame) is allocated at the first
+ * memory append, a stream's two maps and two tables (8 bytes per pixel and stream: 157 MB for 64 streams at 640 x 480) at its first use. */
+#define YH_SCENE_STREAMS_MAX 64
+int yh_scene_batch_append_memory(yh_scene_batch* h, int32_t n_frames,
+                                 const int32_t* streams /* [n], each 0 .. YH_SCENE_STREAMS_MAX - 1, or NULL: all 0 */,
+                                 const int32_t* gather_q16 /* [n][6] */, const int32_t* carry_q16 /* [n][6] */,
+                                 int32_t keep, int32_t ball_max_age);
+/* The memory of one stream as the last call that named it left it, laid out as yh_scene_memory_read; either pointer may be NULL.
+ * Waits. Zeros for a stream never used or reset. YH_EINVAL for a stream outside the bank. */
+int yh_scene_batch_memory_read(yh_scene_batch* h, int32_t stream, uint32_t* map_mem, int32_t* balls_mem /* [100][4] */);
+/* The ball table of frame `frame`'s stream right after that frame of the last memory append. YH_ESTATE unless the current frames came
+ * from yh_scene_batch_append_memory, YH_EINVAL for a frame outside it. Waits. */
+int yh_scene_batch_memory_frame_balls(yh_scene_batch* h, int32_t frame, int32_t* balls_mem /* [100][4] */);
+/* Empties the memory of one stream, or of all (stream = -1); asynchronous on the handle's stream. The current frames and plans stay
+ * as they are. YH_EINVAL for a stream outside the bank. */
+int yh_scene_batch_memory_reset(yh_scene_batch* h, int32_t stream /* -1: all */);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

@@ -142,6 +142,12 @@ int yh_scene_turn_tour_time(yh_scene* h, int32_t reps, float* ms_per_tour, int32
 /* Measurement hook: mean device milliseconds per BATCH over `reps` re-runs of the last yh_scene_batch_append (its n_frames and
  * mode) from the staged slots as they are now. It counts as an append: an earlier plan becomes unreadable. */
 int yh_scene_batch_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch);
+/* The same for frames that came from yh_scene_batch_append_memory (yh_scene_batch_time refuses such frames with YH_ESTATE and names
+ * this function): the append's own slots, motions and streams, replayed from the state every stream it named was in before it - the
+ * bank keeps two maps and two tables per stream - into the state it left, so every field and every memory is rewritten with the same
+ * bits and nothing is committed. YH_ESTATE unless the current frames are a memory append's (a plain append, yh_scene_batch_set_fields,
+ * yh_scene_batch_memory_reset or a staged slot since ends that). */
+int yh_scene_batch_memory_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch);
 /* yh_scene_plan_time for the last yh_scene_batch_plan: milliseconds per batch; rounds = launches in which some tile of some frame
  * ran (those of the slowest frame), tile_runs summed over the frames. */
 int yh_scene_batch_plan_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);

@@ -10,12 +10,16 @@
 
 #include "scene.h"
 
+struct yh_scene_batch_memory;   // the bank of memories, one per camera stream (scene_batch_memory.hip); allocated at the first memory append
+
 struct yh_scene_batch {
     yh_scene core;                      // core.max_frames: the slots; core.batch is set
+    yh_scene_batch_memory* memory = nullptr;
     int n = 0;                          // frames of the last append (or the highest frame given to yh_scene_batch_set_fields + 1)
     int append_n = 0, append_mode = 0;  // the last append proper (yh_scene_batch_time replays it)
     bool from_fields = false;           // the current frames came through yh_scene_batch_set_fields
     std::vector<uint8_t> staged, fields_set, diag_ok;   // per slot / frame
+    uint64_t stagings = 0;              // stage calls so far: a replay of the staged slots knows whether they are still what it ran on
     std::vector<std::string> diag_why;
     int fail(int code, const std::string& m) { return core.fail(code, m); }
     // rc of a check of frame b, its text now naming the frame
@@ -26,3 +30,13 @@ struct yh_scene_batch {
         return YH_OK;
     }
 };
+
+namespace yh {
+// scene_batch.hip: the first two stages of n frames on the handle's stream - n frames of p.map and p.ball_acc cleared, every frame's
+// bumps stamped into its p.map, its ball means into its p.balls (the append's own first half; the memory append stamps into the
+// bank's array)
+int scene_batch_stamp(yh_scene_batch* hb, const SceneParams& p, int n);
+// scene_batch_memory.hip: the bank's buffers (yh_scene_batch_destroy); whether the current frames came from yh_scene_batch_append_memory
+void scene_batch_memory_free(yh_scene_batch* hb);
+bool scene_batch_memory_is_last(const yh_scene_batch* hb);
+}

@@ -4,7 +4,8 @@
 // b frames and runs the body the single handle's kernel runs (scene_dev.h) - there is no second definition of anything.
 //
 // Launches of one append of n frames: two memsets (maps, ball sums), batch_cloud_strips (strips x bands x n), batch_balls (n blocks),
-// batch_world, batch_conn1, batch_conn0 (8 x 8 pixels x n).
+// batch_world, batch_conn1, batch_conn0 (8 x 8 pixels x n). The first four are scene_batch_stamp, which the memory append
+// (scene_batch_memory.hip: a bank of memories, one per camera stream) runs as well, into its own array.
 //
 // The handle holds a yh_scene as its core: device, size, stream, error text, bump tables, the frame generation and mode - and array
 // pointers that are frame 0 of the batch's [max_frames][...] arrays. The planners hang off that core and are the single handle's:
@@ -41,6 +42,21 @@ __global__ __launch_bounds__(64) void batch_conn0(const SceneParams p) { conn0_b
 
 thread_local std::string g_batch_create_error;
 
+}  // namespace
+
+namespace yh {
+int scene_batch_stamp(yh_scene_batch* hb, const SceneParams& p, int n) {
+    yh_scene* h = &hb->core;
+    SCHK(h, hipMemsetAsync(p.map, 0, (size_t)n * p.W * p.H * 4, h->stream));
+    SCHK(h, hipMemsetAsync(p.ball_acc, 0, (size_t)n * 300 * sizeof(long long), h->stream));
+    hipLaunchKernelGGL(batch_cloud_strips, dim3((unsigned)((p.W + SC_CW - 1) / SC_CW), (unsigned)((p.H + p.band_h - 1) / p.band_h), (unsigned)n), dim3(512), 0, h->stream, p);
+    hipLaunchKernelGGL(batch_balls, dim3(1, 1, (unsigned)n), dim3(128), 0, h->stream, p);
+    return YH_OK;
+}
+}  // namespace yh
+
+namespace {
+
 int run_append(yh_scene_batch* hb, int n, int mode) {
     yh_scene* h = &hb->core;
     SceneParams p;
@@ -48,12 +64,9 @@ int run_append(yh_scene_batch* hb, int n, int mode) {
     p.W = h->W; p.H = h->H; p.mode = mode; p.band_h = h->band_h;
     p.terrain_tab = h->terrain_tab; p.robot_tab = h->robot_tab;
     p.map = h->map; p.world = h->world; p.conn0 = h->conn0; p.conn1 = h->conn1; p.ball_acc = h->ball_acc; p.balls = h->balls;
-    const size_t npx = (size_t)h->W * h->H;
-    SCHK(h, hipMemsetAsync(h->map, 0, n * npx * 4, h->stream));
-    SCHK(h, hipMemsetAsync(h->ball_acc, 0, (size_t)n * 300 * sizeof(long long), h->stream));
+    const int rc = scene_batch_stamp(hb, p, n);
+    if (rc) return rc;
     const dim3 grid((unsigned)((h->W + 7) / 8), (unsigned)((h->H + 7) / 8), (unsigned)n), block(8, 8);
-    hipLaunchKernelGGL(batch_cloud_strips, dim3((unsigned)((h->W + SC_CW - 1) / SC_CW), (unsigned)((h->H + h->band_h - 1) / h->band_h), (unsigned)n), dim3(512), 0, h->stream, p);
-    hipLaunchKernelGGL(batch_balls, dim3(1, 1, (unsigned)n), dim3(128), 0, h->stream, p);
     hipLaunchKernelGGL(batch_world, grid, block, 0, h->stream, p);
     hipLaunchKernelGGL(batch_conn1, grid, block, 0, h->stream, p);
     hipLaunchKernelGGL(batch_conn0, grid, block, 0, h->stream, p);
@@ -148,6 +161,7 @@ void yh_scene_batch_destroy(yh_scene_batch* hb) {
     scene_turn_free(h);
     scene_turn_tour_free(h);
     scene_solve_free(h);
+    scene_batch_memory_free(hb);
     void* bufs[] = { h->depth, h->frame, h->map, h->world, h->conn0, h->conn1, h->balls, h->ball_acc, h->terrain_tab, h->robot_tab };
     for (void* b : bufs) if (b) hipFree(b);
     if (h->copied) hipEventDestroy(h->copied);
@@ -161,6 +175,7 @@ int yh_scene_batch_stage(yh_scene_batch* hb, int32_t slot, const uint16_t* depth
     if (slot < 0 || slot >= h->max_frames) return h->fail(YH_EINVAL, "slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(h->max_frames - 1));
     SCHK(h, hipSetDevice(h->dev));
     const size_t npx = (size_t)h->W * h->H;
+    ++hb->stagings;
     SCHK(h, hipMemcpyAsync(h->depth + slot * npx, depth_host, npx * 2, hipMemcpyHostToDevice, h->stream));
     SCHK(h, hipMemcpyAsync(h->frame + slot * npx, frame, npx * 4, frame_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     const int rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame);
@@ -180,6 +195,7 @@ int yh_scene_batch_stage_frames(yh_scene_batch* hb, int32_t first_slot, int32_t 
         return h->fail(YH_EINVAL, "slots " + std::to_string(first_slot) + " .. " + std::to_string((long long)first_slot + n_frames - 1) + " outside 0 .. " + std::to_string(h->max_frames - 1));
     SCHK(h, hipSetDevice(h->dev));
     const size_t npx = (size_t)h->W * h->H;
+    ++hb->stagings;
     SCHK(h, hipMemcpyAsync(h->depth + first_slot * npx, depth_host, n_frames * npx * 2, hipMemcpyHostToDevice, h->stream));
     SCHK(h, hipMemcpyAsync(h->frame + first_slot * npx, frames, n_frames * npx * 4, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     const int rc = host_sources_done(h, depth_host, frames_on_device ? nullptr : frames);
@@ -220,6 +236,8 @@ int yh_scene_batch_read(yh_scene_batch* hb, int32_t frame, uint32_t* map, float*
 int yh_scene_batch_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch) {
     if (!hb || reps < 1 || !ms_per_batch) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (scene_batch_memory_is_last(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory: yh_scene_batch_memory_time replays them");
     if (hb->append_n < 1) return h->fail(YH_ESTATE, "no batch has been appended");
     SCHK(h, hipSetDevice(h->dev));
     struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;

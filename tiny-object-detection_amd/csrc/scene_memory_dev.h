@@ -10,7 +10,7 @@ namespace yh {
 struct SceneFuseParams {
     const uint32_t* stamp;      // N [H][W]: the frame's own bumps (scene_cloud_strips)
     const uint32_t* mem_prev;   // M [H][W]: the memory as the previous memory append left it
-    uint32_t* mem_next;         // F, the new memory: never one of the two above (neighbouring workgroups still read those)
+    uint32_t* mem_next;         // F, the new memory: never one of the two above (neighbouring workgroups still read those); null: not kept
     uint32_t* map;              // F again: the handle's map
     float4 *world, *conn0, *conn1;
     int W, H;
@@ -26,6 +26,22 @@ struct SceneBallsMemParams {
     int W, H;
     int c[6];                   // carry_q16: previous-map pixel -> current-map pixel
     int max_age;                // 0 .. 255
+};
+
+// The batch's device tables (scene_batch_memory.hip): what one grid z of a fuse round, one frame of a stream's ball chain and one
+// chain run on. A frame's arrays are the by-value parameter block's advanced by `frame` frames.
+struct SceneFuseSlot {
+    const uint32_t* mem_prev;   // the stream's bank map (its first frame in the call) or the predecessor's map slot
+    uint32_t* mem_next;         // the bank's other map for the stream's last frame in the call, else null
+    int frame;
+    int g[6];
+    int pad;
+};
+struct SceneBallsStep { int frame; int c[6]; int pad; };
+struct SceneBallsChain {
+    const int4* tab_prev;       // the stream's bank table
+    int4* tab_next;             // the bank's other table: the chain's last table again
+    int first, count;           // its steps, in batch order
 };
 
 // floor((a x + b y + c + 2^15) / 2^16) in 64 bits: |a x| < 2^31 * 2^20 for every x either body passes, so nothing overflows
@@ -95,7 +111,7 @@ __device__ __forceinline__ void fuse_body(const SceneFuseParams& p) {
         }
         const size_t i = (size_t)y * p.W + x;
         p.map[i] = fm;
-        p.mem_next[i] = fm;
+        if (p.mem_next) p.mem_next[i] = fm;   // (uniform: a frame of a batch that is not its stream's last keeps F in its map slot only)
         p.world[i] = make_float4(X, Hm, Y, 0.0f);
         p.conn0[i] = make_float4(v0[0], v0[1], v0[2], v0[3]);
         p.conn1[i] = make_float4(v1[0], v1[1], v1[2], v1[3]);

@@ -10,6 +10,7 @@ _LIB = None
 OK, EINVAL, EHIP, ENOMEM, EWEIGHTS, ESTATE, EDIVERGE, EOVERFLOW = 0, -1, -2, -3, -4, -5, -6, -7
 COMPAT_STRICT, COMPAT_SANE = 0, 1
 TOUR_MAX = 6   # YH_TOUR_MAX
+SCENE_STREAMS_MAX = 64   # YH_SCENE_STREAMS_MAX
 
 
 class YhError(RuntimeError):
@@ -179,6 +180,11 @@ SYMBOLS = [
     ("yh_scene_batch_time", _i, [_vp, _i, C.POINTER(_f)]),
     ("yh_scene_batch_plan_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_scene_batch_set_fields", _i, [_vp, _i, _vp, _vp, _vp]),
+    ("yh_scene_batch_append_memory", _i, [_vp, _i, _vp, _vp, _vp, _i, _i]),
+    ("yh_scene_batch_memory_read", _i, [_vp, _i, _vp, _vp]),
+    ("yh_scene_batch_memory_frame_balls", _i, [_vp, _i, _vp]),
+    ("yh_scene_batch_memory_reset", _i, [_vp, _i]),
+    ("yh_scene_batch_memory_time", _i, [_vp, _i, C.POINTER(_f)]),
     ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
@@ -1365,6 +1371,42 @@ class SceneBatch:
                                                   _p(out["path"]), _p(dirs), n.value, C.byref(n)))
         out["directions"] = dirs[:max(n.value - 1, 0)]
         return out
+
+    def append_memory(self, n, motions=None, streams=None, keep=224, ball_max_age=30):
+        """Slots 0 .. n - 1 as staged, fused into the memories of their camera streams (DESIGN.md §11 "Scene batch: memory"): frame b is
+        Scene.append_memory on the memory of streams[b] (0 .. SCENE_STREAMS_MAX - 1; None: all on stream 0), the calls made in batch
+        order. motions: n (gather_q16, carry_q16) pairs as scene_motion returns them; None: the identity for every frame. keep and
+        ball_max_age are one value per call."""
+        if motions is None:
+            motions = [(SCENE_IDENTITY_Q16, SCENE_IDENTITY_Q16)] * max(n, 0)
+        g = np.array([m[0] for m in motions], np.int32).reshape(-1, 6)   # (a value outside int32 raises here)
+        c = np.array([m[1] for m in motions], np.int32).reshape(-1, 6)
+        assert len(g) == len(c) == max(n, 0), "motions: one (gather, carry) pair per frame"
+        st = Engine._streams(streams, n)
+        self._chk(self.L.yh_scene_batch_append_memory(self.h, n, _p(st) if st is not None else None, _p(g), _p(c), keep, ball_max_age))
+        self.n, self._fields = n, False
+
+    def read_memory(self, stream=0):
+        """The memory of one stream: map u32 [h][w], balls i32 [100][4] = (x, y, count, age); zeros while empty."""
+        out = dict(map=np.zeros((self.H, self.W), np.uint32), balls=np.zeros((100, 4), np.int32))
+        self._chk(self.L.yh_scene_batch_memory_read(self.h, stream, _p(out["map"]), _p(out["balls"])))
+        return out
+
+    def read_frame_memory_balls(self, frame):
+        """The ball table of frame `frame`'s stream right after that frame of the last memory append: i32 [100][4]."""
+        out = np.zeros((100, 4), np.int32)
+        self._chk(self.L.yh_scene_batch_memory_frame_balls(self.h, frame, _p(out)))
+        return out
+
+    def memory_reset(self, stream=-1):
+        """Empties the memory of one stream; -1: of all."""
+        self._chk(self.L.yh_scene_batch_memory_reset(self.h, stream))
+
+    def memory_time(self, reps=20):
+        """Replays the last memory append from the state it started from (nothing is committed): ms per batch."""
+        ms = C.c_float()
+        self._chk(self.L.yh_scene_batch_memory_time(self.h, reps, C.byref(ms)))
+        return ms.value
 
     def time(self, reps=20):
         """Replays the last append: ms per batch."""

@@ -15,21 +15,27 @@ turn tour.
 --tour [--connectivity 8]: the batched plain tour instead (yh_scene_batch_plan_tour, DESIGN.md §11 "Scene batch: tours";
 yh_scene_batch_tour_time) beside the same frames through one Scene.plan_tour (yh_scene_tour_time per frame), to the first K of the same
 camera targets (--targets K, default 3) on the 4- or 8-connected grid, for n = 1, 2, 8, 16, 64; the host wall is then stage + append + tour.
+--memory: the memory append instead (yh_scene_batch_append_memory, DESIGN.md §11 "Scene batch: memory"; yh_scene_batch_memory_time),
+no plans: ms per frame in two columns - a stream per frame (frames share every launch) and every frame on stream 0 (a chain of n fuse
+launches) - beside the same frames through one Scene.append_memory (yh_scene_memory_time per frame), every memory filled before it is
+timed; then, for n = 8 on the robots + balls frame of tools/time_scene.py in every slot, the two ratios and the run-to-run spread of
+each side (what tests/test_scene_batch_memory.py derives its ceiling from).
 --frames n,n,..: those batch sizes only.
 --lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
 LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box.
-Usage: python tools/time_scene_batch.py [sets] [reps] [--turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
+Usage: python tools/time_scene_batch.py [sets] [reps] [--memory | --turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
 from yolact_amd import capi
-args, tau, tour, plain, conn_tour, K, sizes, lib = [], None, False, False, 4, 3, None, None
+args, tau, tour, plain, conn_tour, K, sizes, lib, memory = [], None, False, False, 4, 3, None, None, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--turn-price": tau = float(next(it))
     elif a == "--turn-tour": tour = True
     elif a == "--tour": plain = True
+    elif a == "--memory": memory = True
     elif a == "--connectivity": conn_tour = int(next(it))
     elif a == "--targets": K = int(next(it))
     elif a == "--frames": sizes = tuple(int(v) for v in next(it).split(","))
@@ -39,6 +45,7 @@ sets = int(args[0]) if len(args) > 0 else 5
 reps = int(args[1]) if len(args) > 1 else 20
 if tour and not tau: sys.exit("--turn-tour needs --turn-price P")
 if plain and tau: sys.exit("--tour is the plain tour: no --turn-price")
+if memory and (plain or tau): sys.exit("--memory times the append alone: no --tour, no --turn-price")
 if sizes is None: sizes = (1, 2, 8, 16, 64) if plain else (1, 2, 4, 8, 16, 64)
 own = tau or plain   # the plan columns are one kind of its own instead of the plan with connectivity 4 and 8
 if lib:
@@ -46,7 +53,7 @@ if lib:
 import yolact_amd as ya
 H, W = 480, 640
 TARGETS = [(70, 67), (515, 410), (320, 40), (600, 100), (30, 440), (250, 300)][:K]   # tools/time_tour.py's camera targets
-print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (", memory append" if memory else "") + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
 
 
 def frame(seed):
@@ -58,6 +65,52 @@ def frame(seed):
 
 med = lambda v: sorted(v)[len(v) // 2]
 sc = ya.Scene(W, H)
+
+
+def memory_columns(frames, motion):
+    """(single, a stream per frame, all on stream 0): lists over the sets of ms per frame for these frames, alternated set by set"""
+    n = len(frames)
+    sb = ya.SceneBatch(W, H, n)
+    sb.stage_frames(0, np.stack([d for d, _ in frames]), frames_u32=np.stack([f for _, f in frames]))
+
+    def single():
+        sc.memory_reset()
+        sc.append_memory(frames[-1][0], frame_u32=frames[-1][1], motion=motion)     # a filled memory: every timed frame fuses into one
+        t = 0.0
+        for d, f in frames:
+            sc.append_memory(d, frame_u32=f, motion=motion)
+            t += sc.memory_time(reps) / n
+        return t
+
+    def batch(streams):
+        sb.memory_reset()
+        for _ in range(2):                                                           # the replayed call fuses into filled memories
+            sb.append_memory(n, motions=[motion] * n, streams=streams)
+        return sb.memory_time(reps) / n
+
+    cols = ([], [], [])
+    single(); batch(list(range(n)) if n <= capi.SCENE_STREAMS_MAX else None); batch(None)   # warm-up: buffers, code objects
+    for _ in range(sets):
+        cols[0].append(single()); cols[1].append(batch(list(range(n)))); cols[2].append(batch(None))
+    sb.close()
+    return cols
+
+
+if memory:
+    motion = ya.scene_motion(3.0, -2.0, 0.05)           # tools/time_scene.py's: a small turn and a step
+    print("memory append, ms per frame (median of the sets):")
+    print(f"{'n':>4} {'single handle':>14} {'a stream per frame':>19} {'all on stream 0':>16}")
+    for n in sizes:
+        s, a, o = memory_columns([frame(b) for b in range(n)], motion)
+        print(f"{n:4d} {med(s):14.4f} {med(a):19.4f} {med(o):16.4f}")
+    s, a, o = memory_columns([frame(0)] * 8, motion)   # (slot 0's depth seed is that tool's)
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    print(f"n = 8, the robots + balls frame of tools/time_scene.py in every slot, {sets} sets alternated:")
+    print(f"  single handle          {med(s):.4f} ms per frame, spread (max - min) / median {100 * spread(s):.1f} %")
+    print(f"  a stream per frame     {med(a):.4f} ms per frame, spread {100 * spread(a):.1f} %, ratio to the single handle {med(a) / med(s):.3f}")
+    print(f"  all on stream 0        {med(o):.4f} ms per frame, spread {100 * spread(o):.1f} %, ratio to the single handle {med(o) / med(s):.3f}")
+    sc.close()
+    sys.exit(0)
 for n in sizes:
     frames = [frame(b) for b in range(n)]
     sb = ya.SceneBatch(W, H, n)
