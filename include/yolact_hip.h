@@ -593,7 +593,8 @@ int yh_scene_turn_tour_read(yh_scene* h, int32_t* n_targets, int32_t* targets_xy
  *           on the frame's balls. Every other entry is cleared, its balls[k] zeros.
  * Ball ids carry meaning from frame to frame only when they are TRACK ids (yh_instance_track's frames); the ids of
  * yh_instance_frame are per-frame detection indices, and a memory of those joins unrelated balls.
- * Any six int32 values are a valid motion (affine, not only rigid); where it comes from is the caller's business (odometry).
+ * Any six int32 values are a valid motion (affine, not only rigid); where it comes from is the caller's business (odometry; without it,
+ * yh_scene_append_memory_search below finds it).
  * It counts as a new frame (earlier plans become unreadable) in YH_COMPAT_SANE, and every planner runs on it as on any other.
  * With an empty memory, or keep = 0 and ball_max_age = 0, every output equals yh_scene_append_classified(.., YH_COMPAT_SANE)'s.
  * Asynchronous on the handle's stream; host buffers (depth, a host frame, the two motions) are free again on return.
@@ -607,6 +608,35 @@ int yh_scene_append_memory(yh_scene* h, const uint16_t* depth_host, const uint32
 int yh_scene_memory_read(yh_scene* h, uint32_t* map_mem, int32_t* balls_mem /* [100][4] */);
 /* Empties the memory (asynchronous on the handle's stream). The last frame's fields and plans stay as they are. */
 int yh_scene_memory_reset(yh_scene* h);
+/* ---- scene memory: registration (DESIGN.md section 11 "Scene memory: registration"): the motion found on the device -----------
+ * yh_scene_append_memory with the motion searched for instead of given: the frame's stamps N are scored against the memory M over
+ * candidate motions around a prior, the best is chosen on the device, and the append runs with it - no host wait in between.
+ *   candidates  n_rot (1 .. 16) base motions, gather_q16 [n_rot][6] and carry_q16 [n_rot][6], row 0 the prior (the others typically
+ *               the prior turned by a few steps either way about the robot's pixel), times the shifts -radius <= u, v <= radius
+ *               (radius 0 .. 8). Candidate (k, u, v)'s gather is base k with c += u 65536, f += v 65536 - its source pixel is base
+ *               k's plus (u, v) exactly -, its carry base k's (A, B, Cc, D, E, Ff) with Cc -= A u + B v, Ff -= D u + E v.
+ *   score       S(k, u, v) = sum over frame pixels (x, y) of min(N[y][x], Q), Q = M[sy + v][sx + u] inside the frame, else 0,
+ *               (sx, sy) the source pixel of (x, y) under base k's gather (the carry formula of yh_scene_append_memory); M unfaded.
+ *               Exact in 64 bits. sum_n = sum of N bounds every S.
+ *   choice      the largest S; ties go to the smaller u^2 + v^2, then the smaller k, then the smaller v, then the smaller u: an
+ *               empty memory, an empty frame or a featureless map choose the prior, (0, 0, 0).
+ * Then yh_scene_append_memory's steps run with the chosen candidate's twelve integers: every output and the memory equal what that
+ * call gives when handed them (yh_scene_motion_read returns them), and the call counts as a memory append in every respect. With
+ * n_rot = 1 and radius = 0 it IS yh_scene_append_memory with row 0. Integer only, bit-exact. Asynchronous on the handle's stream;
+ * host buffers are free again on return.
+ * YH_EINVAL with nothing touched, the memory included, for a null pointer, n_rot or radius out of range, keep or ball_max_age out
+ * of yh_scene_append_memory's ranges, or - checked in 64 bits, so that every candidate's coefficients are int32 - unless for every
+ * k: |c| + radius 65536 <= INT32_MAX and |f| + radius 65536 <= INT32_MAX on the gather, |Cc| + radius (|A| + |B|) <= INT32_MAX and
+ * |Ff| + radius (|D| + |E|) <= INT32_MAX on the carry. A call that fails later (YH_EHIP) leaves no frame and an empty memory. */
+int yh_scene_append_memory_search(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                  const int32_t* gather_q16 /* [n_rot][6] */, const int32_t* carry_q16 /* [n_rot][6] */, int32_t radius,
+                                  int32_t keep, int32_t ball_max_age);
+/* What the last yh_scene_append_memory_search chose: its gather and carry, chosen = (k, u, v), score = (S chosen, S of the prior
+ * (0, 0, 0), sum_n), and the whole table scores u64 [n_rot][2 radius + 1][2 radius + 1], indexed [k][v + radius][u + radius]. Any
+ * pointer may be NULL. Waits. YH_ESTATE unless the handle's last memory append was a search (a yh_scene_append_memory or a
+ * yh_scene_memory_reset since ends that; plain appends and plans do not). */
+int yh_scene_motion_read(yh_scene* h, int32_t* gather_q16 /* [6] */, int32_t* carry_q16 /* [6] */, int32_t* chosen /* [3] = k, u, v */,
+                         uint64_t* score /* [3] = S chosen, S prior, sum_n */, uint64_t* scores /* [n_rot][2R+1][2R+1] or NULL */);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

@@ -117,6 +117,18 @@ int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame);
  * append, so the re-runs rewrite the outputs and the memory with the same values and commit nothing. YH_ESTATE unless the
  * handle's last frame is a memory append (a plain append, yh_scene_set_fields or yh_scene_memory_reset since ends that). */
 int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame);
+/* The same for a frame that came from yh_scene_append_memory_search (yh_scene_time and yh_scene_memory_time refuse such a frame
+ * with YH_ESTATE and name this hook): the whole append - stamps, registration, ball memory, fuse - replayed from the state it
+ * started from, ms_per_frame; then its registration launches alone (the clear, the scores, the choice), ms_search. Both rewrite
+ * the same values and commit nothing. YH_ESTATE unless the handle's last frame is a search append. */
+int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search);
+/* Test hook: the registration kernels alone on two caller-given maps u32 [h][w] - n_host as the frame's stamps N, m_host as the
+ * memory M - with n_rot gathers [n_rot][6] and the radius as yh_scene_append_memory_search takes them (the same YH_EINVAL checks on
+ * the gathers; there are no carries). scores u64 [n_rot][2 radius + 1][2 radius + 1] as yh_scene_motion_read lays them out, chosen
+ * [3] = k, u, v, sum_n: each may be NULL. Waits. Reads and writes nothing of the handle's frame, memory or plans: it reaches values
+ * (up to 2^32 - 1) and shapes no depth frame produces. */
+int yh_scene_op_register(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
+                         int32_t radius, uint64_t* scores, int32_t* chosen /* [3] */, uint64_t* sum_n);
 /* Test hook: uploads host fields (height map u32 [h][w], connections0 / connections1 f32 [h][w][4], laid out as yh_scene_read
  * returns them) as if a YH_COMPAT_SANE frame had produced them, so that yh_scene_plan runs on constructed mazes. The planner reads
  * conn0[..][2] (right) and conn1[..][0] (down) and takes left / up from the neighbour, as SANE's symmetry allows: YH_EINVAL (nothing

@@ -8,6 +8,9 @@
 // N, the old M and the new M are three buffers: a workgroup's halo reads N and the old M of pixels whose F a neighbour is writing.
 // The two memory buffers (and the two ball tables) swap at every memory append, so the previous state survives the append:
 // yh_scene_memory_time replays the same launches on it and rewrites the same bits.
+// yh_scene_append_memory_search (DESIGN.md section 11 "Scene memory: registration") is the same append with the motion found on the
+// device: between the stamps and the fuse, scene_register.hip scores N against M over the caller's candidates and leaves the
+// chosen one in a device record, which the fuse and the ball carry read (scene_fuse_dev, scene_balls_memory_dev).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -16,6 +19,7 @@
 #include "scene.h"
 #include "scene_dev.h"
 #include "scene_memory_dev.h"
+#include "scene_register_dev.h"
 #include "yh_internal.h"
 
 using namespace yh;
@@ -35,6 +39,12 @@ struct yh_scene_memory {
     // while h->frames == frame (every append and yh_scene_set_fields counts h->frames up)
     uint64_t frame = 0;
     MemoryCall last;
+    // registration: allocated at the first search. searched: the last memory append was a search - last_bases are its candidates,
+    // reg_rec its choice, reg_acc its sum_n and score table
+    unsigned long long* reg_acc = nullptr;
+    SceneRegisterRecord* reg_rec = nullptr;
+    bool searched = false;
+    SceneRegisterBases last_bases = {};
 };
 
 namespace {
@@ -66,8 +76,16 @@ int memory_reserve(yh_scene* h) {
     return m->stale ? memory_clear(h, m) : YH_OK;
 }
 
+int register_reserve(yh_scene* h) {
+    yh_scene_memory* m = h->memory;
+    if (!m->reg_acc) SCHK(h, hipMalloc((void**)&m->reg_acc, scene_register_acc_bytes()));
+    if (!m->reg_rec) SCHK(h, hipMalloc((void**)&m->reg_rec, sizeof(SceneRegisterRecord)));
+    return YH_OK;
+}
+
 // the launches of one memory append: reads map[from] / tab[from], writes map[from ^ 1] / tab[from ^ 1] and the handle's fields
-int run_memory(yh_scene* h, const MemoryCall& q, int from) {
+// (bases given: the motion is searched for around them and read from the device record, q.g and q.c are not used)
+int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr) {
     yh_scene_memory* m = h->memory;
     SceneParams p;
     p.depth = h->depth; p.cls_id = nullptr; p.frame = q.frame; p.frame_mode = 1;
@@ -84,25 +102,73 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from) {
     f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
     f.W = h->W; f.H = h->H; f.keep = q.keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = q.c[i]; f.g[i] = q.g[i]; }
+    if (bases) {
+        const int rs = scene_register_search(h, m->stamp, m->map[from], *bases, m->reg_acc, m->reg_rec);
+        return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
+    }
     hipLaunchKernelGGL(scene_balls_memory, dim3(1), dim3(128), 0, h->stream, b);
     hipLaunchKernelGGL(scene_fuse, dim3((unsigned)((h->W + SF_TW - 1) / SF_TW), (unsigned)((h->H + SF_TH - 1) / SF_TH)), dim3(256), 0, h->stream, f);
     SCHK(h, hipGetLastError());
     return YH_OK;
 }
 
-int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q) {
+int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q, const SceneRegisterBases* bases = nullptr) {
     SCHK(h, hipSetDevice(h->dev));
     int rc = memory_reserve(h);
     if (rc) return rc;
+    if (bases && (rc = register_reserve(h))) return rc;
     const size_t npx = (size_t)h->W * h->H;
     SCHK(h, hipMemcpyAsync(h->depth, depth_host, npx * 2, hipMemcpyHostToDevice, h->stream));
     q.frame = frame;
     if (!frame_on_device) { SCHK(h, hipMemcpyAsync(h->frame, frame, npx * 4, hipMemcpyHostToDevice, h->stream)); q.frame = h->frame; }
     if ((rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame))) return rc;
     yh_scene_memory* m = h->memory;
-    if ((rc = run_memory(h, q, m->cur))) return rc;
+    if ((rc = run_memory(h, q, m->cur, bases))) return rc;
     m->cur ^= 1;
     m->last = q;
+    m->searched = bases != nullptr;
+    if (bases) m->last_bases = *bases;
+    return YH_OK;
+}
+
+// what both memory appends do around append_memory: the frame count, and what a failure or a success leaves
+int append_memory_call(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, const MemoryCall& q, const SceneRegisterBases* bases) {
+    ++h->frames;   // (earlier plans are of another frame, whatever becomes of this one)
+    const int rc = append_memory(h, depth_host, frame, frame_on_device, q, bases);
+    yh_scene_memory* m = h->memory;
+    if (rc) {
+        // a call that fails after its checks leaves no frame and an empty memory
+        h->ran = false;
+        if (m) { m->stale = true; m->frame = 0; m->searched = false; }
+        return rc;
+    }
+    m->frame = h->frames;
+    h->ran = true;
+    h->last_cls = nullptr; h->last_frame = m->last.frame; h->last_frame_mode = 1; h->last_mode = YH_COMPAT_SANE;
+    h->diag_ok = true; h->diag_why.clear();   // (F is a height map like any other: both ends of a diagonal hold the same length)
+    return YH_OK;
+}
+
+// `reps` replays of the last memory append from the state it started from, between two events; with search_only, of its
+// registration launches alone (the stamps the last replay left are the frame's)
+int replay_time(yh_scene* h, int reps, bool search_only, float* ms_out) {
+    yh_scene_memory* m = h->memory;
+    hipEvent_t a, b;
+    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
+    SCHK(h, hipEventRecord(a, h->stream));
+    // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
+    // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
+    for (int r = 0; r < reps; ++r) {
+        const int rc = search_only ? scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec)
+                                   : run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr);
+        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; m->searched = false; return rc; }
+    }
+    SCHK(h, hipEventRecord(b, h->stream));
+    SCHK(h, hipEventSynchronize(b));
+    float ms = 0;
+    hipEventElapsedTime(&ms, a, b);
+    hipEventDestroy(a); hipEventDestroy(b);
+    *ms_out = ms / reps;
     return YH_OK;
 }
 
@@ -112,13 +178,14 @@ namespace yh {
 void scene_memory_free(yh_scene* h) {
     yh_scene_memory* m = h->memory;
     if (!m) return;
-    void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1] };
+    void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1], m->reg_acc, m->reg_rec };
     for (void* b : bufs) if (b) hipFree(b);
     delete m;
     h->memory = nullptr;
 }
 
 bool scene_memory_is_last(const yh_scene* h) { return h->memory && h->memory->frame != 0 && h->memory->frame == h->frames; }
+bool scene_memory_is_search(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->searched; }
 }  // namespace yh
 
 extern "C" {
@@ -131,19 +198,37 @@ int yh_scene_append_memory(yh_scene* h, const uint16_t* depth_host, const uint32
     MemoryCall q;
     for (int i = 0; i < 6; ++i) { q.g[i] = gather_q16[i]; q.c[i] = carry_q16[i]; }
     q.keep = keep; q.max_age = ball_max_age;
-    ++h->frames;   // (earlier plans are of another frame, whatever becomes of this one)
-    const int rc = append_memory(h, depth_host, frame, frame_on_device, q);
+    return append_memory_call(h, depth_host, frame, frame_on_device, q, nullptr);
+}
+
+int yh_scene_append_memory_search(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                  const int32_t* gather_q16, const int32_t* carry_q16, int32_t radius, int32_t keep, int32_t ball_max_age) {
+    if (!h || !depth_host || !frame || !gather_q16 || !carry_q16) return YH_EINVAL;
+    const int rc = scene_register_bases_check(h, n_rot, gather_q16, carry_q16, radius);
+    if (rc) return rc;
+    if (keep < 0 || keep > 256) return h->fail(YH_EINVAL, "keep outside 0 .. 256");
+    if (ball_max_age < 0 || ball_max_age > 255) return h->fail(YH_EINVAL, "ball_max_age outside 0 .. 255");
+    SceneRegisterBases bases = {};
+    bases.n_rot = n_rot; bases.radius = radius;
+    for (int k = 0; k < n_rot; ++k)
+        for (int i = 0; i < 6; ++i) { bases.g[k][i] = gather_q16[6 * k + i]; bases.c[k][i] = carry_q16[6 * k + i]; }
+    MemoryCall q;   // (its motion stays zero: the kernels read the chosen one from the device record)
+    q.keep = keep; q.max_age = ball_max_age;
+    return append_memory_call(h, depth_host, frame, frame_on_device, q, &bases);
+}
+
+int yh_scene_motion_read(yh_scene* h, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
+    if (!h) return YH_EINVAL;
     yh_scene_memory* m = h->memory;
-    if (rc) {
-        // a call that fails after its checks leaves no frame and an empty memory
-        h->ran = false;
-        if (m) { m->stale = true; m->frame = 0; }
-        return rc;
-    }
-    m->frame = h->frames;
-    h->ran = true;
-    h->last_cls = nullptr; h->last_frame = m->last.frame; h->last_frame_mode = 1; h->last_mode = YH_COMPAT_SANE;
-    h->diag_ok = true; h->diag_why.clear();   // (F is a height map like any other: both ends of a diagonal hold the same length)
+    if (!m || m->stale || !m->searched) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    SceneRegisterRecord rec;
+    const int nu = 2 * m->last_bases.radius + 1;
+    SCHK(h, hipMemcpyAsync(&rec, m->reg_rec, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
+    if (scores) SCHK(h, hipMemcpyAsync(scores, m->reg_acc + 1, (size_t)m->last_bases.n_rot * nu * nu * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 6; ++i) { if (gather_q16) gather_q16[i] = rec.g[i]; if (carry_q16) carry_q16[i] = rec.c[i]; }
+    for (int i = 0; i < 3; ++i) { if (chosen) chosen[i] = rec.chosen[i]; if (score) score[i] = rec.score[i]; }
     return YH_OK;
 }
 
@@ -172,30 +257,25 @@ int yh_scene_memory_reset(yh_scene* h) {
     SCHK(h, hipSetDevice(h->dev));
     m->stale = true;   // (should the clearing fail, it is made again before the next use)
     m->frame = 0;      // (nothing to replay: the state the last memory append started from is gone)
+    m->searched = false;
     return memory_reserve(h);
 }
 
 int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!scene_memory_is_last(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory (or the memory was reset since)");
+    if (h->memory->searched) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");
     SCHK(h, hipSetDevice(h->dev));
-    yh_scene_memory* m = h->memory;
-    hipEvent_t a, b;
-    SCHK(h, hipEventCreate(&a)); SCHK(h, hipEventCreate(&b));
-    SCHK(h, hipEventRecord(a, h->stream));
-    // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
-    // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
-    for (int r = 0; r < reps; ++r) {
-        const int rc = run_memory(h, m->last, m->cur ^ 1);
-        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; return rc; }
-    }
-    SCHK(h, hipEventRecord(b, h->stream));
-    SCHK(h, hipEventSynchronize(b));
-    float ms = 0;
-    hipEventElapsedTime(&ms, a, b);
-    hipEventDestroy(a); hipEventDestroy(b);
-    *ms_per_frame = ms / reps;
-    return YH_OK;
+    return replay_time(h, reps, false, ms_per_frame);
+}
+
+int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
+    if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (!scene_memory_is_search(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // the whole append first, then its registration launches alone on what that left: the same record and scores again
+    const int rc = replay_time(h, reps, false, ms_per_frame);
+    return rc ? rc : replay_time(h, reps, true, ms_search);
 }
 
 }  // extern "C"

@@ -168,6 +168,10 @@ SYMBOLS = [
     ("yh_scene_memory_read", _i, [_vp, _vp, _vp]),
     ("yh_scene_memory_reset", _i, [_vp]),
     ("yh_scene_memory_time", _i, [_vp, _i, C.POINTER(_f)]),
+    ("yh_scene_append_memory_search", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i]),
+    ("yh_scene_motion_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_memory_search_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_op_register", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
@@ -1017,6 +1021,16 @@ def scene_motion(dx=0.0, dy=0.0, dtheta=0.0, pivot=None, size=(640, 480)):
     return q(gather), q(carry)
 
 
+def scene_motion_candidates(prior=(0.0, 0.0, 0.0), dtheta_step=0.01, n_side=2, pivot=None, size=(640, 480)):
+    """(gathers, carries) for Scene.append_memory_search: 2 n_side + 1 rows of six ints each, built with scene_motion. Row 0 is the
+    prior (dx, dy, dtheta); rows 1, 2, 3, 4, .. turn it by +1, -1, +2, -2, .. steps of dtheta_step about the pivot. A convenience:
+    any rows that pass the call's int32 conditions are valid candidates."""
+    dx, dy, dtheta = prior
+    steps = [0] + [s * j for j in range(1, n_side + 1) for s in (1, -1)]
+    rows = [scene_motion(dx, dy, dtheta + s * dtheta_step, pivot, size) for s in steps]
+    return [g for g, _ in rows], [c for _, c in rows]
+
+
 SCENE_IDENTITY_Q16 = (65536, 0, 0, 0, 65536, 0)
 
 
@@ -1100,6 +1114,56 @@ class Scene:
         ms = C.c_float()
         self._chk(self.L.yh_scene_memory_time(self.h, reps, C.byref(ms)))
         return ms.value
+
+    def append_memory_search(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, candidates=None, radius=4, keep=224, ball_max_age=30):
+        """append_memory with the motion found on the device (DESIGN.md §11 "Scene memory: registration"): candidates =
+        (gathers, carries), n_rot rows of six ints each, row 0 the prior (scene_motion_candidates); None: the identity alone. Every
+        row is tried with every whole-pixel shift of up to `radius` (0 .. 8) either way; read_motion tells which won."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        g, c = ([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16]) if candidates is None else candidates
+        g, c = np.ascontiguousarray(np.array(g, np.int32)), np.ascontiguousarray(np.array(c, np.int32))   # (a value outside int32 raises here)
+        assert g.ndim == 2 and g.shape[1] == 6 and c.shape == g.shape
+        if frame_dev_ptr is not None:
+            self._chk(self.L.yh_scene_append_memory_search(self.h, _p(depth), C.c_void_p(frame_dev_ptr), 1, len(g), _p(g), _p(c), radius, keep, ball_max_age))
+            self._search = (len(g), radius)
+            return
+        f = SceneBatch.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+        assert f.size == self.W * self.H
+        self._chk(self.L.yh_scene_append_memory_search(self.h, _p(depth), _p(f), 0, len(g), _p(g), _p(c), radius, keep, ball_max_age))
+        self._search = (len(g), radius)
+
+    def read_motion(self, scores=False):
+        """What the last append_memory_search chose: gather and carry i32 [6], chosen = (k, u, v), score u64 [3] = (S chosen, S of the
+        prior, sum_n) and, if asked for, scores u64 [n_rot][2 radius + 1][2 radius + 1], indexed [k][v + radius][u + radius]."""
+        out = dict(gather=np.zeros(6, np.int32), carry=np.zeros(6, np.int32), chosen=np.zeros(3, np.int32), score=np.zeros(3, np.uint64))
+        table = None
+        if scores and getattr(self, "_search", None):
+            n_rot, radius = self._search
+            table = np.zeros((n_rot, 2 * radius + 1, 2 * radius + 1), np.uint64)
+        self._chk(self.L.yh_scene_motion_read(self.h, _p(out["gather"]), _p(out["carry"]), _p(out["chosen"]), _p(out["score"]), _p(table) if table is not None else None))
+        if scores:
+            out["scores"] = table
+        return out
+
+    def op_register(self, n, m, gathers, radius):
+        """Test hook (yh_scene_op_register): the registration kernels alone on stamps n and memory m, u32 [h][w]; gathers [n_rot][6].
+        Returns (scores u64 [n_rot][2 radius + 1][2 radius + 1], chosen (k, u, v), sum_n); commits nothing."""
+        n, m = np.ascontiguousarray(n, np.uint32), np.ascontiguousarray(m, np.uint32)
+        assert n.shape == (self.H, self.W) and m.shape == (self.H, self.W)
+        g = np.ascontiguousarray(np.array(gathers, np.int32))
+        assert g.ndim == 2 and g.shape[1] == 6
+        ok = 1 <= len(g) <= 16 and 0 <= radius <= 8   # (otherwise the library refuses before it writes anything)
+        scores = np.zeros((len(g), 2 * radius + 1, 2 * radius + 1) if ok else (1,), np.uint64)
+        chosen, sum_n = np.zeros(3, np.int32), C.c_uint64()
+        self._chk(self.L.yh_scene_op_register(self.h, _p(n), _p(m), len(g), _p(g), radius, _p(scores), _p(chosen), C.byref(sum_n)))
+        return scores, tuple(int(v) for v in chosen), sum_n.value
+
+    def memory_search_time(self, reps=20):
+        """(ms per frame, ms of the registration alone) of the last append_memory_search, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_memory_search_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
 
     def plan(self, targets=None, n_targets=3, start=None, connectivity=4):
         """modify_path (src/path.rs:25-120) on the last appended frame. targets: (x, y) pixels, or None: the first n_targets balls

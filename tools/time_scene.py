@@ -1,7 +1,10 @@
 """The scene back-end (yh_scene_*: shaders/pt_cloud.comp + pt_cloud_weights.comp as HIP kernels) on one 640x480 frame:
 device milliseconds per frame (five launches), for a terrain-only frame and one with robots and balls.
 --memory: the memory append (yh_scene_append_memory: stamps, ball memory and ONE fuse launch) against the plain append on the same
-frames, in one process: the two alternated, one warm-up each, the median of five runs of 30 frames, and the spread of each."""
+frames, in one process: the two alternated, one warm-up each, the median of five runs of 30 frames, and the spread of each.
+--memory-search: the search append (yh_scene_append_memory_search: the same with the registration between the stamps and the fuse)
+against the memory append, likewise, over (n_rot, radius) = (1, 0), (1, 4), (5, 4), (9, 8): ms per frame of both, ms of the
+registration launches alone, and its rate in pixel-candidates per second."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,8 +42,44 @@ def memory_table(runs=5, reps=30):
     return rows
 
 
+SEARCH_GRIDS = ((1, 0), (1, 4), (5, 4), (9, 8))
+
+
+def memory_search_table(grids=SEARCH_GRIDS, runs=5, reps=30):
+    """rows of (frame, n_rot, radius, median ms memory, median ms search append, ratio, median ms of the registration alone,
+    pixel-candidates per second, (max - min) / median of memory, of the search append)"""
+    mem, srch = ya.Scene(W, H), ya.Scene(W, H)
+    prior = (3.0, -2.0, 0.05)                            # memory_table's motion: the prior is right, the search confirms it
+    motion = ya.scene_motion(*prior)
+    rows = []
+    for name, ci in frames():
+        for n_rot, radius in grids:
+            cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
+            for sc in (mem, srch):
+                sc.memory_reset()
+                sc.append_memory(depth, cls_id=ci, motion=motion)
+            mem.append_memory(depth, cls_id=ci, motion=motion)
+            srch.append_memory_search(depth, cls_id=ci, candidates=cands, radius=radius)
+            mem.memory_time(reps); srch.memory_search_time(reps)
+            tm, ts, tr = [], [], []
+            for _ in range(runs):
+                tm.append(mem.memory_time(reps))
+                a, b = srch.memory_search_time(reps)
+                ts.append(a); tr.append(b)
+            mm, ms, mr = float(np.median(tm)), float(np.median(ts)), float(np.median(tr))
+            rate = W * H * n_rot * (2 * radius + 1) ** 2 / (mr * 1e-3)
+            rows.append((name, n_rot, radius, mm, ms, ms / mm, mr, rate, (max(tm) - min(tm)) / mm, (max(ts) - min(ts)) / ms))
+    mem.close(); srch.close()
+    return rows
+
+
 if __name__ == "__main__":
-    if "--memory" in sys.argv[1:]:
+    if "--memory-search" in sys.argv[1:]:
+        print(f"scene {W}x{H}: memory append (yh_scene_memory_time) against search append (yh_scene_memory_search_time), ms per frame, median of 5 x 30 frames")
+        print(f"{'frame':<16} {'n_rot':>5} {'R':>2} {'memory':>8} {'search':>8} {'ratio':>7} {'alone':>8} {'Gpx-cand/s':>11} {'spread memory':>14} {'spread search':>14}")
+        for name, n_rot, radius, mm, ms, ratio, mr, rate, sm, ss in memory_search_table():
+            print(f"{name:<16} {n_rot:5d} {radius:2d} {mm:8.4f} {ms:8.4f} {ratio:7.3f} {mr:8.4f} {rate / 1e9:11.2f} {100 * sm:13.1f}% {100 * ss:13.1f}%")
+    elif "--memory" in sys.argv[1:]:
         print(f"scene {W}x{H}: plain append (yh_scene_time) against memory append (yh_scene_memory_time), ms per frame, median of 5 x 30 frames")
         print(f"{'frame':<16} {'plain':>8} {'memory':>8} {'ratio':>7} {'spread plain':>13} {'spread memory':>14}")
         for name, mp, mm, ratio, sp, sm in memory_table():
