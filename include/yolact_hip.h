@@ -786,6 +786,31 @@ int yh_scene_batch_memory_frame_balls(yh_scene_batch* h, int32_t frame, int32_t*
 /* Empties the memory of one stream, or of all (stream = -1); asynchronous on the handle's stream. The current frames and plans stay
  * as they are. YH_EINVAL for a stream outside the bank. */
 int yh_scene_batch_memory_reset(yh_scene_batch* h, int32_t stream /* -1: all */);
+/* ---- scene batch: registration (DESIGN.md section 11 "Scene batch: registration"): each stream's motion found on the device -----
+ * yh_scene_batch_append_memory with every frame's motion searched for instead of given. On slots 0 .. n_frames - 1 as staged it is
+ * EXACTLY this: for b = 0 .. n_frames - 1 in order, a yh_scene_append_memory_search call on a yh_scene of the same size that holds
+ * the memory of streams[b], fed slot b's depth and packed frame, the n_rot bases of row b (gather_q16[b], carry_q16[b]), radius, keep
+ * and ball_max_age. Frame b's five outputs, its ball table (yh_scene_batch_memory_frame_balls), every named stream's final memory,
+ * and frame b's chosen (k, u, v), twelve coefficients, three scores and whole score table (yh_scene_batch_motion_read) are that
+ * call's, bit for bit. So frame r of a stream is scored against the memory frame r - 1 of that stream has just fused, on the device:
+ * with R the most frames one stream has in the call, 3 R + 6 launches, whatever n, and no host wait. n_rot, radius, keep and
+ * ball_max_age are one value per call. Candidates, score, tie rule and int32 conditions are those of the "scene memory:
+ * registration" section; nothing is redefined here. With n_rot = 1 and radius = 0 it IS yh_scene_batch_append_memory with the same
+ * motions. It counts as a memory append of n_frames frames in every respect (earlier plans become unreadable, all four batched
+ * planners run on the fused frames, yh_scene_batch_memory_read, _memory_frame_balls and _memory_reset work as after it).
+ * Checks, for every frame before anything is touched: every check of yh_scene_batch_append_memory; YH_EINVAL for n_rot outside
+ * 1 .. 16 or radius outside 0 .. 8, and unless the four int32 conditions hold for every frame and base (the text names both). A
+ * refused call leaves frames, plans, memories and the last readable motions as they were; a call that fails later behaves as
+ * yh_scene_batch_append_memory does. Asynchronous on the handle's stream; the caller's arrays are free again on return. The score
+ * tables and records (max_frames x (37000 + 88) bytes: 9.5 MB for 256 frames) are allocated at the first batched search. */
+int yh_scene_batch_append_memory_search(yh_scene_batch* h, int32_t n_frames, const int32_t* streams /* [n] or NULL */,
+                                        int32_t n_rot, const int32_t* gather_q16 /* [n][n_rot][6] */,
+                                        const int32_t* carry_q16 /* [n][n_rot][6] */, int32_t radius,
+                                        int32_t keep, int32_t ball_max_age);
+/* What the last yh_scene_batch_append_memory_search chose for frame `frame`, laid out as yh_scene_motion_read; any pointer may be
+ * NULL. Waits. YH_ESTATE unless the current frames came from a batched search append, YH_EINVAL for a frame outside it. */
+int yh_scene_batch_motion_read(yh_scene_batch* h, int32_t frame, int32_t* gather_q16, int32_t* carry_q16,
+                               int32_t* chosen, uint64_t* score, uint64_t* scores);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

@@ -39,4 +39,5 @@ int scene_batch_stamp(yh_scene_batch* hb, const SceneParams& p, int n);
 // scene_batch_memory.hip: the bank's buffers (yh_scene_batch_destroy); whether the current frames came from yh_scene_batch_append_memory
 void scene_batch_memory_free(yh_scene_batch* hb);
 bool scene_batch_memory_is_last(const yh_scene_batch* hb);
+bool scene_batch_memory_is_search(const yh_scene_batch* hb);   // .. from yh_scene_batch_append_memory_search
 }

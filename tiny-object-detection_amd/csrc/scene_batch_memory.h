@@ -1,0 +1,61 @@
+// scene_batch_memory.h — the state of the scene batch's bank of memories (scene_batch_memory.hip), for the two units that run on it:
+// the memory append itself and its registration (scene_batch_register.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "scene_batch.h"
+#include "scene_memory_dev.h"
+#include "scene_register_dev.h"
+
+namespace yh {
+
+struct BankStream {
+    uint32_t* map[2] = { nullptr, nullptr };   // M [H][W]: map[cur] is the memory, map[cur ^ 1] what it was before the last call that named the stream
+    int4* tab[2] = { nullptr, nullptr };       // B [100], likewise
+    int cur = 0;
+    bool stale = true;                         // cleared before the next use: fresh buffers, a reset, or a call that failed half-way
+};
+
+}  // namespace yh
+
+struct yh_scene_batch_memory {
+    uint32_t* stamp = nullptr;    // N [max_frames][H][W]
+    int4* tabs = nullptr;         // [max_frames][100]: every frame's table right after it
+    // device: SceneFuseSlot [max_frames], SceneBallsStep [max_frames], SceneBallsChain [YH_SCENE_STREAMS_MAX] and, from the first
+    // search on, SceneRegisterBases [max_frames]
+    unsigned char* table = nullptr;
+    size_t table_bytes = 0;
+    std::vector<unsigned char> table_host;
+    yh::BankStream bank[YH_SCENE_STREAMS_MAX];
+    // the last memory append, for yh_scene_batch_memory_time: the handle's frames are that append's while core.frames == frame
+    // (every append and yh_scene_batch_set_fields counts core.frames up); a reset or a staged slot since leaves nothing to replay
+    uint64_t frame = 0, stagings = 0;
+    bool replayable = false;
+    int n = 0, keep = 0, max_age = 0, chains = 0;
+    std::vector<int> round_off;   // slots of round r: round_off[r] .. round_off[r + 1]
+    // registration, allocated at the first search: frame b's sum_n and score table at reg_acc + b * acc_stride (the stride is the
+    // call's: 1 + n_rot (2 radius + 1)^2 words), its record at reg_rec + b. searched: the last memory append was a search.
+    unsigned long long* reg_acc = nullptr;    // [max_frames][1 + SR_MAX_ROT * SR_MAX_NU^2]
+    yh::SceneRegisterRecord* reg_rec = nullptr;   // [max_frames]
+    bool searched = false;
+    int n_rot = 0, radius = 0;
+    size_t acc_stride() const { return 1 + (size_t)n_rot * (2 * radius + 1) * (2 * radius + 1); }
+};
+
+namespace yh {
+// the layout of the device table
+inline size_t scene_batch_slots_bytes(const yh_scene* h) { return (size_t)h->max_frames * sizeof(SceneFuseSlot); }
+inline size_t scene_batch_steps_bytes(const yh_scene* h) { return (size_t)h->max_frames * sizeof(SceneBallsStep); }
+inline size_t scene_batch_bases_offset(const yh_scene* h) { return scene_batch_slots_bytes(h) + scene_batch_steps_bytes(h) + YH_SCENE_STREAMS_MAX * sizeof(SceneBallsChain); }
+
+// scene_batch_register.hip, on the handle's stream (its device current), from the device table and the schedule of the last
+// scheduled search append. reserve: the score tables and the records. search: the clear, then per round the scores and the choice
+// and, with `f` given, the fuse of that round with each frame's motion read from its record (without: the registration launches
+// alone, on the map slots an earlier run left). balls: the ball chains with each step's carry read from its frame's record.
+int scene_batch_register_reserve(yh_scene_batch* hb);
+int scene_batch_register_search(yh_scene_batch* hb, const SceneFuseParams* f);
+int scene_batch_register_balls(yh_scene_batch* hb, const SceneBallsMemParams& b);
+}

@@ -14,6 +14,10 @@
 // R + 5 launches against 6 n frame by frame. The bank keeps two maps and two tables per stream (allocated at the stream's first use)
 // which swap at every call that names the stream: the state a call started from survives it, and yh_scene_batch_memory_time replays
 // the same launches from it and rewrites the same bits.
+// yh_scene_batch_append_memory_search (DESIGN.md section 11 "Scene batch: registration") is the same append with every frame's
+// motion found on the device: the same schedule, its slots and steps without motions and the frames' bases behind the chains in the
+// one upload; each round's fuse is preceded by the round's scores and choice, and the ball chains run last, on the records
+// (scene_batch_register.hip). The bank's state is in scene_batch_memory.h for both units.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -23,36 +27,12 @@
 
 #include "scene.h"
 #include "scene_batch.h"
+#include "scene_batch_memory.h"
 #include "scene_dev.h"
 #include "scene_memory_dev.h"
 #include "yh_internal.h"
 
 using namespace yh;
-
-namespace {
-
-struct BankStream {
-    uint32_t* map[2] = { nullptr, nullptr };   // M [H][W]: map[cur] is the memory, map[cur ^ 1] what it was before the last call that named the stream
-    int4* tab[2] = { nullptr, nullptr };       // B [100], likewise
-    int cur = 0;
-    bool stale = true;                         // cleared before the next use: fresh buffers, a reset, or a call that failed half-way
-};
-
-}  // namespace
-
-struct yh_scene_batch_memory {
-    uint32_t* stamp = nullptr;    // N [max_frames][H][W]
-    int4* tabs = nullptr;         // [max_frames][100]: every frame's table right after it
-    unsigned char* table = nullptr;   // device: SceneFuseSlot [max_frames], SceneBallsStep [max_frames], SceneBallsChain [YH_SCENE_STREAMS_MAX]
-    std::vector<unsigned char> table_host;
-    BankStream bank[YH_SCENE_STREAMS_MAX];
-    // the last memory append, for yh_scene_batch_memory_time: the handle's frames are that append's while core.frames == frame
-    // (every append and yh_scene_batch_set_fields counts core.frames up); a reset or a staged slot since leaves nothing to replay
-    uint64_t frame = 0, stagings = 0;
-    bool replayable = false;
-    int n = 0, keep = 0, max_age = 0, chains = 0;
-    std::vector<int> round_off;   // slots of round r: round_off[r] .. round_off[r + 1]
-};
 
 namespace {
 
@@ -84,19 +64,31 @@ __global__ __launch_bounds__(128) void batch_balls_memory(const SceneBallsMemPar
     if (threadIdx.x < 100) ch.tab_next[threadIdx.x] = prev[threadIdx.x];
 }
 
-size_t slots_bytes(const yh_scene* h) { return (size_t)h->max_frames * sizeof(SceneFuseSlot); }
-size_t steps_bytes(const yh_scene* h) { return (size_t)h->max_frames * sizeof(SceneBallsStep); }
+size_t slots_bytes(const yh_scene* h) { return scene_batch_slots_bytes(h); }
+size_t steps_bytes(const yh_scene* h) { return scene_batch_steps_bytes(h); }
 
 // the buffers every memory append uses, at the first one: a batch that never remembers pays nothing
-int memory_reserve(yh_scene_batch* hb) {
+// (a search: the score tables and records too, and the device table grows by the frames' bases - the stream is drained before
+// the smaller one goes, and whoever fails after this leaves nothing to replay)
+int memory_reserve(yh_scene_batch* hb, bool search) {
     yh_scene* h = &hb->core;
     if (!hb->memory) hb->memory = new yh_scene_batch_memory();
     yh_scene_batch_memory* m = hb->memory;
     const size_t all = (size_t)h->max_frames * h->W * h->H;
     if (!m->stamp) SCHK(h, hipMalloc((void**)&m->stamp, all * 4));
     if (!m->tabs) SCHK(h, hipMalloc((void**)&m->tabs, (size_t)h->max_frames * 100 * sizeof(int4)));
-    if (!m->table) SCHK(h, hipMalloc((void**)&m->table, slots_bytes(h) + steps_bytes(h) + YH_SCENE_STREAMS_MAX * sizeof(SceneBallsChain)));
-    return YH_OK;
+    const size_t need = scene_batch_bases_offset(h) + (search ? (size_t)h->max_frames * sizeof(SceneRegisterBases) : 0);
+    if (m->table_bytes < need) {
+        if (m->table) {
+            SCHK(h, hipStreamSynchronize(h->stream));
+            unsigned char* old = m->table;
+            m->table = nullptr; m->table_bytes = 0;
+            SCHK(h, hipFree(old));
+        }
+        SCHK(h, hipMalloc((void**)&m->table, need));
+        m->table_bytes = need;
+    }
+    return search ? scene_batch_register_reserve(hb) : YH_OK;
 }
 
 // one stream's two maps and two tables, at its first use; cleared if they are fresh or stale
@@ -139,6 +131,10 @@ int run_memory(yh_scene_batch* hb) {
     f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
     f.W = h->W; f.H = h->H; f.keep = m->keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = 0; f.g[i] = 0; }
+    if (m->searched) {   // the motions are found round by round; the ball chains need every frame's record
+        const int rs = scene_batch_register_search(hb, &f);
+        return rs ? rs : scene_batch_register_balls(hb, b);
+    }
     hipLaunchKernelGGL(batch_balls_memory, dim3((unsigned)m->chains), dim3(128), 0, h->stream, b, chains, steps, m->tabs);
     const unsigned gx = (unsigned)((h->W + SF_TW - 1) / SF_TW), gy = (unsigned)((h->H + SF_TH - 1) / SF_TH);
     for (size_t r = 0; r + 1 < m->round_off.size(); ++r)
@@ -149,10 +145,13 @@ int run_memory(yh_scene_batch* hb) {
 
 int stream_of(const int32_t* streams, int b) { return streams ? streams[b] : 0; }
 
-int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32_t* gather, const int32_t* carry, int keep, int max_age) {
+// n_rot 0: gather and carry are one motion per frame. Otherwise n_rot bases per frame, searched around with `radius`: the slots and
+// steps carry no motion (the kernels read each frame's from its record) and the frames' bases follow the chains in the one upload.
+int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32_t* gather, const int32_t* carry, int keep, int max_age, int n_rot = 0, int radius = 0) {
     yh_scene* h = &hb->core;
     SCHK(h, hipSetDevice(h->dev));
-    int rc = memory_reserve(hb);
+    const bool search = n_rot > 0;
+    int rc = memory_reserve(hb, search);
     if (rc) return rc;
     yh_scene_batch_memory* m = hb->memory;
     // the schedule: the frames of every stream in batch order; R rounds
@@ -168,7 +167,7 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
     for (int s : named)
         if ((rc = stream_reserve(hb, s))) return rc;
     const size_t npx = (size_t)h->W * h->H;
-    m->table_host.assign(slots_bytes(h) + steps_bytes(h) + YH_SCENE_STREAMS_MAX * sizeof(SceneBallsChain), 0);
+    m->table_host.assign(scene_batch_bases_offset(h) + (search ? (size_t)n * sizeof(SceneRegisterBases) : 0), 0);
     SceneFuseSlot* slots = (SceneFuseSlot*)m->table_host.data();
     SceneBallsStep* steps = (SceneBallsStep*)(m->table_host.data() + slots_bytes(h));
     SceneBallsChain* chains = (SceneBallsChain*)(m->table_host.data() + slots_bytes(h) + steps_bytes(h));
@@ -183,7 +182,7 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
             e.mem_prev = r == 0 ? k.map[k.cur] : h->map + (size_t)f[r - 1] * npx;
             e.mem_next = r + 1 == f.size() ? k.map[k.cur ^ 1] : nullptr;
             e.frame = f[r];
-            for (int i = 0; i < 6; ++i) e.g[i] = gather[6 * f[r] + i];
+            for (int i = 0; i < 6 && !search; ++i) e.g[i] = gather[6 * f[r] + i];
         }
         m->round_off.push_back(total);
     }
@@ -195,10 +194,22 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
         for (int b : frames_of[s]) {
             SceneBallsStep& e = steps[total++];
             e.frame = b;
-            for (int i = 0; i < 6; ++i) e.c[i] = carry[6 * b + i];
+            for (int i = 0; i < 6 && !search; ++i) e.c[i] = carry[6 * b + i];
+        }
+    }
+    if (search) {
+        SceneRegisterBases* bases = (SceneRegisterBases*)(m->table_host.data() + scene_batch_bases_offset(h));
+        for (int b = 0; b < n; ++b) {
+            bases[b].n_rot = n_rot; bases[b].radius = radius;
+            for (int k = 0; k < n_rot; ++k)
+                for (int i = 0; i < 6; ++i) {
+                    bases[b].g[k][i] = gather[((size_t)b * n_rot + k) * 6 + i];
+                    bases[b].c[k][i] = carry[((size_t)b * n_rot + k) * 6 + i];
+                }
         }
     }
     m->n = n; m->keep = keep; m->max_age = max_age;
+    m->searched = search; m->n_rot = n_rot; m->radius = radius;
     // (from pageable memory: staged by the runtime before the call returns, as the caller's own arrays have been read by now)
     SCHK(h, hipMemcpyAsync(m->table, m->table_host.data(), m->table_host.size(), hipMemcpyHostToDevice, h->stream));
     if ((rc = run_memory(hb))) return rc;
@@ -222,20 +233,20 @@ void scene_batch_memory_free(yh_scene_batch* hb) {
         void* bufs[] = { k.map[0], k.map[1], k.tab[0], k.tab[1] };
         for (void* b : bufs) if (b) hipFree(b);
     }
-    void* bufs[] = { m->stamp, m->tabs, m->table };
+    void* bufs[] = { m->stamp, m->tabs, m->table, m->reg_acc, m->reg_rec };
     for (void* b : bufs) if (b) hipFree(b);
     delete m;
     hb->memory = nullptr;
 }
 
 bool scene_batch_memory_is_last(const yh_scene_batch* hb) { return hb->memory && hb->memory->frame != 0 && hb->memory->frame == hb->core.frames; }
+bool scene_batch_memory_is_search(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->searched; }
 }  // namespace yh
 
-extern "C" {
+namespace {
 
-int yh_scene_batch_append_memory(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16,
-                                 int32_t keep, int32_t ball_max_age) {
-    if (!hb) return YH_EINVAL;
+// the checks both memory appends share, for every frame before anything is touched
+int append_memory_checks(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16, int32_t keep, int32_t ball_max_age) {
     yh_scene* h = &hb->core;
     if (!gather_q16 || !carry_q16) return h->fail(YH_EINVAL, "null motion array");
     if (n_frames < 1 || n_frames > h->max_frames) return h->fail(YH_EINVAL, "n_frames " + std::to_string(n_frames) + " outside 1 .. " + std::to_string(h->max_frames));
@@ -246,14 +257,21 @@ int yh_scene_batch_append_memory(yh_scene_batch* hb, int32_t n_frames, const int
             return h->fail(YH_EINVAL, "frame " + std::to_string(b) + ": stream " + std::to_string(streams[b]) + " outside 0 .. " + std::to_string(YH_SCENE_STREAMS_MAX - 1));
         if (!hb->staged[b]) return h->fail(YH_ESTATE, "slot " + std::to_string(b) + " has never been staged");
     }
+    return YH_OK;
+}
+
+// what both do around append_memory once the checks have passed (n_rot 0: the motions are given)
+int append_memory_call(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16,
+                       int32_t keep, int32_t ball_max_age, int32_t n_rot, int32_t radius) {
+    yh_scene* h = &hb->core;
     ++h->frames;   // (earlier plans are of other frames, whatever becomes of these)
-    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius);
     yh_scene_batch_memory* m = hb->memory;
     if (rc) {
         // a call that fails after its checks leaves no frame and empties the memories of the streams it named
         h->ran = false; hb->n = 0;
         if (m) {
-            m->frame = 0; m->replayable = false;
+            m->frame = 0; m->replayable = false; m->searched = false;
             for (int b = 0; b < n_frames; ++b) m->bank[stream_of(streams, b)].stale = true;
         }
         return rc;
@@ -262,6 +280,72 @@ int yh_scene_batch_append_memory(yh_scene_batch* hb, int32_t n_frames, const int
     h->ran = true; h->last_mode = YH_COMPAT_SANE;
     hb->n = n_frames; hb->from_fields = false;
     std::fill(hb->diag_ok.begin(), hb->diag_ok.end(), (uint8_t)1);   // (F is a height map like any other: both ends of a diagonal hold the same length)
+    return YH_OK;
+}
+
+// `reps` runs of `run` between two events on the handle's stream; a failure leaves no frame and nothing to replay
+template <class Run>
+int replay_time(yh_scene_batch* hb, int reps, Run run, float* ms_out) {
+    yh_scene* h = &hb->core;
+    yh_scene_batch_memory* m = hb->memory;
+    struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+    SCHK(h, hipEventCreate(&ev.a)); SCHK(h, hipEventCreate(&ev.b));
+    SCHK(h, hipEventRecord(ev.a, h->stream));
+    for (int r = 0; r < reps; ++r) {
+        const int rc = run();
+        if (rc) {
+            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false; m->searched = false;
+            for (BankStream& k : m->bank) k.stale = true;
+            return rc;
+        }
+    }
+    SCHK(h, hipEventRecord(ev.b, h->stream));
+    SCHK(h, hipEventSynchronize(ev.b));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    *ms_out = ms / reps;
+    return YH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int yh_scene_batch_append_memory(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16,
+                                 int32_t keep, int32_t ball_max_age) {
+    if (!hb) return YH_EINVAL;
+    const int rc = append_memory_checks(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    return rc ? rc : append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, 0, 0);
+}
+
+int yh_scene_batch_append_memory_search(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, int32_t n_rot, const int32_t* gather_q16,
+                                        const int32_t* carry_q16, int32_t radius, int32_t keep, int32_t ball_max_age) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    int rc = append_memory_checks(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    if (rc) return rc;
+    // (the two ranges here: they are about the call, not about frame 0)
+    if (n_rot < 1 || n_rot > SR_MAX_ROT) return h->fail(YH_EINVAL, "n_rot outside 1 .. 16");
+    if (radius < 0 || radius > SR_MAX_R) return h->fail(YH_EINVAL, "radius outside 0 .. 8");
+    for (int b = 0; b < n_frames; ++b)
+        if ((rc = scene_register_bases_check(h, n_rot, gather_q16 + (size_t)b * n_rot * 6, carry_q16 + (size_t)b * n_rot * 6, radius))) return hb->framed(b, rc);
+    return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius);
+}
+
+int yh_scene_batch_motion_read(yh_scene_batch* hb, int32_t frame, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (!h->ran || !scene_batch_memory_is_search(hb)) return h->fail(YH_ESTATE, "the current frames did not come from yh_scene_batch_append_memory_search");
+    if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
+    SCHK(h, hipSetDevice(h->dev));
+    yh_scene_batch_memory* m = hb->memory;
+    SceneRegisterRecord rec;
+    const size_t stride = m->acc_stride();
+    SCHK(h, hipMemcpyAsync(&rec, m->reg_rec + frame, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
+    if (scores) SCHK(h, hipMemcpyAsync(scores, m->reg_acc + (size_t)frame * stride + 1, (stride - 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 6; ++i) { if (gather_q16) gather_q16[i] = rec.g[i]; if (carry_q16) carry_q16[i] = rec.c[i]; }
+    for (int i = 0; i < 3; ++i) { if (chosen) chosen[i] = rec.chosen[i]; if (score) score[i] = rec.score[i]; }
     return YH_OK;
 }
 
@@ -318,29 +402,26 @@ int yh_scene_batch_memory_reset(yh_scene_batch* hb, int32_t stream) {
 int yh_scene_batch_memory_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch) {
     if (!hb || reps < 1 || !ms_per_batch) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_search(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search: yh_scene_batch_memory_search_time replays them");
     if (!h->ran || !scene_batch_memory_is_last(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
         return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory (or a memory was reset or a slot staged since)");
     SCHK(h, hipSetDevice(h->dev));
-    struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-    SCHK(h, hipEventCreate(&ev.a)); SCHK(h, hipEventCreate(&ev.b));
-    SCHK(h, hipEventRecord(ev.a, h->stream));
     // the last append's own slots, motions and streams (its device tables), from the state it started from - the other buffers of
     // every stream it named - into the state it left: the same bits again, so nothing is committed
-    yh_scene_batch_memory* m = hb->memory;
-    for (int r = 0; r < reps; ++r) {
-        const int rc = run_memory(hb);
-        if (rc) {
-            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false;
-            for (BankStream& k : m->bank) k.stale = true;
-            return rc;
-        }
-    }
-    SCHK(h, hipEventRecord(ev.b, h->stream));
-    SCHK(h, hipEventSynchronize(ev.b));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
-    *ms_per_batch = ms / reps;
-    return YH_OK;
+    return replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
+}
+
+int yh_scene_batch_memory_search_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
+    if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (!h->ran || !scene_batch_memory_is_search(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
+        return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_search (or a memory was reset or a slot staged since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // the whole append first, as yh_scene_batch_memory_time replays a plain one; then its registration launches alone, on the map
+    // slots that left - each predecessor's fused map - so the same tables and records again
+    const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
+    return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_register_search(hb, nullptr); }, ms_search);
 }
 
 }  // extern "C"

@@ -189,6 +189,9 @@ SYMBOLS = [
     ("yh_scene_batch_memory_frame_balls", _i, [_vp, _i, _vp]),
     ("yh_scene_batch_memory_reset", _i, [_vp, _i]),
     ("yh_scene_batch_memory_time", _i, [_vp, _i, C.POINTER(_f)]),
+    ("yh_scene_batch_append_memory_search", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i]),
+    ("yh_scene_batch_motion_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_batch_memory_search_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
@@ -1449,6 +1452,42 @@ class SceneBatch:
         st = Engine._streams(streams, n)
         self._chk(self.L.yh_scene_batch_append_memory(self.h, n, _p(st) if st is not None else None, _p(g), _p(c), keep, ball_max_age))
         self.n, self._fields = n, False
+
+    def append_memory_search(self, n, candidates=None, streams=None, radius=4, keep=224, ball_max_age=30):
+        """append_memory with every frame's motion found on the device (DESIGN.md §11 "Scene batch: registration"): frame b is
+        Scene.append_memory_search on the memory of streams[b], the calls made in batch order, so a stream's later frame is scored
+        against what its earlier frame has just fused. candidates: n (gathers, carries) pairs, the same number of rows of six ints
+        each, row 0 the frame's prior (scene_motion_candidates); None: the identity alone for every frame. radius, keep and
+        ball_max_age are one value per call; read_motion(b) tells what frame b chose."""
+        if candidates is None:
+            candidates = [([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16])] * max(n, 0)
+        g = np.ascontiguousarray(np.array([m[0] for m in candidates], np.int32))   # (a value outside int32 raises here)
+        c = np.ascontiguousarray(np.array([m[1] for m in candidates], np.int32))
+        assert len(candidates) == max(n, 0), "candidates: one (gathers, carries) pair per frame"
+        assert n <= 0 or (g.ndim == 3 and g.shape[2] == 6 and c.shape == g.shape), "candidates: the same number of rows of six ints for every frame"
+        n_rot = g.shape[1] if g.ndim == 3 else 0
+        st = Engine._streams(streams, n)
+        self._chk(self.L.yh_scene_batch_append_memory_search(self.h, n, _p(st) if st is not None else None, n_rot, _p(g), _p(c), radius, keep, ball_max_age))
+        self.n, self._fields, self._search = n, False, (n_rot, radius)
+
+    def read_motion(self, frame, scores=False):
+        """What the last append_memory_search chose for frame `frame`: the dict Scene.read_motion returns."""
+        out = dict(gather=np.zeros(6, np.int32), carry=np.zeros(6, np.int32), chosen=np.zeros(3, np.int32), score=np.zeros(3, np.uint64))
+        table = None
+        if scores and getattr(self, "_search", None):
+            n_rot, radius = self._search
+            table = np.zeros((n_rot, 2 * radius + 1, 2 * radius + 1), np.uint64)
+        self._chk(self.L.yh_scene_batch_motion_read(self.h, frame, _p(out["gather"]), _p(out["carry"]), _p(out["chosen"]), _p(out["score"]),
+                                                    _p(table) if table is not None else None))
+        if scores:
+            out["scores"] = table
+        return out
+
+    def memory_search_time(self, reps=20):
+        """(ms per batch, ms of the registration launches alone) of the last append_memory_search, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_batch_memory_search_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
 
     def read_memory(self, stream=0):
         """The memory of one stream: map u32 [h][w], balls i32 [100][4] = (x, y, count, age); zeros while empty."""
