@@ -637,6 +637,36 @@ int yh_scene_append_memory_search(yh_scene* h, const uint16_t* depth_host, const
  * yh_scene_memory_reset since ends that; plain appends and plans do not). */
 int yh_scene_motion_read(yh_scene* h, int32_t* gather_q16 /* [6] */, int32_t* carry_q16 /* [6] */, int32_t* chosen /* [3] = k, u, v */,
                          uint64_t* score /* [3] = S chosen, S prior, sum_n */, uint64_t* scores /* [n_rot][2R+1][2R+1] or NULL */);
+/* Scene memory: pyramid registration (DESIGN.md section 11 "Scene memory: pyramid registration"): the search made coarse to fine.
+ * yh_scene_append_memory_search with a reach of tens of pixels at about the cost of a small search. N and M (unfaded) are pooled into
+ * levels 1 .. levels (1 .. 3): level l + 1 is ceil(W_l / 2) x ceil(H_l / 2), a cell the MAX of the up to four cells under it.
+ *   level bases  base k's gather (a, b, c, d, e, f) at level l keeps a, b, d, e and has c_l = floor(((a + b - 65536)(2^l - 1) + 2 c)
+ *                / 2^(l+1)), f_l likewise from d, e, f (64 bits): the base carried to the centres of the level's cells. Scores at a
+ *                level are S of yh_scene_append_memory_search on that level's maps and sizes.
+ *   descent      every base (n_rot 1 .. 15) on its own: at the top level the (2 radius + 1)^2 shifts around (0, 0), radius 0 .. 8; at
+ *                each level below the (2 refine + 1)^2 shifts, refine 0 .. 8, around TWICE the total shift chosen one level up. Best
+ *                of a level: the larger S, then the smaller U^2 + V^2 of the total shift, then the smaller V, then the smaller U.
+ *                At level 0 hypothesis n_rot joins: base 0 around (0, 0) - "the prior was right".
+ *   choice       over every level-0 entry of all n_rot + 1 hypotheses (hypothesis n_rot counts as k = 0), (u, v) the total shift:
+ *                the largest S, then the smaller u^2 + v^2, then the smaller k, then the smaller v, then the smaller u. The chosen
+ *                S is S(k, u, v) of the plain search exactly; it is never below the plain search's best for base 0 at radius
+ *                refine; an empty memory or an empty frame chooses (0, 0, 0).
+ *   reach        T_levels = radius, T_l = 2 T_(l+1) + refine: 71 pixels at levels 3, radius 8, refine 1.
+ * The chosen candidate's twelve integers are yh_scene_append_memory_search's for (k, u, v), and everything after the choice is that
+ * call's. S is not normalised: on a map dense everywhere a large true shift can lose to "no motion" (DESIGN.md); the home
+ * hypothesis makes the outcome there the plain search's. Integer only, bit-exact, no host wait; host buffers are free on return.
+ * YH_EINVAL with nothing touched, the memory included, for a null pointer, a parameter out of range, or - in 64 bits - unless for
+ * every base and level |c_l| + T_l 65536 <= INT32_MAX and |f_l| + T_l 65536 <= INT32_MAX, and the two carry conditions of
+ * yh_scene_append_memory_search hold with T_0 in place of radius. */
+int yh_scene_append_memory_pyramid(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                   const int32_t* gather_q16 /* [n_rot][6] */, const int32_t* carry_q16 /* [n_rot][6] */, int32_t levels,
+                                   int32_t radius, int32_t refine, int32_t keep, int32_t ball_max_age);
+/* One level (0 .. levels) of the last yh_scene_append_memory_pyramid: the centre each hypothesis was scored around, its score
+ * table indexed [hyp][V - centre_y + p][U - centre_x + p] with p = radius at the top level and refine below, hyp = n_rot or, at
+ * level 0, n_rot + 1, and the sum of the level's N. Any pointer may be NULL. Waits. YH_ESTATE unless the handle's last memory
+ * append was a pyramid append; YH_EINVAL for a level outside 0 .. levels. After a pyramid append yh_scene_motion_read returns the
+ * gather, carry, chosen and score (S chosen, S(0, 0, 0), sum_n) with scores NULL, and YH_EINVAL naming this call if scores is given. */
+int yh_scene_pyramid_read(yh_scene* h, int32_t level, int32_t* centres /* [hyp][2] */, uint64_t* scores /* [hyp][2p+1][2p+1] */, uint64_t* sum_n);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

@@ -129,6 +129,19 @@ int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, 
  * (up to 2^32 - 1) and shapes no depth frame produces. */
 int yh_scene_op_register(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
                          int32_t radius, uint64_t* scores, int32_t* chosen /* [3] */, uint64_t* sum_n);
+/* The same for a frame that came from yh_scene_append_memory_pyramid (yh_scene_time, yh_scene_memory_time and
+ * yh_scene_memory_search_time refuse such a frame with YH_ESTATE and name this hook): the whole append replayed from the state it
+ * started from, ms_per_frame; then its registration launches alone (the levels, the clear, scores and select per level),
+ * ms_search. Both rewrite the same values and commit nothing. YH_ESTATE unless the handle's last frame is a pyramid append. */
+int yh_scene_memory_pyramid_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search);
+/* Test hook: the pyramid registration alone - the levels, every level's scores, the descent and the choice - on two caller-given
+ * maps u32 [h][w], with buffers of its own; n_rot gathers, levels, radius and refine as yh_scene_append_memory_pyramid takes them
+ * (the same YH_EINVAL checks; there are no carries). chosen [3] = k, u, v; score [3] = S chosen, S(0, 0, 0), sum_n; pyr_n and
+ * pyr_m the pooled levels 1 .. levels of each map, concatenated; centres and scores what yh_scene_pyramid_read returns, levels
+ * 0 .. levels concatenated. Each may be NULL. Waits. Reads and writes nothing of the handle's frame, memory or plans. */
+int yh_scene_op_pyramid(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
+                        int32_t levels, int32_t radius, int32_t refine, int32_t* chosen /* [3] */, uint64_t* score /* [3] */, uint32_t* pyr_n,
+                        uint32_t* pyr_m, int32_t* centres, uint64_t* scores);
 /* Test hook: uploads host fields (height map u32 [h][w], connections0 / connections1 f32 [h][w][4], laid out as yh_scene_read
  * returns them) as if a YH_COMPAT_SANE frame had produced them, so that yh_scene_plan runs on constructed mazes. The planner reads
  * conn0[..][2] (right) and conn1[..][0] (down) and takes left / up from the neighbour, as SANE's symmetry allows: YH_EINVAL (nothing

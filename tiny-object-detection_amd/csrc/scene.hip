@@ -225,6 +225,8 @@ int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h->ran) return h->fail(YH_ESTATE, "no frame has been appended");
     if (scene_memory_is_search(h))
         return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");
+    if (scene_memory_is_pyramid(h))
+        return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
     if (scene_memory_is_last(h))
         return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory: yh_scene_memory_time replays it");
     SCHK(h, hipSetDevice(h->dev));

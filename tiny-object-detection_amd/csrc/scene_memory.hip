@@ -11,6 +11,8 @@
 // yh_scene_append_memory_search (DESIGN.md section 11 "Scene memory: registration") is the same append with the motion found on the
 // device: between the stamps and the fuse, scene_register.hip scores N against M over the caller's candidates and leaves the
 // chosen one in a device record, which the fuse and the ball carry read (scene_fuse_dev, scene_balls_memory_dev).
+// yh_scene_append_memory_pyramid (DESIGN.md section 11 "Scene memory: pyramid registration") is that append with the candidates
+// searched coarse to fine (scene_pyramid.hip), into the same record.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -19,6 +21,7 @@
 #include "scene.h"
 #include "scene_dev.h"
 #include "scene_memory_dev.h"
+#include "scene_pyramid_dev.h"
 #include "scene_register_dev.h"
 #include "yh_internal.h"
 
@@ -45,6 +48,11 @@ struct yh_scene_memory {
     SceneRegisterRecord* reg_rec = nullptr;
     bool searched = false;
     SceneRegisterBases last_bases = {};
+    // pyramid registration: allocated at the first pyramid append. pyramid: the last memory append was one - last_pyr is its plan,
+    // reg_rec its choice, pyr.acc its level tables, pyr.table the centres (searched is false then)
+    ScenePyramidBufs pyr;
+    bool pyramid = false;
+    ScenePyramidPlan last_pyr;
 };
 
 namespace {
@@ -84,8 +92,9 @@ int register_reserve(yh_scene* h) {
 }
 
 // the launches of one memory append: reads map[from] / tab[from], writes map[from ^ 1] / tab[from ^ 1] and the handle's fields
-// (bases given: the motion is searched for around them and read from the device record, q.g and q.c are not used)
-int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr) {
+// (bases or pyr given: the motion is searched for around them and read from the device record, q.g and q.c are not used; upload:
+// the pyramid's table goes to the device first - a replay finds it there)
+int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr, const ScenePyramidPlan* pyr = nullptr, bool upload = false) {
     yh_scene_memory* m = h->memory;
     SceneParams p;
     p.depth = h->depth; p.cls_id = nullptr; p.frame = q.frame; p.frame_mode = 1;
@@ -102,6 +111,10 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBa
     f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
     f.W = h->W; f.H = h->H; f.keep = q.keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = q.c[i]; f.g[i] = q.g[i]; }
+    if (pyr) {
+        const int rs = scene_pyramid_search(h, m->stamp, m->map[from], *pyr, m->pyr, m->reg_rec, upload);
+        return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
+    }
     if (bases) {
         const int rs = scene_register_search(h, m->stamp, m->map[from], *bases, m->reg_acc, m->reg_rec);
         return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
@@ -112,34 +125,38 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBa
     return YH_OK;
 }
 
-int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q, const SceneRegisterBases* bases = nullptr) {
+int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q, const SceneRegisterBases* bases, const ScenePyramidPlan* pyr) {
     SCHK(h, hipSetDevice(h->dev));
     int rc = memory_reserve(h);
     if (rc) return rc;
-    if (bases && (rc = register_reserve(h))) return rc;
+    if ((bases || pyr) && (rc = register_reserve(h))) return rc;
+    if (pyr && (rc = scene_pyramid_reserve(h, h->memory->pyr))) return rc;
     const size_t npx = (size_t)h->W * h->H;
     SCHK(h, hipMemcpyAsync(h->depth, depth_host, npx * 2, hipMemcpyHostToDevice, h->stream));
     q.frame = frame;
     if (!frame_on_device) { SCHK(h, hipMemcpyAsync(h->frame, frame, npx * 4, hipMemcpyHostToDevice, h->stream)); q.frame = h->frame; }
     if ((rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame))) return rc;
     yh_scene_memory* m = h->memory;
-    if ((rc = run_memory(h, q, m->cur, bases))) return rc;
+    if (pyr) m->last_pyr = *pyr;   // (the upload reads the handle's copy: the caller's is free when the call returns)
+    if ((rc = run_memory(h, q, m->cur, bases, pyr ? &m->last_pyr : nullptr, true))) return rc;
     m->cur ^= 1;
     m->last = q;
     m->searched = bases != nullptr;
+    m->pyramid = pyr != nullptr;
     if (bases) m->last_bases = *bases;
     return YH_OK;
 }
 
-// what both memory appends do around append_memory: the frame count, and what a failure or a success leaves
-int append_memory_call(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, const MemoryCall& q, const SceneRegisterBases* bases) {
+// what every memory append does around append_memory: the frame count, and what a failure or a success leaves
+int append_memory_call(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, const MemoryCall& q, const SceneRegisterBases* bases,
+                       const ScenePyramidPlan* pyr = nullptr) {
     ++h->frames;   // (earlier plans are of another frame, whatever becomes of this one)
-    const int rc = append_memory(h, depth_host, frame, frame_on_device, q, bases);
+    const int rc = append_memory(h, depth_host, frame, frame_on_device, q, bases, pyr);
     yh_scene_memory* m = h->memory;
     if (rc) {
         // a call that fails after its checks leaves no frame and an empty memory
         h->ran = false;
-        if (m) { m->stale = true; m->frame = 0; m->searched = false; }
+        if (m) { m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; }
         return rc;
     }
     m->frame = h->frames;
@@ -159,9 +176,10 @@ int replay_time(yh_scene* h, int reps, bool search_only, float* ms_out) {
     // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
     // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
     for (int r = 0; r < reps; ++r) {
-        const int rc = search_only ? scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec)
-                                   : run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr);
-        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; m->searched = false; return rc; }
+        const int rc = !search_only ? run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr, m->pyramid ? &m->last_pyr : nullptr)
+                       : m->pyramid ? scene_pyramid_search(h, m->stamp, m->map[m->cur ^ 1], m->last_pyr, m->pyr, m->reg_rec, false)
+                                    : scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec);
+        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; return rc; }
     }
     SCHK(h, hipEventRecord(b, h->stream));
     SCHK(h, hipEventSynchronize(b));
@@ -180,12 +198,14 @@ void scene_memory_free(yh_scene* h) {
     if (!m) return;
     void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1], m->reg_acc, m->reg_rec };
     for (void* b : bufs) if (b) hipFree(b);
+    scene_pyramid_release(m->pyr);
     delete m;
     h->memory = nullptr;
 }
 
 bool scene_memory_is_last(const yh_scene* h) { return h->memory && h->memory->frame != 0 && h->memory->frame == h->frames; }
 bool scene_memory_is_search(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->searched; }
+bool scene_memory_is_pyramid(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->pyramid; }
 }  // namespace yh
 
 extern "C" {
@@ -217,10 +237,45 @@ int yh_scene_append_memory_search(yh_scene* h, const uint16_t* depth_host, const
     return append_memory_call(h, depth_host, frame, frame_on_device, q, &bases);
 }
 
+int yh_scene_append_memory_pyramid(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                   const int32_t* gather_q16, const int32_t* carry_q16, int32_t levels, int32_t radius, int32_t refine, int32_t keep,
+                                   int32_t ball_max_age) {
+    if (!h || !depth_host || !frame || !gather_q16 || !carry_q16) return YH_EINVAL;
+    ScenePyramidPlan plan;
+    const int rc = scene_pyramid_plan_make(h, n_rot, gather_q16, carry_q16, levels, radius, refine, plan);
+    if (rc) return rc;
+    if (keep < 0 || keep > 256) return h->fail(YH_EINVAL, "keep outside 0 .. 256");
+    if (ball_max_age < 0 || ball_max_age > 255) return h->fail(YH_EINVAL, "ball_max_age outside 0 .. 255");
+    MemoryCall q;   // (its motion stays zero: the kernels read the chosen one from the device record)
+    q.keep = keep; q.max_age = ball_max_age;
+    return append_memory_call(h, depth_host, frame, frame_on_device, q, nullptr, &plan);
+}
+
+int yh_scene_pyramid_read(yh_scene* h, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* sum_n) {
+    if (!h) return YH_EINVAL;
+    yh_scene_memory* m = h->memory;
+    if (!m || m->stale || !m->pyramid) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_pyramid (or the memory was reset since)");
+    const ScenePyramidPlan& plan = m->last_pyr;
+    if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
+    SCHK(h, hipSetDevice(h->dev));
+    const int hyp = plan.hyp(level), nu = 2 * plan.rho(level) + 1;
+    const unsigned long long* acc = m->pyr.acc + plan.acc_offset(level);
+    int cen[SR_MAX_ROT][2];
+    unsigned long long sum = 0;
+    if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr.table->centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
+    if (sum_n) SCHK(h, hipMemcpyAsync(&sum, acc, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
+    if (scores) SCHK(h, hipMemcpyAsync(scores, acc + 1, (size_t)hyp * nu * nu * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < hyp && centres; ++k) { centres[2 * k] = cen[k][0]; centres[2 * k + 1] = cen[k][1]; }
+    if (sum_n) *sum_n = sum;
+    return YH_OK;
+}
+
 int yh_scene_motion_read(yh_scene* h, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
     if (!h) return YH_EINVAL;
     yh_scene_memory* m = h->memory;
-    if (!m || m->stale || !m->searched) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search (or the memory was reset since)");
+    if (!m || m->stale || !(m->searched || m->pyramid)) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search (or the memory was reset since)");
+    if (m->pyramid && scores) return h->fail(YH_EINVAL, "the last memory append was yh_scene_append_memory_pyramid: yh_scene_pyramid_read returns its level tables");
     SCHK(h, hipSetDevice(h->dev));
     SceneRegisterRecord rec;
     const int nu = 2 * m->last_bases.radius + 1;
@@ -258,6 +313,7 @@ int yh_scene_memory_reset(yh_scene* h) {
     m->stale = true;   // (should the clearing fail, it is made again before the next use)
     m->frame = 0;      // (nothing to replay: the state the last memory append started from is gone)
     m->searched = false;
+    m->pyramid = false;
     return memory_reserve(h);
 }
 
@@ -265,15 +321,26 @@ int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!scene_memory_is_last(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory (or the memory was reset since)");
     if (h->memory->searched) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");
+    if (h->memory->pyramid) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
     SCHK(h, hipSetDevice(h->dev));
     return replay_time(h, reps, false, ms_per_frame);
 }
 
 int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
     if (!scene_memory_is_search(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search (or the memory was reset since)");
     SCHK(h, hipSetDevice(h->dev));
     // the whole append first, then its registration launches alone on what that left: the same record and scores again
+    const int rc = replay_time(h, reps, false, ms_per_frame);
+    return rc ? rc : replay_time(h, reps, true, ms_search);
+}
+
+int yh_scene_memory_pyramid_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
+    if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (!scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_pyramid (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_memory_search_time: the whole append, then its registration launches alone (the levels, the clear, scores and select)
     const int rc = replay_time(h, reps, false, ms_per_frame);
     return rc ? rc : replay_time(h, reps, true, ms_search);
 }

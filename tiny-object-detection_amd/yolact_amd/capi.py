@@ -172,6 +172,10 @@ SYMBOLS = [
     ("yh_scene_motion_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_memory_search_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_op_register", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    ("yh_scene_append_memory_pyramid", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("yh_scene_pyramid_read", _i, [_vp, _i, _vp, _vp, _vp]),
+    ("yh_scene_memory_pyramid_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_op_pyramid", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
@@ -1166,6 +1170,76 @@ class Scene:
         """(ms per frame, ms of the registration alone) of the last append_memory_search, replayed; commits nothing."""
         ms, ms_search = C.c_float(), C.c_float()
         self._chk(self.L.yh_scene_memory_search_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
+    def append_memory_pyramid(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, candidates=None, levels=3, radius=8, refine=1, keep=224,
+                              ball_max_age=30):
+        """append_memory_search with the candidates searched coarse to fine (DESIGN.md §11 "Scene memory: pyramid registration"):
+        candidates as there, at most 15 rows. Every row is scored on `levels` (1 .. 3) max-pooled levels of both maps: `radius`
+        (0 .. 8) either way at the coarsest, `refine` (0 .. 8) around twice the shift found above at each finer one; at full size
+        "row 0, no shift" joins. read_motion tells which won (its table is read_pyramid's), read_pyramid the levels' tables."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        g, c = ([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16]) if candidates is None else candidates
+        g, c = np.ascontiguousarray(np.array(g, np.int32)), np.ascontiguousarray(np.array(c, np.int32))   # (a value outside int32 raises here)
+        assert g.ndim == 2 and g.shape[1] == 6 and c.shape == g.shape
+        if frame_dev_ptr is not None:
+            f, on_device = C.c_void_p(frame_dev_ptr), 1
+        else:
+            keepalive = SceneBatch.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+            assert keepalive.size == self.W * self.H
+            f, on_device = _p(keepalive), 0
+        self._chk(self.L.yh_scene_append_memory_pyramid(self.h, _p(depth), f, on_device, len(g), _p(g), _p(c), levels, radius, refine, keep, ball_max_age))
+        self._pyramid = (len(g), levels, radius, refine)
+        self._search = (len(g) + 1, refine)   # (read_motion(scores=True) is refused after this append: it names read_pyramid)
+
+    def read_pyramid(self, level):
+        """Level `level` (0 .. levels) of the last append_memory_pyramid: centres i32 [hyp][2], the centre each hypothesis was scored
+        around; scores u64 [hyp][2 p + 1][2 p + 1] indexed [hyp][V - centre_y + p][U - centre_x + p], p = radius at the top level,
+        refine below, hyp = n_rot (n_rot + 1 at level 0: the last is "row 0, no shift"); sum_n of the level's stamps."""
+        n_rot, levels, radius, refine = getattr(self, "_pyramid", None) or (1, 0, 0, 0)
+        ok = 0 <= level <= levels                # (otherwise the library refuses before it writes anything)
+        p, hyp = (radius if level == levels else refine), n_rot + (1 if level == 0 else 0)
+        out = dict(centres=np.zeros((hyp, 2), np.int32), scores=np.zeros((hyp, 2 * p + 1, 2 * p + 1), np.uint64))
+        sum_n = C.c_uint64()
+        self._chk(self.L.yh_scene_pyramid_read(self.h, level, _p(out["centres"]) if ok else None, _p(out["scores"]) if ok else None, C.byref(sum_n)))
+        out["sum_n"] = sum_n.value
+        return out
+
+    def op_pyramid(self, n, m, gathers, levels, radius, refine):
+        """Test hook (yh_scene_op_pyramid): the pyramid registration alone on stamps n and memory m, u32 [h][w]; gathers [n_rot][6].
+        Returns dict(chosen (k, u, v), score u64 [3], pyr_n and pyr_m: lists of the pooled levels 1 .. levels, and centres, scores,
+        lists over levels 0 .. levels laid out as read_pyramid's); commits nothing."""
+        n, m = np.ascontiguousarray(n, np.uint32), np.ascontiguousarray(m, np.uint32)
+        assert n.shape == (self.H, self.W) and m.shape == (self.H, self.W)
+        g = np.ascontiguousarray(np.array(gathers, np.int32))
+        assert g.ndim == 2 and g.shape[1] == 6
+        ok = 1 <= len(g) <= 15 and 1 <= levels <= 3 and 0 <= radius <= 8 and 0 <= refine <= 8   # (otherwise the library refuses before it writes anything)
+        dims, hs, ps = [], [], []
+        for lv in range((levels if ok else 0) + 1):
+            dims.append((-(-self.H >> lv), -(-self.W >> lv)))
+            hs.append(len(g) + (1 if lv == 0 else 0)); ps.append(2 * (radius if lv == levels else refine) + 1)
+        words = sum(h * w for h, w in dims[1:])
+        pyr_n, pyr_m = np.zeros(max(words, 1), np.uint32), np.zeros(max(words, 1), np.uint32)
+        centres, scores = np.zeros((sum(hs), 2), np.int32), np.zeros(sum(h * p * p for h, p in zip(hs, ps)), np.uint64)
+        chosen, score = np.zeros(3, np.int32), np.zeros(3, np.uint64)
+        self._chk(self.L.yh_scene_op_pyramid(self.h, _p(n), _p(m), len(g), _p(g), levels, radius, refine, _p(chosen), _p(score), _p(pyr_n), _p(pyr_m),
+                                             _p(centres), _p(scores)))
+        out = dict(chosen=tuple(int(v) for v in chosen), score=score, pyr_n=[], pyr_m=[], centres=[], scores=[])
+        o = 0
+        for h, w in dims[1:]:
+            out["pyr_n"].append(pyr_n[o:o + h * w].reshape(h, w)); out["pyr_m"].append(pyr_m[o:o + h * w].reshape(h, w))
+            o += h * w
+        oc = os_ = 0
+        for h, p in zip(hs, ps):
+            out["centres"].append(centres[oc:oc + h]); out["scores"].append(scores[os_:os_ + h * p * p].reshape(h, p, p))
+            oc += h; os_ += h * p * p
+        return out
+
+    def memory_pyramid_time(self, reps=20):
+        """(ms per frame, ms of the registration alone) of the last append_memory_pyramid, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_memory_pyramid_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
         return ms.value, ms_search.value
 
     def plan(self, targets=None, n_targets=3, start=None, connectivity=4):
