@@ -841,6 +841,36 @@ int yh_scene_batch_append_memory_search(yh_scene_batch* h, int32_t n_frames, con
  * NULL. Waits. YH_ESTATE unless the current frames came from a batched search append, YH_EINVAL for a frame outside it. */
 int yh_scene_batch_motion_read(yh_scene_batch* h, int32_t frame, int32_t* gather_q16, int32_t* carry_q16,
                                int32_t* chosen, uint64_t* score, uint64_t* scores);
+/* ---- scene batch: pyramid registration (DESIGN.md section 11 "Scene batch: pyramid registration"): the search coarse to fine ------
+ * yh_scene_batch_append_memory_search with every frame's motion searched for coarse to fine over a map pyramid. On slots
+ * 0 .. n_frames - 1 as staged it is EXACTLY this: for b = 0 .. n_frames - 1 in order, a yh_scene_append_memory_pyramid call on a
+ * yh_scene of the same size that holds the memory of streams[b], fed slot b's depth and packed frame, the n_rot bases of row b, levels,
+ * radius, refine, keep and ball_max_age. Frame b's five outputs, its ball table, every named stream's final memory, frame b's chosen
+ * (k, u, v), twelve coefficients and three scores (yh_scene_batch_motion_read) and every level's centres and score tables
+ * (yh_scene_batch_pyramid_read) are that call's, bit for bit. Frame r of a stream is registered against the memory frame r - 1 of
+ * that stream has just fused - both maps are pooled round by round on the device: with R the most frames one stream has in the call,
+ * R (2 levels + 4) + 5 launches, whatever n, and no host wait. n_rot (1 .. 15), levels (1 .. 3), radius and refine (0 .. 8), keep and
+ * ball_max_age are one value per call. Levels, level bases, descent, choice, reach and int32 conditions are those of the "scene
+ * memory: pyramid registration" section; nothing is redefined here. It counts as a memory append of n_frames frames in every respect,
+ * as yh_scene_batch_append_memory_search does.
+ * Checks, for every frame before anything is touched: every check of yh_scene_batch_append_memory; YH_EINVAL for a parameter outside
+ * its range, and unless the int32 conditions of yh_scene_append_memory_pyramid hold for every frame, base and level (the text names
+ * the frame, the base and, where a coarse level alone refuses, the level). A refused call leaves frames, plans, memories, the last
+ * readable motions and level tables as they were; a call that fails later behaves as yh_scene_batch_append_memory does. Asynchronous
+ * on the handle's stream; the caller's arrays are free again on return. The pooled levels (2 x 4 bytes x the 21 / 64 of a frame's
+ * pixels that levels 1 .. 3 have: 0.8 MB per frame at 640 x 480), the level tables (148 KB per frame), tables of level bases and
+ * records of max_frames frames are allocated at the first batched pyramid append. */
+int yh_scene_batch_append_memory_pyramid(yh_scene_batch* h, int32_t n_frames, const int32_t* streams /* [n] or NULL */,
+                                         int32_t n_rot, const int32_t* gather_q16 /* [n][n_rot][6] */,
+                                         const int32_t* carry_q16 /* [n][n_rot][6] */, int32_t levels, int32_t radius,
+                                         int32_t refine, int32_t keep, int32_t ball_max_age);
+/* One level (0 .. levels) of what the last yh_scene_batch_append_memory_pyramid did for frame `frame`, laid out as
+ * yh_scene_pyramid_read; any pointer may be NULL. Waits. YH_ESTATE unless the last memory append of the batch was a pyramid append
+ * whose frames are the current ones (a memory reset since ends that too); YH_EINVAL for a frame outside it or a level outside
+ * 0 .. levels. After a pyramid append yh_scene_batch_motion_read returns the gather, carry, chosen and score with scores NULL, and
+ * YH_EINVAL naming this call if scores is given. */
+int yh_scene_batch_pyramid_read(yh_scene_batch* h, int32_t frame, int32_t level, int32_t* centres /* [hyp][2] */,
+                                uint64_t* scores /* [hyp][2p+1][2p+1] */, uint64_t* sum_n);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

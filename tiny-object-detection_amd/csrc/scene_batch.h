@@ -40,4 +40,5 @@ int scene_batch_stamp(yh_scene_batch* hb, const SceneParams& p, int n);
 void scene_batch_memory_free(yh_scene_batch* hb);
 bool scene_batch_memory_is_last(const yh_scene_batch* hb);
 bool scene_batch_memory_is_search(const yh_scene_batch* hb);   // .. from yh_scene_batch_append_memory_search
+bool scene_batch_memory_is_pyramid(const yh_scene_batch* hb);  // .. from yh_scene_batch_append_memory_pyramid
 }

@@ -1,5 +1,5 @@
-// scene_batch_memory.h — the state of the scene batch's bank of memories (scene_batch_memory.hip), for the two units that run on it:
-// the memory append itself and its registration (scene_batch_register.hip).
+// scene_batch_memory.h — the state of the scene batch's bank of memories (scene_batch_memory.hip), for the units that run on it:
+// the memory append itself, its registration (scene_batch_register.hip) and its pyramid registration (scene_batch_pyramid.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +8,7 @@
 
 #include "scene_batch.h"
 #include "scene_memory_dev.h"
+#include "scene_pyramid_dev.h"
 #include "scene_register_dev.h"
 
 namespace yh {
@@ -43,6 +44,16 @@ struct yh_scene_batch_memory {
     bool searched = false;
     int n_rot = 0, radius = 0;
     size_t acc_stride() const { return 1 + (size_t)n_rot * (2 * radius + 1) * (2 * radius + 1); }
+    // pyramid registration, allocated at the first pyramid append (it shares reg_rec): frame b's pooled levels of N, then of M, at
+    // pyr_maps + b * 2 * scene_pyramid_map_words, its level tables at pyr_acc + b * pyr.acc_offset(levels + 1) (the stride is the
+    // call's), its table of level bases at pyr_table + b. pyramid: the last memory append was a pyramid append; pyr: its n_rot,
+    // levels, radius and refine (the plan's own table is not used: every frame has one in pyr_host).
+    uint32_t* pyr_maps = nullptr;             // [max_frames][2][scene_pyramid_map_words]
+    unsigned long long* pyr_acc = nullptr;    // [max_frames][scene_pyramid_acc_bytes / 8]
+    yh::ScenePyramidTable* pyr_table = nullptr;   // [max_frames]
+    std::vector<yh::ScenePyramidTable> pyr_host;
+    bool pyramid = false;
+    yh::ScenePyramidPlan pyr;
 };
 
 namespace yh {
@@ -58,4 +69,13 @@ inline size_t scene_batch_bases_offset(const yh_scene* h) { return scene_batch_s
 int scene_batch_register_reserve(yh_scene_batch* hb);
 int scene_batch_register_search(yh_scene_batch* hb, const SceneFuseParams* f);
 int scene_batch_register_balls(yh_scene_batch* hb, const SceneBallsMemParams& b);
+// the fuse of one round alone: `count` slots from `round`, each frame's motion read from its record
+void scene_batch_register_fuse_round(yh_scene_batch* hb, const SceneFuseParams& f, const SceneFuseSlot* round, unsigned count);
+
+// scene_batch_pyramid.hip, likewise, for the last scheduled pyramid append. reserve: the pooled levels, the level tables, the tables
+// of level bases and the records. search: the clear, then per round the levels of every frame's N and M, scores and choice level by
+// level and, with `f` given, the fuse of that round (without: the registration launches alone). The ball chains are
+// scene_batch_register_balls.
+int scene_batch_pyramid_reserve(yh_scene_batch* hb);
+int scene_batch_pyramid_search(yh_scene_batch* hb, const SceneFuseParams* f);
 }

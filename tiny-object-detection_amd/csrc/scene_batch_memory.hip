@@ -17,7 +17,9 @@
 // yh_scene_batch_append_memory_search (DESIGN.md section 11 "Scene batch: registration") is the same append with every frame's
 // motion found on the device: the same schedule, its slots and steps without motions and the frames' bases behind the chains in the
 // one upload; each round's fuse is preceded by the round's scores and choice, and the ball chains run last, on the records
-// (scene_batch_register.hip). The bank's state is in scene_batch_memory.h for both units.
+// (scene_batch_register.hip). yh_scene_batch_append_memory_pyramid (DESIGN.md section 11 "Scene batch: pyramid registration") is that
+// again with each round's motions found coarse to fine (scene_batch_pyramid.hip): the frames' tables of level bases go up in a copy
+// of their own. The bank's state is in scene_batch_memory.h for the three units.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -30,6 +32,7 @@
 #include "scene_batch_memory.h"
 #include "scene_dev.h"
 #include "scene_memory_dev.h"
+#include "scene_pyramid_dev.h"
 #include "yh_internal.h"
 
 using namespace yh;
@@ -69,8 +72,8 @@ size_t steps_bytes(const yh_scene* h) { return scene_batch_steps_bytes(h); }
 
 // the buffers every memory append uses, at the first one: a batch that never remembers pays nothing
 // (a search: the score tables and records too, and the device table grows by the frames' bases - the stream is drained before
-// the smaller one goes, and whoever fails after this leaves nothing to replay)
-int memory_reserve(yh_scene_batch* hb, bool search) {
+// the smaller one goes, and whoever fails after this leaves nothing to replay; a pyramid append: its own buffers instead)
+int memory_reserve(yh_scene_batch* hb, bool search, bool pyramid) {
     yh_scene* h = &hb->core;
     if (!hb->memory) hb->memory = new yh_scene_batch_memory();
     yh_scene_batch_memory* m = hb->memory;
@@ -88,6 +91,7 @@ int memory_reserve(yh_scene_batch* hb, bool search) {
         SCHK(h, hipMalloc((void**)&m->table, need));
         m->table_bytes = need;
     }
+    if (pyramid) return scene_batch_pyramid_reserve(hb);
     return search ? scene_batch_register_reserve(hb) : YH_OK;
 }
 
@@ -131,8 +135,8 @@ int run_memory(yh_scene_batch* hb) {
     f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
     f.W = h->W; f.H = h->H; f.keep = m->keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = 0; f.g[i] = 0; }
-    if (m->searched) {   // the motions are found round by round; the ball chains need every frame's record
-        const int rs = scene_batch_register_search(hb, &f);
+    if (m->searched || m->pyramid) {   // the motions are found round by round; the ball chains need every frame's record
+        const int rs = m->pyramid ? scene_batch_pyramid_search(hb, &f) : scene_batch_register_search(hb, &f);
         return rs ? rs : scene_batch_register_balls(hb, b);
     }
     hipLaunchKernelGGL(batch_balls_memory, dim3((unsigned)m->chains), dim3(128), 0, h->stream, b, chains, steps, m->tabs);
@@ -147,11 +151,14 @@ int stream_of(const int32_t* streams, int b) { return streams ? streams[b] : 0; 
 
 // n_rot 0: gather and carry are one motion per frame. Otherwise n_rot bases per frame, searched around with `radius`: the slots and
 // steps carry no motion (the kernels read each frame's from its record) and the frames' bases follow the chains in the one upload.
-int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32_t* gather, const int32_t* carry, int keep, int max_age, int n_rot = 0, int radius = 0) {
+// plans given: a pyramid append, frame b's table of level bases in plans[b]; the slots and steps carry no motion either, there are no
+// plain bases, and the tables go up in a second copy.
+int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32_t* gather, const int32_t* carry, int keep, int max_age, int n_rot = 0, int radius = 0,
+                  const std::vector<ScenePyramidPlan>* plans = nullptr) {
     yh_scene* h = &hb->core;
     SCHK(h, hipSetDevice(h->dev));
-    const bool search = n_rot > 0;
-    int rc = memory_reserve(hb, search);
+    const bool search = n_rot > 0 && !plans, given = n_rot == 0;
+    int rc = memory_reserve(hb, search, plans != nullptr);
     if (rc) return rc;
     yh_scene_batch_memory* m = hb->memory;
     // the schedule: the frames of every stream in batch order; R rounds
@@ -182,7 +189,7 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
             e.mem_prev = r == 0 ? k.map[k.cur] : h->map + (size_t)f[r - 1] * npx;
             e.mem_next = r + 1 == f.size() ? k.map[k.cur ^ 1] : nullptr;
             e.frame = f[r];
-            for (int i = 0; i < 6 && !search; ++i) e.g[i] = gather[6 * f[r] + i];
+            for (int i = 0; i < 6 && given; ++i) e.g[i] = gather[6 * f[r] + i];
         }
         m->round_off.push_back(total);
     }
@@ -194,7 +201,7 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
         for (int b : frames_of[s]) {
             SceneBallsStep& e = steps[total++];
             e.frame = b;
-            for (int i = 0; i < 6 && !search; ++i) e.c[i] = carry[6 * b + i];
+            for (int i = 0; i < 6 && given; ++i) e.c[i] = carry[6 * b + i];
         }
     }
     if (search) {
@@ -210,8 +217,15 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
     }
     m->n = n; m->keep = keep; m->max_age = max_age;
     m->searched = search; m->n_rot = n_rot; m->radius = radius;
+    m->pyramid = plans != nullptr;
     // (from pageable memory: staged by the runtime before the call returns, as the caller's own arrays have been read by now)
     SCHK(h, hipMemcpyAsync(m->table, m->table_host.data(), m->table_host.size(), hipMemcpyHostToDevice, h->stream));
+    if (plans) {
+        m->pyr = (*plans)[0];   // (n_rot, levels, radius and refine are the call's)
+        m->pyr_host.resize((size_t)n);
+        for (int b = 0; b < n; ++b) m->pyr_host[b] = (*plans)[b].table;
+        SCHK(h, hipMemcpyAsync(m->pyr_table, m->pyr_host.data(), (size_t)n * sizeof(ScenePyramidTable), hipMemcpyHostToDevice, h->stream));
+    }
     if ((rc = run_memory(hb))) return rc;
     for (int s : named) m->bank[s].cur ^= 1;
     return YH_OK;
@@ -233,7 +247,7 @@ void scene_batch_memory_free(yh_scene_batch* hb) {
         void* bufs[] = { k.map[0], k.map[1], k.tab[0], k.tab[1] };
         for (void* b : bufs) if (b) hipFree(b);
     }
-    void* bufs[] = { m->stamp, m->tabs, m->table, m->reg_acc, m->reg_rec };
+    void* bufs[] = { m->stamp, m->tabs, m->table, m->reg_acc, m->reg_rec, m->pyr_maps, m->pyr_acc, m->pyr_table };
     for (void* b : bufs) if (b) hipFree(b);
     delete m;
     hb->memory = nullptr;
@@ -241,6 +255,7 @@ void scene_batch_memory_free(yh_scene_batch* hb) {
 
 bool scene_batch_memory_is_last(const yh_scene_batch* hb) { return hb->memory && hb->memory->frame != 0 && hb->memory->frame == hb->core.frames; }
 bool scene_batch_memory_is_search(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->searched; }
+bool scene_batch_memory_is_pyramid(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->pyramid; }
 }  // namespace yh
 
 namespace {
@@ -260,18 +275,18 @@ int append_memory_checks(yh_scene_batch* hb, int32_t n_frames, const int32_t* st
     return YH_OK;
 }
 
-// what both do around append_memory once the checks have passed (n_rot 0: the motions are given)
+// what all three do around append_memory once the checks have passed (n_rot 0: the motions are given; plans: a pyramid append)
 int append_memory_call(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16,
-                       int32_t keep, int32_t ball_max_age, int32_t n_rot, int32_t radius) {
+                       int32_t keep, int32_t ball_max_age, int32_t n_rot, int32_t radius, const std::vector<ScenePyramidPlan>* plans = nullptr) {
     yh_scene* h = &hb->core;
     ++h->frames;   // (earlier plans are of other frames, whatever becomes of these)
-    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius);
+    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, plans);
     yh_scene_batch_memory* m = hb->memory;
     if (rc) {
         // a call that fails after its checks leaves no frame and empties the memories of the streams it named
         h->ran = false; hb->n = 0;
         if (m) {
-            m->frame = 0; m->replayable = false; m->searched = false;
+            m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false;
             for (int b = 0; b < n_frames; ++b) m->bank[stream_of(streams, b)].stale = true;
         }
         return rc;
@@ -294,7 +309,7 @@ int replay_time(yh_scene_batch* hb, int reps, Run run, float* ms_out) {
     for (int r = 0; r < reps; ++r) {
         const int rc = run();
         if (rc) {
-            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false; m->searched = false;
+            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false;
             for (BankStream& k : m->bank) k.stale = true;
             return rc;
         }
@@ -332,10 +347,53 @@ int yh_scene_batch_append_memory_search(yh_scene_batch* hb, int32_t n_frames, co
     return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius);
 }
 
+int yh_scene_batch_append_memory_pyramid(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, int32_t n_rot, const int32_t* gather_q16,
+                                         const int32_t* carry_q16, int32_t levels, int32_t radius, int32_t refine, int32_t keep, int32_t ball_max_age) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    int rc = append_memory_checks(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    if (rc) return rc;
+    // (the four ranges here: they are about the call, not about frame 0)
+    if (n_rot < 1 || n_rot > SP_MAX_ROT) return h->fail(YH_EINVAL, "n_rot outside 1 .. 15");
+    if (levels < 1 || levels > SP_MAX_LEVELS) return h->fail(YH_EINVAL, "levels outside 1 .. 3");
+    if (radius < 0 || radius > SR_MAX_R) return h->fail(YH_EINVAL, "radius outside 0 .. 8");
+    if (refine < 0 || refine > SR_MAX_R) return h->fail(YH_EINVAL, "refine outside 0 .. 8");
+    std::vector<ScenePyramidPlan> plans((size_t)n_frames);
+    for (int b = 0; b < n_frames; ++b)
+        if ((rc = scene_pyramid_plan_make(h, n_rot, gather_q16 + (size_t)b * n_rot * 6, carry_q16 + (size_t)b * n_rot * 6, levels, radius, refine, plans[b]))) return hb->framed(b, rc);
+    return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, &plans);
+}
+
+int yh_scene_batch_pyramid_read(yh_scene_batch* hb, int32_t frame, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* sum_n) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    // (replayable: no memory has been reset since, as yh_scene_pyramid_read asks of the single handle)
+    if (!h->ran || !scene_batch_memory_is_pyramid(hb) || !hb->memory->replayable)
+        return h->fail(YH_ESTATE, "the last memory append of the batch was not yh_scene_batch_append_memory_pyramid (or a memory was reset since)");
+    if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
+    yh_scene_batch_memory* m = hb->memory;
+    const ScenePyramidPlan& plan = m->pyr;
+    if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
+    SCHK(h, hipSetDevice(h->dev));
+    const int hyp = plan.hyp(level), nu = 2 * plan.rho(level) + 1;
+    const unsigned long long* acc = m->pyr_acc + (size_t)frame * plan.acc_offset(plan.levels + 1) + plan.acc_offset(level);
+    int cen[SR_MAX_ROT][2];
+    unsigned long long sum = 0;
+    if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr_table[frame].centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
+    if (sum_n) SCHK(h, hipMemcpyAsync(&sum, acc, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
+    if (scores) SCHK(h, hipMemcpyAsync(scores, acc + 1, (size_t)hyp * nu * nu * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < hyp && centres; ++k) { centres[2 * k] = cen[k][0]; centres[2 * k + 1] = cen[k][1]; }
+    if (sum_n) *sum_n = sum;
+    return YH_OK;
+}
+
 int yh_scene_batch_motion_read(yh_scene_batch* hb, int32_t frame, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
     if (!hb) return YH_EINVAL;
     yh_scene* h = &hb->core;
-    if (!h->ran || !scene_batch_memory_is_search(hb)) return h->fail(YH_ESTATE, "the current frames did not come from yh_scene_batch_append_memory_search");
+    const bool pyramid = h->ran && scene_batch_memory_is_pyramid(hb);
+    if (!pyramid && (!h->ran || !scene_batch_memory_is_search(hb))) return h->fail(YH_ESTATE, "the current frames did not come from yh_scene_batch_append_memory_search");
+    if (pyramid && scores) return h->fail(YH_EINVAL, "the current frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_pyramid_read returns their level tables");
     if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
     SCHK(h, hipSetDevice(h->dev));
     yh_scene_batch_memory* m = hb->memory;
@@ -402,6 +460,8 @@ int yh_scene_batch_memory_reset(yh_scene_batch* hb, int32_t stream) {
 int yh_scene_batch_memory_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch) {
     if (!hb || reps < 1 || !ms_per_batch) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_pyramid(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_memory_pyramid_time replays them");
     if (h->ran && scene_batch_memory_is_search(hb))
         return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search: yh_scene_batch_memory_search_time replays them");
     if (!h->ran || !scene_batch_memory_is_last(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
@@ -415,6 +475,8 @@ int yh_scene_batch_memory_time(yh_scene_batch* hb, int32_t reps, float* ms_per_b
 int yh_scene_batch_memory_search_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
     if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_pyramid(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_memory_pyramid_time replays them");
     if (!h->ran || !scene_batch_memory_is_search(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
         return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_search (or a memory was reset or a slot staged since)");
     SCHK(h, hipSetDevice(h->dev));
@@ -422,6 +484,18 @@ int yh_scene_batch_memory_search_time(yh_scene_batch* hb, int32_t reps, float* m
     // slots that left - each predecessor's fused map - so the same tables and records again
     const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
     return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_register_search(hb, nullptr); }, ms_search);
+}
+
+int yh_scene_batch_memory_pyramid_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
+    if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (!h->ran || !scene_batch_memory_is_pyramid(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
+        return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_pyramid (or a memory was reset or a slot staged since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_batch_memory_search_time: the whole append from the tables on the device (select rewrites the same centres into
+    // them), then the clear and every round's levels, scores and choices alone, on each predecessor's fused map
+    const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
+    return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_pyramid_search(hb, nullptr); }, ms_search);
 }
 
 }  // extern "C"

@@ -87,6 +87,12 @@ int scene_batch_register_reserve(yh_scene_batch* hb) {
     return YH_OK;
 }
 
+void scene_batch_register_fuse_round(yh_scene_batch* hb, const SceneFuseParams& f, const SceneFuseSlot* round, unsigned count) {
+    yh_scene* h = &hb->core;
+    const unsigned gx = (unsigned)((h->W + SF_TW - 1) / SF_TW), gy = (unsigned)((h->H + SF_TH - 1) / SF_TH);
+    hipLaunchKernelGGL(batch_fuse_dev, dim3(gx, gy, count), dim3(256), 0, h->stream, f, round, (const SceneRegisterRecord*)hb->memory->reg_rec);
+}
+
 int scene_batch_register_search(yh_scene_batch* hb, const SceneFuseParams* f) {
     yh_scene* h = &hb->core;
     yh_scene_batch_memory* m = hb->memory;
@@ -97,13 +103,12 @@ int scene_batch_register_search(yh_scene_batch* hb, const SceneFuseParams* f) {
     SceneRegisterParams p;
     p.stamp = m->stamp; p.mem = nullptr; p.acc = m->reg_acc; p.W = h->W; p.H = h->H;
     const unsigned tiles = (unsigned)(((h->W + SR_TW - 1) / SR_TW) * ((h->H + SR_TH - 1) / SR_TH));   // <= 128 * 512
-    const unsigned gx = (unsigned)((h->W + SF_TW - 1) / SF_TW), gy = (unsigned)((h->H + SF_TH - 1) / SF_TH);
     for (size_t r = 0; r + 1 < m->round_off.size(); ++r) {
         const SceneFuseSlot* round = slots + m->round_off[r];
         const unsigned count = (unsigned)(m->round_off[r + 1] - m->round_off[r]);   // <= max_frames <= 256
         hipLaunchKernelGGL(batch_register_scores, dim3(tiles, (unsigned)m->n_rot, count), dim3(256), 0, h->stream, p, round, bases, stride);
         hipLaunchKernelGGL(batch_register_select, dim3(count), dim3(256), 0, h->stream, (const unsigned long long*)m->reg_acc, round, bases, m->reg_rec, stride);
-        if (f) hipLaunchKernelGGL(batch_fuse_dev, dim3(gx, gy, count), dim3(256), 0, h->stream, *f, round, (const SceneRegisterRecord*)m->reg_rec);
+        if (f) scene_batch_register_fuse_round(hb, *f, round, count);
     }
     SCHK(h, hipGetLastError());
     return YH_OK;

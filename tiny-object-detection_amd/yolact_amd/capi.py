@@ -196,6 +196,9 @@ SYMBOLS = [
     ("yh_scene_batch_append_memory_search", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i]),
     ("yh_scene_batch_motion_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_batch_memory_search_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_batch_append_memory_pyramid", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("yh_scene_batch_pyramid_read", _i, [_vp, _i, _i, _vp, _vp, _vp]),
+    ("yh_scene_batch_memory_pyramid_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
@@ -1544,8 +1547,46 @@ class SceneBatch:
         self._chk(self.L.yh_scene_batch_append_memory_search(self.h, n, _p(st) if st is not None else None, n_rot, _p(g), _p(c), radius, keep, ball_max_age))
         self.n, self._fields, self._search = n, False, (n_rot, radius)
 
+    def append_memory_pyramid(self, n, candidates=None, streams=None, levels=3, radius=8, refine=1, keep=224, ball_max_age=30):
+        """append_memory_search with every frame's candidates searched coarse to fine (DESIGN.md §11 "Scene batch: pyramid
+        registration"): frame b is Scene.append_memory_pyramid on the memory of streams[b], the calls made in batch order, so a
+        stream's later frame is registered against what its earlier frame has just fused. candidates as append_memory_search takes
+        them, at most 15 rows a frame; None: the identity alone. levels, radius, refine, keep and ball_max_age are one value per call;
+        read_motion(b) tells what frame b chose, read_pyramid(b, level) its levels' tables."""
+        if candidates is None:
+            candidates = [([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16])] * max(n, 0)
+        g = np.ascontiguousarray(np.array([m[0] for m in candidates], np.int32))   # (a value outside int32 raises here)
+        c = np.ascontiguousarray(np.array([m[1] for m in candidates], np.int32))
+        assert len(candidates) == max(n, 0), "candidates: one (gathers, carries) pair per frame"
+        assert n <= 0 or (g.ndim == 3 and g.shape[2] == 6 and c.shape == g.shape), "candidates: the same number of rows of six ints for every frame"
+        n_rot = g.shape[1] if g.ndim == 3 else 0
+        st = Engine._streams(streams, n)
+        self._chk(self.L.yh_scene_batch_append_memory_pyramid(self.h, n, _p(st) if st is not None else None, n_rot, _p(g), _p(c), levels, radius, refine, keep,
+                                                              ball_max_age))
+        self.n, self._fields, self._pyramid = n, False, (n_rot, levels, radius, refine)
+        self._search = (n_rot + 1, refine)   # (read_motion(scores=True) is refused after this append: it names read_pyramid)
+
+    def read_pyramid(self, frame, level):
+        """Level `level` (0 .. levels) of what the last append_memory_pyramid did for frame `frame`: the dict Scene.read_pyramid
+        returns (centres, scores, sum_n)."""
+        n_rot, levels, radius, refine = getattr(self, "_pyramid", None) or (1, 0, 0, 0)
+        ok = 0 <= level <= levels                # (otherwise the library refuses before it writes anything)
+        p, hyp = (radius if level == levels else refine), n_rot + (1 if level == 0 else 0)
+        out = dict(centres=np.zeros((hyp, 2), np.int32), scores=np.zeros((hyp, 2 * p + 1, 2 * p + 1), np.uint64))
+        sum_n = C.c_uint64()
+        self._chk(self.L.yh_scene_batch_pyramid_read(self.h, frame, level, _p(out["centres"]) if ok else None, _p(out["scores"]) if ok else None, C.byref(sum_n)))
+        out["sum_n"] = sum_n.value
+        return out
+
+    def memory_pyramid_time(self, reps=20):
+        """(ms per batch, ms of the registration launches alone) of the last append_memory_pyramid, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_batch_memory_pyramid_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
     def read_motion(self, frame, scores=False):
-        """What the last append_memory_search chose for frame `frame`: the dict Scene.read_motion returns."""
+        """What the last append_memory_search or append_memory_pyramid chose for frame `frame`: the dict Scene.read_motion returns
+        (after a pyramid append scores=True is refused: read_pyramid has the tables)."""
         out = dict(gather=np.zeros(6, np.int32), carry=np.zeros(6, np.int32), chosen=np.zeros(3, np.int32), score=np.zeros(3, np.uint64))
         table = None
         if scores and getattr(self, "_search", None):

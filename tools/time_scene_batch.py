@@ -27,10 +27,16 @@ frames through one Scene.append_memory_search (yh_scene_memory_search_time per f
 with bases 0.01 rad apart. Then, for n = 8 and (5, 4) on the robots + balls frame in every slot, alternated with the single handle, one
 warm-up each, five runs of 30 replays: the two ratios and the single handle's spread (what tests/test_scene_batch_register.py derives
 its ceiling from).
+--memory-pyramid [--levels L --radius R --refine r --n-rot K]: the batched pyramid append instead (yh_scene_batch_append_memory_pyramid,
+DESIGN.md §11 "Scene batch: pyramid registration"; yh_scene_batch_memory_pyramid_time), no plans, at (n_rot, levels, radius, refine) =
+(5, 3, 8, 1) or the one given: the same columns as --memory-search, beside the same frames through one Scene.append_memory_pyramid
+(yh_scene_memory_pyramid_time per frame). Then, for n = 8 and (5, 3, 8, 1) on the robots + balls frame in every slot, alternated with
+the single handle, one warm-up each, five runs of 30 replays: the two ratios and the single handle's spread (what
+tests/test_scene_batch_pyramid.py derives its ceiling from).
 --frames n,n,..: those batch sizes only.
 --lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
 LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box.
-Usage: python tools/time_scene_batch.py [sets] [reps] [--memory | --memory-search [--n-rot K --radius R] | --turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
+Usage: python tools/time_scene_batch.py [sets] [reps] [--memory | --memory-search [--n-rot K --radius R] | --memory-pyramid [--levels L --radius R --refine r --n-rot K] | --turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,6 +44,7 @@ sys.path.insert(0, os.path.join(ROOT, "tiny-object-detection_amd"))
 from yolact_amd import capi
 args, tau, tour, plain, conn_tour, K, sizes, lib, memory = [], None, False, False, 4, 3, None, None, False
 search, n_rot_arg, radius_arg = False, None, None
+pyramid, levels_arg, refine_arg = False, None, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--turn-price": tau = float(next(it))
@@ -45,6 +52,9 @@ for a in it:
     elif a == "--tour": plain = True
     elif a == "--memory": memory = True
     elif a == "--memory-search": search = True
+    elif a == "--memory-pyramid": pyramid = True
+    elif a == "--levels": levels_arg = int(next(it))
+    elif a == "--refine": refine_arg = int(next(it))
     elif a == "--n-rot": n_rot_arg = int(next(it))
     elif a == "--radius": radius_arg = int(next(it))
     elif a == "--connectivity": conn_tour = int(next(it))
@@ -58,7 +68,12 @@ if tour and not tau: sys.exit("--turn-tour needs --turn-price P")
 if plain and tau: sys.exit("--tour is the plain tour: no --turn-price")
 if memory and (plain or tau): sys.exit("--memory times the append alone: no --tour, no --turn-price")
 if search and (memory or plain or tau): sys.exit("--memory-search times the search append alone: no --memory, no --tour, no --turn-price")
-if (n_rot_arg is None) != (radius_arg is None) or (n_rot_arg is not None and not search): sys.exit("--n-rot K and --radius R go together, with --memory-search")
+if pyramid and (search or memory or plain or tau): sys.exit("--memory-pyramid times the pyramid append alone: no --memory, no --memory-search, no --tour, no --turn-price")
+if pyramid:
+    given = [v is not None for v in (n_rot_arg, levels_arg, radius_arg, refine_arg)]
+    if any(given) and not all(given): sys.exit("--n-rot K, --levels L, --radius R and --refine r go together")
+elif (n_rot_arg is None) != (radius_arg is None) or (n_rot_arg is not None and not search) or levels_arg is not None or refine_arg is not None:
+    sys.exit("--n-rot K and --radius R go together, with --memory-search; --levels and --refine go with --memory-pyramid")
 if sizes is None: sizes = (1, 2, 8, 16, 64) if plain else (1, 2, 4, 8, 16, 64)
 own = tau or plain   # the plan columns are one kind of its own instead of the plan with connectivity 4 and 8
 if lib:
@@ -66,7 +81,7 @@ if lib:
 import yolact_amd as ya
 H, W = 480, 640
 TARGETS = [(70, 67), (515, 410), (320, 40), (600, 100), (30, 440), (250, 300)][:K]   # tools/time_tour.py's camera targets
-print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (", memory append" if memory else "") + (", search append" if search else "") + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (", memory append" if memory else "") + (", search append" if search else "") + (", pyramid append" if pyramid else "") + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
 
 
 def frame(seed):
@@ -126,9 +141,10 @@ if memory:
     sys.exit(0)
 
 
-def search_columns(frames, prior, cands, radius, runs, replays):
+def search_columns(frames, prior, cands, radius, runs, replays, pyr=None):
     """(single, a stream per frame, all on stream 0): lists over the runs of (ms per frame, ms of the registration alone per frame)
-    for these frames, alternated run by run, one warm-up each; every memory filled before it is timed"""
+    for these frames, alternated run by run, one warm-up each; every memory filled before it is timed. pyr = (levels, refine): the
+    pyramid append instead of the search append"""
     n = len(frames)
     motion = ya.scene_motion(*prior)
     sb = ya.SceneBatch(W, H, n)
@@ -140,16 +156,24 @@ def search_columns(frames, prior, cands, radius, runs, replays):
         sc.append_memory(frames[-1][0], frame_u32=frames[-1][1], motion=motion)
         t, r = 0.0, 0.0
         for d, f in (frames[:1] if same else frames):      # (the same frame in every slot: one replay stands for all)
-            sc.append_memory_search(d, frame_u32=f, candidates=cands, radius=radius)
-            a, b = sc.memory_search_time(replays)
+            if pyr:
+                sc.append_memory_pyramid(d, frame_u32=f, candidates=cands, levels=pyr[0], radius=radius, refine=pyr[1])
+                a, b = sc.memory_pyramid_time(replays)
+            else:
+                sc.append_memory_search(d, frame_u32=f, candidates=cands, radius=radius)
+                a, b = sc.memory_search_time(replays)
             t += a / (1 if same else n); r += b / (1 if same else n)
         return t, r
 
     def batch(streams):
         sb.memory_reset()
         sb.append_memory(n, motions=[motion] * n, streams=streams)
-        sb.append_memory_search(n, candidates=[cands] * n, streams=streams, radius=radius)
-        a, b = sb.memory_search_time(replays)
+        if pyr:
+            sb.append_memory_pyramid(n, candidates=[cands] * n, streams=streams, levels=pyr[0], radius=radius, refine=pyr[1])
+            a, b = sb.memory_pyramid_time(replays)
+        else:
+            sb.append_memory_search(n, candidates=[cands] * n, streams=streams, radius=radius)
+            a, b = sb.memory_search_time(replays)
         return a / n, b / n
 
     per_frame = list(range(n)) if n <= capi.SCENE_STREAMS_MAX else None
@@ -180,6 +204,26 @@ if search:
     print(f"  single handle          {med(ms(s)):.4f} ms per frame, spread (max - min) / median {100 * spread(ms(s)):.2f} %")
     print(f"  a stream per frame     {med(ms(a)):.4f} ms per frame, spread {100 * spread(ms(a)):.2f} %, ratio to the single handle {med(ms(a)) / med(ms(s)):.3f}")
     print(f"  all on one stream      {med(ms(o)):.4f} ms per frame, spread {100 * spread(ms(o)):.2f} %, ratio to the single handle {med(ms(o)) / med(ms(s)):.3f}")
+    sc.close()
+    sys.exit(0)
+if pyramid:
+    prior = (3.0, -2.0, 0.05)                             # tools/time_scene.py's: the prior is right, the search confirms it
+    n_rot, levels, radius, refine = (n_rot_arg, levels_arg, radius_arg, refine_arg) if n_rot_arg is not None else (5, 3, 8, 1)
+    cell = lambda c: f"{med([v[0] for v in c]):.4f} ({med([v[1] for v in c]):.4f})"
+    print("pyramid append, ms per frame (median of the sets), the registration launches alone in brackets:")
+    print(f"{'n':>4} {'n_rot':>5} {'L':>2} {'R':>2} {'r':>2} {'single handle':>18} {'a stream per frame':>20} {'all on one stream':>20}")
+    cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
+    for n in sizes:
+        cols = search_columns([frame(b) for b in range(n)], prior, cands, radius, sets, reps, (levels, refine))
+        print(f"{n:4d} {n_rot:5d} {levels:2d} {radius:2d} {refine:2d} {cell(cols[0]):>18} {cell(cols[1]):>20} {cell(cols[2]):>20}")
+    cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=2)
+    s, a, o = search_columns([frame(0)] * 8, prior, cands, 8, 5, 30, (3, 1))
+    ms = lambda c: [v[0] for v in c]
+    spread = lambda v: (max(v) - min(v)) / med(v)
+    print("n = 8, (n_rot, L, R, r) = (5, 3, 8, 1), the robots + balls frame of tools/time_scene.py in every slot, 5 runs of 30 replays alternated:")
+    print(f"  single handle          {med(ms(s)):.4f} ms per frame ({cell(s)}), spread (max - min) / median {100 * spread(ms(s)):.2f} %")
+    print(f"  a stream per frame     {med(ms(a)):.4f} ms per frame ({cell(a)}), spread {100 * spread(ms(a)):.2f} %, ratio to the single handle {med(ms(a)) / med(ms(s)):.3f}")
+    print(f"  all on one stream      {med(ms(o)):.4f} ms per frame ({cell(o)}), spread {100 * spread(ms(o)):.2f} %, ratio to the single handle {med(ms(o)) / med(ms(s)):.3f}")
     sc.close()
     sys.exit(0)
 for n in sizes:
