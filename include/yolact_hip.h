@@ -667,6 +667,28 @@ int yh_scene_append_memory_pyramid(yh_scene* h, const uint16_t* depth_host, cons
  * append was a pyramid append; YH_EINVAL for a level outside 0 .. levels. After a pyramid append yh_scene_motion_read returns the
  * gather, carry, chosen and score (S chosen, S(0, 0, 0), sum_n) with scores NULL, and YH_EINVAL naming this call if scores is given. */
 int yh_scene_pyramid_read(yh_scene* h, int32_t level, int32_t* centres /* [hyp][2] */, uint64_t* scores /* [hyp][2p+1][2p+1] */, uint64_t* sum_n);
+/* Scene memory: normalised registration (DESIGN.md section 11 "Scene memory: normalised registration"): yh_scene_append_memory_search
+ * with the choice made by a normalised score, for maps that are dense - a height map stamped at every pixel the camera sees -, where
+ * the plain S favours whichever candidate keeps the most pixels inside the frame. Candidates, int32 conditions and refusals are the
+ * plain search's. For candidate (k, u, v), over the frame pixels whose source (sx + u, sy + v) lies in the frame ("inside"; the test
+ * is made on the 64-bit values), Q = M at that source:
+ *   S = sum of min(N, Q) - the plain S exactly -, T = sum of N + Q, C = the number of inside pixels; U = T - S = sum of max(N, Q).
+ *   qualified   C >= min_inside (1 .. width x height) and U > 0. The score S / U is 1 wherever the maps agree on their overlap,
+ *               however small that is: min_inside is what keeps a sliver of overlap from winning.
+ *   choice      among the qualified candidates the largest S / U, compared as exact 128-bit cross products (no division, no float);
+ *               ties go to the smaller u^2 + v^2, then the smaller k, then the smaller v, then the smaller u. None qualified (an empty
+ *               frame on an empty memory, or every candidate short of min_inside): the prior (0, 0, 0).
+ * Everything after the choice is yh_scene_append_memory_search's; with n_rot = 1 and radius = 0 it IS yh_scene_append_memory with
+ * row 0. Integer only, bit-exact, no host wait. Afterwards yh_scene_motion_read works as after a plain search (score = S chosen,
+ * S(0, 0, 0), sum_n; scores = the S table). YH_EINVAL with nothing touched as there, and for min_inside out of range. */
+int yh_scene_append_memory_search_norm(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                       const int32_t* gather_q16 /* [n_rot][6] */, const int32_t* carry_q16 /* [n_rot][6] */, int32_t radius,
+                                       int32_t min_inside, int32_t keep, int32_t ball_max_age);
+/* What the last yh_scene_append_memory_search_norm saw beside yh_scene_motion_read's: the tables totals (T) and inside (C), u64
+ * [n_rot][2 radius + 1][2 radius + 1] laid out as scores there, (S, T, C) of the choice and of (0, 0, 0), and qualified: 0 if no
+ * candidate qualified. Any pointer may be NULL. Waits. YH_ESTATE unless the handle's last memory append was a normalised search. */
+int yh_scene_motion_norm_read(yh_scene* h, uint64_t* totals /* [n_rot][2R+1][2R+1] or NULL */, uint64_t* inside /* likewise */,
+                              uint64_t* chosen_stc /* [3] = S, T, C */, uint64_t* prior_stc /* [3] */, int32_t* qualified);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

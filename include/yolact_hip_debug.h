@@ -134,6 +134,18 @@ int yh_scene_op_register(yh_scene* h, const uint32_t* n_host, const uint32_t* m_
  * started from, ms_per_frame; then its registration launches alone (the levels, the clear, scores and select per level),
  * ms_search. Both rewrite the same values and commit nothing. YH_ESTATE unless the handle's last frame is a pyramid append. */
 int yh_scene_memory_pyramid_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search);
+/* The same for a frame that came from yh_scene_append_memory_search_norm (yh_scene_time, yh_scene_memory_time,
+ * yh_scene_memory_search_time and yh_scene_memory_pyramid_time refuse such a frame with YH_ESTATE and name this hook): the whole
+ * append replayed from the state it started from, ms_per_frame; then its registration launches alone (the clear, the three tables,
+ * the choice), ms_search. Both rewrite the same values and commit nothing. YH_ESTATE unless the last frame is a normalised search. */
+int yh_scene_memory_search_norm_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search);
+/* Test hook: the normalised registration's two kernels alone on two caller-given maps u32 [h][w], as yh_scene_op_register runs the
+ * plain ones, with min_inside as yh_scene_append_memory_search_norm takes it (the same YH_EINVAL checks). scores (S), totals (T) and
+ * inside (C), each u64 [n_rot][2 radius + 1][2 radius + 1]; chosen [3] = k, u, v; qualified; sum_n: each may be NULL. Waits. Reads
+ * and writes nothing of the handle's frame, memory or plans. */
+int yh_scene_op_register_norm(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
+                              int32_t radius, int32_t min_inside, uint64_t* scores, uint64_t* totals, uint64_t* inside, int32_t* chosen /* [3] */,
+                              int32_t* qualified, uint64_t* sum_n);
 /* Test hook: the pyramid registration alone - the levels, every level's scores, the descent and the choice - on two caller-given
  * maps u32 [h][w], with buffers of its own; n_rot gathers, levels, radius and refine as yh_scene_append_memory_pyramid takes them
  * (the same YH_EINVAL checks; there are no carries). chosen [3] = k, u, v; score [3] = S chosen, S(0, 0, 0), sum_n; pyr_n and

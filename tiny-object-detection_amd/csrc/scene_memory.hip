@@ -13,6 +13,8 @@
 // chosen one in a device record, which the fuse and the ball carry read (scene_fuse_dev, scene_balls_memory_dev).
 // yh_scene_append_memory_pyramid (DESIGN.md section 11 "Scene memory: pyramid registration") is that append with the candidates
 // searched coarse to fine (scene_pyramid.hip), into the same record.
+// yh_scene_append_memory_search_norm (DESIGN.md section 11 "Scene memory: normalised registration") is the search append with the
+// candidates ranked by the normalised score (scene_register_norm.hip), into the same record and an extension of it.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -23,6 +25,7 @@
 #include "scene_memory_dev.h"
 #include "scene_pyramid_dev.h"
 #include "scene_register_dev.h"
+#include "scene_register_norm_dev.h"
 #include "yh_internal.h"
 
 using namespace yh;
@@ -48,6 +51,10 @@ struct yh_scene_memory {
     SceneRegisterRecord* reg_rec = nullptr;
     bool searched = false;
     SceneRegisterBases last_bases = {};
+    // normalised registration: norm_min_inside != 0: the last memory append was a normalised search (searched is true as well: the
+    // record, sum_n and the S table are where a plain search leaves them) - reg_acc holds T and C behind S, norm_rec the extension
+    SceneRegisterNormRecord* norm_rec = nullptr;
+    int norm_min_inside = 0;
     // pyramid registration: allocated at the first pyramid append. pyramid: the last memory append was one - last_pyr is its plan,
     // reg_rec its choice, pyr.acc its level tables, pyr.table the centres (searched is false then)
     ScenePyramidBufs pyr;
@@ -86,15 +93,17 @@ int memory_reserve(yh_scene* h) {
 
 int register_reserve(yh_scene* h) {
     yh_scene_memory* m = h->memory;
-    if (!m->reg_acc) SCHK(h, hipMalloc((void**)&m->reg_acc, scene_register_acc_bytes()));
+    if (!m->reg_acc) SCHK(h, hipMalloc((void**)&m->reg_acc, scene_register_norm_acc_bytes()));   // (the plain search's table is its first third)
+    if (!m->norm_rec) SCHK(h, hipMalloc((void**)&m->norm_rec, sizeof(SceneRegisterNormRecord)));
     if (!m->reg_rec) SCHK(h, hipMalloc((void**)&m->reg_rec, sizeof(SceneRegisterRecord)));
     return YH_OK;
 }
 
 // the launches of one memory append: reads map[from] / tab[from], writes map[from ^ 1] / tab[from ^ 1] and the handle's fields
 // (bases or pyr given: the motion is searched for around them and read from the device record, q.g and q.c are not used; upload:
-// the pyramid's table goes to the device first - a replay finds it there)
-int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr, const ScenePyramidPlan* pyr = nullptr, bool upload = false) {
+// the pyramid's table goes to the device first - a replay finds it there; min_inside != 0 with bases: the normalised search)
+int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr, const ScenePyramidPlan* pyr = nullptr, bool upload = false,
+               int min_inside = 0) {
     yh_scene_memory* m = h->memory;
     SceneParams p;
     p.depth = h->depth; p.cls_id = nullptr; p.frame = q.frame; p.frame_mode = 1;
@@ -116,7 +125,8 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBa
         return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
     }
     if (bases) {
-        const int rs = scene_register_search(h, m->stamp, m->map[from], *bases, m->reg_acc, m->reg_rec);
+        const int rs = min_inside ? scene_register_norm_search(h, m->stamp, m->map[from], *bases, min_inside, m->reg_acc, m->reg_rec, m->norm_rec)
+                                  : scene_register_search(h, m->stamp, m->map[from], *bases, m->reg_acc, m->reg_rec);
         return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
     }
     hipLaunchKernelGGL(scene_balls_memory, dim3(1), dim3(128), 0, h->stream, b);
@@ -125,7 +135,8 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBa
     return YH_OK;
 }
 
-int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q, const SceneRegisterBases* bases, const ScenePyramidPlan* pyr) {
+int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, MemoryCall q, const SceneRegisterBases* bases, const ScenePyramidPlan* pyr,
+                  int min_inside) {
     SCHK(h, hipSetDevice(h->dev));
     int rc = memory_reserve(h);
     if (rc) return rc;
@@ -138,25 +149,26 @@ int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame
     if ((rc = host_sources_done(h, depth_host, frame_on_device ? nullptr : frame))) return rc;
     yh_scene_memory* m = h->memory;
     if (pyr) m->last_pyr = *pyr;   // (the upload reads the handle's copy: the caller's is free when the call returns)
-    if ((rc = run_memory(h, q, m->cur, bases, pyr ? &m->last_pyr : nullptr, true))) return rc;
+    if ((rc = run_memory(h, q, m->cur, bases, pyr ? &m->last_pyr : nullptr, true, min_inside))) return rc;
     m->cur ^= 1;
     m->last = q;
     m->searched = bases != nullptr;
     m->pyramid = pyr != nullptr;
+    m->norm_min_inside = bases ? min_inside : 0;
     if (bases) m->last_bases = *bases;
     return YH_OK;
 }
 
 // what every memory append does around append_memory: the frame count, and what a failure or a success leaves
 int append_memory_call(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int frame_on_device, const MemoryCall& q, const SceneRegisterBases* bases,
-                       const ScenePyramidPlan* pyr = nullptr) {
+                       const ScenePyramidPlan* pyr = nullptr, int min_inside = 0) {
     ++h->frames;   // (earlier plans are of another frame, whatever becomes of this one)
-    const int rc = append_memory(h, depth_host, frame, frame_on_device, q, bases, pyr);
+    const int rc = append_memory(h, depth_host, frame, frame_on_device, q, bases, pyr, min_inside);
     yh_scene_memory* m = h->memory;
     if (rc) {
         // a call that fails after its checks leaves no frame and an empty memory
         h->ran = false;
-        if (m) { m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; }
+        if (m) { m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; }
         return rc;
     }
     m->frame = h->frames;
@@ -176,10 +188,16 @@ int replay_time(yh_scene* h, int reps, bool search_only, float* ms_out) {
     // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
     // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
     for (int r = 0; r < reps; ++r) {
-        const int rc = !search_only ? run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr, m->pyramid ? &m->last_pyr : nullptr)
+        const int rc = !search_only ? run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr, m->pyramid ? &m->last_pyr : nullptr, false, m->norm_min_inside)
                        : m->pyramid ? scene_pyramid_search(h, m->stamp, m->map[m->cur ^ 1], m->last_pyr, m->pyr, m->reg_rec, false)
-                                    : scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec);
-        if (rc) { hipEventDestroy(a); hipEventDestroy(b); h->ran = false; m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; return rc; }
+                       : m->norm_min_inside
+                           ? scene_register_norm_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->norm_min_inside, m->reg_acc, m->reg_rec, m->norm_rec)
+                           : scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec);
+        if (rc) {
+            hipEventDestroy(a); hipEventDestroy(b);
+            h->ran = false; m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0;
+            return rc;
+        }
     }
     SCHK(h, hipEventRecord(b, h->stream));
     SCHK(h, hipEventSynchronize(b));
@@ -196,7 +214,7 @@ namespace yh {
 void scene_memory_free(yh_scene* h) {
     yh_scene_memory* m = h->memory;
     if (!m) return;
-    void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1], m->reg_acc, m->reg_rec };
+    void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1], m->reg_acc, m->reg_rec, m->norm_rec };
     for (void* b : bufs) if (b) hipFree(b);
     scene_pyramid_release(m->pyr);
     delete m;
@@ -205,6 +223,7 @@ void scene_memory_free(yh_scene* h) {
 
 bool scene_memory_is_last(const yh_scene* h) { return h->memory && h->memory->frame != 0 && h->memory->frame == h->frames; }
 bool scene_memory_is_search(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->searched; }
+bool scene_memory_is_norm(const yh_scene* h) { return scene_memory_is_search(h) && h->memory->norm_min_inside != 0; }
 bool scene_memory_is_pyramid(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->pyramid; }
 }  // namespace yh
 
@@ -235,6 +254,40 @@ int yh_scene_append_memory_search(yh_scene* h, const uint16_t* depth_host, const
     MemoryCall q;   // (its motion stays zero: the kernels read the chosen one from the device record)
     q.keep = keep; q.max_age = ball_max_age;
     return append_memory_call(h, depth_host, frame, frame_on_device, q, &bases);
+}
+
+int yh_scene_append_memory_search_norm(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                       const int32_t* gather_q16, const int32_t* carry_q16, int32_t radius, int32_t min_inside, int32_t keep, int32_t ball_max_age) {
+    if (!h || !depth_host || !frame || !gather_q16 || !carry_q16) return YH_EINVAL;
+    const int rc = scene_register_bases_check(h, n_rot, gather_q16, carry_q16, radius);
+    if (rc) return rc;
+    if (min_inside < 1 || (long long)min_inside > (long long)h->W * h->H) return h->fail(YH_EINVAL, "min_inside outside 1 .. width x height");
+    if (keep < 0 || keep > 256) return h->fail(YH_EINVAL, "keep outside 0 .. 256");
+    if (ball_max_age < 0 || ball_max_age > 255) return h->fail(YH_EINVAL, "ball_max_age outside 0 .. 255");
+    SceneRegisterBases bases = {};
+    bases.n_rot = n_rot; bases.radius = radius;
+    for (int k = 0; k < n_rot; ++k)
+        for (int i = 0; i < 6; ++i) { bases.g[k][i] = gather_q16[6 * k + i]; bases.c[k][i] = carry_q16[6 * k + i]; }
+    MemoryCall q;   // (its motion stays zero: the kernels read the chosen one from the device record)
+    q.keep = keep; q.max_age = ball_max_age;
+    return append_memory_call(h, depth_host, frame, frame_on_device, q, &bases, nullptr, min_inside);
+}
+
+int yh_scene_motion_norm_read(yh_scene* h, uint64_t* totals, uint64_t* inside, uint64_t* chosen_stc, uint64_t* prior_stc, int32_t* qualified) {
+    if (!h) return YH_EINVAL;
+    yh_scene_memory* m = h->memory;
+    if (!m || m->stale || !m->searched || !m->norm_min_inside)
+        return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search_norm (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    SceneRegisterNormRecord ext;
+    const size_t words = register_norm_table_words(m->last_bases.n_rot, m->last_bases.radius);
+    SCHK(h, hipMemcpyAsync(&ext, m->norm_rec, sizeof(ext), hipMemcpyDeviceToHost, h->stream));
+    if (totals) SCHK(h, hipMemcpyAsync(totals, m->reg_acc + 1 + words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    if (inside) SCHK(h, hipMemcpyAsync(inside, m->reg_acc + 1 + 2 * words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; ++i) { if (chosen_stc) chosen_stc[i] = ext.chosen[i]; if (prior_stc) prior_stc[i] = ext.prior[i]; }
+    if (qualified) *qualified = ext.qualified;
+    return YH_OK;
 }
 
 int yh_scene_append_memory_pyramid(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
@@ -314,12 +367,14 @@ int yh_scene_memory_reset(yh_scene* h) {
     m->frame = 0;      // (nothing to replay: the state the last memory append started from is gone)
     m->searched = false;
     m->pyramid = false;
+    m->norm_min_inside = 0;
     return memory_reserve(h);
 }
 
 int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!scene_memory_is_last(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory (or the memory was reset since)");
+    if (h->memory->norm_min_inside) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (h->memory->searched) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");
     if (h->memory->pyramid) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
     SCHK(h, hipSetDevice(h->dev));
@@ -329,6 +384,7 @@ int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
 int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
     if (scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
+    if (scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (!scene_memory_is_search(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search (or the memory was reset since)");
     SCHK(h, hipSetDevice(h->dev));
     // the whole append first, then its registration launches alone on what that left: the same record and scores again
@@ -336,8 +392,18 @@ int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, 
     return rc ? rc : replay_time(h, reps, true, ms_search);
 }
 
+int yh_scene_memory_search_norm_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
+    if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (!scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search_norm (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_memory_search_time: the whole append, then its registration launches alone (the clear, the three tables, the choice)
+    const int rc = replay_time(h, reps, false, ms_per_frame);
+    return rc ? rc : replay_time(h, reps, true, ms_search);
+}
+
 int yh_scene_memory_pyramid_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (!scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_pyramid (or the memory was reset since)");
     SCHK(h, hipSetDevice(h->dev));
     // as yh_scene_memory_search_time: the whole append, then its registration launches alone (the levels, the clear, scores and select)

@@ -172,6 +172,10 @@ SYMBOLS = [
     ("yh_scene_motion_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_memory_search_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_op_register", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    ("yh_scene_append_memory_search_norm", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i]),
+    ("yh_scene_motion_norm_read", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_memory_search_norm_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_op_register_norm", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_scene_append_memory_pyramid", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i]),
     ("yh_scene_pyramid_read", _i, [_vp, _i, _vp, _vp, _vp]),
     ("yh_scene_memory_pyramid_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
@@ -1173,6 +1177,63 @@ class Scene:
         """(ms per frame, ms of the registration alone) of the last append_memory_search, replayed; commits nothing."""
         ms, ms_search = C.c_float(), C.c_float()
         self._chk(self.L.yh_scene_memory_search_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
+    def append_memory_search_norm(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, candidates=None, radius=4, min_inside=None, keep=224,
+                                  ball_max_age=30):
+        """append_memory_search with the choice made by the normalised score S / (T - S) over the pixels both maps cover (DESIGN.md §11
+        "Scene memory: normalised registration"), for dense maps. candidates and radius as there; min_inside: how many frame pixels
+        a candidate must keep inside the frame to qualify, 1 .. W H; None: W H // 4. read_motion works as after append_memory_search,
+        read_motion_norm returns the rest."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        g, c = ([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16]) if candidates is None else candidates
+        g, c = np.ascontiguousarray(np.array(g, np.int32)), np.ascontiguousarray(np.array(c, np.int32))   # (a value outside int32 raises here)
+        assert g.ndim == 2 and g.shape[1] == 6 and c.shape == g.shape
+        if min_inside is None:
+            min_inside = (self.W * self.H) // 4
+        if frame_dev_ptr is not None:
+            f, on_device = C.c_void_p(frame_dev_ptr), 1
+        else:
+            keepalive = SceneBatch.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+            assert keepalive.size == self.W * self.H
+            f, on_device = _p(keepalive), 0
+        self._chk(self.L.yh_scene_append_memory_search_norm(self.h, _p(depth), f, on_device, len(g), _p(g), _p(c), radius, min_inside, keep, ball_max_age))
+        self._search = (len(g), radius)
+
+    def read_motion_norm(self):
+        """What the last append_memory_search_norm saw beside read_motion's: totals (T) and inside (C), u64 [n_rot][2 radius + 1]
+        [2 radius + 1] laid out as read_motion's scores, chosen_stc and prior_stc u64 [3] = (S, T, C) of the choice and of (0, 0, 0),
+        and qualified: False if no candidate qualified."""
+        n_rot, radius = getattr(self, "_search", None) or (1, 0)
+        shape = (n_rot, 2 * radius + 1, 2 * radius + 1)
+        out = dict(totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64), chosen_stc=np.zeros(3, np.uint64), prior_stc=np.zeros(3, np.uint64))
+        q = C.c_int32()
+        self._chk(self.L.yh_scene_motion_norm_read(self.h, _p(out["totals"]), _p(out["inside"]), _p(out["chosen_stc"]), _p(out["prior_stc"]), C.byref(q)))
+        out["qualified"] = bool(q.value)
+        return out
+
+    def op_register_norm(self, n, m, gathers, radius, min_inside):
+        """Test hook (yh_scene_op_register_norm): the normalised registration's kernels alone on stamps n and memory m, u32 [h][w];
+        gathers [n_rot][6]. Returns dict(scores, totals, inside: u64 [n_rot][2 radius + 1][2 radius + 1], chosen (k, u, v), qualified,
+        sum_n); commits nothing."""
+        n, m = np.ascontiguousarray(n, np.uint32), np.ascontiguousarray(m, np.uint32)
+        assert n.shape == (self.H, self.W) and m.shape == (self.H, self.W)
+        g = np.ascontiguousarray(np.array(gathers, np.int32))
+        assert g.ndim == 2 and g.shape[1] == 6
+        ok = 1 <= len(g) <= 16 and 0 <= radius <= 8   # (otherwise the library refuses before it writes anything)
+        shape = (len(g), 2 * radius + 1, 2 * radius + 1) if ok else (1,)
+        out = dict(scores=np.zeros(shape, np.uint64), totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64))
+        chosen, q, sum_n = np.zeros(3, np.int32), C.c_int32(), C.c_uint64()
+        self._chk(self.L.yh_scene_op_register_norm(self.h, _p(n), _p(m), len(g), _p(g), radius, min_inside, _p(out["scores"]), _p(out["totals"]), _p(out["inside"]),
+                                                   _p(chosen), C.byref(q), C.byref(sum_n)))
+        out.update(chosen=tuple(int(v) for v in chosen), qualified=bool(q.value), sum_n=sum_n.value)
+        return out
+
+    def memory_search_norm_time(self, reps=20):
+        """(ms per frame, ms of the registration alone) of the last append_memory_search_norm, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_memory_search_norm_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
         return ms.value, ms_search.value
 
     def append_memory_pyramid(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, candidates=None, levels=3, radius=8, refine=1, keep=224,

@@ -7,7 +7,10 @@ against the memory append, likewise, over (n_rot, radius) = (1, 0), (1, 4), (5, 
 registration launches alone, and its rate in pixel-candidates per second.
 --memory-pyramid: the pyramid append (yh_scene_append_memory_pyramid: the registration made coarse to fine) against the search
 append at the same n_rot with radius 8, likewise, over (n_rot, levels, radius, refine) = (1, 3, 8, 1), (5, 3, 8, 1), (9, 3, 8, 2):
-ms per frame of both and ms of the registration launches alone of both, their ratio and the spread of each."""
+ms per frame of both and ms of the registration launches alone of both, their ratio and the spread of each.
+--memory-search-norm: the normalised search append (yh_scene_append_memory_search_norm: three sums per shift, no empty-tile exit)
+against the plain search append with the same candidates, likewise, over the grids of --memory-search: ms per frame of both, ms of
+the registration launches alone of both, their ratio and the spread of each."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,6 +79,34 @@ def memory_search_table(grids=SEARCH_GRIDS, runs=5, reps=30):
     return rows
 
 
+def memory_search_norm_table(grids=SEARCH_GRIDS, runs=5, reps=30):
+    """rows of (frame, n_rot, radius, median ms search append, median ms normalised append, median ms of the plain registration
+    alone, of the normalised registration alone, their ratio, (max - min) / median of the plain registration, of the normalised)"""
+    srch, norm = ya.Scene(W, H), ya.Scene(W, H)
+    prior = (3.0, -2.0, 0.05)                            # memory_search_table's prior: it is right, both searches confirm it
+    motion = ya.scene_motion(*prior)
+    rows = []
+    for name, ci in frames():
+        for n_rot, radius in grids:
+            cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
+            for sc in (srch, norm):
+                sc.memory_reset()
+                sc.append_memory(depth, cls_id=ci, motion=motion)
+            srch.append_memory_search(depth, cls_id=ci, candidates=cands, radius=radius)
+            norm.append_memory_search_norm(depth, cls_id=ci, candidates=cands, radius=radius)
+            srch.memory_search_time(reps); norm.memory_search_norm_time(reps)
+            ts, tr, tn, tq = [], [], [], []
+            for _ in range(runs):
+                a, b = srch.memory_search_time(reps)
+                ts.append(a); tr.append(b)
+                a, b = norm.memory_search_norm_time(reps)
+                tn.append(a); tq.append(b)
+            ms, mr, mn, mq = (float(np.median(t)) for t in (ts, tr, tn, tq))
+            rows.append((name, n_rot, radius, ms, mn, mr, mq, mq / mr, (max(tr) - min(tr)) / mr, (max(tq) - min(tq)) / mq))
+    srch.close(); norm.close()
+    return rows
+
+
 PYRAMID_GRIDS = ((1, 3, 8, 1), (5, 3, 8, 1), (9, 3, 8, 2))
 
 
@@ -114,6 +145,11 @@ if __name__ == "__main__":
         print(f"{'frame':<16} {'n_rot':>5} {'L':>1} {'R':>1} {'r':>1} {'search':>8} {'pyramid':>8} {'reg plain':>9} {'reg pyr':>8} {'ratio':>7} {'spread plain':>13} {'spread pyr':>11}")
         for name, n_rot, levels, radius, refine, ms, mp, mr, mq, ratio, sr, sq in memory_pyramid_table():
             print(f"{name:<16} {n_rot:5d} {levels:1d} {radius:1d} {refine:1d} {ms:8.4f} {mp:8.4f} {mr:9.4f} {mq:8.4f} {ratio:7.3f} {100 * sr:12.1f}% {100 * sq:10.1f}%")
+    elif "--memory-search-norm" in sys.argv[1:]:
+        print(f"scene {W}x{H}: search append (yh_scene_memory_search_time) against normalised search append (yh_scene_memory_search_norm_time), ms, median of 5 x 30 replays")
+        print(f"{'frame':<16} {'n_rot':>5} {'R':>2} {'search':>8} {'norm':>8} {'reg plain':>9} {'reg norm':>8} {'ratio':>7} {'spread plain':>13} {'spread norm':>12}")
+        for name, n_rot, radius, ms, mn, mr, mq, ratio, sr, sq in memory_search_norm_table():
+            print(f"{name:<16} {n_rot:5d} {radius:2d} {ms:8.4f} {mn:8.4f} {mr:9.4f} {mq:8.4f} {ratio:7.3f} {100 * sr:12.1f}% {100 * sq:11.1f}%")
     elif "--memory-search" in sys.argv[1:]:
         print(f"scene {W}x{H}: memory append (yh_scene_memory_time) against search append (yh_scene_memory_search_time), ms per frame, median of 5 x 30 frames")
         print(f"{'frame':<16} {'n_rot':>5} {'R':>2} {'memory':>8} {'search':>8} {'ratio':>7} {'alone':>8} {'Gpx-cand/s':>11} {'spread memory':>14} {'spread search':>14}")
