@@ -1048,6 +1048,19 @@ def scene_motion_candidates(prior=(0.0, 0.0, 0.0), dtheta_step=0.01, n_side=2, p
 SCENE_IDENTITY_Q16 = (65536, 0, 0, 0, 65536, 0)
 
 
+_SCENE_OUTPUTS = ("map", "world", "conn0", "conn1", "balls")   # in the argument order of yh_scene_read / yh_scene_batch_read
+
+
+def _scene_outputs(W, H, which):
+    """Host arrays for the outputs named in `which` (None: all of them)."""
+    which = _SCENE_OUTPUTS if which is None else tuple(which)
+    if not which or any(k not in _SCENE_OUTPUTS for k in which):
+        raise ValueError(f"which: need some of {_SCENE_OUTPUTS}, got {which}")
+    shapes = dict(map=((H, W), np.uint32), world=((H, W, 4), np.float32), conn0=((H, W, 4), np.float32), conn1=((H, W, 4), np.float32),
+                  balls=((100, 4), np.float32))
+    return {k: np.zeros(*shapes[k]) for k in _SCENE_OUTPUTS if k in which}
+
+
 class Scene:
     """RAII wrapper of yh_scene: append_scene's two compute dispatches (src/scene.rs:147-331) on the GPU."""
 
@@ -1087,11 +1100,10 @@ class Scene:
             assert f.size == self.W * self.H
             self._chk(self.L.yh_scene_append_classified(self.h, _p(depth), _p(f), 0, mode))
 
-    def read(self):
-        out = dict(map=np.zeros((self.H, self.W), np.uint32), world=np.zeros((self.H, self.W, 4), np.float32),
-                   conn0=np.zeros((self.H, self.W, 4), np.float32), conn1=np.zeros((self.H, self.W, 4), np.float32),
-                   balls=np.zeros((100, 4), np.float32))
-        self._chk(self.L.yh_scene_read(self.h, _p(out["map"]), _p(out["world"]), _p(out["conn0"]), _p(out["conn1"]), _p(out["balls"])))
+    def read(self, which=None):
+        """The last frame's outputs; `which` names the ones wanted (default: all five) - the others are not copied (yh_scene_read takes nulls)."""
+        out = _scene_outputs(self.W, self.H, which)
+        self._chk(self.L.yh_scene_read(self.h, *(_p(out[k]) if k in out else None for k in _SCENE_OUTPUTS)))
         return out
 
     def time(self, reps=20):
@@ -1536,11 +1548,10 @@ class SceneBatch:
         self._chk(self.L.yh_scene_batch_append(self.h, n, mode))
         self.n, self._fields = n, False
 
-    def read(self, b):
-        out = dict(map=np.zeros((self.H, self.W), np.uint32), world=np.zeros((self.H, self.W, 4), np.float32),
-                   conn0=np.zeros((self.H, self.W, 4), np.float32), conn1=np.zeros((self.H, self.W, 4), np.float32),
-                   balls=np.zeros((100, 4), np.float32))
-        self._chk(self.L.yh_scene_batch_read(self.h, b, _p(out["map"]), _p(out["world"]), _p(out["conn0"]), _p(out["conn1"]), _p(out["balls"])))
+    def read(self, b, which=None):
+        """Frame b's outputs; `which` as in Scene.read (yh_scene_batch_read takes nulls as well)."""
+        out = _scene_outputs(self.W, self.H, which)
+        self._chk(self.L.yh_scene_batch_read(self.h, b, *(_p(out[k]) if k in out else None for k in _SCENE_OUTPUTS)))
         return out
 
     def plan(self, targets=None, n_targets=3, starts=None, connectivity=4):
