@@ -689,6 +689,35 @@ int yh_scene_append_memory_search_norm(yh_scene* h, const uint16_t* depth_host, 
  * candidate qualified. Any pointer may be NULL. Waits. YH_ESTATE unless the handle's last memory append was a normalised search. */
 int yh_scene_motion_norm_read(yh_scene* h, uint64_t* totals /* [n_rot][2R+1][2R+1] or NULL */, uint64_t* inside /* likewise */,
                               uint64_t* chosen_stc /* [3] = S, T, C */, uint64_t* prior_stc /* [3] */, int32_t* qualified);
+/* Scene memory: normalised pyramid registration (DESIGN.md section 11 "Scene memory: normalised pyramid registration"):
+ * yh_scene_append_memory_pyramid with every level, and the choice, decided by the normalised score of
+ * yh_scene_append_memory_search_norm - the reach of the one on the dense maps of the other. Pooled levels, level bases, hypotheses,
+ * the home hypothesis, reach, the chosen candidate's twelve integers and the int32 conditions are yh_scene_append_memory_pyramid's.
+ *   tables      at level l, S, T and C of yh_scene_append_memory_search_norm on that level's maps, gathers and radius; "inside" is
+ *               taken against the level's W_l x H_l.
+ *   qualified   at level l: C >= m_l = (min_inside + 4^l - 1) >> 2 l, and U = T - S > 0. min_inside is 1 .. width x height.
+ *   descent     per hypothesis, among its qualified entries the largest S / U as exact 128-bit cross products; ties: the smaller
+ *               U^2 + V^2 of the total shift, then the smaller V, then the smaller U. None qualified: the hypothesis keeps its
+ *               centre (relative shift 0).
+ *   choice      over the qualified level-0 entries of all n_rot + 1 hypotheses (hypothesis n_rot counts as k = 0) the largest S / U;
+ *               ties: the smaller u^2 + v^2, then k, then v, then u. None qualified: (0, 0, 0) of base 0.
+ * The chosen (S, T, C) are the flat normalised search's for that gather; if the prior (0, 0, 0) qualifies the chosen ratio is never
+ * below its ratio; an empty memory or an empty frame chooses (0, 0, 0); with n_rot = 1, radius = refine = 0 it IS
+ * yh_scene_append_memory with row 0. Integer only, bit-exact, no host wait; host buffers are free on return. Afterwards
+ * yh_scene_motion_read and yh_scene_pyramid_read (centres, the S tables, sum_n) work as after yh_scene_append_memory_pyramid, and
+ * yh_scene_motion_norm_read returns chosen_stc, prior_stc - (S, T, C) of (0, 0, 0) at the home hypothesis - and qualified with
+ * totals and inside NULL (YH_EINVAL naming yh_scene_pyramid_norm_read if either is given). YH_EINVAL with nothing touched as
+ * yh_scene_append_memory_pyramid, and for min_inside out of range. */
+int yh_scene_append_memory_pyramid_norm(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                        const int32_t* gather_q16 /* [n_rot][6] */, const int32_t* carry_q16 /* [n_rot][6] */, int32_t levels,
+                                        int32_t radius, int32_t refine, int32_t min_inside, int32_t keep, int32_t ball_max_age);
+/* One level (0 .. levels) of the last yh_scene_append_memory_pyramid_norm: centres, scores (S) and sum_n as yh_scene_pyramid_read
+ * returns them, totals (T) and inside (C) laid out as scores, the level's threshold m_l, and per hypothesis whether any of its
+ * entries qualified. Any pointer may be NULL. Waits. YH_ESTATE unless the handle's last memory append was a normalised pyramid
+ * append; YH_EINVAL for a level outside 0 .. levels. */
+int yh_scene_pyramid_norm_read(yh_scene* h, int32_t level, int32_t* centres /* [hyp][2] */, uint64_t* scores /* [hyp][2p+1][2p+1] */,
+                               uint64_t* totals /* likewise */, uint64_t* inside /* likewise */, uint64_t* sum_n, int32_t* level_min_inside,
+                               int32_t* qualified /* [hyp] */);
 /* ---- scene batch (DESIGN.md section 11 "Scene batch"): append and plan N frames in one set of launches -------------
  * Frame b of a batch has EXACTLY the results a yh_scene handle of the same size gives when it is fed that frame alone with the same
  * mode, targets, start and connectivity - bit for bit, every output: the kernels run the single handle's device code with the frame

@@ -154,6 +154,22 @@ int yh_scene_op_register_norm(yh_scene* h, const uint32_t* n_host, const uint32_
 int yh_scene_op_pyramid(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
                         int32_t levels, int32_t radius, int32_t refine, int32_t* chosen /* [3] */, uint64_t* score /* [3] */, uint32_t* pyr_n,
                         uint32_t* pyr_m, int32_t* centres, uint64_t* scores);
+/* The same for a frame that came from yh_scene_append_memory_pyramid_norm (yh_scene_time, yh_scene_memory_time,
+ * yh_scene_memory_search_time, yh_scene_memory_pyramid_time and yh_scene_memory_search_norm_time refuse such a frame with YH_ESTATE
+ * and name this hook): the whole append replayed from the state it started from, ms_per_frame; then its registration launches alone
+ * (the levels, the clear, tables and select per level), ms_search. Both rewrite the same values and commit nothing. YH_ESTATE
+ * unless the handle's last frame is a normalised pyramid append. */
+int yh_scene_memory_pyramid_norm_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search);
+/* Test hook: the normalised pyramid registration alone on two caller-given maps, as yh_scene_op_pyramid runs the plain one, with
+ * min_inside as yh_scene_append_memory_pyramid_norm takes it (the same YH_EINVAL checks). The arguments up to scores are
+ * yh_scene_op_pyramid's (scores: the S tables); totals (T) and inside (C) are laid out as scores; qualified holds one flag per
+ * hypothesis, levels 0 .. levels concatenated as centres are - whether any of its entries qualified - and after them one more:
+ * whether the choice qualified; chosen_stc [3] = S, T, C of the choice. Each may be NULL. Waits. Buffers of its own: reads and writes
+ * nothing of the handle's frame, memory or plans. */
+int yh_scene_op_pyramid_norm(yh_scene* h, const uint32_t* n_host, const uint32_t* m_host, int32_t n_rot, const int32_t* gather_q16 /* [n_rot][6] */,
+                             int32_t levels, int32_t radius, int32_t refine, int32_t* chosen /* [3] */, uint64_t* score /* [3] */, uint32_t* pyr_n,
+                             uint32_t* pyr_m, int32_t* centres, uint64_t* scores, int32_t min_inside, uint64_t* totals, uint64_t* inside,
+                             int32_t* qualified, uint64_t* chosen_stc /* [3] */);
 /* Test hook: uploads host fields (height map u32 [h][w], connections0 / connections1 f32 [h][w][4], laid out as yh_scene_read
  * returns them) as if a YH_COMPAT_SANE frame had produced them, so that yh_scene_plan runs on constructed mazes. The planner reads
  * conn0[..][2] (right) and conn1[..][0] (down) and takes left / up from the neighbour, as SANE's symmetry allows: YH_EINVAL (nothing

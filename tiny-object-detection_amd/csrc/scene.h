@@ -83,6 +83,7 @@ bool scene_memory_is_last(const yh_scene* h);
 bool scene_memory_is_search(const yh_scene* h);   // .. from yh_scene_append_memory_search
 bool scene_memory_is_norm(const yh_scene* h);     // .. from yh_scene_append_memory_search_norm (is_search holds as well)
 bool scene_memory_is_pyramid(const yh_scene* h);  // .. from yh_scene_append_memory_pyramid
+bool scene_memory_is_pyramid_norm(const yh_scene* h);   // .. from yh_scene_append_memory_pyramid_norm (is_pyramid does not hold)
 // what an 8-connected plan or tour asks of a frame's diagonal lengths (YH_ESTATE and why if they fail it: ok and why are the
 // scene's diag_ok / diag_why, or those of a batch's frame); touches nothing
 int scene_plan_diagonals(yh_scene* h, bool ok, const std::string& why);

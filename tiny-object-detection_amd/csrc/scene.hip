@@ -223,6 +223,7 @@ int yh_scene_read(yh_scene* h, uint32_t* map, float* world, float* conn0, float*
 int yh_scene_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!h->ran) return h->fail(YH_ESTATE, "no frame has been appended");
+    if (scene_memory_is_pyramid_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid_norm: yh_scene_memory_pyramid_norm_time replays it");
     if (scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (scene_memory_is_search(h))
         return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");

@@ -15,6 +15,8 @@
 // searched coarse to fine (scene_pyramid.hip), into the same record.
 // yh_scene_append_memory_search_norm (DESIGN.md section 11 "Scene memory: normalised registration") is the search append with the
 // candidates ranked by the normalised score (scene_register_norm.hip), into the same record and an extension of it.
+// yh_scene_append_memory_pyramid_norm (DESIGN.md section 11 "Scene memory: normalised pyramid registration") is the pyramid append
+// with every level decided by that score (scene_pyramid_norm.hip), into the same two records.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -24,6 +26,7 @@
 #include "scene_dev.h"
 #include "scene_memory_dev.h"
 #include "scene_pyramid_dev.h"
+#include "scene_pyramid_norm_dev.h"
 #include "scene_register_dev.h"
 #include "scene_register_norm_dev.h"
 #include "yh_internal.h"
@@ -60,6 +63,11 @@ struct yh_scene_memory {
     ScenePyramidBufs pyr;
     bool pyramid = false;
     ScenePyramidPlan last_pyr;
+    // normalised pyramid registration: pyrn allocated at the first such append. pyr_norm_min_inside != 0: the last memory append was
+    // one (pyramid and searched are false then) - last_pyr is its plan, pyr.table the centres, pyr.maps the levels, reg_rec and
+    // norm_rec its choice, pyrn.acc its level tables, pyrn.ext its flags
+    ScenePyramidNormBufs pyrn;
+    int pyr_norm_min_inside = 0;
 };
 
 namespace {
@@ -101,7 +109,8 @@ int register_reserve(yh_scene* h) {
 
 // the launches of one memory append: reads map[from] / tab[from], writes map[from ^ 1] / tab[from ^ 1] and the handle's fields
 // (bases or pyr given: the motion is searched for around them and read from the device record, q.g and q.c are not used; upload:
-// the pyramid's table goes to the device first - a replay finds it there; min_inside != 0 with bases: the normalised search)
+// the pyramid's table goes to the device first - a replay finds it there; min_inside != 0: the normalised search, or with pyr the
+// normalised pyramid)
 int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBases* bases = nullptr, const ScenePyramidPlan* pyr = nullptr, bool upload = false,
                int min_inside = 0) {
     yh_scene_memory* m = h->memory;
@@ -121,7 +130,8 @@ int run_memory(yh_scene* h, const MemoryCall& q, int from, const SceneRegisterBa
     f.W = h->W; f.H = h->H; f.keep = q.keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = q.c[i]; f.g[i] = q.g[i]; }
     if (pyr) {
-        const int rs = scene_pyramid_search(h, m->stamp, m->map[from], *pyr, m->pyr, m->reg_rec, upload);
+        const int rs = min_inside ? scene_pyramid_norm_search(h, m->stamp, m->map[from], *pyr, min_inside, m->pyr, m->pyrn, m->reg_rec, m->norm_rec, upload)
+                                  : scene_pyramid_search(h, m->stamp, m->map[from], *pyr, m->pyr, m->reg_rec, upload);
         return rs ? rs : scene_register_fuse(h, f, b, m->reg_rec);
     }
     if (bases) {
@@ -142,6 +152,7 @@ int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame
     if (rc) return rc;
     if ((bases || pyr) && (rc = register_reserve(h))) return rc;
     if (pyr && (rc = scene_pyramid_reserve(h, h->memory->pyr))) return rc;
+    if (pyr && min_inside && (rc = scene_pyramid_norm_reserve(h, h->memory->pyrn))) return rc;
     const size_t npx = (size_t)h->W * h->H;
     SCHK(h, hipMemcpyAsync(h->depth, depth_host, npx * 2, hipMemcpyHostToDevice, h->stream));
     q.frame = frame;
@@ -153,8 +164,9 @@ int append_memory(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame
     m->cur ^= 1;
     m->last = q;
     m->searched = bases != nullptr;
-    m->pyramid = pyr != nullptr;
+    m->pyramid = pyr != nullptr && !min_inside;
     m->norm_min_inside = bases ? min_inside : 0;
+    m->pyr_norm_min_inside = pyr ? min_inside : 0;
     if (bases) m->last_bases = *bases;
     return YH_OK;
 }
@@ -168,7 +180,7 @@ int append_memory_call(yh_scene* h, const uint16_t* depth_host, const uint32_t* 
     if (rc) {
         // a call that fails after its checks leaves no frame and an empty memory
         h->ran = false;
-        if (m) { m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; }
+        if (m) { m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; m->pyr_norm_min_inside = 0; }
         return rc;
     }
     m->frame = h->frames;
@@ -188,14 +200,18 @@ int replay_time(yh_scene* h, int reps, bool search_only, float* ms_out) {
     // the last append's own inputs and motion, from the state it started from (the other pair of buffers) into the state it left:
     // the same bits again, so nothing is committed (a device frame given to the append must still be valid)
     for (int r = 0; r < reps; ++r) {
-        const int rc = !search_only ? run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr, m->pyramid ? &m->last_pyr : nullptr, false, m->norm_min_inside)
+        const bool pyr = m->pyramid || m->pyr_norm_min_inside;
+        const int rc = !search_only ? run_memory(h, m->last, m->cur ^ 1, m->searched ? &m->last_bases : nullptr, pyr ? &m->last_pyr : nullptr, false,
+                                                 m->norm_min_inside | m->pyr_norm_min_inside)
+                       : m->pyr_norm_min_inside
+                           ? scene_pyramid_norm_search(h, m->stamp, m->map[m->cur ^ 1], m->last_pyr, m->pyr_norm_min_inside, m->pyr, m->pyrn, m->reg_rec, m->norm_rec, false)
                        : m->pyramid ? scene_pyramid_search(h, m->stamp, m->map[m->cur ^ 1], m->last_pyr, m->pyr, m->reg_rec, false)
                        : m->norm_min_inside
                            ? scene_register_norm_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->norm_min_inside, m->reg_acc, m->reg_rec, m->norm_rec)
                            : scene_register_search(h, m->stamp, m->map[m->cur ^ 1], m->last_bases, m->reg_acc, m->reg_rec);
         if (rc) {
             hipEventDestroy(a); hipEventDestroy(b);
-            h->ran = false; m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0;
+            h->ran = false; m->stale = true; m->frame = 0; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; m->pyr_norm_min_inside = 0;
             return rc;
         }
     }
@@ -217,6 +233,7 @@ void scene_memory_free(yh_scene* h) {
     void* bufs[] = { m->stamp, m->map[0], m->map[1], m->tab[0], m->tab[1], m->reg_acc, m->reg_rec, m->norm_rec };
     for (void* b : bufs) if (b) hipFree(b);
     scene_pyramid_release(m->pyr);
+    scene_pyramid_norm_release(m->pyrn);
     delete m;
     h->memory = nullptr;
 }
@@ -225,6 +242,7 @@ bool scene_memory_is_last(const yh_scene* h) { return h->memory && h->memory->fr
 bool scene_memory_is_search(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->searched; }
 bool scene_memory_is_norm(const yh_scene* h) { return scene_memory_is_search(h) && h->memory->norm_min_inside != 0; }
 bool scene_memory_is_pyramid(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->pyramid; }
+bool scene_memory_is_pyramid_norm(const yh_scene* h) { return scene_memory_is_last(h) && h->memory->pyr_norm_min_inside != 0; }
 }  // namespace yh
 
 extern "C" {
@@ -276,8 +294,11 @@ int yh_scene_append_memory_search_norm(yh_scene* h, const uint16_t* depth_host, 
 int yh_scene_motion_norm_read(yh_scene* h, uint64_t* totals, uint64_t* inside, uint64_t* chosen_stc, uint64_t* prior_stc, int32_t* qualified) {
     if (!h) return YH_EINVAL;
     yh_scene_memory* m = h->memory;
-    if (!m || m->stale || !m->searched || !m->norm_min_inside)
+    const bool pyr_norm = m && !m->stale && m->pyr_norm_min_inside;
+    if (!pyr_norm && (!m || m->stale || !m->searched || !m->norm_min_inside))
         return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search_norm (or the memory was reset since)");
+    if (pyr_norm && (totals || inside))
+        return h->fail(YH_EINVAL, "the last memory append was yh_scene_append_memory_pyramid_norm: yh_scene_pyramid_norm_read returns its level tables");
     SCHK(h, hipSetDevice(h->dev));
     SceneRegisterNormRecord ext;
     const size_t words = register_norm_table_words(m->last_bases.n_rot, m->last_bases.radius);
@@ -304,15 +325,62 @@ int yh_scene_append_memory_pyramid(yh_scene* h, const uint16_t* depth_host, cons
     return append_memory_call(h, depth_host, frame, frame_on_device, q, nullptr, &plan);
 }
 
+int yh_scene_append_memory_pyramid_norm(yh_scene* h, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device, int32_t n_rot,
+                                        const int32_t* gather_q16, const int32_t* carry_q16, int32_t levels, int32_t radius, int32_t refine, int32_t min_inside,
+                                        int32_t keep, int32_t ball_max_age) {
+    if (!h || !depth_host || !frame || !gather_q16 || !carry_q16) return YH_EINVAL;
+    ScenePyramidPlan plan;
+    const int rc = scene_pyramid_plan_make(h, n_rot, gather_q16, carry_q16, levels, radius, refine, plan);
+    if (rc) return rc;
+    if (min_inside < 1 || (long long)min_inside > (long long)h->W * h->H) return h->fail(YH_EINVAL, "min_inside outside 1 .. width x height");
+    if (keep < 0 || keep > 256) return h->fail(YH_EINVAL, "keep outside 0 .. 256");
+    if (ball_max_age < 0 || ball_max_age > 255) return h->fail(YH_EINVAL, "ball_max_age outside 0 .. 255");
+    MemoryCall q;   // (its motion stays zero: the kernels read the chosen one from the device record)
+    q.keep = keep; q.max_age = ball_max_age;
+    return append_memory_call(h, depth_host, frame, frame_on_device, q, nullptr, &plan, min_inside);
+}
+
+int yh_scene_pyramid_norm_read(yh_scene* h, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* totals, uint64_t* inside, uint64_t* sum_n,
+                               int32_t* level_min_inside, int32_t* qualified) {
+    if (!h) return YH_EINVAL;
+    yh_scene_memory* m = h->memory;
+    if (!m || m->stale || !m->pyr_norm_min_inside)
+        return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_pyramid_norm (or the memory was reset since)");
+    const ScenePyramidPlan& plan = m->last_pyr;
+    if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
+    SCHK(h, hipSetDevice(h->dev));
+    const int hyp = plan.hyp(level);
+    const size_t words = register_norm_table_words(hyp, plan.rho(level));
+    const unsigned long long* acc = m->pyrn.acc + pyramid_norm_acc_offset(plan, level);
+    int cen[SR_MAX_ROT][2], flags[SR_MAX_ROT];
+    unsigned long long sum = 0;
+    if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr.table->centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
+    if (qualified) SCHK(h, hipMemcpyAsync(flags, m->pyrn.ext->qualified[level], sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    if (sum_n) SCHK(h, hipMemcpyAsync(&sum, acc, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
+    uint64_t* const tabs[3] = { scores, totals, inside };
+    for (int t = 0; t < 3; ++t)
+        if (tabs[t]) SCHK(h, hipMemcpyAsync(tabs[t], acc + 1 + t * words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < hyp; ++k) {
+        if (centres) { centres[2 * k] = cen[k][0]; centres[2 * k + 1] = cen[k][1]; }
+        if (qualified) qualified[k] = flags[k];
+    }
+    if (sum_n) *sum_n = sum;
+    if (level_min_inside) *level_min_inside = (int32_t)pyramid_norm_min_inside(m->pyr_norm_min_inside, level);
+    return YH_OK;
+}
+
 int yh_scene_pyramid_read(yh_scene* h, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* sum_n) {
     if (!h) return YH_EINVAL;
     yh_scene_memory* m = h->memory;
-    if (!m || m->stale || !m->pyramid) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_pyramid (or the memory was reset since)");
+    if (!m || m->stale || !(m->pyramid || m->pyr_norm_min_inside))
+        return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_pyramid (or the memory was reset since)");
     const ScenePyramidPlan& plan = m->last_pyr;
     if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
     SCHK(h, hipSetDevice(h->dev));
     const int hyp = plan.hyp(level), nu = 2 * plan.rho(level) + 1;
-    const unsigned long long* acc = m->pyr.acc + plan.acc_offset(level);
+    // (after a normalised pyramid append: its S tables, which lie first in each level of its own tables)
+    const unsigned long long* acc = m->pyr_norm_min_inside ? m->pyrn.acc + pyramid_norm_acc_offset(plan, level) : m->pyr.acc + plan.acc_offset(level);
     int cen[SR_MAX_ROT][2];
     unsigned long long sum = 0;
     if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr.table->centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
@@ -327,7 +395,10 @@ int yh_scene_pyramid_read(yh_scene* h, int32_t level, int32_t* centres, uint64_t
 int yh_scene_motion_read(yh_scene* h, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
     if (!h) return YH_EINVAL;
     yh_scene_memory* m = h->memory;
-    if (!m || m->stale || !(m->searched || m->pyramid)) return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search (or the memory was reset since)");
+    if (!m || m->stale || !(m->searched || m->pyramid || m->pyr_norm_min_inside))
+        return h->fail(YH_ESTATE, "the last memory append was not yh_scene_append_memory_search (or the memory was reset since)");
+    if (m->pyr_norm_min_inside && scores)
+        return h->fail(YH_EINVAL, "the last memory append was yh_scene_append_memory_pyramid_norm: yh_scene_pyramid_read returns its level tables");
     if (m->pyramid && scores) return h->fail(YH_EINVAL, "the last memory append was yh_scene_append_memory_pyramid: yh_scene_pyramid_read returns its level tables");
     SCHK(h, hipSetDevice(h->dev));
     SceneRegisterRecord rec;
@@ -368,12 +439,14 @@ int yh_scene_memory_reset(yh_scene* h) {
     m->searched = false;
     m->pyramid = false;
     m->norm_min_inside = 0;
+    m->pyr_norm_min_inside = 0;
     return memory_reserve(h);
 }
 
 int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
     if (!h || reps < 1 || !ms_per_frame) return YH_EINVAL;
     if (!scene_memory_is_last(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory (or the memory was reset since)");
+    if (h->memory->pyr_norm_min_inside) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid_norm: yh_scene_memory_pyramid_norm_time replays it");
     if (h->memory->norm_min_inside) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (h->memory->searched) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search: yh_scene_memory_search_time replays it");
     if (h->memory->pyramid) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
@@ -383,6 +456,7 @@ int yh_scene_memory_time(yh_scene* h, int32_t reps, float* ms_per_frame) {
 
 int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (scene_memory_is_pyramid_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid_norm: yh_scene_memory_pyramid_norm_time replays it");
     if (scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid: yh_scene_memory_pyramid_time replays it");
     if (scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (!scene_memory_is_search(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search (or the memory was reset since)");
@@ -394,6 +468,7 @@ int yh_scene_memory_search_time(yh_scene* h, int32_t reps, float* ms_per_frame, 
 
 int yh_scene_memory_search_norm_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (scene_memory_is_pyramid_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid_norm: yh_scene_memory_pyramid_norm_time replays it");
     if (!scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_search_norm (or the memory was reset since)");
     SCHK(h, hipSetDevice(h->dev));
     // as yh_scene_memory_search_time: the whole append, then its registration launches alone (the clear, the three tables, the choice)
@@ -403,10 +478,20 @@ int yh_scene_memory_search_norm_time(yh_scene* h, int32_t reps, float* ms_per_fr
 
 int yh_scene_memory_pyramid_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
     if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (scene_memory_is_pyramid_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_pyramid_norm: yh_scene_memory_pyramid_norm_time replays it");
     if (scene_memory_is_norm(h)) return h->fail(YH_ESTATE, "the last frame came from yh_scene_append_memory_search_norm: yh_scene_memory_search_norm_time replays it");
     if (!scene_memory_is_pyramid(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_pyramid (or the memory was reset since)");
     SCHK(h, hipSetDevice(h->dev));
     // as yh_scene_memory_search_time: the whole append, then its registration launches alone (the levels, the clear, scores and select)
+    const int rc = replay_time(h, reps, false, ms_per_frame);
+    return rc ? rc : replay_time(h, reps, true, ms_search);
+}
+
+int yh_scene_memory_pyramid_norm_time(yh_scene* h, int32_t reps, float* ms_per_frame, float* ms_search) {
+    if (!h || reps < 1 || !ms_per_frame || !ms_search) return YH_EINVAL;
+    if (!scene_memory_is_pyramid_norm(h)) return h->fail(YH_ESTATE, "the last frame did not come from yh_scene_append_memory_pyramid_norm (or the memory was reset since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_memory_pyramid_time: the whole append, then its registration launches alone (the levels, the clear, tables and select)
     const int rc = replay_time(h, reps, false, ms_per_frame);
     return rc ? rc : replay_time(h, reps, true, ms_search);
 }

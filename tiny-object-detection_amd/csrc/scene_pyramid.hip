@@ -124,6 +124,21 @@ int scene_pyramid_search(yh_scene* h, const uint32_t* stamp, const uint32_t* mem
     return YH_OK;
 }
 
+// the scene_pyramid launch alone, for a search that scores the levels with kernels of its own (scene_pyramid_norm.hip): where the
+// levels lie comes back in pp
+void scene_pyramid_levels(yh_scene* h, const uint32_t* stamp, const uint32_t* mem, int levels, const ScenePyramidBufs& b, ScenePyramidParams& pp) {
+    const int W = h->W, H = h->H;
+    const size_t words = scene_pyramid_map_words(W, H);
+    pp = ScenePyramidParams();
+    pp.src[0] = stamp; pp.src[1] = mem; pp.W = W; pp.H = H; pp.levels = levels;
+    for (int l = 1; l <= levels; ++l) {
+        pp.dst[0][l - 1] = b.maps + scene_pyramid_map_offset(W, H, l);
+        pp.dst[1][l - 1] = b.maps + words + scene_pyramid_map_offset(W, H, l);
+    }
+    const unsigned tiles0 = (unsigned)(((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH));   // <= 128 * 512
+    hipLaunchKernelGGL(scene_pyramid, dim3(tiles0, 2), dim3(256), 0, h->stream, pp);
+}
+
 }  // namespace yh
 
 extern "C" {

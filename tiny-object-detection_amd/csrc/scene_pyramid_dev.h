@@ -160,4 +160,5 @@ int scene_pyramid_plan_make(yh_scene* h, int32_t n_rot, const int32_t* gather_q1
 int scene_pyramid_reserve(yh_scene* h, ScenePyramidBufs& b);
 void scene_pyramid_release(ScenePyramidBufs& b);
 int scene_pyramid_search(yh_scene* h, const uint32_t* stamp, const uint32_t* mem, const ScenePyramidPlan& plan, const ScenePyramidBufs& b, SceneRegisterRecord* rec, bool upload);
+void scene_pyramid_levels(yh_scene* h, const uint32_t* stamp, const uint32_t* mem, int levels, const ScenePyramidBufs& b, ScenePyramidParams& pp);
 }

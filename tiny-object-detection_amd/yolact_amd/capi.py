@@ -180,6 +180,10 @@ SYMBOLS = [
     ("yh_scene_pyramid_read", _i, [_vp, _i, _vp, _vp, _vp]),
     ("yh_scene_memory_pyramid_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_op_pyramid", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_append_memory_pyramid_norm", _i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    ("yh_scene_pyramid_norm_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_memory_pyramid_norm_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_op_pyramid_norm", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("yh_scene_batch_create", _i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_batch_destroy", None, [_vp]),
     ("yh_scene_batch_last_error", C.c_char_p, [_vp]),
@@ -1212,16 +1216,21 @@ class Scene:
             f, on_device = _p(keepalive), 0
         self._chk(self.L.yh_scene_append_memory_search_norm(self.h, _p(depth), f, on_device, len(g), _p(g), _p(c), radius, min_inside, keep, ball_max_age))
         self._search = (len(g), radius)
+        self._norm_levels = False
 
     def read_motion_norm(self):
         """What the last append_memory_search_norm saw beside read_motion's: totals (T) and inside (C), u64 [n_rot][2 radius + 1]
         [2 radius + 1] laid out as read_motion's scores, chosen_stc and prior_stc u64 [3] = (S, T, C) of the choice and of (0, 0, 0),
-        and qualified: False if no candidate qualified."""
+        and qualified: False if no candidate qualified. After append_memory_pyramid_norm: chosen_stc, prior_stc and qualified alone
+        (read_pyramid_norm has the levels' tables)."""
         n_rot, radius = getattr(self, "_search", None) or (1, 0)
         shape = (n_rot, 2 * radius + 1, 2 * radius + 1)
-        out = dict(totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64), chosen_stc=np.zeros(3, np.uint64), prior_stc=np.zeros(3, np.uint64))
+        out = dict(chosen_stc=np.zeros(3, np.uint64), prior_stc=np.zeros(3, np.uint64))
+        if not getattr(self, "_norm_levels", False):
+            out.update(totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64))
         q = C.c_int32()
-        self._chk(self.L.yh_scene_motion_norm_read(self.h, _p(out["totals"]), _p(out["inside"]), _p(out["chosen_stc"]), _p(out["prior_stc"]), C.byref(q)))
+        t, i = (_p(out[k]) if k in out else None for k in ("totals", "inside"))
+        self._chk(self.L.yh_scene_motion_norm_read(self.h, t, i, _p(out["chosen_stc"]), _p(out["prior_stc"]), C.byref(q)))
         out["qualified"] = bool(q.value)
         return out
 
@@ -1316,6 +1325,89 @@ class Scene:
         """(ms per frame, ms of the registration alone) of the last append_memory_pyramid, replayed; commits nothing."""
         ms, ms_search = C.c_float(), C.c_float()
         self._chk(self.L.yh_scene_memory_pyramid_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
+    def append_memory_pyramid_norm(self, depth, frame_u32=None, frame_dev_ptr=None, cls_id=None, candidates=None, levels=3, radius=8, refine=1, min_inside=None,
+                                   keep=224, ball_max_age=30):
+        """append_memory_pyramid with every level, and the choice, decided by the normalised score S / (T - S) of
+        append_memory_search_norm (DESIGN.md §11 "Scene memory: normalised pyramid registration"): the pyramid's reach on dense maps.
+        candidates, levels, radius and refine as append_memory_pyramid; min_inside as append_memory_search_norm (None: W H // 4), carried
+        to level l as (min_inside + 4^l - 1) >> 2 l. read_motion and read_pyramid work as after append_memory_pyramid, read_motion_norm
+        returns chosen_stc, prior_stc and qualified, read_pyramid_norm the levels' three tables and flags."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.H, self.W)
+        g, c = ([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16]) if candidates is None else candidates
+        g, c = np.ascontiguousarray(np.array(g, np.int32)), np.ascontiguousarray(np.array(c, np.int32))   # (a value outside int32 raises here)
+        assert g.ndim == 2 and g.shape[1] == 6 and c.shape == g.shape
+        if min_inside is None:
+            min_inside = (self.W * self.H) // 4
+        if frame_dev_ptr is not None:
+            f, on_device = C.c_void_p(frame_dev_ptr), 1
+        else:
+            keepalive = SceneBatch.pack(cls_id) if cls_id is not None else np.ascontiguousarray(frame_u32, np.uint32)
+            assert keepalive.size == self.W * self.H
+            f, on_device = _p(keepalive), 0
+        self._chk(self.L.yh_scene_append_memory_pyramid_norm(self.h, _p(depth), f, on_device, len(g), _p(g), _p(c), levels, radius, refine, min_inside, keep,
+                                                             ball_max_age))
+        self._pyramid = (len(g), levels, radius, refine)
+        self._search = (len(g) + 1, refine)   # (read_motion(scores=True) is refused after this append: it names read_pyramid)
+        self._norm_levels = True              # (read_motion_norm asks for no tables: they are read_pyramid_norm's)
+
+    def read_pyramid_norm(self, level):
+        """Level `level` (0 .. levels) of the last append_memory_pyramid_norm: centres, scores (S) and sum_n as read_pyramid returns
+        them, totals (T) and inside (C) laid out as scores, min_inside: the level's threshold, qualified i32 [hyp]: whether any entry
+        of the hypothesis qualified."""
+        n_rot, levels, radius, refine = getattr(self, "_pyramid", None) or (1, 0, 0, 0)
+        ok = 0 <= level <= levels                # (otherwise the library refuses before it writes anything)
+        p, hyp = (radius if level == levels else refine), n_rot + (1 if level == 0 else 0)
+        shape = (hyp, 2 * p + 1, 2 * p + 1)
+        out = dict(centres=np.zeros((hyp, 2), np.int32), scores=np.zeros(shape, np.uint64), totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64),
+                   qualified=np.zeros(hyp, np.int32))
+        sum_n, need = C.c_uint64(), C.c_int32()
+        a = [_p(out[k]) if ok else None for k in ("centres", "scores", "totals", "inside")]
+        self._chk(self.L.yh_scene_pyramid_norm_read(self.h, level, a[0], a[1], a[2], a[3], C.byref(sum_n), C.byref(need), _p(out["qualified"]) if ok else None))
+        out.update(sum_n=sum_n.value, min_inside=need.value)
+        return out
+
+    def op_pyramid_norm(self, n, m, gathers, levels, radius, refine, min_inside):
+        """Test hook (yh_scene_op_pyramid_norm): the normalised pyramid registration alone on stamps n and memory m, u32 [h][w];
+        gathers [n_rot][6]. Returns op_pyramid's dict (scores: the S tables) with totals, inside (lists over levels, laid out as
+        scores), flags (list over levels of i32 [hyp]: whether any entry of the hypothesis qualified), chosen_stc u64 [3] = (S, T, C)
+        of the choice and qualified; commits nothing."""
+        n, m = np.ascontiguousarray(n, np.uint32), np.ascontiguousarray(m, np.uint32)
+        assert n.shape == (self.H, self.W) and m.shape == (self.H, self.W)
+        g = np.ascontiguousarray(np.array(gathers, np.int32))
+        assert g.ndim == 2 and g.shape[1] == 6
+        ok = 1 <= len(g) <= 15 and 1 <= levels <= 3 and 0 <= radius <= 8 and 0 <= refine <= 8   # (otherwise the library refuses before it writes anything)
+        dims, hs, ps = [], [], []
+        for lv in range((levels if ok else 0) + 1):
+            dims.append((-(-self.H >> lv), -(-self.W >> lv)))
+            hs.append(len(g) + (1 if lv == 0 else 0)); ps.append(2 * (radius if lv == levels else refine) + 1)
+        words = sum(h * w for h, w in dims[1:])
+        pyr_n, pyr_m = np.zeros(max(words, 1), np.uint32), np.zeros(max(words, 1), np.uint32)
+        nt = sum(h * p * p for h, p in zip(hs, ps))
+        centres, scores, totals, inside = np.zeros((sum(hs), 2), np.int32), np.zeros(nt, np.uint64), np.zeros(nt, np.uint64), np.zeros(nt, np.uint64)
+        chosen, score, flags, stc = np.zeros(3, np.int32), np.zeros(3, np.uint64), np.zeros(sum(hs) + 1, np.int32), np.zeros(3, np.uint64)
+        self._chk(self.L.yh_scene_op_pyramid_norm(self.h, _p(n), _p(m), len(g), _p(g), levels, radius, refine, _p(chosen), _p(score), _p(pyr_n), _p(pyr_m),
+                                                  _p(centres), _p(scores), min_inside, _p(totals), _p(inside), _p(flags), _p(stc)))
+        out = dict(chosen=tuple(int(v) for v in chosen), score=score, pyr_n=[], pyr_m=[], centres=[], scores=[], totals=[], inside=[], flags=[],
+                   chosen_stc=stc, qualified=bool(flags[-1]))
+        o = 0
+        for h, w in dims[1:]:
+            out["pyr_n"].append(pyr_n[o:o + h * w].reshape(h, w)); out["pyr_m"].append(pyr_m[o:o + h * w].reshape(h, w))
+            o += h * w
+        oc = os_ = 0
+        for h, p in zip(hs, ps):
+            out["centres"].append(centres[oc:oc + h]); out["flags"].append(flags[oc:oc + h])
+            for key, tab in (("scores", scores), ("totals", totals), ("inside", inside)):
+                out[key].append(tab[os_:os_ + h * p * p].reshape(h, p, p))
+            oc += h; os_ += h * p * p
+        return out
+
+    def memory_pyramid_norm_time(self, reps=20):
+        """(ms per frame, ms of the registration alone) of the last append_memory_pyramid_norm, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_memory_pyramid_norm_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
         return ms.value, ms_search.value
 
     def plan(self, targets=None, n_targets=3, start=None, connectivity=4):

@@ -10,7 +10,10 @@ append at the same n_rot with radius 8, likewise, over (n_rot, levels, radius, r
 ms per frame of both and ms of the registration launches alone of both, their ratio and the spread of each.
 --memory-search-norm: the normalised search append (yh_scene_append_memory_search_norm: three sums per shift, no empty-tile exit)
 against the plain search append with the same candidates, likewise, over the grids of --memory-search: ms per frame of both, ms of
-the registration launches alone of both, their ratio and the spread of each."""
+the registration launches alone of both, their ratio and the spread of each.
+--memory-pyramid-norm: the normalised pyramid append (yh_scene_append_memory_pyramid_norm: every level decided by S / U) against the
+plain pyramid append with the same candidates, on a second handle, likewise, over the grids of --memory-pyramid: ms per frame of
+both, ms of the registration launches alone of both, their ratio and the spread of each."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,8 +142,42 @@ def memory_pyramid_table(grids=PYRAMID_GRIDS, runs=5, reps=30):
     return rows
 
 
+def memory_pyramid_norm_table(grids=PYRAMID_GRIDS, runs=5, reps=30):
+    """rows of (frame, n_rot, levels, radius, refine, median ms pyramid append, median ms normalised pyramid append, median ms of
+    the plain pyramid registration alone, of the normalised one alone, their ratio, (max - min) / median of the plain pyramid
+    registration, of the normalised)"""
+    pyr, norm = ya.Scene(W, H), ya.Scene(W, H)
+    prior = (3.0, -2.0, 0.05)                            # memory_pyramid_table's prior: it is right, both descents confirm it
+    motion = ya.scene_motion(*prior)
+    rows = []
+    for name, ci in frames():
+        for n_rot, levels, radius, refine in grids:
+            cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
+            for sc in (pyr, norm):
+                sc.memory_reset()
+                sc.append_memory(depth, cls_id=ci, motion=motion)
+            pyr.append_memory_pyramid(depth, cls_id=ci, candidates=cands, levels=levels, radius=radius, refine=refine)
+            norm.append_memory_pyramid_norm(depth, cls_id=ci, candidates=cands, levels=levels, radius=radius, refine=refine)
+            pyr.memory_pyramid_time(reps); norm.memory_pyramid_norm_time(reps)
+            tp, tr, tn, tq = [], [], [], []
+            for _ in range(runs):
+                a, b = pyr.memory_pyramid_time(reps)
+                tp.append(a); tr.append(b)
+                a, b = norm.memory_pyramid_norm_time(reps)
+                tn.append(a); tq.append(b)
+            mp, mr, mn, mq = (float(np.median(t)) for t in (tp, tr, tn, tq))
+            rows.append((name, n_rot, levels, radius, refine, mp, mn, mr, mq, mq / mr, (max(tr) - min(tr)) / mr, (max(tq) - min(tq)) / mq))
+    pyr.close(); norm.close()
+    return rows
+
+
 if __name__ == "__main__":
-    if "--memory-pyramid" in sys.argv[1:]:
+    if "--memory-pyramid-norm" in sys.argv[1:]:
+        print(f"scene {W}x{H}: pyramid append (yh_scene_memory_pyramid_time) against normalised pyramid append (yh_scene_memory_pyramid_norm_time), ms, median of 5 x 30 replays")
+        print(f"{'frame':<16} {'n_rot':>5} {'L':>1} {'R':>1} {'r':>1} {'pyramid':>8} {'norm':>8} {'reg pyr':>8} {'reg norm':>8} {'ratio':>7} {'spread pyr':>11} {'spread norm':>12}")
+        for name, n_rot, levels, radius, refine, mp, mn, mr, mq, ratio, sr, sq in memory_pyramid_norm_table():
+            print(f"{name:<16} {n_rot:5d} {levels:1d} {radius:1d} {refine:1d} {mp:8.4f} {mn:8.4f} {mr:8.4f} {mq:8.4f} {ratio:7.3f} {100 * sr:10.1f}% {100 * sq:11.1f}%")
+    elif "--memory-pyramid" in sys.argv[1:]:
         print(f"scene {W}x{H}: search append at radius 8 (yh_scene_memory_search_time) against pyramid append (yh_scene_memory_pyramid_time), ms, median of 5 x 30 replays")
         print(f"{'frame':<16} {'n_rot':>5} {'L':>1} {'R':>1} {'r':>1} {'search':>8} {'pyramid':>8} {'reg plain':>9} {'reg pyr':>8} {'ratio':>7} {'spread plain':>13} {'spread pyr':>11}")
         for name, n_rot, levels, radius, refine, ms, mp, mr, mq, ratio, sr, sq in memory_pyramid_table():
