@@ -922,6 +922,63 @@ int yh_scene_batch_append_memory_pyramid(yh_scene_batch* h, int32_t n_frames, co
  * YH_EINVAL naming this call if scores is given. */
 int yh_scene_batch_pyramid_read(yh_scene_batch* h, int32_t frame, int32_t level, int32_t* centres /* [hyp][2] */,
                                 uint64_t* scores /* [hyp][2p+1][2p+1] */, uint64_t* sum_n);
+/* ---- batched normalised registration (DESIGN.md section 11 "Scene batch: normalised registration") --------------------------------
+ * yh_scene_batch_append_memory_search with the candidates ranked by the normalised score of the "scene memory: normalised
+ * registration" section, as a dense height map needs. On slots 0 .. n_frames - 1 as staged it is EXACTLY this: for
+ * b = 0 .. n_frames - 1 in order, a yh_scene_append_memory_search_norm call on a yh_scene of the same size that holds the memory of
+ * streams[b], fed slot b's depth and packed frame, the n_rot bases of row b, radius, min_inside, keep and ball_max_age. Frame b's five
+ * outputs, its ball table, every named stream's final memory, frame b's chosen (k, u, v), twelve coefficients, three scores and S
+ * table (yh_scene_batch_motion_read) and its T and C tables, (S, T, C) of the choice and of the prior and `qualified`
+ * (yh_scene_batch_motion_norm_read) are that call's, bit for bit. Frame r of a stream is scored against the memory frame r - 1 of
+ * that stream has just fused, on the device: with R the most frames one stream has in the call, 3 R + 6 launches, as the plain batched
+ * search, and no host wait. n_rot, radius, min_inside (1 .. width x height), keep and ball_max_age are one value per call. Score,
+ * qualification, choice, tie rule and int32 conditions are the single handle's; nothing is redefined here. With n_rot = 1 and
+ * radius = 0 it IS yh_scene_batch_append_memory with the same motions. It counts as a memory append of n_frames frames in every
+ * respect, as yh_scene_batch_append_memory_search does.
+ * Checks, for every frame before anything is touched: every check of yh_scene_batch_append_memory_search, with its texts; YH_EINVAL
+ * for min_inside out of range. A refused call leaves frames, plans, memories and the last readable motions and tables as they were;
+ * a call that fails later behaves as yh_scene_batch_append_memory does. Asynchronous on the handle's stream; the caller's arrays are
+ * free again on return. The tables (three times the plain search's: 110 984 bytes per frame), records (88 bytes) and extensions
+ * (56 bytes) of max_frames frames are allocated at the first batched normalised search: 28.4 MB for 256 frames. */
+int yh_scene_batch_append_memory_search_norm(yh_scene_batch* h, int32_t n_frames, const int32_t* streams /* [n] or NULL */,
+                                             int32_t n_rot, const int32_t* gather_q16 /* [n][n_rot][6] */,
+                                             const int32_t* carry_q16 /* [n][n_rot][6] */, int32_t radius, int32_t min_inside,
+                                             int32_t keep, int32_t ball_max_age);
+/* What yh_scene_batch_motion_read leaves out after the last yh_scene_batch_append_memory_search_norm, for frame `frame`, laid out
+ * as yh_scene_motion_norm_read; any pointer may be NULL. Waits. YH_ESTATE unless the current frames came from a batched normalised
+ * append, YH_EINVAL for a frame outside it. After yh_scene_batch_append_memory_pyramid_norm it returns chosen_stc, prior_stc and
+ * qualified with totals and inside NULL, and YH_EINVAL naming yh_scene_batch_pyramid_norm_read if either is given. */
+int yh_scene_batch_motion_norm_read(yh_scene_batch* h, int32_t frame, uint64_t* totals, uint64_t* inside,
+                                    uint64_t* chosen_stc /* [3] */, uint64_t* prior_stc /* [3] */, int32_t* qualified);
+/* ---- batched normalised pyramid registration (DESIGN.md section 11 "Scene batch: normalised pyramid registration") ---------------
+ * yh_scene_batch_append_memory_pyramid with every level, and the choice, decided by the normalised score. On slots
+ * 0 .. n_frames - 1 as staged it is EXACTLY this: for b = 0 .. n_frames - 1 in order, a yh_scene_append_memory_pyramid_norm call on
+ * a yh_scene of the same size that holds the memory of streams[b], fed slot b's depth and packed frame, the n_rot bases of row b,
+ * levels, radius, refine, min_inside, keep and ball_max_age. Frame b's five outputs, its ball table, every named stream's final
+ * memory, its chosen (k, u, v), twelve coefficients and three scores (yh_scene_batch_motion_read with scores NULL), (S, T, C) of
+ * the choice and of the prior and `qualified` (yh_scene_batch_motion_norm_read) and every level's centres, S, T and C tables, sum_n,
+ * threshold m_l and per-hypothesis flags (yh_scene_batch_pyramid_norm_read; centres, S and sum_n through yh_scene_batch_pyramid_read
+ * too) are that call's, bit for bit. With R the most frames one stream has in the call, R (2 levels + 4) + 5 launches, as the plain
+ * batched pyramid, and no host wait. Levels, descent, thresholds, choice, reach and int32 conditions are those of the "scene
+ * memory: normalised pyramid registration" section; nothing is redefined here. With n_rot = 1 and radius = refine = 0 it IS
+ * yh_scene_batch_append_memory with the same motions.
+ * Checks, for every frame before anything is touched: every check of yh_scene_batch_append_memory_pyramid, with its texts;
+ * YH_EINVAL for min_inside out of range. A refused call leaves frames, plans, memories, the last readable motions and level tables
+ * as they were; a call that fails later behaves as yh_scene_batch_append_memory does. Asynchronous on the handle's stream. The
+ * level tables (three times the plain pyramid's: 443 936 bytes per frame), the flags (256 bytes per frame), the pooled levels,
+ * tables of level bases, records and extensions of max_frames frames are allocated at the first batched normalised pyramid append:
+ * 113.6 MB of level tables for 256 frames, beside the plain batched pyramid's 0.8 MB of pooled levels per frame at 640 x 480. */
+int yh_scene_batch_append_memory_pyramid_norm(yh_scene_batch* h, int32_t n_frames, const int32_t* streams /* [n] or NULL */,
+                                              int32_t n_rot, const int32_t* gather_q16 /* [n][n_rot][6] */,
+                                              const int32_t* carry_q16 /* [n][n_rot][6] */, int32_t levels, int32_t radius,
+                                              int32_t refine, int32_t min_inside, int32_t keep, int32_t ball_max_age);
+/* One level (0 .. levels) of what the last yh_scene_batch_append_memory_pyramid_norm did for frame `frame`, laid out as
+ * yh_scene_pyramid_norm_read; any pointer may be NULL. Waits. YH_ESTATE unless the last memory append of the batch was a normalised
+ * pyramid append whose frames are the current ones (a memory reset since ends that too); YH_EINVAL for a frame outside it or a level
+ * outside 0 .. levels. */
+int yh_scene_batch_pyramid_norm_read(yh_scene_batch* h, int32_t frame, int32_t level, int32_t* centres /* [hyp][2] */,
+                                     uint64_t* scores, uint64_t* totals, uint64_t* inside /* [hyp][2p+1][2p+1] each */,
+                                     uint64_t* sum_n, int32_t* level_min_inside, int32_t* qualified /* [hyp] */);
 /* Device copy of the frame the last yh_classify_frame_u32 produced (valid until the next classify on this handle). */
 const uint32_t* yh_classify_device_frame(const yh_engine* h);
 

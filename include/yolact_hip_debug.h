@@ -213,6 +213,16 @@ int yh_scene_batch_memory_search_time(yh_scene_batch* h, int32_t reps, float* ms
  * alone (the clear, every round's levels, scores and choices), ms_search. Both rewrite the same bits and commit nothing. Refused as
  * yh_scene_batch_memory_search_time refuses. */
 int yh_scene_batch_memory_pyramid_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, float* ms_search);
+/* The same for frames that came from yh_scene_batch_append_memory_search_norm (the four hooks above refuse such frames with
+ * YH_ESTATE and name this function): the whole append replayed from the state it started from, ms_per_batch; then its registration
+ * launches alone (the clear, every round's three tables and choice), ms_search. Both rewrite the same bits and commit nothing.
+ * YH_ESTATE in every other state: frames of any other append, a memory reset or a slot staged since. */
+int yh_scene_batch_memory_search_norm_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, float* ms_search);
+/* The same for frames that came from yh_scene_batch_append_memory_pyramid_norm (the four hooks above refuse such frames with
+ * YH_ESTATE and name this function): the whole append replayed from the state it started from and the tables of level bases as they
+ * stand on the device, ms_per_batch; then its registration launches alone (the clear, every round's levels, tables and choices),
+ * ms_search. Refused as yh_scene_batch_memory_search_norm_time refuses. */
+int yh_scene_batch_memory_pyramid_norm_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, float* ms_search);
 /* yh_scene_plan_time for the last yh_scene_batch_plan: milliseconds per batch; rounds = launches in which some tile of some frame
  * ran (those of the slowest frame), tile_runs summed over the frames. */
 int yh_scene_batch_plan_time(yh_scene_batch* h, int32_t reps, float* ms_per_batch, int32_t* rounds, int32_t* tile_runs);

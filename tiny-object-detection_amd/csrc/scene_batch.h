@@ -41,4 +41,6 @@ void scene_batch_memory_free(yh_scene_batch* hb);
 bool scene_batch_memory_is_last(const yh_scene_batch* hb);
 bool scene_batch_memory_is_search(const yh_scene_batch* hb);   // .. from yh_scene_batch_append_memory_search
 bool scene_batch_memory_is_pyramid(const yh_scene_batch* hb);  // .. from yh_scene_batch_append_memory_pyramid
+bool scene_batch_memory_is_norm(const yh_scene_batch* hb);          // .. from yh_scene_batch_append_memory_search_norm (is_search holds too)
+bool scene_batch_memory_is_pyramid_norm(const yh_scene_batch* hb);  // .. from yh_scene_batch_append_memory_pyramid_norm (is_pyramid does not hold)
 }

@@ -236,6 +236,10 @@ int yh_scene_batch_read(yh_scene_batch* hb, int32_t frame, uint32_t* map, float*
 int yh_scene_batch_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch) {
     if (!hb || reps < 1 || !ms_per_batch) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (scene_batch_memory_is_pyramid_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_memory_pyramid_norm_time replays them");
+    if (scene_batch_memory_is_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search_norm: yh_scene_batch_memory_search_norm_time replays them");
     if (scene_batch_memory_is_pyramid(hb))
         return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_memory_pyramid_time replays them");
     if (scene_batch_memory_is_search(hb))

@@ -1,5 +1,6 @@
 // scene_batch_memory.h — the state of the scene batch's bank of memories (scene_batch_memory.hip), for the units that run on it:
-// the memory append itself, its registration (scene_batch_register.hip) and its pyramid registration (scene_batch_pyramid.hip).
+// the memory append itself, its registration (scene_batch_register.hip), its pyramid registration (scene_batch_pyramid.hip) and the
+// normalised forms of both (scene_batch_register_norm.hip, scene_batch_pyramid_norm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,7 +10,9 @@
 #include "scene_batch.h"
 #include "scene_memory_dev.h"
 #include "scene_pyramid_dev.h"
+#include "scene_pyramid_norm_dev.h"
 #include "scene_register_dev.h"
+#include "scene_register_norm_dev.h"
 
 namespace yh {
 
@@ -43,7 +46,7 @@ struct yh_scene_batch_memory {
     yh::SceneRegisterRecord* reg_rec = nullptr;   // [max_frames]
     bool searched = false;
     int n_rot = 0, radius = 0;
-    size_t acc_stride() const { return 1 + (size_t)n_rot * (2 * radius + 1) * (2 * radius + 1); }
+    size_t acc_stride() const { return 1 + (norm_min_inside ? 3 : 1) * yh::register_norm_table_words(n_rot, radius); }
     // pyramid registration, allocated at the first pyramid append (it shares reg_rec): frame b's pooled levels of N, then of M, at
     // pyr_maps + b * 2 * scene_pyramid_map_words, its level tables at pyr_acc + b * pyr.acc_offset(levels + 1) (the stride is the
     // call's), its table of level bases at pyr_table + b. pyramid: the last memory append was a pyramid append; pyr: its n_rot,
@@ -54,6 +57,19 @@ struct yh_scene_batch_memory {
     std::vector<yh::ScenePyramidTable> pyr_host;
     bool pyramid = false;
     yh::ScenePyramidPlan pyr;
+    // normalised registration, allocated at the first such append. norm_min_inside != 0: the last memory append was a normalised
+    // search (searched is true as well, n_rot and radius are its own): frame b's sum_n, then its S, T and C tables, at
+    // norm_acc + b * acc_stride (the call's: 1 + 3 n_rot (2 radius + 1)^2 words), its record at reg_rec + b, the extension at
+    // norm_rec + b.
+    unsigned long long* norm_acc = nullptr;          // [max_frames][scene_register_norm_acc_bytes / 8]
+    yh::SceneRegisterNormRecord* norm_rec = nullptr; // [max_frames]
+    int norm_min_inside = 0;
+    // normalised pyramid registration, allocated at the first such append (it shares pyr_maps, pyr_table, pyr_host, reg_rec and
+    // norm_rec; pyramid stays false). pyr_norm_min_inside != 0: the last memory append was one, pyr its parameters: frame b's level
+    // tables at pyrn_acc + b * pyramid_norm_acc_offset(pyr, levels + 1) (the stride is the call's), its flags at pyrn_ext + b.
+    unsigned long long* pyrn_acc = nullptr;          // [max_frames][scene_pyramid_norm_acc_bytes / 8]
+    yh::ScenePyramidNormExt* pyrn_ext = nullptr;     // [max_frames]
+    int pyr_norm_min_inside = 0;
 };
 
 namespace yh {
@@ -78,4 +94,17 @@ void scene_batch_register_fuse_round(yh_scene_batch* hb, const SceneFuseParams& 
 // scene_batch_register_balls.
 int scene_batch_pyramid_reserve(yh_scene_batch* hb);
 int scene_batch_pyramid_search(yh_scene_batch* hb, const SceneFuseParams* f);
+// the pooling of one round alone: levels 1 .. levels of N and M of `count` slots from `round` into the frames' parts of pyr_maps;
+// pp is filled for frame 0 (level l of its N at pp.dst[0][l - 1], of its M at pp.dst[1][l - 1]; a frame 2 x map_words further on)
+void scene_batch_pyramid_levels_round(yh_scene_batch* hb, int levels, const SceneFuseSlot* round, unsigned count, ScenePyramidParams& pp);
+
+// scene_batch_register_norm.hip: scene_batch_register_reserve / _search for the last scheduled normalised search append (the S, T
+// and C tables, the records and their extensions; min_inside is the call's). The fuse and the ball chains are the plain search's.
+int scene_batch_register_norm_reserve(yh_scene_batch* hb);
+int scene_batch_register_norm_search(yh_scene_batch* hb, const SceneFuseParams* f);
+
+// scene_batch_pyramid_norm.hip: scene_batch_pyramid_reserve / _search for the last scheduled normalised pyramid append. The pooling
+// is scene_batch_pyramid_levels_round, the fuse and the ball chains are the plain search's.
+int scene_batch_pyramid_norm_reserve(yh_scene_batch* hb);
+int scene_batch_pyramid_norm_search(yh_scene_batch* hb, const SceneFuseParams* f);
 }

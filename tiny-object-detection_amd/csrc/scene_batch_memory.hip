@@ -19,7 +19,10 @@
 // one upload; each round's fuse is preceded by the round's scores and choice, and the ball chains run last, on the records
 // (scene_batch_register.hip). yh_scene_batch_append_memory_pyramid (DESIGN.md section 11 "Scene batch: pyramid registration") is that
 // again with each round's motions found coarse to fine (scene_batch_pyramid.hip): the frames' tables of level bases go up in a copy
-// of their own. The bank's state is in scene_batch_memory.h for the three units.
+// of their own. yh_scene_batch_append_memory_search_norm and _pyramid_norm (DESIGN.md section 11 "Scene batch: normalised
+// registration", "Scene batch: normalised pyramid registration") are those two with every choice made by the single handle's
+// normalised score among the candidates that keep min_inside pixels inside (scene_batch_register_norm.hip,
+// scene_batch_pyramid_norm.hip): the same schedule, uploads and launches. The bank's state is in scene_batch_memory.h for the units.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -73,7 +76,7 @@ size_t steps_bytes(const yh_scene* h) { return scene_batch_steps_bytes(h); }
 // the buffers every memory append uses, at the first one: a batch that never remembers pays nothing
 // (a search: the score tables and records too, and the device table grows by the frames' bases - the stream is drained before
 // the smaller one goes, and whoever fails after this leaves nothing to replay; a pyramid append: its own buffers instead)
-int memory_reserve(yh_scene_batch* hb, bool search, bool pyramid) {
+int memory_reserve(yh_scene_batch* hb, bool search, bool pyramid, bool norm) {
     yh_scene* h = &hb->core;
     if (!hb->memory) hb->memory = new yh_scene_batch_memory();
     yh_scene_batch_memory* m = hb->memory;
@@ -91,8 +94,9 @@ int memory_reserve(yh_scene_batch* hb, bool search, bool pyramid) {
         SCHK(h, hipMalloc((void**)&m->table, need));
         m->table_bytes = need;
     }
-    if (pyramid) return scene_batch_pyramid_reserve(hb);
-    return search ? scene_batch_register_reserve(hb) : YH_OK;
+    if (pyramid) return norm ? scene_batch_pyramid_norm_reserve(hb) : scene_batch_pyramid_reserve(hb);
+    if (search) return norm ? scene_batch_register_norm_reserve(hb) : scene_batch_register_reserve(hb);
+    return YH_OK;
 }
 
 // one stream's two maps and two tables, at its first use; cleared if they are fresh or stale
@@ -111,6 +115,14 @@ int stream_reserve(yh_scene_batch* hb, int s) {
     }
     k.stale = false;
     return YH_OK;
+}
+
+// the registration launches of the last scheduled searching append (with f: each round's fuse behind them)
+int registration(yh_scene_batch* hb, const SceneFuseParams* f) {
+    const yh_scene_batch_memory* m = hb->memory;
+    if (m->pyr_norm_min_inside) return scene_batch_pyramid_norm_search(hb, f);
+    if (m->pyramid) return scene_batch_pyramid_search(hb, f);
+    return m->norm_min_inside ? scene_batch_register_norm_search(hb, f) : scene_batch_register_search(hb, f);
 }
 
 // the launches of the last scheduled memory append, from the device tables as they stand
@@ -135,8 +147,8 @@ int run_memory(yh_scene_batch* hb) {
     f.map = h->map; f.world = h->world; f.conn0 = h->conn0; f.conn1 = h->conn1;
     f.W = h->W; f.H = h->H; f.keep = m->keep;
     for (int i = 0; i < 6; ++i) { b.c[i] = 0; f.g[i] = 0; }
-    if (m->searched || m->pyramid) {   // the motions are found round by round; the ball chains need every frame's record
-        const int rs = m->pyramid ? scene_batch_pyramid_search(hb, &f) : scene_batch_register_search(hb, &f);
+    if (m->searched || m->pyramid || m->pyr_norm_min_inside) {   // the motions are found round by round; the ball chains need every frame's record
+        const int rs = registration(hb, &f);
         return rs ? rs : scene_batch_register_balls(hb, b);
     }
     hipLaunchKernelGGL(batch_balls_memory, dim3((unsigned)m->chains), dim3(128), 0, h->stream, b, chains, steps, m->tabs);
@@ -152,13 +164,13 @@ int stream_of(const int32_t* streams, int b) { return streams ? streams[b] : 0; 
 // n_rot 0: gather and carry are one motion per frame. Otherwise n_rot bases per frame, searched around with `radius`: the slots and
 // steps carry no motion (the kernels read each frame's from its record) and the frames' bases follow the chains in the one upload.
 // plans given: a pyramid append, frame b's table of level bases in plans[b]; the slots and steps carry no motion either, there are no
-// plain bases, and the tables go up in a second copy.
+// plain bases, and the tables go up in a second copy. min_inside != 0: the normalised form of the search or of the pyramid append.
 int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32_t* gather, const int32_t* carry, int keep, int max_age, int n_rot = 0, int radius = 0,
-                  const std::vector<ScenePyramidPlan>* plans = nullptr) {
+                  const std::vector<ScenePyramidPlan>* plans = nullptr, int min_inside = 0) {
     yh_scene* h = &hb->core;
     SCHK(h, hipSetDevice(h->dev));
     const bool search = n_rot > 0 && !plans, given = n_rot == 0;
-    int rc = memory_reserve(hb, search, plans != nullptr);
+    int rc = memory_reserve(hb, search, plans != nullptr, min_inside != 0);
     if (rc) return rc;
     yh_scene_batch_memory* m = hb->memory;
     // the schedule: the frames of every stream in batch order; R rounds
@@ -217,7 +229,9 @@ int append_memory(yh_scene_batch* hb, int n, const int32_t* streams, const int32
     }
     m->n = n; m->keep = keep; m->max_age = max_age;
     m->searched = search; m->n_rot = n_rot; m->radius = radius;
-    m->pyramid = plans != nullptr;
+    m->pyramid = plans != nullptr && !min_inside;
+    m->norm_min_inside = search ? min_inside : 0;
+    m->pyr_norm_min_inside = plans ? min_inside : 0;
     // (from pageable memory: staged by the runtime before the call returns, as the caller's own arrays have been read by now)
     SCHK(h, hipMemcpyAsync(m->table, m->table_host.data(), m->table_host.size(), hipMemcpyHostToDevice, h->stream));
     if (plans) {
@@ -247,7 +261,7 @@ void scene_batch_memory_free(yh_scene_batch* hb) {
         void* bufs[] = { k.map[0], k.map[1], k.tab[0], k.tab[1] };
         for (void* b : bufs) if (b) hipFree(b);
     }
-    void* bufs[] = { m->stamp, m->tabs, m->table, m->reg_acc, m->reg_rec, m->pyr_maps, m->pyr_acc, m->pyr_table };
+    void* bufs[] = { m->stamp, m->tabs, m->table, m->reg_acc, m->reg_rec, m->pyr_maps, m->pyr_acc, m->pyr_table, m->norm_acc, m->norm_rec, m->pyrn_acc, m->pyrn_ext };
     for (void* b : bufs) if (b) hipFree(b);
     delete m;
     hb->memory = nullptr;
@@ -256,6 +270,8 @@ void scene_batch_memory_free(yh_scene_batch* hb) {
 bool scene_batch_memory_is_last(const yh_scene_batch* hb) { return hb->memory && hb->memory->frame != 0 && hb->memory->frame == hb->core.frames; }
 bool scene_batch_memory_is_search(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->searched; }
 bool scene_batch_memory_is_pyramid(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->pyramid; }
+bool scene_batch_memory_is_norm(const yh_scene_batch* hb) { return scene_batch_memory_is_search(hb) && hb->memory->norm_min_inside != 0; }
+bool scene_batch_memory_is_pyramid_norm(const yh_scene_batch* hb) { return scene_batch_memory_is_last(hb) && hb->memory->pyr_norm_min_inside != 0; }
 }  // namespace yh
 
 namespace {
@@ -275,18 +291,20 @@ int append_memory_checks(yh_scene_batch* hb, int32_t n_frames, const int32_t* st
     return YH_OK;
 }
 
-// what all three do around append_memory once the checks have passed (n_rot 0: the motions are given; plans: a pyramid append)
+// what all five do around append_memory once the checks have passed (n_rot 0: the motions are given; plans: a pyramid append;
+// min_inside != 0: a normalised one)
 int append_memory_call(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, const int32_t* gather_q16, const int32_t* carry_q16,
-                       int32_t keep, int32_t ball_max_age, int32_t n_rot, int32_t radius, const std::vector<ScenePyramidPlan>* plans = nullptr) {
+                       int32_t keep, int32_t ball_max_age, int32_t n_rot, int32_t radius, const std::vector<ScenePyramidPlan>* plans = nullptr,
+                       int32_t min_inside = 0) {
     yh_scene* h = &hb->core;
     ++h->frames;   // (earlier plans are of other frames, whatever becomes of these)
-    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, plans);
+    const int rc = append_memory(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, plans, min_inside);
     yh_scene_batch_memory* m = hb->memory;
     if (rc) {
         // a call that fails after its checks leaves no frame and empties the memories of the streams it named
         h->ran = false; hb->n = 0;
         if (m) {
-            m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false;
+            m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; m->pyr_norm_min_inside = 0;
             for (int b = 0; b < n_frames; ++b) m->bank[stream_of(streams, b)].stale = true;
         }
         return rc;
@@ -309,7 +327,7 @@ int replay_time(yh_scene_batch* hb, int reps, Run run, float* ms_out) {
     for (int r = 0; r < reps; ++r) {
         const int rc = run();
         if (rc) {
-            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false;
+            h->ran = false; hb->n = 0; m->frame = 0; m->replayable = false; m->searched = false; m->pyramid = false; m->norm_min_inside = 0; m->pyr_norm_min_inside = 0;
             for (BankStream& k : m->bank) k.stale = true;
             return rc;
         }
@@ -364,11 +382,99 @@ int yh_scene_batch_append_memory_pyramid(yh_scene_batch* hb, int32_t n_frames, c
     return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, &plans);
 }
 
+int yh_scene_batch_append_memory_search_norm(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, int32_t n_rot, const int32_t* gather_q16,
+                                             const int32_t* carry_q16, int32_t radius, int32_t min_inside, int32_t keep, int32_t ball_max_age) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    int rc = append_memory_checks(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    if (rc) return rc;
+    if (n_rot < 1 || n_rot > SR_MAX_ROT) return h->fail(YH_EINVAL, "n_rot outside 1 .. 16");
+    if (radius < 0 || radius > SR_MAX_R) return h->fail(YH_EINVAL, "radius outside 0 .. 8");
+    if (min_inside < 1 || (long long)min_inside > (long long)h->W * h->H) return h->fail(YH_EINVAL, "min_inside outside 1 .. width x height");
+    for (int b = 0; b < n_frames; ++b)
+        if ((rc = scene_register_bases_check(h, n_rot, gather_q16 + (size_t)b * n_rot * 6, carry_q16 + (size_t)b * n_rot * 6, radius))) return hb->framed(b, rc);
+    return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, nullptr, min_inside);
+}
+
+int yh_scene_batch_append_memory_pyramid_norm(yh_scene_batch* hb, int32_t n_frames, const int32_t* streams, int32_t n_rot, const int32_t* gather_q16,
+                                              const int32_t* carry_q16, int32_t levels, int32_t radius, int32_t refine, int32_t min_inside, int32_t keep,
+                                              int32_t ball_max_age) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    int rc = append_memory_checks(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age);
+    if (rc) return rc;
+    if (n_rot < 1 || n_rot > SP_MAX_ROT) return h->fail(YH_EINVAL, "n_rot outside 1 .. 15");
+    if (levels < 1 || levels > SP_MAX_LEVELS) return h->fail(YH_EINVAL, "levels outside 1 .. 3");
+    if (radius < 0 || radius > SR_MAX_R) return h->fail(YH_EINVAL, "radius outside 0 .. 8");
+    if (refine < 0 || refine > SR_MAX_R) return h->fail(YH_EINVAL, "refine outside 0 .. 8");
+    if (min_inside < 1 || (long long)min_inside > (long long)h->W * h->H) return h->fail(YH_EINVAL, "min_inside outside 1 .. width x height");
+    std::vector<ScenePyramidPlan> plans((size_t)n_frames);
+    for (int b = 0; b < n_frames; ++b)
+        if ((rc = scene_pyramid_plan_make(h, n_rot, gather_q16 + (size_t)b * n_rot * 6, carry_q16 + (size_t)b * n_rot * 6, levels, radius, refine, plans[b]))) return hb->framed(b, rc);
+    return append_memory_call(hb, n_frames, streams, gather_q16, carry_q16, keep, ball_max_age, n_rot, radius, &plans, min_inside);
+}
+
+int yh_scene_batch_motion_norm_read(yh_scene_batch* hb, int32_t frame, uint64_t* totals, uint64_t* inside, uint64_t* chosen_stc, uint64_t* prior_stc, int32_t* qualified) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    const bool pyr_norm = h->ran && scene_batch_memory_is_pyramid_norm(hb);
+    if (!pyr_norm && (!h->ran || !scene_batch_memory_is_norm(hb))) return h->fail(YH_ESTATE, "the current frames did not come from yh_scene_batch_append_memory_search_norm");
+    if (pyr_norm && (totals || inside))
+        return h->fail(YH_EINVAL, "the current frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_pyramid_norm_read returns their level tables");
+    if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
+    SCHK(h, hipSetDevice(h->dev));
+    yh_scene_batch_memory* m = hb->memory;
+    SceneRegisterNormRecord ext;
+    const size_t words = register_norm_table_words(m->n_rot, m->radius);
+    const unsigned long long* acc = pyr_norm ? nullptr : m->norm_acc + (size_t)frame * m->acc_stride();
+    SCHK(h, hipMemcpyAsync(&ext, m->norm_rec + frame, sizeof(ext), hipMemcpyDeviceToHost, h->stream));
+    if (totals) SCHK(h, hipMemcpyAsync(totals, acc + 1 + words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    if (inside) SCHK(h, hipMemcpyAsync(inside, acc + 1 + 2 * words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 3; ++i) { if (chosen_stc) chosen_stc[i] = ext.chosen[i]; if (prior_stc) prior_stc[i] = ext.prior[i]; }
+    if (qualified) *qualified = ext.qualified;
+    return YH_OK;
+}
+
+int yh_scene_batch_pyramid_norm_read(yh_scene_batch* hb, int32_t frame, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* totals, uint64_t* inside,
+                                     uint64_t* sum_n, int32_t* level_min_inside, int32_t* qualified) {
+    if (!hb) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    // (replayable: no memory has been reset since, as yh_scene_batch_pyramid_read asks)
+    if (!h->ran || !scene_batch_memory_is_pyramid_norm(hb) || !hb->memory->replayable)
+        return h->fail(YH_ESTATE, "the last memory append of the batch was not yh_scene_batch_append_memory_pyramid_norm (or a memory was reset since)");
+    if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
+    yh_scene_batch_memory* m = hb->memory;
+    const ScenePyramidPlan& plan = m->pyr;
+    if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
+    SCHK(h, hipSetDevice(h->dev));
+    const int hyp = plan.hyp(level);
+    const size_t words = register_norm_table_words(hyp, plan.rho(level));
+    const unsigned long long* acc = m->pyrn_acc + (size_t)frame * pyramid_norm_acc_offset(plan, plan.levels + 1) + pyramid_norm_acc_offset(plan, level);
+    int cen[SR_MAX_ROT][2], flags[SR_MAX_ROT];
+    unsigned long long sum = 0;
+    if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr_table[frame].centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
+    if (qualified) SCHK(h, hipMemcpyAsync(flags, m->pyrn_ext[frame].qualified[level], sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    if (sum_n) SCHK(h, hipMemcpyAsync(&sum, acc, sizeof(sum), hipMemcpyDeviceToHost, h->stream));
+    uint64_t* const tabs[3] = { scores, totals, inside };
+    for (int t = 0; t < 3; ++t)
+        if (tabs[t]) SCHK(h, hipMemcpyAsync(tabs[t], acc + 1 + t * words, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < hyp; ++k) {
+        if (centres) { centres[2 * k] = cen[k][0]; centres[2 * k + 1] = cen[k][1]; }
+        if (qualified) qualified[k] = flags[k];
+    }
+    if (sum_n) *sum_n = sum;
+    if (level_min_inside) *level_min_inside = (int32_t)pyramid_norm_min_inside(m->pyr_norm_min_inside, level);
+    return YH_OK;
+}
+
 int yh_scene_batch_pyramid_read(yh_scene_batch* hb, int32_t frame, int32_t level, int32_t* centres, uint64_t* scores, uint64_t* sum_n) {
     if (!hb) return YH_EINVAL;
     yh_scene* h = &hb->core;
     // (replayable: no memory has been reset since, as yh_scene_pyramid_read asks of the single handle)
-    if (!h->ran || !scene_batch_memory_is_pyramid(hb) || !hb->memory->replayable)
+    const bool norm = scene_batch_memory_is_pyramid_norm(hb);
+    if (!h->ran || !(scene_batch_memory_is_pyramid(hb) || norm) || !hb->memory->replayable)
         return h->fail(YH_ESTATE, "the last memory append of the batch was not yh_scene_batch_append_memory_pyramid (or a memory was reset since)");
     if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
     yh_scene_batch_memory* m = hb->memory;
@@ -376,7 +482,9 @@ int yh_scene_batch_pyramid_read(yh_scene_batch* hb, int32_t frame, int32_t level
     if (level < 0 || level > plan.levels) return h->fail(YH_EINVAL, "level outside 0 .. " + std::to_string(plan.levels));
     SCHK(h, hipSetDevice(h->dev));
     const int hyp = plan.hyp(level), nu = 2 * plan.rho(level) + 1;
-    const unsigned long long* acc = m->pyr_acc + (size_t)frame * plan.acc_offset(plan.levels + 1) + plan.acc_offset(level);
+    // (after a normalised pyramid append: its S tables, which lie first in each level of its own tables)
+    const unsigned long long* acc = norm ? m->pyrn_acc + (size_t)frame * pyramid_norm_acc_offset(plan, plan.levels + 1) + pyramid_norm_acc_offset(plan, level)
+                                         : m->pyr_acc + (size_t)frame * plan.acc_offset(plan.levels + 1) + plan.acc_offset(level);
     int cen[SR_MAX_ROT][2];
     unsigned long long sum = 0;
     if (centres) SCHK(h, hipMemcpyAsync(cen, m->pyr_table[frame].centre[level], sizeof(cen), hipMemcpyDeviceToHost, h->stream));
@@ -391,8 +499,11 @@ int yh_scene_batch_pyramid_read(yh_scene_batch* hb, int32_t frame, int32_t level
 int yh_scene_batch_motion_read(yh_scene_batch* hb, int32_t frame, int32_t* gather_q16, int32_t* carry_q16, int32_t* chosen, uint64_t* score, uint64_t* scores) {
     if (!hb) return YH_EINVAL;
     yh_scene* h = &hb->core;
-    const bool pyramid = h->ran && scene_batch_memory_is_pyramid(hb);
+    const bool pyr_norm = h->ran && scene_batch_memory_is_pyramid_norm(hb);
+    const bool pyramid = pyr_norm || (h->ran && scene_batch_memory_is_pyramid(hb));
     if (!pyramid && (!h->ran || !scene_batch_memory_is_search(hb))) return h->fail(YH_ESTATE, "the current frames did not come from yh_scene_batch_append_memory_search");
+    if (pyr_norm && scores)
+        return h->fail(YH_EINVAL, "the current frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_pyramid_read returns their level tables");
     if (pyramid && scores) return h->fail(YH_EINVAL, "the current frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_pyramid_read returns their level tables");
     if (frame < 0 || frame >= hb->n) return h->fail(YH_EINVAL, "frame " + std::to_string(frame) + " outside the last append's " + std::to_string(hb->n));
     SCHK(h, hipSetDevice(h->dev));
@@ -400,7 +511,9 @@ int yh_scene_batch_motion_read(yh_scene_batch* hb, int32_t frame, int32_t* gathe
     SceneRegisterRecord rec;
     const size_t stride = m->acc_stride();
     SCHK(h, hipMemcpyAsync(&rec, m->reg_rec + frame, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
-    if (scores) SCHK(h, hipMemcpyAsync(scores, m->reg_acc + (size_t)frame * stride + 1, (stride - 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    // (after a normalised search: its S table, which lies first in the frame's tables)
+    const unsigned long long* acc = m->norm_min_inside ? m->norm_acc : m->reg_acc;
+    if (scores) SCHK(h, hipMemcpyAsync(scores, acc + (size_t)frame * stride + 1, register_norm_table_words(m->n_rot, m->radius) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < 6; ++i) { if (gather_q16) gather_q16[i] = rec.g[i]; if (carry_q16) carry_q16[i] = rec.c[i]; }
     for (int i = 0; i < 3; ++i) { if (chosen) chosen[i] = rec.chosen[i]; if (score) score[i] = rec.score[i]; }
@@ -460,6 +573,10 @@ int yh_scene_batch_memory_reset(yh_scene_batch* hb, int32_t stream) {
 int yh_scene_batch_memory_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch) {
     if (!hb || reps < 1 || !ms_per_batch) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_pyramid_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_memory_pyramid_norm_time replays them");
+    if (h->ran && scene_batch_memory_is_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search_norm: yh_scene_batch_memory_search_norm_time replays them");
     if (h->ran && scene_batch_memory_is_pyramid(hb))
         return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_memory_pyramid_time replays them");
     if (h->ran && scene_batch_memory_is_search(hb))
@@ -475,6 +592,10 @@ int yh_scene_batch_memory_time(yh_scene_batch* hb, int32_t reps, float* ms_per_b
 int yh_scene_batch_memory_search_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
     if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_pyramid_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_memory_pyramid_norm_time replays them");
+    if (h->ran && scene_batch_memory_is_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search_norm: yh_scene_batch_memory_search_norm_time replays them");
     if (h->ran && scene_batch_memory_is_pyramid(hb))
         return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid: yh_scene_batch_memory_pyramid_time replays them");
     if (!h->ran || !scene_batch_memory_is_search(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
@@ -489,6 +610,10 @@ int yh_scene_batch_memory_search_time(yh_scene_batch* hb, int32_t reps, float* m
 int yh_scene_batch_memory_pyramid_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
     if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
     yh_scene* h = &hb->core;
+    if (h->ran && scene_batch_memory_is_pyramid_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_pyramid_norm: yh_scene_batch_memory_pyramid_norm_time replays them");
+    if (h->ran && scene_batch_memory_is_norm(hb))
+        return h->fail(YH_ESTATE, "the last frames came from yh_scene_batch_append_memory_search_norm: yh_scene_batch_memory_search_norm_time replays them");
     if (!h->ran || !scene_batch_memory_is_pyramid(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
         return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_pyramid (or a memory was reset or a slot staged since)");
     SCHK(h, hipSetDevice(h->dev));
@@ -496,6 +621,29 @@ int yh_scene_batch_memory_pyramid_time(yh_scene_batch* hb, int32_t reps, float* 
     // them), then the clear and every round's levels, scores and choices alone, on each predecessor's fused map
     const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
     return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_pyramid_search(hb, nullptr); }, ms_search);
+}
+
+int yh_scene_batch_memory_search_norm_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
+    if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (!h->ran || !scene_batch_memory_is_norm(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
+        return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_search_norm (or a memory was reset or a slot staged since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_batch_memory_search_time: the whole append, then its registration launches alone on the map slots that left
+    const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
+    return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_register_norm_search(hb, nullptr); }, ms_search);
+}
+
+int yh_scene_batch_memory_pyramid_norm_time(yh_scene_batch* hb, int32_t reps, float* ms_per_batch, float* ms_search) {
+    if (!hb || reps < 1 || !ms_per_batch || !ms_search) return YH_EINVAL;
+    yh_scene* h = &hb->core;
+    if (!h->ran || !scene_batch_memory_is_pyramid_norm(hb) || !hb->memory->replayable || hb->memory->stagings != hb->stagings)
+        return h->fail(YH_ESTATE, "the last frames did not come from yh_scene_batch_append_memory_pyramid_norm (or a memory was reset or a slot staged since)");
+    SCHK(h, hipSetDevice(h->dev));
+    // as yh_scene_batch_memory_pyramid_time: the whole append from the tables on the device, then the clear and every round's
+    // levels, tables and choices alone, on each predecessor's fused map
+    const int rc = replay_time(hb, reps, [hb] { return run_memory(hb); }, ms_per_batch);
+    return rc ? rc : replay_time(hb, reps, [hb] { return scene_batch_pyramid_norm_search(hb, nullptr); }, ms_search);
 }
 
 }  // extern "C"

@@ -85,6 +85,21 @@ int scene_batch_pyramid_reserve(yh_scene_batch* hb) {
     return YH_OK;
 }
 
+void scene_batch_pyramid_levels_round(yh_scene_batch* hb, int levels, const SceneFuseSlot* round, unsigned count, ScenePyramidParams& pp) {
+    yh_scene* h = &hb->core;
+    yh_scene_batch_memory* m = hb->memory;
+    const int W = h->W, H = h->H;
+    const size_t words = scene_pyramid_map_words(W, H);
+    pp = ScenePyramidParams{};
+    pp.src[0] = m->stamp; pp.src[1] = nullptr; pp.W = W; pp.H = H; pp.levels = levels;
+    for (int l = 1; l <= levels; ++l) {
+        pp.dst[0][l - 1] = m->pyr_maps + scene_pyramid_map_offset(W, H, l);
+        pp.dst[1][l - 1] = m->pyr_maps + words + scene_pyramid_map_offset(W, H, l);
+    }
+    const unsigned tiles0 = (unsigned)(((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH));   // <= 128 * 512
+    hipLaunchKernelGGL(batch_pyramid, dim3(tiles0, 2, count), dim3(256), 0, h->stream, pp, round, 2 * words);
+}
+
 int scene_batch_pyramid_search(yh_scene_batch* hb, const SceneFuseParams* f) {
     yh_scene* h = &hb->core;
     yh_scene_batch_memory* m = hb->memory;
@@ -95,16 +110,10 @@ int scene_batch_pyramid_search(yh_scene_batch* hb, const SceneFuseParams* f) {
     const SceneFuseSlot* slots = (const SceneFuseSlot*)m->table;
     const size_t words = scene_pyramid_map_words(W, H), npx = (size_t)W * H;
     ScenePyramidParams pp = {};
-    pp.src[0] = m->stamp; pp.src[1] = nullptr; pp.W = W; pp.H = H; pp.levels = L;
-    for (int l = 1; l <= L; ++l) {
-        pp.dst[0][l - 1] = m->pyr_maps + scene_pyramid_map_offset(W, H, l);
-        pp.dst[1][l - 1] = m->pyr_maps + words + scene_pyramid_map_offset(W, H, l);
-    }
-    const unsigned tiles0 = (unsigned)(((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH));   // <= 128 * 512
     for (size_t r = 0; r + 1 < m->round_off.size(); ++r) {
         const SceneFuseSlot* round = slots + m->round_off[r];
         const unsigned count = (unsigned)(m->round_off[r + 1] - m->round_off[r]);   // <= max_frames <= 256
-        hipLaunchKernelGGL(batch_pyramid, dim3(tiles0, 2, count), dim3(256), 0, h->stream, pp, round, 2 * words);
+        scene_batch_pyramid_levels_round(hb, L, round, count, pp);
         for (int l = L; l >= 0; --l) {
             SceneRegisterParams p;
             p.stamp = l ? pp.dst[0][l - 1] : m->stamp; p.mem = nullptr;

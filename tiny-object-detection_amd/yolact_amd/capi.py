@@ -207,6 +207,12 @@ SYMBOLS = [
     ("yh_scene_batch_append_memory_pyramid", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
     ("yh_scene_batch_pyramid_read", _i, [_vp, _i, _i, _vp, _vp, _vp]),
     ("yh_scene_batch_memory_pyramid_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_batch_append_memory_search_norm", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i]),
+    ("yh_scene_batch_motion_norm_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_batch_memory_search_norm_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("yh_scene_batch_append_memory_pyramid_norm", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    ("yh_scene_batch_pyramid_norm_read", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("yh_scene_batch_memory_pyramid_norm_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("yh_scene_batch_plan_turn", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("yh_scene_batch_turn_read", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_turn_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
@@ -1766,6 +1772,88 @@ class SceneBatch:
         """(ms per batch, ms of the registration launches alone) of the last append_memory_search, replayed; commits nothing."""
         ms, ms_search = C.c_float(), C.c_float()
         self._chk(self.L.yh_scene_batch_memory_search_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
+    def _candidates(self, n, candidates):
+        """(gathers, carries, n_rot) of n (gathers, carries) pairs as the batched searching appends take them; None: the identity alone."""
+        if candidates is None:
+            candidates = [([SCENE_IDENTITY_Q16], [SCENE_IDENTITY_Q16])] * max(n, 0)
+        g = np.ascontiguousarray(np.array([m[0] for m in candidates], np.int32))   # (a value outside int32 raises here)
+        c = np.ascontiguousarray(np.array([m[1] for m in candidates], np.int32))
+        assert len(candidates) == max(n, 0), "candidates: one (gathers, carries) pair per frame"
+        assert n <= 0 or (g.ndim == 3 and g.shape[2] == 6 and c.shape == g.shape), "candidates: the same number of rows of six ints for every frame"
+        return g, c, (g.shape[1] if g.ndim == 3 else 0)
+
+    def append_memory_search_norm(self, n, candidates=None, streams=None, radius=4, min_inside=None, keep=224, ball_max_age=30):
+        """append_memory_search with every frame's choice made by the normalised score (DESIGN.md §11 "Scene batch: normalised
+        registration"), for dense maps: frame b is Scene.append_memory_search_norm on the memory of streams[b], the calls made in
+        batch order. candidates, streams and radius as append_memory_search; min_inside: how many frame pixels a candidate must keep
+        inside the frame to qualify, 1 .. W H, one value per call; None: W H // 4. read_motion(b) works as after append_memory_search
+        (its scores are the S table), read_motion_norm(b) returns the rest."""
+        g, c, n_rot = self._candidates(n, candidates)
+        if min_inside is None:
+            min_inside = (self.W * self.H) // 4
+        st = Engine._streams(streams, n)
+        self._chk(self.L.yh_scene_batch_append_memory_search_norm(self.h, n, _p(st) if st is not None else None, n_rot, _p(g), _p(c), radius, min_inside, keep,
+                                                                  ball_max_age))
+        self.n, self._fields, self._search, self._norm_levels = n, False, (n_rot, radius), False
+
+    def read_motion_norm(self, frame):
+        """What the last append_memory_search_norm saw for frame `frame` beside read_motion's: the dict Scene.read_motion_norm returns
+        (after append_memory_pyramid_norm: chosen_stc, prior_stc and qualified alone; read_pyramid_norm has the levels' tables)."""
+        n_rot, radius = getattr(self, "_search", None) or (1, 0)
+        shape = (n_rot, 2 * radius + 1, 2 * radius + 1)
+        out = dict(chosen_stc=np.zeros(3, np.uint64), prior_stc=np.zeros(3, np.uint64))
+        if not getattr(self, "_norm_levels", False):
+            out.update(totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64))
+        q = C.c_int32()
+        t, i = (_p(out[k]) if k in out else None for k in ("totals", "inside"))
+        self._chk(self.L.yh_scene_batch_motion_norm_read(self.h, frame, t, i, _p(out["chosen_stc"]), _p(out["prior_stc"]), C.byref(q)))
+        out["qualified"] = bool(q.value)
+        return out
+
+    def memory_search_norm_time(self, reps=20):
+        """(ms per batch, ms of the registration launches alone) of the last append_memory_search_norm, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_batch_memory_search_norm_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
+        return ms.value, ms_search.value
+
+    def append_memory_pyramid_norm(self, n, candidates=None, streams=None, levels=3, radius=8, refine=1, min_inside=None, keep=224, ball_max_age=30):
+        """append_memory_pyramid with every level, and the choice, decided by the normalised score (DESIGN.md §11 "Scene batch:
+        normalised pyramid registration"): frame b is Scene.append_memory_pyramid_norm on the memory of streams[b], the calls made
+        in batch order. candidates, streams, levels, radius and refine as append_memory_pyramid; min_inside as
+        append_memory_search_norm. read_motion(b) and read_pyramid(b, level) work as after append_memory_pyramid, read_motion_norm(b)
+        returns chosen_stc, prior_stc and qualified, read_pyramid_norm(b, level) the levels' three tables and flags."""
+        g, c, n_rot = self._candidates(n, candidates)
+        if min_inside is None:
+            min_inside = (self.W * self.H) // 4
+        st = Engine._streams(streams, n)
+        self._chk(self.L.yh_scene_batch_append_memory_pyramid_norm(self.h, n, _p(st) if st is not None else None, n_rot, _p(g), _p(c), levels, radius, refine,
+                                                                   min_inside, keep, ball_max_age))
+        self.n, self._fields, self._pyramid = n, False, (n_rot, levels, radius, refine)
+        self._search = (n_rot + 1, refine)   # (read_motion(scores=True) is refused after this append: it names read_pyramid)
+        self._norm_levels = True             # (read_motion_norm asks for no tables: they are read_pyramid_norm's)
+
+    def read_pyramid_norm(self, frame, level):
+        """Level `level` (0 .. levels) of what the last append_memory_pyramid_norm did for frame `frame`: the dict
+        Scene.read_pyramid_norm returns (centres, scores, totals, inside, sum_n, min_inside, qualified)."""
+        n_rot, levels, radius, refine = getattr(self, "_pyramid", None) or (1, 0, 0, 0)
+        ok = 0 <= level <= levels                # (otherwise the library refuses before it writes anything)
+        p, hyp = (radius if level == levels else refine), n_rot + (1 if level == 0 else 0)
+        shape = (hyp, 2 * p + 1, 2 * p + 1)
+        out = dict(centres=np.zeros((hyp, 2), np.int32), scores=np.zeros(shape, np.uint64), totals=np.zeros(shape, np.uint64), inside=np.zeros(shape, np.uint64),
+                   qualified=np.zeros(hyp, np.int32))
+        sum_n, need = C.c_uint64(), C.c_int32()
+        a = [_p(out[k]) if ok else None for k in ("centres", "scores", "totals", "inside")]
+        self._chk(self.L.yh_scene_batch_pyramid_norm_read(self.h, frame, level, a[0], a[1], a[2], a[3], C.byref(sum_n), C.byref(need),
+                                                          _p(out["qualified"]) if ok else None))
+        out.update(sum_n=sum_n.value, min_inside=need.value)
+        return out
+
+    def memory_pyramid_norm_time(self, reps=20):
+        """(ms per batch, ms of the registration launches alone) of the last append_memory_pyramid_norm, replayed; commits nothing."""
+        ms, ms_search = C.c_float(), C.c_float()
+        self._chk(self.L.yh_scene_batch_memory_pyramid_norm_time(self.h, reps, C.byref(ms), C.byref(ms_search)))
         return ms.value, ms_search.value
 
     def read_memory(self, stream=0):

@@ -33,10 +33,17 @@ DESIGN.md §11 "Scene batch: pyramid registration"; yh_scene_batch_memory_pyrami
 (yh_scene_memory_pyramid_time per frame). Then, for n = 8 and (5, 3, 8, 1) on the robots + balls frame in every slot, alternated with
 the single handle, one warm-up each, five runs of 30 replays: the two ratios and the single handle's spread (what
 tests/test_scene_batch_pyramid.py derives its ceiling from).
+--memory-search-norm [--n-rot K --radius R] [--min-inside m], --memory-pyramid-norm [--levels L --radius R --refine r --n-rot K]
+[--min-inside m]: the two normalised batched appends instead (yh_scene_batch_append_memory_search_norm, _pyramid_norm, DESIGN.md §11
+"Scene batch: normalised registration", "Scene batch: normalised pyramid registration"; yh_scene_batch_memory_search_norm_time,
+_pyramid_norm_time): the columns of --memory-search and --memory-pyramid, beside the same frames through one
+Scene.append_memory_search_norm or _pyramid_norm (yh_scene_memory_search_norm_time, _pyramid_norm_time per frame), min_inside W H // 4
+unless given; then the n = 8 run at (5, 4) or (5, 3, 8, 1) whose single-handle spread tests/test_scene_batch_register_norm.py and
+tests/test_scene_batch_pyramid_norm.py derive their ceilings from.
 --frames n,n,..: those batch sizes only.
 --lib times another build of the library (a build of the parent commit: `make -C tiny-object-detection_amd BUILD=build_old
 LIBDIR=lib_old` in a checkout of it), to alternate with this one process by process on one box.
-Usage: python tools/time_scene_batch.py [sets] [reps] [--memory | --memory-search [--n-rot K --radius R] | --memory-pyramid [--levels L --radius R --refine r --n-rot K] | --turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
+Usage: python tools/time_scene_batch.py [sets] [reps] [--memory | --memory-search [--n-rot K --radius R] | --memory-pyramid [--levels L --radius R --refine r --n-rot K] | --memory-search-norm .. | --memory-pyramid-norm .. [--min-inside m] | --turn-price P [--turn-tour [--targets K]] | --tour [--connectivity 8] [--targets K]] [--frames n,n,..] [--lib <other libyolact_hip.so>]"""
 import os, socket, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,6 +52,7 @@ from yolact_amd import capi
 args, tau, tour, plain, conn_tour, K, sizes, lib, memory = [], None, False, False, 4, 3, None, None, False
 search, n_rot_arg, radius_arg = False, None, None
 pyramid, levels_arg, refine_arg = False, None, None
+norm, min_inside = False, None
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--turn-price": tau = float(next(it))
@@ -53,6 +61,9 @@ for a in it:
     elif a == "--memory": memory = True
     elif a == "--memory-search": search = True
     elif a == "--memory-pyramid": pyramid = True
+    elif a == "--memory-search-norm": search = norm = True
+    elif a == "--memory-pyramid-norm": pyramid = norm = True
+    elif a == "--min-inside": min_inside = int(next(it))
     elif a == "--levels": levels_arg = int(next(it))
     elif a == "--refine": refine_arg = int(next(it))
     elif a == "--n-rot": n_rot_arg = int(next(it))
@@ -69,6 +80,7 @@ if plain and tau: sys.exit("--tour is the plain tour: no --turn-price")
 if memory and (plain or tau): sys.exit("--memory times the append alone: no --tour, no --turn-price")
 if search and (memory or plain or tau): sys.exit("--memory-search times the search append alone: no --memory, no --tour, no --turn-price")
 if pyramid and (search or memory or plain or tau): sys.exit("--memory-pyramid times the pyramid append alone: no --memory, no --memory-search, no --tour, no --turn-price")
+if min_inside is not None and not norm: sys.exit("--min-inside goes with --memory-search-norm or --memory-pyramid-norm")
 if pyramid:
     given = [v is not None for v in (n_rot_arg, levels_arg, radius_arg, refine_arg)]
     if any(given) and not all(given): sys.exit("--n-rot K, --levels L, --radius R and --refine r go together")
@@ -81,7 +93,7 @@ if lib:
 import yolact_amd as ya
 H, W = 480, 640
 TARGETS = [(70, 67), (515, 410), (320, 40), (600, 100), (30, 440), (250, 300)][:K]   # tools/time_tour.py's camera targets
-print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (", memory append" if memory else "") + (", search append" if search else "") + (", pyramid append" if pyramid else "") + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
+print(f"box {socket.gethostname()}, {ya.version()}, {os.path.relpath(capi.lib_path(), ROOT)}, {sets} sets x {reps} reps" + (", memory append" if memory else "") + (", search append" if search else "") + (", pyramid append" if pyramid else "") + (f", normalised, min_inside {min_inside if min_inside is not None else (W * H) // 4}" if norm else "") + (f", turn price {tau}" if tau else "") + (f", turn tour of {K} targets" if tour else "") + (f", tour of {K} targets, {conn_tour}-connected" if plain else ""))
 
 
 def frame(seed):
@@ -141,10 +153,10 @@ if memory:
     sys.exit(0)
 
 
-def search_columns(frames, prior, cands, radius, runs, replays, pyr=None):
+def search_columns(frames, prior, cands, radius, runs, replays, pyr=None, norm=False):
     """(single, a stream per frame, all on stream 0): lists over the runs of (ms per frame, ms of the registration alone per frame)
     for these frames, alternated run by run, one warm-up each; every memory filled before it is timed. pyr = (levels, refine): the
-    pyramid append instead of the search append"""
+    pyramid append instead of the search append; norm: the normalised form of either, at min_inside"""
     n = len(frames)
     motion = ya.scene_motion(*prior)
     sb = ya.SceneBatch(W, H, n)
@@ -156,7 +168,13 @@ def search_columns(frames, prior, cands, radius, runs, replays, pyr=None):
         sc.append_memory(frames[-1][0], frame_u32=frames[-1][1], motion=motion)
         t, r = 0.0, 0.0
         for d, f in (frames[:1] if same else frames):      # (the same frame in every slot: one replay stands for all)
-            if pyr:
+            if pyr and norm:
+                sc.append_memory_pyramid_norm(d, frame_u32=f, candidates=cands, levels=pyr[0], radius=radius, refine=pyr[1], min_inside=min_inside)
+                a, b = sc.memory_pyramid_norm_time(replays)
+            elif norm:
+                sc.append_memory_search_norm(d, frame_u32=f, candidates=cands, radius=radius, min_inside=min_inside)
+                a, b = sc.memory_search_norm_time(replays)
+            elif pyr:
                 sc.append_memory_pyramid(d, frame_u32=f, candidates=cands, levels=pyr[0], radius=radius, refine=pyr[1])
                 a, b = sc.memory_pyramid_time(replays)
             else:
@@ -168,7 +186,13 @@ def search_columns(frames, prior, cands, radius, runs, replays, pyr=None):
     def batch(streams):
         sb.memory_reset()
         sb.append_memory(n, motions=[motion] * n, streams=streams)
-        if pyr:
+        if pyr and norm:
+            sb.append_memory_pyramid_norm(n, candidates=[cands] * n, streams=streams, levels=pyr[0], radius=radius, refine=pyr[1], min_inside=min_inside)
+            a, b = sb.memory_pyramid_norm_time(replays)
+        elif norm:
+            sb.append_memory_search_norm(n, candidates=[cands] * n, streams=streams, radius=radius, min_inside=min_inside)
+            a, b = sb.memory_search_norm_time(replays)
+        elif pyr:
             sb.append_memory_pyramid(n, candidates=[cands] * n, streams=streams, levels=pyr[0], radius=radius, refine=pyr[1])
             a, b = sb.memory_pyramid_time(replays)
         else:
@@ -188,16 +212,16 @@ def search_columns(frames, prior, cands, radius, runs, replays, pyr=None):
 if search:
     prior = (3.0, -2.0, 0.05)                             # tools/time_scene.py's: the prior is right, the search confirms it
     grids = ((n_rot_arg, radius_arg),) if n_rot_arg is not None else ((1, 0), (1, 4), (5, 4), (9, 8))
-    print("search append, ms per frame (median of the sets), the registration launches alone in brackets:")
+    print(("normalised " if norm else "") + "search append, ms per frame (median of the sets), the registration launches alone in brackets:")
     print(f"{'n':>4} {'n_rot':>5} {'R':>2} {'single handle':>18} {'a stream per frame':>20} {'all on one stream':>20}")
     for n in sizes:
         for n_rot, radius in grids:
             cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
-            cols = search_columns([frame(b) for b in range(n)], prior, cands, radius, sets, reps)
+            cols = search_columns([frame(b) for b in range(n)], prior, cands, radius, sets, reps, norm=norm)
             cell = lambda c: f"{med([v[0] for v in c]):.4f} ({med([v[1] for v in c]):.4f})"
             print(f"{n:4d} {n_rot:5d} {radius:2d} {cell(cols[0]):>18} {cell(cols[1]):>20} {cell(cols[2]):>20}" + ("   (n > 64 streams: both columns on one stream)" if n > capi.SCENE_STREAMS_MAX else ""))
     cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=2)
-    s, a, o = search_columns([frame(0)] * 8, prior, cands, 4, 5, 30)
+    s, a, o = search_columns([frame(0)] * 8, prior, cands, 4, 5, 30, norm=norm)
     ms = lambda c: [v[0] for v in c]
     spread = lambda v: (max(v) - min(v)) / med(v)
     print("n = 8, (n_rot, R) = (5, 4), the robots + balls frame of tools/time_scene.py in every slot, 5 runs of 30 replays alternated:")
@@ -210,14 +234,14 @@ if pyramid:
     prior = (3.0, -2.0, 0.05)                             # tools/time_scene.py's: the prior is right, the search confirms it
     n_rot, levels, radius, refine = (n_rot_arg, levels_arg, radius_arg, refine_arg) if n_rot_arg is not None else (5, 3, 8, 1)
     cell = lambda c: f"{med([v[0] for v in c]):.4f} ({med([v[1] for v in c]):.4f})"
-    print("pyramid append, ms per frame (median of the sets), the registration launches alone in brackets:")
+    print(("normalised " if norm else "") + "pyramid append, ms per frame (median of the sets), the registration launches alone in brackets:")
     print(f"{'n':>4} {'n_rot':>5} {'L':>2} {'R':>2} {'r':>2} {'single handle':>18} {'a stream per frame':>20} {'all on one stream':>20}")
     cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=(n_rot - 1) // 2)
     for n in sizes:
-        cols = search_columns([frame(b) for b in range(n)], prior, cands, radius, sets, reps, (levels, refine))
+        cols = search_columns([frame(b) for b in range(n)], prior, cands, radius, sets, reps, (levels, refine), norm)
         print(f"{n:4d} {n_rot:5d} {levels:2d} {radius:2d} {refine:2d} {cell(cols[0]):>18} {cell(cols[1]):>20} {cell(cols[2]):>20}")
     cands = ya.scene_motion_candidates(prior=prior, dtheta_step=0.01, n_side=2)
-    s, a, o = search_columns([frame(0)] * 8, prior, cands, 8, 5, 30, (3, 1))
+    s, a, o = search_columns([frame(0)] * 8, prior, cands, 8, 5, 30, (3, 1), norm)
     ms = lambda c: [v[0] for v in c]
     spread = lambda v: (max(v) - min(v)) / med(v)
     print("n = 8, (n_rot, L, R, r) = (5, 3, 8, 1), the robots + balls frame of tools/time_scene.py in every slot, 5 runs of 30 replays alternated:")
