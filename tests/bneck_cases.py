@@ -9,7 +9,13 @@ One launch computes, for M = n P Q output pixels,
     a' = f16(relu(w1n y + bias1n))                             4 planes -> planes
 Integer cases: a in [-3, 3] (bneck_xn_f16's b in [0, 3]), weights in {-1, 0, 1}, biases in [-4, 4], res / x2 in [-5, 5]. Every
 product and every partial sum is then an integer below 2^24 (bounds() computes the worst case), so every summation order gives the
-same float32 and the kernels must equal reference() bit for bit. Wider weights overflow a' to inf at 128 planes: keep the ranges."""
+same float32 and the kernels must equal reference() bit for bit. Wider weights overflow a' to inf at 128 planes: keep the ranges.
+
+Dyadic cases (DYADIC, one per form): the integer cases cannot see how a chain rounds - their sums are integers f16 mostly holds -
+so these make every operand an integer times a power of two (DYADIC_GRIDS). Stage i's products and partial sums are then
+multiples of 2^-g_i (c["g"]), float32 holds each exactly while sum |x| |w| + |bias| + |res| stays below 2^(22 - g_i), and the
+sums carry far more than f16's 11 bits: b, y and a' are each really rounded, once, and a chain that rounds twice, rounds toward
+zero or carries b or y to the next stage unrounded differs from reference() in many elements."""
 import functools
 import zlib
 
@@ -57,6 +63,15 @@ SHAPES = [
 ]
 SHAPE_IDS = [s[0] for s in SHAPES]
 REAL = "real_n3_7x11"                  # the one real-valued case: normal data, weights scaled by 1 / sqrt(K)
+DYADIC = "dy_n3_7x11"                  # the one dyadic case: compared with reference(), like the integer cases
+# planes -> (a = k / qa with |k| <= ka (bneck_xn_f16's b: 0 <= k <= ka), w2 = k / q2 with |k| <= q2 / 2, w3 = k / q3 with |k| <= q3,
+# w1n = k / q1 with |k| <= q1, the share of w3 and w1n kept nonzero, res = k / qr with |k| <= kr). bias2, bias3 and bias1n lie on
+# their stage's product grid 2^-g with |bias| <= 1; x2 = k / (qa q2) with |x2| <= 2. Wider ranges pass 2^22 at the third stage.
+DYADIC_GRIDS = {
+    64:  dict(qa=32, ka=16, q2=32, q3=2, q1=1, dens=1.0, qr=1024, kr=2048),
+    128: dict(qa=32, ka=16, q2=32, q3=2, q1=1, dens=0.5, qr=1024, kr=2048),
+    256: dict(qa=64, ka=128, q2=1, q3=8, q1=2, dens=0.5, qr=512, kr=2048),
+}
 
 
 def case_ids(form):
@@ -65,10 +80,10 @@ def case_ids(form):
     the op refuses the gap case (the GPU test asserts the refusal)."""
     sym, planes, tm, nxt, dual = FORMS[FORM_IDS.index(form)]
     if dual:
-        return [f"{s}_x2s{k}" for s in SHAPE_IDS for k in (1, 2)] + [REAL + "_x2s1"]
+        return [f"{s}_x2s{k}" for s in SHAPE_IDS for k in (1, 2)] + [REAL + "_x2s1", DYADIC + "_x2s1"]
     if planes == 256:
-        return [s for s in SHAPE_IDS if not s.startswith("s2_")] + [REAL]
-    return SHAPE_IDS + [REAL]
+        return [s for s in SHAPE_IDS if not s.startswith("s2_")] + [REAL, DYADIC]
+    return SHAPE_IDS + [REAL, DYADIC]
 
 
 def h16(a):
@@ -89,8 +104,8 @@ def build(planes, case_id):
     if "_x2s" in case_id:
         shape_id, k = case_id.rsplit("_x2s", 1)
         x2s = int(k)
-    real = shape_id == REAL
-    sid, n, H, W, stride, gap = SHAPES[SHAPE_IDS.index("n3_7x11" if real else shape_id)]
+    real, dyadic = shape_id == REAL, shape_id == DYADIC
+    sid, n, H, W, stride, gap = SHAPES[SHAPE_IDS.index("n3_7x11" if real or dyadic else shape_id)]
     xn = planes == 256
     assert not (xn and (stride != 1 or x2s)) and not (x2s and planes != 64)
     P, Q = out_dim(H, stride), out_dim(W, stride)
@@ -104,6 +119,17 @@ def build(planes, case_id):
                  w3=nrm((C4, K3), K3), bias3=rng.normal(0, 0.1, C4).astype(np.float32),
                  w1n=nrm((planes, C4), C4), bias1n=rng.normal(0, 0.1, planes).astype(np.float32))
         side = lambda shape: nrm(shape)
+    elif dyadic:
+        d = DYADIC_GRIDS[planes]
+        dy = lambda q, lim, shape, lo=None: (rng.integers(-lim if lo is None else lo, lim + 1, shape) / q).astype(np.float32)
+        thin = lambda w: w * (rng.random(w.shape) < d["dens"]).astype(np.float32)
+        q_b = d["qa"] * d["q2"]                    # the grids of the three stages' sums: 1 / q_b, 1 / q_y, 1 / q_a
+        q_y, q_a = q_b * d["q3"], q_b * d["q3"] * d["q1"]
+        g = tuple(int(np.log2(q)) for q in (q_b, q_y, q_a))
+        c = dict(a=dy(d["qa"], d["ka"], (n, H, W, planes), lo=0 if xn else None), w2=dy(d["q2"], d["q2"] // 2, (planes, 3, 3, planes)),
+                 bias2=dy(q_b, q_b, planes), w3=thin(dy(d["q3"], d["q3"], (C4, K3))), bias3=dy(q_y, q_y, C4),
+                 w1n=thin(dy(d["q1"], d["q1"], (planes, C4))), bias1n=dy(q_a, q_a, planes))
+        side = lambda shape: dy(q_b, 2 * q_b, shape) if x2s else dy(d["qr"], d["kr"], shape)
     else:
         ints = lambda lo, hi, shape: rng.integers(lo, hi + 1, shape).astype(np.float32)
         c = dict(a=ints(0 if xn else -3, 3, (n, H, W, planes)), w2=ints(-1, 1, (planes, 3, 3, planes)), bias2=ints(-4, 4, planes),
@@ -120,7 +146,8 @@ def build(planes, case_id):
     for v in c.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
-    return dict(c, id=case_id, planes=planes, n=n, H=H, W=W, P=P, Q=Q, M=n * P * Q, stride=stride, stride2=x2s or 1, gap=gap, real=real, xn=xn)
+    return dict(c, id=case_id, planes=planes, n=n, H=H, W=W, P=P, Q=Q, M=n * P * Q, stride=stride, stride2=x2s or 1, gap=gap, real=real, xn=xn,
+                dyadic=dyadic, g=g if dyadic else None)
 
 
 def _conv3x3(a, w, stride, P, Q):
@@ -163,7 +190,7 @@ _REF = {}
 
 
 def reference(c, oracle=None):
-    """dict(b, y, a_next[, a_next8]) of an integer case, computed once per case. a_next8 (256 planes; needs the oracle module):
+    """dict(b, y, a_next[, a_next8]) of an integer or dyadic case, computed once per case. a_next8 (256 planes; needs the oracle module):
     the E4M3 codes of the float32 product a' * inv_scale[channel]."""
     assert not c["real"]
     key = (c["planes"], c["id"])

@@ -2,6 +2,8 @@
 yh_op_bneck_f16 on the edge shapes of tests/bneck_cases.py, bit for bit against that module's numpy reference (three convolutions in
 float64 with the f16 roundings in between; tests/test_bneck_cases.py ties it to the oracle and proves that integer data makes
 every summation order exact). No tolerance anywhere: y, a_next and bneck_xn_f16's E4M3 codes are compared with np.array_equal.
+The dyadic case of every form (operands on power-of-two grids, sums exact in float32 and far wider than f16) is compared the same
+way: there b, y and a' are really rounded, so a chain that rounds in the wrong place or the wrong way fails it.
 The op stages 256 guard rows of 0xFF behind every output and fails if the launch touched one, and fills the outputs with the NaN
 pattern first, so a row the kernel skipped shows as well.
 
