@@ -104,6 +104,23 @@ int yh_tfl_create_tuned(const void* model_bytes, size_t nbytes, int32_t device, 
 /* Kernel launches per invoke of the prepared plan; how many are CONV_2D and how many of those run on the int8 matrix pipes. */
 int yh_tfl_plan_info(const yh_tfl* h, int32_t* launches, int32_t* conv_launches, int32_t* conv_mfma_launches);
 
+/* Test hooks: which kernel every operator of a plan runs on (tests/test_gpu_tflite_forms.py asserts it case by case).
+ * yh_tfl_direct_forms: the rows of the register-fed int8 convolution's table of forms - returns their number and writes (D, once, KK)
+ * of the first `cap` rows to rows[3 * i ..] (rows may be NULL). No handle, no device: a CPU test calls it.
+ * yh_tfl_op_info: operator `op` of the model (file order) in the handle's plan, for the image count of the next invoke: its kernel
+ * family (below; the answer of the same functions the launches ask), the row of the table of forms it runs (-1: not register-fed),
+ * whether it is launched as a member of a group, and whether it is folded into another launch (then it has no launch of its own;
+ * a RESHAPE that shares its input's buffer reports YH_TFL_FAM_NONE, folded). Any of the four pointers may be NULL. */
+enum {
+    YH_TFL_FAM_NONE = -1,
+    YH_TFL_FAM_CONV_SCALAR = 0, YH_TFL_FAM_CONV_PX8 = 1, YH_TFL_FAM_CONV_DOT1 = 2, YH_TFL_FAM_CONV_DOT4 = 3,
+    YH_TFL_FAM_CONV_I8_LDS = 4, YH_TFL_FAM_CONV_I8_DIRECT = 5, YH_TFL_FAM_DW_SCALAR = 6, YH_TFL_FAM_DW_C4 = 7,
+    YH_TFL_FAM_ADD = 8, YH_TFL_FAM_REQUANT = 9, YH_TFL_FAM_QUANTIZE_F32 = 10, YH_TFL_FAM_DEQUANTIZE = 11, YH_TFL_FAM_LUT = 12,
+    YH_TFL_FAM_PAD = 13, YH_TFL_FAM_RESIZE = 14, YH_TFL_FAM_CONCAT = 15, YH_TFL_FAM_COPY = 16
+};
+int yh_tfl_direct_forms(int32_t* rows, int32_t cap);
+int yh_tfl_op_info(const yh_tfl* h, int32_t op, int32_t* family, int32_t* form_row, int32_t* grouped, int32_t* folded);
+
 int yh_tfl_tensor_count(const yh_tfl* h);
 
 int yh_tfl_tensor_read(yh_tfl* h, int32_t tensor, void* dst, size_t nbytes);   /* test hook: any tensor by index */

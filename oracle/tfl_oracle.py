@@ -246,6 +246,11 @@ def concat_u8(xs, params, zo, so, axis):
     return np.concatenate(outs, axis=axis)
 
 
+def _bias(val, ins, co):
+    """A convolution's bias operand: absent (two inputs, or index -1) means zeros."""
+    return val[ins[2]] if len(ins) > 2 and ins[2] >= 0 else np.zeros(co, np.int32)
+
+
 def run_model(model, inputs):
     """Evaluates tests/tfl_builder.Model on a dict {tensor index: array}; returns all tensor values."""
     val = {}
@@ -258,13 +263,14 @@ def run_model(model, inputs):
         ins, outs, o = op.inputs, op.outputs, op.opts
         t_out = T[outs[0]]
         if op.code == "CONV_2D":
-            x, w, b = T[ins[0]], T[ins[1]], T[ins[2]]
-            val[outs[0]] = conv2d_u8(val[ins[0]], x.zp, x.scale, val[ins[1]], w.zp, w.scale, val[ins[2]], t_out.zp, t_out.scale,
-                                     (o["stride_h"], o["stride_w"]), o["padding"], o.get("act", 0))
+            x, w = T[ins[0]], T[ins[1]]
+            val[outs[0]] = conv2d_u8(val[ins[0]], x.zp, x.scale, val[ins[1]], w.zp, w.scale, _bias(val, ins, w.shape[0]), t_out.zp, t_out.scale,
+                                     (o["stride_h"], o["stride_w"]), o["padding"], o.get("act", 0), (o.get("dil_h", 1), o.get("dil_w", 1)))
         elif op.code == "DEPTHWISE_CONV_2D":
             x, w = T[ins[0]], T[ins[1]]
-            val[outs[0]] = dwconv2d_u8(val[ins[0]], x.zp, x.scale, val[ins[1]], w.zp, w.scale, val[ins[2]], t_out.zp, t_out.scale,
-                                       (o["stride_h"], o["stride_w"]), o["padding"], o.get("act", 0), o.get("depth_multiplier", 1))
+            val[outs[0]] = dwconv2d_u8(val[ins[0]], x.zp, x.scale, val[ins[1]], w.zp, w.scale, _bias(val, ins, w.shape[3]), t_out.zp, t_out.scale,
+                                       (o["stride_h"], o["stride_w"]), o["padding"], o.get("act", 0), o.get("depth_multiplier", 1),
+                                       (o.get("dil_h", 1), o.get("dil_w", 1)))
         elif op.code == "ADD":
             a, b = T[ins[0]], T[ins[1]]
             val[outs[0]] = add_u8(val[ins[0]], a.zp, a.scale, val[ins[1]], b.zp, b.scale, t_out.zp, t_out.scale, o.get("act", 0))
@@ -276,9 +282,9 @@ def run_model(model, inputs):
         elif op.code == "TANH":
             x = T[ins[0]]
             val[outs[0]] = tanh_lut_u8(x.zp, x.scale, t_out.zp, t_out.scale)[val[ins[0]]]
-        elif op.code == "RELU":
+        elif op.code in ("RELU", "RELU6"):
             x = T[ins[0]]
-            val[outs[0]] = relu_u8(val[ins[0]], x.zp, x.scale, t_out.zp, t_out.scale)
+            val[outs[0]] = relu_u8(val[ins[0]], x.zp, x.scale, t_out.zp, t_out.scale, 1 if op.code == "RELU" else 3)
         elif op.code == "CONCATENATION":
             axis = o["axis"] if o["axis"] >= 0 else o["axis"] + len(t_out.shape)
             val[outs[0]] = concat_u8([val[i] for i in ins], [(T[i].zp, T[i].scale) for i in ins], t_out.zp, t_out.scale, axis)

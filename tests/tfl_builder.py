@@ -9,10 +9,10 @@ import struct
 
 import numpy as np
 
-BUILTIN = {"ADD": 0, "CONCATENATION": 2, "CONV_2D": 3, "DEPTHWISE_CONV_2D": 4, "DEQUANTIZE": 6, "RELU": 19,
+BUILTIN = {"ADD": 0, "CONCATENATION": 2, "CONV_2D": 3, "DEPTHWISE_CONV_2D": 4, "DEQUANTIZE": 6, "RELU": 19, "RELU6": 21,
            "RESHAPE": 22, "RESIZE_BILINEAR": 23, "TANH": 28, "PAD": 34, "QUANTIZE": 114}
 OPTIONS_TYPE = {"CONV_2D": 1, "DEPTHWISE_CONV_2D": 2, "CONCATENATION": 10, "ADD": 11, "RESIZE_BILINEAR": 15,
-                "RESHAPE": 17, "PAD": 22, "DEQUANTIZE": 61, "QUANTIZE": 87, "TANH": 0, "RELU": 0}
+                "RESHAPE": 17, "PAD": 22, "DEQUANTIZE": 61, "QUANTIZE": 87, "TANH": 0, "RELU": 0, "RELU6": 0}
 TENSOR_TYPE = {"f32": 0, "i32": 2, "u8": 3}
 NP_TYPE = {"f32": np.float32, "i32": np.int32, "u8": np.uint8}
 

@@ -52,12 +52,17 @@ constexpr int kMaxGroup = 16;   // convolutions of one tfl_conv_i8_direct_group 
 // dimension, or nb x the elements of an image-major activation); a ConvI8 holds its image count in M. Launch errors are left to
 // the caller's hipGetLastError().
 // CONV_2D: the dot-product kernel where p.wsum is set, else (dot) the 8-channels-per-lane kernel while its weights fit LDS, else one lane per element
+enum ConvU8Kernel { CONV_U8_SCALAR, CONV_U8_PX8, CONV_U8_DOT1, CONV_U8_DOT4 };
+ConvU8Kernel conv_u8_kernel(const ConvQ& p, bool dot);   // the kernel launch_conv_u8 runs (also what yh_tfl_op_info reports)
 void launch_conv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s);
 // DEPTHWISE_CONV_2D: (dot) four channels per lane where the layer allows it, else one lane per element
+bool dwconv_u8_takes_c4(const ConvQ& p, bool dot);       // the choice launch_dwconv_u8 makes (also what yh_tfl_op_info reports)
 void launch_dwconv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s);
 void launch_conv_i8_mfma(const ConvI8& q, hipStream_t s);
 // The register-fed int8 kernel is built in a table of forms (ring depth, whole K in one pass, compile-time extent).
 int conv_i8_direct_form(int kh, int kw, int Ci);   // the table row a convolution runs, < 0: the table has none for it
+int conv_i8_direct_form_count();                   // the table's rows, and row i's (D, ONCE, KK) (yh_tfl_direct_forms)
+void conv_i8_direct_form_row(int i, int* D, int* once, int* KK);
 bool conv_i8_direct_pays(const ConvI8& q);         // this launch is faster register-fed than on the LDS tiles
 void launch_conv_i8_direct(int form, const ConvI8& q, hipStream_t s);
 // ... several convolutions of one form as one launch: parameter blocks and tile prefix table in device memory, `tiles` workgroups

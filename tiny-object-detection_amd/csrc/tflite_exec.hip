@@ -76,6 +76,7 @@ struct yh_tfl {
     TflModel m;
     std::vector<void*> tens;
     std::vector<char> alias;    // tens[i] shares another tensor's buffer (RESHAPE): not freed twice
+    std::vector<char> per_image;   // constant i is read as an operator's DATA operand (ADD, CONCATENATION, RESHAPE ...): stored once per image
     std::vector<void*> extra;   // LUTs etc.
     std::vector<Prepared> plan;
     static constexpr int kMaxBatch = 2;          // images per invoke the buffers are sized for (the two tiles of yolact.rs:216-217)
@@ -119,8 +120,13 @@ int upload(yh_tfl* h, const T* src, size_t count, const char* what, const T** ou
     return YH_OK;
 }
 // The bytes of a tensor's device allocation: a constant's own, an activation's for kMaxBatch images (image-major: room for the
-// batch plan), and 16 more (the kernels' dword and 16-byte loads may reach past the last element).
-size_t tensor_alloc_bytes(const TflTensor& t) { return t.count() * t.elem() * (t.data ? 1 : yh_tfl::kMaxBatch) + 16; }
+// batch plan), and 16 more (the kernels' dword and 16-byte loads may reach past the last element). A constant that an operator reads
+// where an activation could stand (an ADD operand, a CONCATENATION part, a RESHAPE's input ...) is stored like one, a copy per image:
+// the kernels index every data operand image-major, and the second image of a batch plan must meet the same constant, not the bytes behind it.
+size_t tensor_alloc_bytes(const yh_tfl* h, size_t i) {
+    const TflTensor& t = h->m.tensors[i];
+    return t.count() * t.elem() * (t.data && !h->per_image[i] ? 1 : yh_tfl::kMaxBatch) + 16;
+}
 
 // One operator on its way into the plan: its tensors and their device buffers by tensor index, its YH_EINVAL, and one function per
 // operator family that fills the plan entry or returns the error.
@@ -314,12 +320,22 @@ int prepare(yh_tfl* h) {
     TflModel& m = h->m;
     h->tens.assign(m.tensors.size(), nullptr);
     h->alias.assign(m.tensors.size(), 0);
+    h->per_image.assign(m.tensors.size(), 0);
+    for (const TflOp& op : m.ops) {   // the data operands: every input of ADD and CONCATENATION, the first of every other operator
+        const size_t nd = op.code == TFL_ADD || op.code == TFL_CONCATENATION ? op.in.size() : (op.in.empty() ? 0 : 1);
+        for (size_t k = 0; k < nd; ++k)
+            if (op.in[k] >= 0 && op.in[k] < (int)m.tensors.size() && m.tensors[op.in[k]].data) h->per_image[op.in[k]] = 1;
+    }
     for (size_t i = 0; i < m.tensors.size(); ++i) {
         const TflTensor& t = m.tensors[i];
-        if (t.count() * t.elem() == 0) continue;
-        const size_t alloc = tensor_alloc_bytes(t);
+        const size_t bytes = t.count() * t.elem();
+        if (bytes == 0) continue;
+        const size_t alloc = tensor_alloc_bytes(h, i);
         TCHK(h, hipMalloc(&h->tens[i], alloc));
-        if (t.data) TCHK(h, hipMemcpy(h->tens[i], t.data, t.count() * t.elem(), hipMemcpyHostToDevice));
+        if (t.data) {
+            for (int k = 0; k < (h->per_image[i] ? yh_tfl::kMaxBatch : 1); ++k)
+                TCHK(h, hipMemcpy((char*)h->tens[i] + (size_t)k * bytes, t.data, bytes, hipMemcpyHostToDevice));
+        }
         else TCHK(h, hipMemset(h->tens[i], 0, alloc));
     }
     for (size_t oi = 0; oi < m.ops.size(); ++oi) {
@@ -479,7 +495,7 @@ std::vector<int> plan_depths(const yh_tfl* h) {
     struct Range { const char* lo; const char* hi; };
     std::vector<Range> al;
     for (size_t i = 0; i < h->tens.size(); ++i)
-        if (h->tens[i] && !h->alias[i]) al.push_back(Range{ (const char*)h->tens[i], (const char*)h->tens[i] + tensor_alloc_bytes(h->m.tensors[i]) });
+        if (h->tens[i] && !h->alias[i]) al.push_back(Range{ (const char*)h->tens[i], (const char*)h->tens[i] + tensor_alloc_bytes(h, i) });
     auto alloc_of = [&](const void* q) -> int {
         for (size_t i = 0; i < al.size(); ++i) if ((const char*)q >= al[i].lo && (const char*)q < al[i].hi) return (int)i;
         return -1;
@@ -553,6 +569,10 @@ int group_plan(yh_tfl* h) {
     return YH_OK;
 }
 
+// Whether a P_CONV_I8 entry runs the register-fed kernel (its own launch or its group's) for `nb` images, else the LDS tiles.
+bool conv_i8_runs_direct(const yh_tfl* h, const Prepared& p, int nb) {
+    return p.group >= 0 || (h->use_dot >= 3 && conv_i8_direct_pays(conv_i8_args(p, nb)));
+}
 // Whether a plan entry issues a launch of its own: it is not folded into another (fuse_plan), and a group is launched by its first member.
 bool launches(const yh_tfl* h, size_t pi) { const Prepared& p = h->plan[pi]; return !p.dead && (p.group < 0 || h->groups[p.group].members[0] == (int)pi); }
 
@@ -572,7 +592,7 @@ int enqueue_plan(yh_tfl* h) {
                 const yh_tfl::ConvGroup* g = p.group >= 0 ? &h->groups[p.group] : nullptr;
                 const ConvI8 q = conv_i8_args(p, (int)nb);
                 if (g) launch_conv_i8_direct_group(p.form, g->probs[nb - 1], g->tile_start[nb - 1], (int)g->members.size(), g->tiles[nb - 1], s);
-                else if (h->use_dot >= 3 && conv_i8_direct_pays(q)) launch_conv_i8_direct(p.form, q, s);
+                else if (conv_i8_runs_direct(h, p, (int)nb)) launch_conv_i8_direct(p.form, q, s);
                 else launch_conv_i8_mfma(q, s);
                 break;
             }
@@ -714,6 +734,54 @@ int yh_tfl_plan_info(const yh_tfl* h, int32_t* launches_out, int32_t* conv_launc
     if (launches_out) *launches_out = n;
     if (conv_launches) *conv_launches = nc;
     if (conv_mfma_launches) *conv_mfma_launches = nm;
+    return YH_OK;
+}
+
+// The rows of the register-fed kernel's table of forms (no device is touched).
+int yh_tfl_direct_forms(int32_t* rows, int32_t cap) {
+    const int n = conv_i8_direct_form_count();
+    for (int i = 0; rows && i < n && i < cap; ++i) {
+        int D, once, KK;
+        conv_i8_direct_form_row(i, &D, &once, &KK);
+        rows[3 * i] = D; rows[3 * i + 1] = once; rows[3 * i + 2] = KK;
+    }
+    return n;
+}
+// What operator `op` of the model runs on in the handle's plan, for the image count of the next invoke: the answers of the very
+// functions the launches ask (conv_u8_kernel, dwconv_u8_takes_c4, conv_i8_runs_direct, launches).
+int yh_tfl_op_info(const yh_tfl* h, int32_t op, int32_t* family, int32_t* form_row, int32_t* grouped, int32_t* folded) {
+    if (!h || op < 0 || op >= (int)h->m.ops.size()) return YH_EINVAL;
+    int fam = YH_TFL_FAM_NONE, row = -1, grp = 0, fold = 1;   // (a RESHAPE that shares its input's buffer has no plan entry)
+    for (const Prepared& p : h->plan) {
+        if (p.oi != op) continue;
+        fold = p.dead ? 1 : 0;
+        switch (p.kind) {
+            case P_CONV: {
+                static const int fams[] = { YH_TFL_FAM_CONV_SCALAR, YH_TFL_FAM_CONV_PX8, YH_TFL_FAM_CONV_DOT1, YH_TFL_FAM_CONV_DOT4 };
+                fam = fams[conv_u8_kernel(p.conv, h->use_dot != 0)];
+                break;
+            }
+            case P_CONV_I8:
+                if (conv_i8_runs_direct(h, p, h->nb)) { fam = YH_TFL_FAM_CONV_I8_DIRECT; row = p.form; grp = p.group >= 0 ? 1 : 0; }
+                else fam = YH_TFL_FAM_CONV_I8_LDS;
+                break;
+            case P_DW: fam = dwconv_u8_takes_c4(p.conv, h->use_dot != 0) ? YH_TFL_FAM_DW_C4 : YH_TFL_FAM_DW_SCALAR; break;
+            case P_ADD: fam = YH_TFL_FAM_ADD; break;
+            case P_REQUANT: fam = YH_TFL_FAM_REQUANT; break;
+            case P_QUANT_F32: fam = YH_TFL_FAM_QUANTIZE_F32; break;
+            case P_DEQUANT: fam = YH_TFL_FAM_DEQUANTIZE; break;
+            case P_LUT: fam = YH_TFL_FAM_LUT; break;
+            case P_PAD: fam = YH_TFL_FAM_PAD; break;
+            case P_RESIZE: fam = YH_TFL_FAM_RESIZE; break;
+            case P_CONCAT: fam = YH_TFL_FAM_CONCAT; break;
+            case P_COPY: fam = YH_TFL_FAM_COPY; break;
+        }
+        break;
+    }
+    if (family) *family = fam;
+    if (form_row) *form_row = row;
+    if (grouped) *grouped = grp;
+    if (folded) *folded = fold;
     return YH_OK;
 }
 

@@ -638,20 +638,28 @@ inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 namespace yh {
 
+ConvU8Kernel conv_u8_kernel(const ConvQ& p, bool dot) {
+    if (p.wsum) return p.Ci % 16 == 0 ? CONV_U8_DOT4 : CONV_U8_DOT1;
+    return dot && p.kh * p.kw * p.Ci <= kPx8MaxK ? CONV_U8_PX8 : CONV_U8_SCALAR;
+}
 void launch_conv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s) {
-    if (p.wsum) {
+    const ConvU8Kernel k = conv_u8_kernel(p, dot);
+    if (k == CONV_U8_DOT4 || k == CONV_U8_DOT1) {
         const dim3 grid((unsigned)(((long long)p.Ho * p.Wo + 63) / 64), (unsigned)((p.Co + 7) / 8), nb);
-        if (p.Ci % 16 == 0) hipLaunchKernelGGL(tfl_conv_u8_dot<4>, grid, dim3(256), 0, s, p);
+        if (k == CONV_U8_DOT4) hipLaunchKernelGGL(tfl_conv_u8_dot<4>, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(tfl_conv_u8_dot<1>, grid, dim3(64), 0, s, p);
     }
-    else if (dot && p.kh * p.kw * p.Ci <= kPx8MaxK) {
+    else if (k == CONV_U8_PX8) {
         const dim3 grid((unsigned)(((long long)p.Ho * p.Wo + 255) / 256), (unsigned)((p.Co + 7) / 8), nb);
         hipLaunchKernelGGL((tfl_conv_u8_px8<0, 0, 0>), grid, dim3(256), 0, s, p);   // (the <3, 3, 3> form - all 27 input bytes asked for up front - measured 13.0 us against 10.6)
     }
     else hipLaunchKernelGGL(tfl_conv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
 }
+bool dwconv_u8_takes_c4(const ConvQ& p, bool dot) {
+    return dot && p.dm == 1 && p.kh == 3 && p.kw == 3 && p.Co % 4 == 0 && (((size_t)p.x | (size_t)p.w) & 3) == 0;
+}
 void launch_dwconv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s) {
-    if (dot && p.dm == 1 && p.kh == 3 && p.kw == 3 && p.Co % 4 == 0 && (((size_t)p.x | (size_t)p.w) & 3) == 0)
+    if (dwconv_u8_takes_c4(p, dot))
         hipLaunchKernelGGL((tfl_dwconv_u8_c4<3, 3>), dim3(nblk((long long)p.Ho * p.Wo * (p.Co >> 2)), nb), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(tfl_dwconv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
 }
@@ -682,6 +690,8 @@ int conv_i8_direct_form(int kh, int kw, int Ci) {
     const int fits = exact ? deepest : least;
     return fits >= 0 ? fits : shallowest;
 }
+int conv_i8_direct_form_count() { return kDirectFormCount; }
+void conv_i8_direct_form_row(int i, int* D, int* once, int* KK) { *D = kDirectForms[i].D; *once = kDirectForms[i].once ? 1 : 0; *KK = kDirectForms[i].KK; }
 // Which int8 MFMA launches take the register-fed kernel: every one whose input channels the LDS tiles cannot take (Ci % 64 != 0), and
 // the small ones - up to 2048 waves (8 per CU), or up to 8 k-steps. A large layer with a long K (the protonet's 3x3 x 128 channels
 // at 56 x 56 x 2 images: 3136 waves of 18 steps) re-reads its operands once per 16 x 16 tile and measured 26.0 us against 14.2 on

@@ -140,6 +140,8 @@ SYMBOLS = [
     ("yh_tfl_output_read", _i, [_vp, _i, _vp, _sz]),
     ("yh_tfl_tensor_count", _i, [_vp]),
     ("yh_tfl_plan_info", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_tfl_direct_forms", _i, [C.POINTER(_i), _i]),
+    ("yh_tfl_op_info", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_tfl_tensor_read", _i, [_vp, _i, _vp, _sz]),
     ("yh_tfl_classify_frame_u32", _i, [_vp, _vp, _i, _i, _i]),
     ("yh_scene_create", _i, [_i, _i, _i, C.POINTER(_vp)]),
@@ -2057,6 +2059,19 @@ def tfl_validate(model_bytes):
 
 _KIND_NP = {1: np.float32, 3: np.uint8, 2: np.int32}
 
+# YH_TFL_FAM_* (include/yolact_hip_debug.h), by value
+TFL_FAMILIES = ("conv_scalar", "conv_px8", "conv_dot1", "conv_dot4", "conv_i8_lds", "conv_i8_direct", "dw_scalar", "dw_c4",
+                "add", "requant", "quantize_f32", "dequantize", "lut", "pad", "resize", "concat", "copy")
+
+
+def tfl_direct_forms():
+    """yh_tfl_direct_forms: the rows (D, once, KK) of the register-fed int8 convolution's table of forms (no GPU)."""
+    L = load_library()
+    n = L.yh_tfl_direct_forms(None, 0)
+    rows = (_i * (3 * n))()
+    L.yh_tfl_direct_forms(rows, n)
+    return [(rows[3 * i], bool(rows[3 * i + 1]), rows[3 * i + 2]) for i in range(n)]
+
 
 class TfliteEngine:
     """RAII wrapper of yh_tfl: the reference's own model family (uint8 MobileNetV2-style .tflite)."""
@@ -2123,6 +2138,13 @@ class TfliteEngine:
         a, b, c = _i(), _i(), _i()
         self._chk(self.L.yh_tfl_plan_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(launches_per_invoke=a.value, conv2d_launches=b.value, conv2d_on_int8_mfma=c.value)
+
+    def op_info(self, op):
+        """yh_tfl_op_info: dict(family = a name of TFL_FAMILIES or None, row = the table-of-forms row or -1, grouped, folded) of
+        operator `op` (file order) for the image count of the next invoke."""
+        f, r, g, d = _i(), _i(), _i(), _i()
+        self._chk(self.L.yh_tfl_op_info(self.h, op, C.byref(f), C.byref(r), C.byref(g), C.byref(d)))
+        return dict(family=TFL_FAMILIES[f.value] if f.value >= 0 else None, row=r.value, grouped=bool(g.value), folded=bool(d.value))
 
     def tensor(self, index, shape, dtype):
         nb = getattr(self, "nb", 1)
