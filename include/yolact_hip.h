@@ -385,6 +385,31 @@ int yh_instance_track_reset_stream(yh_engine* h, int32_t stream);
  * (224 for the reference) and max_batch >= 2. Synchronous (the reference's classify is). */
 int yh_classify_frame_u32(yh_engine* h, uint32_t* frame_host, int32_t width, int32_t height,
                           int32_t compat_mode);
+/* ---- classify batch: n camera frames through one network step (DESIGN.md section 11 "Classify batch") ----------------------------
+ * Yolact::classify on n frames at once. frames: [n][H][W] packed u32 (r<<24|g<<16|b<<8), on the host or
+ * (frames_on_device = 1) on the device. The 2n tiles run as ONE step of the engine (needs 2n <= max_batch).
+ * out_host: [n][H][W] or NULL; it may be the host `frames` itself (in place, as the reference's classify).
+ * diverged_host: [n] ints or NULL.
+ * What "equal" means: the engine's launch plan depends on the batch size (tile choice, split-K), so output 4 of tile t in a step
+ * of 2n tiles is not promised to be the bits of the same tile in a step of 2. Everything around the network is exact: tiles 2b and
+ * 2b + 1 of the step are the reference's pre half of frame b (unpack, Triangle resize to 2S x S, crop), frame b of the result is
+ * the reference's post half (argmax, ids, pack, x8 upsample, stitch, Triangle resize back, repack) of the engine's own output 4
+ * for those two tiles, and with n = 1 the whole call equals yh_classify_frame_u32 bit for bit.
+ * Synchronous. One host-to-device copy when the frames are on the host, one read-back and one wait per call, whatever n (in
+ * YH_COMPAT_STRICT with out_host the frames are read back behind the divergence flags, a second wait). Everything is checked
+ * before anything is touched: YH_EINVAL for n_frames < 1, 2 n_frames > max_batch, a bad mode or size, or input_size not a multiple
+ * of 8 (<= 512); YH_ESTATE without weights; a refused call leaves the previous batch and its pointer as they were, a call that
+ * fails later leaves no batch. The batch has buffers of its own (allocated at the first call, grow only, freed by yh_destroy): it
+ * does not disturb yh_classify_device_frame, and yh_classify_frame_u32 does not disturb the batch.
+ * In YH_COMPAT_STRICT a frame whose flood fill would not terminate makes the call return YH_EDIVERGE: out_host is untouched,
+ * diverged_host[b] is 1 for exactly the frames that diverged, and no batch is left (the pointer is NULL). On success
+ * diverged_host is all zero. */
+int yh_classify_batch_u32(yh_engine* h, const uint32_t* frames, int32_t frames_on_device, int32_t n_frames,
+                          int32_t width, int32_t height, int32_t compat_mode,
+                          uint32_t* out_host, int32_t* diverged_host);
+/* Device copy of the last batch's classified frames [n][H][W]; NULL before a batch or after a failed one; valid until the next
+ * yh_classify_batch_u32 on the handle. It is what yh_scene_batch_stage_frames(.., frames_on_device = 1) takes. */
+const uint32_t* yh_classify_batch_device_frames(const yh_engine* h);
 /* The post-network half only, on caller-provided output-4 logits (n_tiles x cells x C f32, host):
  * exactly `postprocess` (src/yolact.rs:90-131) per tile. out: n_tiles x (S*S) u32. Lets the
  * reference's integer logic be checked bit-for-bit without a network in the loop. */
@@ -738,7 +763,7 @@ const char* yh_scene_batch_last_error(const yh_scene_batch* h);
  * outside 0 .. max_frames - 1. */
 int yh_scene_batch_stage(yh_scene_batch* h, int32_t slot, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device);
 /* yh_scene_batch_stage for slots first_slot .. first_slot + n_frames - 1 at once: depth u16 [n][h][w] from the host and the packed
- * frames u32 [n][h][w] from the host or (frames_on_device = 1) from a device pointer such as yh_instance_batch_device_frames. The slot
+ * frames u32 [n][h][w] from the host or (frames_on_device = 1) from a device pointer such as yh_instance_batch_device_frames or yh_classify_batch_device_frames. The slot
  * buffers are contiguous, so this is one depth copy and one frame copy on the handle's stream, then the waits yh_scene_batch_stage
  * makes: on return the caller's buffers are free again. The slots are marked staged only on success. YH_EINVAL for n_frames < 1 or a
  * range outside 0 .. max_frames - 1. */

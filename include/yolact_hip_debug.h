@@ -413,6 +413,19 @@ int yh_op_instance_track_batch(yh_engine* h, const uint8_t* masks, const int32_t
                                const uint8_t* class_map, float min_score, int32_t iou_permille, int32_t max_age, const int32_t* streams,
                                uint32_t* out_host);
 
+/* The classify batch's two kernels without the network (yh_classify_batch_u32, csrc/classify_batch.hip), for edge shapes; both need
+ * 2n <= max_batch and neither needs weights. The pre half: n packed frames u32 [n][hgt][w] from the host -> the RGB8 tiles
+ * [2n][S][S][3] the step would read (tiles 2b, 2b + 1 of frame b). *form (if not NULL) receives the form the kernel took at this
+ * geometry: 0 the vertical pass in LDS, 1 the fallback that loops over global memory. The frames of an earlier batch are overwritten:
+ * yh_classify_batch_device_frames is NULL afterwards. */
+int yh_op_classify_pre_batch(yh_engine* h, const uint32_t* frames_host, int32_t n, int32_t w, int32_t hgt,
+                             uint8_t* tiles_host /* [2n][S][S][3] */, int32_t* form /* 0 LDS, 1 fallback */);
+/* The post half on caller-provided output-4 logits f32 [2n][cells][C]: cells_postprocess and classify_post_batch, with the batch
+ * call's results and errors (YH_EDIVERGE, frames_host untouched, diverged_host [n]); frames_host and diverged_host may be NULL.
+ * On success yh_classify_batch_device_frames shows this batch. */
+int yh_op_classify_post_batch(yh_engine* h, const float* cells_host /* [2n][cells][C] */, int32_t n, int32_t w, int32_t hgt,
+                              int32_t compat_mode, uint32_t* frames_host /* [n][hgt][w] */, int32_t* diverged_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 // engine.h - the engine's data model and the functions that cross its translation units (internal, beside yh_internal.h).
 // Units: engine.hip (network, planner, step, C ABI), weights.hip (YHW1 blob), fp8.hip, rccl.hip, engine_probe.hip
 // (yh_debug_* / yh_profile_*), engine_ops.hip (yh_op_*), instance.hip, instance_batch.hip, instance_track.hip and
-// instance_track_batch.hip (yh_instance_*). DESIGN.md section 4 says what each may see.
+// instance_track_batch.hip (yh_instance_*), classify_batch.hip (yh_classify_batch_*). DESIGN.md section 4 says what each may see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -51,6 +51,10 @@ struct Buf {               // dense NHWC f16 tensor [max_batch][h][w][c] or a sl
 };
 
 struct DevAlloc { void* p; size_t bytes; };   // one hipMalloc of a handle
+
+// One Triangle resize table of the classify batch (classify_batch.hip, resize_tables): for output index o the source window
+// win[o] = (left, n) and its n weights w[o * pitch ..], each the quotient tri_w / sum the single-frame kernels form per lane.
+struct ResizeTab { int2* win; float* w; int pitch, in_size, out_size; };
 
 // One tracker of the handle's bank (instance_track.hip): stream 0 is yh_instance_track's, the others are reached through
 // yh_instance_track_batch only. Device buffers are allocated at the stream's first use and freed by yh_destroy.
@@ -207,6 +211,17 @@ struct yh_engine {
     std::vector<uint32_t> instb_meta_host;          // [n][2][128] as read back
     std::vector<std::vector<int32_t>> instb_tables; // per frame of the last batch: [rows][4]
     int instb_n = -1;                 // frames of the last batch; -1: no batch
+    // classify batch (classify_batch.hip): its own buffers, allocated at the first yh_classify_batch_u32, grow only
+    uint32_t* clsb_frames = nullptr;  // [n][height][width]: the frames as uploaded, then as classified
+    float* clsb_cells = nullptr;      // [2n][cells][C] output 4 of the step
+    uint32_t* clsb_codes = nullptr;   // [2n][cells]
+    int* clsb_div = nullptr;          // [2n] divergence flags
+    void* clsb_tab = nullptr;         // the four resize tables of geometry (clsb_tab_w, clsb_tab_h, S)
+    size_t clsb_frames_cap = 0, clsb_cells_cap = 0, clsb_codes_cap = 0, clsb_div_cap = 0, clsb_tab_cap = 0;
+    yh::ResizeTab clsb_tabs[4] = {};  // vertical H -> S, horizontal W -> 2S, vertical S -> H, horizontal 2S -> W
+    int clsb_tab_w = 0, clsb_tab_h = 0;
+    int clsb_pre_cols = 0;            // LDS columns of a classify_pre_batch block at this geometry; 0: the fallback form
+    int clsb_n = -1;                  // frames of the last batch; -1: no batch
     // instance tracks (instance_track.hip): the bank of trackers, stream 0 the one yh_instance_track advances
     yh::TrkStream trk[yh::kTrkStreams];
     uint32_t* trk_ov = nullptr;     // I [128][128] then A [128]: zeroed on the stream by every tracked call
@@ -312,6 +327,8 @@ int track_batch_readback(yh_engine* h, int n);
 void track_batch_finish(yh_engine* h, int n, const InstTrackBatch& trk);
 void track_batch_drop(yh_engine* h, int n, const InstTrackBatch& trk);   // empties every tracker the call named
 void track_batch_free(yh_engine* h);
+// classify_batch.hip
+void classify_batch_free(yh_engine* h);
 // fp8.hip
 void plan_fp8(yh_engine* h);
 std::string fp8_missing(const yh_engine* h);

@@ -1256,6 +1256,7 @@ void yh_destroy(yh_engine* h) {
     if (h->out_f32) hipFree(h->out_f32);
     if (h->frame_dev) hipFree(h->frame_dev);
     instance_free(h);
+    classify_batch_free(h);
     if (h->rs_tmp) hipFree(h->rs_tmp);
     if (h->cells_dev) hipFree(h->cells_dev);
     if (h->codes_dev) hipFree(h->codes_dev);

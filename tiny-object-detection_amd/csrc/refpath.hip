@@ -13,35 +13,9 @@
 // explicit round-to-nearest op per operator, bit-identical to oracle/orc_ref.c.
 // HBM-bound byte work: one lane per output pixel, consecutive lanes on consecutive pixels.
 #include "yh_internal.h"
+#include "refpath_dev.h"   // sample_window, tri_w, to_u8: shared with classify_batch.hip
 
 namespace yh {
-
-struct SampleWin { int left, n; float inputc, sratio, sum; };
-
-__device__ __forceinline__ float tri_w(int i, float inputc, float sratio) {
-    const float x = __fdiv_rn(__fsub_rn((float)i, inputc), sratio);
-    const float a = fabsf(x);
-    return a < 1.0f ? __fsub_rn(1.0f, a) : 0.0f;
-}
-
-__device__ __forceinline__ SampleWin sample_window(int out_i, int in_size, int out_size) {
-    SampleWin s;
-    const float ratio = __fdiv_rn((float)in_size, (float)out_size);
-    s.sratio = ratio < 1.0f ? 1.0f : ratio;
-    const float support = __fmul_rn(1.0f, s.sratio);
-    float inputc = __fmul_rn(__fadd_rn((float)out_i, 0.5f), ratio);
-    long long left = (long long)floorf(__fsub_rn(inputc, support));
-    left = left < 0 ? 0 : (left > in_size - 1 ? in_size - 1 : left);
-    long long right = (long long)ceilf(__fadd_rn(inputc, support));
-    right = right < left + 1 ? left + 1 : (right > in_size ? in_size : right);
-    s.inputc = __fsub_rn(inputc, 0.5f);
-    s.left = (int)left;
-    s.n = (int)(right - left);
-    float sum = 0.0f;
-    for (int i = 0; i < s.n; ++i) sum = __fadd_rn(sum, tri_w(s.left + i, s.inputc, s.sratio));
-    s.sum = sum;
-    return s;
-}
 
 template <bool PACKED>
 __global__ __launch_bounds__(256) void resize_v(const void* __restrict__ src, int sw, int sh,
@@ -68,11 +42,6 @@ __global__ __launch_bounds__(256) void resize_v(const void* __restrict__ src, in
     }
     float* o = tmp + (long long)t * 3;
     o[0] = a0; o[1] = a1; o[2] = a2;
-}
-
-__device__ __forceinline__ uint32_t to_u8(float v) {
-    v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
-    return (uint32_t)roundf(v);
 }
 
 __global__ __launch_bounds__(256) void resize_h(const float* __restrict__ tmp, int sw, int dh,

@@ -225,6 +225,8 @@ SYMBOLS = [
     ("yh_scene_batch_tour_read", _i, [_vp, _i, C.POINTER(_i), _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_scene_batch_tour_time", _i, [_vp, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_classify_device_frame", _vp, [_vp]),
+    ("yh_classify_batch_u32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    ("yh_classify_batch_device_frames", _vp, [_vp]),
     ("yh_instance_frame", _i, [_vp, _i, _i, _i, _vp, _f, _vp]),
     ("yh_instance_device_frame", _vp, [_vp]),
     ("yh_instance_read", _i, [_vp, C.POINTER(_i), _vp, _i]),
@@ -265,6 +267,8 @@ SYMBOLS = [
     ("yh_op_instance_track", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(_i)]),
     ("yh_op_instance_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     ("yh_op_instance_track_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp]),
+    ("yh_op_classify_pre_batch", _i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    ("yh_op_classify_post_batch", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 ]
 
 
@@ -714,6 +718,68 @@ class Engine:
         """In place on a C-contiguous uint32 array of width*height packed pixels."""
         assert frame_u32.dtype == np.uint32 and frame_u32.flags.c_contiguous and frame_u32.size == width * height
         self._chk(self.L.yh_classify_frame_u32(self.h, _p(frame_u32), width, height, mode))
+
+    def classify_batch(self, frames_u32=None, frames_dev_ptr=None, n=None, width=640, height=480, mode=COMPAT_STRICT, out=True):
+        """yh_classify_batch_u32: classify on n frames as one step of 2n tiles (DESIGN.md §11 "Classify batch"). frames_u32: uint32
+        [n][height][width] on the host (n defaults to its first dimension), or frames_dev_ptr: a device pointer to the same layout
+        with n given. out: True (a new array), False (nothing is copied back) or the uint32 array to write, which may be frames_u32
+        itself. Returns (frames uint32 [n][height][width], or None with out=False; diverged int32 [n]). On YH_EDIVERGE the
+        YhError carries the flags as .diverged. The device copy: classify_batch_device_frames."""
+        assert (frames_u32 is None) != (frames_dev_ptr is None), "give frames_u32 or frames_dev_ptr"
+        if frames_u32 is not None:
+            src = np.ascontiguousarray(frames_u32, np.uint32)
+            if n is None:
+                n = src.shape[0]
+            assert src.size >= max(int(n), 0) * width * height, (src.shape, n, width, height)
+            ptr, on_dev = _p(src), 0
+        else:
+            assert n is not None, "frames_dev_ptr needs n"
+            ptr, on_dev = C.c_void_p(frames_dev_ptr), 1
+        if isinstance(out, np.ndarray):   # the array to write (it may be frames_u32 itself: in place)
+            assert out.dtype == np.uint32 and out.flags.c_contiguous and out.size == int(n) * width * height
+            res = out
+        else:
+            res = np.zeros((max(int(n), 0), height, width), np.uint32) if out else None
+        div = np.zeros(max(int(n), 1), np.int32)
+        try:
+            self._chk(self.L.yh_classify_batch_u32(self.h, ptr, on_dev, int(n), width, height, mode,
+                                                   _p(res) if res is not None else None, _p(div)))
+        except YhError as e:
+            e.diverged = div[:max(int(n), 0)].copy()
+            raise
+        return res, div[:int(n)]
+
+    def classify_batch_device_frames(self):
+        """Device pointer of the last classify_batch's frames [n][height][width] (None before a batch or after a failed one): what
+        SceneBatch.stage_frames(frames_dev_ptr=...) takes."""
+        return self.L.yh_classify_batch_device_frames(self.h)
+
+    def op_classify_pre_batch(self, frames_u32, width, height):
+        """yh_op_classify_pre_batch: the batch's pre kernel alone on uint32 [n][height][width]. Returns (tiles uint8 [2n][S][S][3],
+        form: 0 the LDS form, 1 the fallback)."""
+        src = np.ascontiguousarray(frames_u32, np.uint32)
+        n = src.size // (width * height)
+        assert src.size == n * width * height
+        tiles = np.zeros((2 * n, self.S, self.S, 3), np.uint8)
+        form = C.c_int32(-1)
+        self._chk(self.L.yh_op_classify_pre_batch(self.h, _p(src), n, width, height, _p(tiles), C.byref(form)))
+        return tiles, form.value
+
+    def op_classify_post_batch(self, cells, width, height, mode=COMPAT_STRICT, out=None):
+        """yh_op_classify_post_batch: cells_postprocess and the batch's post kernel on float32 [2n][cells][C] logits. Returns
+        (frames uint32 [n][height][width], diverged int32 [n]); `out`, if given, is the array written (left untouched on
+        YH_EDIVERGE, where the YhError carries the flags as .diverged)."""
+        cells = np.ascontiguousarray(cells, np.float32)
+        n = cells.shape[0] // 2
+        res = out if out is not None else np.zeros((n, height, width), np.uint32)
+        assert res.dtype == np.uint32 and res.flags.c_contiguous and res.size == n * width * height
+        div = np.zeros(max(n, 1), np.int32)
+        try:
+            self._chk(self.L.yh_op_classify_post_batch(self.h, _p(cells), n, width, height, mode, _p(res), _p(div)))
+        except YhError as e:
+            e.diverged = div[:n].copy()
+            raise
+        return res, div[:n]
 
     def postprocess_cells(self, cells, mode=COMPAT_STRICT):
         cells = np.ascontiguousarray(cells, np.float32)
