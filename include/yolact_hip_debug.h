@@ -279,6 +279,20 @@ int yh_debug_fp8_weights(yh_engine* h, int32_t layer_index, uint8_t* codes, floa
 /* Test hook: number of conv kernel launches the last yh_op_conv2d_f16 on this handle was planned as
  * (1 = single launch, 2 = two-phase or channel-split plan; the split-K reduce is not counted). */
 int yh_debug_last_conv_launches(const yh_engine* h);
+/* The forms conv_igemm_f16 is instantiated in (ConvForm, csrc/yh_internal.h): plain, the streaming tile's 3x3 form, split-K (the slice
+ * kernel; splitk_reduce_f16 finishes it), multi-level, multi-level split-K, two-source, two-source split-K, upsampled residual, fused
+ * 1x1 tail, dense 1x1. YH_FORM_REDUCE is no form of the table: it stands for splitk_reduce_f16 in yh_debug_last_conv_forms. */
+enum { YH_FORM_PLAIN = 0, YH_FORM_K3, YH_FORM_SPLITK, YH_FORM_ML, YH_FORM_ML_SPLITK, YH_FORM_DUAL, YH_FORM_DUAL_SPLITK, YH_FORM_RESUP,
+       YH_FORM_TAIL, YH_FORM_LIN, YH_CONV_FORMS, YH_FORM_REDUCE = YH_CONV_FORMS };
+/* The table of conv kernel instances (kConvTiles, csrc/conv_igemm.hip) as it was compiled: returns the number of tiles and writes, for
+ * the first `cap` of them, rows[5 i ..] = { tile id, channels per tile, rows per tile, 1 if the tile reads E4M3 operands, form mask
+ * (bit f: the tile is instantiated in form f) }. Takes no handle and touches no device: tests/test_conv_form_cases.py holds the
+ * table against the tests' cases (a (tile, form) without a case does not ship). rows may be NULL. */
+int yh_conv_forms(int32_t* rows, int32_t cap);
+/* Test hook: the kernels the last single-op conv call on this handle launched, in order: pairs[2 i] = tile id, pairs[2 i + 1] = form
+ * (the value the launch was made with, not a re-derivation); a split-K call lists its reduce kernel as (-1, YH_FORM_REDUCE).
+ * Returns their number and writes the first `cap` pairs. A refused call (YH_EINVAL) leaves the list as it was. */
+int yh_debug_last_conv_forms(const yh_engine* h, int32_t* pairs, int32_t cap);
 
 /* Audit hooks (profiles/r03_fault_audit.md). Text into out[cap] (YH_EOVERFLOW if truncated): every buffer of the handle
  * with [base, end) and where those sit inside their 2 MiB page; the nodes of the step for the current batch size as the
@@ -376,6 +390,31 @@ int yh_op_absmax_channels_f16(yh_engine* h, const uint16_t* x, int64_t rows, int
 int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
                      const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
                      const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch);
+/* tune.op_tile may name another fp8 tile (TILE_128x128_FP8 = 23, TILE_64x64_FP8 = 24; the weight panel is then padded to that tile's
+ * channels); YH_EINVAL, and no launch, for a tile that is not an fp8 tile of the plain form.
+ * The multi-level form of the fp8 convolution (yh_op_conv2d_levels_f16's layout, E4M3 codes as in yh_op_conv2d_fp8; k 1 or 3, stride 1,
+ * 'same' padding) on the fp8 tiles that have it: tune.op_tile 20 (default) or 23. */
+int yh_op_conv2d_levels_fp8(yh_engine* h, const uint8_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
+                            const uint8_t* w, const float* scale, const float* bias, int32_t cout, int32_t k, int32_t act, uint16_t* y);
+/* The FPN lateral: a 1x1 convolution whose residual is the lower pyramid level resized in the epilogue (ConvParams::res_up),
+ *   y[n][P][Q][cout] = f16(act((acc + bias) + f16(bilinear(res_lo -> P x Q)))),   x [n][P][Q][cin], w [cout][cin], res_lo [n][rh][rw][cout]
+ * (cin % 64 == 0; act 0 / 1). tune.op_tile selects the tile (default TILE_128x128); tune.op_kslices forces a split-K on the tiles that
+ * have that form (the residual is then resized by splitk_reduce_f16). YH_EINVAL, and no launch, for a tile without the form. */
+int yh_op_conv2d_resup_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t P, int32_t Q, int32_t cin, const uint16_t* w,
+                           const float* bias, int32_t cout, const uint16_t* res_lo, int32_t rh, int32_t rw, int32_t act, uint16_t* y);
+/* A k x k stride-1 'same' convolution to exactly 256 channels with the 1x1 convolution to 32 channels run on its LDS image in the
+ * epilogue (ConvParams::w2: the protonet's last two layers as one launch):
+ *   t = f16(act(conv(x, w) + bias)),  y2[M][32] = f16(relu(w2 t + bias2)),   w [256][k][k][cin], w2 [32][256], M = n hh ww
+ * (cin % 64 == 0, act 0 / 1; t is never stored). tune.op_tile: a tile with the form (default TILE_256x256_M16). y2 is staged with 256
+ * guard rows of 0xFF behind row M - 1: YH_EOVERFLOW if the launch changed one of their bytes. YH_EINVAL, and no launch, for cout != 256
+ * or a tile without the form. */
+int yh_op_conv2d_tail_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
+                          const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2, const float* bias2, uint16_t* y2);
+/* ... with E4M3 operands for the first convolution (x, w: codes, cin % 128 == 0; t = f16(act(acc * scale[ch] + bias[ch]))), on
+ * TILE_256x256_FP8. */
+int yh_op_conv2d_tail_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
+                          const float* scale, const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2,
+                          const float* bias2, uint16_t* y2);
 /* Detection tail alone on caller-provided head outputs (host f16 bits, layouts as outputs 0..3)
  * for n frames; results are then read with yh_read_detections. Lets the tail be checked
  * bit-for-bit against the oracle on identical inputs. */

@@ -142,3 +142,8 @@ def test_fp8_epilogue(eng, oracle, cid):
     xc, wc = oracle.quantize_e4m3(c["xi"]), oracle.quantize_e4m3(c["wi"])
     got, _ = eng.op_conv2d_fp8(xc, wc, c["scale"], c["bias"], c["stride"], c["pad"], c["res"], c["act"])
     _same(got, cid)
+    # ... and of the small-batch fp8 tiles (128 x 128: id 23, 64 x 64: id 24), which the entry point runs when tune.op_tile names them
+    for name, tile in (("128x128_FP8", 23), ("64x64_FP8", 24)):
+        got, _ = _forced(eng, {"op_tile": tile}, lambda: eng.op_conv2d_fp8(xc, wc, c["scale"], c["bias"], c["stride"], c["pad"], c["res"], c["act"]))
+        assert eng.last_conv_forms() == [(tile, "PLAIN")]
+        _same(got, cid, name)

@@ -1057,6 +1057,7 @@ int conv_tile_ch(ConvTile t) { return conv_row(t).tch; }
 int conv_tile_m(ConvTile t) { return conv_row(t).tm; }
 const char* conv_tile_symbol(ConvTile t) { return conv_row(t).symbol; }
 bool conv_tile_has(ConvTile t, ConvForm f) { return conv_row(t).kernel[f] != nullptr; }
+bool conv_tile_fp8(ConvTile t) { return conv_row(t).fp8; }
 
 // The form a launch with these parameters takes, whether or not the tile has it.
 static ConvForm conv_form(const ConvParams& p, ConvTile tile) {
@@ -1132,17 +1133,54 @@ hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// One kernel launch (for split-K: the main kernel only; launch_splitk_reduce finishes it).
-hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream) {
+// What launch_conv checks before it launches: the form the parameters take on this tile, and its grid's row tiles.
+static bool conv_launch_check(const ConvParams& p, ConvTile tile, ConvForm* form, int* n_m_tiles) {
     const ConvTileRow& r = conv_row(tile);
     const ConvForm f = conv_form(p, tile);
-    if (!r.kernel[f] || conv_form_rejects(p, f) || (r.fp8 && !p.scale)) return hipErrorInvalidValue;
-    const int n_m_tiles = (p.M + r.tm - 1) / r.tm - p.m_tile0;
-    if (n_m_tiles < 1) return hipErrorInvalidValue;
-    if (!conv_geometry_matches(p, tile, n_m_tiles)) return hipErrorInvalidValue;   // conv_set_geometry was not run on these parameters, or refused them
+    if (!r.kernel[f] || conv_form_rejects(p, f) || (r.fp8 && !p.scale)) return false;
+    *n_m_tiles = (p.M + r.tm - 1) / r.tm - p.m_tile0;
+    if (*n_m_tiles < 1) return false;
+    if (!conv_geometry_matches(p, tile, *n_m_tiles)) return false;   // conv_set_geometry was not run on these parameters, or refused them
+    *form = f;
+    return true;
+}
+bool conv_launchable(const ConvParams& p, ConvTile tile) {
+    ConvForm f;
+    int n_m_tiles;
+    return conv_launch_check(p, tile, &f, &n_m_tiles);
+}
+
+// One kernel launch (for split-K: the main kernel only; launch_splitk_reduce finishes it).
+hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream, int* form_out) {
+    ConvForm f;
+    int n_m_tiles;
+    if (!conv_launch_check(p, tile, &f, &n_m_tiles)) return hipErrorInvalidValue;
+    const ConvTileRow& r = conv_row(tile);
     const int slices = p.k_slices > 1 ? p.k_slices : 1;   // (the split-K forms' grid also splits K)
     hipLaunchKernelGGL(r.kernel[f], dim3((unsigned)(n_m_tiles * p.n_ch_tiles * slices)), dim3(r.threads), 0, stream, p);
+    if (form_out) *form_out = (int)f;
     return hipGetLastError();
 }
 
 }  // namespace yh
+
+// The table itself, for the tests' coverage rule (tests/conv_form_cases.py: a (tile, form) without a case does not ship): no handle,
+// no device. The form numbering of include/yolact_hip_debug.h is ConvForm's.
+static_assert(YH_FORM_PLAIN == yh::FORM_PLAIN && YH_FORM_K3 == yh::FORM_K3 && YH_FORM_SPLITK == yh::FORM_SPLITK && YH_FORM_ML == yh::FORM_ML &&
+              YH_FORM_ML_SPLITK == yh::FORM_ML_SPLITK && YH_FORM_DUAL == yh::FORM_DUAL && YH_FORM_DUAL_SPLITK == yh::FORM_DUAL_SPLITK &&
+              YH_FORM_RESUP == yh::FORM_RESUP && YH_FORM_TAIL == yh::FORM_TAIL && YH_FORM_LIN == yh::FORM_LIN && YH_CONV_FORMS == yh::CONV_FORMS,
+              "include/yolact_hip_debug.h exports ConvForm's numbering");
+extern "C" int yh_conv_forms(int32_t* rows, int32_t cap) {
+    int n = 0;
+    for (const yh::ConvTileRow& r : yh::kConvTiles) {
+        if (rows && n < cap) {
+            unsigned mask = 0;
+            for (int f = 0; f < yh::CONV_FORMS; ++f)
+                if (yh::conv_tile_has((yh::ConvTile)r.id, (yh::ConvForm)f)) mask |= 1u << f;
+            int32_t* o = rows + 5 * n;
+            o[0] = r.id; o[1] = r.tch; o[2] = r.tm; o[3] = r.fp8 ? 1 : 0; o[4] = (int32_t)mask;
+        }
+        ++n;
+    }
+    return n;
+}

@@ -251,6 +251,7 @@ struct yh_engine {
     hipEvent_t stage_ev[2] = { nullptr, nullptr };
     int stage_idx = 0;
     int last_conv_launches = 0;   // yh_debug_last_conv_launches
+    std::vector<int> last_conv_forms;   // yh_debug_last_conv_forms: (tile, form) of every kernel the last single-op conv call launched
     bool stem_fused = false;
     int tail_fork_op = 0;   // ops[tail_fork_op..] (the protonet) do not feed the tail's K1-K3
     int head_fork_op = 0;   // ops[head_fork_op .. tail_fork_op) are the shared prediction head; the protonet does not read them
@@ -281,7 +282,11 @@ int ensure_out_f32(yh_engine* h, size_t nfloats);
 void drop_graphs(yh_engine* h);   // captured steps bake in tuning, scales, streams: whoever changes one of those drops them
 int plan_conv(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, KLaunch out[3]);
 hipError_t launch_k(const KLaunch& k, hipStream_t stream);
-hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches = nullptr);
+// n_launches (the single-op entry points): the plan's launch count and, in forms, the (tile, form) pair of every kernel launched - the
+// split-K reduce as (-1, YH_FORM_REDUCE); hipErrorInvalidValue BEFORE the first launch, both left as they were, when launch_conv
+// would refuse one of the plan's launches.
+hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches = nullptr,
+                               std::vector<int>* forms = nullptr);
 bool conv_absorbed(yh_engine* h, const Op& o, int n);
 bool chain_active(const yh_engine* h, const Op& ob, int n);
 int plan_op(yh_engine* h, const Op& o, int n, OpLaunch* out);

@@ -640,13 +640,21 @@ hipError_t launch_k(const KLaunch& k, hipStream_t stream) {
     return k.reduce ? launch_splitk_reduce(k.p, stream) : launch_conv(k.p, k.tile, stream);
 }
 
-hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches) {
+hipError_t launch_conv_planned(const Tune& tu, const ConvParams& p, ConvTile tile, int coutPad, hipStream_t stream, int* n_launches,
+                               std::vector<int>* forms) {
     KLaunch k[3];
     const int nk = plan_conv(tu, p, tile, coutPad, k);
-    if (n_launches) *n_launches = p.k_slices > 1 ? 1 : nk;   // (the split-K reduce is not counted: include/yolact_hip.h)
+    if (n_launches) {
+        for (int i = 0; i < nk; ++i)
+            if (!k[i].reduce && !conv_launchable(k[i].p, k[i].tile)) return hipErrorInvalidValue;
+        *n_launches = p.k_slices > 1 ? 1 : nk;   // (the split-K reduce is not counted: include/yolact_hip.h)
+        if (forms) forms->clear();
+    }
     for (int i = 0; i < nk; ++i) {
-        const hipError_t e = launch_k(k[i], stream);
+        int form = YH_FORM_REDUCE;
+        const hipError_t e = k[i].reduce ? launch_splitk_reduce(k[i].p, stream) : launch_conv(k[i].p, k[i].tile, stream, &form);
         if (e != hipSuccess) return e;
+        if (n_launches && forms) { forms->push_back(k[i].reduce ? -1 : (int)k[i].tile); forms->push_back(form); }
     }
     return hipSuccess;
 }

@@ -57,6 +57,22 @@ void force_split_k(yh_engine* h, ConvParams& p, size_t M, int coutPad) {
     p.partial = h->splitk_ws;
 }
 
+
+// launch_conv_planned for a single-op call: counts and names the launches on the handle; false = no launch of the plan was made,
+// because launch_conv has no kernel for one of them (the caller answers YH_EINVAL)
+bool launch_op_conv(yh_engine* h, OpStaging& st, const ConvParams& p, ConvTile tile, int coutPad) {
+    st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches, &h->last_conv_forms);
+    if (st.e != hipErrorInvalidValue) return true;
+    st.e = hipSuccess;
+    return false;
+}
+
+bool guard_touched(const void* v, size_t from, size_t to) {
+    const uint8_t* b = (const uint8_t*)v;
+    for (size_t i = from; i < to; ++i) if (b[i] != 0xFF) return true;
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -96,7 +112,9 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     std::vector<uint16_t> wp((size_t)coutPad * Kpad, 0), rs, ys(M * cout8);
     for (int o = 0; o < cout; ++o)
         for (int t = 0; t < k * k; ++t) memcpy(&wp[(size_t)o * Kpad + (size_t)t * cs], &w[((size_t)o * k * k + t) * cin], (size_t)cin * 2);
-    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    // (+ 32: the 96-channel tile's epilogue has 16 lanes of 8 channels per row - 12 in use - and every lane reads its bias, so the
+    // last channel tile reads up to channel coutPad + 31; the engine's bias arrays are padded to 384 behind that tile's base of 256)
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad + 32);
     if (residual) rs = pad_rows(residual, M, cout, cout8);
     std::vector<int2> tab;
     if (cin == 3) { tab.resize(Kpad / 8); for (int i = 0; i < Kpad / 8; ++i) tab[i] = i < k * k ? make_int2(i / k, i % k) : make_int2(1 << 20, 0); }
@@ -123,7 +141,7 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
             for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
         }
         force_split_k(h, p, M, coutPad);
-        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
+        if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "conv op: no conv kernel for these parameters on this tile (tune.op_tile, tune.op_kslices)");
     }
     st.sync(h->stream);
     st.get(ys.data(), dy, ys.size() * 2);
@@ -174,7 +192,7 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
         p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
         if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, p, M, coutPad);
-        st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches);
+        if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "dual conv op: no conv kernel for these parameters on this tile");
     }
     st.sync(h->stream);
     st.get(y, dy, M * cout * 2);
@@ -358,17 +376,22 @@ int yh_op_stem_pool_rgb8(yh_engine* h, const uint8_t* rgb, int32_t n, int32_t S,
     return op_stem_pool_impl(h, nullptr, rgb, n, S, w, bias, stem_out, pool_out);
 }
 
-// Experimental: the fp8 form of the convolution through the 256x256 tile. x: E4M3 codes
-// [n][hh][ww][cin], w: E4M3 codes [cout][k][k][cin], out = act(acc * scale[ch] + bias[ch] (+ residual)) as f16.
-int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
-                     const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
-                     const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch) {
-    if (!h || !x || !w || !scale || !bias || !y || n < 1 || k < 1 || stride < 1 || cin % 128 != 0 || (act < 0 || act > 1))
+// Experimental: the fp8 form of the convolution (the 256x256 tile unless tune.op_tile names another fp8 tile). x: E4M3
+// codes [n][hh][ww][cin], w: E4M3 codes [cout][k][k][cin], out = act(acc * scale[ch] + bias[ch] (+ residual)) as f16.
+// nlev > 0: the multi-level form, x [n][cells][cin] (hh = cells, ww = 1) as in op_conv2d_impl.
+static int op_conv2d_fp8_impl(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
+                              const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                              const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch,
+                              const int32_t* level_sizes, int32_t nlev) {
+    if (!h || !x || !w || !scale || !bias || !y || n < 1 || k < 1 || stride < 1 || cout < 1 || cin < 128 || cin % 128 != 0 || (act < 0 || act > 1))
         return h ? h->fail(YH_EINVAL, "fp8 conv op: need cin % 128 == 0") : YH_EINVAL;
+    const ConvTile tile = h->tune.op_tile >= 0 ? (ConvTile)h->tune.op_tile : TILE_256x256_FP8;
+    if (!conv_tile_fp8(tile) || !conv_tile_has(tile, nlev > 0 ? FORM_ML : FORM_PLAIN))
+        return h->fail(YH_EINVAL, "fp8 conv op: tune.op_tile is not an fp8 tile of this form");
     HIPCHK(h, hipSetDevice(h->dev));
-    const int P = out_dim(hh, k, stride, pad), Q = out_dim(ww, k, stride, pad);
+    const int P = nlev > 0 ? hh : out_dim(hh, k, stride, pad), Q = nlev > 0 ? 1 : out_dim(ww, k, stride, pad);
     if (P < 1 || Q < 1) return h->fail(YH_EINVAL, "fp8 conv op: empty output");
-    const int Kpad = k * k * cin, coutPad = round_up(cout, 256), cout8 = round_up(cout, 8);
+    const int tch = conv_tile_ch(tile), Kpad = k * k * cin, coutPad = round_up(cout, tch), cout8 = round_up(cout, 8);
     const size_t M = (size_t)n * P * Q, xbytes = (size_t)n * hh * ww * cin;
     const std::vector<uint8_t> wp = pad_rows(w, 1, (size_t)cout * Kpad, (size_t)coutPad * Kpad);   // [cout][k][k][cin] is already the panel's K order
     const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad), sp = pad_rows(scale, 1, cout, coutPad);
@@ -391,13 +414,19 @@ int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int3
         p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)wp.size();
         p.N = n; p.H = hh; p.W = ww; p.C = cin / 2; p.P = P; p.Q = Q; p.R = k; p.S = k; p.stride = stride; p.pad = pad;
         p.M = (int)M; p.cout8 = cout8; p.ldw = Kpad / 2; p.ksteps = Kpad / 128; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
-        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / 256; p.k_slices = 1;
-        st.e = conv_set_geometry(p, TILE_256x256_FP8);
-        if (st.ok()) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / tch; p.k_slices = 1;
+        if (nlev > 0) {
+            p.nlev = nlev;
+            for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
+        }
+        if (conv_set_geometry(p, tile) != hipSuccess || !conv_launchable(p, tile)) return h->fail(YH_EINVAL, "fp8 conv op: no conv kernel for these parameters on this tile");
+        int form = -1;
+        st.e = launch_conv(p, tile, h->stream, &form);
+        if (st.ok()) { h->last_conv_launches = 1; h->last_conv_forms.assign({ (int)tile, form }); }
         st.sync(h->stream);
         if (st.ok() && reps > 0 && ms_per_launch) {          // timing: reps back-to-back launches between two events
             hipEventRecord(h->ev0, h->stream);
-            for (int r = 0; r < reps && st.ok(); ++r) st.e = launch_conv(p, TILE_256x256_FP8, h->stream);
+            for (int r = 0; r < reps && st.ok(); ++r) st.e = launch_conv(p, tile, h->stream);
             hipEventRecord(h->ev1, h->stream);
             if (st.ok()) st.e = hipEventSynchronize(h->ev1);
             float ms = 0; hipEventElapsedTime(&ms, h->ev0, h->ev1);
@@ -408,6 +437,120 @@ int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int3
     if (const int rc = st.status(h, "fp8 conv op: ")) return rc;
     unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
+}
+
+int yh_op_conv2d_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
+                     const float* scale, const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad,
+                     const uint16_t* residual, int32_t act, uint16_t* y, int32_t reps, float* ms_per_launch) {
+    return op_conv2d_fp8_impl(h, x, n, hh, ww, cin, w, scale, bias, cout, k, stride, pad, residual, act, y, reps, ms_per_launch, nullptr, 0);
+}
+
+int yh_op_conv2d_levels_fp8(yh_engine* h, const uint8_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
+                            const uint8_t* w, const float* scale, const float* bias, int32_t cout, int32_t k, int32_t act, uint16_t* y) {
+    if (!level_sizes || nlev < 1 || nlev > 5 || (k != 1 && k != 3)) return YH_EINVAL;
+    int cells = 0;
+    for (int l = 0; l < nlev; ++l) { if (level_sizes[l] < 1) return YH_EINVAL; cells += level_sizes[l] * level_sizes[l]; }
+    return op_conv2d_fp8_impl(h, x, n, cells, 1, cin, w, scale, bias, cout, k, 1, k / 2, nullptr, act, y, 0, nullptr, level_sizes, nlev);
+}
+
+// The FPN lateral as the engine launches it (fill_conv_params with Op::res_up): a 1x1 conv, the residual the lower level resized in
+// the epilogue - or, under a forced split-K, in splitk_reduce_f16.
+int yh_op_conv2d_resup_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t P, int32_t Q, int32_t cin, const uint16_t* w,
+                           const float* bias, int32_t cout, const uint16_t* res_lo, int32_t rh, int32_t rw, int32_t act, uint16_t* y) {
+    if (!h || !x || !w || !bias || !res_lo || !y) return YH_EINVAL;
+    if (n < 1 || P < 1 || Q < 1 || rh < 1 || rw < 1 || cout < 1 || cin < 64 || cin % 64 != 0 || act < 0 || act > 1)
+        return h->fail(YH_EINVAL, "resup conv op: need cin % 64 == 0, act 0 or 1 and non-empty tensors");
+    const ConvTile tile = h->tune.op_tile >= 0 ? (ConvTile)h->tune.op_tile : TILE_128x128;
+    if (!conv_tile_has(tile, FORM_RESUP)) return h->fail(YH_EINVAL, "resup conv op: tune.op_tile is not a tile of the upsampled-residual form");
+    HIPCHK(h, hipSetDevice(h->dev));
+    const int tch = conv_tile_ch(tile), coutPad = round_up(cout, tch), cout8 = round_up(cout, 8);
+    const size_t M = (size_t)n * P * Q, Mr = (size_t)n * rh * rw, nx = M * cin;
+    const std::vector<uint16_t> wp = pad_rows(w, 1, (size_t)cout * cin, (size_t)coutPad * cin);
+    const std::vector<float> bp = pad_rows(bias, 1, cout, coutPad);
+    const std::vector<uint16_t> rs = pad_rows(res_lo, Mr, cout, cout8);
+    std::vector<uint16_t> ys(M * cout8);
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(x, nx * 2, nx * 2 + 64, &zo);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
+    const half_t* dr = st.upload<half_t>(rs.data(), rs.size() * 2);
+    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    if (st.ok()) {
+        ConvParams p;
+        memset(&p, 0, sizeof p);
+        p.x = dx; p.w = dw; p.bias = db; p.res = dr; p.y = dy;
+        p.res_up = 1; p.res_h = rh; p.res_w = rw;
+        p.x_img_stride = (long long)P * Q * cin; p.y_img_stride = (long long)P * Q * cout8; p.res_img_stride = (long long)rh * rw * cout8;
+        p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)(wp.size() * 2);
+        p.N = n; p.H = P; p.W = Q; p.C = cin; p.P = P; p.Q = Q; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
+        p.M = (int)M; p.cout8 = cout8; p.ldw = cin; p.ksteps = cin / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
+        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / tch; p.k_slices = 1;
+        if (conv_tile_has(tile, FORM_SPLITK)) force_split_k(h, p, M, coutPad);
+        if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "resup conv op: no conv kernel for these parameters on this tile");
+    }
+    st.sync(h->stream);
+    st.get(ys.data(), dy, ys.size() * 2);
+    if (const int rc = st.status(h, "resup conv op: ")) return rc;
+    unpad_rows(y, ys, M, cout, cout8);
+    return YH_OK;
+}
+
+// The protonet's last two layers as the engine launches them (fill_conv_params with Op::tail_op): the first conv's 256 channels stay in
+// LDS, only y2 is written. fp8: x and w are E4M3 codes (scale given), the loader's units two codes.
+static int op_conv2d_tail_impl(yh_engine* h, const void* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const void* w, const float* scale,
+                               const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2, const float* bias2, uint16_t* y2,
+                               bool fp8) {
+    const char* const what = fp8 ? "fp8 tail conv op: " : "tail conv op: ";
+    if (!h || !x || !w || !bias || !w2 || !bias2 || !y2 || (fp8 && !scale)) return YH_EINVAL;
+    const int cq = fp8 ? 128 : 64;   // channels per K step
+    if (n < 1 || hh < 1 || ww < 1 || k < 1 || !(k & 1) || cin < cq || cin % cq != 0 || act < 0 || act > 1)
+        return h->fail(YH_EINVAL, std::string(what) + "need an odd square kernel, act 0 or 1 and cin a multiple of a K step");
+    if (cout != 256) return h->fail(YH_EINVAL, std::string(what) + "the fused 1x1 tail runs on a convolution to exactly 256 channels");
+    const ConvTile tile = h->tune.op_tile >= 0 ? (ConvTile)h->tune.op_tile : (fp8 ? TILE_256x256_FP8 : TILE_256x256_M16);
+    if (!conv_tile_has(tile, FORM_TAIL) || conv_tile_fp8(tile) != fp8) return h->fail(YH_EINVAL, std::string(what) + "tune.op_tile is not a tile of the fused-tail form");
+    HIPCHK(h, hipSetDevice(h->dev));
+    constexpr size_t kGuardRows = 256;
+    const int es = fp8 ? 1 : 2, Kpad = k * k * cin;           // bytes per operand element
+    const size_t M = (size_t)n * hh * ww, xbytes = M * cin * es, wbytes = (size_t)256 * Kpad * es, ny = M * 32, gy = kGuardRows * 32;
+    OpStaging st;
+    unsigned zo = 0;
+    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
+    const half_t* dw = st.upload<half_t>(w, wbytes);
+    const float* db = st.upload<float>(bias, 256 * 4);
+    const float* dsc = fp8 ? st.upload<float>(scale, 256 * 4) : nullptr;
+    const half_t* dw2 = st.upload<half_t>(w2, (size_t)32 * 256 * 2);
+    const float* db2 = st.upload<float>(bias2, 32 * 4);
+    half_t* dy2 = st.alloc<half_t>((ny + gy) * 2, 0xFF);   // kGuardRows rows behind row M - 1 that the launch may not touch
+    if (st.ok()) {
+        ConvParams p;
+        memset(&p, 0, sizeof p);
+        const int C = fp8 ? cin / 2 : cin;   // (fp8: the loader's units are 2 bytes, two codes)
+        p.x = dx; p.w = dw; p.bias = db; p.scale = dsc; p.w2 = dw2; p.bias2 = db2; p.y2 = dy2;
+        p.x_img_stride = (long long)hh * ww * C; p.y_img_stride = (long long)hh * ww * 256;
+        p.x_zero_off = zo; p.x_bytes = zo + 16u; p.w_bytes = (unsigned)wbytes;
+        p.N = n; p.H = hh; p.W = ww; p.C = C; p.P = hh; p.Q = ww; p.R = k; p.S = k; p.stride = 1; p.pad = k / 2;
+        p.M = (int)M; p.cout8 = 256; p.ldw = fp8 ? Kpad / 2 : Kpad; p.ksteps = Kpad / cq; p.ldy = 256; p.y_dense = 1;
+        p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = 1; p.k_slices = 1;
+        if (!launch_op_conv(h, st, p, tile, 256)) return h->fail(YH_EINVAL, std::string(what) + "no conv kernel for these parameters on this tile");
+    }
+    st.sync(h->stream);
+    std::vector<uint16_t> ys(ny + gy);
+    st.get(ys.data(), dy2, ys.size() * 2);
+    if (const int rc = st.status(h, what)) return rc;
+    if (guard_touched(ys.data(), ny * 2, ys.size() * 2)) return h->fail(YH_EOVERFLOW, std::string(what) + conv_tile_symbol(tile) + "[+1x1] stored y2 rows past M");
+    memcpy(y2, ys.data(), ny * 2);
+    return YH_OK;
+}
+
+int yh_op_conv2d_tail_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
+                          const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2, const float* bias2, uint16_t* y2) {
+    return op_conv2d_tail_impl(h, x, n, hh, ww, cin, w, nullptr, bias, cout, k, act, w2, bias2, y2, false);
+}
+int yh_op_conv2d_tail_fp8(yh_engine* h, const uint8_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint8_t* w,
+                          const float* scale, const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2,
+                          const float* bias2, uint16_t* y2) {
+    return op_conv2d_tail_impl(h, x, n, hh, ww, cin, w, scale, bias, cout, k, act, w2, bias2, y2, true);
 }
 
 int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_scale, uint8_t* y) {

@@ -58,6 +58,12 @@ int yh_debug_setup_audit(int64_t out[4]) {
 }
 
 int yh_debug_last_conv_launches(const yh_engine* h) { return h ? h->last_conv_launches : 0; }
+int yh_debug_last_conv_forms(const yh_engine* h, int32_t* pairs, int32_t cap) {
+    if (!h) return 0;
+    const int n = (int)(h->last_conv_forms.size() / 2);
+    for (int i = 0; pairs && i < n && i < cap; ++i) { pairs[2 * i] = h->last_conv_forms[2 * i]; pairs[2 * i + 1] = h->last_conv_forms[2 * i + 1]; }
+    return n;
+}
 
 // Is `name` the output of a conv whose 1x1 tail ran in its epilogue at the current batch size (the tensor was not written)?
 static bool absorbed_output(yh_engine* h, const char* name) {

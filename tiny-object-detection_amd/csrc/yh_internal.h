@@ -153,8 +153,12 @@ int conv_tile_ch(ConvTile t);   // (0: not a tile id)
 int conv_tile_m(ConvTile t);
 const char* conv_tile_symbol(ConvTile t);
 bool conv_tile_has(ConvTile t, ConvForm f);
+bool conv_tile_fp8(ConvTile t);   // the tile reads E4M3 operands (ConvParams::scale)
 std::string conv_label(const ConvParams& p, ConvTile tile);   // the tile's symbol + the form's suffix ([ml], [+1x1], [3x3])
-hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream);
+// Would launch_conv take these parameters on this tile? (The single-op entry points ask before the first launch of a plan.)
+bool conv_launchable(const ConvParams& p, ConvTile tile);
+// form_out: the form the launch ran in (yh_debug_last_conv_forms)
+hipError_t launch_conv(const ConvParams& p, ConvTile tile, hipStream_t stream, int* form_out = nullptr);
 hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t stream);
 
 // A bottleneck block's 3x3 conv, its 1x1 expand conv with the residual add, and the NEXT block's 1x1 reduce conv as one

@@ -244,6 +244,8 @@ SYMBOLS = [
     ("yh_debug_read_tensor_e4m3", _i, [_vp, C.c_char_p, _i, _vp, _sz, C.POINTER(_i * 4)]),
     ("yh_debug_fp8_weights", _i, [_vp, _i, _vp, _vp, C.POINTER(_i * 2)]),
     ("yh_debug_last_conv_launches", _i, [_vp]),
+    ("yh_debug_last_conv_forms", _i, [_vp, _vp, _i]),
+    ("yh_conv_forms", _i, [_vp, _i]),
     ("yh_debug_alloc_map", _i, [_vp, C.c_char_p, _sz]),
     ("yh_debug_setup_audit", _i, [C.POINTER(C.c_int64 * 4)]),
     ("yh_debug_rccl_shared_device", _i, [_i]),
@@ -256,6 +258,10 @@ SYMBOLS = [
     ("yh_op_quantize_e4m3", _i, [_vp, _vp, _sz, C.c_float, _vp]),
     ("yh_op_absmax_channels_f16", _i, [_vp, _vp, C.c_int64, _i, _vp]),
     ("yh_op_conv2d_fp8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    ("yh_op_conv2d_levels_fp8", _i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    ("yh_op_conv2d_resup_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    ("yh_op_conv2d_tail_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("yh_op_conv2d_tail_fp8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     ("yh_op_conv2d_dual_f16", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     ("yh_op_bneck_f16", _i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("yh_op_conv2d_levels_f16", _i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
@@ -291,6 +297,24 @@ def load_library():
 
 def version():
     return load_library().yh_version().decode()
+
+
+# ConvForm (csrc/yh_internal.h, exported as YH_FORM_* by include/yolact_hip_debug.h): index = the form's number. "REDUCE" is no form of
+# the table: Engine.last_conv_forms lists splitk_reduce_f16 as (-1, "REDUCE").
+CONV_FORMS = ("PLAIN", "K3", "SPLITK", "ML", "ML_SPLITK", "DUAL", "DUAL_SPLITK", "RESUP", "TAIL", "LIN")
+CONV_FORM_NAMES = CONV_FORMS + ("REDUCE",)
+
+
+def conv_forms():
+    """yh_conv_forms: the compiled table of conv kernel instances, one dict(tile, tch, tm, fp8, forms) per tile - forms = the names
+    (CONV_FORMS) of the forms the tile is instantiated in. Needs no GPU."""
+    L = load_library()
+    n = L.yh_conv_forms(None, 0)
+    rows = np.zeros((n, 5), np.int32)
+    assert L.yh_conv_forms(_p(rows), n) == n
+    assert not (rows[:, 4] >> len(CONV_FORMS)).any(), "a form bit this binding has no name for"
+    return [dict(tile=int(r[0]), tch=int(r[1]), tm=int(r[2]), fp8=bool(r[3]), forms=tuple(f for i, f in enumerate(CONV_FORMS) if r[4] >> i & 1))
+            for r in rows]
 
 
 def setup_audit():
@@ -858,6 +882,13 @@ class Engine:
     def last_conv_launches(self):
         return self.L.yh_debug_last_conv_launches(self.h)
 
+    def last_conv_forms(self):
+        """The kernels the last single-op conv call launched, in order: [(tile id, form name)]; a split-K call ends with (-1, "REDUCE")."""
+        n = self.L.yh_debug_last_conv_forms(self.h, None, 0)
+        pairs = np.zeros((max(n, 1), 2), np.int32)
+        self.L.yh_debug_last_conv_forms(self.h, _p(pairs), n)
+        return [(int(t), CONV_FORM_NAMES[f]) for t, f in pairs[:n]]
+
     # ---- single ops (tests)
     def op_conv2d(self, x, w, bias, stride=1, pad=0, residual=None, act=0):
         n, hh, ww, cin = x.shape
@@ -973,6 +1004,50 @@ class Engine:
         self._chk(self.L.yh_op_conv2d_fp8(self.h, _p(xc), n, hh, ww, cin, _p(wc), _p(sc), _p(bs), cout, k, stride, pad,
                                           _p(rb) if rb is not None else None, act, _p(y), reps, C.byref(ms) if reps else None))
         return y.view(np.float16).astype(np.float32), (ms.value if reps else None)
+
+    def op_conv2d_levels_fp8(self, x_codes, level_sizes, w_codes, scale, bias, act=0):
+        """op_conv2d_levels with E4M3 codes: x_codes [n][cells][cin], w_codes [cout][k][k][cin] uint8 -> [n][cells][cout] f32."""
+        n, cells, cin = x_codes.shape
+        cout, k = w_codes.shape[0], w_codes.shape[1]
+        ls = np.ascontiguousarray(level_sizes, np.int32)
+        assert cells == int((ls.astype(np.int64) ** 2).sum())
+        xc, wc = np.ascontiguousarray(x_codes, np.uint8), np.ascontiguousarray(w_codes, np.uint8)
+        sc, bs = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(bias, np.float32)
+        y = np.zeros((n, cells, cout), np.uint16)
+        self._chk(self.L.yh_op_conv2d_levels_fp8(self.h, _p(xc), n, _p(ls), len(ls), cin, _p(wc), _p(sc), _p(bs), cout, k, act, _p(y)))
+        return y.view(np.float16).astype(np.float32)
+
+    def op_conv2d_resup(self, x, w, bias, res_lo, act=0):
+        """The FPN lateral: x [n][P][Q][cin], w [cout][cin] (or [cout][1][1][cin]), res_lo [n][rh][rw][cout] resized to P x Q in the
+        conv's epilogue and added -> [n][P][Q][cout] f32."""
+        n, P, Q, cin = x.shape
+        cout = w.shape[0]
+        _, rh, rw, rc = res_lo.shape
+        assert rc == cout and w.size == cout * cin and res_lo.shape[0] == n
+        xb, wb, rb = _f16_bits(x), _f16_bits(w), _f16_bits(res_lo)
+        bias = np.ascontiguousarray(bias, np.float32)
+        y = np.zeros((n, P, Q, cout), np.uint16)
+        self._chk(self.L.yh_op_conv2d_resup_f16(self.h, _p(xb), n, P, Q, cin, _p(wb), _p(bias), cout, _p(rb), rh, rw, act, _p(y)))
+        return _bits_f32(y, y.shape)
+
+    def op_conv2d_tail(self, x, w, bias, w2, bias2, act=1, scale=None):
+        """A k x k 'same' conv to 256 channels with the 1x1 conv to 32 channels in its epilogue: x [n][h][w][cin], w [cout][k][k][cin],
+        w2 [32][256] -> y2 [n][h][w][32] f32. scale given: x and w are uint8 E4M3 codes (the fp8 tile)."""
+        n, hh, ww, cin = x.shape
+        cout, k = w.shape[0], w.shape[1]
+        w2b = _f16_bits(w2)
+        assert w2b.size == 32 * 256
+        bias, bias2 = np.ascontiguousarray(bias, np.float32), np.ascontiguousarray(bias2, np.float32)
+        y2 = np.zeros((n, hh, ww, 32), np.uint16)
+        if scale is None:
+            xb, wb = _f16_bits(x), _f16_bits(w)
+            self._chk(self.L.yh_op_conv2d_tail_f16(self.h, _p(xb), n, hh, ww, cin, _p(wb), _p(bias), cout, k, act, _p(w2b), _p(bias2), _p(y2)))
+        else:
+            xc, wc = np.ascontiguousarray(x, np.uint8), np.ascontiguousarray(w, np.uint8)
+            sc = np.ascontiguousarray(scale, np.float32)
+            self._chk(self.L.yh_op_conv2d_tail_fp8(self.h, _p(xc), n, hh, ww, cin, _p(wc), _p(sc), _p(bias), cout, k, act, _p(w2b), _p(bias2),
+                                                   _p(y2)))
+        return _bits_f32(y2, y2.shape)
 
     def op_quantize_e4m3(self, x_f16_bits, inv_scale=1.0):
         """x: uint16 array of f16 bit patterns -> uint8 e4m3 codes of x * inv_scale."""
