@@ -430,12 +430,24 @@ typedef struct yh_tfl yh_tfl;
 int yh_tfl_validate(const void* model_bytes, size_t nbytes, int32_t* n_tensors, int32_t* n_ops, char* err, size_t err_cap);
 /* FlatBufferModel::build_from_file + InterpreterBuilder + allocate_tensors (src/yolact.rs:18-35). */
 int yh_tfl_create(const void* model_bytes, size_t nbytes, int32_t device, yh_tfl** out);
+/* The same with room for up to max_images images per invoke, 1 .. YH_TFL_MAX_IMAGES (yh_tfl_create: 2, the two tiles of a frame).
+ * Every activation, every constant an operator reads as a data operand and the graph input are stored max_images times
+ * (image-major); a classify batch of n frames needs max_images >= 2n, and 512 is the 256 frames of a yh_scene_batch. YH_EINVAL,
+ * before the device is touched, for any other max_images. Why 512 holds: every launch of the executor's kernels was checked at that
+ * image count. Element-wise kernels, PAD, CONCATENATION and RESHAPE index with 64 bits; the per-image kernels take the image
+ * as a grid dimension (<= 65535) and index one image with the 32 bits they use at one image; the only 32-bit expression the image
+ * count enters is the int8 MFMA convolutions' pixel index (M = Ho x Wo x images, rounded up to a tile by the grid), and the tile
+ * prefix sums of a convolution group built on it. A model where Ho x Wo x max_images of a convolution passes 2^31 - 65 is refused
+ * at create (YH_EINVAL), a group whose tiles pass 2^31 - 1 at the first invoke of that image count: no model is capped below 512
+ * by its size alone (a 224 x 224 MobileNetV2's largest convolution: 112 x 112 x 512 = 6.4 M pixels). */
+#define YH_TFL_MAX_IMAGES 512
+int yh_tfl_create_batch(const void* model_bytes, size_t nbytes, int32_t device, int32_t max_images, yh_tfl** out);
 void yh_tfl_destroy(yh_tfl* h);
 const char* yh_tfl_last_error(const yh_tfl* h);
 int yh_tfl_input_info(const yh_tfl* h, yh_tensor_info* info);                 /* inputs()[0], :149-150 */
 int yh_tfl_output_count(const yh_tfl* h);                                      /* outputs(), :166 */
 int yh_tfl_output_info(const yh_tfl* h, int32_t i, yh_tensor_info* info);      /* tensor_info(output), :170-175 */
-/* Images per invoke: 1 (default) or 2 - the model is batch 1 (yolact.rs:149-150), its two tiles per frame are independent
+/* Images per invoke: 1 (default) .. the handle's max_images (2 unless it came from yh_tfl_create_batch) - the model is batch 1 (yolact.rs:149-150), its two tiles per frame are independent
  * (:216-217) and run as one pass of a batch plan (activations image-major; yh_tfl_classify_frame_u32 does this itself).
  * yh_tfl_set_input then takes n images, yh_tfl_output_read / yh_tfl_tensor_read return n. YH_EINVAL for a model with an
  * operator along the image axis. */
@@ -444,8 +456,36 @@ int yh_tfl_set_input(yh_tfl* h, const void* data, size_t nbytes);              /
 int yh_tfl_invoke(yh_tfl* h);                                                  /* interpreter.invoke(), :163 */
 int yh_tfl_output_read(yh_tfl* h, int32_t i, void* dst, size_t nbytes);        /* tensor_data::<u8|f32>, :173,:180 */
 /* Yolact::classify (src/yolact.rs:192-234) with this model in the middle: two S x S tiles, one
- * invoke each, output 4 dequantised (:177) and post-processed (:90-131), all on device. */
+ * invoke each, output 4 dequantised (:177) and post-processed (:90-131), all on device. (The two tiles
+ * share one invoke of two images where the handle has room for two and no operator works along the
+ * image axis; a handle made with max_images = 1 runs them one after the other: the same bytes.) */
 int yh_tfl_classify_frame_u32(yh_tfl* h, uint32_t* frame_host, int32_t width, int32_t height, int32_t compat_mode);
+/* ---- TFLite classify batch: n camera frames through one invoke of 2n images (DESIGN.md section 11 "TFLite classify batch") -----
+ * yh_classify_batch_u32 for a yh_tfl handle. frames: [n][H][W] packed u32 (r<<24|g<<16|b<<8), on the host or
+ * (frames_on_device = 1) on the device. The 2n tiles are written straight into the model's input tensor as images 2b, 2b + 1 and
+ * run as ONE invoke (needs 2n <= max_images: yh_tfl_create_batch). out_host: [n][H][W] or NULL; it may be the host `frames`
+ * itself (in place, as the reference's classify). diverged_host: [n] ints or NULL.
+ * What "equal" means: MORE than for the engine. Every kernel form of the executor is integer-exact, so an image's bytes do not
+ * depend on how many images share its invoke: frame b of the result is yh_tfl_classify_frame_u32 on frame b alone, bit for bit,
+ * for every n - and with it the reference's pre half, TFLite's uint8 arithmetic on each tile, and the reference's post half.
+ * Synchronous. One host-to-device copy when the frames are on the host, one read-back and one wait per call, whatever n (in
+ * YH_COMPAT_STRICT with out_host the frames are read back behind the divergence flags, a second wait). Everything is checked
+ * before anything is touched: YH_EINVAL for n_frames < 1, 2 n_frames > max_images, a bad mode or size, a model
+ * yh_tfl_classify_frame_u32 refuses (input not [1,S,S,3] uint8 with S % 8 == 0, S <= 512; fewer than five outputs; output 4 not
+ * (S/8)^2 cells of >= 4 logits), or a model with an operator along the image axis (one image per invoke: classify its frames one
+ * by one with yh_tfl_classify_frame_u32); a refused call leaves the previous batch and its pointer as they were, a call that
+ * fails later leaves no batch. The batch has buffers of its own (allocated at the first call, grow only, freed by yh_tfl_destroy):
+ * yh_tfl_classify_frame_u32 does not disturb the batch's frames and the batch does not disturb the single call; both run the
+ * handle's one plan, so the model's tensors hold whichever ran last. The yh_tfl_set_batch value of the caller survives the call.
+ * In YH_COMPAT_STRICT a frame whose flood fill would not terminate makes the call return YH_EDIVERGE: out_host is untouched,
+ * diverged_host[b] is 1 for exactly the frames that diverged, and no batch is left (the pointer is NULL). On success
+ * diverged_host is all zero. */
+int yh_tfl_classify_batch_u32(yh_tfl* h, const uint32_t* frames, int32_t frames_on_device, int32_t n_frames,
+                              int32_t width, int32_t height, int32_t compat_mode,
+                              uint32_t* out_host, int32_t* diverged_host);
+/* Device copy of the last batch's classified frames [n][H][W]; NULL before a batch or after a failed one; valid until the next
+ * yh_tfl_classify_batch_u32 on the handle. It is what yh_scene_batch_stage_frames(.., frames_on_device = 1) takes. */
+const uint32_t* yh_tfl_classify_batch_device_frames(const yh_tfl* h);
 
 /* ---- scene back-end: append_scene's two compute dispatches (src/scene.rs:147-331) --------------
  * shaders/pt_cloud.comp (depth + class image -> bird's-eye height map with sigmoid bumps, ball centroids) and

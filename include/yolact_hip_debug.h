@@ -100,6 +100,8 @@ double yh_flops_per_frame(const yh_engine* h);
 
 /* Same with the TFLite fields of a tuning struct (tfl_dot, tfl_graph, tfl_fuse, tfl_group; tune may be NULL). */
 int yh_tfl_create_tuned(const void* model_bytes, size_t nbytes, int32_t device, const yh_tuning* tune, yh_tfl** out);
+/* yh_tfl_create_batch with the same fields. */
+int yh_tfl_create_batch_tuned(const void* model_bytes, size_t nbytes, int32_t device, int32_t max_images, const yh_tuning* tune, yh_tfl** out);
 
 /* Kernel launches per invoke of the prepared plan; how many are CONV_2D and how many of those run on the int8 matrix pipes. */
 int yh_tfl_plan_info(const yh_tfl* h, int32_t* launches, int32_t* conv_launches, int32_t* conv_mfma_launches);

@@ -14,6 +14,8 @@
 // Every output value is the sequence of __fmul_rn / __fadd_rn the two-pass kernels of refpath.hip perform, in their order: taps left
 // to right from 0.0f, vertical first into f32, then horizontal; no FMA, no reassociation. cells_f32 and cells_postprocess are the
 // single call's kernels at 2n tiles. The batch's buffers are its own.
+// The three kernels, their tables and the pre kernel's plan are reached through classify_geo.h's geometry record and functions, which
+// take a stream: the TFLite executor's batch (tflite_exec.hip, yh_tfl_classify_batch_u32) issues the same launches around its invoke.
 #include "engine.h"
 #include "refpath_dev.h"
 
@@ -181,46 +183,82 @@ int tab_pitch(int in_size, int out_size) {
     return bound < in_size ? bound : in_size;
 }
 
-// The tables of geometry (w, hh, S) exist on the device (enqueued on the stream if they had to be built).
-int ensure_tables(yh_engine* h, int w, int hh) {
-    if (h->clsb_tab && h->clsb_tab_w == w && h->clsb_tab_h == hh) return YH_OK;
-    const int S = h->S;
+}  // namespace
+
+namespace yh {
+
+hipError_t classify_geo_ensure(ClassifyGeo* g, int w, int hh, int S, hipStream_t s) {
+    if (g->tab && g->w == w && g->h == hh && g->S == S) return hipSuccess;
     const int in[4] = { hh, w, S, 2 * S }, out[4] = { S, 2 * S, hh, w };
     size_t n_out = 0, n_w = 0;
     for (int k = 0; k < 4; ++k) { n_out += (size_t)out[k]; n_w += (size_t)out[k] * tab_pitch(in[k], out[k]); }
-    h->clsb_tab_w = h->clsb_tab_h = 0;
-    int rc = instance_grow(h, &h->clsb_tab, &h->clsb_tab_cap, n_out * sizeof(int2) + n_w * sizeof(float));
-    if (rc) return rc;
+    g->w = g->h = g->S = 0;
+    const size_t bytes = n_out * sizeof(int2) + n_w * sizeof(float);
+    if (bytes > g->tab_cap) {   // (grows only; the old one is freed)
+        if (g->tab) hipFree(g->tab);
+        g->tab = nullptr; g->tab_cap = 0;
+        if (hipMalloc(&g->tab, bytes) != hipSuccess) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
+        g->tab_cap = bytes;
+    }
     ResizeTabs tabs;
-    int2* win = (int2*)h->clsb_tab;
+    int2* win = (int2*)g->tab;
     float* wts = (float*)(win + n_out);
     for (int k = 0; k < 4; ++k) {
         tabs.t[k] = ResizeTab{ win, wts, tab_pitch(in[k], out[k]), in[k], out[k] };
         win += out[k];
         wts += (size_t)out[k] * tabs.t[k].pitch;
-        h->clsb_tabs[k] = tabs.t[k];
+        g->tabs[k] = tabs.t[k];
     }
-    hipLaunchKernelGGL(resize_tables, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, h->stream, tabs);
-    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(resize_tables, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, tabs);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
     // plan: the source columns a block of kPreBX output columns can cover, from the ratio; past the LDS budget: the fallback form
     const double r = (double)w / (double)(2 * S);
     int cols = (int)((kPreBX - 1) * r + 2.0 * (r < 1.0 ? 1.0 : r)) + 5;
     if (cols > w) cols = w;
-    h->clsb_pre_cols = cols <= kPreLdsCols ? cols : 0;
-    h->clsb_tab_w = w; h->clsb_tab_h = hh;
+    g->pre_cols = cols <= kPreLdsCols ? cols : 0;
+    g->w = w; g->h = hh; g->S = S;
+    return hipSuccess;
+}
+
+hipError_t classify_geo_pre(const ClassifyGeo& g, const uint32_t* frames_dev, int n, uint8_t* tiles, hipStream_t s) {
+    const int S = g.S, cols = g.pre_cols;
+    const dim3 grid((unsigned)((2 * S + kPreBX - 1) / kPreBX), (unsigned)((S + kPreBY - 1) / kPreBY), (unsigned)n);
+    if (cols > 0)
+        hipLaunchKernelGGL((classify_pre_batch<true>), grid, dim3(256), (size_t)3 * kPreBY * cols * sizeof(float), s, frames_dev, g.w, g.h,
+                           S, g.tabs[0], g.tabs[1], cols, tiles);
+    else
+        hipLaunchKernelGGL((classify_pre_batch<false>), grid, dim3(256), 0, s, frames_dev, g.w, g.h, S, g.tabs[0], g.tabs[1], 0, tiles);
+    return hipGetLastError();
+}
+
+hipError_t classify_geo_post(const ClassifyGeo& g, const uint32_t* codes, int n, uint32_t* out, hipStream_t s) {
+    const int grid = g.S / 8;
+    const dim3 gr((unsigned)((g.w + kPostBX - 1) / kPostBX), (unsigned)((g.h + kPostBY - 1) / kPostBY), (unsigned)n);
+    hipLaunchKernelGGL(classify_post_batch, gr, dim3(256), (size_t)2 * grid * grid * sizeof(uint32_t), s, codes, grid, g.w, g.h, g.tabs[2],
+                       g.tabs[3], out);
+    return hipGetLastError();
+}
+
+void classify_geo_free(ClassifyGeo* g) {
+    if (g->tab) hipFree(g->tab);
+    *g = ClassifyGeo();
+}
+
+}  // namespace yh
+
+namespace {
+
+// The tables of geometry (w, hh, S) exist on the device (enqueued on the stream if they had to be built).
+int ensure_tables(yh_engine* h, int w, int hh) {
+    const hipError_t e = classify_geo_ensure(&h->clsb_geo, w, hh, h->S, h->stream);
+    if (e == hipErrorOutOfMemory) return h->fail(YH_ENOMEM, "hipMalloc classify batch tables");
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("classify batch tables: ") + hipGetErrorString(e));
     return YH_OK;
 }
 
-int enqueue_pre(yh_engine* h, const uint32_t* frames_dev, int n, int w, int hh, uint8_t* tiles) {
-    const int S = h->S, cols = h->clsb_pre_cols;
-    const dim3 g((unsigned)((2 * S + kPreBX - 1) / kPreBX), (unsigned)((S + kPreBY - 1) / kPreBY), (unsigned)n);
-    if (cols > 0)
-        hipLaunchKernelGGL((classify_pre_batch<true>), g, dim3(256), (size_t)3 * kPreBY * cols * sizeof(float), h->stream, frames_dev, w, hh,
-                           S, h->clsb_tabs[0], h->clsb_tabs[1], cols, tiles);
-    else
-        hipLaunchKernelGGL((classify_pre_batch<false>), g, dim3(256), 0, h->stream, frames_dev, w, hh, S, h->clsb_tabs[0], h->clsb_tabs[1],
-                           0, tiles);
-    HIPCHK(h, hipGetLastError());
+int enqueue_pre(yh_engine* h, const uint32_t* frames_dev, int n, uint8_t* tiles) {
+    HIPCHK(h, classify_geo_pre(h->clsb_geo, frames_dev, n, tiles, h->stream));
     return YH_OK;
 }
 
@@ -231,10 +269,7 @@ int post_stage(yh_engine* h, int n, int w, int hh, int mode, uint32_t* out_host,
     const size_t npx = (size_t)w * hh;
     hipError_t e = launch_cells_postprocess(h->clsb_cells, 2 * n, grid, h->C, mode, h->clsb_codes, h->clsb_div, h->stream);
     if (e != hipSuccess) return h->fail(YH_EHIP, std::string("classify batch post: ") + hipGetErrorString(e));
-    const dim3 g((unsigned)((w + kPostBX - 1) / kPostBX), (unsigned)((hh + kPostBY - 1) / kPostBY), (unsigned)n);
-    hipLaunchKernelGGL(classify_post_batch, g, dim3(256), (size_t)2 * grid * grid * sizeof(uint32_t), h->stream,
-                       (const uint32_t*)h->clsb_codes, grid, w, hh, h->clsb_tabs[2], h->clsb_tabs[3], h->clsb_frames);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, classify_geo_post(h->clsb_geo, h->clsb_codes, n, h->clsb_frames, h->stream));
     std::vector<int> div((size_t)2 * n);
     HIPCHK(h, hipMemcpyAsync(div.data(), h->clsb_div, div.size() * 4, hipMemcpyDeviceToHost, h->stream));
     const bool early = out_host && mode == YH_COMPAT_SANE;   // (SANE never diverges)
@@ -277,8 +312,9 @@ int grow_batch(yh_engine* h, int n, int w, int hh) {
 namespace yh {
 
 void classify_batch_free(yh_engine* h) {
-    void* bufs[] = { h->clsb_frames, h->clsb_cells, h->clsb_codes, h->clsb_div, h->clsb_tab };
+    void* bufs[] = { h->clsb_frames, h->clsb_cells, h->clsb_codes, h->clsb_div };
     for (void* b : bufs) if (b) hipFree(b);
+    classify_geo_free(&h->clsb_geo);
 }
 
 }  // namespace yh
@@ -305,7 +341,7 @@ int yh_classify_batch_u32(yh_engine* h, const uint32_t* frames, int32_t frames_o
         HIPCHK(h, hipMemcpyAsync(h->clsb_frames, frames, (size_t)n * npx * 4, hipMemcpyHostToDevice, h->stream));
         src = h->clsb_frames;
     }
-    if ((rc = enqueue_pre(h, src, n, w, hh, h->in_u8()))) return rc;
+    if ((rc = enqueue_pre(h, src, n, h->in_u8()))) return rc;
     // yolact.rs:216-217 + :163: the 2n tiles as one batch
     h->cur_n = 2 * n;
     if ((rc = run(h, 0))) return rc;
@@ -330,7 +366,7 @@ int yh_op_classify_pre_batch(yh_engine* h, const uint32_t* frames_host, int32_t 
     if (hipMalloc((void**)&tiles, nb) != hipSuccess) return h->fail(YH_ENOMEM, "hipMalloc tiles");
     hipError_t e = hipMemcpyAsync(h->clsb_frames, frames_host, (size_t)n * w * hh * 4, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-        rc = enqueue_pre(h, h->clsb_frames, n, w, hh, tiles);
+        rc = enqueue_pre(h, h->clsb_frames, n, tiles);
         if (rc == YH_OK) e = hipMemcpyAsync(tiles_host, tiles, nb, hipMemcpyDeviceToHost, h->stream);
     }
     const hipError_t es = hipStreamSynchronize(h->stream);
@@ -338,7 +374,7 @@ int yh_op_classify_pre_batch(yh_engine* h, const uint32_t* frames_host, int32_t 
     if (rc) return rc;
     if (e != hipSuccess || es != hipSuccess)
         return h->fail(YH_EHIP, std::string("classify pre batch: ") + hipGetErrorString(e != hipSuccess ? e : es));
-    if (form) *form = h->clsb_pre_cols > 0 ? 0 : 1;
+    if (form) *form = h->clsb_geo.pre_cols > 0 ? 0 : 1;
     return YH_OK;
 }
 

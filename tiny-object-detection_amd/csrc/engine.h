@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "classify_geo.h"
 #include "yh_internal.h"
 
 // (hidden: nothing declared here is exported from the shared library)
@@ -51,10 +52,6 @@ struct Buf {               // dense NHWC f16 tensor [max_batch][h][w][c] or a sl
 };
 
 struct DevAlloc { void* p; size_t bytes; };   // one hipMalloc of a handle
-
-// One Triangle resize table of the classify batch (classify_batch.hip, resize_tables): for output index o the source window
-// win[o] = (left, n) and its n weights w[o * pitch ..], each the quotient tri_w / sum the single-frame kernels form per lane.
-struct ResizeTab { int2* win; float* w; int pitch, in_size, out_size; };
 
 // One tracker of the handle's bank (instance_track.hip): stream 0 is yh_instance_track's, the others are reached through
 // yh_instance_track_batch only. Device buffers are allocated at the stream's first use and freed by yh_destroy.
@@ -216,11 +213,8 @@ struct yh_engine {
     float* clsb_cells = nullptr;      // [2n][cells][C] output 4 of the step
     uint32_t* clsb_codes = nullptr;   // [2n][cells]
     int* clsb_div = nullptr;          // [2n] divergence flags
-    void* clsb_tab = nullptr;         // the four resize tables of geometry (clsb_tab_w, clsb_tab_h, S)
-    size_t clsb_frames_cap = 0, clsb_cells_cap = 0, clsb_codes_cap = 0, clsb_div_cap = 0, clsb_tab_cap = 0;
-    yh::ResizeTab clsb_tabs[4] = {};  // vertical H -> S, horizontal W -> 2S, vertical S -> H, horizontal 2S -> W
-    int clsb_tab_w = 0, clsb_tab_h = 0;
-    int clsb_pre_cols = 0;            // LDS columns of a classify_pre_batch block at this geometry; 0: the fallback form
+    size_t clsb_frames_cap = 0, clsb_cells_cap = 0, clsb_codes_cap = 0, clsb_div_cap = 0;
+    yh::ClassifyGeo clsb_geo;         // the four resize tables of the last geometry (W, H, S) and the pre kernel's plan (classify_geo.h)
     int clsb_n = -1;                  // frames of the last batch; -1: no batch
     // instance tracks (instance_track.hip): the bank of trackers, stream 0 the one yh_instance_track advances
     yh::TrkStream trk[yh::kTrkStreams];

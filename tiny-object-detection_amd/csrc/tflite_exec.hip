@@ -9,10 +9,12 @@
 // against oracle/tfl_oracle.py on synthetic models.
 //
 // This unit is the host side: the plan (one Prepared per operator: prepare), its fusion (fuse_plan) and grouping (group_plan)
-// passes, the launches of one invoke (enqueue_plan), their capture (run_plan) and the yh_tfl_* C ABI. The kernels, their
+// passes, the launches of one invoke (enqueue_plan), their capture (run_plan) and the yh_tfl_* C ABI - among it the classify batch
+// (yh_tfl_classify_batch_u32: n frames as one invoke of 2n images on a handle made by yh_tfl_create_batch). The kernels, their
 // parameter structs and launchers are tflite_kernels.hip / tflite_exec.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <limits.h>
 #include <string.h>
 
 #include <algorithm>
@@ -20,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "classify_geo.h"
 #include "tflite_exec.h"
 #include "tflite_model.h"
 #include "yh_internal.h"
@@ -79,13 +82,14 @@ struct yh_tfl {
     std::vector<char> per_image;   // constant i is read as an operator's DATA operand (ADD, CONCATENATION, RESHAPE ...): stored once per image
     std::vector<void*> extra;   // LUTs etc.
     std::vector<Prepared> plan;
-    static constexpr int kMaxBatch = 2;          // images per invoke the buffers are sized for (the two tiles of yolact.rs:216-217)
+    int max_images = 2;                          // images per invoke the buffers are sized for: 2 (the two tiles of yolact.rs:216-217) or yh_tfl_create_batch's
     int nb = 1;                                  // images of the next invoke (yh_tfl_set_batch)
     bool batch_ok = true;                        // no operator of the model touches the image axis
-    hipGraphExec_t gexecs[kMaxBatch] = { nullptr, nullptr };   // the plan per batch size, captured once and replayed (tensor addresses never change)
+    std::vector<hipGraphExec_t> gexecs;          // [max_images]: the plan per batch size, captured at its first invoke and replayed (tensor addresses never change)
     // yh_tuning.tfl_group (round 4): independent register-fed convolutions of one kernel form and one depth of the plan's DAG as ONE
     // launch (group_plan); `order` is the plan in execution order (by depth; the identity when nothing is grouped)
-    struct ConvGroup { std::vector<int> members; const ConvI8* probs[kMaxBatch] = { nullptr, nullptr }; const int* tile_start[kMaxBatch] = { nullptr, nullptr }; int tiles[kMaxBatch] = { 0, 0 }; };
+    // (the tables of image count nb at [nb - 1]: 1 and 2 built at create, every other at the first invoke of that nb - group_tables)
+    struct ConvGroup { std::vector<int> members; std::vector<const ConvI8*> probs; std::vector<const int*> tile_start; std::vector<int> tiles; };
     int use_group = 1;
     std::vector<ConvGroup> groups;
     std::vector<int> order;
@@ -101,6 +105,14 @@ struct yh_tfl {
     float *rs_tmp = nullptr, *cells_dev = nullptr;
     int* diverged_dev = nullptr;
     size_t frame_cap = 0, rs_cap = 0;
+    // classify batch (yh_tfl_classify_batch_u32): its own buffers, allocated at the first call, grow only
+    uint32_t* clsb_frames = nullptr;  // [n][height][width]: the frames as uploaded, then as classified
+    float* clsb_cells = nullptr;      // [2n][cells][C] output 4 of the invoke as f32
+    uint32_t* clsb_codes = nullptr;   // [2n][cells]
+    int* clsb_div = nullptr;          // [2n] divergence flags
+    size_t clsb_frames_cap = 0, clsb_cells_cap = 0, clsb_codes_cap = 0, clsb_div_cap = 0;
+    yh::ClassifyGeo clsb_geo;         // the resize tables of the last geometry and the pre kernel's plan (classify_geo.h)
+    int clsb_n = -1;                  // frames of the last batch; -1: no batch
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
 
@@ -119,13 +131,13 @@ int upload(yh_tfl* h, const T* src, size_t count, const char* what, const T** ou
     *out = (const T*)d;
     return YH_OK;
 }
-// The bytes of a tensor's device allocation: a constant's own, an activation's for kMaxBatch images (image-major: room for the
+// The bytes of a tensor's device allocation: a constant's own, an activation's for max_images images (image-major: room for the
 // batch plan), and 16 more (the kernels' dword and 16-byte loads may reach past the last element). A constant that an operator reads
 // where an activation could stand (an ADD operand, a CONCATENATION part, a RESHAPE's input ...) is stored like one, a copy per image:
 // the kernels index every data operand image-major, and the second image of a batch plan must meet the same constant, not the bytes behind it.
 size_t tensor_alloc_bytes(const yh_tfl* h, size_t i) {
     const TflTensor& t = h->m.tensors[i];
-    return t.count() * t.elem() * (t.data && !h->per_image[i] ? 1 : yh_tfl::kMaxBatch) + 16;
+    return t.count() * t.elem() * (t.data && !h->per_image[i] ? 1 : (size_t)h->max_images) + 16;
 }
 
 // One operator on its way into the plan: its tensors and their device buffers by tensor index, its YH_EINVAL, and one function per
@@ -333,7 +345,7 @@ int prepare(yh_tfl* h) {
         const size_t alloc = tensor_alloc_bytes(h, i);
         TCHK(h, hipMalloc(&h->tens[i], alloc));
         if (t.data) {
-            for (int k = 0; k < (h->per_image[i] ? yh_tfl::kMaxBatch : 1); ++k)
+            for (int k = 0; k < (h->per_image[i] ? h->max_images : 1); ++k)
                 TCHK(h, hipMemcpy((char*)h->tens[i] + (size_t)k * bytes, t.data, bytes, hipMemcpyHostToDevice));
         }
         else TCHK(h, hipMemset(h->tens[i], 0, alloc));
@@ -524,12 +536,35 @@ std::vector<int> plan_depths(const yh_tfl* h) {
     }
     return depth;
 }
-// ---- the entries of one depth (in execution order): those that run the register-fed kernel, bucketed by its form, as groups of 2 to kMaxGroup
+// ---- a group's parameter blocks and tile prefix table for `nb` images, in device memory the handle owns (uploaded with blocking
+// copies: never inside a capture window, never behind a launch of the invoke that needs them - run_plan calls group_tables first)
+int group_tables_of(yh_tfl* h, yh_tfl::ConvGroup& g, int nb) {
+    if (g.probs[nb - 1]) return YH_OK;
+    std::vector<ConvI8> probs;
+    std::vector<int> start(1, 0);
+    long long total = 0;
+    for (int mi : g.members) {
+        probs.push_back(conv_i8_args(h->plan[mi], nb));
+        total += (long long)((probs.back().M + 15) / 16) * ((probs.back().Co + 15) / 16);
+        if (total > INT_MAX) return h->fail(YH_EINVAL, "a convolution group's tiles at this image count exceed a 32-bit grid");
+        start.push_back((int)total);
+    }
+    if (int rc = upload(h, probs.data(), probs.size(), "conv group", &g.probs[nb - 1])) return rc;
+    if (int rc = upload(h, start.data(), start.size(), "conv group", &g.tile_start[nb - 1])) return rc;
+    g.tiles[nb - 1] = start.back();
+    return YH_OK;
+}
+int group_tables(yh_tfl* h, int nb) {
+    for (yh_tfl::ConvGroup& g : h->groups) if (int rc = group_tables_of(h, g, nb)) return rc;
+    return YH_OK;
+}
+// ---- the entries of one depth (in execution order): those that run the register-fed kernel, bucketed by its form, as groups of 2 to kMaxGroup.
+// Membership is decided at two images whatever max_images is: the groups of a handle are the same at every image count.
 int group_one_depth(yh_tfl* h, const int* first, const int* last) {
     std::map<int, std::vector<int>> byform;
     for (const int* k = first; k != last; ++k) {
         const Prepared& p = h->plan[*k];
-        if (p.kind == P_CONV_I8 && h->use_dot >= 3 && conv_i8_direct_pays(conv_i8_args(p, yh_tfl::kMaxBatch))) byform[p.form].push_back(*k);
+        if (p.kind == P_CONV_I8 && h->use_dot >= 3 && conv_i8_direct_pays(conv_i8_args(p, 2))) byform[p.form].push_back(*k);
     }
     for (auto& kv : byform) {
         std::vector<int>& v = kv.second;
@@ -538,17 +573,9 @@ int group_one_depth(yh_tfl* h, const int* first, const int* last) {
             if (c1 - c0 < 2) break;
             yh_tfl::ConvGroup g;
             g.members.assign(v.begin() + c0, v.begin() + c1);
-            for (int nb = 1; nb <= yh_tfl::kMaxBatch; ++nb) {
-                std::vector<ConvI8> probs;
-                std::vector<int> start(1, 0);
-                for (int mi : g.members) {
-                    probs.push_back(conv_i8_args(h->plan[mi], nb));
-                    start.push_back(start.back() + ((probs.back().M + 15) / 16) * ((probs.back().Co + 15) / 16));
-                }
-                if (int rc = upload(h, probs.data(), probs.size(), "conv group", &g.probs[nb - 1])) return rc;
-                if (int rc = upload(h, start.data(), start.size(), "conv group", &g.tile_start[nb - 1])) return rc;
-                g.tiles[nb - 1] = start.back();
-            }
+            g.probs.assign((size_t)h->max_images, nullptr); g.tile_start.assign((size_t)h->max_images, nullptr); g.tiles.assign((size_t)h->max_images, 0);
+            for (int nb = 1; nb <= std::min(2, h->max_images); ++nb)
+                if (int rc = group_tables_of(h, g, nb)) return rc;
             for (int mi : g.members) h->plan[mi].group = (int)h->groups.size();
             h->groups.push_back(g);
         }
@@ -623,6 +650,7 @@ int enqueue_plan(yh_tfl* h) {
 // fine, and so is the single-branch form with DEBUG_CLR_GRAPH_PACKET_CAPTURE=0. The same replay path later produced a GPU
 // memory access fault WITHOUT the profiler (engine.hip, enqueue_all), so this library never builds a single-branch graph.
 int run_plan(yh_tfl* h) {
+    if (int rc = group_tables(h, h->nb)) return rc;   // (an image count's first invoke: before the capture and before any launch)
     if (!h->use_graph) return enqueue_plan(h);
     hipGraphExec_t& gexec = h->gexecs[h->nb - 1];
     if (!gexec) {
@@ -672,6 +700,31 @@ int output4_to_f32(yh_tfl* h, size_t n, float* dst) {
     return YH_OK;
 }
 
+// What classify asks of the model (the single call and the batch): its tile size S and the logits per cell C; nullptr: fine.
+const char* classify_model_check(const yh_tfl* h, int* S_out, int* C_out) {
+    const TflTensor& in = h->m.tensors[h->m.inputs[0]];
+    if (in.type != TFL_U8 || in.shape.size() != 4 || in.shape[0] != 1 || in.shape[1] != in.shape[2] || in.shape[3] != 3 || in.shape[1] % 8 != 0 || in.shape[1] / 8 > 64)
+        return "classify needs a [1,S,S,3] uint8 input with S % 8 == 0";
+    if (h->m.outputs.size() < 5) return "classify reads output index 4 (yolact.rs:91): the model has fewer outputs";
+    const TflTensor& o4 = h->m.tensors[h->m.outputs[4]];
+    const int S = in.shape[1], grid = S / 8;
+    const size_t cells = (size_t)grid * grid;
+    if (o4.count() % cells != 0 || o4.count() / cells < 4 || (o4.type != TFL_U8 && o4.type != TFL_F32))
+        return "output 4 must hold (S/8)^2 cells of >= 4 uint8 or float32 logits";
+    *S_out = S; *C_out = (int)(o4.count() / cells);
+    return nullptr;
+}
+
+// A device buffer of the classify batch that only grows (the old one is freed).
+int batch_grow(yh_tfl* h, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return YH_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    if (hipMalloc(p, bytes) != hipSuccess) return h->fail(YH_ENOMEM, "hipMalloc classify batch");
+    *cap = bytes;
+    return YH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -693,12 +746,23 @@ int yh_tfl_create(const void* model_bytes, size_t nbytes, int32_t device, yh_tfl
 }
 
 int yh_tfl_create_tuned(const void* model_bytes, size_t nbytes, int32_t device, const yh_tuning* tune, yh_tfl** out) {
+    return yh_tfl_create_batch_tuned(model_bytes, nbytes, device, 2, tune, out);
+}
+
+int yh_tfl_create_batch(const void* model_bytes, size_t nbytes, int32_t device, int32_t max_images, yh_tfl** out) {
+    return yh_tfl_create_batch_tuned(model_bytes, nbytes, device, max_images, nullptr, out);
+}
+
+int yh_tfl_create_batch_tuned(const void* model_bytes, size_t nbytes, int32_t device, int32_t max_images, const yh_tuning* tune, yh_tfl** out) {
     if (!model_bytes || !out) { g_tfl_create_error = "null argument"; return YH_EINVAL; }
     *out = nullptr;
+    if (max_images < 1 || max_images > YH_TFL_MAX_IMAGES) { g_tfl_create_error = "max_images must be 1 .. " + std::to_string(YH_TFL_MAX_IMAGES); return YH_EINVAL; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_tfl_create_error = "no such HIP device (no CPU fallback)"; return YH_EHIP; }
     yh_tfl* h = new yh_tfl();
     h->dev = device;
+    h->max_images = max_images;
+    h->gexecs.assign((size_t)max_images, nullptr);
     if (tune && tune->tfl_dot >= 0) h->use_dot = tune->tfl_dot;
     if (tune && tune->tfl_graph >= 0) h->use_graph = tune->tfl_graph;
     if (tune && tune->tfl_fuse >= 0) h->use_fuse = tune->tfl_fuse;
@@ -712,6 +776,12 @@ int yh_tfl_create_tuned(const void* model_bytes, size_t nbytes, int32_t device, 
         hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess || hipMalloc(&h->side_word, 16) != hipSuccess) { h->err = "device setup failed"; return bail(YH_EHIP); }
     int rc = prepare(h);
     if (rc) return bail(rc);
+    // the int8 MFMA kernels fold the images into a 32-bit pixel index (ConvI8::M = Ho Wo nb, rounded up to a tile by the grid)
+    for (const Prepared& p : h->plan)
+        if (p.kind == P_CONV_I8 && (long long)p.conv.Ho * p.conv.Wo * max_images > INT_MAX - 64) {
+            h->err = "a convolution's output pixels times max_images exceed a 32-bit index (operator " + std::to_string(p.oi) + ")";
+            return bail(YH_EINVAL);
+        }
     h->gone.assign(h->m.tensors.size(), 0);
     if (h->use_fuse) fuse_plan(h);
     for (int i = 0; i < (int)h->plan.size(); ++i) h->order.push_back(i);
@@ -796,8 +866,10 @@ void yh_tfl_destroy(yh_tfl* h) {
     if (h->side_word) hipFree(h->side_word);
     for (size_t i = 0; i < h->tens.size(); ++i) if (h->tens[i] && !(i < h->alias.size() && h->alias[i])) hipFree(h->tens[i]);
     for (void* p : h->extra) hipFree(p);
-    void* scratch[] = { h->frame_dev, h->codes_dev, h->stitch_dev, h->tiles_dev, h->rs_tmp, h->cells_dev, h->diverged_dev };
+    void* scratch[] = { h->frame_dev, h->codes_dev, h->stitch_dev, h->tiles_dev, h->rs_tmp, h->cells_dev, h->diverged_dev,
+                        h->clsb_frames, h->clsb_cells, h->clsb_codes, h->clsb_div };
     for (void* p : scratch) if (p) hipFree(p);
+    classify_geo_free(&h->clsb_geo);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -817,7 +889,8 @@ int yh_tfl_tensor_count(const yh_tfl* h) { return h ? (int)h->m.tensors.size() :
 
 int yh_tfl_set_batch(yh_tfl* h, int32_t n_images) {
     if (!h) return YH_EINVAL;
-    if (n_images < 1 || n_images > yh_tfl::kMaxBatch) return h->fail(YH_EINVAL, "1 or 2 images per invoke");
+    if (n_images < 1 || n_images > h->max_images)
+        return h->fail(YH_EINVAL, h->max_images == 2 ? std::string("1 or 2 images per invoke") : "1 .. " + std::to_string(h->max_images) + " images per invoke (yh_tfl_create_batch's max_images)");
     if (n_images > 1 && !h->batch_ok) return h->fail(YH_EINVAL, "an operator of this model works along the image axis: one image per invoke only");
     h->nb = n_images;
     return YH_OK;
@@ -861,16 +934,10 @@ int yh_tfl_output_read(yh_tfl* h, int32_t i, void* dst, size_t nbytes) {
 int yh_tfl_classify_frame_u32(yh_tfl* h, uint32_t* frame, int32_t w, int32_t hh, int32_t mode) {
     if (!h || !frame || w < 1 || hh < 1) return YH_EINVAL;
     if (mode != YH_COMPAT_STRICT && mode != YH_COMPAT_SANE) return h->fail(YH_EINVAL, "bad compat mode");
-    const TflTensor& in = h->m.tensors[h->m.inputs[0]];
-    if (in.type != TFL_U8 || in.shape.size() != 4 || in.shape[0] != 1 || in.shape[1] != in.shape[2] || in.shape[3] != 3 || in.shape[1] % 8 != 0 || in.shape[1] / 8 > 64)
-        return h->fail(YH_EINVAL, "classify needs a [1,S,S,3] uint8 input with S % 8 == 0");
-    if (h->m.outputs.size() < 5) return h->fail(YH_EINVAL, "classify reads output index 4 (yolact.rs:91): the model has fewer outputs");
-    const TflTensor& o4 = h->m.tensors[h->m.outputs[4]];
-    const int S = in.shape[1], grid = S / 8;
+    int S = 0, C = 0;
+    if (const char* why = classify_model_check(h, &S, &C)) return h->fail(YH_EINVAL, why);
+    const int grid = S / 8;
     const size_t cells = (size_t)grid * grid;
-    if (o4.count() % cells != 0 || o4.count() / cells < 4 || (o4.type != TFL_U8 && o4.type != TFL_F32))
-        return h->fail(YH_EINVAL, "output 4 must hold (S/8)^2 cells of >= 4 uint8 or float32 logits");
-    const int C = (int)(o4.count() / cells);
     TCHK(h, hipSetDevice(h->dev));
     const size_t npx = (size_t)w * hh;
     auto grow = [&](void** p, size_t* cap, size_t bytes) { if (bytes <= *cap) return true; if (*p) hipFree(*p); *p = nullptr; *cap = 0; if (hipMalloc(p, bytes) != hipSuccess) return false; *cap = bytes; return true; };
@@ -887,7 +954,7 @@ int yh_tfl_classify_frame_u32(yh_tfl* h, uint32_t* frame, int32_t w, int32_t hh,
     TCHK(h, hipMemcpyAsync(h->frame_dev, frame, npx * 4, hipMemcpyHostToDevice, s));
     hipError_t e = launch_resize_v_u32(h->frame_dev, w, hh, h->rs_tmp, S, s);
     const int nb_saved = h->nb;
-    if (h->batch_ok) {
+    if (h->batch_ok && h->max_images >= 2) {   // (a handle made for one image per invoke - yh_tfl_create_batch(.., 1, ..) - takes the per-tile loop below)
         // yolact.rs:216-217: the two tiles are independent - they run as ONE invoke of the batch plan (the horizontal resize
         // writes them, image-major, straight into the input tensor): half the launches per frame, twice the work per launch
         if (e == hipSuccess) e = launch_resize_h(h->rs_tmp, w, S, h->tens[h->m.inputs[0]], 2 * S, 1, s);
@@ -901,7 +968,7 @@ int yh_tfl_classify_frame_u32(yh_tfl* h, uint32_t* frame, int32_t w, int32_t hh,
         if (e == hipSuccess) e = launch_resize_h(h->rs_tmp, w, S, h->tiles_dev, 2 * S, 1, s);
         if (e != hipSuccess) return h->fail(YH_EHIP, "classify pre failed");
         h->nb = 1;
-        for (int t = 0; t < 2; ++t) {   // one invoke per tile (an operator of this model works along the image axis)
+        for (int t = 0; t < 2; ++t) {   // one invoke per tile (an operator of this model works along the image axis, or the handle holds one image)
             TCHK(h, hipMemcpyAsync(h->tens[h->m.inputs[0]], h->tiles_dev + (size_t)t * S * S * 3, (size_t)S * S * 3, hipMemcpyDeviceToDevice, s));
             int rc = run_plan(h);
             if (!rc) rc = output4_to_f32(h, cells * C, h->cells_dev + (size_t)t * cells * C);
@@ -921,5 +988,71 @@ int yh_tfl_classify_frame_u32(yh_tfl* h, uint32_t* frame, int32_t w, int32_t hh,
     TCHK(h, hipMemcpy(frame, h->frame_dev, npx * 4, hipMemcpyDeviceToHost));
     return YH_OK;
 }
+
+// Yolact::classify on n frames as ONE invoke of 2n images (DESIGN.md section 11 "TFLite classify batch"): the engine's batch
+// (classify_batch.hip) with this executor in the middle - the same pre / post kernels through classify_geo.h, the same host logic.
+int yh_tfl_classify_batch_u32(yh_tfl* h, const uint32_t* frames, int32_t frames_on_device, int32_t n, int32_t w, int32_t hh, int32_t mode,
+                              uint32_t* out_host, int32_t* diverged_host) {
+    if (!h || !frames) return YH_EINVAL;
+    if (n < 1) return h->fail(YH_EINVAL, "classify batch: n_frames must be at least 1");
+    if (w < 1 || hh < 1) return h->fail(YH_EINVAL, "classify batch: bad frame size");
+    if (mode != YH_COMPAT_STRICT && mode != YH_COMPAT_SANE) return h->fail(YH_EINVAL, "bad compat mode");
+    int S = 0, C = 0;
+    if (const char* why = classify_model_check(h, &S, &C)) return h->fail(YH_EINVAL, why);
+    if (!h->batch_ok)
+        return h->fail(YH_EINVAL, "an operator of this model works along the image axis (one image per invoke): classify its frames one by one with yh_tfl_classify_frame_u32");
+    if (n > h->max_images / 2) return h->fail(YH_EINVAL, "classify batch: 2 n_frames images exceed the handle's max_images (yh_tfl_create_batch)");
+    TCHK(h, hipSetDevice(h->dev));
+    TraceRange tr("yh_tfl_classify_batch_u32");
+    const int grid = S / 8;
+    const size_t cells = (size_t)grid * grid, npx = (size_t)w * hh, nt = (size_t)2 * n;
+    const hipStream_t s = h->stream;
+    h->clsb_n = -1;   // (until this batch is complete there is none: the buffers below may move)
+    int rc;
+    if ((rc = batch_grow(h, (void**)&h->clsb_frames, &h->clsb_frames_cap, (size_t)n * npx * 4))) return rc;
+    if ((rc = batch_grow(h, (void**)&h->clsb_cells, &h->clsb_cells_cap, nt * cells * C * 4))) return rc;
+    if ((rc = batch_grow(h, (void**)&h->clsb_codes, &h->clsb_codes_cap, nt * cells * 4))) return rc;
+    if ((rc = batch_grow(h, (void**)&h->clsb_div, &h->clsb_div_cap, nt * 4))) return rc;
+    hipError_t e = classify_geo_ensure(&h->clsb_geo, w, hh, S, s);
+    if (e == hipErrorOutOfMemory) return h->fail(YH_ENOMEM, "hipMalloc classify batch tables");
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("classify batch tables: ") + hipGetErrorString(e));
+    // yolact.rs:195-214 per frame: unpack, resize_exact(2S, S), crop two tiles -> images 2b, 2b + 1 of the model's input tensor
+    const uint32_t* src = frames;
+    if (!frames_on_device) {
+        TCHK(h, hipMemcpyAsync(h->clsb_frames, frames, (size_t)n * npx * 4, hipMemcpyHostToDevice, s));
+        src = h->clsb_frames;
+    }
+    TCHK(h, classify_geo_pre(h->clsb_geo, src, n, (uint8_t*)h->tens[h->m.inputs[0]], s));
+    // yolact.rs:216-217 + :163: the 2n tiles as one invoke (the caller's yh_tfl_set_batch value survives)
+    const int nb_saved = h->nb;
+    h->nb = 2 * n;
+    rc = run_plan(h);
+    h->nb = nb_saved;
+    if (rc) return rc;
+    // yolact.rs:169-189 (results[4] as f32), :90-131, :219-233
+    if ((rc = output4_to_f32(h, nt * cells * C, h->clsb_cells))) return rc;
+    e = launch_cells_postprocess(h->clsb_cells, 2 * n, grid, C, mode, h->clsb_codes, h->clsb_div, s);
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("classify batch post: ") + hipGetErrorString(e));
+    TCHK(h, classify_geo_post(h->clsb_geo, h->clsb_codes, n, h->clsb_frames, s));
+    // the read of the 2n flags (and of the frames) and the one wait. STRICT holds the frames back until the flags are known:
+    // out_host stays untouched when a frame diverges.
+    std::vector<int> div(nt);
+    TCHK(h, hipMemcpyAsync(div.data(), h->clsb_div, nt * 4, hipMemcpyDeviceToHost, s));
+    const bool early = out_host && mode == YH_COMPAT_SANE;   // (SANE never diverges)
+    if (early) TCHK(h, hipMemcpyAsync(out_host, h->clsb_frames, (size_t)n * npx * 4, hipMemcpyDeviceToHost, s));
+    TCHK(h, hipStreamSynchronize(s));
+    bool any = false;
+    for (int b = 0; b < n; ++b) {
+        const int d = (div[2 * b] || div[2 * b + 1]) ? 1 : 0;
+        if (diverged_host) diverged_host[b] = d;
+        any = any || d;
+    }
+    if (any) return h->fail(YH_EDIVERGE, "reference flood fill (yolact.rs:57-78) does not terminate on a frame of this batch");
+    if (out_host && !early) TCHK(h, hipMemcpy(out_host, h->clsb_frames, (size_t)n * npx * 4, hipMemcpyDeviceToHost));
+    h->clsb_n = n;
+    return YH_OK;
+}
+
+const uint32_t* yh_tfl_classify_batch_device_frames(const yh_tfl* h) { return h && h->clsb_n >= 1 ? h->clsb_frames : nullptr; }
 
 }  // extern "C"

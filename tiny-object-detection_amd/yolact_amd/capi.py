@@ -129,6 +129,8 @@ SYMBOLS = [
     ("yh_tfl_validate", _i, [_vp, _sz, C.POINTER(_i), C.POINTER(_i), C.c_char_p, _sz]),
     ("yh_tfl_create", _i, [_vp, _sz, _i, C.POINTER(_vp)]),
     ("yh_tfl_create_tuned", _i, [_vp, _sz, _i, C.POINTER(Tuning), C.POINTER(_vp)]),
+    ("yh_tfl_create_batch", _i, [_vp, _sz, _i, _i, C.POINTER(_vp)]),
+    ("yh_tfl_create_batch_tuned", _i, [_vp, _sz, _i, _i, C.POINTER(Tuning), C.POINTER(_vp)]),
     ("yh_tfl_destroy", None, [_vp]),
     ("yh_tfl_last_error", C.c_char_p, [_vp]),
     ("yh_tfl_input_info", _i, [_vp, C.POINTER(TensorInfo)]),
@@ -144,6 +146,8 @@ SYMBOLS = [
     ("yh_tfl_op_info", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_tfl_tensor_read", _i, [_vp, _i, _vp, _sz]),
     ("yh_tfl_classify_frame_u32", _i, [_vp, _vp, _i, _i, _i]),
+    ("yh_tfl_classify_batch_u32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    ("yh_tfl_classify_batch_device_frames", _vp, [_vp]),
     ("yh_scene_create", _i, [_i, _i, _i, C.POINTER(_vp)]),
     ("yh_scene_destroy", None, [_vp]),
     ("yh_scene_last_error", C.c_char_p, [_vp]),
@@ -2199,6 +2203,7 @@ def tfl_validate(model_bytes):
 
 
 _KIND_NP = {1: np.float32, 3: np.uint8, 2: np.int32}
+TFL_MAX_IMAGES = 512   # YH_TFL_MAX_IMAGES
 
 # YH_TFL_FAM_* (include/yolact_hip_debug.h), by value
 TFL_FAMILIES = ("conv_scalar", "conv_px8", "conv_dot1", "conv_dot4", "conv_i8_lds", "conv_i8_direct", "dw_scalar", "dw_c4",
@@ -2217,11 +2222,13 @@ def tfl_direct_forms():
 class TfliteEngine:
     """RAII wrapper of yh_tfl: the reference's own model family (uint8 MobileNetV2-style .tflite)."""
 
-    def __init__(self, model_bytes, device=0, tune=None):
+    def __init__(self, model_bytes, device=0, tune=None, max_images=2):
+        """max_images: images per invoke the handle has room for (yh_tfl_create_batch: 1 .. TFL_MAX_IMAGES; classify_batch on n frames
+        needs 2n)."""
         self.L = load_library()
         h = C.c_void_p()
         t = Tuning.of(**(tune or {}))
-        rc = self.L.yh_tfl_create_tuned(model_bytes, len(model_bytes), device, C.byref(t), C.byref(h))
+        rc = self.L.yh_tfl_create_batch_tuned(model_bytes, len(model_bytes), device, int(max_images), C.byref(t), C.byref(h))
         if rc != OK:
             raise YhError(rc, self.L.yh_tfl_last_error(None).decode())
         self.h = h
@@ -2256,7 +2263,7 @@ class TfliteEngine:
         return self._info(ti)
 
     def set_batch(self, n):
-        """1 or 2 images per invoke (the two tiles of a frame as one pass); inputs / outputs / tensors then carry n images."""
+        """1 .. max_images images per invoke (the two tiles of a frame as one pass); inputs / outputs / tensors then carry n images."""
         self._chk(self.L.yh_tfl_set_batch(self.h, n))
         self.nb = n
 
@@ -2296,3 +2303,40 @@ class TfliteEngine:
     def classify_frame(self, frame_u32, width, height, mode=COMPAT_STRICT):
         assert frame_u32.dtype == np.uint32 and frame_u32.flags.c_contiguous and frame_u32.size == width * height
         self._chk(self.L.yh_tfl_classify_frame_u32(self.h, _p(frame_u32), width, height, mode))
+
+    def classify_batch(self, frames_u32=None, frames_dev_ptr=None, n=None, width=640, height=480, mode=COMPAT_STRICT, out=None,
+                       read=True):
+        """yh_tfl_classify_batch_u32: classify on n frames as one invoke of 2n images (DESIGN.md §11 "TFLite classify batch"; the
+        handle needs max_images >= 2n). frames_u32: uint32 [n][height][width] on the host (n defaults to its first dimension), or
+        frames_dev_ptr: a device pointer to the same layout with n given. out: the uint32 array to write, which may be frames_u32
+        itself; None: a new array, or with read=False nothing is copied back. Returns (frames uint32 [n][height][width] or None;
+        diverged int32 [n]), like Engine.classify_batch. On YH_EDIVERGE the YhError carries the flags as .diverged. The device
+        copy: classify_batch_device_frames."""
+        assert (frames_u32 is None) != (frames_dev_ptr is None), "give frames_u32 or frames_dev_ptr"
+        if frames_u32 is not None:
+            src = np.ascontiguousarray(frames_u32, np.uint32)
+            if n is None:
+                n = src.shape[0]
+            assert src.size >= max(int(n), 0) * width * height, (src.shape, n, width, height)
+            ptr, on_dev = _p(src), 0
+        else:
+            assert n is not None, "frames_dev_ptr needs n"
+            ptr, on_dev = C.c_void_p(frames_dev_ptr), 1
+        if out is not None:   # the array to write (it may be frames_u32 itself: in place)
+            assert out.dtype == np.uint32 and out.flags.c_contiguous and out.size == int(n) * width * height
+            res = out
+        else:
+            res = np.zeros((max(int(n), 0), height, width), np.uint32) if read else None
+        div = np.zeros(max(int(n), 1), np.int32)
+        try:
+            self._chk(self.L.yh_tfl_classify_batch_u32(self.h, ptr, on_dev, int(n), width, height, mode,
+                                                       _p(res) if res is not None else None, _p(div)))
+        except YhError as e:
+            e.diverged = div[:max(int(n), 0)].copy()
+            raise
+        return res, div[:int(n)]
+
+    def classify_batch_device_frames(self):
+        """Device pointer of the last classify_batch's frames [n][height][width] (None before a batch or after a failed one): what
+        SceneBatch.stage_frames(frames_dev_ptr=...) takes."""
+        return self.L.yh_tfl_classify_batch_device_frames(self.h)

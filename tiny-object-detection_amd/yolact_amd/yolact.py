@@ -19,7 +19,8 @@ class Yolact:
         """reference: `Yolact::init()` (src/yolact.rs:17-37), which hard-codes
         "data/FRC_model_edgetpu.tflite". Here:
           * model_path = a non-EdgeTPU .tflite (the reference's data/FRC_model.tflite family: uint8
-            MobileNetV2-style graph) -> the TFLite model path runs it on the GPU;
+            MobileNetV2-style graph) -> the TFLite model path runs it on the GPU, with room for max_batch images per
+            invoke (TfliteEngine's max_images; classify_batch on n frames needs 2n);
           * otherwise the YOLACT R50/R101 engine at `input_size` (224 = the reference's tile,
             yolact.rs:143-144) with `weights` (a YHW1 blob) or the seeded synthetic blob; max_batch tiles
             per step (classify_batch on n frames needs 2n).
@@ -28,7 +29,7 @@ class Yolact:
             if not os.path.exists(model_path):
                 raise FileNotFoundError(f"failed to load model: {model_path}")   # yolact.rs:20
             with open(model_path, "rb") as f:
-                return cls(TfliteEngine(f.read(), device=device), compat_mode)
+                return cls(TfliteEngine(f.read(), device=device, max_images=max(2, max_batch)), compat_mode)
         eng = Engine(input_size=input_size, backbone=backbone, max_batch=max_batch, use_graph=True, device=device)
         eng.load_weights(weights if weights is not None else eng.generate_weights(seed))
         return cls(eng, compat_mode)
@@ -41,7 +42,7 @@ class Yolact:
 
     def classify_batch(self, frames, width=640, height=480):
         """classify on n frames at once, in place on a uint32 [n][height * width] array: one network step of 2n tiles
-        (Engine.classify_batch; the engine needs max_batch >= 2n). Returns the per-frame divergence flags (all zero)."""
+        (Engine.classify_batch or TfliteEngine.classify_batch; the handle needs max_batch >= 2n). Returns the per-frame divergence flags (all zero)."""
         assert isinstance(frames, np.ndarray) and frames.dtype == np.uint32 and frames.flags.c_contiguous
         n = frames.size // (width * height)
         _, diverged = self.interpreter.classify_batch(frames_u32=frames, n=n, width=width, height=height, mode=self.compat_mode,

@@ -14,10 +14,54 @@ import tfl_builder as B, tfl_models as M
 ap = argparse.ArgumentParser()
 ap.add_argument("--graph", type=int, default=-1, help="yh_tuning.tfl_graph: 1 = hipGraph replay of the plan, 0 = eager launches, -1 = library default")
 ap.add_argument("--invokes", type=int, default=220)
+ap.add_argument("--batch", action="store_true", help="the classify batch (yh_tfl_classify_batch_u32): ms per 640x480 frame for n = 1 .. 32 frames, three paths alternated in one process (profiles/tfl_classify_batch_timings.txt)")
 a = ap.parse_args()
 rng = np.random.default_rng(0)
 model = M.mobilenetv2_yolact(rng)
 buf = bytes(B.serialize(model))
+
+
+def clock(fn):
+    t0 = time.perf_counter(); fn(); return (time.perf_counter() - t0) * 1e3
+
+
+def batch_arm():
+    """ms per frame of n frames, 640x480: classify_batch host in / host out; classify_batch from a device pointer with read=False;
+    n single classify_frame calls. One handle (max_images = 64); per n the three paths alternate `rounds` times, medians reported."""
+    import ctypes as C
+    W, H, rounds = 640, 480, 15
+    eng = ya.TfliteEngine(buf, max_images=64)
+    hip = C.CDLL(next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64.so" in ln))
+    frames = rng.integers(0, 2 ** 32, (32, H, W), dtype=np.uint64).astype(np.uint32)
+    dev = C.c_void_p()
+    assert hip.hipMalloc(C.byref(dev), C.c_size_t(frames.nbytes)) == 0
+    assert hip.hipMemcpy(dev, frames.ctypes.data_as(C.c_void_p), C.c_size_t(frames.nbytes), 1) == 0
+    out, one = np.empty_like(frames), np.empty(W * H, np.uint32)
+    print(f"tflite classify batch, {len(model.ops)}-op stand-in (S = 224), frames {W}x{H}, COMPAT_SANE; ms per frame, median of {rounds} alternated rounds (min .. max)")
+    print(f"{'n':>3} {'batch host->host':>26} {'batch device->device':>26} {'n x classify_frame':>26} {'host/single':>12}")
+    for n in (1, 2, 4, 8, 16, 32):
+        def host(): eng.classify_batch(frames_u32=frames[:n], n=n, width=W, height=H, mode=ya.COMPAT_SANE, out=out[:n])
+        def device(): eng.classify_batch(frames_dev_ptr=dev.value, n=n, width=W, height=H, mode=ya.COMPAT_SANE, read=False)
+        def single():   # (the single call works in place: its buffer is refilled outside the clock, only the n calls are timed)
+            total = 0.0
+            for b in range(n):
+                one[:] = frames[b].reshape(-1)
+                total += clock(lambda: eng.classify_frame(one, W, H, ya.COMPAT_SANE))
+            return total
+        for _ in range(3):
+            host(); device(); single()
+        assert np.array_equal(out[n - 1].reshape(-1), one)      # (frame n - 1 of the batch is the single call's)
+        t = np.array([[clock(host), clock(device), single()] for _ in range(rounds)]) / n
+        med, lo, hi = np.median(t, 0), t.min(0), t.max(0)
+        cols = [f"{med[k]:8.3f} ({lo[k]:6.3f} .. {hi[k]:6.3f})" for k in range(3)]
+        print(f"{n:3d} {cols[0]:>26} {cols[1]:>26} {cols[2]:>26} {med[0] / med[2]:12.3f}")
+    hip.hipFree(dev)
+    eng.close()
+
+
+if a.batch:
+    batch_arm()
+    sys.exit(0)
 eng = ya.TfliteEngine(buf, tune=dict(tfl_graph=a.graph))
 x = rng.integers(0, 256, (1, 224, 224, 3), dtype=np.uint8)
 def invoke():
