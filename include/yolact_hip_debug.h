@@ -59,7 +59,7 @@ typedef struct yh_tuning {
                               * graph as ONE launch (the prediction head's convolutions over the pyramid levels: 23 launches become 3), the
                               * plan in depth order; 0: one launch per convolution in file order. Same bytes */
     int32_t op_xgap;         /* single-op conv entry points: the staged input keeps this many extra f16 elements (a multiple of 8,
-                              * filled with ones) behind every image, so x_img_stride is not the dense H * W * C (0: dense) */
+                              * filled with NaN, 0x7E00) behind every image, so x_img_stride is not the dense H * W * C (0: dense) */
     int32_t op_tanh_from;    /* single-op conv entry points with act = 2: tanh on the channels from this one on (0: all of them) */
     int32_t reserved[15];    /* ignored by the library (the slots of retired fields: DESIGN.md §9) */
 } yh_tuning;
@@ -350,7 +350,7 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
  * q stride2)) together with w1n. a_next is written iff w1n is given. planes 256, tile_m 64: bneck_xn_f16 - a IS b, [n][hh][ww][256]
  * (w2, bias2, stride unused), res and w1n required, and a' goes to a_next and / or, as E4M3 codes of a' * inv_scale[channel],
  * to a_next8 [M][256] (at least one of the two). YH_EINVAL with a message, and no launch, for a combination launch_bneck has no
- * kernel for. tune.op_xgap: every image of a is followed by that many elements of 1.0 (chains only: bneck_xn_f16 reads dense
+ * kernel for. tune.op_xgap: every image of a is followed by that many elements of NaN (chains only: bneck_xn_f16 reads dense
  * rows and refuses a gap). Every output is staged with 256 guard rows of 0xFF behind row M - 1: YH_EOVERFLOW with a message if the
  * launch changed one of their bytes. */
 int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t* a, int32_t n, int32_t hh, int32_t ww,

@@ -219,7 +219,7 @@ def f16(a):
 
 
 def _act(v, act):
-    return np.maximum(v, 0) if act else v
+    return np.where(v > 0, v, 0.0) if act else v       # (the spec's v > 0 ? v : 0: a NaN becomes 0; np.maximum would keep it)
 
 
 def dual_cat(c, t):

@@ -7,7 +7,7 @@ Shapes are the smallest that cross each boundary: 3 frames of 5 x 7 and of 9 x 9
 rows of two frames share a tile; pyramid levels 5, 3, 2, 1, 1 (all five level boundaries inside one tile).
 
 Two test switches of the single-op conv entry points reach what a plain call cannot: tune.op_xgap stages every image with extra
-elements (ones) behind it - a non-dense image stride, which must NOT take the m * C form - and tune.op_tanh_from sets the first
+elements (NaN) behind it - a non-dense image stride, which must NOT take the m * C form - and tune.op_tanh_from sets the first
 tanh channel (inside, at the edge of, beyond a channel tile). The forms no single op expresses run through small engines, each
 compared bit for bit with the engine form that does not use the kernel path under test: the upsampled residual (3 x 3 -> 5 x 5
 and 18 x 18 -> 35 x 35, against bilinear + add: tune.upfuse = 0), the head (tanh from channel 255, non-dense output strides)
@@ -66,7 +66,7 @@ def test_conv_rows_exact_on_integers(eng, oracle, tile, n, h, w, k, stride, pad)
 @pytest.mark.parametrize("tile", PLAIN_TILES)
 @pytest.mark.parametrize("xgap", [8, 200])
 def test_1x1_with_a_non_dense_image_stride_exact_on_integers(eng, oracle, tile, n, h, w, xgap):
-    """A 1x1, stride-1, unpadded conv whose input images lie xgap elements apart more than H * W * C (the gap holds ones): row m's
+    """A 1x1, stride-1, unpadded conv whose input images lie xgap elements apart more than H * W * C (the gap holds NaN): row m's
     source is n * x_img_stride + rem * C, not m * C. The streaming tiles must take their general form - with the dense form's
     offsets every row of the second and third frame would read shifted data or the gap - and every tile must match the oracle."""
     rng = np.random.default_rng(tile + xgap + h)

@@ -99,13 +99,14 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     const int coutPad = round_up(cout, conv_tile_ch(tile)), cout8 = round_up(cout, 8);
     const size_t M = (size_t)n * P * Q;
     // host-side staging: pad input channels, repack weights, pad output rows to cout8
-    // (test hook, tune.op_xgap: every image is followed by `gap` elements of 1.0, so the image stride is not the dense H * W * C)
+    // (test hook, tune.op_xgap: every image is followed by `gap` elements of NaN (0x7E00), so the image stride is not the dense
+    // H * W * C and a gap element that contributed to any sum, even times a zero weight, would show in the output)
     const int gap = h->tune.op_xgap;
     if (gap % 8 != 0) return h->fail(YH_EINVAL, "conv op: tune.op_xgap must be a multiple of 8");
     const size_t img = (size_t)hh * ww * cs;
     std::vector<uint16_t> xs = pad_rows(x, (size_t)n * hh * ww, cin, cs);
     if (gap > 0) {
-        std::vector<uint16_t> g((img + gap) * n, 0x3C00);
+        std::vector<uint16_t> g((img + gap) * n, 0x7E00);
         for (int b = 0; b < n; ++b) memcpy(&g[b * (img + gap)], &xs[b * img], img * 2);
         xs.swap(g);
     }
@@ -236,7 +237,7 @@ int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t
     constexpr size_t kGuardRows = 256;
     const int C4 = 4 * planes, C2 = dual ? 64 : 0;
     const size_t M = (size_t)n * P * Q, img = (size_t)hh * ww * planes, n2 = dual ? (size_t)n * h2 * w2w * 64 : 0;
-    std::vector<uint16_t> as((img + gap) * n, 0x3C00);   // (test hook, tune.op_xgap: ones behind every image)
+    std::vector<uint16_t> as((img + gap) * n, 0x7E00);   // (test hook, tune.op_xgap: NaN behind every image)
     for (int b = 0; b < n; ++b) memcpy(&as[b * (img + gap)], &a[b * img], img * 2);
     const size_t ny = M * C4, nan_ = M * planes, gy = kGuardRows * C4, ga = kGuardRows * planes;
     OpStaging st;
