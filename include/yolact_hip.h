@@ -40,7 +40,7 @@ enum {
 enum { YH_BACKBONE_R50 = 50, YH_BACKBONE_R101 = 101 };
 
 /* Output tensor element kinds; mirrors tflite::context::ElementKind as used at src/yolact.rs:171-186. */
-enum { YH_KIND_F32 = 1, YH_KIND_U8 = 3, YH_KIND_F16 = 10 };
+enum { YH_KIND_F32 = 1, YH_KIND_U8 = 3, YH_KIND_I8 = 9, YH_KIND_F16 = 10 };   /* (I8: an int8 tensor of a TFLite model; its bytes are read as they are) */
 
 /* Reference-compat behaviour of yh_classify_frame_u32. */
 enum {
@@ -421,7 +421,11 @@ int yh_resize_triangle_rgb8(yh_engine* h, const uint8_t* src_host, int32_t sw, i
 
 /* ---- TFLite model path: run the reference's own model family ---------------- */
 /* A user who holds data/FRC_model.tflite (uint8 per-tensor quantised MobileNetV2-FPN YOLACT,
- * data/README.md:5-16; absent from the checkout) runs it here instead of tflite+EdgeTPU. Supported
+ * data/README.md:5-16; absent from the checkout) runs it here instead of tflite+EdgeTPU - and so does
+ * one who converts such a model today: int8 tensors, int8 weights with zero point 0 and one scale per
+ * tensor or per output channel, uint8 or float32 at the graph's edges behind QUANTIZE / DEQUANTIZE
+ * (DESIGN.md section 11 "TFLite int8"; classify still asks for a uint8 input and a uint8 or float32
+ * output 4, as yolact.rs:171-186 does). Supported
  * builtin ops: the histogram of data/FRC_model_edgetpu.log:7-19 (CONV_2D, DEPTHWISE_CONV_2D, ADD,
  * PAD, RESIZE_BILINEAR, TANH, RELU, CONCATENATION, RESHAPE, QUANTIZE) plus RELU6 and DEQUANTIZE.
  * The EdgeTPU-compiled file is one custom op and is rejected with a message naming it. */

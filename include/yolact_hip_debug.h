@@ -112,7 +112,10 @@ int yh_tfl_plan_info(const yh_tfl* h, int32_t* launches, int32_t* conv_launches,
  * yh_tfl_op_info: operator `op` of the model (file order) in the handle's plan, for the image count of the next invoke: its kernel
  * family (below; the answer of the same functions the launches ask), the row of the table of forms it runs (-1: not register-fed),
  * whether it is launched as a member of a group, and whether it is folded into another launch (then it has no launch of its own;
- * a RESHAPE that shares its input's buffer reports YH_TFL_FAM_NONE, folded). Any of the four pointers may be NULL. */
+ * a RESHAPE that shares its input's buffer reports YH_TFL_FAM_NONE, folded). Any of the four pointers may be NULL.
+ * yh_tfl_op_quant: the type of the operator's output - 0 uint8, 1 int8, -1 any other - and whether it is an int8 convolution whose
+ * weights carry one scale per output channel (its launch reads a multiplier table either way; with a single scale the entries are
+ * equal and 0 is reported). Both pointers may be NULL. */
 enum {
     YH_TFL_FAM_NONE = -1,
     YH_TFL_FAM_CONV_SCALAR = 0, YH_TFL_FAM_CONV_PX8 = 1, YH_TFL_FAM_CONV_DOT1 = 2, YH_TFL_FAM_CONV_DOT4 = 3,
@@ -122,6 +125,7 @@ enum {
 };
 int yh_tfl_direct_forms(int32_t* rows, int32_t cap);
 int yh_tfl_op_info(const yh_tfl* h, int32_t op, int32_t* family, int32_t* form_row, int32_t* grouped, int32_t* folded);
+int yh_tfl_op_quant(const yh_tfl* h, int32_t op, int32_t* signed_act, int32_t* per_channel);
 
 int yh_tfl_tensor_count(const yh_tfl* h);
 

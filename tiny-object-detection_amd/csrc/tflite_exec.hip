@@ -1,5 +1,6 @@
 // tflite_exec.hip — executes a parsed TFLite model (uint8 per-tensor quantised MobileNetV2-style
-// graphs: the reference's FRC_model.tflite family, data/README.md:5-16) on the GPU.
+// graphs: the reference's FRC_model.tflite family, data/README.md:5-16 - and what today's converter writes of it: int8
+// tensors, per-channel weight scales, uint8 at the edges; DESIGN.md section 11 "TFLite int8") on the GPU.
 //
 // SURVEY.md §8f-1. Replaces, for a user who holds the reference's model file, the whole of
 // interpreter.invoke() (src/yolact.rs:163) plus the surrounding classify
@@ -40,12 +41,14 @@ void quantize_multiplier(double m, int* mult, int* shift) {
     if (e < -31) { e = 0; qf = 0; }
     *mult = (int)qf; *shift = e;
 }
-void act_range(int act, float scale, int zp, int* lo, int* hi) {
+// (sgn: the output is int8 - the type range is [-128, 127] instead of [0, 255])
+void act_range(int act, float scale, int zp, int* lo, int* hi, bool sgn = false) {
     auto q = [&](float v) { const float d = v / scale; return zp + (int)(d >= 0 ? floorf(d + 0.5f) : ceilf(d - 0.5f)); };
-    *lo = 0; *hi = 255;
-    if (act == 1) { *lo = q(0.0f) > 0 ? q(0.0f) : 0; }
-    else if (act == 3) { *lo = q(0.0f) > 0 ? q(0.0f) : 0; *hi = q(6.0f) < 255 ? q(6.0f) : 255; }
-    else if (act == 2) { *lo = q(-1.0f) > 0 ? q(-1.0f) : 0; *hi = q(1.0f) < 255 ? q(1.0f) : 255; }
+    const int tlo = sgn ? -128 : 0, thi = sgn ? 127 : 255;
+    *lo = tlo; *hi = thi;
+    if (act == 1) { *lo = q(0.0f) > tlo ? q(0.0f) : tlo; }
+    else if (act == 3) { *lo = q(0.0f) > tlo ? q(0.0f) : tlo; *hi = q(6.0f) < thi ? q(6.0f) : thi; }
+    else if (act == 2) { *lo = q(-1.0f) > tlo ? q(-1.0f) : tlo; *hi = q(1.0f) < thi ? q(1.0f) : thi; }
 }
 void same_pad(int in, int k, int stride, int dil, int* out, int* before) {
     *out = (in + stride - 1) / stride;
@@ -66,6 +69,7 @@ struct Prepared {
     std::vector<CatQ> cat;
     const void* src = nullptr; void* dst = nullptr; long long n = 0;
     int zi = 0, zo = 0, m = 0, s = 0, lo = 0, hi = 255; float scale = 1.0f;
+    bool sgn_in = false, sgn_out = false;   // element-wise entries: the input / the output is int8 (a QUANTIZE may change type)
     const uint8_t* lut = nullptr;
 };
 
@@ -146,6 +150,9 @@ struct OpPrep {
     yh_tfl* h; const TflOp& op; size_t oi;
     const TflTensor& T(int i) const { return h->m.tensors[i]; }
     bool u8(int i) const { return T(i).type == TFL_U8 && T(i).quant; }
+    bool i8(int i) const { return T(i).type == TFL_I8 && T(i).quant; }
+    bool q8(int i) const { return u8(i) || i8(i); }
+    bool same8(int a, int b) const { return q8(a) && T(a).type == T(b).type && T(b).quant; }   // both uint8 or both int8
     void* dev(int i) const { return h->tens[i]; }
     int bad(const std::string& what) const { return h->fail(YH_EINVAL, what + " (operator " + std::to_string(oi) + ")"); }
     // CONV_2D / DEPTHWISE_CONV_2D: the record, and what the kernel form that tfl_dot selects needs beside it in device memory
@@ -154,9 +161,12 @@ struct OpPrep {
         const TflTensor &x = T(op.in[0]), &w = T(op.in[1]), &y = T(op.out[0]);
         const bool dw = op.code == TFL_DEPTHWISE_CONV_2D;
         const int bi = op.in.size() > 2 ? op.in[2] : -1;
-        if (!(u8(op.in[0]) && u8(op.in[1]) && u8(op.out[0]) && x.shape.size() == 4 && w.shape.size() == 4 && y.shape.size() == 4 &&
-              x.shape[0] == 1 && (bi < 0 || (T(bi).type == TFL_I32 && T(bi).data)) && w.data))
-            return bad("conv: only uint8 per-tensor quantised NHWC batch-1 convolutions with constant weights are supported");
+        if (u8(op.in[0]) && w.per_channel()) return bad("conv: uint8 activations with per-channel weight scales are not supported");
+        if (i8(op.in[0]) && u8(op.in[1])) return bad("conv: int8 activations with uint8 weights are not supported");
+        const bool sgn = i8(op.in[0]);   // int8 activations, symmetric int8 weights (the reader has checked their zero points), int8 output
+        if (!(((u8(op.in[0]) && u8(op.in[1]) && u8(op.out[0])) || (sgn && i8(op.in[1]) && i8(op.out[0]))) && x.shape.size() == 4 && w.shape.size() == 4 &&
+              y.shape.size() == 4 && x.shape[0] == 1 && (bi < 0 || (T(bi).type == TFL_I32 && T(bi).data)) && w.data))
+            return bad("conv: only uint8 per-tensor, or int8 with int8 per-tensor / per-channel weights, quantised NHWC batch-1 convolutions with constant weights are supported");
         ConvQ& c = pr.conv;
         c.H = x.shape[1]; c.W = x.shape[2]; c.Ci = x.shape[3];
         c.kh = w.shape[1]; c.kw = w.shape[2];
@@ -173,17 +183,34 @@ struct OpPrep {
         c.zx = x.zp; c.zw = w.zp; c.zo = y.zp;
         c.xs = (long long)c.H * c.W * c.Ci; c.ys = (long long)c.Ho * c.Wo * c.Co;
         quantize_multiplier((double)x.scale * (double)w.scale / (double)y.scale, &c.mult, &c.shift);
-        act_range(op.act, y.scale, y.zp, &c.lo, &c.hi);
+        act_range(op.act, y.scale, y.zp, &c.lo, &c.hi, sgn);
         pr.kind = dw ? P_DW : P_CONV;
+        const int CoPad = (c.Co + 63) / 64 * 64;
+        if (sgn) {   // one multiplier per output channel (a single weight scale: all equal), padded like the MFMA kernels' cterm
+            std::vector<int> mt(CoPad, 0), st(CoPad, 0);
+            for (int oc = 0; oc < c.Co; ++oc)
+                quantize_multiplier((double)x.scale * (double)(w.per_channel() ? w.scales[oc] : w.scale) / (double)y.scale, &mt[oc], &st[oc]);
+            if (int rc = upload(h, mt.data(), mt.size(), "multiplier table", &c.mtab)) return rc;
+            if (int rc = upload(h, st.data(), st.size(), "shift table", &c.stab)) return rc;
+            c.sgn = 1;
+        }
         if (!dw && h->use_dot >= 2 && c.Ci % (h->use_dot >= 3 ? 4 : 64) == 0 && (((size_t)c.x) & 3) == 0 && (long long)c.kh * c.kw * c.Ci < 131072) {
             // int8 MFMA form: the weight panel as int8 (w ^ 0x80) padded to 64-channel tiles, and per channel
             //   cterm = (128 - zx) sum(w - 128) + K (128 - zx)(128 - zw) + bias   (all exact in int32: |.| < 2^31 for K < 2^17)
-            const int K = c.kh * c.kw * c.Ci, CoPad = (c.Co + 63) / 64 * 64;
-            std::vector<uint8_t> wq((size_t)CoPad * K + 16, 0x80);   // padding rows: w' = 0 (+ 16 bytes: the register-fed kernel's last load of a row may reach past it)
+            // int8 (sgn), the native form: the weight bytes as they are and cterm = bias - zx sum(w), computed in 64 bits and kept modulo
+            //   2^32 - which is all the kernel's int32 accumulator keeps of sum(x w) too, so the sum of the two is TFLite's value
+            //   whenever TFLite's own accumulator does not overflow
+            const int K = c.kh * c.kw * c.Ci;
+            std::vector<uint8_t> wq((size_t)CoPad * K + 16, sgn ? 0x00 : 0x80);   // padding rows: w' = 0 (+ 16 bytes: the register-fed kernel's last load of a row may reach past it)
             std::vector<int> ct(CoPad, 0);
             const int* bias_h = bi >= 0 ? (const int*)T(bi).data : nullptr;
             for (int oc = 0; oc < c.Co; ++oc) {
                 long long sw = 0;
+                if (sgn) {
+                    for (int k = 0; k < K; ++k) { const uint8_t b = w.data[(size_t)oc * K + k]; wq[(size_t)oc * K + k] = b; sw += (int)(int8_t)b; }
+                    ct[oc] = (int)(uint32_t)(uint64_t)((long long)(bias_h ? bias_h[oc] : 0) - (long long)c.zx * sw);
+                    continue;
+                }
                 for (int k = 0; k < K; ++k) { const uint8_t b = w.data[(size_t)oc * K + k]; wq[(size_t)oc * K + k] = (uint8_t)(b ^ 0x80); sw += (int)b - 128; }
                 ct[oc] = (int)((128 - c.zx) * sw + (long long)K * (128 - c.zx) * (128 - c.zw) + (bias_h ? bias_h[oc] : 0));
             }
@@ -193,7 +220,7 @@ struct OpPrep {
             if (h->use_dot >= 3 && (pr.form = conv_i8_direct_form(c.kh, c.kw, c.Ci)) < 0) return bad("conv: the register-fed kernel has no form for this extent and depth");
             return YH_OK;
         }
-        if (!dw && h->use_dot && c.Ci % 4 == 0 && (long long)c.kh * c.kw * c.Ci * 65025ll < (1ll << 31)) {
+        if (!dw && !sgn && h->use_dot && c.Ci % 4 == 0 && (long long)c.kh * c.kw * c.Ci * 65025ll < (1ll << 31)) {
             // per (channel, tap) sums of the raw weight bytes for the dot-product kernel
             const int ntaps = c.kh * c.kw;
             std::vector<int> ws((size_t)c.Co * ntaps, 0);
@@ -209,9 +236,9 @@ struct OpPrep {
         return YH_OK;
     }
     int add(Prepared& pr) const {
-        if (!(op.in.size() == 2 && u8(op.in[0]) && u8(op.in[1]) && u8(op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count() &&
+        if (!(op.in.size() == 2 && same8(op.in[0], op.in[1]) && same8(op.in[0], op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count() &&
               T(op.in[1]).count() == T(op.out[0]).count()))
-            return bad("add: only same-shape uint8 tensors are supported");
+            return bad("add: only same-shape tensors of one type, uint8 or int8, are supported");
         const TflTensor &a = T(op.in[0]), &b = T(op.in[1]), &y = T(op.out[0]);
         AddQ& q = pr.add; pr.kind = P_ADD;
         q.a = (const uint8_t*)dev(op.in[0]); q.b = (const uint8_t*)dev(op.in[1]); q.y = (uint8_t*)dev(op.out[0]);
@@ -220,46 +247,57 @@ struct OpPrep {
         quantize_multiplier((double)a.scale / twice, &q.m1, &q.s1);
         quantize_multiplier((double)b.scale / twice, &q.m2, &q.s2);
         quantize_multiplier(twice / ((double)(1 << 20) * (double)y.scale), &q.mo, &q.so);
-        act_range(op.act, y.scale, y.zp, &q.lo, &q.hi);
+        q.sgn = i8(op.out[0]) ? 1 : 0;
+        act_range(op.act, y.scale, y.zp, &q.lo, &q.hi, q.sgn != 0);
         return YH_OK;
     }
-    // RELU / RELU6 / QUANTIZE: a requantisation of uint8, or QUANTIZE of float32
+    // RELU / RELU6 / QUANTIZE: a requantisation of uint8 or int8 (QUANTIZE: to either type), or QUANTIZE of float32
     int requant(Prepared& pr) const {
-        if (!(op.in.size() == 1 && op.out.size() == 1 && u8(op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count())) return bad("quantize/relu: bad tensors");
+        if (!(op.in.size() == 1 && op.out.size() == 1 && q8(op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count())) return bad("quantize/relu: bad tensors");
         const TflTensor &x = T(op.in[0]), &y = T(op.out[0]);
         pr.src = dev(op.in[0]); pr.dst = dev(op.out[0]); pr.n = (long long)y.count();
+        pr.sgn_in = i8(op.in[0]); pr.sgn_out = i8(op.out[0]);
         if (x.type == TFL_F32 && op.code == TFL_QUANTIZE) { pr.kind = P_QUANT_F32; pr.scale = y.scale; pr.zo = y.zp; return YH_OK; }
-        if (!u8(op.in[0])) return bad("quantize/relu: input must be float32 or quantised uint8");
+        if (!q8(op.in[0])) return bad("quantize/relu: input must be float32 or quantised uint8 / int8");
+        if (op.code != TFL_QUANTIZE && pr.sgn_in != pr.sgn_out) return bad("relu: input and output must be of one type");
         pr.kind = P_REQUANT; pr.zi = x.zp; pr.zo = y.zp;
         quantize_multiplier((double)x.scale / (double)y.scale, &pr.m, &pr.s);
-        act_range(op.code == TFL_RELU ? 1 : (op.code == TFL_RELU6 ? 3 : 0), y.scale, y.zp, &pr.lo, &pr.hi);
+        act_range(op.code == TFL_RELU ? 1 : (op.code == TFL_RELU6 ? 3 : 0), y.scale, y.zp, &pr.lo, &pr.hi, pr.sgn_out);
         return YH_OK;
     }
     int dequant(Prepared& pr) const {
-        if (!(op.in.size() == 1 && u8(op.in[0]) && T(op.out[0]).type == TFL_F32 && T(op.in[0]).count() == T(op.out[0]).count())) return bad("dequantize: bad tensors");
+        if (!(op.in.size() == 1 && q8(op.in[0]) && T(op.out[0]).type == TFL_F32 && T(op.in[0]).count() == T(op.out[0]).count())) return bad("dequantize: bad tensors");
         pr.kind = P_DEQUANT; pr.src = dev(op.in[0]); pr.dst = dev(op.out[0]); pr.n = (long long)T(op.out[0]).count();
-        pr.scale = T(op.in[0]).scale; pr.zi = T(op.in[0]).zp;
+        pr.scale = T(op.in[0]).scale; pr.zi = T(op.in[0]).zp; pr.sgn_in = i8(op.in[0]);
         return YH_OK;
     }
     int tanh_table(Prepared& pr) const {
-        if (!(op.in.size() == 1 && u8(op.in[0]) && u8(op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count())) return bad("tanh: only uint8 is supported");
+        if (!(op.in.size() == 1 && same8(op.in[0], op.out[0]) && T(op.in[0]).count() == T(op.out[0]).count())) return bad("tanh: only uint8 -> uint8 and int8 -> int8 are supported");
         const TflTensor &x = T(op.in[0]), &y = T(op.out[0]);
-        uint8_t lut[256];
+        const bool sgn = i8(op.in[0]);
+        // uint8: entry q of 256. int8: one entry per value q in [-128, 127], stored at index q AND at its raw byte's index q + 256 -
+        // 384 entries from index -128, `lut` pointing at index 0: the kernel's byte and a folded chain's true integer find the same one
+        uint8_t lut[384];
         const float inv = 1.0f / y.scale;
-        for (int q = 0; q < 256; ++q) {   // PopulateLookupTable<uint8_t>
+        const int first = sgn ? -128 : 0, tlo = sgn ? -128 : 0, thi = sgn ? 127 : 255;
+        for (int i = first; i < 256; ++i) {   // PopulateLookupTable
+            const int q = sgn && i > 127 ? i - 256 : i;
             const float xv = x.scale * (float)(q - x.zp);
             const float yv = (float)tanh((double)xv);
             const float r = yv * inv;
             const int rr = (int)(r >= 0 ? floorf(r + 0.5f) : ceilf(r - 0.5f)) + y.zp;
-            lut[q] = (uint8_t)(rr < 0 ? 0 : (rr > 255 ? 255 : rr));
+            lut[i - first] = (uint8_t)(rr < tlo ? tlo : (rr > thi ? thi : rr));
         }
         pr.kind = P_LUT; pr.src = dev(op.in[0]); pr.dst = dev(op.out[0]); pr.n = (long long)y.count();
-        return upload(h, lut, 256, "tanh table", &pr.lut);
+        pr.sgn_in = pr.sgn_out = sgn;
+        if (int rc = upload(h, lut, (size_t)(256 - first), "tanh table", &pr.lut)) return rc;
+        pr.lut -= first;
+        return YH_OK;
     }
     int pad(Prepared& pr) const {
-        if (!(op.in.size() == 2 && u8(op.in[0]) && u8(op.out[0]) && T(op.in[1]).type == TFL_I32 && T(op.in[1]).data &&
+        if (!(op.in.size() == 2 && same8(op.in[0], op.out[0]) && T(op.in[1]).type == TFL_I32 && T(op.in[1]).data &&
               T(op.in[0]).shape.size() == 4 && T(op.in[1]).count() == 8))
-            return bad("pad: need a uint8 4-D input and constant [4,2] paddings");
+            return bad("pad: need a uint8 or int8 4-D input, an output of its type and constant [4,2] paddings");
         const TflTensor &x = T(op.in[0]), &y = T(op.out[0]);
         const int* pp = (const int*)T(op.in[1]).data;
         PadQ& q = pr.pad; pr.kind = P_PAD;
@@ -272,9 +310,9 @@ struct OpPrep {
         return YH_OK;
     }
     int resize(Prepared& pr) const {
-        if (!(op.in.size() == 2 && u8(op.in[0]) && u8(op.out[0]) && T(op.in[1]).type == TFL_I32 && T(op.in[1]).data && T(op.in[1]).count() == 2 &&
+        if (!(op.in.size() == 2 && same8(op.in[0], op.out[0]) && T(op.in[1]).type == TFL_I32 && T(op.in[1]).data && T(op.in[1]).count() == 2 &&
               T(op.in[0]).shape.size() == 4 && T(op.in[0]).shape[0] == 1))
-            return bad("resize_bilinear: need uint8 NHWC batch 1 and a constant size");
+            return bad("resize_bilinear: need uint8 or int8 NHWC batch 1, an output of its type and a constant size");
         const TflTensor &x = T(op.in[0]), &y = T(op.out[0]);
         const int* sz = (const int*)T(op.in[1]).data;
         ResizeQ& q = pr.rs; pr.kind = P_RESIZE;
@@ -283,6 +321,14 @@ struct OpPrep {
         q.hs = (op.align_corners && q.Ho > 1) ? (float)(q.H - 1) / (float)(q.Ho - 1) : (float)q.H / (float)q.Ho;
         q.ws = (op.align_corners && q.Wo > 1) ? (float)(q.W - 1) / (float)(q.Wo - 1) : (float)q.W / (float)q.Wo;
         q.x = (const uint8_t*)dev(op.in[0]); q.y = (uint8_t*)dev(op.out[0]); q.ys = (long long)q.Ho * q.Wo * q.C;
+        if (i8(op.in[0])) {   // TFLite's integer kernel: the steps in 10-bit fixed point (the positions stay inside 32 bits: sizes <= 2^16)
+            if (x.scale != y.scale || x.zp != y.zp) return bad("resize_bilinear: an int8 input and its output must share scale and zero point");
+            if (q.H > 65536 || q.W > 65536 || q.Ho > 65536 || q.Wo > 65536 || q.Ho < 1 || q.Wo < 1) return bad("resize_bilinear: int8 sizes must be 1 .. 65536");
+            auto step10 = [&](int in, int out) {
+                return op.align_corners && out > 1 ? (int)(((1ll << 10) * (in - 1) + (out - 1) / 2) / (out - 1)) : (int)(((1ll << 10) * in + out / 2) / out);
+            };
+            q.sgn = 1; q.hs10 = step10(q.H, q.Ho); q.ws10 = step10(q.W, q.Wo);
+        }
         return YH_OK;
     }
     int concat(Prepared& pr) const {
@@ -302,7 +348,9 @@ struct OpPrep {
             for (int d = axis; d < nd; ++d) inner *= x.shape[d];
             CatQ c;
             c.x = (const uint8_t*)dev(ii); c.y = (uint8_t*)dev(op.out[0]); c.outer = outer; c.inner = inner; c.row = inner_o; c.off = off;
-            c.esz = x.type == TFL_U8 ? 1 : 4; c.rescale = 0; c.sc = 1.0f; c.bias = 0.0f; c.zo = y.zp;
+            c.esz = x.type == TFL_U8 || x.type == TFL_I8 ? 1 : 4; c.rescale = 0; c.sc = 1.0f; c.bias = 0.0f; c.zo = y.zp;
+            if (x.type == TFL_I8 && (x.zp != y.zp || x.scale != y.scale))   // (TFLite rescales only uint8)
+                return bad("concatenation: every int8 input must have the output's scale and zero point");
             if (x.type == TFL_U8 && y.quant && (x.zp != y.zp || x.scale != y.scale)) {  // ConcatenationWithScaling
                 const float inv = 1.0f / y.scale;
                 c.rescale = 1; c.sc = x.scale * inv; c.bias = (float)(-x.zp) * c.sc;
@@ -428,6 +476,7 @@ void fuse_plan(yh_tfl* h) {
         uint8_t* y = nullptr;
         long long ys = 0;
         bool has_add = false;
+        const int prod_sgn = p.kind == P_RESIZE ? p.rs.sgn : p.conv.sgn;   // the producer kernel's signedness: how it reads an ADD's other operand
         while (!out_refs[cur] && cons[cur].size() == 1) {
             const int c = cons[cur][0], cp = plan_of[c];
             if (cp <= (int)pi) break;
@@ -435,9 +484,9 @@ void fuse_plan(yh_tfl* h) {
             if (q.dead) break;
             if ((q.kind == P_REQUANT || q.kind == P_LUT) && po.n < 3) {
                 PostStep& t = po.st[po.n++];
-                t.kind = q.kind == P_REQUANT ? 1 : 2;
+                t.kind = q.kind == P_REQUANT ? 1 : (q.sgn_out ? 4 : 2);
                 t.zi = q.zi; t.zo = q.zo; t.m = q.m; t.s = q.s; t.lo = q.lo; t.hi = q.hi; t.lut = q.lut;
-            } else if (q.kind == P_ADD && !has_add && po.n < 3) {
+            } else if (q.kind == P_ADD && !has_add && po.n < 3 && q.add.sgn == prod_sgn) {
                 const int a = root[m.ops[c].in[0]], b = root[m.ops[c].in[1]], other = a == cur ? b : a;
                 // the other operand must be complete when this producer runs: written by an earlier launch (or the graph input / a constant)
                 if (a == b || (prod[other] >= (int)pi) || h->gone[other]) break;
@@ -492,6 +541,7 @@ static ConvI8 conv_i8_args(const Prepared& p, int nb) {
     q.H = c.H; q.W = c.W; q.Ci = c.Ci; q.Ho = c.Ho; q.Wo = c.Wo; q.Co = c.Co; q.kh = c.kh; q.kw = c.kw; q.sh = c.sh; q.sw = c.sw;
     q.ph = c.ph; q.pw = c.pw; q.dh = c.dh; q.dw = c.dw; q.zx = c.zx; q.zw = c.zw; q.zo = c.zo; q.mult = c.mult; q.shift = c.shift;
     q.lo = c.lo; q.hi = c.hi; q.K = c.kh * c.kw * c.Ci; q.M = c.Ho * c.Wo * nb; q.xs = c.xs; q.ys = c.ys; q.po = c.po;
+    q.mtab = c.mtab; q.stab = c.stab; q.sgn = c.sgn;
     return q;
 }
 
@@ -561,10 +611,10 @@ int group_tables(yh_tfl* h, int nb) {
 // ---- the entries of one depth (in execution order): those that run the register-fed kernel, bucketed by its form, as groups of 2 to kMaxGroup.
 // Membership is decided at two images whatever max_images is: the groups of a handle are the same at every image count.
 int group_one_depth(yh_tfl* h, const int* first, const int* last) {
-    std::map<int, std::vector<int>> byform;
+    std::map<int, std::vector<int>> byform;   // (key: the form, then the signedness - a uint8 and an int8 convolution never share a group)
     for (const int* k = first; k != last; ++k) {
         const Prepared& p = h->plan[*k];
-        if (p.kind == P_CONV_I8 && h->use_dot >= 3 && conv_i8_direct_pays(conv_i8_args(p, 2))) byform[p.form].push_back(*k);
+        if (p.kind == P_CONV_I8 && h->use_dot >= 3 && conv_i8_direct_pays(conv_i8_args(p, 2))) byform[2 * p.form + p.conv.sgn].push_back(*k);
     }
     for (auto& kv : byform) {
         std::vector<int>& v = kv.second;
@@ -618,16 +668,16 @@ int enqueue_plan(yh_tfl* h) {
             case P_CONV_I8: {
                 const yh_tfl::ConvGroup* g = p.group >= 0 ? &h->groups[p.group] : nullptr;
                 const ConvI8 q = conv_i8_args(p, (int)nb);
-                if (g) launch_conv_i8_direct_group(p.form, g->probs[nb - 1], g->tile_start[nb - 1], (int)g->members.size(), g->tiles[nb - 1], s);
+                if (g) launch_conv_i8_direct_group(p.form, p.conv.sgn != 0, g->probs[nb - 1], g->tile_start[nb - 1], (int)g->members.size(), g->tiles[nb - 1], s);
                 else if (conv_i8_runs_direct(h, p, (int)nb)) launch_conv_i8_direct(p.form, q, s);
                 else launch_conv_i8_mfma(q, s);
                 break;
             }
             case P_DW: launch_dwconv_u8(p.conv, h->use_dot != 0, nb, s); break;
             case P_ADD: launch_add_u8(p.add, nb, s); break;
-            case P_REQUANT: launch_requant_u8((const uint8_t*)p.src, (uint8_t*)p.dst, p.n * nb, p.zi, p.zo, p.m, p.s, p.lo, p.hi, s); break;
-            case P_QUANT_F32: launch_quantize_f32((const float*)p.src, (uint8_t*)p.dst, p.n * nb, p.scale, p.zo, s); break;
-            case P_DEQUANT: launch_dequantize_u8((const uint8_t*)p.src, (float*)p.dst, p.n * nb, p.scale, p.zi, s); break;
+            case P_REQUANT: launch_requant_u8((const uint8_t*)p.src, (uint8_t*)p.dst, p.n * nb, p.zi, p.zo, p.m, p.s, p.lo, p.hi, s, p.sgn_in); break;
+            case P_QUANT_F32: launch_quantize_f32((const float*)p.src, (uint8_t*)p.dst, p.n * nb, p.scale, p.zo, s, p.sgn_out); break;
+            case P_DEQUANT: launch_dequantize_u8((const uint8_t*)p.src, (float*)p.dst, p.n * nb, p.scale, p.zi, s, p.sgn_in); break;
             case P_LUT: launch_lut_u8((const uint8_t*)p.src, (uint8_t*)p.dst, p.n * nb, p.lut, s); break;
             case P_PAD: launch_pad_u8(p.pad, nb, s); break;
             case P_RESIZE: launch_resize_bilinear_u8(p.rs, nb, s); break;
@@ -709,6 +759,8 @@ const char* classify_model_check(const yh_tfl* h, int* S_out, int* C_out) {
     const TflTensor& o4 = h->m.tensors[h->m.outputs[4]];
     const int S = in.shape[1], grid = S / 8;
     const size_t cells = (size_t)grid * grid;
+    if (o4.type == TFL_I8)
+        return "output 4 is int8: classify reads it as uint8 or float32 only (yolact.rs:171-186) - end the model with a QUANTIZE to uint8 or a DEQUANTIZE";
     if (o4.count() % cells != 0 || o4.count() / cells < 4 || (o4.type != TFL_U8 && o4.type != TFL_F32))
         return "output 4 must hold (S/8)^2 cells of >= 4 uint8 or float32 logits";
     *S_out = S; *C_out = (int)(o4.count() / cells);
@@ -852,6 +904,18 @@ int yh_tfl_op_info(const yh_tfl* h, int32_t op, int32_t* family, int32_t* form_r
     if (form_row) *form_row = row;
     if (grouped) *grouped = grp;
     if (folded) *folded = fold;
+    return YH_OK;
+}
+
+// Operator `op`'s output type and whether its launch takes its multipliers from per-channel tables (the int8 convolutions do).
+int yh_tfl_op_quant(const yh_tfl* h, int32_t op, int32_t* signed_act, int32_t* per_channel) {
+    if (!h || op < 0 || op >= (int)h->m.ops.size() || h->m.ops[op].out.empty()) return YH_EINVAL;
+    const TflTensor& y = h->m.tensors[h->m.ops[op].out[0]];
+    // (an int8 convolution always reads its multipliers from tables; what is reported is whether they differ: the weights' scale vector)
+    const TflOp& o = h->m.ops[op];
+    const int pc = (o.code == TFL_CONV_2D || o.code == TFL_DEPTHWISE_CONV_2D) && y.type == TFL_I8 && h->m.tensors[o.in[1]].per_channel() ? 1 : 0;
+    if (signed_act) *signed_act = y.type == TFL_U8 ? 0 : (y.type == TFL_I8 ? 1 : -1);
+    if (per_channel) *per_channel = pc;
     return YH_OK;
 }
 

@@ -1,6 +1,7 @@
 // tflite_kernels.hip — the device code of the TFLite executor (tflite_exec.hip holds the plan and the C ABI): uint8 per-tensor
 // quantised kernels whose arithmetic restates TensorFlow Lite's published uint8 reference kernels (gemmlowp fixed-point
-// requantisation), and one launcher per kernel family (tflite_exec.h).
+// requantisation), their int8 / per-channel forms (DESIGN.md section 11 "TFLite int8"), and one launcher per kernel family
+// (tflite_exec.h).
 //
 // Most are HBM/latency-bound byte kernels on small tensors (a 224x224 MobileNetV2 is ~0.3 GMAC): one lane per output element, output
 // channel fastest (coalesced NHWC stores, broadcast input reads), int32 accumulation; the convolutions with Ci % 4 == 0 also have
@@ -31,6 +32,12 @@ __device__ __forceinline__ int q_mbqm(int x, int m, int shift) {
 }
 __device__ __forceinline__ int q_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// A quantised byte as the integer it stands for: S = the tensor is int8.
+template <bool S> __device__ __forceinline__ int ldq(const uint8_t* p) { return S ? (int)(int8_t)*p : (int)*p; }
+template <bool S> __device__ __forceinline__ int byteq(unsigned word, int e) { const unsigned b = (word >> (8 * e)) & 255u; return S ? (int)(int8_t)b : (int)b; }
+
+// OS: the folded ADD's other operand is int8 (the producer's own signedness: fuse_plan folds no ADD of another type)
+template <bool OS = false>
 __device__ __forceinline__ int apply_post(const PostOps& po, int q, long long img, long long elem) {
     // (compile-time step indices: a run-time index into the kernel-argument block makes the compiler copy the whole block to
     // scratch - 344 bytes of private memory per lane in every convolution kernel, +45 % per invoke when first measured)
@@ -40,8 +47,9 @@ __device__ __forceinline__ int apply_post(const PostOps& po, int q, long long im
         const PostStep& t = po.st[i];
         if (t.kind == 1) q = q_clamp(q_mbqm(q - t.zi, t.m, t.s) + t.zo, t.lo, t.hi);
         else if (t.kind == 2) q = t.lut[q];
+        else if (t.kind == 4) q = (int)(int8_t)t.lut[q];   // (an int8 table: its entry is the byte of a signed value)
         else {
-            const int o = po.other[img * po.other_s + elem];
+            const int o = ldq<OS>(po.other + img * po.other_s + elem);
             const int a = po.q_is_a ? q : o, b = po.q_is_a ? o : q;
             const int v1 = q_mbqm((a - po.za) * (1 << 20), po.m1, po.s1), v2 = q_mbqm((b - po.zb) * (1 << 20), po.m2, po.s2);
             q = q_clamp(q_mbqm(v1 + v2, po.mo, po.so) + po.azo, po.alo, po.ahi);
@@ -53,7 +61,18 @@ __device__ __forceinline__ int apply_post(const PostOps& po, int q, long long im
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v4i_u __attribute__((ext_vector_type(4), aligned(4)));   // (a 16-byte load from a dword-aligned address)
 
-__global__ __launch_bounds__(256) void tfl_conv_u8(const ConvQ p) {
+// A convolution's accumulator (bias added) to its output value: one multiplier for the tensor (uint8), or channel oc's (int8, SGN)
+template <bool SGN, class P>
+__device__ __forceinline__ int conv_requant(const P& p, int acc, int oc) {
+    return q_clamp(q_mbqm(acc, SGN ? p.mtab[oc] : p.mult, SGN ? p.stab[oc] : p.shift) + p.zo, p.lo, p.hi);
+}
+
+// Every kernel below that reads quantised bytes is a body with the signedness as a template parameter and two entry points: the
+// uint8 one under its old name, compiled to what it was, and the int8 one (.._s8: int8 activations, symmetric int8 weights, one
+// multiplier per output channel). (The px8 kernel takes the flag as a fourth parameter of the kernel template instead: as a body
+// behind two entry points its uint8 instance compiled to other register counts.)
+template <bool SGN>
+__device__ __forceinline__ void conv_scalar_body(const ConvQ& p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.Ho * p.Wo * p.Co) return;
     const uint8_t* const px = p.x + blockIdx.y * p.xs;
@@ -68,25 +87,27 @@ __global__ __launch_bounds__(256) void tfl_conv_u8(const ConvQ p) {
             if ((unsigned)ix >= (unsigned)p.W) continue;
             const uint8_t* xp = px + ((size_t)iy * p.W + ix) * p.Ci;
             const uint8_t* wp = p.w + (((size_t)oc * p.kh + r) * p.kw + s) * p.Ci;
-            for (int c = 0; c < p.Ci; ++c) acc += ((int)xp[c] - p.zx) * ((int)wp[c] - p.zw);
+            for (int c = 0; c < p.Ci; ++c) acc += (ldq<SGN>(xp + c) - p.zx) * (ldq<SGN>(wp + c) - p.zw);
         }
     }
     acc += p.bias ? p.bias[oc] : 0;
-    py[t] = (uint8_t)apply_post(p.po, q_clamp(q_mbqm(acc, p.mult, p.shift) + p.zo, p.lo, p.hi), blockIdx.y, t);
+    py[t] = (uint8_t)apply_post<SGN>(p.po, conv_requant<SGN>(p, acc, oc), blockIdx.y, t);
 }
+__global__ __launch_bounds__(256) void tfl_conv_u8(const ConvQ p) { conv_scalar_body<false>(p); }
+__global__ __launch_bounds__(256) void tfl_conv_s8(const ConvQ p) { conv_scalar_body<true>(p); }
 
 // The same for layers the dot-product and MFMA kernels cannot take (Ci % 4 != 0: the model's first convolution, 3 channels) when
 // yh_tuning.tfl_dot >= 1: one lane = one pixel x 8 output channels instead of one output element. The workgroup (256 pixels x 8
 // channels) first puts its 8 x K weights, zero point already subtracted, into LDS as [k][8] ints: a lane then loads each input byte
 // once for eight MACs and reads its weights with two broadcast ds_read_b128 (the element-per-lane kernel loads an input byte and a
 // weight byte per MAC: 19.2 us for the 224 x 224 x 3 -> 112 x 112 x 32 layer of two images; this form: see DESIGN.md section 8).
-template <int KH, int KW, int CI>   // (0, 0, 0: run-time extent; 3, 3, 3: the RGB stem)
+template <int KH, int KW, int CI, bool SGN>   // (0, 0, 0: run-time extent; 3, 3, 3: the RGB stem; SGN: the int8 form)
 __global__ __launch_bounds__(256) void tfl_conv_u8_px8(const ConvQ p) {
     __shared__ __attribute__((aligned(16))) int wl[kPx8MaxK * 8];
     const int K = p.kh * p.kw * p.Ci, oc0 = blockIdx.y * 8;
     for (int i = threadIdx.x; i < K * 8; i += 256) {
         const int k = i >> 3, j = i & 7, oc = oc0 + j < p.Co ? oc0 + j : p.Co - 1;   // (the clamped duplicates are not stored)
-        wl[i] = (int)p.w[(size_t)oc * K + k] - p.zw;
+        wl[i] = ldq<SGN>(p.w + (size_t)oc * K + k) - p.zw;
     }
     __syncthreads();
     const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -105,7 +126,7 @@ __global__ __launch_bounds__(256) void tfl_conv_u8_px8(const ConvQ p) {
                 const bool in = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
                 const uint8_t* xp = px + ((size_t)(in ? iy : 0) * p.W + (in ? ix : 0)) * CI;
 #pragma unroll
-                for (int c = 0; c < CI; ++c) { const int v = (int)xp[c]; xv[(r * KW + s) * CI + c] = in ? v - p.zx : 0; }
+                for (int c = 0; c < CI; ++c) { const int v = ldq<SGN>(xp + c); xv[(r * KW + s) * CI + c] = in ? v - p.zx : 0; }
             }
 #pragma unroll
         for (int k = 0; k < KH * KW * CI; ++k) {
@@ -123,7 +144,7 @@ __global__ __launch_bounds__(256) void tfl_conv_u8_px8(const ConvQ p) {
                 const uint8_t* xp = px + ((size_t)iy * p.W + ix) * p.Ci;
                 const int* wk = wl + (r * p.kw + s) * p.Ci * 8;
                 for (int c = 0; c < p.Ci; ++c) {
-                    const int xv = (int)xp[c] - p.zx;
+                    const int xv = ldq<SGN>(xp + c) - p.zx;
                     const v4i w0 = *(const v4i*)(wk + c * 8), w1 = *(const v4i*)(wk + c * 8 + 4);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { acc[j] += xv * w0[j]; acc[4 + j] += xv * w1[j]; }
@@ -136,7 +157,7 @@ __global__ __launch_bounds__(256) void tfl_conv_u8_px8(const ConvQ p) {
         const int oc = oc0 + j;
         if (oc < p.Co) {
             const int a = acc[j] + (p.bias ? p.bias[oc] : 0);
-            py[(size_t)pix * p.Co + oc] = (uint8_t)apply_post(p.po, q_clamp(q_mbqm(a, p.mult, p.shift) + p.zo, p.lo, p.hi), blockIdx.z, (long long)pix * p.Co + oc);
+            py[(size_t)pix * p.Co + oc] = (uint8_t)apply_post<SGN>(p.po, conv_requant<SGN>(p, a, oc), blockIdx.z, (long long)pix * p.Co + oc);
         }
     }
 }
@@ -222,7 +243,13 @@ __global__ __launch_bounds__(64 * KS) void tfl_conv_u8_dot(const ConvQ p) {
 // 64 channels per k-step, register-staged double buffer (tiles are 4 KB: the layers are small and latency-bound).
 // Epilogue of the int8 MFMA convolutions: lane = pixel (wm, j, l15), channels (wc, i, 4 lg + e) [C/D layout of the 16 x 16 MFMA:
 // column = lane & 15, rows 4 (lane >> 4) + e]; sx[j] = sum of the raw input bytes over the whole K of pixel (wm, j, l15).
-template <int TI, int TJ>   // MFMA tiles per wave along the channels / the pixels
+//
+// int8 tensors (SGN; DESIGN.md section 11 "TFLite int8") are the native form of the same kernels: with symmetric weights (zw = 0)
+//   sum (x - zx) w = sum x w - zx sum w,
+// the bytes go to the MFMA as loaded - no sum of x, no top-bit flip - the second term is in cterm[oc] with the bias (equal modulo
+// 2^32, which is all the int32 accumulator keeps), a padded tap is fed the byte of zx, and the epilogue takes channel oc's
+// multiplier and shift from tables padded like cterm.
+template <int TI, int TJ, bool SGN>   // MFMA tiles per wave along the channels / the pixels
 __device__ __forceinline__ void conv_i8_epilogue(const ConvI8& p, const v4i (&acc)[TI][TJ], const unsigned (&sx)[TJ], int m0, int ch0, int wc, int wm, int l15, int lg, int HoWo) {
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
@@ -230,7 +257,7 @@ __device__ __forceinline__ void conv_i8_epilogue(const ConvI8& p, const v4i (&ac
         if (mo >= p.M) continue;
         const int im = mo / HoWo, px = mo - im * HoWo;
         uint8_t* yrow = p.y + (long long)im * p.ys + (size_t)px * p.Co;
-        const int xterm = (128 - p.zw) * ((int)sx[j] - 128 * p.K);
+        const int xterm = SGN ? 0 : (128 - p.zw) * ((int)sx[j] - 128 * p.K);
 #pragma unroll
         for (int i = 0; i < TI; ++i) {
             const int ch = ch0 + wc * 16 * TI + i * 16 + 4 * lg;
@@ -239,8 +266,8 @@ __device__ __forceinline__ void conv_i8_epilogue(const ConvI8& p, const v4i (&ac
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int a = acc[i][j][e] + xterm + p.cterm[ch + e];   // (cterm is padded to CoPad)
-                const unsigned q = (unsigned)apply_post(p.po, q_clamp(q_mbqm(a, p.mult, p.shift) + p.zo, p.lo, p.hi), im, (long long)px * p.Co + (ch + e < p.Co ? ch + e : 0));
-                packed |= q << (8 * e);
+                const unsigned q = (unsigned)apply_post<SGN>(p.po, conv_requant<SGN>(p, a, ch + e), im, (long long)px * p.Co + (ch + e < p.Co ? ch + e : 0));
+                packed |= (q & 255u) << (8 * e);   // (a folded chain may end in int8 behind a uint8 producer too: the value's low byte)
             }
             if ((p.Co & 3) == 0 && (((size_t)yrow) & 3) == 0) *(unsigned*)(yrow + ch) = packed;   // (a CONCATENATION part may start at any byte)
             else {
@@ -252,8 +279,8 @@ __device__ __forceinline__ void conv_i8_epilogue(const ConvI8& p, const v4i (&ac
 }
 
 
-__global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
-    __shared__ __attribute__((aligned(16))) char lds[2][8192];   // [stage][A 64 rows x 64 B | B 64 rows x 64 B]
+template <bool SGN>
+__device__ __forceinline__ void conv_i8_mfma_body(const ConvI8& p, char (&lds)[2][8192]) {   // lds: [stage][A 64 rows x 64 B | B 64 rows x 64 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
     const int m0 = blockIdx.x * 64, ch0 = blockIdx.y * 64;
     // loader role: 16-byte chunk `lchunk` of row `lrow` of both tiles
@@ -264,7 +291,7 @@ __global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
     const int img = mlive ? m / HoWo : 0, rem = mlive ? m - img * HoWo : 0, oy = rem / p.Wo, ox = rem - oy * p.Wo;
     const uint8_t* ximg = p.x + (long long)img * p.xs;
     const uint8_t* wrow = p.wq + (size_t)(ch0 + lrow) * p.K + lchunk * 16;
-    const unsigned zx4 = (unsigned)p.zx * 0x01010101u;
+    const unsigned zx4 = (unsigned)(SGN ? p.zx & 255 : p.zx) * 0x01010101u;
     const int lds_w = lrow * 64 + ((lchunk ^ ((lrow >> 2) & 3)) << 4);
     const int cchunks = p.Ci >> 6, nsteps = p.kh * p.kw * cchunks;
     // Register ring: the tiles of the next THREE k-steps are in flight while one is computed. The layers are small (50-200
@@ -322,8 +349,11 @@ __global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
             const v4i raw = *(const v4i*)(lds[st] + 4096 + row * 64 + ((lg ^ ((row >> 2) & 3)) << 4));
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                sx[j] = __builtin_amdgcn_udot4((unsigned)raw[e], 0x01010101u, sx[j], false);
-                fb[j][e] = raw[e] ^ (int)0x80808080u;
+                if constexpr (SGN) fb[j][e] = raw[e];
+                else {
+                    sx[j] = __builtin_amdgcn_udot4((unsigned)raw[e], 0x01010101u, sx[j], false);
+                    fb[j][e] = raw[e] ^ (int)0x80808080u;
+                }
             }
         }
 #pragma unroll
@@ -340,7 +370,15 @@ __global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
         sx[j] += __shfl_xor(sx[j], 16);
         sx[j] += __shfl_xor(sx[j], 32);
     }
-    conv_i8_epilogue<2, 2>(p, acc, sx, m0, ch0, wc, wm, l15, lg, HoWo);
+    conv_i8_epilogue<2, 2, SGN>(p, acc, sx, m0, ch0, wc, wm, l15, lg, HoWo);
+}
+__global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
+    __shared__ __attribute__((aligned(16))) char lds[2][8192];
+    conv_i8_mfma_body<false>(p, lds);
+}
+__global__ __launch_bounds__(256) void tfl_conv_s8_mfma(const ConvI8 p) {
+    __shared__ __attribute__((aligned(16))) char lds[2][8192];
+    conv_i8_mfma_body<true>(p, lds);
 }
 
 // ---- The same convolution with NO LDS and no barrier (yh_tuning.tfl_dot = 3, the default, for the launches conv_i8_direct_pays()
@@ -362,7 +400,7 @@ __global__ __launch_bounds__(256) void tfl_conv_i8_mfma(const ConvI8 p) {
 // (the 3x3 x 128-channel head convolutions, 18 steps: 9.5 -> 7 us against two drained iterations of a ring of 9).
 // KK (ONCE only): the kernel extent, 1 x 1 or 3 x 3 - the tap and the channel chunk of step d are then compile-time constants and
 // the position bookkeeping below disappears from the prologue (0: run-time extent, looped form).
-template <int D, bool ONCE, int KK>
+template <int D, bool ONCE, int KK, bool SGN>
 __device__ __forceinline__ void conv_i8_direct_tile(const ConvI8& p, int tile_m, int tile_c) {
     static_assert(KK == 0 || (ONCE && D % (KK * KK) == 0), "compile-time extents: the launch's k-steps are exactly D");
     const int lane = threadIdx.x, l15 = lane & 15, lg = lane >> 4;
@@ -375,7 +413,7 @@ __device__ __forceinline__ void conv_i8_direct_tile(const ConvI8& p, int tile_m,
     const int iy0 = oy * p.sh - p.ph, ix0 = ox * p.sw - p.pw;
     const uint8_t* const wa = p.wq + (size_t)(ch0 + l15) * p.K;   // (rows up to CoPad exist)
     const int cchunks = (p.Ci + 63) >> 6, nsteps = p.kh * p.kw * cchunks;
-    const int zx4 = (int)((unsigned)p.zx * 0x01010101u);
+    const int zx4 = (int)((unsigned)(SGN ? p.zx & 255 : p.zx) * 0x01010101u);
     struct Tile { v4i a, b; };
     int f_r = 0, f_s = 0, f_cc = 0, f_tap = 0, f_n = 0;   // the next k-step to fetch: tap (f_r, f_s) = f_tap, 64-channel chunk f_cc
     auto fetch_at = [&](int r, int s_, int tap, int cc, bool more) {
@@ -426,35 +464,51 @@ __device__ __forceinline__ void conv_i8_direct_tile(const ConvI8& p, int tile_m,
         for (int d = 0; d < D; ++d) {
             const Tile t = ring[d];
             if (!ONCE) ring[d] = fetch(d);   // (k-step step + d + D: asked for before this step's MFMA is issued)
-            v4i fb;
+            v4i fb = t.b;   // (int8: the operand as loaded - the k-step is 2 loads and 1 MFMA)
+            if constexpr (!SGN) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sx[0] = __builtin_amdgcn_udot4((unsigned)t.b[e], 0x01010101u, sx[0], false);
-                fb[e] = t.b[e] ^ (int)0x80808080u;
+                for (int e = 0; e < 4; ++e) {
+                    sx[0] = __builtin_amdgcn_udot4((unsigned)t.b[e], 0x01010101u, sx[0], false);
+                    fb[e] = t.b[e] ^ (int)0x80808080u;
+                }
             }
             acc[0][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(t.a, fb, acc[0][0], 0, 0, 0);
         }
     }
-    sx[0] += __shfl_xor(sx[0], 16);
-    sx[0] += __shfl_xor(sx[0], 32);
-    conv_i8_epilogue<1, 1>(p, acc, sx, m0, ch0, 0, 0, l15, lg, HoWo);
+    if constexpr (!SGN) {
+        sx[0] += __shfl_xor(sx[0], 16);
+        sx[0] += __shfl_xor(sx[0], 32);
+    }
+    conv_i8_epilogue<1, 1, SGN>(p, acc, sx, m0, ch0, 0, 0, l15, lg, HoWo);
 }
 template <int D, bool ONCE, int KK>
 __global__ __launch_bounds__(64) void tfl_conv_i8_direct(const ConvI8 p) {
-    conv_i8_direct_tile<D, ONCE, KK>(p, blockIdx.x, blockIdx.y);
+    conv_i8_direct_tile<D, ONCE, KK, false>(p, blockIdx.x, blockIdx.y);
+}
+template <int D, bool ONCE, int KK>
+__global__ __launch_bounds__(64) void tfl_conv_s8_direct(const ConvI8 p) {
+    conv_i8_direct_tile<D, ONCE, KK, true>(p, blockIdx.x, blockIdx.y);
 }
 // Several INDEPENDENT convolutions of one kernel form as ONE launch (yh_tuning.tfl_group; group_plan): the prediction head's
 // tower convolutions of the five pyramid levels, then its fifteen output convolutions, the FPN's output convolutions. The
 // problems' parameter blocks sit in device memory; a workgroup finds its problem in the tile prefix table (at most kMaxGroup
 // entries, wave-uniform) and runs the same tile code on it.
-template <int D, bool ONCE, int KK>
-__global__ __launch_bounds__(64) void tfl_conv_i8_direct_group(const ConvI8* __restrict__ probs, const int* __restrict__ tile_start, int nprob) {
+template <int D, bool ONCE, int KK, bool SGN>
+__device__ __forceinline__ void conv_i8_direct_group_body(const ConvI8* __restrict__ probs, const int* __restrict__ tile_start, int nprob) {
     const int bid = blockIdx.x;
     int pi = 0;
     for (int i = 1; i < nprob; ++i) pi = bid >= tile_start[i] ? i : pi;
     const ConvI8 p = probs[pi];
     const int t = bid - tile_start[pi], mtiles = (p.M + 15) >> 4;
-    conv_i8_direct_tile<D, ONCE, KK>(p, t % mtiles, t / mtiles);
+    conv_i8_direct_tile<D, ONCE, KK, SGN>(p, t % mtiles, t / mtiles);
+}
+template <int D, bool ONCE, int KK>
+__global__ __launch_bounds__(64) void tfl_conv_i8_direct_group(const ConvI8* __restrict__ probs, const int* __restrict__ tile_start, int nprob) {
+    conv_i8_direct_group_body<D, ONCE, KK, false>(probs, tile_start, nprob);
+}
+template <int D, bool ONCE, int KK>
+__global__ __launch_bounds__(64) void tfl_conv_s8_direct_group(const ConvI8* __restrict__ probs, const int* __restrict__ tile_start, int nprob) {
+    conv_i8_direct_group_body<D, ONCE, KK, true>(probs, tile_start, nprob);
 }
 // The forms the register-fed kernel is built in, one row each: taking the two kernels' addresses instantiates them, and nothing else
 // names a (D, ONCE, KK). conv_i8_direct_form (below) finds a convolution's row; a group's members share one. The rows' order - and
@@ -464,9 +518,13 @@ struct DirectForm {
     int D; bool once; int KK;
     void (*group)(const ConvI8*, const int*, int);
     void (*single)(const ConvI8);
+    void (*group_s8)(const ConvI8*, const int*, int);   // the row's second instantiation: int8 activations (not a row of its own)
+    void (*single_s8)(const ConvI8);
 };
 template <int D, bool ONCE, int KK>
-constexpr DirectForm direct_form() { return { D, ONCE, KK, tfl_conv_i8_direct_group<D, ONCE, KK>, tfl_conv_i8_direct<D, ONCE, KK> }; }
+constexpr DirectForm direct_form() {
+    return { D, ONCE, KK, tfl_conv_i8_direct_group<D, ONCE, KK>, tfl_conv_i8_direct<D, ONCE, KK>, tfl_conv_s8_direct_group<D, ONCE, KK>, tfl_conv_s8_direct<D, ONCE, KK> };
+}
 constexpr DirectForm kDirectForms[] = {
     // the whole K in one pass, 3 x 3: 64 and 128 input channels
     direct_form<9, true, 3>(), direct_form<18, true, 3>(),
@@ -484,7 +542,8 @@ constexpr int kDirectFormCount = (int)(sizeof kDirectForms / sizeof kDirectForms
 // tfl_conv_steps.py), and that per-step cost is the wave's own instruction issue - 88 instructions - not a latency the split
 // could overlap: four times the work per wave and step took four times as long. Removed.)
 
-__global__ __launch_bounds__(256) void tfl_dwconv_u8(const ConvQ p) {
+template <bool SGN>
+__device__ __forceinline__ void dwconv_body(const ConvQ& p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.Ho * p.Wo * p.Co) return;
     const uint8_t* const px = p.x + blockIdx.y * p.xs;
@@ -497,27 +556,29 @@ __global__ __launch_bounds__(256) void tfl_dwconv_u8(const ConvQ p) {
         for (int s = 0; s < p.kw; ++s) {
             const int ix = ox * p.sw - p.pw + s * p.dw;
             if ((unsigned)ix >= (unsigned)p.W) continue;
-            acc += ((int)px[((size_t)iy * p.W + ix) * p.Ci + ic] - p.zx) * ((int)p.w[((size_t)r * p.kw + s) * p.Co + oc] - p.zw);
+            acc += (ldq<SGN>(px + ((size_t)iy * p.W + ix) * p.Ci + ic) - p.zx) * (ldq<SGN>(p.w + ((size_t)r * p.kw + s) * p.Co + oc) - p.zw);
         }
     }
     acc += p.bias ? p.bias[oc] : 0;
-    py[t] = (uint8_t)apply_post(p.po, q_clamp(q_mbqm(acc, p.mult, p.shift) + p.zo, p.lo, p.hi), blockIdx.y, t);
+    py[t] = (uint8_t)apply_post<SGN>(p.po, conv_requant<SGN>(p, acc, oc), blockIdx.y, t);
 }
+__global__ __launch_bounds__(256) void tfl_dwconv_u8(const ConvQ p) { dwconv_body<false>(p); }
+__global__ __launch_bounds__(256) void tfl_dwconv_s8(const ConvQ p) { dwconv_body<true>(p); }
 
 // Depth multiplier 1, channels a multiple of 4, dword-aligned tensors, kernel extent known at compile time (3 x 3: every depthwise
 // layer of the model family): one lane = one pixel x FOUR channels - a tap is one dword of input and one dword of weights for four
 // MACs - and the loop over the taps has no branch: all KH x KW input dwords are asked for at once (a tap outside the image loads
 // from a clamped address and is given the zero point, (x - zx) = 0), so a lane waits one memory latency instead of one per tap. The
 // element-per-lane kernel above takes 5.2 us (small layers) to 10.7 us (112 x 112 x 32 x 2 images) per launch.
-template <int KH, int KW>
-__global__ __launch_bounds__(256) void tfl_dwconv_u8_c4(const ConvQ p) {
+template <int KH, int KW, bool SGN>
+__device__ __forceinline__ void dwconv_c4_body(const ConvQ& p) {
     const int c4n = p.Co >> 2;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.Ho * p.Wo * c4n) return;
     const uint8_t* const px = p.x + blockIdx.y * p.xs + 4 * (t % c4n);
     uint8_t* const py = p.y + blockIdx.y * p.ys;
     const int cg = t % c4n, r0 = t / c4n, ox = r0 % p.Wo, oy = r0 / p.Wo;
-    const unsigned zx4 = (unsigned)p.zx * 0x01010101u;
+    const unsigned zx4 = (unsigned)(SGN ? p.zx & 255 : p.zx) * 0x01010101u;
     unsigned xv[KH * KW], wv[KH * KW];
 #pragma unroll
     for (int r = 0; r < KH; ++r)
@@ -533,13 +594,14 @@ __global__ __launch_bounds__(256) void tfl_dwconv_u8_c4(const ConvQ p) {
 #pragma unroll
     for (int k = 0; k < KH * KW; ++k)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += ((int)((xv[k] >> (8 * e)) & 255u) - p.zx) * ((int)((wv[k] >> (8 * e)) & 255u) - p.zw);
+        for (int e = 0; e < 4; ++e) acc[e] += (byteq<SGN>(xv[k], e) - p.zx) * (byteq<SGN>(wv[k], e) - p.zw);
     const long long e0 = (long long)r0 * p.Co + 4 * cg;
     unsigned packed = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int a = acc[e] + (p.bias ? p.bias[4 * cg + e] : 0);
-        packed |= (unsigned)apply_post(p.po, q_clamp(q_mbqm(a, p.mult, p.shift) + p.zo, p.lo, p.hi), blockIdx.y, e0 + e) << (8 * e);
+        const unsigned q = (unsigned)apply_post<SGN>(p.po, conv_requant<SGN>(p, a, 4 * cg + e), blockIdx.y, e0 + e);
+        packed |= (q & 255u) << (8 * e);
     }
     if ((((size_t)py) & 3) == 0) *(unsigned*)(py + e0) = packed;   // (a CONCATENATION part may start at any byte)
     else {
@@ -547,6 +609,10 @@ __global__ __launch_bounds__(256) void tfl_dwconv_u8_c4(const ConvQ p) {
         for (int e = 0; e < 4; ++e) py[e0 + e] = (uint8_t)(packed >> (8 * e));
     }
 }
+template <int KH, int KW>
+__global__ __launch_bounds__(256) void tfl_dwconv_u8_c4(const ConvQ p) { dwconv_c4_body<KH, KW, false>(p); }
+template <int KH, int KW>
+__global__ __launch_bounds__(256) void tfl_dwconv_s8_c4(const ConvQ p) { dwconv_c4_body<KH, KW, true>(p); }
 
 // RESHAPE: a plain device copy as a kernel (a memcpy NODE in the captured plan crashed rocprofv3's
 // kernel tracing on graph replay; kernels are also what the profiler can attribute)
@@ -557,29 +623,44 @@ __global__ __launch_bounds__(256) void tfl_copy_bytes(const uint8_t* __restrict_
     if (t < (n & 15)) y[(n16 << 4) + t] = x[(n16 << 4) + t];
 }
 
-__global__ __launch_bounds__(256) void tfl_add_u8(const AddQ p) {
+template <bool SGN>
+__device__ __forceinline__ void add_body(const AddQ& p) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= p.n) return;
-    const int v1 = q_mbqm(((int)p.a[t] - p.za) * (1 << 20), p.m1, p.s1);
-    const int v2 = q_mbqm(((int)p.b[t] - p.zb) * (1 << 20), p.m2, p.s2);
+    const int v1 = q_mbqm((ldq<SGN>(p.a + t) - p.za) * (1 << 20), p.m1, p.s1);
+    const int v2 = q_mbqm((ldq<SGN>(p.b + t) - p.zb) * (1 << 20), p.m2, p.s2);
     p.y[t] = (uint8_t)q_clamp(q_mbqm(v1 + v2, p.mo, p.so) + p.zo, p.lo, p.hi);
 }
+__global__ __launch_bounds__(256) void tfl_add_u8(const AddQ p) { add_body<false>(p); }
+__global__ __launch_bounds__(256) void tfl_add_s8(const AddQ p) { add_body<true>(p); }
 
 // requantise (QUANTIZE u8->u8, RELU/RELU6) : clamp(mbqm(q - zi) + zo, lo, hi)
 __global__ __launch_bounds__(256) void tfl_requant_u8(const uint8_t* x, uint8_t* y, long long n, int zi, int zo, int m, int s, int lo, int hi) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t < n) y[t] = (uint8_t)q_clamp(q_mbqm((int)x[t] - zi, m, s) + zo, lo, hi);
 }
-__global__ __launch_bounds__(256) void tfl_quantize_f32(const float* x, uint8_t* y, long long n, float scale, int zo) {
+// ... of an int8 input (QUANTIZE i8->i8 and i8->u8, RELU / RELU6 on int8; u8->i8 is the kernel above: the output's type is its range)
+__global__ __launch_bounds__(256) void tfl_requant_s8(const uint8_t* x, uint8_t* y, long long n, int zi, int zo, int m, int s, int lo, int hi) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) y[t] = (uint8_t)q_clamp(q_mbqm(ldq<true>(x + t) - zi, m, s) + zo, lo, hi);
+}
+template <bool SGN>
+__device__ __forceinline__ void quantize_f32_body(const float* x, uint8_t* y, long long n, float scale, int zo) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
     const float v = __fdiv_rn(x[t], scale);
     const float r = v >= 0.0f ? floorf(__fadd_rn(v, 0.5f)) : ceilf(__fsub_rn(v, 0.5f));
-    y[t] = (uint8_t)q_clamp((int)r + zo, 0, 255);
+    y[t] = (uint8_t)q_clamp((int)r + zo, SGN ? -128 : 0, SGN ? 127 : 255);
 }
+__global__ __launch_bounds__(256) void tfl_quantize_f32(const float* x, uint8_t* y, long long n, float scale, int zo) { quantize_f32_body<false>(x, y, n, scale, zo); }
+__global__ __launch_bounds__(256) void tfl_quantize_f32_s8(const float* x, uint8_t* y, long long n, float scale, int zo) { quantize_f32_body<true>(x, y, n, scale, zo); }
 __global__ __launch_bounds__(256) void tfl_dequantize_u8(const uint8_t* x, float* y, long long n, float scale, int z) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t < n) y[t] = __fmul_rn(scale, (float)((int)x[t] - z));   // yolact.rs:177
+}
+__global__ __launch_bounds__(256) void tfl_dequantize_s8(const uint8_t* x, float* y, long long n, float scale, int z) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) y[t] = __fmul_rn(scale, (float)(ldq<true>(x + t) - z));
 }
 __global__ __launch_bounds__(256) void tfl_lut_u8(const uint8_t* x, uint8_t* y, long long n, const uint8_t* lut) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -617,6 +698,28 @@ __global__ __launch_bounds__(256) void tfl_resize_bilinear_u8(const ResizeQ p) {
     const float r = floorf(__fadd_rn(v, 0.5f));
     py[t] = (uint8_t)apply_post(p.po, r < 0.0f ? 0 : (r > 255.0f ? 255 : (int)r), blockIdx.y, t);
 }
+// RESIZE_BILINEAR of int8: not the float interpolation above but TFLite's integer kernel - positions and weights in 10-bit fixed
+// point (hs10 / ws10: the plan's steps), the four products summed in 64 bits and rounded half away from zero at bit 20; `/` here
+// truncates toward zero as the definition's does. Input and output share scale and zero point.
+__global__ __launch_bounds__(256) void tfl_resize_bilinear_s8(const ResizeQ p) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.Ho * p.Wo * p.C) return;
+    const uint8_t* const px = p.x + (size_t)blockIdx.y * p.H * p.W * p.C;
+    uint8_t* const py = p.y + blockIdx.y * p.ys;
+    const int c = t % p.C, r0 = t / p.C, ox = r0 % p.Wo, oy = r0 / p.Wo;
+    const int iy = p.half_pixel ? oy * p.hs10 + p.hs10 / 2 - (1 << 9) : oy * p.hs10;
+    const int ix = p.half_pixel ? ox * p.ws10 + p.ws10 / 2 - (1 << 9) : ox * p.ws10;
+    int y0 = iy / (1 << 10), y1 = (iy + (1 << 10) - 1) / (1 << 10), x0 = ix / (1 << 10), x1 = (ix + (1 << 10) - 1) / (1 << 10);
+    // (the definition bounds y0 below and y1 above only; a step rounded up can carry y0 past the last row when Ho is in the thousands
+    // and H is not - bounded here, and in the tests' reference, so that nothing is read outside the image)
+    y0 = y0 < 0 ? 0 : (y0 > p.H - 1 ? p.H - 1 : y0); x0 = x0 < 0 ? 0 : (x0 > p.W - 1 ? p.W - 1 : x0);
+    y1 = y1 > p.H - 1 ? p.H - 1 : y1; x1 = x1 > p.W - 1 ? p.W - 1 : x1;
+    const long long fy = iy - (1 << 10) * y0, fx = ix - (1 << 10) * x0, gy = (1 << 10) - fy, gx = (1 << 10) - fx;
+    auto at = [&](int yy, int xx) { return (long long)ldq<true>(px + ((size_t)yy * p.W + xx) * p.C + c); };
+    const long long v = at(y0, x0) * gy * gx + at(y1, x0) * fy * gx + at(y0, x1) * gy * fx + at(y1, x1) * fy * fx;
+    const int q = (int)(int8_t)((v + (v > 0 ? (1ll << 19) : -(1ll << 19))) / (1ll << 20));
+    py[t] = (uint8_t)apply_post<true>(p.po, q, blockIdx.y, t);
+}
 __global__ __launch_bounds__(256) void tfl_concat_part(const CatQ p) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= p.outer * p.inner * p.esz) return;
@@ -651,19 +754,20 @@ void launch_conv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s) {
     }
     else if (k == CONV_U8_PX8) {
         const dim3 grid((unsigned)(((long long)p.Ho * p.Wo + 255) / 256), (unsigned)((p.Co + 7) / 8), nb);
-        hipLaunchKernelGGL((tfl_conv_u8_px8<0, 0, 0>), grid, dim3(256), 0, s, p);   // (the <3, 3, 3> form - all 27 input bytes asked for up front - measured 13.0 us against 10.6)
+        if (p.sgn) hipLaunchKernelGGL((tfl_conv_u8_px8<0, 0, 0, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((tfl_conv_u8_px8<0, 0, 0, false>), grid, dim3(256), 0, s, p);   // (the <3, 3, 3> form - all 27 input bytes asked for up front - measured 13.0 us against 10.6)
     }
-    else hipLaunchKernelGGL(tfl_conv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(p.sgn ? tfl_conv_s8 : tfl_conv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
 }
 bool dwconv_u8_takes_c4(const ConvQ& p, bool dot) {
     return dot && p.dm == 1 && p.kh == 3 && p.kw == 3 && p.Co % 4 == 0 && (((size_t)p.x | (size_t)p.w) & 3) == 0;
 }
 void launch_dwconv_u8(const ConvQ& p, bool dot, unsigned nb, hipStream_t s) {
     if (dwconv_u8_takes_c4(p, dot))
-        hipLaunchKernelGGL((tfl_dwconv_u8_c4<3, 3>), dim3(nblk((long long)p.Ho * p.Wo * (p.Co >> 2)), nb), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(tfl_dwconv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((p.sgn ? tfl_dwconv_s8_c4<3, 3> : tfl_dwconv_u8_c4<3, 3>), dim3(nblk((long long)p.Ho * p.Wo * (p.Co >> 2)), nb), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(p.sgn ? tfl_dwconv_s8 : tfl_dwconv_u8, dim3(nblk((long long)p.Ho * p.Wo * p.Co), nb), dim3(256), 0, s, p);
 }
-void launch_conv_i8_mfma(const ConvI8& q, hipStream_t s) { hipLaunchKernelGGL(tfl_conv_i8_mfma, dim3((unsigned)((q.M + 63) / 64), (unsigned)((q.Co + 63) / 64)), dim3(256), 0, s, q); }
+void launch_conv_i8_mfma(const ConvI8& q, hipStream_t s) { hipLaunchKernelGGL(q.sgn ? tfl_conv_s8_mfma : tfl_conv_i8_mfma, dim3((unsigned)((q.M + 63) / 64), (unsigned)((q.Co + 63) / 64)), dim3(256), 0, s, q); }
 
 // The row of a convolution of n = taps x 64-channel chunks k-steps: the one-pass row of exactly n steps and this extent; else a
 // looped row - where one-pass rows of n steps exist for other extents only, the deepest ring that n fills, otherwise the ring that
@@ -702,25 +806,25 @@ bool conv_i8_direct_pays(const ConvI8& q) {
     return waves <= 2048 || q.kh * q.kw * (q.Ci / 64) <= 8;
 }
 void launch_conv_i8_direct(int form, const ConvI8& q, hipStream_t s) {
-    hipLaunchKernelGGL(kDirectForms[form].single, dim3((unsigned)((q.M + 15) / 16), (unsigned)((q.Co + 15) / 16)), dim3(64), 0, s, q);
+    hipLaunchKernelGGL(q.sgn ? kDirectForms[form].single_s8 : kDirectForms[form].single, dim3((unsigned)((q.M + 15) / 16), (unsigned)((q.Co + 15) / 16)), dim3(64), 0, s, q);
 }
-void launch_conv_i8_direct_group(int form, const ConvI8* probs, const int* tile_start, int nprob, int tiles, hipStream_t s) {
-    hipLaunchKernelGGL(kDirectForms[form].group, dim3((unsigned)tiles), dim3(64), 0, s, probs, tile_start, nprob);
+void launch_conv_i8_direct_group(int form, bool sgn, const ConvI8* probs, const int* tile_start, int nprob, int tiles, hipStream_t s) {
+    hipLaunchKernelGGL(sgn ? kDirectForms[form].group_s8 : kDirectForms[form].group, dim3((unsigned)tiles), dim3(64), 0, s, probs, tile_start, nprob);
 }
 
-void launch_add_u8(const AddQ& p, unsigned nb, hipStream_t s) { AddQ q = p; q.n *= nb; hipLaunchKernelGGL(tfl_add_u8, dim3(nblk(q.n)), dim3(256), 0, s, q); }
-void launch_requant_u8(const uint8_t* x, uint8_t* y, long long n, int zi, int zo, int m, int sh, int lo, int hi, hipStream_t s) {
-    hipLaunchKernelGGL(tfl_requant_u8, dim3(nblk(n)), dim3(256), 0, s, x, y, n, zi, zo, m, sh, lo, hi);
+void launch_add_u8(const AddQ& p, unsigned nb, hipStream_t s) { AddQ q = p; q.n *= nb; hipLaunchKernelGGL(q.sgn ? tfl_add_s8 : tfl_add_u8, dim3(nblk(q.n)), dim3(256), 0, s, q); }
+void launch_requant_u8(const uint8_t* x, uint8_t* y, long long n, int zi, int zo, int m, int sh, int lo, int hi, hipStream_t s, bool sgn) {
+    hipLaunchKernelGGL(sgn ? tfl_requant_s8 : tfl_requant_u8, dim3(nblk(n)), dim3(256), 0, s, x, y, n, zi, zo, m, sh, lo, hi);
 }
-void launch_quantize_f32(const float* x, uint8_t* y, long long n, float scale, int zo, hipStream_t s) { hipLaunchKernelGGL(tfl_quantize_f32, dim3(nblk(n)), dim3(256), 0, s, x, y, n, scale, zo); }
-void launch_dequantize_u8(const uint8_t* x, float* y, long long n, float scale, int z, hipStream_t s) { hipLaunchKernelGGL(tfl_dequantize_u8, dim3(nblk(n)), dim3(256), 0, s, x, y, n, scale, z); }
+void launch_quantize_f32(const float* x, uint8_t* y, long long n, float scale, int zo, hipStream_t s, bool sgn) { hipLaunchKernelGGL(sgn ? tfl_quantize_f32_s8 : tfl_quantize_f32, dim3(nblk(n)), dim3(256), 0, s, x, y, n, scale, zo); }
+void launch_dequantize_u8(const uint8_t* x, float* y, long long n, float scale, int z, hipStream_t s, bool sgn) { hipLaunchKernelGGL(sgn ? tfl_dequantize_s8 : tfl_dequantize_u8, dim3(nblk(n)), dim3(256), 0, s, x, y, n, scale, z); }
 void launch_lut_u8(const uint8_t* x, uint8_t* y, long long n, const uint8_t* lut, hipStream_t s) { hipLaunchKernelGGL(tfl_lut_u8, dim3(nblk(n)), dim3(256), 0, s, x, y, n, lut); }
 void launch_pad_u8(const PadQ& p, unsigned nb, hipStream_t s) {
     PadQ q = p;
     q.id[0] *= (int)nb; q.od[0] *= (int)nb;
     hipLaunchKernelGGL(tfl_pad_u8, dim3(nblk((long long)q.od[0] * q.od[1] * q.od[2] * q.od[3])), dim3(256), 0, s, q);
 }
-void launch_resize_bilinear_u8(const ResizeQ& p, unsigned nb, hipStream_t s) { hipLaunchKernelGGL(tfl_resize_bilinear_u8, dim3(nblk((long long)p.Ho * p.Wo * p.C), nb), dim3(256), 0, s, p); }
+void launch_resize_bilinear_u8(const ResizeQ& p, unsigned nb, hipStream_t s) { hipLaunchKernelGGL(p.sgn ? tfl_resize_bilinear_s8 : tfl_resize_bilinear_u8, dim3(nblk((long long)p.Ho * p.Wo * p.C), nb), dim3(256), 0, s, p); }
 void launch_concat_part(const CatQ& p, unsigned nb, hipStream_t s) { CatQ c = p; c.outer *= nb; hipLaunchKernelGGL(tfl_concat_part, dim3(nblk(c.outer * c.inner * c.esz)), dim3(256), 0, s, c); }
 void launch_copy_bytes(const uint8_t* x, uint8_t* y, long long n, hipStream_t s) { hipLaunchKernelGGL(tfl_copy_bytes, dim3(nblk((n >> 4) + 16)), dim3(256), 0, s, x, y, n); }
 

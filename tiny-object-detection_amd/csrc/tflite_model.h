@@ -1,8 +1,8 @@
 // tflite_model.h — dependency-free, bounds-checked reader of TensorFlow Lite flatbuffers (schema v3).
 //
 // Stands in for FlatBufferModel::build_from_file + the interpreter's graph walk
-// (/root/reference/src/yolact.rs:18-35): tensors (shape, type, constant data, per-tensor
-// quantisation), operators with the builtin options of the op set listed in
+// (/root/reference/src/yolact.rs:18-35): tensors (shape, type, constant data, per-tensor or
+// per-channel quantisation), operators with the builtin options of the op set listed in
 // data/FRC_model_edgetpu.log:7-19, subgraph inputs/outputs. Every offset is range-checked: a
 // malformed file yields an error string, never an out-of-bounds read.
 #pragma once
@@ -28,6 +28,12 @@ struct TflTensor {
     bool quant = false;
     float scale = 1.0f;
     int zp = 0;
+    // the whole quantisation record: scale / zp above stay element 0. A per-channel constant (int8 convolution weights, their bias)
+    // has one scale per index of dimension qdim; its zero points are one for all, or one per scale
+    std::vector<float> scales;
+    std::vector<int> zps;
+    int qdim = 0;
+    bool per_channel() const { return scales.size() > 1; }
     size_t count() const { size_t c = 1; for (int s : shape) c *= (size_t)s; return c; }   // (parse() bounds it: <= kMaxElems)
     static constexpr uint64_t kMaxElems = 1ull << 31;
     // element count with overflow checking: false if a dimension is negative or the product exceeds kMaxElems
@@ -91,13 +97,17 @@ public:
             const uint32_t q = sub(t, 4);
             if (q) {
                 const uint32_t sv = vec(q, 2), zv = vec(q, 3);
+                // (a forged vector length must not drive the loops: every element needs its bytes of file)
+                if (sv && !range((uint64_t)sv + 4, (uint64_t)vlen(sv) * 4)) return fail("scale vector longer than the file (tensor " + x.name + ")");
+                if (zv && !range((uint64_t)zv + 4, (uint64_t)vlen(zv) * 8)) return fail("zero-point vector longer than the file (tensor " + x.name + ")");
                 if (sv && vlen(sv) >= 1) {
                     x.quant = true;
-                    uint32_t bits = rd32(sv + 4);
-                    memcpy(&x.scale, &bits, 4);
-                    if (vlen(sv) > 1) return fail("per-channel quantisation is not supported (tensor " + x.name + ")");
+                    for (uint32_t k = 0; k < vlen(sv); ++k) { const uint32_t bits = rd32(sv + 4 + 4 * k); float f; memcpy(&f, &bits, 4); x.scales.push_back(f); }
+                    x.scale = x.scales[0];
                 }
-                if (zv && vlen(zv) >= 1) x.zp = (int)(int64_t)rd64(zv + 4);
+                if (zv) for (uint32_t k = 0; k < vlen(zv); ++k) x.zps.push_back((int)(int64_t)rd64(zv + 4 + 8 * k));
+                if (!x.zps.empty()) x.zp = x.zps[0];
+                x.qdim = (int)scalar32(q, 6, 0);
             }
             if (bi != 0) {
                 if (!buffers || bi >= vlen(buffers)) return fail("tensor buffer index out of range");
@@ -112,6 +122,12 @@ public:
             uint64_t ne = 0;
             if (x.shape.size() > 8 || !x.count_checked(&ne)) return fail("tensor too large or of too high a rank: " + x.name);
             if (x.data && x.nbytes != x.count() * x.elem()) return fail("constant size mismatch in " + x.name);
+            if (x.scales.size() > 1) {
+                if (x.qdim < 0 || x.qdim >= (int)x.shape.size()) return fail("quantized_dimension outside the rank of tensor " + x.name);
+                if (x.scales.size() != (size_t)x.shape[x.qdim]) return fail("scale vector of tensor " + x.name + " has neither 1 nor shape[quantized_dimension] entries");
+                if (!x.data) return fail("per-channel quantisation on a tensor that is not a constant: " + x.name);
+            }
+            if (x.zps.size() > 1 && x.zps.size() != x.scales.size()) return fail("zero-point vector of tensor " + x.name + " has neither 1 nor as many entries as its scale vector");
             tensors.push_back(x);
         }
         for (uint32_t i = 0; ok_ && i < vlen(ov); ++i) {
@@ -159,6 +175,13 @@ public:
     bool validate_graph() {
         const int nt = (int)tensors.size();
         auto idx = [&](int t) { return t >= 0 && t < nt; };
+        // a per-channel constant means something only as a convolution's weights or bias: anywhere else it would be computed with
+        // element 0 of its vectors
+        for (const TflOp& op : ops)
+            for (size_t k = 0; k < op.in.size(); ++k)
+                if (idx(op.in[k]) && tensors[op.in[k]].per_channel() &&
+                    !((op.code == TFL_CONV_2D || op.code == TFL_DEPTHWISE_CONV_2D) && (k == 1 || k == 2)))
+                    return fail("per-channel quantisation on tensor " + tensors[op.in[k]].name + ", which is not a convolution's weights or bias");
         for (size_t oi = 0; oi < ops.size(); ++oi) {
             const TflOp& op = ops[oi];
             const std::string at = " (operator " + std::to_string(oi) + ")";
@@ -178,6 +201,11 @@ public:
                     const std::vector<int>& w = tensors[op.in[1]].shape;
                     if (w[1] < 1 || w[2] < 1 || w[0] < 1 || w[3] < 1) return fail("conv: empty kernel" + at);
                     for (int d : tensors[op.in[0]].shape) if (d < 1) return fail("conv: empty input" + at);
+                    const TflTensor& wt = tensors[op.in[1]];
+                    if (wt.per_channel() && wt.qdim != (op.code == TFL_CONV_2D ? 0 : 3))
+                        return fail("conv: per-channel weight scales of tensor " + wt.name + " must run along dimension 0 (CONV_2D) or 3 (DEPTHWISE_CONV_2D)" + at);
+                    if (wt.type == TFL_I8)   // (TFLite's int8 kernels take the weights as symmetric, and so do ours)
+                        for (int z : wt.zps) if (z != 0) return fail("conv: int8 weights must have zero point 0 (tensor " + wt.name + ")" + at);
                     break;
                 }
                 case TFL_ADD:

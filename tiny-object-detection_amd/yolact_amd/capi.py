@@ -144,6 +144,7 @@ SYMBOLS = [
     ("yh_tfl_plan_info", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("yh_tfl_direct_forms", _i, [C.POINTER(_i), _i]),
     ("yh_tfl_op_info", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    ("yh_tfl_op_quant", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     ("yh_tfl_tensor_read", _i, [_vp, _i, _vp, _sz]),
     ("yh_tfl_classify_frame_u32", _i, [_vp, _vp, _i, _i, _i]),
     ("yh_tfl_classify_batch_u32", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -2202,7 +2203,7 @@ def tfl_validate(model_bytes):
     return rc == OK, nt.value, no.value, err.value.decode()
 
 
-_KIND_NP = {1: np.float32, 3: np.uint8, 2: np.int32}
+_KIND_NP = {1: np.float32, 3: np.uint8, 2: np.int32, 9: np.int8}
 TFL_MAX_IMAGES = 512   # YH_TFL_MAX_IMAGES
 
 # YH_TFL_FAM_* (include/yolact_hip_debug.h), by value
@@ -2220,7 +2221,8 @@ def tfl_direct_forms():
 
 
 class TfliteEngine:
-    """RAII wrapper of yh_tfl: the reference's own model family (uint8 MobileNetV2-style .tflite)."""
+    """RAII wrapper of yh_tfl: the reference's own model family (MobileNetV2-style .tflite), uint8 per-tensor quantised or int8
+    with per-tensor / per-channel weight scales and uint8 / float32 edges."""
 
     def __init__(self, model_bytes, device=0, tune=None, max_images=2):
         """max_images: images per invoke the handle has room for (yh_tfl_create_batch: 1 .. TFL_MAX_IMAGES; classify_batch on n frames
@@ -2293,6 +2295,13 @@ class TfliteEngine:
         f, r, g, d = _i(), _i(), _i(), _i()
         self._chk(self.L.yh_tfl_op_info(self.h, op, C.byref(f), C.byref(r), C.byref(g), C.byref(d)))
         return dict(family=TFL_FAMILIES[f.value] if f.value >= 0 else None, row=r.value, grouped=bool(g.value), folded=bool(d.value))
+
+    def op_quant(self, op):
+        """yh_tfl_op_quant: dict(signed = the operator's output is int8 (True), uint8 (False) or another type (None); per_channel =
+        it is an int8 convolution whose weights carry one scale per output channel)."""
+        a, b = _i(), _i()
+        self._chk(self.L.yh_tfl_op_quant(self.h, op, C.byref(a), C.byref(b)))
+        return dict(signed=None if a.value < 0 else bool(a.value), per_channel=bool(b.value))
 
     def tensor(self, index, shape, dtype):
         nb = getattr(self, "nb", 1)

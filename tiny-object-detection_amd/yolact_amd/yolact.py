@@ -18,8 +18,8 @@ class Yolact:
              max_batch=2):
         """reference: `Yolact::init()` (src/yolact.rs:17-37), which hard-codes
         "data/FRC_model_edgetpu.tflite". Here:
-          * model_path = a non-EdgeTPU .tflite (the reference's data/FRC_model.tflite family: uint8
-            MobileNetV2-style graph) -> the TFLite model path runs it on the GPU, with room for max_batch images per
+          * model_path = a non-EdgeTPU .tflite (the reference's data/FRC_model.tflite family: a uint8 or int8
+            MobileNetV2-style graph with a uint8 input and a uint8 or float32 output 4) -> the TFLite model path runs it on the GPU, with room for max_batch images per
             invoke (TfliteEngine's max_images; classify_batch on n frames needs 2n);
           * otherwise the YOLACT R50/R101 engine at `input_size` (224 = the reference's tile,
             yolact.rs:143-144) with `weights` (a YHW1 blob) or the seeded synthetic blob; max_batch tiles

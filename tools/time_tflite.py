@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--graph", type=int, default=-1, help="yh_tuning.tfl_graph: 1 = hipGraph replay of the plan, 0 = eager launches, -1 = library default")
 ap.add_argument("--invokes", type=int, default=220)
 ap.add_argument("--batch", action="store_true", help="the classify batch (yh_tfl_classify_batch_u32): ms per 640x480 frame for n = 1 .. 32 frames, three paths alternated in one process (profiles/tfl_classify_batch_timings.txt)")
+ap.add_argument("--int8", action="store_true", help="the int8 / per-channel twin of the stand-in (tests/tfl_models_q.py) beside the uint8 stand-in, interleaved in one process: the invoke at 1, 2 and 16 images, or with --batch the classify batch at n = 4, 8, 32 (profiles/tfl_int8_timings.txt)")
 a = ap.parse_args()
 rng = np.random.default_rng(0)
 model = M.mobilenetv2_yolact(rng)
@@ -59,6 +60,45 @@ def batch_arm():
     eng.close()
 
 
+def int8_arm():
+    """The uint8 stand-in and its int8 twin on two handles, alternated round by round: ms per invoke (set_input + invoke + read
+    output 4) at 1, 2 and 16 images, or per 640x480 frame of the classify batch (host in, host out). The uint8 rows are the yardstick."""
+    import tfl_builder_q as BQ, tfl_models_q as MQ
+    twin = MQ.mobilenetv2_yolact_q(np.random.default_rng(0))
+    rounds = 15
+    engs = {"uint8": ya.TfliteEngine(buf, max_images=64), "int8": ya.TfliteEngine(BQ.serialize(twin), max_images=64)}
+    plain = ya.TfliteEngine(BQ.serialize(twin), tune=dict(tfl_fuse=0, tfl_group=0))
+    x = rng.integers(0, 256, (16, 224, 224, 3), dtype=np.uint8)
+    for e in (engs["int8"], plain):
+        e.set_batch(2); e.set_input(x[:2]); e.invoke()
+    assert all(np.array_equal(engs["int8"].output(k), plain.output(k)) for k in range(plain.output_count()))   # (fused and grouped = one launch per operator)
+    plain.close()
+    print("plans:", {k: e.plan_summary() for k, e in engs.items()})
+    def row(label, fns):
+        for _ in range(3):
+            for f in fns.values(): f()
+        t = np.array([[clock(f) for f in fns.values()] for _ in range(rounds)])
+        med, lo, hi = np.median(t, 0), t.min(0), t.max(0)
+        print(f"{label:>12} " + " ".join(f"{k:>6} {med[i]:8.3f} ({lo[i]:6.3f} .. {hi[i]:6.3f})" for i, k in enumerate(fns)) + f"   int8/uint8 {med[1] / med[0]:.3f}")
+    if a.batch:
+        W, H = 640, 480
+        frames = rng.integers(0, 2 ** 32, (32, H, W), dtype=np.uint64).astype(np.uint32)
+        out = np.empty_like(frames)
+        print(f"classify batch, frames {W}x{H}, COMPAT_SANE, host in / host out; ms per BATCH, median of {rounds} alternated rounds (min .. max)")
+        for n in (4, 8, 32):
+            row(f"n = {n}", {k: (lambda e=e, n=n: e.classify_batch(frames_u32=frames[:n], n=n, width=W, height=H, mode=ya.COMPAT_SANE, out=out[:n])) for k, e in engs.items()})
+    else:
+        print(f"invoke 224x224 (set_input + invoke + read output 4); ms per invoke, median of {rounds} alternated rounds (min .. max)")
+        for nb in (1, 2, 16):
+            def one(e, nb=nb):
+                e.set_batch(nb); e.set_input(x[:nb]); e.invoke(); return e.output(4)
+            row(f"{nb} images", {k: (lambda e=e: one(e)) for k, e in engs.items()})
+    for e in engs.values(): e.close()
+
+
+if a.int8:
+    int8_arm()
+    sys.exit(0)
 if a.batch:
     batch_arm()
     sys.exit(0)
