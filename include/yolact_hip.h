@@ -491,6 +491,57 @@ int yh_tfl_classify_batch_u32(yh_tfl* h, const uint32_t* frames, int32_t frames_
  * yh_tfl_classify_batch_u32 on the handle. It is what yh_scene_batch_stage_frames(.., frames_on_device = 1) takes. */
 const uint32_t* yh_tfl_classify_batch_device_frames(const yh_tfl* h);
 
+/* ---- TFLite detections: the detection tail on the model's own output tensors (DESIGN.md section 11 "TFLite detections") -----
+ * The reference stops at an argmax over output 4 (src/yolact.rs:3-5, :93-95, :108). The model's other four outputs - loc [1,P,4],
+ * conf [1,P,C], mask [1,P,32], proto [1,hp,wp,32] - are what a YOLACT detection tail reads: softmax and threshold, per-class
+ * top-k, SSD decode, Fast-NMS, top max_dets, mask assembly. yh_tfl_detect_setup binds that tail to four outputs of the handle's
+ * model; it then runs on the device on the tensors as they lie - uint8, int8 or float32, no host copy, no f16 copy - for every
+ * image of the last invoke. What is computed: a quantised element's value is (float)(q - zero_point) * scale (one f32 multiply);
+ * scores, candidates, boxes, NMS, ranking and crop windows are the engine's tail (yh_evaluate) on those values, operation for
+ * operation, with priors indexed by the prior; the mask bit of a pixel inside a detection's crop window is the sign of the exact
+ * integer sum over k of (proto_q[k] - z_proto)(mask_q[k] - z_mask) when mask and proto are both quantised, and the engine's
+ * fmaf chain on the values above when either is float32.
+ * A .tflite file holds no priors: the host passes them, [P][4] cx, cy, w, h (yolact_amd.tfl_priors builds YOLACT's).
+ * yh_tfl_detect_setup checks everything before it allocates, and yh_tfl_last_error names the rule: each of the four tensors is a
+ * graph output of kind YH_KIND_U8 / _I8 / _F32 with one scale and zero point (a per-channel head is refused), shaped as above with
+ * one P that equals n_priors and C in 2 .. 81 (a model whose heads are transposed or that has another number of prototypes than
+ * 32 is refused); a quantised tensor's scale is finite and positive and its zero point inside its type's range; top_k, max_dets
+ * and (C - 1) * top_k within the engine's limits (256, 128, 16384); max_images in 0 .. the handle's, and 1 for a model with an
+ * operator along the image axis. A refused setup returns YH_EINVAL and leaves the handle - an earlier setup included - as it was.
+ * A second setup replaces the first.
+ * MEMORY: the workspaces are allocated by the setup, never by a later call, for max_images images. The candidate lists alone take
+ *     max_images * (C - 1) * P * 8 bytes
+ * (every (class, prior) pair may pass the threshold) - 128 MB at 64 images of an 81-class model with 3 117 priors (MobileNetV2-FPN at
+ * 224 x 224), 1.02 GB at 512 - and the masks max_images * max_dets * hp * wp bytes; the rest is small beside them
+ * ((C - 1) * top_k * 24 + max_dets * 176 bytes per image). Hence max_images: a handle made for 512 images (classify batches)
+ * that detects on 8 at a time pays for 8.
+ * yh_tfl_evaluate: yh_tfl_invoke and the tail on every image of that invoke; asynchronous, the tail's four launches follow the
+ * invoke on the handle's stream (eager launches, outside the invoke's captured graph). yh_tfl_detect: the tail alone on the
+ * outputs of the last invoke, whoever made it (yh_tfl_invoke, yh_tfl_classify_frame_u32, yh_tfl_classify_batch_u32: its 2n tiles).
+ * States: yh_tfl_evaluate / yh_tfl_detect before a setup, yh_tfl_detect before any invoke, and yh_tfl_read_detections when no tail
+ * has run since the last yh_tfl_set_input or invoke return YH_ESTATE; a batch larger than the setup's max_images YH_EINVAL. A
+ * refused call has touched nothing. */
+typedef struct yh_tfl_detect_config {
+    int32_t outputs[4];   /* indices into the model's outputs: loc, conf, mask, proto; yh_tfl_default_detect_config sets 0,1,2,3 */
+    int32_t top_k, max_dets;          /* 200, 100; limits as the engine's tail (256, 128) */
+    float conf_thresh, nms_thresh;    /* 0.05, 0.5 */
+    int32_t max_images;               /* images the workspaces are sized for; 0: the handle's max_images */
+    int32_t reserved[4];              /* zero */
+} yh_tfl_detect_config;
+void yh_tfl_default_detect_config(yh_tfl_detect_config* cfg);
+int yh_tfl_detect_setup(yh_tfl* h, const yh_tfl_detect_config* cfg, const float* priors_host /* [P][4] cx,cy,w,h */, int32_t n_priors);
+int yh_tfl_evaluate(yh_tfl* h);
+int yh_tfl_detect(yh_tfl* h);
+/* As yh_read_detections, for image `image` of the last yh_tfl_evaluate / yh_tfl_detect: the one wait. */
+int yh_tfl_read_detections(yh_tfl* h, int32_t image, int32_t* count, yh_detection* dets, int32_t dets_capacity,
+                           uint8_t* masks, size_t masks_capacity);
+int yh_tfl_proto_dims(const yh_tfl* h, int32_t dims[2]);   /* {hp, wp} of the setup; YH_EINVAL before one */
+/* The setup's result buffers on the device (NULL before a setup; valid until the next setup or yh_tfl_destroy; written by the
+ * tail's launches on the handle's stream): what an instance frame painted from these detections will read. */
+const yh_detection* yh_tfl_detections_device(const yh_tfl* h);   /* [max_images][max_dets] */
+const int32_t*      yh_tfl_detection_counts_device(const yh_tfl* h);
+const uint8_t*      yh_tfl_masks_device(const yh_tfl* h);        /* [max_images][max_dets][hp*wp] */
+
 /* ---- scene back-end: append_scene's two compute dispatches (src/scene.rs:147-331) --------------
  * shaders/pt_cloud.comp (depth + class image -> bird's-eye height map with sigmoid bumps, ball centroids) and
  * shaders/pt_cloud_weights.comp (world positions, 8-neighbour edge lengths) as HIP kernels, one lane per pixel in

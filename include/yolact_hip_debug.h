@@ -471,6 +471,22 @@ int yh_op_classify_pre_batch(yh_engine* h, const uint32_t* frames_host, int32_t 
 int yh_op_classify_post_batch(yh_engine* h, const float* cells_host /* [2n][cells][C] */, int32_t n, int32_t w, int32_t hgt,
                               int32_t compat_mode, uint32_t* frames_host /* [n][hgt][w] */, int32_t* diverged_host);
 
+/* Measurement: the handle's detection tail (yh_tfl_detect_setup) on the outputs of the last invoke, `reps` times, each of its four
+ * launches (softmax and candidates, per-class NMS, top max_dets, masks) between two events on the handle's stream: ms_out[4], the
+ * mean ms per launch. Synchronous; the states of yh_tfl_detect. */
+int yh_tfl_detect_stage_times(yh_tfl* h, int32_t reps, float* ms_out);
+/* The TFLite detection tail (yh_tfl_detect_setup's kernels) on caller-provided bytes, no model involved: what yh_op_detect is to
+ * the engine. n images; loc [n][P][4], conf [n][P][C], mask [n][P][32], proto [n][hp][wp][32] in host memory, each with its kind
+ * (YH_KIND_U8, YH_KIND_I8 or YH_KIND_F32), scale and zero point (ignored for float32); priors [P][4]. The handle gives the device,
+ * the stream and the error text only; its model and its detect setup are not touched. Checks as yh_tfl_detect_setup's (YH_EINVAL).
+ * Synchronous; the results are read with yh_tfl_read_detections. */
+int yh_tfl_op_detect(yh_tfl* h, int32_t n, int32_t P, int32_t C, int32_t hp, int32_t wp,
+                     const void* loc, int32_t loc_kind, float loc_scale, int32_t loc_zp,
+                     const void* conf, int32_t conf_kind, float conf_scale, int32_t conf_zp,
+                     const void* mask, int32_t mask_kind, float mask_scale, int32_t mask_zp,
+                     const void* proto, int32_t proto_kind, float proto_scale, int32_t proto_zp,
+                     const float* priors, int32_t top_k, int32_t max_dets, float conf_thresh, float nms_thresh);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "classify_geo.h"
+#include "tfl_detect.h"
 #include "tflite_exec.h"
 #include "tflite_model.h"
 #include "yh_internal.h"
@@ -117,6 +118,13 @@ struct yh_tfl {
     size_t clsb_frames_cap = 0, clsb_cells_cap = 0, clsb_codes_cap = 0, clsb_div_cap = 0;
     yh::ClassifyGeo clsb_geo;         // the resize tables of the last geometry and the pre kernel's plan (classify_geo.h)
     int clsb_n = -1;                  // frames of the last batch; -1: no batch
+    // detection tail on the model's own outputs (yh_tfl_detect_setup; DESIGN.md section 11 "TFLite detections"): the setup's
+    // parameters and workspaces, the test entry's own (yh_tfl_op_detect), and whose results are current
+    struct DetSet { bool ready = false; yh::TflDetectParams p{}; int max_images = 0; std::vector<void*> bufs; std::vector<int> sig; };
+    DetSet det, opdet;
+    const DetSet* det_last = nullptr; // what yh_tfl_read_detections shows; nullptr: nothing current (no tail yet, or a newer input / invoke)
+    int det_last_n = 0;               // its images
+    int last_nb = 0;                  // images of the last invoke; 0: none yet
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
 
@@ -701,7 +709,8 @@ int enqueue_plan(yh_tfl* h) {
 // memory access fault WITHOUT the profiler (engine.hip, enqueue_all), so this library never builds a single-branch graph.
 int run_plan(yh_tfl* h) {
     if (int rc = group_tables(h, h->nb)) return rc;   // (an image count's first invoke: before the capture and before any launch)
-    if (!h->use_graph) return enqueue_plan(h);
+    h->det_last = nullptr;   // (detections of an earlier invoke are no longer the handle's state)
+    if (!h->use_graph) { const int rc = enqueue_plan(h); if (!rc) h->last_nb = h->nb; return rc; }
     hipGraphExec_t& gexec = h->gexecs[h->nb - 1];
     if (!gexec) {
         hipGraph_t g = nullptr;
@@ -731,6 +740,7 @@ int run_plan(yh_tfl* h) {
         if (ei != hipSuccess) { gexec = nullptr; return h->fail(YH_EHIP, std::string("tflite plan instantiate: ") + hipGetErrorString(ei)); }
     }
     TCHK(h, hipGraphLaunch(gexec, h->stream));
+    h->last_nb = h->nb;
     return YH_OK;
 }
 
@@ -774,6 +784,71 @@ int batch_grow(yh_tfl* h, void** p, size_t* cap, size_t bytes) {
     *p = nullptr; *cap = 0;
     if (hipMalloc(p, bytes) != hipSuccess) return h->fail(YH_ENOMEM, "hipMalloc classify batch");
     *cap = bytes;
+    return YH_OK;
+}
+
+// ---- detection tail on the model's own outputs (DESIGN.md section 11 "TFLite detections") ----
+void det_release(yh_tfl::DetSet& d) {
+    for (void* q : d.bufs) hipFree(q);
+    d = yh_tfl::DetSet();
+}
+// What the tail's kernels hold (the engine's limits: detect.hip); nullptr: fine. Nothing is touched.
+const char* det_limits_check(int P, int C, int hp, int wp, int top_k, int max_dets, float conf_thresh, float nms_thresh) {
+    if (P < 1) return "detect: the number of priors must be at least 1";
+    if (C < 2 || C > kTdClassesMax) return "detect: conf must hold 2 .. 81 classes per prior (background first)";
+    if (hp < 1 || hp > 4096 || wp < 1 || wp > 4096) return "detect: proto must be 1 .. 4096 pixels high and wide";
+    if (top_k < 1 || top_k > kTdTopkMax) return "detect: top_k must be 1 .. 256 (YH_TOPK_MAX)";
+    if (max_dets < 1 || max_dets > kTdDetsMax) return "detect: max_dets must be 1 .. 128 (YH_DETS_MAX)";
+    if ((C - 1) * top_k > kTdSlotsMax) return "detect: (classes - 1) x top_k must not exceed 16384";
+    if (!(conf_thresh >= 0.0f) || !(nms_thresh >= 0.0f)) return "detect: conf_thresh and nms_thresh must be non-negative numbers";
+    return nullptr;
+}
+const char* det_quant_check(int kind, float scale, int zp, const char* name, std::string* why) {
+    if (kind == TQ_F32) return nullptr;
+    if (!(scale > 0.0f) || !std::isfinite(scale)) { *why = std::string("detect: the scale of ") + name + " must be finite and positive"; return why->c_str(); }
+    if (kind == TQ_U8 ? (zp < 0 || zp > 255) : (zp < -128 || zp > 127)) { *why = std::string("detect: the zero point of ") + name + " lies outside its type's range"; return why->c_str(); }
+    return nullptr;
+}
+// The workspaces for n images of d.p's geometry (P, C, hp, wp, top_k, max_dets set by the caller) and the priors; every buffer is
+// recorded in d.bufs as it is made, so a failure half way is undone by det_release.
+int det_alloc(yh_tfl* h, yh_tfl::DetSet& d, int n, const float* priors_host) {
+    TflDetectParams& q = d.p;
+    const size_t N = (size_t)n, Cf = (size_t)q.C - 1, px = (size_t)q.hp * q.wp;
+    void* a;
+#define TD_AL(field, type, count) do { a = nullptr; if (hipMalloc(&a, sizeof(type) * (size_t)(count)) != hipSuccess) { (void)hipGetLastError(); return h->fail(YH_ENOMEM, "hipMalloc detect workspaces (see yh_tfl_detect_config.max_images)"); } d.bufs.push_back(a); q.field = (type*)a; } while (0)
+    TD_AL(cls_count, int, N * Cf);
+    TD_AL(cand, uint2, N * Cf * q.P);
+    TD_AL(surv_score, float, N * Cf * q.top_k);
+    TD_AL(surv_prior, int, N * Cf * q.top_k);
+    TD_AL(surv_box, float, N * Cf * q.top_k * 4);
+    TD_AL(det_count, int, N);
+    TD_AL(dets, yh_detection, N * q.max_dets);
+    TD_AL(det_crop, float, N * q.max_dets * 4);
+    TD_AL(det_csum, int, N * q.max_dets);
+    TD_AL(masks, uint8_t, N * q.max_dets * px + 16);
+    a = nullptr;
+    if (hipMalloc(&a, sizeof(float) * N * q.max_dets * 32) != hipSuccess) { (void)hipGetLastError(); return h->fail(YH_ENOMEM, "hipMalloc detect workspaces"); }
+    d.bufs.push_back(a); q.det_coef = a;
+    float* pr = nullptr;
+    if (hipMalloc((void**)&pr, sizeof(float) * (size_t)q.P * 4) != hipSuccess) { (void)hipGetLastError(); return h->fail(YH_ENOMEM, "hipMalloc detect priors"); }
+    d.bufs.push_back(pr); q.priors = pr;
+#undef TD_AL
+    // the candidate counters start at zero and their one consumer (K2q) leaves them at zero; the detection counts start at zero too
+    if (hipMemcpy(pr, priors_host, sizeof(float) * (size_t)q.P * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(q.cls_count, 0, sizeof(int) * N * Cf) != hipSuccess || hipMemset(q.det_count, 0, sizeof(int) * N) != hipSuccess)
+        return h->fail(YH_EHIP, "detect workspace initialisation failed");
+    d.max_images = n;
+    d.ready = true;
+    return YH_OK;
+}
+// The tail's four launches on the setup's tensors for the n images of the last invoke, eagerly on the handle's stream.
+int det_run(yh_tfl* h, int n) {
+    h->det.p.n = n;
+    TraceRange tr("yh_tfl:detect");
+    const hipError_t e = launch_tfl_detect(h->det.p, h->stream);
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("tflite detect: ") + hipGetErrorString(e));
+    h->det_last = &h->det;
+    h->det_last_n = n;
     return YH_OK;
 }
 
@@ -934,6 +1009,8 @@ void yh_tfl_destroy(yh_tfl* h) {
                         h->clsb_frames, h->clsb_cells, h->clsb_codes, h->clsb_div };
     for (void* p : scratch) if (p) hipFree(p);
     classify_geo_free(&h->clsb_geo);
+    for (void* p : h->det.bufs) hipFree(p);
+    for (void* p : h->opdet.bufs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -964,6 +1041,7 @@ int yh_tfl_set_input(yh_tfl* h, const void* data, size_t nbytes) {
     if (!h || !data) return YH_EINVAL;
     const TflTensor& t = h->m.tensors[h->m.inputs[0]];
     if (nbytes != t.count() * t.elem() * (size_t)h->nb) return h->fail(YH_EINVAL, "input size mismatch");   // the reference only warns (yolact.rs:151-158)
+    h->det_last = nullptr;
     TCHK(h, hipSetDevice(h->dev));
     TCHK(h, hipMemcpyAsync(h->tens[h->m.inputs[0]], data, nbytes, hipMemcpyHostToDevice, h->stream));
     // copy_from_slice semantics (yolact.rs:161-162): the caller's buffer is free again on return. From pageable memory the
@@ -1118,5 +1196,212 @@ int yh_tfl_classify_batch_u32(yh_tfl* h, const uint32_t* frames, int32_t frames_
 }
 
 const uint32_t* yh_tfl_classify_batch_device_frames(const yh_tfl* h) { return h && h->clsb_n >= 1 ? h->clsb_frames : nullptr; }
+
+void yh_tfl_default_detect_config(yh_tfl_detect_config* cfg) {
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    for (int i = 0; i < 4; ++i) cfg->outputs[i] = i;
+    cfg->top_k = 200; cfg->max_dets = 100;
+    cfg->conf_thresh = 0.05f; cfg->nms_thresh = 0.5f;
+}
+
+int yh_tfl_detect_setup(yh_tfl* h, const yh_tfl_detect_config* cfg, const float* priors_host, int32_t n_priors) {
+    if (!h || !cfg || !priors_host) return YH_EINVAL;
+    // every rule first: a refused setup has touched nothing, and an earlier setup stays
+    static const char* role[4] = { "loc", "conf", "mask", "proto" };
+    const TflTensor* t[4];
+    for (int i = 0; i < 4; ++i) {
+        if (cfg->outputs[i] < 0 || cfg->outputs[i] >= (int)h->m.outputs.size())
+            return h->fail(YH_EINVAL, std::string("detect setup: outputs[") + role[i] + "] is not an index into the model's outputs");
+        t[i] = &h->m.tensors[h->m.outputs[cfg->outputs[i]]];
+        if (t[i]->type != TFL_U8 && t[i]->type != TFL_I8 && t[i]->type != TFL_F32)
+            return h->fail(YH_EINVAL, std::string("detect setup: ") + role[i] + " ('" + t[i]->name + "') must be uint8, int8 or float32");
+        // (a constant is stored once, not per image - tensor_alloc_bytes - and the tail strides over images; a graph output is never
+        // folded away by fuse_plan, which counts it as a reader, so there is no "never written" case to refuse)
+        if (t[i]->data)
+            return h->fail(YH_EINVAL, std::string("detect setup: ") + role[i] + " ('" + t[i]->name + "') is a constant of the model, not a tensor an invoke writes");
+        if (t[i]->type != TFL_F32 && (t[i]->per_channel() || t[i]->zps.size() > 1))
+            return h->fail(YH_EINVAL, std::string("detect setup: ") + role[i] + " ('" + t[i]->name + "') is quantised per channel: a head tensor needs one scale and zero point");
+    }
+    for (int i = 0; i < 4; ++i) if (cfg->reserved[i] != 0) return h->fail(YH_EINVAL, "detect setup: reserved fields must be zero");
+    const std::vector<int>&ls = t[0]->shape, &cs = t[1]->shape, &ms = t[2]->shape, &ps = t[3]->shape;
+    if (ls.size() != 3 || ls[0] != 1 || ls[2] != 4) return h->fail(YH_EINVAL, "detect setup: loc must be [1,P,4]");
+    if (cs.size() != 3 || cs[0] != 1 || cs[2] < 2) return h->fail(YH_EINVAL, "detect setup: conf must be [1,P,C] with C >= 2");
+    if (ms.size() != 3 || ms[0] != 1 || ms[2] != 32) return h->fail(YH_EINVAL, "detect setup: mask must be [1,P,32] (a model with another number of prototypes, or transposed heads, is not supported)");
+    if (ps.size() != 4 || ps[0] != 1 || ps[3] != 32) return h->fail(YH_EINVAL, "detect setup: proto must be [1,hp,wp,32] (a model with another number of prototypes, or transposed heads, is not supported)");
+    if (ls[1] != cs[1] || ls[1] != ms[1]) return h->fail(YH_EINVAL, "detect setup: loc, conf and mask disagree on the number of priors P");
+    if (ls[1] != n_priors) return h->fail(YH_EINVAL, "detect setup: n_priors is " + std::to_string(n_priors) + ", the model's heads hold P = " + std::to_string(ls[1]));
+    if (const char* why = det_limits_check(ls[1], cs[2], ps[1], ps[2], cfg->top_k, cfg->max_dets, cfg->conf_thresh, cfg->nms_thresh)) return h->fail(YH_EINVAL, why);
+    TflHead hd[4];
+    for (int i = 0; i < 4; ++i) {
+        hd[i].p = h->tens[h->m.outputs[cfg->outputs[i]]];
+        hd[i].kind = t[i]->type == TFL_U8 ? TQ_U8 : (t[i]->type == TFL_I8 ? TQ_I8 : TQ_F32);
+        hd[i].scale = t[i]->type == TFL_F32 ? 1.0f : t[i]->scale;
+        hd[i].zp = t[i]->type == TFL_F32 ? 0 : t[i]->zp;
+        hd[i].stride = (long long)t[i]->count();
+        std::string why;
+        if (det_quant_check(hd[i].kind, hd[i].scale, hd[i].zp, role[i], &why)) return h->fail(YH_EINVAL, why);
+    }
+    if (cfg->max_images < 0 || cfg->max_images > h->max_images) return h->fail(YH_EINVAL, "detect setup: max_images must be 0 (the handle's) .. the handle's max_images");
+    const int mi = cfg->max_images ? cfg->max_images : h->max_images;
+    if (mi > 1 && !h->batch_ok) return h->fail(YH_EINVAL, "detect setup: an operator of this model works along the image axis (one image per invoke): set max_images = 1");
+    TCHK(h, hipSetDevice(h->dev));
+    yh_tfl::DetSet nd;
+    nd.p.loc = hd[0]; nd.p.conf = hd[1]; nd.p.mask = hd[2]; nd.p.proto = hd[3];
+    nd.p.P = ls[1]; nd.p.C = cs[2]; nd.p.hp = ps[1]; nd.p.wp = ps[2];
+    nd.p.top_k = cfg->top_k; nd.p.max_dets = cfg->max_dets;
+    nd.p.conf_thresh = cfg->conf_thresh; nd.p.nms_thresh = cfg->nms_thresh;
+    nd.p.int_mask = hd[2].kind != TQ_F32 && hd[3].kind != TQ_F32 ? 1 : 0;
+    if (int rc = det_alloc(h, nd, mi, priors_host)) { det_release(nd); return rc; }
+    // a second setup replaces the first (whose launches, if any are in flight, finish first)
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { det_release(nd); return h->fail(YH_EHIP, "detect setup: hipStreamSynchronize failed"); }
+    if (h->det_last == &h->det) h->det_last = nullptr;
+    det_release(h->det);
+    h->det = nd;
+    return YH_OK;
+}
+
+int yh_tfl_evaluate(yh_tfl* h) {
+    if (!h) return YH_EINVAL;
+    if (!h->det.ready) return h->fail(YH_ESTATE, "yh_tfl_evaluate before yh_tfl_detect_setup");
+    if (h->nb > h->det.max_images) return h->fail(YH_EINVAL, "the batch exceeds the detect setup's max_images");
+    TCHK(h, hipSetDevice(h->dev));
+    TraceRange tr("yh_tfl_evaluate");
+    if (int rc = run_plan(h)) return rc;
+    return det_run(h, h->last_nb);
+}
+
+int yh_tfl_detect(yh_tfl* h) {
+    if (!h) return YH_EINVAL;
+    if (!h->det.ready) return h->fail(YH_ESTATE, "yh_tfl_detect before yh_tfl_detect_setup");
+    if (h->last_nb < 1) return h->fail(YH_ESTATE, "yh_tfl_detect before any invoke");
+    if (h->last_nb > h->det.max_images) return h->fail(YH_EINVAL, "the last invoke's batch exceeds the detect setup's max_images");
+    TCHK(h, hipSetDevice(h->dev));
+    return det_run(h, h->last_nb);
+}
+
+int yh_tfl_read_detections(yh_tfl* h, int32_t image, int32_t* count, yh_detection* dets, int32_t cap, uint8_t* masks, size_t masks_cap) {
+    if (!h || !count) return YH_EINVAL;
+    if (!h->det_last) return h->fail(YH_ESTATE, "no detections: yh_tfl_evaluate / yh_tfl_detect has not run since the last yh_tfl_set_input or invoke");
+    if (image < 0 || image >= h->det_last_n) return h->fail(YH_EINVAL, "image out of range");
+    const TflDetectParams& q = h->det_last->p;
+    TCHK(h, hipSetDevice(h->dev));
+    TraceRange tr("yh_tfl_read_detections");
+    TCHK(h, hipStreamSynchronize(h->stream));
+    int nd = 0;
+    TCHK(h, hipMemcpy(&nd, q.det_count + image, 4, hipMemcpyDeviceToHost));
+    *count = nd;
+    if (dets) {
+        if (cap < nd) return h->fail(YH_EINVAL, "dets capacity too small");
+        TCHK(h, hipMemcpy(dets, q.dets + (size_t)image * q.max_dets, sizeof(yh_detection) * (size_t)nd, hipMemcpyDeviceToHost));
+    }
+    if (masks) {
+        const size_t px = (size_t)q.hp * q.wp;
+        if (masks_cap < px * nd) return h->fail(YH_EINVAL, "masks capacity too small");
+        TCHK(h, hipMemcpy(masks, q.masks + (size_t)image * q.max_dets * px, px * nd, hipMemcpyDeviceToHost));
+    }
+    return YH_OK;
+}
+
+int yh_tfl_proto_dims(const yh_tfl* h, int32_t dims[2]) {
+    if (!h || !dims || !h->det.ready) return YH_EINVAL;
+    dims[0] = h->det.p.hp; dims[1] = h->det.p.wp;
+    return YH_OK;
+}
+const yh_detection* yh_tfl_detections_device(const yh_tfl* h) { return h && h->det.ready ? h->det.p.dets : nullptr; }
+const int32_t* yh_tfl_detection_counts_device(const yh_tfl* h) { return h && h->det.ready ? h->det.p.det_count : nullptr; }
+const uint8_t* yh_tfl_masks_device(const yh_tfl* h) { return h && h->det.ready ? h->det.p.masks : nullptr; }
+
+// The setup's tail on the outputs of the last invoke, `reps` times, each of its launches between two events: ms per launch (mean).
+int yh_tfl_detect_stage_times(yh_tfl* h, int32_t reps, float* ms_out) {
+    if (!h || !ms_out || reps < 1) return YH_EINVAL;
+    if (!h->det.ready) return h->fail(YH_ESTATE, "yh_tfl_detect_stage_times before yh_tfl_detect_setup");
+    if (h->last_nb < 1) return h->fail(YH_ESTATE, "yh_tfl_detect_stage_times before any invoke");
+    if (h->last_nb > h->det.max_images) return h->fail(YH_EINVAL, "the last invoke's batch exceeds the detect setup's max_images");
+    TCHK(h, hipSetDevice(h->dev));
+    const int ns = tfl_detect_launch_count();
+    std::vector<hipEvent_t> ev((size_t)ns + 1, nullptr);
+    for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) { for (hipEvent_t& f : ev) if (f) hipEventDestroy(f); return h->fail(YH_EHIP, "hipEventCreate"); }
+    std::vector<double> sum((size_t)ns, 0.0);
+    h->det.p.n = h->last_nb;
+    hipError_t e = hipSuccess;
+    for (int r = 0; r < reps && e == hipSuccess; ++r) {
+        e = hipEventRecord(ev[0], h->stream);
+        for (int st = 0; st < ns && e == hipSuccess; ++st) {
+            e = launch_tfl_detect_stage(h->det.p, st, h->stream);
+            if (e == hipSuccess) e = hipEventRecord(ev[(size_t)st + 1], h->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        for (int st = 0; st < ns && e == hipSuccess; ++st) { float ms = 0.0f; e = hipEventElapsedTime(&ms, ev[(size_t)st], ev[(size_t)st + 1]); sum[(size_t)st] += ms; }
+    }
+    for (hipEvent_t& f : ev) hipEventDestroy(f);
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("detect stage times: ") + hipGetErrorString(e));
+    for (int st = 0; st < ns; ++st) ms_out[st] = (float)(sum[(size_t)st] / reps);
+    h->det_last = &h->det;
+    h->det_last_n = h->last_nb;
+    return YH_OK;
+}
+
+// The tail on caller-provided bytes, no model involved (include/yolact_hip_debug.h): buffers and workspaces of its own, kept from one
+// call to the next of the same geometry, kinds and limits (as they were left), made anew by any other call.
+int yh_tfl_op_detect(yh_tfl* h, int32_t n, int32_t P, int32_t C, int32_t hp, int32_t wp,
+                     const void* loc, int32_t loc_kind, float loc_scale, int32_t loc_zp,
+                     const void* conf, int32_t conf_kind, float conf_scale, int32_t conf_zp,
+                     const void* mask, int32_t mask_kind, float mask_scale, int32_t mask_zp,
+                     const void* proto, int32_t proto_kind, float proto_scale, int32_t proto_zp,
+                     const float* priors, int32_t top_k, int32_t max_dets, float conf_thresh, float nms_thresh) {
+    if (!h || !loc || !conf || !mask || !proto || !priors) return YH_EINVAL;
+    if (n < 1 || n > YH_TFL_MAX_IMAGES) return h->fail(YH_EINVAL, "detect op: n must be 1 .. YH_TFL_MAX_IMAGES");
+    if (const char* why = det_limits_check(P, C, hp, wp, top_k, max_dets, conf_thresh, nms_thresh)) return h->fail(YH_EINVAL, why);
+    static const char* role[4] = { "loc", "conf", "mask", "proto" };
+    const void* src[4] = { loc, conf, mask, proto };
+    const int kinds[4] = { loc_kind, conf_kind, mask_kind, proto_kind };
+    const float scales[4] = { loc_scale, conf_scale, mask_scale, proto_scale };
+    const int zps[4] = { loc_zp, conf_zp, mask_zp, proto_zp };
+    const long long per[4] = { (long long)P * 4, (long long)P * C, (long long)P * 32, (long long)hp * wp * 32 };
+    TflHead hd[4];
+    for (int i = 0; i < 4; ++i) {
+        if (kinds[i] != YH_KIND_U8 && kinds[i] != YH_KIND_I8 && kinds[i] != YH_KIND_F32) return h->fail(YH_EINVAL, std::string("detect op: ") + role[i] + " must be YH_KIND_U8, YH_KIND_I8 or YH_KIND_F32");
+        hd[i].kind = kinds[i] == YH_KIND_U8 ? TQ_U8 : (kinds[i] == YH_KIND_I8 ? TQ_I8 : TQ_F32);
+        hd[i].scale = hd[i].kind == TQ_F32 ? 1.0f : scales[i];
+        hd[i].zp = hd[i].kind == TQ_F32 ? 0 : zps[i];
+        hd[i].stride = per[i];
+        std::string why;
+        if (det_quant_check(hd[i].kind, hd[i].scale, hd[i].zp, role[i], &why)) return h->fail(YH_EINVAL, why);
+    }
+    TCHK(h, hipSetDevice(h->dev));
+    TCHK(h, hipStreamSynchronize(h->stream));
+    if (h->det_last == &h->opdet) h->det_last = nullptr;
+    yh_tfl::DetSet& d = h->opdet;
+    // A call of the geometry, kinds and limits of the one before runs on that call's buffers and workspaces AS THEY WERE LEFT
+    // (counters, survivor slots, masks): what a handle's second evaluate meets. Any other call makes them anew.
+    const std::vector<int> sig = { n, P, C, hp, wp, top_k, max_dets, hd[0].kind, hd[1].kind, hd[2].kind, hd[3].kind };
+    const bool reuse = d.ready && d.sig == sig;
+    if (!reuse) det_release(d);
+    for (int i = 0; i < 4; ++i) {   // (16 bytes behind each tensor, as the executor's own allocations have: K1q's last dword may reach past the last byte)
+        const size_t bytes = (size_t)per[i] * (size_t)n * (hd[i].kind == TQ_F32 ? 4 : 1);
+        void* a = reuse ? d.bufs[i] : nullptr;
+        if (!reuse) {
+            if (hipMalloc(&a, bytes + 16) != hipSuccess) { (void)hipGetLastError(); det_release(d); return h->fail(YH_ENOMEM, "hipMalloc detect op tensors"); }
+            d.bufs.push_back(a);
+        }
+        if (hipMemcpy(a, src[i], bytes, hipMemcpyHostToDevice) != hipSuccess) { det_release(d); return h->fail(YH_EHIP, "detect op upload failed"); }
+        hd[i].p = a;
+    }
+    d.p.loc = hd[0]; d.p.conf = hd[1]; d.p.mask = hd[2]; d.p.proto = hd[3];
+    d.p.P = P; d.p.C = C; d.p.hp = hp; d.p.wp = wp; d.p.top_k = top_k; d.p.max_dets = max_dets;
+    d.p.conf_thresh = conf_thresh; d.p.nms_thresh = nms_thresh;
+    d.p.int_mask = hd[2].kind != TQ_F32 && hd[3].kind != TQ_F32 ? 1 : 0;
+    if (reuse) { if (hipMemcpy((void*)d.p.priors, priors, sizeof(float) * (size_t)P * 4, hipMemcpyHostToDevice) != hipSuccess) { det_release(d); return h->fail(YH_EHIP, "detect op upload failed"); } }
+    else if (int rc = det_alloc(h, d, n, priors)) { det_release(d); return rc; }
+    d.sig = sig;
+    d.p.n = n;
+    const hipError_t e = launch_tfl_detect(d.p, h->stream);
+    if (e != hipSuccess) return h->fail(YH_EHIP, std::string("tflite detect op: ") + hipGetErrorString(e));
+    TCHK(h, hipStreamSynchronize(h->stream));
+    h->det_last = &d;
+    h->det_last_n = n;
+    return YH_OK;
+}
 
 }  // extern "C"

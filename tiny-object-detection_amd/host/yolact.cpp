@@ -80,6 +80,31 @@ void Yolact::evaluate(const std::uint8_t* rgb_frames, int n) {
     if (yh_evaluate(engine_) != YH_OK) expect_failed("invoke failed", yh_last_error(engine_));                  // :163
 }
 
+void Yolact::tfl_detect_setup(const float* priors, int n_priors, const yh_tfl_detect_config* cfg) {
+    if (!tfl_) expect_failed("tfl_detect_setup", "this handle runs the YOLACT engine: its tail is evaluate()");
+    yh_tfl_detect_config c;
+    yh_tfl_default_detect_config(&c);
+    if (yh_tfl_detect_setup(tfl_, cfg ? cfg : &c, priors, n_priors) != YH_OK) expect_failed("detect setup failed", yh_tfl_last_error(tfl_));
+}
+
+void Yolact::tfl_evaluate(const std::uint8_t* images, std::size_t nbytes, int n) {
+    if (!tfl_) expect_failed("tfl_evaluate", "this handle runs the YOLACT engine: its tail is evaluate()");
+    if (yh_tfl_set_batch(tfl_, n) != YH_OK || yh_tfl_set_input(tfl_, images, nbytes) != YH_OK) expect_failed("must data", yh_tfl_last_error(tfl_));   // :161-162
+    if (yh_tfl_evaluate(tfl_) != YH_OK) expect_failed("invoke failed", yh_tfl_last_error(tfl_));                                                        // :163
+}
+
+std::vector<yh_detection> Yolact::tfl_detections(int image, std::vector<std::uint8_t>* masks_out) {
+    if (!tfl_) expect_failed("tfl_detections", "this handle runs the YOLACT engine");
+    std::int32_t n = 0, dims[2] = { 0, 0 };
+    if (yh_tfl_read_detections(tfl_, image, &n, nullptr, 0, nullptr, 0) != YH_OK || yh_tfl_proto_dims(tfl_, dims) != YH_OK)
+        expect_failed("must data", yh_tfl_last_error(tfl_));
+    std::vector<yh_detection> dets(static_cast<std::size_t>(n));
+    if (masks_out) masks_out->assign(static_cast<std::size_t>(n) * dims[0] * dims[1], 0);
+    if (yh_tfl_read_detections(tfl_, image, &n, dets.data(), n, masks_out ? masks_out->data() : nullptr, masks_out ? masks_out->size() : 0) != YH_OK)
+        expect_failed("must data", yh_tfl_last_error(tfl_));
+    return dets;
+}
+
 std::vector<std::int32_t> Yolact::instance_frame(int frame, int width, int height, const std::uint8_t* class_map, float min_score,
                                                  std::uint32_t* frame_out) {
     if (!engine_) expect_failed("instance_frame", "the detection tail belongs to the YOLACT engine");

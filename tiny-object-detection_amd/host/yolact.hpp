@@ -83,6 +83,15 @@ public:
                                                                 std::uint32_t* frames_out = nullptr);
     std::vector<std::int32_t> tracks_of(int b);
 
+    // The fused path on a .tflite handle (model_path given): the detection tail on the model's own outputs 0 .. 3, quantised as they
+    // lie (yh_tfl_detect_setup / yh_tfl_evaluate / yh_tfl_read_detections; DESIGN.md section 11 "TFLite detections"). priors: [P][4]
+    // cx, cy, w, h - a .tflite file holds none. cfg: nullptr = yh_tfl_default_detect_config. The handle made by init() holds two
+    // images per invoke, so n is 1 or 2.
+    void tfl_detect_setup(const float* priors, int n_priors, const yh_tfl_detect_config* cfg = nullptr);
+    void tfl_evaluate(const std::uint8_t* images, std::size_t nbytes, int n);
+    // image `image` of that batch: its detections in rank order; masks_out (or nullptr): count x hp x wp bytes of 0 / 1
+    std::vector<yh_detection> tfl_detections(int image, std::vector<std::uint8_t>* masks_out = nullptr);
+
     static std::string version();      // edgetpu::version(), scene.rs:62
 
 private:

@@ -60,6 +60,12 @@ class Detection(C.Structure):
     _fields_ = [("class_id", C.c_int32), ("prior", C.c_int32), ("score", C.c_float), ("box", C.c_float * 4)]
 
 
+class TflDetectConfig(C.Structure):
+    """yh_tfl_detect_config (include/yolact_hip.h)."""
+    _fields_ = [("outputs", C.c_int32 * 4), ("top_k", C.c_int32), ("max_dets", C.c_int32), ("conf_thresh", C.c_float),
+                ("nms_thresh", C.c_float), ("max_images", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 def lib_path():
     return os.path.join(_PKG, "lib", "libyolact_hip.so")
 
@@ -280,6 +286,17 @@ SYMBOLS = [
     ("yh_op_instance_track_batch", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp]),
     ("yh_op_classify_pre_batch", _i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     ("yh_op_classify_post_batch", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    ("yh_tfl_default_detect_config", None, [_vp]),
+    ("yh_tfl_detect_setup", _i, [_vp, _vp, _vp, _i]),
+    ("yh_tfl_evaluate", _i, [_vp]),
+    ("yh_tfl_detect", _i, [_vp]),
+    ("yh_tfl_read_detections", _i, [_vp, _i, C.POINTER(_i), _vp, _i, _vp, _sz]),
+    ("yh_tfl_proto_dims", _i, [_vp, C.POINTER(_i * 2)]),
+    ("yh_tfl_detections_device", _vp, [_vp]),
+    ("yh_tfl_detection_counts_device", _vp, [_vp]),
+    ("yh_tfl_masks_device", _vp, [_vp]),
+    ("yh_tfl_detect_stage_times", _i, [_vp, _i, C.POINTER(_f * 4)]),
+    ("yh_tfl_op_detect", _i, [_vp, _i, _i, _i, _i, _i] + [_vp, _i, _f, _i] * 4 + [_vp, _i, _i, _f, _f]),
 ]
 
 
@@ -2211,6 +2228,27 @@ TFL_FAMILIES = ("conv_scalar", "conv_px8", "conv_dot1", "conv_dot4", "conv_i8_ld
                 "add", "requant", "quantize_f32", "dequantize", "lut", "pad", "resize", "concat", "copy")
 
 
+def tfl_priors(level_sizes, input_size, aspect_ratios=(1.0, 0.5, 2.0), base_scale=24.0):
+    """YOLACT priors [P][4] (cx, cy, w, h; float32) for square feature levels of level_sizes cells at a square input of input_size
+    pixels: level l carries anchors of base_scale * 2^l pixels at a 550-pixel input, one per aspect ratio, square (YOLACT's
+    use_square_anchors) - the engine's prior table (Engine.priors()) in its arithmetic and order: level, row, column, anchor. A
+    .tflite file holds no priors, so TfliteEngine.detect_setup takes these."""
+    f = np.float32
+    S = f(input_size)
+    out = []
+    for l, n in enumerate(level_sizes):
+        scale = f(f(base_scale * 2.0 ** l) * S) / f(550.0)
+        wv = np.array([f(f(scale * np.sqrt(f(a))) / S) for a in aspect_ratios], f)
+        c = (np.arange(n, dtype=f) + f(0.5)) / f(n)
+        q = np.empty((n, n, len(aspect_ratios), 4), f)
+        q[..., 0] = c[None, :, None]
+        q[..., 1] = c[:, None, None]
+        q[..., 2] = wv[None, None, :]
+        q[..., 3] = wv[None, None, :]
+        out.append(q.reshape(-1, 4))
+    return np.ascontiguousarray(np.concatenate(out, 0))
+
+
 def tfl_direct_forms():
     """yh_tfl_direct_forms: the rows (D, once, KK) of the register-fed int8 convolution's table of forms (no GPU)."""
     L = load_library()
@@ -2349,3 +2387,87 @@ class TfliteEngine:
         """Device pointer of the last classify_batch's frames [n][height][width] (None before a batch or after a failed one): what
         SceneBatch.stage_frames(frames_dev_ptr=...) takes."""
         return self.L.yh_tfl_classify_batch_device_frames(self.h)
+
+    # ---- detections on the model's own outputs (DESIGN.md §11 "TFLite detections")
+    def detect_setup(self, priors, **cfg):
+        """yh_tfl_detect_setup: binds the detection tail to four of the model's outputs. priors: float32 [P][4] cx, cy, w, h
+        (tfl_priors). cfg: outputs=(loc, conf, mask, proto) indices into the model's outputs (0, 1, 2, 3), top_k=200, max_dets=100,
+        conf_thresh=0.05, nms_thresh=0.5, max_images=0 (the handle's): the images the workspaces are sized for - the candidate
+        lists alone take max_images * (C - 1) * P * 8 bytes."""
+        c = TflDetectConfig()
+        self.L.yh_tfl_default_detect_config(C.byref(c))
+        for k, v in cfg.items():
+            if k == "outputs":
+                c.outputs[:] = [int(x) for x in v]
+            elif k == "reserved":
+                c.reserved[:] = [int(x) for x in v]
+            else:
+                assert hasattr(c, k), k
+                setattr(c, k, v)
+        pr = np.ascontiguousarray(priors, np.float32)
+        assert pr.ndim == 2 and pr.shape[1] == 4, pr.shape
+        self._chk(self.L.yh_tfl_detect_setup(self.h, C.byref(c), _p(pr), pr.shape[0]))
+        self._det_cfg = c
+
+    def evaluate(self):
+        """yh_tfl_evaluate: invoke + the tail on every image of the batch (asynchronous; detections() waits)."""
+        self._chk(self.L.yh_tfl_evaluate(self.h))
+        self._det_geo = None
+
+    def detect(self):
+        """yh_tfl_detect: the tail alone on the outputs of the last invoke / classify call."""
+        self._chk(self.L.yh_tfl_detect(self.h))
+        self._det_geo = None
+
+    def detect_stage_times(self, reps=20):
+        """yh_tfl_detect_stage_times: mean ms of each of the tail's four launches on the last invoke's outputs, timed by events."""
+        ms = (_f * 4)()
+        self._chk(self.L.yh_tfl_detect_stage_times(self.h, reps, C.byref(ms)))
+        self._det_geo = None
+        return list(ms)
+
+    def proto_dims(self):
+        d = (_i * 2)()
+        self._chk(self.L.yh_tfl_proto_dims(self.h, C.byref(d)))
+        return d[0], d[1]
+
+    def _read_detections(self, image, max_dets, hp, wp, want_masks):
+        nd = C.c_int32()
+        dets = (Detection * max_dets)()
+        masks = np.zeros((max_dets, hp, wp), np.uint8) if want_masks else None
+        self._chk(self.L.yh_tfl_read_detections(self.h, image, C.byref(nd), C.cast(dets, C.c_void_p), max_dets,
+                                                _p(masks) if want_masks else None, masks.size if want_masks else 0))
+        out = [dict(class_id=d.class_id, prior=d.prior, score=d.score, box=tuple(d.box)) for d in dets[:nd.value]]
+        return out, (masks[:nd.value] if want_masks else None)
+
+    def detections(self, image, want_masks=True):
+        """yh_tfl_read_detections for image `image` of the last evaluate / detect / op_detect: (list of dict(class_id, prior, score,
+        box), masks uint8 [nd][hp][wp] or None), as Engine.detections."""
+        geo = getattr(self, "_det_geo", None)   # (op_detect's geometry while its results are the current ones)
+        if geo is None and getattr(self, "_det_cfg", None) is None:   # no setup, no op_detect: the library's own answer (YH_ESTATE)
+            nd = C.c_int32()
+            self._chk(self.L.yh_tfl_read_detections(self.h, image, C.byref(nd), None, 0, None, 0))
+        if geo is None:
+            hp, wp = self.proto_dims()
+            geo = (self._det_cfg.max_dets, hp, wp)
+        return self._read_detections(image, geo[0], geo[1], geo[2], want_masks)
+
+    def op_detect(self, loc, conf, mask, proto, priors, quant=None, top_k=200, max_dets=100, conf_thresh=0.05, nms_thresh=0.5):
+        """yh_tfl_op_detect: the tail on caller-provided tensors, no model involved. loc [n][P][4], conf [n][P][C], mask [n][P][32],
+        proto [n][hp][wp][32], each uint8, int8 or float32; quant: dict role -> (scale, zero_point) for the quantised ones. The
+        results are read with detections()."""
+        arrs, args = [], []
+        for name, a in (("loc", loc), ("conf", conf), ("mask", mask), ("proto", proto)):
+            a = np.ascontiguousarray(a)
+            kind = {np.dtype(np.uint8): 3, np.dtype(np.int8): 9, np.dtype(np.float32): 1}[a.dtype]
+            sc, zp = (quant or {}).get(name, (1.0, 0))
+            arrs.append(a)
+            args += [_p(a), kind, float(sc), int(zp)]
+        n, P, Cc = arrs[1].shape
+        hp, wp = arrs[3].shape[1:3]
+        assert arrs[0].shape == (n, P, 4) and arrs[2].shape == (n, P, 32) and arrs[3].shape == (n, hp, wp, 32)
+        pr = np.ascontiguousarray(priors, np.float32)
+        assert pr.shape == (P, 4)
+        self._det_geo = None
+        self._chk(self.L.yh_tfl_op_detect(self.h, n, P, Cc, hp, wp, *args, _p(pr), top_k, max_dets, conf_thresh, nms_thresh))
+        self._det_geo = (max_dets, hp, wp)

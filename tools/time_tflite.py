@@ -16,6 +16,7 @@ ap.add_argument("--graph", type=int, default=-1, help="yh_tuning.tfl_graph: 1 = 
 ap.add_argument("--invokes", type=int, default=220)
 ap.add_argument("--batch", action="store_true", help="the classify batch (yh_tfl_classify_batch_u32): ms per 640x480 frame for n = 1 .. 32 frames, three paths alternated in one process (profiles/tfl_classify_batch_timings.txt)")
 ap.add_argument("--int8", action="store_true", help="the int8 / per-channel twin of the stand-in (tests/tfl_models_q.py) beside the uint8 stand-in, interleaved in one process: the invoke at 1, 2 and 16 images, or with --batch the classify batch at n = 4, 8, 32 (profiles/tfl_int8_timings.txt)")
+ap.add_argument("--detect", action="store_true", help="the detection tail on the model's own heads (yh_tfl_evaluate): ms per image of invoke alone and of evaluate at 2, 16 and 64 images, uint8 heads beside float32 heads (DEQUANTIZE behind the four), interleaved in one process, and the tail's four launches timed by events (profiles/tfl_detect_timings.txt)")
 a = ap.parse_args()
 rng = np.random.default_rng(0)
 model = M.mobilenetv2_yolact(rng)
@@ -96,6 +97,52 @@ def int8_arm():
     for e in engs.values(): e.close()
 
 
+def detect_arm():
+    """Two handles on the stand-in - its uint8 heads, and the same heads behind DEQUANTIZE (float32: the mask kernel's float form) -
+    alternated round by round: invoke alone (set_input + invoke + read output 4) and evaluate (set_input + evaluate + read image 0's
+    detections, the one wait) per image count; then the tail's four launches on those outputs, timed by events."""
+    import tfl_detect_cases as K
+    rounds, S = 15, 224
+    fmodel = K.dequantized_heads(M.mobilenetv2_yolact(np.random.default_rng(0)))
+    engs = {"uint8": ya.TfliteEngine(buf, max_images=64), "float32": ya.TfliteEngine(bytes(B.serialize(fmodel)), max_images=64)}
+    levels = [28, 14, 7, 3, 1]   # (S / 8, / 16, / 32, then two PAD + VALID stride-2 levels)
+    pri = ya.tfl_priors(levels, S)
+    for e in engs.values(): e.detect_setup(pri)
+    x = rng.integers(0, 256, (64, S, S, 3), dtype=np.uint8)
+    print(f"tflite detections, {len(model.ops)}-op stand-in (S = {S}, P = {len(pri)}, C = 81, proto {engs['uint8'].proto_dims()}), top_k 200, max_dets 100, conf_thresh 0.05; "
+          f"the reference's own model file is absent: random weights, so the detections are those of noise")
+    print(f"ms per IMAGE, median of {rounds} alternated rounds (min .. max); invoke = set_input + invoke + read output 4; evaluate = set_input + evaluate + read image 0's detections")
+    for nb in (2, 16, 64):
+        def inv(e):
+            e.set_batch(nb); e.set_input(x[:nb]); e.invoke(); return e.output(4)
+        def ev(e):
+            e.set_batch(nb); e.set_input(x[:nb]); e.evaluate(); return e.detections(0, want_masks=False)
+        fns = {f"{k} {w}": (lambda e=e, f=f: f(e)) for k, e in engs.items() for w, f in (("invoke", inv), ("evaluate", ev))}
+        for _ in range(3):
+            for f in fns.values(): f()
+        t = np.array([[clock(f) for f in fns.values()] for _ in range(rounds)]) / nb
+        med, lo, hi = np.median(t, 0), t.min(0), t.max(0)
+        for i, k in enumerate(fns):
+            print(f"{nb:3d} images  {k:>17}  {med[i]:8.4f} ({lo[i]:7.4f} .. {hi[i]:7.4f})")
+        nd = {k: [len(e.detections(b, want_masks=False)[0]) for b in range(nb)] for k, e in engs.items()}
+        # the tail alone, by events on the handle's stream (mean of 20 runs per launch): three rounds, the two handles alternated
+        st = {k: [] for k in engs}
+        for _ in range(3):
+            for k, e in engs.items(): st[k].append(e.detect_stage_times(20))
+        st = {k: np.array(v) for k, v in st.items()}
+        for k in engs:
+            m = np.median(st[k], 0)
+            share = m.sum() / nb / med[list(fns).index(f"{k} evaluate")]
+            print(f"{nb:3d} images  {k:>8} tail by events, ms per launch (whole batch): softmax+cand {m[0]:.4f}  class nms {m[1]:.4f}  top dets {m[2]:.4f}  masks {m[3]:.4f}"
+                  f"  sum {m.sum():.4f} = {m.sum() / nb:.4f} per image = {100 * share:.1f} % of evaluate; detections per image {min(nd[k])} .. {max(nd[k])}")
+        mq, mf = np.median(st["uint8"], 0)[3], np.median(st["float32"], 0)[3]
+        print(f"{nb:3d} images  mask kernel: integer form (uint8 heads) {mq:.4f} ms, float form (float32 heads) {mf:.4f} ms, integer / float {mq / mf:.3f}")
+    for e in engs.values(): e.close()
+
+
+if a.detect:
+    detect_arm()
+    sys.exit(0)
 if a.int8:
     int8_arm()
     sys.exit(0)
