@@ -326,6 +326,21 @@ int yh_debug_rccl_shared_device(int32_t allow);
  * cannot reach the stand-in there (bench.py --rccl-library); processes without torch find it through LD_LIBRARY_PATH, hook unused. */
 int yh_debug_rccl_library(const char* path);
 int yh_debug_graph_nodes(yh_engine* h, int32_t with_tail, char* out, size_t cap);
+/* Bounds hooks ("Bounds"); none of the three launches a kernel.
+ * yh_debug_guard_selfcheck: the check of the single-op entry points' output guards on itself. It stages an output of 3 rows x 64 f16
+ * as those entry points do - 4096 bytes in front of the payload, 256 rows behind it, all 0xFF - changes ONE guard byte with a copy
+ * (where: 0 none, 1 the last byte of the front guard, 2 the first byte behind the payload, 3 the last byte of the back guard, 4 the
+ * first byte of the front guard) and runs the same check: YH_OK for 0, YH_EOVERFLOW for 1 .. 4 with a message that names the
+ * output, the side and the byte. YH_EINVAL for any other `where`.
+ * yh_debug_act_paint: fills images first_image .. max_batch - 1 of every activation allocation of the handle (and of its E4M3 twin
+ * in fp8 handles) with 0xFF - NaN in both formats; the 256 zero bytes behind each allocation, zero pixel first, are not touched.
+ * yh_debug_act_check: the painted images must still be 0xFF in every byte and those 256 bytes zero: YH_EOVERFLOW otherwise, the first
+ * changed byte (allocation, image, row, byte) in yh_last_error and, one per line, up to nine of them in out[cap] (out may be NULL).
+ * Both: YH_EINVAL for first_image outside 1 .. max_batch - 1, YH_ESTATE before the weights are loaded; both wait for the handle's
+ * streams first. A step of n <= first_image frames between the two must leave everything painted as it was. */
+int yh_debug_guard_selfcheck(yh_engine* h, int32_t where);
+int yh_debug_act_paint(yh_engine* h, int32_t first_image);
+int yh_debug_act_check(yh_engine* h, int32_t first_image, char* out, size_t cap);
 
 /* ---- single-op entry points (parity tests call kernels through the C ABI) ------------------- */
 
@@ -355,8 +370,9 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
  * (w2, bias2, stride unused), res and w1n required, and a' goes to a_next and / or, as E4M3 codes of a' * inv_scale[channel],
  * to a_next8 [M][256] (at least one of the two). YH_EINVAL with a message, and no launch, for a combination launch_bneck has no
  * kernel for. tune.op_xgap: every image of a is followed by that many elements of NaN (chains only: bneck_xn_f16 reads dense
- * rows and refuses a gap). Every output is staged with 256 guard rows of 0xFF behind row M - 1: YH_EOVERFLOW with a message if the
- * launch changed one of their bytes. */
+ * rows and refuses a gap). Like every single-op convolution, resize, pool, quantise and absmax entry point here, it stages each
+ * output between guards of 0xFF - 4096 bytes in front, 256 rows behind row M - 1 - and each input between 4096-byte bands of NaN:
+ * YH_EOVERFLOW with a message (output, side, byte, row) if the launch changed a guard byte. */
 int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t* a, int32_t n, int32_t hh, int32_t ww,
                     const uint16_t* w2, const float* bias2, int32_t stride, const uint16_t* w3, const float* bias3,
                     const uint16_t* res, const uint16_t* x2, int32_t h2, int32_t w2w, int32_t stride2,
@@ -411,8 +427,8 @@ int yh_op_conv2d_resup_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t P
 /* A k x k stride-1 'same' convolution to exactly 256 channels with the 1x1 convolution to 32 channels run on its LDS image in the
  * epilogue (ConvParams::w2: the protonet's last two layers as one launch):
  *   t = f16(act(conv(x, w) + bias)),  y2[M][32] = f16(relu(w2 t + bias2)),   w [256][k][k][cin], w2 [32][256], M = n hh ww
- * (cin % 64 == 0, act 0 / 1; t is never stored). tune.op_tile: a tile with the form (default TILE_256x256_M16). y2 is staged with 256
- * guard rows of 0xFF behind row M - 1: YH_EOVERFLOW if the launch changed one of their bytes. YH_EINVAL, and no launch, for cout != 256
+ * (cin % 64 == 0, act 0 / 1; t is never stored). tune.op_tile: a tile with the form (default TILE_256x256_M16). y2 is staged between
+ * guards of 0xFF as every output here: YH_EOVERFLOW if the launch changed one of their bytes. YH_EINVAL, and no launch, for cout != 256
  * or a tile without the form. */
 int yh_op_conv2d_tail_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
                           const float* bias, int32_t cout, int32_t k, int32_t act, const uint16_t* w2, const float* bias2, uint16_t* y2);

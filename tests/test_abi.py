@@ -29,6 +29,28 @@ def test_every_declared_symbol_is_exported_and_bound(built):
     assert bound <= set(declared)
 
 
+def test_bounds_hooks_are_declared_exported_and_bound_as_the_header_says(built):
+    """The three bounds hooks of include/yolact_hip_debug.h (Bounds): each is declared there and not in the
+    drop-in header, exported, and bound with the declaration's argument list; the wrapper has a method for each."""
+    import ctypes as C
+    from yolact_amd import capi
+    L = capi.load_library()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "yolact_hip_debug.h")).read(), flags=re.S)
+    bound = {s[0]: s for s in capi.SYMBOLS}
+    want = {"yh_debug_guard_selfcheck": ("yh_engine* h, int32_t where", [C.c_void_p, C.c_int32]),
+            "yh_debug_act_paint": ("yh_engine* h, int32_t first_image", [C.c_void_p, C.c_int32]),
+            "yh_debug_act_check": ("yh_engine* h, int32_t first_image, char* out, size_t cap", [C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t])}
+    for name, (args, types) in want.items():
+        assert re.search(r"\bint\s+%s\s*\(%s\)\s*;" % (name, re.escape(args)), src), name
+        assert name not in _declared(("yolact_hip.h",)) and hasattr(L, name)
+        assert bound[name][1] is C.c_int32 or bound[name][1] is C.c_int, name
+        assert list(bound[name][2]) == types, (name, bound[name][2])
+    for method in ("guard_selfcheck", "act_paint", "act_check"):
+        assert callable(getattr(capi.Engine, method))
+    assert L.yh_debug_guard_selfcheck(None, 0) == capi.EINVAL and L.yh_debug_act_paint(None, 1) == capi.EINVAL
+    assert L.yh_debug_act_check(None, 1, None, 0) == capi.EINVAL
+
+
 def test_version_and_defaults(built):
     from yolact_amd import capi
     L = capi.load_library()

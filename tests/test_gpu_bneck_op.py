@@ -4,8 +4,9 @@ float64 with the f16 roundings in between; tests/test_bneck_cases.py ties it to 
 every summation order exact). No tolerance anywhere: y, a_next and bneck_xn_f16's E4M3 codes are compared with np.array_equal.
 The dyadic case of every form (operands on power-of-two grids, sums exact in float32 and far wider than f16) is compared the same
 way: there b, y and a' are really rounded, so a chain that rounds in the wrong place or the wrong way fails it.
-The op stages 256 guard rows of 0xFF behind every output and fails if the launch touched one, and fills the outputs with the NaN
-pattern first, so a row the kernel skipped shows as well.
+The op stages every output as all single-op entry points do (OpStaging, csrc/engine_ops.hip): 4096 guard bytes in front of it and 256
+guard rows behind it, all 0xFF, YH_EOVERFLOW if the launch changed one; the output itself is filled with the same NaN pattern first,
+so a row the kernel skipped shows as well; every input lies between bands of NaN.
 
 The one real-valued case per form is held against the same three convolutions as three single-op launches on the streaming tiles
 the chain = 0 plan gives these layers, forced with tune.op_tile: TILE_64x256_K1 (id 22) for the convolutions with 64 output

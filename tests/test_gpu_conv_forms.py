@@ -7,7 +7,8 @@ the tile forced (tune.op_tile), a split-K forced where the case is one (tune.op_
   * yh_debug_last_conv_forms == the case's (tile, form), plus splitk_reduce_f16 behind a split-K: a case "for" the dense 1x1 form
     that silently ran the plain one, or on another tile, fails here.
 
-The fused-tail entry points also check 256 guard rows behind y2's row M - 1 themselves (YH_EOVERFLOW)."""
+Every entry point stages its output between guards of 0xFF, 4096 bytes in front and 256 rows behind row M - 1, and checks them itself
+(YH_EOVERFLOW; tests/test_gpu_op_guards.py runs every (tile, form) at the shapes where that decides something)."""
 import numpy as np
 import pytest
 

@@ -71,7 +71,10 @@ constexpr int kTrkStreams = 64;     // YH_TRACK_STREAMS_MAX
 // every channel). The channel scale is folded into the consumer's weights along K before their per-output-channel quantisation
 // (refresh_fp8_scales) and the producer's epilogue multiplies by the reciprocal table instead of a scalar: no extra pass.
 struct ActAlloc {
+    std::string name;              // new_buf's name (the layer's): what yh_debug_act_check reports
     half_t* base = nullptr;        // first element
+    size_t bytes = 0;              // max_batch images; 256 bytes of zeros (the zero pixel first) follow them
+    uint8_t* q = nullptr;          // fp8 handles: the E4M3 twin, bytes / 2 and its own 256 zeros
     long long img = 0;             // elements per image
     int c = 0;                     // channels (= row stride in elements)
     float scale = 1.0f;            // the largest channel scale (what yh_fp8_layer_info reports)

@@ -82,6 +82,7 @@ int new_buf(yh_engine* h, const char* name, int hh, int ww, int c, Buf* out) {
     b.sid = (int)h->act.size();
     h->act.emplace_back();
     h->act.back().base = b.d; h->act.back().img = b.img_stride; h->act.back().c = c;
+    h->act.back().name = name; h->act.back().bytes = data_bytes;
     if (h->cfg.precision == YH_PRECISION_FP8) {   // the E4M3 twin (288 GB of HBM: no aliasing games)
         void* t = nullptr;
         const std::vector<float> ones((size_t)c, 1.0f);
@@ -96,8 +97,9 @@ int new_buf(yh_engine* h, const char* name, int hh, int ww, int c, Buf* out) {
         if (hipMemset(p, 0, qbytes + 256) != hipSuccess) return h->fail(YH_EHIP, "hipMemset arena");
         b.q = (uint8_t*)p;
         b.qzero = b.q + ((qbytes + 15) & ~(size_t)15);
+        h->act.back().q = b.q;
     }
-    if (name) h->named[name] = b;
+    h->named[name] = b;
     *out = b;
     return YH_OK;
 }

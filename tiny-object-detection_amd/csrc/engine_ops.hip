@@ -1,4 +1,5 @@
 // engine_ops.hip - the single-op entry points (yh_op_*): one kernel on caller-supplied tensors. Only tests call them.
+#include <stdio.h>
 #include <string.h>
 
 #include "engine.h"
@@ -7,34 +8,118 @@ using namespace yh;
 
 namespace {
 
-// The device buffers of one single-op call: allocated (and filled - 0 behind a zero-padded input, 0xFF, the NaN pattern an
-// unwritten element shows, in an output) and uploaded in the order the call asks for them, freed when the call returns.
+// The NaN an element outside an uploaded input reads as: 0x7E00 per f16, 0x7FC00000 per f32, 0x7F per E4M3 code or raw byte.
+enum NanBand { NAN_F16, NAN_F32, NAN_BYTE };
+
+// The device buffers of one single-op call, allocated and uploaded in the order the call asks for them, freed when the call returns.
+// Every one is guarded (Bounds):
+//   an input  (upload, upload_padded)  kBand bytes of NaN | the data (| zeros up to `cap`) | kBand bytes of NaN - a plain load
+//             outside the data poisons a stored value, and the value comparison every test makes fails;
+//   an output (alloc_out, check_out)   kBand bytes | the payload | kGuardRows rows (no row stride: kBand bytes), all 0xFF before the
+//             launch - the NaN pattern an unwritten element shows - and both guards read back behind it: a changed byte is
+//             YH_EOVERFLOW (overflow_text);
+//   the split-K workspace (paint_ws, check_ws)  the bytes behind the last slice's slab.
+// kGuardRows is the largest row count of a tile in kConvTiles: a tile-granular overrun falls inside the back guard.
 // The first HIP error is kept and every step after it is skipped.
 struct OpStaging {
+    static constexpr size_t kBand = 4096, kGuardRows = 256;
+    struct Out { const char* name; uint8_t* base; size_t bytes, row_bytes, back; };   // base: the allocation's; payload at base + kBand
+    struct Hit { const char* name = nullptr; bool front = false; size_t off = 0, row_bytes = 0; unsigned value = 0; };
     hipError_t e = hipSuccess;
     std::vector<void*> bufs;
+    std::vector<Out> outs;
+    Hit hit;                      // the first changed guard byte check_out met (name == nullptr: none)
+    float* ws = nullptr;          // painted part of the split-K workspace: [ws_from, ws_to) bytes
+    size_t ws_from = 0, ws_to = 0;
+    bool ws_hit = false;
     OpStaging() = default;
     OpStaging(const OpStaging&) = delete;
     ~OpStaging() { for (void* d : bufs) hipFree(d); }
     bool ok() const { return e == hipSuccess; }
+    // (unguarded: the instance ops' buffers, which belong to a later pull request's bounds work)
     template <class T> T* alloc(size_t bytes, int fill = -1) {
         void* d = nullptr;
         if (ok() && (e = hipMalloc(&d, bytes)) == hipSuccess) bufs.push_back(d);
         if (ok() && fill >= 0) e = hipMemset(d, fill, bytes);
+        // (a device memset may return before it ran, and the handle's streams do not wait for the null stream: a launch right
+        // behind it could have its stores painted over)
+        if (ok() && fill >= 0) e = hipStreamSynchronize(nullptr);
         return ok() ? (T*)d : nullptr;
     }
     void put(const void* d, const void* src, size_t bytes) { if (ok()) e = hipMemcpy((void*)d, src, bytes, hipMemcpyHostToDevice); }
-    template <class T> T* upload(const void* src, size_t bytes) { T* d = alloc<T>(bytes); put(d, src, bytes); return d; }
-    // a conv input with its zero pixel behind the data: `cap` zeroed bytes, the data first; *zero_off = where the zeros start
-    template <class T> T* upload_padded(const void* src, size_t bytes, size_t cap, unsigned* zero_off) {
+    template <class T> T* upload_raw(const void* src, size_t bytes) { T* d = alloc<T>(bytes); put(d, src, bytes); return d; }
+    // an input between its NaN bands; cap > bytes: zeros from the data's end up to cap (upload_padded)
+    template <class T> T* upload(const void* src, size_t bytes, NanBand nan, size_t cap = 0) {
+        if (cap < bytes) cap = bytes;
+        std::vector<uint8_t> img(kBand + cap + kBand, 0);
+        for (uint8_t* band : { img.data(), img.data() + kBand + cap })
+            for (size_t i = 0; i < kBand; ++i)
+                band[i] = nan == NAN_BYTE ? 0x7F : nan == NAN_F16 ? ((i & 1) ? 0x7E : 0x00) : ((i & 3) == 3 ? 0x7F : (i & 3) == 2 ? 0xC0 : 0x00);
+        memcpy(img.data() + kBand, src, bytes);
+        uint8_t* d = alloc<uint8_t>(img.size());
+        put(d, img.data(), img.size());
+        return ok() ? (T*)(d + kBand) : nullptr;
+    }
+    // a conv input with its zero pixel behind the data: `cap` bytes, the data first, zeros behind; *zero_off = where the zeros start
+    template <class T> T* upload_padded(const void* src, size_t bytes, size_t cap, unsigned* zero_off, NanBand nan = NAN_F16) {
         *zero_off = (unsigned)pad16(bytes);
-        T* d = alloc<T>(cap, 0);
-        put(d, src, bytes);
-        return d;
+        return upload<T>(src, bytes, nan, cap);
+    }
+    template <class T> T* alloc_out(const char* name, size_t bytes, size_t row_bytes) {
+        const size_t back = row_bytes ? kGuardRows * row_bytes : kBand;
+        uint8_t* d = alloc<uint8_t>(kBand + bytes + back, 0xFF);
+        if (!d) return nullptr;
+        outs.push_back(Out{ name, d, bytes, row_bytes, back });
+        return (T*)(d + kBand);
     }
     void sync(hipStream_t s) { if (ok()) e = hipStreamSynchronize(s); }
     void get(void* dst, const void* d, size_t bytes) { if (ok()) e = hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost); }
+    // reads an output of alloc_out back - guards and payload in one copy: the payload to dst (nullptr: not wanted), the first
+    // changed guard byte, front guard first, to `hit`
+    void check_out(const void* payload, void* dst) {
+        const Out* o = nullptr;
+        for (const Out& c : outs) if (c.base + kBand == (const uint8_t*)payload) o = &c;
+        if (!ok() || !o) return;
+        std::vector<uint8_t> all(kBand + o->bytes + o->back);
+        get(all.data(), o->base, all.size());
+        if (!ok()) return;
+        if (dst) memcpy(dst, all.data() + kBand, o->bytes);
+        for (size_t i = 0; i < all.size() && !hit.name; i = i + 1 == kBand ? kBand + o->bytes : i + 1)
+            if (all[i] != 0xFF) hit = Hit{ o->name, i < kBand, i < kBand ? i : i - kBand - o->bytes, o->row_bytes, all[i] };
+    }
+    void paint_ws(float* w, size_t from, size_t to) {
+        if (!ok() || from >= to) return;
+        ws = w; ws_from = from; ws_to = to;
+        e = hipMemset((char*)w + from, 0xFF, to - from);
+        if (ok()) e = hipStreamSynchronize(nullptr);
+    }
+    void check_ws() {
+        if (!ok() || !ws) return;
+        std::vector<uint8_t> v(ws_to - ws_from);
+        get(v.data(), (const char*)ws + ws_from, v.size());
+        for (size_t i = 0; ok() && i < v.size() && !ws_hit; ++i) ws_hit = v[i] != 0xFF;
+    }
+    bool overflowed() const { return hit.name || ws_hit; }
+    // who = the op's prefix and, where the entry knows it, the kernel's symbol: "bneck op: bneck_chain_f16<..>"
+    std::string overflow_text(std::string who) const {
+        while (!who.empty() && who.back() == ' ') who.pop_back();   // (no symbol: "bilinear op: stored ..")
+        if (!hit.name) return who + " stored split-K partials past slice k_slices - 1";
+        const std::string n = hit.name;
+        char at[160];
+        if (hit.front)
+            snprintf(at, sizeof at, ": %s front guard, byte %zu (%zu in front of the payload) is 0x%02X", hit.name, hit.off, kBand - hit.off, hit.value);
+        else if (hit.row_bytes)
+            snprintf(at, sizeof at, ": %s back guard, byte %zu (row M + %zu) is 0x%02X", hit.name, hit.off, hit.off / hit.row_bytes, hit.value);
+        else
+            snprintf(at, sizeof at, ": %s back guard, byte %zu is 0x%02X", hit.name, hit.off, hit.value);
+        return who + (hit.front ? " stored in front of " + n : hit.row_bytes ? " stored " + n + " rows past M" : " stored past the end of " + n) + at;
+    }
     int status(yh_engine* h, const char* what) const { return ok() ? YH_OK : h->fail(YH_EHIP, std::string(what) + hipGetErrorString(e)); }
+    // ... and YH_EOVERFLOW when a guard changed
+    int status(yh_engine* h, const char* what, const std::string& symbol) const {
+        if (!ok()) return status(h, what);
+        return overflowed() ? h->fail(YH_EOVERFLOW, overflow_text(what + symbol)) : YH_OK;
+    }
 };
 
 // rows of c values, zero-padded to rows of ld (input channels to the stored count, output channels to cout8) - and back
@@ -48,15 +133,17 @@ void unpad_rows(uint16_t* dst, const std::vector<uint16_t>& src, size_t rows, si
 }
 
 // test hook (tune.op_kslices): a forced split-K of a single-op launch (the engine decides it in fill_conv_params)
-void force_split_k(yh_engine* h, ConvParams& p, size_t M, int coutPad) {
+// Where it takes effect, up to kGuardRows rows of the workspace behind the last slice's slab are painted 0xFF (OpStaging::check_ws).
+void force_split_k(yh_engine* h, OpStaging& st, ConvParams& p, size_t M, int coutPad) {
     const int ksl = h->tune.op_kslices;
     if (ksl < 2 || ksl > p.ksteps || (size_t)ksl * M * coutPad * 4 > yh_engine::kSplitKBytes) return;
     p.ksteps_per_slice = (p.ksteps + ksl - 1) / ksl;
     p.k_slices = (p.ksteps + p.ksteps_per_slice - 1) / p.ksteps_per_slice;
     p.partial_ld = coutPad;
     p.partial = h->splitk_ws;
+    const size_t used = (size_t)p.k_slices * M * coutPad * 4, end = used + OpStaging::kGuardRows * (size_t)coutPad * 4, cap = yh_engine::kSplitKBytes;
+    st.paint_ws(h->splitk_ws, used, end < cap ? end : cap);
 }
-
 
 // launch_conv_planned for a single-op call: counts and names the launches on the handle; false = no launch of the plan was made,
 // because launch_conv has no kernel for one of them (the caller answers YH_EINVAL)
@@ -64,12 +151,6 @@ bool launch_op_conv(yh_engine* h, OpStaging& st, const ConvParams& p, ConvTile t
     st.e = launch_conv_planned(h->tune, p, tile, coutPad, h->stream, &h->last_conv_launches, &h->last_conv_forms);
     if (st.e != hipErrorInvalidValue) return true;
     st.e = hipSuccess;
-    return false;
-}
-
-bool guard_touched(const void* v, size_t from, size_t to) {
-    const uint8_t* b = (const uint8_t*)v;
-    for (size_t i = from; i < to; ++i) if (b[i] != 0xFF) return true;
     return false;
 }
 
@@ -122,11 +203,11 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
     OpStaging st;
     unsigned zo = 0;
     const half_t* dx = st.upload_padded<half_t>(xs.data(), xs.size() * 2, xs.size() * 2 + 64, &zo);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
-    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
-    const int2* dt = cin == 3 ? st.upload<int2>(tab.data(), tab.size() * sizeof(int2)) : nullptr;
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2, NAN_F16);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4, NAN_F32);
+    half_t* dy = st.alloc_out<half_t>("y", ys.size() * 2, (size_t)cout8 * 2);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2, NAN_F16) : nullptr;
+    const int2* dt = cin == 3 ? st.upload<int2>(tab.data(), tab.size() * sizeof(int2), NAN_BYTE) : nullptr;
     if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
@@ -141,12 +222,13 @@ static int op_conv2d_impl(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh
             p.nlev = nlev;
             for (int l = 0, s = 0; l < nlev; ++l) { p.lev_start[l] = s; p.lev_h[l] = p.lev_w[l] = level_sizes[l]; s += level_sizes[l] * level_sizes[l]; }
         }
-        force_split_k(h, p, M, coutPad);
+        force_split_k(h, st, p, M, coutPad);
         if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "conv op: no conv kernel for these parameters on this tile (tune.op_tile, tune.op_kslices)");
     }
     st.sync(h->stream);
-    st.get(ys.data(), dy, ys.size() * 2);
-    if (const int rc = st.status(h, "conv op: ")) return rc;
+    st.check_out(dy, ys.data());
+    st.check_ws();
+    if (const int rc = st.status(h, "conv op: ", conv_tile_symbol(tile))) return rc;
     unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
 }
@@ -176,9 +258,9 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
     unsigned z1 = 0, z2 = 0;
     const half_t* d1 = st.upload_padded<half_t>(x1, n1 * 2, n1 * 2 + 64, &z1);
     const half_t* d2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    half_t* dy = st.alloc<half_t>(M * cout * 2, 0xFF);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2, NAN_F16);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4, NAN_F32);
+    half_t* dy = st.alloc_out<half_t>("y", M * cout * 2, (size_t)cout * 2);
     if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
@@ -192,12 +274,13 @@ int yh_op_conv2d_dual_f16(yh_engine* h, const uint16_t* x1, int32_t n, int32_t h
         p.N = n; p.H = ho; p.W = wo; p.C = c1; p.P = ho; p.Q = wo; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
         p.M = (int)M; p.cout8 = cout; p.ldw = K; p.ksteps = K / 64; p.ldy = cout; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / conv_tile_ch(tile); p.k_slices = 1;
-        if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, p, M, coutPad);
+        if (conv_tile_has(tile, FORM_DUAL_SPLITK)) force_split_k(h, st, p, M, coutPad);
         if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "dual conv op: no conv kernel for these parameters on this tile");
     }
     st.sync(h->stream);
-    st.get(y, dy, M * cout * 2);
-    return st.status(h, "dual conv op: ");
+    st.check_out(dy, y);
+    st.check_ws();
+    return st.status(h, "dual conv op: ", conv_tile_symbol(tile));
 }
 
 // One launch of bneck.hip (a row of kBneckChains, or bneck_xn_f16 for 256 planes) on caller tensors. The host arrays are already
@@ -234,12 +317,11 @@ int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t
             return h->fail(YH_EINVAL, "bneck op: x2 must cover the strided output grid");
     }
     HIPCHK(h, hipSetDevice(h->dev));
-    constexpr size_t kGuardRows = 256;
     const int C4 = 4 * planes, C2 = dual ? 64 : 0;
     const size_t M = (size_t)n * P * Q, img = (size_t)hh * ww * planes, n2 = dual ? (size_t)n * h2 * w2w * 64 : 0;
     std::vector<uint16_t> as((img + gap) * n, 0x7E00);   // (test hook, tune.op_xgap: NaN behind every image)
     for (int b = 0; b < n; ++b) memcpy(&as[b * (img + gap)], &a[b * img], img * 2);
-    const size_t ny = M * C4, nan_ = M * planes, gy = kGuardRows * C4, ga = kGuardRows * planes;
+    const size_t ny = M * C4, nan_ = M * planes;
     OpStaging st;
     BneckParams p;
     memset(&p, 0, sizeof p);
@@ -249,48 +331,32 @@ int yh_op_bneck_f16(yh_engine* h, int32_t planes, int32_t tile_m, const uint16_t
     p.N = n; p.H = hh; p.W = ww; p.P = P; p.Q = Q; p.stride = xn ? 1 : stride; p.M = (int)M; p.no_b = xn ? 1 : 0;
     if (!xn) {
         p.w2_bytes = (unsigned)((size_t)planes * 9 * planes * 2);
-        p.w2 = st.upload<half_t>(w2, p.w2_bytes); p.bias2 = st.upload<float>(bias2, (size_t)planes * 4);
+        p.w2 = st.upload<half_t>(w2, p.w2_bytes, NAN_F16); p.bias2 = st.upload<float>(bias2, (size_t)planes * 4, NAN_F32);
     }
     p.w3_bytes = (unsigned)((size_t)C4 * (planes + C2) * 2);
-    p.w3 = st.upload<half_t>(w3, p.w3_bytes); p.bias3 = st.upload<float>(bias3, (size_t)C4 * 4);
-    if (res) { p.res_bytes = (unsigned)(ny * 2); p.res = st.upload<half_t>(res, ny * 2); }
+    p.w3 = st.upload<half_t>(w3, p.w3_bytes, NAN_F16); p.bias3 = st.upload<float>(bias3, (size_t)C4 * 4, NAN_F32);
+    if (res) { p.res_bytes = (unsigned)(ny * 2); p.res = st.upload<half_t>(res, ny * 2, NAN_F16); }
     if (dual) {
         p.x2 = st.upload_padded<half_t>(x2, n2 * 2, n2 * 2 + 64, &z2);
         p.x2_bytes = z2 + 16u; p.x2_img_stride = (long long)h2 * w2w * 64; p.W2 = w2w; p.C2 = 64; p.stride2 = stride2;
     }
     if (next) {
         p.w1n_bytes = (unsigned)((size_t)planes * C4 * 2);
-        p.w1n = st.upload<half_t>(w1n, p.w1n_bytes); p.bias1n = st.upload<float>(bias1n, (size_t)planes * 4);
+        p.w1n = st.upload<half_t>(w1n, p.w1n_bytes, NAN_F16); p.bias1n = st.upload<float>(bias1n, (size_t)planes * 4, NAN_F32);
     }
-    // outputs: 0xFF everywhere, kGuardRows rows behind row M - 1 that no launch may touch
-    p.y = st.alloc<half_t>((ny + gy) * 2, 0xFF);
-    if (a_next) p.a_next = st.alloc<half_t>((nan_ + ga) * 2, 0xFF);
-    if (a_next8) { p.a_next8 = st.alloc<uint8_t>(nan_ + ga, 0xFF); p.a_next8_inv = st.upload<float>(inv_scale, (size_t)planes * 4); }
+    p.y = st.alloc_out<half_t>("y", ny * 2, (size_t)C4 * 2);
+    if (a_next) p.a_next = st.alloc_out<half_t>("a_next", nan_ * 2, (size_t)planes * 2);
+    if (a_next8) { p.a_next8 = st.alloc_out<uint8_t>("a_next8", nan_, (size_t)planes); p.a_next8_inv = st.upload<float>(inv_scale, (size_t)planes * 4, NAN_F32); }
     if (st.ok()) {
         if (bneck_set_geometry(p) != hipSuccess) return h->fail(YH_EINVAL, "bneck op: row geometry out of range");
         st.e = launch_bneck(p, planes, tile_m, h->stream);
         if (st.e == hipErrorInvalidValue) return h->fail(YH_EINVAL, "bneck op: launch_bneck has no kernel for these parameters");   // (nothing was launched)
     }
     st.sync(h->stream);
-    std::vector<uint16_t> ys(ny + gy), an(a_next ? nan_ + ga : 0);
-    std::vector<uint8_t> a8(a_next8 ? nan_ + ga : 0);
-    st.get(ys.data(), p.y, ys.size() * 2);
-    if (a_next) st.get(an.data(), p.a_next, an.size() * 2);
-    if (a_next8) st.get(a8.data(), p.a_next8, a8.size());
-    if (const int rc = st.status(h, "bneck op: ")) return rc;
-    const auto touched = [](const void* v, size_t from, size_t to) {
-        const uint8_t* b = (const uint8_t*)v;
-        for (size_t i = from; i < to; ++i) if (b[i] != 0xFF) return true;
-        return false;
-    };
-    const char* const sym = bneck_symbol(planes, tile_m, next, dual);
-    if (touched(ys.data(), ny * 2, ys.size() * 2)) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored y rows past M");
-    if (a_next && touched(an.data(), nan_ * 2, an.size() * 2)) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored a_next rows past M");
-    if (a_next8 && touched(a8.data(), nan_, a8.size())) return h->fail(YH_EOVERFLOW, std::string("bneck op: ") + sym + " stored a_next8 rows past M");
-    memcpy(y, ys.data(), ny * 2);
-    if (a_next) memcpy(a_next, an.data(), nan_ * 2);
-    if (a_next8) memcpy(a_next8, a8.data(), nan_);
-    return YH_OK;
+    st.check_out(p.y, y);
+    if (a_next) st.check_out(p.a_next, a_next);
+    if (a_next8) st.check_out(p.a_next8, a_next8);
+    return st.status(h, "bneck op: ", bneck_symbol(planes, tile_m, next, dual));
 }
 
 int yh_op_conv2d_levels_f16(yh_engine* h, const uint16_t* x, int32_t n, const int32_t* level_sizes, int32_t nlev, int32_t cin,
@@ -306,12 +372,12 @@ int yh_op_bilinear_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, i
     HIPCHK(h, hipSetDevice(h->dev));
     const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
     OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, ni * 2);
-    half_t* dy = st.alloc<half_t>(no * 2);
+    const half_t* dx = st.upload<half_t>(x, ni * 2, NAN_F16);
+    half_t* dy = st.alloc_out<half_t>("y", no * 2, (size_t)c * 2);
     if (st.ok()) st.e = launch_bilinear(dx, dy, n, hh, ww, c, ho, wo, (long long)hh * ww * c, (long long)ho * wo * c, h->stream);
     st.sync(h->stream);
-    st.get(y, dy, no * 2);
-    return st.status(h, "bilinear op: ");
+    st.check_out(dy, y);
+    return st.status(h, "bilinear op: ", "");
 }
 
 int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t c, uint16_t* y) {
@@ -320,12 +386,12 @@ int yh_op_maxpool3x3s2_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t h
     const int ho = out_dim(hh, 3, 2, 1), wo = out_dim(ww, 3, 2, 1);
     const size_t ni = (size_t)n * hh * ww * c, no = (size_t)n * ho * wo * c;
     OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, ni * 2);
-    half_t* dy = st.alloc<half_t>(no * 2);
+    const half_t* dx = st.upload<half_t>(x, ni * 2, NAN_F16);
+    half_t* dy = st.alloc_out<half_t>("y", no * 2, (size_t)c * 2);
     if (st.ok()) st.e = launch_maxpool3x3s2(dx, dy, n, hh, ww, c, ho, wo, h->stream);
     st.sync(h->stream);
-    st.get(y, dy, no * 2);
-    return st.status(h, "maxpool op: ");
+    st.check_out(dy, y);
+    return st.status(h, "maxpool op: ", "maxpool3x3s2_f16");
 }
 
 static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb, int32_t n, int32_t S, const uint16_t* w, const float* bias,
@@ -346,13 +412,13 @@ static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb
                 for (int c = 0; c < 3; ++c) wp[(size_t)o * 256 + r * 32 + sx * 4 + c] = w[(((size_t)o * 7 + r) * 7 + sx) * 3 + c];
     const size_t ns = (size_t)n * SO * SO * 64, np = (size_t)n * PO * PO * 64;
     OpStaging st;
-    const half_t* dx = st.alloc<half_t>(xs.size() * 2);
-    const uint8_t* drgb = rgb ? st.upload<uint8_t>(rgb, (size_t)n * S * S * 3) : nullptr;
-    st.put(dx, xs.data(), xs.size() * 2);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bias, 64 * 4);
-    half_t* ds = st.alloc<half_t>(ns * 2, 0xFF);
-    half_t* dp = st.alloc<half_t>(np * 2, 0xFF);
+    const half_t* dx = st.upload<half_t>(xs.data(), xs.size() * 2, NAN_F16);
+    const uint8_t* drgb = rgb ? st.upload<uint8_t>(rgb, (size_t)n * S * S * 3, NAN_BYTE) : nullptr;
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2, NAN_F16);
+    const float* db = st.upload<float>(bias, 64 * 4, NAN_F32);
+    // (the stem output is staged, and its guards checked, when the launch is told not to write it too)
+    half_t* ds = st.alloc_out<half_t>("stem", ns * 2, 64 * 2);
+    half_t* dp = st.alloc_out<half_t>("pool", np * 2, 64 * 2);
     if (st.ok()) {
         StemPoolParams sp;
         sp.x = dx; sp.w = dw; sp.bias = db; sp.pool = dp;
@@ -363,9 +429,9 @@ static int op_stem_pool_impl(yh_engine* h, const uint16_t* x, const uint8_t* rgb
         st.e = launch_stem_pool(sp, h->stream);
     }
     st.sync(h->stream);
-    if (stem_out) st.get(stem_out, ds, ns * 2);
-    st.get(pool_out, dp, np * 2);
-    return st.status(h, "stem+pool op: ");
+    st.check_out(ds, stem_out);
+    st.check_out(dp, pool_out);
+    return st.status(h, "stem+pool op: ", "stem_pool_f16");
 }
 
 int yh_op_stem_pool_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t S, const uint16_t* w, const float* bias,
@@ -400,12 +466,12 @@ static int op_conv2d_fp8_impl(yh_engine* h, const uint8_t* x, int32_t n, int32_t
     if (residual) rs = pad_rows(residual, M, cout, cout8);
     OpStaging st;
     unsigned zo = 0;
-    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size());
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    const float* dsc = st.upload<float>(sp.data(), sp.size() * 4);
-    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
-    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2) : nullptr;
+    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo, NAN_BYTE);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size(), NAN_BYTE);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4, NAN_F32);
+    const float* dsc = st.upload<float>(sp.data(), sp.size() * 4, NAN_F32);
+    half_t* dy = st.alloc_out<half_t>("y", ys.size() * 2, (size_t)cout8 * 2);
+    const half_t* dr = residual ? st.upload<half_t>(rs.data(), rs.size() * 2, NAN_F16) : nullptr;
     if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
@@ -434,8 +500,8 @@ static int op_conv2d_fp8_impl(yh_engine* h, const uint8_t* x, int32_t n, int32_t
             *ms_per_launch = ms / reps;
         }
     }
-    st.get(ys.data(), dy, ys.size() * 2);
-    if (const int rc = st.status(h, "fp8 conv op: ")) return rc;
+    st.check_out(dy, ys.data());
+    if (const int rc = st.status(h, "fp8 conv op: ", conv_tile_symbol(tile))) return rc;
     unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
 }
@@ -473,10 +539,10 @@ int yh_op_conv2d_resup_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t P
     OpStaging st;
     unsigned zo = 0;
     const half_t* dx = st.upload_padded<half_t>(x, nx * 2, nx * 2 + 64, &zo);
-    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2);
-    const float* db = st.upload<float>(bp.data(), bp.size() * 4);
-    const half_t* dr = st.upload<half_t>(rs.data(), rs.size() * 2);
-    half_t* dy = st.alloc<half_t>(ys.size() * 2, 0xFF);
+    const half_t* dw = st.upload<half_t>(wp.data(), wp.size() * 2, NAN_F16);
+    const float* db = st.upload<float>(bp.data(), bp.size() * 4, NAN_F32);
+    const half_t* dr = st.upload<half_t>(rs.data(), rs.size() * 2, NAN_F16);
+    half_t* dy = st.alloc_out<half_t>("y", ys.size() * 2, (size_t)cout8 * 2);
     if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
@@ -487,12 +553,13 @@ int yh_op_conv2d_resup_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t P
         p.N = n; p.H = P; p.W = Q; p.C = cin; p.P = P; p.Q = Q; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
         p.M = (int)M; p.cout8 = cout8; p.ldw = cin; p.ksteps = cin / 64; p.ldy = cout8; p.ldres = cout8; p.y_dense = 1;
         p.act = act; p.tanh_from = INT_MAX; p.n_ch_tiles = coutPad / tch; p.k_slices = 1;
-        if (conv_tile_has(tile, FORM_SPLITK)) force_split_k(h, p, M, coutPad);
+        if (conv_tile_has(tile, FORM_SPLITK)) force_split_k(h, st, p, M, coutPad);
         if (!launch_op_conv(h, st, p, tile, coutPad)) return h->fail(YH_EINVAL, "resup conv op: no conv kernel for these parameters on this tile");
     }
     st.sync(h->stream);
-    st.get(ys.data(), dy, ys.size() * 2);
-    if (const int rc = st.status(h, "resup conv op: ")) return rc;
+    st.check_out(dy, ys.data());
+    st.check_ws();
+    if (const int rc = st.status(h, "resup conv op: ", conv_tile_symbol(tile))) return rc;
     unpad_rows(y, ys, M, cout, cout8);
     return YH_OK;
 }
@@ -511,18 +578,18 @@ static int op_conv2d_tail_impl(yh_engine* h, const void* x, int32_t n, int32_t h
     const ConvTile tile = h->tune.op_tile >= 0 ? (ConvTile)h->tune.op_tile : (fp8 ? TILE_256x256_FP8 : TILE_256x256_M16);
     if (!conv_tile_has(tile, FORM_TAIL) || conv_tile_fp8(tile) != fp8) return h->fail(YH_EINVAL, std::string(what) + "tune.op_tile is not a tile of the fused-tail form");
     HIPCHK(h, hipSetDevice(h->dev));
-    constexpr size_t kGuardRows = 256;
     const int es = fp8 ? 1 : 2, Kpad = k * k * cin;           // bytes per operand element
-    const size_t M = (size_t)n * hh * ww, xbytes = M * cin * es, wbytes = (size_t)256 * Kpad * es, ny = M * 32, gy = kGuardRows * 32;
+    const size_t M = (size_t)n * hh * ww, xbytes = M * cin * es, wbytes = (size_t)256 * Kpad * es, ny = M * 32;
+    const NanBand nan = fp8 ? NAN_BYTE : NAN_F16;
     OpStaging st;
     unsigned zo = 0;
-    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo);
-    const half_t* dw = st.upload<half_t>(w, wbytes);
-    const float* db = st.upload<float>(bias, 256 * 4);
-    const float* dsc = fp8 ? st.upload<float>(scale, 256 * 4) : nullptr;
-    const half_t* dw2 = st.upload<half_t>(w2, (size_t)32 * 256 * 2);
-    const float* db2 = st.upload<float>(bias2, 32 * 4);
-    half_t* dy2 = st.alloc<half_t>((ny + gy) * 2, 0xFF);   // kGuardRows rows behind row M - 1 that the launch may not touch
+    const half_t* dx = st.upload_padded<half_t>(x, xbytes, pad16(xbytes) + 64, &zo, nan);
+    const half_t* dw = st.upload<half_t>(w, wbytes, nan);
+    const float* db = st.upload<float>(bias, 256 * 4, NAN_F32);
+    const float* dsc = fp8 ? st.upload<float>(scale, 256 * 4, NAN_F32) : nullptr;
+    const half_t* dw2 = st.upload<half_t>(w2, (size_t)32 * 256 * 2, NAN_F16);
+    const float* db2 = st.upload<float>(bias2, 32 * 4, NAN_F32);
+    half_t* dy2 = st.alloc_out<half_t>("y2", ny * 2, 32 * 2);   // (the only output: y and y8 are nullptr in this launch)
     if (st.ok()) {
         ConvParams p;
         memset(&p, 0, sizeof p);
@@ -536,12 +603,8 @@ static int op_conv2d_tail_impl(yh_engine* h, const void* x, int32_t n, int32_t h
         if (!launch_op_conv(h, st, p, tile, 256)) return h->fail(YH_EINVAL, std::string(what) + "no conv kernel for these parameters on this tile");
     }
     st.sync(h->stream);
-    std::vector<uint16_t> ys(ny + gy);
-    st.get(ys.data(), dy2, ys.size() * 2);
-    if (const int rc = st.status(h, what)) return rc;
-    if (guard_touched(ys.data(), ny * 2, ys.size() * 2)) return h->fail(YH_EOVERFLOW, std::string(what) + conv_tile_symbol(tile) + "[+1x1] stored y2 rows past M");
-    memcpy(y2, ys.data(), ny * 2);
-    return YH_OK;
+    st.check_out(dy2, y2);
+    return st.status(h, what, std::string(conv_tile_symbol(tile)) + "[+1x1]");
 }
 
 int yh_op_conv2d_tail_f16(yh_engine* h, const uint16_t* x, int32_t n, int32_t hh, int32_t ww, int32_t cin, const uint16_t* w,
@@ -558,28 +621,48 @@ int yh_op_quantize_e4m3(yh_engine* h, const uint16_t* x, size_t n, float inv_sca
     if (!h || !x || !y || n < 1) return YH_EINVAL;
     HIPCHK(h, hipSetDevice(h->dev));
     OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, n * 2);
-    uint8_t* dy = st.alloc<uint8_t>(n);
+    const half_t* dx = st.upload<half_t>(x, n * 2, NAN_F16);
+    uint8_t* dy = st.alloc_out<uint8_t>("y", n, 0);
     if (st.ok()) st.e = launch_quantize_e4m3(dx, dy, (long long)n, inv_scale, h->stream);
     st.sync(h->stream);
-    st.get(y, dy, n);
-    return st.status(h, "quantize op: ");
+    st.check_out(dy, y);
+    return st.status(h, "quantize op: ", "quantize_e4m3");
 }
 
 int yh_op_absmax_channels_f16(yh_engine* h, const uint16_t* x, int64_t rows, int32_t C, uint32_t* out_bits) {
     if (!h || !x || !out_bits || rows < 1 || C < 1) return YH_EINVAL;
     HIPCHK(h, hipSetDevice(h->dev));
     OpStaging st;
-    const half_t* dx = st.upload<half_t>(x, (size_t)rows * C * 2);
-    unsigned* dm = st.alloc<unsigned>((size_t)C * 4);
+    const half_t* dx = st.upload<half_t>(x, (size_t)rows * C * 2, NAN_F16);
+    unsigned* dm = st.alloc_out<unsigned>("out_bits", (size_t)C * 4, 0);
     if (st.ok()) st.e = hipMemsetAsync(dm, 0, (size_t)C * 4, h->stream);   // (on the kernel's stream, as the calibration does: its atomicMax starts from these zeros)
     if (st.ok()) {
         st.e = launch_absmax_channels_f16(dx, (long long)rows, C, dm, h->stream);
         if (st.e == hipErrorInvalidValue) return h->fail(YH_EINVAL, "absmax op: C must be a multiple of 8 with 256 % (C / 8) == 0");   // (nothing was launched)
     }
     st.sync(h->stream);
-    st.get(out_bits, dm, (size_t)C * 4);
-    return st.status(h, "absmax op: ");
+    st.check_out(dm, out_bits);
+    return st.status(h, "absmax op: ", "absmax_channels_f16");
+}
+
+// The check of the checker (no kernel): a guarded output of 3 rows x 64 f16 through alloc_out, one guard byte changed by a copy at
+// `where` - 0 none, 1 the front guard's last byte, 2 the first byte behind the payload, 3 the back guard's last byte, 4 the front
+// guard's first byte - and check_out on it. Every byte written lies inside the call's own allocation.
+int yh_debug_guard_selfcheck(yh_engine* h, int32_t where) {
+    if (!h) return YH_EINVAL;
+    if (where < 0 || where > 4) return h->fail(YH_EINVAL, "guard selfcheck: where must be 0 .. 4");
+    HIPCHK(h, hipSetDevice(h->dev));
+    constexpr size_t row_bytes = 64 * 2, bytes = 3 * row_bytes, B = OpStaging::kBand;
+    OpStaging st;
+    const uint16_t* d = st.alloc_out<uint16_t>("y", bytes, row_bytes);
+    if (st.ok() && where > 0) {
+        const OpStaging::Out& o = st.outs.back();
+        const size_t at[5] = { 0, B - 1, B + bytes, B + bytes + o.back - 1, 0 };
+        const uint8_t changed = 0x00;
+        st.put(o.base + at[where], &changed, 1);
+    }
+    st.check_out(d, nullptr);
+    return st.status(h, "guard selfcheck: ", "");
 }
 
 int yh_op_detect(yh_engine* h, const uint16_t* loc, const uint16_t* conf, const uint16_t* mask, const uint16_t* proto, int32_t n) {
@@ -628,8 +711,8 @@ static int op_instance_impl(yh_engine* h, const uint8_t* masks, const int32_t* c
     // (0xFF behind the n masks in use: the slots past the count are stale in the engine too, and must not be read)
     uint8_t* dm = st.alloc<uint8_t>((size_t)h->cfg.max_dets * px, 0xFF);
     if (n > 0) st.put(dm, masks, (size_t)n * px);
-    const yh_detection* dd = st.upload<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
-    const int* dc = st.upload<int>(&n, sizeof(int));
+    const yh_detection* dd = st.upload_raw<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
+    const int* dc = st.upload_raw<int>(&n, sizeof(int));
     if (const int rc = st.status(h, "instance frame op: ")) {
         if (trk) track_drop(h);
         return rc;
@@ -686,9 +769,9 @@ static int op_instance_batch_impl(yh_engine* h, const uint8_t* masks, const int3
         for (int d = 0; d < counts[b]; ++d) { dets[o + d].class_id = class_ids[o + d]; dets[o + d].score = scores[o + d]; }
     }
     OpStaging st;
-    const uint8_t* dm = st.upload<uint8_t>(ms.data(), ms.size());
-    const yh_detection* dd = st.upload<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
-    const int* dc = st.upload<int>(counts, (size_t)n_frames * sizeof(int));
+    const uint8_t* dm = st.upload_raw<uint8_t>(ms.data(), ms.size());
+    const yh_detection* dd = st.upload_raw<yh_detection>(dets.data(), dets.size() * sizeof(yh_detection));
+    const int* dc = st.upload_raw<int>(counts, (size_t)n_frames * sizeof(int));
     if (const int rc = st.status(h, "instance batch op: ")) {
         if (trk) track_batch_drop(h, n_frames, *trk);
         return rc;

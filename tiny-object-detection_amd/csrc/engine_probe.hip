@@ -367,6 +367,75 @@ int yh_profile_run(yh_engine* h, int32_t with_tail, int32_t reps, float* ms, dou
     return YH_OK;
 }
 
+// ---- activation guards (Bounds): a step of n < max_batch frames must leave images n .. max_batch - 1 of every
+// activation allocation, and the 256 zero bytes behind each, as they were. Memsets and copies only: nothing is launched.
+static size_t next_changed(const uint8_t* b, size_t i, size_t end, uint8_t want) {   // the first index in [i, end) whose byte is not `want`, or end
+    const uint64_t pat = want ? ~0ull : 0ull;
+    for (uint64_t w; i + 8 <= end; i += 8) { memcpy(&w, b + i, 8); if (w != pat) break; }
+    while (i < end && b[i] == want) ++i;
+    return i;
+}
+
+static int act_guard_args(yh_engine* h, int32_t first_image) {
+    if (!h->weights_loaded) return h->fail(YH_ESTATE, "activation guards: load the weights first");
+    if (first_image < 1 || first_image >= h->cfg.max_batch) return h->fail(YH_EINVAL, "activation guards: first_image outside 1 .. max_batch - 1");
+    HIPCHK(h, hipSetDevice(h->dev));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->side));
+    return YH_OK;
+}
+
+int yh_debug_act_paint(yh_engine* h, int32_t first_image) {
+    if (!h) return YH_EINVAL;
+    if (const int rc = act_guard_args(h, first_image)) return rc;
+    for (const ActAlloc& a : h->act) {
+        const size_t from = (size_t)first_image * a.img * 2;
+        HIPCHK(h, hipMemsetAsync((char*)a.base + from, 0xFF, a.bytes - from, h->stream));
+        if (a.q) HIPCHK(h, hipMemsetAsync(a.q + from / 2, 0xFF, (a.bytes - from) / 2, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return YH_OK;
+}
+
+int yh_debug_act_check(yh_engine* h, int32_t first_image, char* out, size_t cap) {
+    if (!h) return YH_EINVAL;
+    if (out && cap) out[0] = 0;
+    if (const int rc = act_guard_args(h, first_image)) return rc;
+    std::vector<uint8_t> host;
+    std::string text;
+    int hits = 0;
+    // one region of one allocation: [from, data) must be 0xFF, [data, data + 256) zero; es = bytes per element
+    auto scan = [&](const std::string& name, const uint8_t* dev, size_t from, size_t data, const ActAlloc& a, size_t es) -> hipError_t {
+        host.resize(data + 256 - from);
+        const hipError_t e = hipMemcpy(host.data(), dev + from, host.size(), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        const size_t img = (size_t)a.img * es, row = (size_t)a.c * es;
+        for (int trailer = 0; trailer < 2; ++trailer) {
+            const size_t end = trailer ? host.size() : data - from;
+            const uint8_t want = trailer ? 0x00 : 0xFF;
+            for (size_t i = next_changed(host.data(), trailer ? data - from : 0, end, want); i < end && hits < 9; i = next_changed(host.data(), i + 1, end, want)) {
+                const size_t off = from + i;
+                char ln[256];
+                if (!trailer)
+                    snprintf(ln, sizeof ln, "%s: image %zu row %zu byte %zu is 0x%02X, painted 0xFF\n", name.c_str(), off / img, (off % img) / row, off % img, host[i]);
+                else
+                    snprintf(ln, sizeof ln, "%s: trailer byte %zu behind image %d is 0x%02X, not 0\n", name.c_str(), off - data, h->cfg.max_batch - 1, host[i]);
+                text += ln;
+                ++hits;
+            }
+        }
+        return hipSuccess;
+    };
+    for (const ActAlloc& a : h->act) {
+        if (hits >= 9) break;
+        HIPCHK(h, scan(a.name, (const uint8_t*)a.base, (size_t)first_image * a.img * 2, a.bytes, a, 2));
+        if (a.q && hits < 9) HIPCHK(h, scan(a.name + ".e4m3", a.q, (size_t)first_image * a.img, a.bytes / 2, a, 1));
+    }
+    if (!hits) return YH_OK;
+    if (out && cap) snprintf(out, cap, "%s", text.c_str());
+    return h->fail(YH_EOVERFLOW, "activation guards: a step stored outside its " + std::to_string(first_image) + " image(s): " + text.substr(0, text.find('\n')));
+}
+
 int yh_time_steps(yh_engine* h, int32_t with_tail, int32_t steps, float* ms_total) {
     if (!h || !ms_total || steps < 1) return YH_EINVAL;
     HIPCHK(h, hipSetDevice(h->dev));

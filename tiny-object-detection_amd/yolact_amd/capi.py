@@ -264,6 +264,9 @@ SYMBOLS = [
     ("yh_debug_set_cu_mask", _i, [_vp, _vp, _i]),
     ("yh_debug_run_phase", _i, [_vp, _i, _i, C.POINTER(_f)]),
     ("yh_debug_graph_nodes", _i, [_vp, _i, C.c_char_p, _sz]),
+    ("yh_debug_guard_selfcheck", _i, [_vp, _i]),
+    ("yh_debug_act_paint", _i, [_vp, _i]),
+    ("yh_debug_act_check", _i, [_vp, _i, C.c_char_p, _sz]),
     ("yh_op_stem_pool_f16", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("yh_op_stem_pool_rgb8", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("yh_op_quantize_e4m3", _i, [_vp, _vp, _sz, C.c_float, _vp]),
@@ -900,6 +903,25 @@ class Engine:
         buf = C.create_string_buffer(1 << 20)
         self._chk(self.L.yh_debug_graph_nodes(self.h, 1 if with_tail else 0, buf, len(buf)))
         return buf.value.decode()
+
+    def guard_selfcheck(self, where):
+        """The single-op entry points' guard check on a staged output with one guard byte changed (where 1 .. 4; 0: none): raises
+        YhError(EOVERFLOW) naming the output, the side and the byte; no kernel runs."""
+        self._chk(self.L.yh_debug_guard_selfcheck(self.h, where))
+
+    def act_paint(self, first_image):
+        """0xFF into images first_image .. max_batch - 1 of every activation allocation (and E4M3 twin)."""
+        self._chk(self.L.yh_debug_act_paint(self.h, first_image))
+
+    def act_check(self, first_image):
+        """The painted images are still 0xFF and every allocation's 256 trailing bytes zero, or YhError(EOVERFLOW) whose `offenders`
+        lists up to nine changed bytes, one line each."""
+        buf = C.create_string_buffer(1 << 14)
+        rc = self.L.yh_debug_act_check(self.h, first_image, buf, len(buf))
+        if rc != OK:
+            err = YhError(rc, self.L.yh_last_error(self.h).decode())
+            err.offenders = buf.value.decode().splitlines()
+            raise err
 
     def last_conv_launches(self):
         return self.L.yh_debug_last_conv_launches(self.h)
