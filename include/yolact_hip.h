@@ -537,10 +537,48 @@ int yh_tfl_read_detections(yh_tfl* h, int32_t image, int32_t* count, yh_detectio
                            uint8_t* masks, size_t masks_capacity);
 int yh_tfl_proto_dims(const yh_tfl* h, int32_t dims[2]);   /* {hp, wp} of the setup; YH_EINVAL before one */
 /* The setup's result buffers on the device (NULL before a setup; valid until the next setup or yh_tfl_destroy; written by the
- * tail's launches on the handle's stream): what an instance frame painted from these detections will read. */
+ * tail's launches on the handle's stream): what yh_tfl_instance_batch / yh_tfl_instance_frames read. */
 const yh_detection* yh_tfl_detections_device(const yh_tfl* h);   /* [max_images][max_dets] */
 const int32_t*      yh_tfl_detection_counts_device(const yh_tfl* h);
 const uint8_t*      yh_tfl_masks_device(const yh_tfl* h);        /* [max_images][max_dets][hp*wp] */
+
+/* ---- TFLite instance frames: the setup's detections painted for the scene (DESIGN.md section 11 "TFLite instance frames") ------
+ * What yh_instance_batch is to yh_evaluate: the detections of the last yh_tfl_evaluate / yh_tfl_detect, read on the device where the
+ * tail left them, rasterised into packed class << 24 | id << 16 frames of width x height that yh_scene_batch_stage_frames takes.
+ * yh_tfl_instance_batch paints images first_image .. first_image + n_images - 1, each exactly as yh_instance_batch paints a frame
+ * (eligibility class_map[class_id] != 0 and score >= min_score; id = the eligible detections of the same output class with smaller
+ * rank; the exact-integer bilinear mask resize, on iff S > 2 W H; the smallest rank wins a pixel); its table rows are int32 [4] =
+ * (rank, output class, id, pixels won).
+ * yh_tfl_instance_frames paints camera frames: after yh_tfl_classify_batch_u32 the tail's images are the two S x S tiles of each
+ * frame, and frame b is painted from images 2 (first_frame + b) (tile 0, the left half) and 2 (first_frame + b) + 1 (tile 1).
+ * The eligible detections of both tiles are ordered by score descending (float32), ties to tile 0 before tile 1 and then to the
+ * smaller rank - the stable merge of the two lists - which gives the frame rank q < 2 max_dets; the id counts the eligible
+ * detections of the same output class with smaller q, across the tiles; a detection of tile t has the stitched hp x 2wp mask that
+ * is its own on columns t wp .. (t + 1) wp - 1 and 0 elsewhere, resized by the same rule with input width 2wp; the smallest q wins
+ * a pixel. Its table rows are int32 [5] = (tile, rank within the tile, output class, id, pixels won) in frame order. An object
+ * across the seam is two instances, one per tile; a seam pixel whose horizontal weight is exactly one half (a whole column at odd
+ * width) belongs to neither tile and stays 0.
+ * class_map: uint8 [C - 1] of the setup's C with values 0 .. 3, NULL: foreground 0, 1, 2 -> 1, 2, 3. out_host: [n][height][width]
+ * or NULL. Both calls are synchronous (one class-map upload, one read-back, one wait, whatever n): on return another stream may
+ * read the frames. Both fill the handle's ONE batch - the later call replaces the earlier - with buffers of its own (allocated at
+ * the first call, grow only, freed by yh_tfl_destroy; the sets take images x hp x wp x 16 bytes); neither touches the detections,
+ * the classify batch's frames, the model's tensors or the invoke's captured graph.
+ * Checked before anything is touched: YH_ESTATE before a setup, or when no tail has run since the last yh_tfl_set_input or invoke
+ * (what yh_tfl_read_detections refuses); YH_EINVAL for n < 1, images or frames outside the last tail's (per frame:
+ * 2 (first_frame + n_frames) <= its images), a size outside 1 .. 4096, a class_map value above 3, a NaN min_score. A refused call
+ * leaves the previous batch, its pointer and its tables as they were; a call that fails later leaves no batch. */
+int yh_tfl_instance_batch(yh_tfl* h, int32_t first_image, int32_t n_images, int32_t width, int32_t height,
+                          const uint8_t* class_map, float min_score, uint32_t* out_host /* [n][H][W] or NULL */);
+int yh_tfl_instance_frames(yh_tfl* h, int32_t first_frame, int32_t n_frames, int32_t width, int32_t height,
+                           const uint8_t* class_map, float min_score, uint32_t* out_host /* [n][H][W] or NULL */);
+/* Device copy of the last batch's frames [n][H][W]; NULL before a batch or after a failed one; valid until the next instance call on
+ * the handle. It is what yh_scene_batch_stage_frames(.., frames_on_device = 1) takes. */
+const uint32_t* yh_tfl_instance_device_frames(const yh_tfl* h);
+/* The table of image / frame `index` of the last batch, with the conventions of yh_instance_batch_read (capacity in rows; table
+ * NULL: the row count only; YH_EOVERFLOW if it does not fit); a row has yh_tfl_instance_row_width ints: 4 after
+ * yh_tfl_instance_batch, 5 after yh_tfl_instance_frames. */
+int yh_tfl_instance_read(yh_tfl* h, int32_t index, int32_t* n_instances, int32_t* table, int32_t capacity);
+int yh_tfl_instance_row_width(const yh_tfl* h);
 
 /* ---- scene back-end: append_scene's two compute dispatches (src/scene.rs:147-331) --------------
  * shaders/pt_cloud.comp (depth + class image -> bird's-eye height map with sigmoid bumps, ball centroids) and
@@ -858,7 +896,7 @@ const char* yh_scene_batch_last_error(const yh_scene_batch* h);
  * outside 0 .. max_frames - 1. */
 int yh_scene_batch_stage(yh_scene_batch* h, int32_t slot, const uint16_t* depth_host, const uint32_t* frame, int32_t frame_on_device);
 /* yh_scene_batch_stage for slots first_slot .. first_slot + n_frames - 1 at once: depth u16 [n][h][w] from the host and the packed
- * frames u32 [n][h][w] from the host or (frames_on_device = 1) from a device pointer such as yh_instance_batch_device_frames or yh_classify_batch_device_frames. The slot
+ * frames u32 [n][h][w] from the host or (frames_on_device = 1) from a device pointer such as yh_instance_batch_device_frames, yh_classify_batch_device_frames or yh_tfl_instance_device_frames. The slot
  * buffers are contiguous, so this is one depth copy and one frame copy on the handle's stream, then the waits yh_scene_batch_stage
  * makes: on return the caller's buffers are free again. The slots are marked staged only on success. YH_EINVAL for n_frames < 1 or a
  * range outside 0 .. max_frames - 1. */

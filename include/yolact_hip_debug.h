@@ -502,6 +502,17 @@ int yh_tfl_op_detect(yh_tfl* h, int32_t n, int32_t P, int32_t C, int32_t hp, int
                      const void* mask, int32_t mask_kind, float mask_scale, int32_t mask_zp,
                      const void* proto, int32_t proto_kind, float proto_scale, int32_t proto_zp,
                      const float* priors, int32_t top_k, int32_t max_dets, float conf_thresh, float nms_thresh);
+/* yh_tfl_instance_frames' kernels on caller-provided detections, no model and no setup: what yh_op_instance_batch is to the engine.
+ * n_frames (1 .. 64) camera frames of two images each, image 2b the left tile of frame b: masks uint8 [2n][n_dets][hp][wp],
+ * class_ids and scores [2n][n_dets] in rank order per image, counts [2n], n_dets 0 .. 128. There is no setup to give C: a class id
+ * lies in 0 .. 79 and class_map, if not NULL, has 80 entries. The mask slots past an image's count are uploaded as 0xFF (a kernel
+ * that read them would paint them). YH_EINVAL as yh_tfl_instance_frames, and when the scores within an image's count are not
+ * non-increasing (the order the tail returns and the kernels may rely on). The frames are painted between two guard bands of 4096
+ * bytes of 0xFF, which are read back: YH_EOVERFLOW, naming the band and the byte, if one changed. The handle gives the device, the
+ * stream and the error text only; on success the batch is the handle's (yh_tfl_instance_read, yh_tfl_instance_device_frames). */
+int yh_tfl_op_instance_frames(yh_tfl* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                              int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height,
+                              const uint8_t* class_map, float min_score, uint32_t* out_host /* [n][H][W] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "classify_geo.h"
+#include "instance_host.h"
 #include "yh_internal.h"
 
 // (hidden: nothing declared here is exported from the shared library)
@@ -297,15 +298,12 @@ int alloc_panels(yh_engine* h);
 int check_blob(yh_engine* h, const uint8_t* b, size_t nbytes);
 int upload_panels(yh_engine* h, const uint8_t* blob);
 int ensure_blob(yh_engine* h);
-// instance.hip
-const char* instance_check(int width, int height, const uint8_t* class_map, int ncls, float min_score);   // nullptr: fine
+// instance.hip (instance_check, instance_class_map, instance_table and instance_grow_bytes need no handle: instance_host.h)
 struct InstTrack { int iou_permille, max_age; };   // a tracked call's parameters (instance_run: nullptr = yh_instance_frame's ids)
 int instance_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int hp, int wp,
                  int width, int height, const uint8_t* class_map, float min_score, uint32_t* out_host, const InstTrack* trk = nullptr);
 void instance_free(yh_engine* h);
-int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes);   // a device buffer that only grows (the old one is freed)
-void instance_class_map(const uint8_t* class_map, int ncls, std::vector<uint8_t>& out);   // the call's class map, NULL resolved
-void instance_table(const uint32_t* meta, std::vector<int32_t>& table);   // meta [2][128] as read back -> rows (rank, class, id, pixels)
+int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes);   // instance_grow_bytes, a failure as the handle's YH_ENOMEM
 // instance_batch.hip: n frames in one pair of launches; frame b reads masks + b max_n px, dets + b max_n, count + b
 struct InstTrackBatch { InstTrack p; const int32_t* streams; };   // a tracked batch: streams [n] or nullptr (all 0); checked by the caller
 int instance_batch_run(yh_engine* h, const uint8_t* masks, const yh_detection* dets, const int* count, int max_n, int n, int hp, int wp,

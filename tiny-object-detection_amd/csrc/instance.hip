@@ -34,13 +34,17 @@ __global__ void __launch_bounds__(kPaintX * kPaintY) inst_paint(const uint4* __r
 
 namespace yh {
 
-int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return YH_OK;
+bool instance_grow_bytes(void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return true;
     if (*p) hipFree(*p);
     *p = nullptr; *cap = 0;
-    if (hipMalloc(p, bytes) != hipSuccess) return h->fail(YH_ENOMEM, "hipMalloc instance frame");
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
     *cap = bytes;
-    return YH_OK;
+    return true;
+}
+
+int instance_grow(yh_engine* h, void** p, size_t* cap, size_t bytes) {
+    return instance_grow_bytes(p, cap, bytes) ? YH_OK : h->fail(YH_ENOMEM, "hipMalloc instance frame");
 }
 
 void instance_table(const uint32_t* meta, std::vector<int32_t>& table) {

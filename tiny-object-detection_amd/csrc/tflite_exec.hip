@@ -24,7 +24,9 @@
 #include <vector>
 
 #include "classify_geo.h"
+#include "instance_host.h"
 #include "tfl_detect.h"
+#include "tfl_instance.h"
 #include "tflite_exec.h"
 #include "tflite_model.h"
 #include "yh_internal.h"
@@ -125,6 +127,9 @@ struct yh_tfl {
     const DetSet* det_last = nullptr; // what yh_tfl_read_detections shows; nullptr: nothing current (no tail yet, or a newer input / invoke)
     int det_last_n = 0;               // its images
     int last_nb = 0;                  // images of the last invoke; 0: none yet
+    // instance frames painted from the setup's detections (tfl_instance.hip; DESIGN.md section 11 "TFLite instance frames"): one
+    // batch, filled by yh_tfl_instance_batch, yh_tfl_instance_frames or yh_tfl_op_instance_frames, whichever ran last
+    yh::TflInstance inst;
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
 
@@ -1011,6 +1016,7 @@ void yh_tfl_destroy(yh_tfl* h) {
     classify_geo_free(&h->clsb_geo);
     for (void* p : h->det.bufs) hipFree(p);
     for (void* p : h->opdet.bufs) hipFree(p);
+    tfl_instance_free(h->inst);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1402,6 +1408,101 @@ int yh_tfl_op_detect(yh_tfl* h, int32_t n, int32_t P, int32_t C, int32_t hp, int
     h->det_last = &d;
     h->det_last_n = n;
     return YH_OK;
+}
+
+// ---- instance frames from the setup's detections (tfl_instance.hip; DESIGN.md section 11 "TFLite instance frames") ----
+// Both calls: every check, then the one run on the setup's buffers where the tail left them. per_frame: `first` and `n` count
+// camera frames of two images each.
+static int tfl_instance_call(yh_tfl* h, bool per_frame, int32_t first, int32_t n, int32_t width, int32_t height, const uint8_t* class_map,
+                             float min_score, uint32_t* out_host) {
+    if (!h) return YH_EINVAL;
+    const char* what = per_frame ? "instance frames" : "instance batch";
+    if (!h->det.ready) return h->fail(YH_ESTATE, std::string(what) + " before yh_tfl_detect_setup");
+    if (h->det_last != &h->det)
+        return h->fail(YH_ESTATE, std::string(what) + ": no detections: yh_tfl_evaluate / yh_tfl_detect has not run since the last yh_tfl_set_input or invoke");
+    if (n < 1) return h->fail(YH_EINVAL, std::string(what) + (per_frame ? ": n_frames must be at least 1" : ": n_images must be at least 1"));
+    const int have = per_frame ? h->det_last_n / 2 : h->det_last_n;
+    if (first < 0 || first >= have || n > have - first)
+        return h->fail(YH_EINVAL, std::string(what) + (per_frame ? ": frames outside the last tail's images (frame b is images 2b and 2b + 1)"
+                                                                 : ": images outside the last tail's"));
+    const TflDetectParams& q = h->det.p;
+    if (const char* why = instance_check(width, height, class_map, q.C - 1, min_score)) return h->fail(YH_EINVAL, why);
+    TCHK(h, hipSetDevice(h->dev));
+    TraceRange tr(per_frame ? "yh_tfl_instance_frames" : "yh_tfl_instance_batch");
+    const size_t img = (size_t)first * (per_frame ? 2 : 1), px = (size_t)q.hp * q.wp;
+    const TflInstSource src = { q.masks + img * q.max_dets * px, q.dets + img * q.max_dets, q.det_count + img, q.max_dets, q.hp, q.wp, q.C - 1 };
+    return tfl_instance_run(h->inst, h->stream, &h->err, src, n, per_frame, width, height, class_map, min_score, out_host, false);
+}
+
+int yh_tfl_instance_batch(yh_tfl* h, int32_t first_image, int32_t n_images, int32_t width, int32_t height, const uint8_t* class_map,
+                          float min_score, uint32_t* out_host) {
+    return tfl_instance_call(h, false, first_image, n_images, width, height, class_map, min_score, out_host);
+}
+
+int yh_tfl_instance_frames(yh_tfl* h, int32_t first_frame, int32_t n_frames, int32_t width, int32_t height, const uint8_t* class_map,
+                           float min_score, uint32_t* out_host) {
+    return tfl_instance_call(h, true, first_frame, n_frames, width, height, class_map, min_score, out_host);
+}
+
+const uint32_t* yh_tfl_instance_device_frames(const yh_tfl* h) { return h ? tfl_instance_frames(h->inst) : nullptr; }
+
+int yh_tfl_instance_row_width(const yh_tfl* h) { return h ? h->inst.row_width : YH_EINVAL; }
+
+int yh_tfl_instance_read(yh_tfl* h, int32_t index, int32_t* n_instances, int32_t* table, int32_t capacity) {
+    if (!h || !n_instances) return YH_EINVAL;
+    if (h->inst.n < 1) return h->fail(YH_ESTATE, "instance table: no instance batch yet");
+    if (index < 0 || index >= h->inst.n) return h->fail(YH_EINVAL, "instance table: index outside the last batch");
+    const std::vector<int32_t>& t = h->inst.tables[(size_t)index];
+    *n_instances = (int32_t)(t.size() / (size_t)h->inst.row_width);
+    if (!table) return YH_OK;
+    if (capacity < *n_instances) return h->fail(YH_EOVERFLOW, "instance table: capacity too small");
+    memcpy(table, t.data(), t.size() * sizeof(int32_t));
+    return YH_OK;
+}
+
+// The per-frame kernels on caller-provided detections, no model and no setup (include/yolact_hip_debug.h): the handle gives the
+// device, the stream and the error text. The mask slots past an image's count are uploaded as 0xFF - a kernel that read them would
+// paint them - and the frames are painted between two guard bands of 0xFF that are read back and checked (tfl_instance_run).
+int yh_tfl_op_instance_frames(yh_tfl* h, const uint8_t* masks, const int32_t* class_ids, const float* scores, const int32_t* counts,
+                              int32_t n_frames, int32_t n_dets, int32_t hp, int32_t wp, int32_t width, int32_t height,
+                              const uint8_t* class_map, float min_score, uint32_t* out_host) {
+    if (!h || !counts || (n_dets > 0 && (!masks || !class_ids || !scores))) return YH_EINVAL;
+    if (n_frames < 1 || n_frames > 64) return h->fail(YH_EINVAL, "instance frames op: n_frames outside 1 .. 64");
+    if (n_dets < 0 || n_dets > kTdDetsMax) return h->fail(YH_EINVAL, "instance frames op: n_dets outside 0 .. 128");
+    if (hp < 1 || hp > 4096 || wp < 1 || wp > 4096) return h->fail(YH_EINVAL, "instance frames op: hp and wp must be in 1 .. 4096");
+    const int images = 2 * n_frames;
+    for (int b = 0; b < images; ++b) {
+        if (counts[b] < 0 || counts[b] > n_dets) return h->fail(YH_EINVAL, "instance frames op: a count outside 0 .. n_dets");
+        for (int d = 0; d < counts[b]; ++d) {
+            const size_t i = (size_t)b * n_dets + d;
+            if (class_ids[i] < 0 || class_ids[i] >= kTflOpClasses) return h->fail(YH_EINVAL, "instance frames op: class id outside 0 .. 79");
+            if (d > 0 && !(scores[i] <= scores[i - 1]))
+                return h->fail(YH_EINVAL, "instance frames op: an image's scores are not non-increasing (the order the tail returns)");
+        }
+    }
+    if (const char* why = instance_check(width, height, class_map, kTflOpClasses, min_score)) return h->fail(YH_EINVAL, why);
+    TCHK(h, hipSetDevice(h->dev));
+    const size_t px = (size_t)hp * wp, slots = (size_t)images * n_dets;
+    std::vector<yh_detection> dets(slots + 1);
+    memset(dets.data(), 0, dets.size() * sizeof(yh_detection));
+    std::vector<uint8_t> ms(slots * px + 16, 0xFF);
+    for (int b = 0; b < images; ++b) {
+        const size_t o = (size_t)b * n_dets;
+        if (counts[b] > 0) memcpy(&ms[o * px], &masks[o * px], (size_t)counts[b] * px);
+        for (int d = 0; d < counts[b]; ++d) { dets[o + d].class_id = class_ids[o + d]; dets[o + d].score = scores[o + d]; }
+    }
+    TflInstance& st = h->inst;
+    TCHK(h, hipStreamSynchronize(h->stream));   // (the buffers below may move: nothing of an earlier call is in flight)
+    st.n = -1;
+    if (!instance_grow_bytes(&st.op_masks, &st.op_masks_cap, ms.size()) ||
+        !instance_grow_bytes(&st.op_dets, &st.op_dets_cap, dets.size() * sizeof(yh_detection)) ||
+        !instance_grow_bytes(&st.op_counts, &st.op_counts_cap, (size_t)images * sizeof(int)))
+        return h->fail(YH_ENOMEM, "hipMalloc instance frames op");
+    TCHK(h, hipMemcpy(st.op_masks, ms.data(), ms.size(), hipMemcpyHostToDevice));
+    TCHK(h, hipMemcpy(st.op_dets, dets.data(), dets.size() * sizeof(yh_detection), hipMemcpyHostToDevice));
+    TCHK(h, hipMemcpy(st.op_counts, counts, (size_t)images * sizeof(int), hipMemcpyHostToDevice));
+    const TflInstSource src = { (const uint8_t*)st.op_masks, (const yh_detection*)st.op_dets, (const int*)st.op_counts, n_dets, hp, wp, kTflOpClasses };
+    return tfl_instance_run(st, h->stream, &h->err, src, n_frames, true, width, height, class_map, min_score, out_host, true);
 }
 
 }  // extern "C"

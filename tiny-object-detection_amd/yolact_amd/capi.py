@@ -300,6 +300,12 @@ SYMBOLS = [
     ("yh_tfl_masks_device", _vp, [_vp]),
     ("yh_tfl_detect_stage_times", _i, [_vp, _i, C.POINTER(_f * 4)]),
     ("yh_tfl_op_detect", _i, [_vp, _i, _i, _i, _i, _i] + [_vp, _i, _f, _i] * 4 + [_vp, _i, _i, _f, _f]),
+    ("yh_tfl_instance_batch", _i, [_vp, _i, _i, _i, _i, _vp, _f, _vp]),
+    ("yh_tfl_instance_frames", _i, [_vp, _i, _i, _i, _i, _vp, _f, _vp]),
+    ("yh_tfl_instance_device_frames", _vp, [_vp]),
+    ("yh_tfl_instance_read", _i, [_vp, _i, C.POINTER(_i), _vp, _i]),
+    ("yh_tfl_instance_row_width", _i, [_vp]),
+    ("yh_tfl_op_instance_frames", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp]),
 ]
 
 
@@ -2493,3 +2499,70 @@ class TfliteEngine:
         self._det_geo = None
         self._chk(self.L.yh_tfl_op_detect(self.h, n, P, Cc, hp, wp, *args, _p(pr), top_k, max_dets, conf_thresh, nms_thresh))
         self._det_geo = (max_dets, hp, wp)
+
+    # ---- instance frames from the setup's detections (DESIGN.md §11 "TFLite instance frames")
+    def _inst_class_map(self, class_map, ncls=None):
+        if class_map is None:
+            return None
+        cm = np.ascontiguousarray(class_map, np.uint8)
+        if ncls is None:   # the setup's C - 1, from the conf output bound by detect_setup
+            assert getattr(self, "_det_cfg", None) is not None, "class_map needs detect_setup"
+            ncls = self.output_info(self._det_cfg.outputs[1])["dims"][-1] - 1
+        assert cm.shape == (ncls,), "class_map: one value per foreground class"
+        return cm
+
+    def instance_batch(self, first, n, width, height, class_map=None, min_score=0.0, read=True):
+        """yh_tfl_instance_batch: images first .. first + n - 1 of the last evaluate / detect, each painted as Engine.instance_batch
+        paints a frame. Returns uint32 [n][height][width], or None with read=False (the frames stay on the device:
+        instance_device_frames; the tables, rows of 4: instances_of)."""
+        cm = self._inst_class_map(class_map)
+        out = np.zeros((max(n, 0), height, width), np.uint32) if read else None
+        self._chk(self.L.yh_tfl_instance_batch(self.h, first, n, width, height, _p(cm) if cm is not None else None, C.c_float(min_score),
+                                               _p(out) if read else None))
+        return out
+
+    def instance_frames(self, first, n, width, height, class_map=None, min_score=0.0, read=True):
+        """yh_tfl_instance_frames: camera frames first .. first + n - 1, frame b painted from images 2b (the left tile) and 2b + 1
+        of the last tail - what detect() after classify_batch leaves. Returns uint32 [n][height][width], or None with read=False
+        (instance_device_frames; the tables, rows of 5 = (tile, rank, class, id, pixels): instances_of)."""
+        cm = self._inst_class_map(class_map)
+        out = np.zeros((max(n, 0), height, width), np.uint32) if read else None
+        self._chk(self.L.yh_tfl_instance_frames(self.h, first, n, width, height, _p(cm) if cm is not None else None, C.c_float(min_score),
+                                                _p(out) if read else None))
+        return out
+
+    def instance_device_frames(self):
+        """Device pointer of the last instance batch's frames [n][height][width] (None before a batch or after a failed one): what
+        SceneBatch.stage_frames(frames_dev_ptr=...) takes."""
+        return self.L.yh_tfl_instance_device_frames(self.h)
+
+    def instances_of(self, i):
+        """The instance table of image / frame i of the last batch: int32 [m][4] = (rank, output class, id, pixels won) after
+        instance_batch, int32 [m][5] = (tile, rank within the tile, output class, id, pixels won) after instance_frames."""
+        n = C.c_int32()
+        self._chk(self.L.yh_tfl_instance_read(self.h, i, C.byref(n), None, 0))
+        w = self.L.yh_tfl_instance_row_width(self.h)
+        t = np.zeros((n.value, w), np.int32)
+        self._chk(self.L.yh_tfl_instance_read(self.h, i, C.byref(n), _p(t), n.value))
+        return t
+
+    def op_instance_frames(self, masks, class_ids, scores, counts, width, height, class_map=None, min_score=0.0):
+        """yh_tfl_op_instance_frames: instance_frames' kernels on caller-provided masks uint8 [2n][n_dets][hp][wp], class ids and
+        scores [2n][n_dets] in rank order per image, counts [2n]; image 2b is the left tile of frame b. class_map: up to 80 values
+        (the rest 0). Returns (frames uint32 [n][height][width], the list of the frames' tables)."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        ni, nd, hp, wp = masks.shape
+        assert ni % 2 == 0, "two images per camera frame"
+        ids = np.ascontiguousarray(class_ids, np.int32).reshape(ni, nd)
+        sc = np.ascontiguousarray(scores, np.float32).reshape(ni, nd)
+        cnt = np.ascontiguousarray(counts, np.int32).reshape(ni)
+        cm = None
+        if class_map is not None:
+            given = np.ascontiguousarray(class_map, np.uint8).reshape(-1)
+            assert given.size <= 80, "class_map: at most 80 foreground classes"
+            cm = np.zeros(80, np.uint8)
+            cm[:given.size] = given
+        out = np.zeros((ni // 2, height, width), np.uint32)
+        self._chk(self.L.yh_tfl_op_instance_frames(self.h, _p(masks), _p(ids), _p(sc), _p(cnt), ni // 2, nd, hp, wp, width, height,
+                                                   _p(cm) if cm is not None else None, C.c_float(min_score), _p(out)))
+        return out, [self.instances_of(b) for b in range(ni // 2)]

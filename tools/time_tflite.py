@@ -17,6 +17,7 @@ ap.add_argument("--invokes", type=int, default=220)
 ap.add_argument("--batch", action="store_true", help="the classify batch (yh_tfl_classify_batch_u32): ms per 640x480 frame for n = 1 .. 32 frames, three paths alternated in one process (profiles/tfl_classify_batch_timings.txt)")
 ap.add_argument("--int8", action="store_true", help="the int8 / per-channel twin of the stand-in (tests/tfl_models_q.py) beside the uint8 stand-in, interleaved in one process: the invoke at 1, 2 and 16 images, or with --batch the classify batch at n = 4, 8, 32 (profiles/tfl_int8_timings.txt)")
 ap.add_argument("--detect", action="store_true", help="the detection tail on the model's own heads (yh_tfl_evaluate): ms per image of invoke alone and of evaluate at 2, 16 and 64 images, uint8 heads beside float32 heads (DEQUANTIZE behind the four), interleaved in one process, and the tail's four launches timed by events (profiles/tfl_detect_timings.txt)")
+ap.add_argument("--instance", action="store_true", help="the instance frames painted from the model's detections (yh_tfl_instance_frames): after a classify batch of n 640x480 frames and detect, ms per camera frame at n = 1, 4, 8, 32, left on the device and copied to the host, beside the engine's instance_batch at the same n (profiles/tfl_instance_timings.txt)")
 a = ap.parse_args()
 rng = np.random.default_rng(0)
 model = M.mobilenetv2_yolact(rng)
@@ -140,6 +141,48 @@ def detect_arm():
     for e in engs.values(): e.close()
 
 
+def instance_arm():
+    """One handle on the stand-in (max_images = 64) with a detect setup: per n a classify batch of n frames and the tail on its 2n
+    tiles, then instance_frames(0, n) on those detections - the frames left on the device, and copied to a host array that exists
+    already - alternated round by round. For context the engine's instance_batch(0, n, read=False) on YOLACT-550's detections of n
+    noise frames, in the same rounds: another network's detections, the same painter per image."""
+    import ctypes as C
+    W, H, rounds, S = 640, 480, 15, 224
+    eng = ya.TfliteEngine(buf, max_images=64)
+    eng.detect_setup(ya.tfl_priors([28, 14, 7, 3, 1], S))
+    yeng = ya.Engine(input_size=550, backbone=50, max_batch=32, use_graph=False)
+    yeng.load_weights(yeng.generate_weights(seed=1))
+    yeng.set_input(np.random.default_rng(5).integers(0, 256, (32, 550, 550, 3), dtype=np.uint8))
+    yeng.evaluate()
+    ynd = [len(yeng.detections(b, want_masks=False)[0]) for b in range(32)]
+    frames = rng.integers(0, 2 ** 32, (32, H, W), dtype=np.uint64).astype(np.uint32)
+    out = np.empty_like(frames)
+    cm = (1 + np.arange(80) % 3).astype(np.uint8)   # every foreground class painted
+    cmp, outp = cm.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+    print(f"tflite instance frames, {len(model.ops)}-op stand-in (S = {S}, proto {eng.proto_dims()}, max_dets 100), frames {W}x{H}, every class painted, min_score 0; "
+          f"random weights, so the detections are those of noise")
+    print(f"ms per camera FRAME, median of {rounds} alternated rounds (min .. max), 3 warm-ups; engine = yh_instance_batch on YOLACT-550's detections ({min(ynd)} .. {max(ynd)} per frame), frames left on the device")
+    print(f"{'n':>3} {'dets per tile':>14} {'instance_frames, device':>28} {'instance_frames, host copy':>28} {'engine instance_batch':>28}")
+    for n in (1, 4, 8, 32):
+        eng.classify_batch(frames_u32=frames[:n], n=n, width=W, height=H, mode=ya.COMPAT_SANE, read=False)
+        eng.detect()
+        nd = [len(eng.detections(i, want_masks=False)[0]) for i in range(2 * n)]
+        def device(): eng._chk(eng.L.yh_tfl_instance_frames(eng.h, 0, n, W, H, cmp, C.c_float(0.0), None))
+        def host(): eng._chk(eng.L.yh_tfl_instance_frames(eng.h, 0, n, W, H, cmp, C.c_float(0.0), outp))
+        def engine(): yeng.instance_batch(0, n, W, H, class_map=cm, read=False)
+        for _ in range(3):
+            device(); host(); engine()
+        assert out[:n].any() and sum(len(eng.instances_of(b)) for b in range(n)) > 0
+        t = np.array([[clock(device), clock(host), clock(engine)] for _ in range(rounds)]) / n
+        med, lo, hi = np.median(t, 0), t.min(0), t.max(0)
+        cols = [f"{med[k]:8.4f} ({lo[k]:7.4f} .. {hi[k]:7.4f})" for k in range(3)]
+        print(f"{n:3d} {f'{min(nd)} .. {max(nd)}':>14} {cols[0]:>28} {cols[1]:>28} {cols[2]:>28}")
+    yeng.close(); eng.close()
+
+
+if a.instance:
+    instance_arm()
+    sys.exit(0)
 if a.detect:
     detect_arm()
     sys.exit(0)
